@@ -17,7 +17,7 @@ distinct primes per polynomial (configs[2] shape).
 
 Multi-GPU: residue polynomials are independent, so every rank transforms its own batch
 (weak scaling, no collective on the data path, `value` = all ranks' NTTs / max time).  The
-path's one exchange -- the base-conversion join of key switching -- is measured by the
+path's one exchange -- the base-conversion join of key switching -- is measured (with --full) by the
 strong-scaling legs `also.strong_scaling_config5` (BASELINE configs[4]: a rotation at
 N = 2^16, L = 44) and `also.strong_scaling_config4` (configs[3]: hmult at N = 2^17, L = 32), limbs
 sharded over the ranks, two RCCL all-gathers per key switch and one broadcast per rescale,
@@ -26,10 +26,15 @@ compute and joins timed separately.
 Timing: an untimed device pre-warm of --prewarm-s seconds of the same step (a freshly leased GPU sits at idle clocks; with the
 driver's --steps 20 the whole timed region would otherwise lie on the clock ramp: 0.31 instead of 0.37), then W untimed warm-up
 steps, then exactly K timed steps between barrier + synchronize on both sides; `config.prewarm_steps_untimed` reports the count.
+The batch is drawn again from its seed after the pre-warm, so the W + K steps always start from the same input.
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline`
-(algorithmic bytes 16*N per limb-NTT / HIP-event time vs 8 TB/s) and `cpu_baseline`
-(the oracle's C port on one core and on all host cores, and the pure-Python form).
+(algorithmic bytes 16*N per limb-NTT / HIP-event time vs 8 TB/s).  A plain run does only that; --full adds what takes runs
+of its own: `roofline.per_launch` and the one-call figures, `also` (other shapes, the composites, the strong-scaling legs)
+and `cpu_baseline` (the oracle's C port on one core and on all host cores, and the pure-Python form).
+
+--dump-outputs DIR: after the timed steps, DIR/forward_ntt.npy (float64, a fixed seeded sample of whole polynomials of the
+transformed batch, <= 32 MiB; `_hi` / `_lo` 32-bit halves when a prime exceeds 2^53; `_rank<r>` per rank when N > 1).
 """
 import argparse
 import json
@@ -153,10 +158,14 @@ def main():
     ap.add_argument("--polys", type=int, default=1024, help="residue polynomials per limb in the batch (1024 = 512 MiB: HBM streaming)")
     ap.add_argument("--limbs", type=int, default=1, help="distinct RNS primes per polynomial")
     ap.add_argument("--bits", type=int, default=50, help="prime size (50 = reference; 61 = integer path)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: per-launch timing, the secondary and strong-scaling legs, the CPU baselines")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR",
+                    help="write a fixed seeded sample of what the last timed step computed to DIR/*.npy (float64)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
     ap.add_argument("--check", action="store_true", help="verify one limb against the oracle before timing")
     ap.add_argument("--mode", choices=["fused", "twopass"], default="twopass")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary measurements (other batch shapes, composites)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary measurements (other batch shapes, composites)")
     ap.add_argument("--chunk-mib", type=int, default=96, help="sub-batch size of each library call (0 = whole slab per launch pair)")
     ap.add_argument("--streams", type=int, default=2,
                     help="HIP streams the batch's polynomials are sharded over inside one GPU (each step = one call per stream)")
@@ -177,7 +186,8 @@ def main():
     if os.environ.get("FHE_BENCH_DRYRUN"):
         # launcher rehearsal (tests/test_bench_launcher.py, no GPU): every rank reports in, rank 0 prints the line's skeleton
         if rank == 0:
-            print(json.dumps({"metric": "dry run of the launcher", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "dryrun": True}), flush=True)
+            print(json.dumps({"metric": "dry run of the launcher", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "dryrun": True,
+                              "full": args.full, "dump_outputs": args.dump_outputs}), flush=True)
         sys.exit(int(os.environ.get("FHE_BENCH_DRYRUN_RC", "0")) if rank == world - 1 else 0)
 
     import torch
@@ -216,10 +226,15 @@ def main():
 
     # synthetic residue polynomials: uniform in [0, q_l), seeded per rank, resident in HBM
     g = torch.Generator(device="cuda")
-    g.manual_seed(2025 + rank)
     data = torch.empty((args.polys, args.limbs, N), dtype=torch.int64, device="cuda")
-    for l, q in enumerate(qs):
-        data[:, l, :] = torch.randint(0, q, (args.polys, N), generator=g, device="cuda", dtype=torch.int64)
+
+    def fill():
+        torch.cuda.synchronize()
+        g.manual_seed(2025 + rank)
+        for l, q in enumerate(qs):
+            data[:, l, :] = torch.randint(0, q, (args.polys, N), generator=g, device="cuda", dtype=torch.int64)
+        torch.cuda.synchronize()
+    fill()
     first_limb = data[0, 0].clone()
     torch.cuda.synchronize()
     # a non-default torch stream: its handle is non-null, so the library launches on it and
@@ -273,6 +288,7 @@ def main():
             step_sharded()
         torch.cuda.synchronize()
         prewarm_steps += 20
+    fill()          # the pre-warm ran for a wall time, not a step count: every run times the same W + K steps of the same input
     for _ in range(args.warmup):
         step_sharded()
     barrier()
@@ -291,6 +307,26 @@ def main():
         tmax = torch.tensor([wall], device="cuda", dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         wall = float(tmax.item())
+
+    if args.dump_outputs:
+        # what the caller of the timed path holds after its last step: the transformed batch (in place), as a fixed seeded
+        # sample of whole polynomials, before anything below transforms `data` again.  Residues below 2^53 are exact in
+        # float64; above, the two 32-bit halves are written.
+        wide = max(qs) >= 1 << 53
+        budget = (4 << 20) // world // (2 if wide else 1)           # float64 words: 32 MiB over all ranks
+        nl = min(args.limbs, max(1, budget // N))
+        npl = min(args.polys, max(1, budget // (nl * N)))
+        pick = np.random.default_rng(20250)
+        pi = torch.as_tensor(np.sort(pick.choice(args.polys, npl, replace=False)), device="cuda")
+        li = torch.as_tensor(np.sort(pick.choice(args.limbs, nl, replace=False)), device="cuda")
+        out = data.index_select(0, pi).index_select(1, li).cpu().numpy().view(np.uint64)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        tag = f"_rank{rank}" if world > 1 else ""
+        if wide:
+            np.save(os.path.join(args.dump_outputs, f"forward_ntt_hi{tag}.npy"), (out >> np.uint64(32)).astype(np.float64))
+            np.save(os.path.join(args.dump_outputs, f"forward_ntt_lo{tag}.npy"), (out & np.uint64(0xFFFFFFFF)).astype(np.float64))
+        else:
+            np.save(os.path.join(args.dump_outputs, f"forward_ntt{tag}.npy"), out.astype(np.float64))
 
     ntts = units * args.steps * world
     value = ntts / wall
@@ -351,8 +387,8 @@ def main():
     # each kernel of the step timed on its own, inside real transforms on ONE stream (column pass, event, row pass, event, ...:
     # the sequence the transform runs; each launch moves the batch once in and once out, 16*N bytes per limb-polynomial per
     # LAUNCH; the transform needs both).  Always 200 transforms, whatever --steps is; the rocprofv3 kernel trace of this command
-    # (profiles/) must agree with these averages.
-    if args.mode == "twopass" and rank == 0:
+    # (profiles/) must agree with these averages.  --full only: runs of their own, beside the headline.
+    if args.full and args.mode == "twopass" and rank == 0:
         eng.set_option("ntt_stream", 1)        # the kernels the headline's sub-batches run: non-temporal accesses on the external side
         marks = []
         for i in range(220):
@@ -402,7 +438,7 @@ def main():
             result["roofline"]["traffic"] = tr[key]["bytes_per_step"]
             result["roofline"]["traffic_note"] = tr[key]["note"]
 
-    extras = not args.no_extras
+    extras = args.full and not args.no_extras
     also = {}
     # everything below is one library call per step with the library's defaults (96 MiB sub-batches, side stream)
     eng.set_option("ntt_chunk_mib", 96)
@@ -899,8 +935,8 @@ def main():
     if rank == 0 and also:
         result["also"] = also
 
-    # ------------------------------------------------------------------ CPU baselines (rank 0, one GPU)
-    if rank == 0 and world == 1 and not args.no_cpu:
+    # ------------------------------------------------------------------ CPU baselines (rank 0, one GPU, --full)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         from oracle import cport as O
         from oracle import pyport as PY
         cores = host_cores()

@@ -6,8 +6,8 @@ cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/r03
 mkdir -p $OUT
 sum() { python3 profiles/rocpd_summary.py $(find $1 -name "*.db" | head -1) ${2:-0}; }
-DRIVER="python3 bench.py --gpus 1 --steps 20 --warmup 5"
-# 1. the driver's exact command: the JSON line, then its kernel trace (headline loop rows: 3072- / 2048-workgroup sub-batch launches)
+DRIVER="python3 bench.py --gpus 1 --steps 20 --warmup 5 --full"
+# 1. the driver's command with --full (every leg): the JSON line, then its kernel trace (headline loop rows: 3072- / 2048-workgroup sub-batch launches)
 $DRIVER > $OUT/r03_bench.json 2> $OUT/r03_bench.err
 rocprofv3 --kernel-trace --stats -d $OUT/kt -o r -- $DRIVER --no-cpu > /dev/null 2>&1
 sum $OUT/kt 100000 > $OUT/r03_bench_kt.txt

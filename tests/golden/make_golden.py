@@ -183,6 +183,25 @@ def main():
                        "small": {"M": [[int(x) for x in b] for b in Ms], "v": [int(x) for x in vs],
                                  "y": [int(x) for x in ys]}})
 
+    dump_crt()
+
+
+def dump_crt():
+    """a8: crt_reconstruct of rfhe_framewk/src/baseConv.cpp:146-173 as compiled into oracle/_ref by
+    ``make -C oracle ref`` -- the inputs of tests/test_oracle_golden.py::test_crt_garner_roundtrip_and_reference_build
+    (random.Random(11), 4 limbs x 20 bits, N = 64) and the reference's outputs, so the test needs no reference build."""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(OUT)))
+    from oracle import cport
+    rng = random.Random(11)
+    mod = [1048583, 1048589, 1048601, 1048609]
+    N = 64
+    res = [[rng.randrange(p) for _ in range(N)] for p in mod]
+    ref = cport.ref_crt_reconstruct(res, mod)
+    if ref is None:
+        raise SystemExit("oracle/_ref/libref_baseconv.so is missing: run make -C oracle ref first")
+    dump("crt_reconstruct.json", {"mod": mod, "seed": 11, "N": N, "res": res,
+                                  "lo": [int(x) for x in ref[0]], "hi": [int(x) for x in ref[1]]})
+
 
 if __name__ == "__main__":
     main()

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -37,6 +38,30 @@ def test_plain_start_with_two_gpus_launches_two_ranks_and_relays_their_line():
     assert len(lines) == 1
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["steps"] == 3 and out["warmup"] == 1 and out["dryrun"] is True
+    assert out["full"] is False and out["dump_outputs"] is None
+
+
+def test_full_and_dump_outputs_reach_the_ranks(tmp_path):
+    r = run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--dump-outputs", str(tmp_path)], {"FHE_BENCH_DRYRUN": "1"})
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads([l for l in r.stdout.splitlines() if l.lstrip().startswith("{")][-1])
+    assert out["full"] is True and out["dump_outputs"] == str(tmp_path)
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_the_same_outputs_whatever_the_prewarm(tmp_path):
+    # a small plain run twice: the pre-warm runs for a wall time, yet the dumped outputs of the K timed steps must be identical
+    outs = []
+    for i, pre in enumerate(("0", "0.3")):
+        d = tmp_path / f"run{i}"
+        r = run(["--gpus", "1", "--steps", "4", "--warmup", "2", "--polys", "96", "--prewarm-s", pre, "--dump-outputs", str(d)], {}, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.lstrip().startswith("{")][-1])
+        assert line["steps"] == 4 and line["ms_per_step"] > 0 and "also" not in line and "cpu_baseline" not in line
+        outs.append(np.load(d / "forward_ntt.npy"))
+    assert outs[0].dtype == np.float64 and outs[0].shape == (64, 1, 1 << 16)
+    assert (outs[0] == outs[1]).all()
+    assert outs[0].max() < 2 ** 50 and outs[0].min() >= 0 and (outs[0] == np.floor(outs[0])).all()
 
 
 def test_a_failing_rank_fails_the_launcher():
