@@ -1106,6 +1106,69 @@ hipError_t launch_weighted_checksum(hipStream_t st, u64 *out, const u64 *x, cons
     return hipGetLastError();
 }
 
+// the same with a second factor per word: out[unit] = scal * sum_i w_i x_i y_i (input side of the unfused product's check, w = w^ unscaled)
+__global__ __launch_bounds__(256) void k_weighted_checksum3(u64 *out, const u64 *x, const u64 *y, const u64 *w, const u64 *scal,
+                                                            const LimbParams *lp, u32 limb0, u32 limbs, u32 poly_stride, int logn)
+{
+    __shared__ u64 part[256];
+    const u32 unit = blockIdx.x, poly = unit / limbs, l = unit % limbs;
+    const LimbParams &p = lp[limb0 + l];
+    const u64 q = p.q, r0 = p.barrett_lo, r1 = p.barrett_hi;
+    const u64 uoff = ((u64)poly * poly_stride + l) << logn;
+    const u64 *xs = x + uoff, *ys = y + uoff, *ws = w + ((u64)(limb0 + l) << logn);
+    u64 acc = 0;
+    for (u32 i = threadIdx.x; i < (1u << logn); i += 256) {
+        acc += mulmod_b(mulmod_b(xs[i], ws[i], q, r0, r1), ys[i], q, r0, r1);
+        acc = acc >= q ? acc - q : acc;
+    }
+    part[threadIdx.x] = acc;
+    __syncthreads();
+    for (u32 s = 128; s > 0; s >>= 1) {
+        if (threadIdx.x < s) {
+            u64 v = part[threadIdx.x] + part[threadIdx.x + s];
+            part[threadIdx.x] = v >= q ? v - q : v;
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[unit] = scal ? mulmod_b(part[0], scal[limb0 + l], q, r0, r1) : part[0];
+}
+
+hipError_t launch_weighted_checksum3(hipStream_t st, u64 *out, const u64 *x, const u64 *y, const u64 *w, const u64 *scal, const LimbParams *lp,
+                                     u32 limb0, u32 limbs, u32 units, u32 poly_stride, int logn)
+{
+    if (!units) return hipSuccess;
+    hipLaunchKernelGGL(k_weighted_checksum3, dim3(units), dim3(256), 0, st, out, x, y, w, scal, lp, limb0, limbs, poly_stride, logn);
+    return hipGetLastError();
+}
+
+// checked product: flags[3 unit + k], k = 0 / 1 / 2 for a / b / the product (PolymulSums, per-tile partial sums)
+__global__ void k_compare_polymul(u32 *flags, PolymulSums s, const LimbParams *lp, u32 limb0, u32 limbs, u32 units)
+{
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= units) return;
+    const u64 q = lp[limb0 + i % limbs].q;
+    auto total = [&](const u64 *v, u32 n) {
+        u64 t = 0;
+        for (u32 j = 0; j < n; j++) {
+            t += v[(u64)i * n + j];
+            t = t >= q ? t - q : t;
+        }
+        return t;
+    };
+    const u64 ain = total(s.ain, s.t_in), bin = total(s.bin, s.t_in), aout = total(s.aout, s.t_mid), bout = total(s.bout, s.t_mid);
+    const u64 cin = total(s.cin, s.t_mid), cout = total(s.cout, s.t_out);
+    flags[3 * i] = ain != aout;
+    flags[3 * i + 1] = bin != bout;
+    flags[3 * i + 2] = cin != cout;
+}
+
+hipError_t launch_compare_polymul(hipStream_t st, u32 *flags, const PolymulSums &s, const LimbParams *lp, u32 limb0, u32 limbs, u32 units)
+{
+    if (!units) return hipSuccess;
+    hipLaunchKernelGGL(k_compare_polymul, dim3((units + 255) / 256), dim3(256), 0, st, flags, s, lp, limb0, limbs, units);
+    return hipGetLastError();
+}
+
 __global__ void k_compare_flags(u32 *flags, const u64 *a, const u64 *b, u32 units)
 {
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x;

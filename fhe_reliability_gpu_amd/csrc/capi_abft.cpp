@@ -1,4 +1,4 @@
-// capi_abft.cpp -- ABFT detector around the forward transform (part of the C ABI of include/fhe_mi355x.h; shared pieces in capi_internal.hpp)
+// capi_abft.cpp -- ABFT detector around the forward and inverse transforms and the negacyclic product (part of the C ABI of include/fhe_mi355x.h; shared pieces in capi_internal.hpp)
 #include "capi_internal.hpp"
 
 extern "C" {
@@ -137,16 +137,18 @@ int fhe_abft_checksum(fhe_ctx *ctx, const fhe_abft *a, int side, const uint64_t 
     return FHE_OK;
 }
 
-int fhe_ntt_forward_checked(fhe_ctx *ctx, uint64_t *d_data, const fhe_ntt_tables *t, const fhe_abft *a, size_t n_poly,
-                            size_t limbs, size_t start_idx, uint32_t *d_flags, void *stream)
+// checked forward / inverse transform (the inverse: the same weight tables with the sides swapped, abft_taps.hpp)
+static int checked_ntt(fhe_ctx *ctx, uint64_t *d_data, const fhe_ntt_tables *t, const fhe_abft *a, size_t n_poly, size_t limbs,
+                       size_t start_idx, uint32_t *d_flags, void *stream, bool inverse)
 {
     if (!ctx || !a || a->t != t || !d_flags) return fail(FHE_ERR_INVALID, "bad checked-transform arguments");
+    if (inverse && !t->has_inverse) return fail(FHE_ERR_UNSUPPORTED, "table set has no inverse (twiddle or N not invertible)");
     const size_t units = n_poly * limbs;
     fhe_abft *m = const_cast<fhe_abft *>(a);
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = pick(ctx, stream);
     u32 tin = 1, tout = 1;
-    ntt_checked_tiles(t->log_n, &tin, &tout);
+    ntt_checked_tiles(t->log_n, &tin, &tout, inverse);
     if (m->sum_in.bytes < units * 8 * tin || m->sum_out.bytes < units * 8 * tout) {
         HIP_TRY(hipStreamSynchronize(st));
         HIP_TRY(m->sum_in.alloc(units * 16 * tin));
@@ -165,7 +167,7 @@ int fhe_ntt_forward_checked(fhe_ctx *ctx, uint64_t *d_data, const fhe_ntt_tables
             hipError_t e;
             if (hook) {
                 // fault-injection hook: corrupt the intermediate between the two launches (one shot, after the last run's first pass)
-                e = launch_ntt_checked(st, pa, a->win.as<Tw>(), a->wout.as<Tw>(), a->wout8.as<u64>(), si, so, t->log_n, path, 0);
+                e = launch_ntt_checked(st, pa, a->win.as<Tw>(), a->wout.as<Tw>(), a->wout8.as<u64>(), si, so, t->log_n, path, 0, inverse);
                 if (e == hipSuccess && off + len == limbs) e = launch_flip_bit(st, d_data, (u64)ctx->fault_idx, ctx->fault_bit);
                 if (e != hipSuccess) return hip_fail(e, "launch_ntt_checked");
                 return FHE_OK;
@@ -183,10 +185,11 @@ int fhe_ntt_forward_checked(fhe_ctx *ctx, uint64_t *d_data, const fhe_ntt_tables
                     c.units = (u32)(cnt * len);
                     c.tmp = side_tmp ? side_tmp + off * N : pp ? pp + off * N : nullptr;
                     c.stream_hint = ctx->stream_hint != 0;
-                    return launch_ntt_checked(s, c, a->win.as<Tw>(), a->wout.as<Tw>(), a->wout8.as<u64>(), si + p0 * limbs * tin, so + p0 * limbs * tout, t->log_n, path);
+                    return launch_ntt_checked(s, c, a->win.as<Tw>(), a->wout.as<Tw>(), a->wout8.as<u64>(), si + p0 * limbs * tin, so + p0 * limbs * tout, t->log_n, path,
+                                              -1, inverse);
                 });
             }
-            e = launch_ntt_checked(st, pa, a->win.as<Tw>(), a->wout.as<Tw>(), a->wout8.as<u64>(), si, so, t->log_n, path);
+            e = launch_ntt_checked(st, pa, a->win.as<Tw>(), a->wout.as<Tw>(), a->wout8.as<u64>(), si, so, t->log_n, path, -1, inverse);
             return e == hipSuccess ? FHE_OK : hip_fail(e, "launch_ntt_checked");
         });
         if (rc) return rc;
@@ -195,7 +198,7 @@ int fhe_ntt_forward_checked(fhe_ctx *ctx, uint64_t *d_data, const fhe_ntt_tables
             rc = for_each_run(t, limbs, start_idx, [&](size_t off, size_t len, int path) -> int {
                 PassArgs pa{d_data + off * N, t->d_lp.as<LimbParams>(), (u32)(start_idx + off), (u32)len, (u32)(n_poly * len), (u32)limbs, nullptr};
                 hipError_t e = launch_ntt_checked(st, pa, a->win.as<Tw>(), a->wout.as<Tw>(), a->wout8.as<u64>(), m->sum_in.as<u64>() + off * tin, m->sum_out.as<u64>() + off * tout,
-                                                  t->log_n, path, 1);
+                                                  t->log_n, path, 1, inverse);
                 return e == hipSuccess ? FHE_OK : hip_fail(e, "launch_ntt_checked");
             });
             if (rc) return rc;
@@ -205,12 +208,133 @@ int fhe_ntt_forward_checked(fhe_ctx *ctx, uint64_t *d_data, const fhe_ntt_tables
         if (e != hipSuccess) return hip_fail(e, "launch_compare_sums");
         return FHE_OK;
     }
-    // separate reduction launches (tiny sizes, fused-NTT mode)
-    if ((rc = fhe_abft_checksum(ctx, a, 0, d_data, m->sum_in.as<u64>(), n_poly, limbs, start_idx, st))) return rc;
-    if ((rc = ntt_batch(ctx, d_data, t, n_poly, limbs, start_idx, st, false))) return rc;
-    if ((rc = fhe_abft_checksum(ctx, a, 1, d_data, m->sum_out.as<u64>(), n_poly, limbs, start_idx, st))) return rc;
+    // separate reduction launches (tiny sizes, fused-NTT mode); the inverse weighs its input with w^ and its output with w
+    if ((rc = fhe_abft_checksum(ctx, a, inverse ? 1 : 0, d_data, m->sum_in.as<u64>(), n_poly, limbs, start_idx, st))) return rc;
+    if ((rc = ntt_batch(ctx, d_data, t, n_poly, limbs, start_idx, st, inverse))) return rc;
+    if ((rc = fhe_abft_checksum(ctx, a, inverse ? 0 : 1, d_data, m->sum_out.as<u64>(), n_poly, limbs, start_idx, st))) return rc;
     hipError_t e = launch_compare_flags(st, d_flags, m->sum_in.as<u64>(), m->sum_out.as<u64>(), (u32)units);
     if (e != hipSuccess) return hip_fail(e, "launch_compare_flags");
+    return FHE_OK;
+}
+
+int fhe_ntt_forward_checked(fhe_ctx *ctx, uint64_t *d_data, const fhe_ntt_tables *t, const fhe_abft *a, size_t n_poly,
+                            size_t limbs, size_t start_idx, uint32_t *d_flags, void *stream)
+{
+    return checked_ntt(ctx, d_data, t, a, n_poly, limbs, start_idx, d_flags, stream, false);
+}
+
+int fhe_ntt_inverse_checked(fhe_ctx *ctx, uint64_t *d_data, const fhe_ntt_tables *t, const fhe_abft *a, size_t n_poly,
+                            size_t limbs, size_t start_idx, uint32_t *d_flags, void *stream)
+{
+    return checked_ntt(ctx, d_data, t, a, n_poly, limbs, start_idx, d_flags, stream, true);
+}
+
+int fhe_ctx_inject_fault_polymul(fhe_ctx *ctx, int point, long long idx, int bit)
+{
+    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
+    if (point < 0) {
+        ctx->pm_fault_point = -1;
+        return FHE_OK;
+    }
+    if (point > 3 || idx < 0 || bit < 0 || bit > 63) return fail(FHE_ERR_INVALID, "bad fault");
+    ctx->pm_fault_point = point;
+    ctx->pm_fault_idx = idx;
+    ctx->pm_fault_bit = bit;
+    return FHE_OK;
+}
+
+int fhe_polymul_checked(fhe_ctx *ctx, uint64_t *d_c, uint64_t *d_a, uint64_t *d_b, const fhe_ntt_tables *t, const fhe_abft *a,
+                        size_t n_poly, size_t limbs, size_t start_idx, uint32_t *d_flags, void *stream)
+{
+    if (!ctx || !a || a->t != t || !d_flags || !d_a || !d_b || !d_c) return fail(FHE_ERR_INVALID, "bad checked-product arguments");
+    int rc = check_range(t, n_poly, limbs, start_idx);
+    if (rc) return rc;
+    if (!t->has_inverse) return fail(FHE_ERR_UNSUPPORTED, "table set has no inverse (twiddle or N not invertible)");
+    const size_t units = n_poly * limbs, N = (size_t)1 << t->log_n;
+    const bool fused = ctx->mode == 0 && polymul_fused_supported(t->log_n);
+    // one-shot test hook: check that its point exists for this call before anything is launched
+    const int point = ctx->pm_fault_point;
+    const long long fidx = ctx->pm_fault_idx;
+    ctx->pm_fault_point = -1;
+    if (point >= 0) {
+        if (!fused || (point != 2 && t->log_n < 13))
+            return fail(FHE_ERR_UNSUPPORTED, "fault point does not exist at this size / mode (0, 1, 3: two-launch sizes N >= 2^13; 2: the fused product)");
+        if ((size_t)fidx >= units * N) return fail(FHE_ERR_INVALID, "fault index outside the call's window");
+    }
+    if (!units) return FHE_OK;
+    fhe_abft *m = const_cast<fhe_abft *>(a);
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = pick(ctx, stream);
+    PolymulSums s{};
+    if (fused) polymul_checked_tiles(t->log_n, &s.t_in, &s.t_mid, &s.t_out);
+    else s.t_in = s.t_mid = s.t_out = 1;
+    const size_t words = units * (2 * s.t_in + 3 * s.t_mid + s.t_out);
+    if (m->psum.bytes < words * 8) {
+        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(m->psum.alloc(words * 16));
+    }
+    u64 *ps = m->psum.as<u64>();
+    s.ain = ps;
+    s.bin = s.ain + units * s.t_in;
+    s.aout = s.bin + units * s.t_in;
+    s.bout = s.aout + units * s.t_mid;
+    s.cin = s.bout + units * s.t_mid;
+    s.cout = s.cin + units * s.t_mid;
+    if (d_b == d_a) s.bin = s.ain;           // squaring: one forward transform, both checks read its input sums
+    TraceScope tr(ctx, st, "POLYMUL");
+    if (fused) {
+        const size_t hit_unit = (size_t)fidx / N, hit_limb = hit_unit % limbs;
+        rc = for_each_run(t, limbs, start_idx, [&](size_t off, size_t len, int path) -> int {
+            PassArgs pa{d_a + off * N, t->d_lp.as<LimbParams>(), (u32)(start_idx + off), (u32)len, (u32)(n_poly * len), (u32)limbs};
+            PolymulChecks k{a->win.as<Tw>(), a->wout.as<Tw>(), a->wout8.as<u64>(), s, -1, nullptr, ctx->pm_fault_bit};
+            auto rows = [&](PolymulSums &r, size_t o) {      // this launch's rows of the sums: unit (p0 * limbs + l0) of the call
+                r.ain += o * r.t_in, r.bin += o * r.t_in, r.aout += o * r.t_mid, r.bout += o * r.t_mid, r.cin += o * r.t_mid, r.cout += o * r.t_out;
+            };
+            rows(k.s, off);
+            if (point >= 0 && hit_limb >= off && hit_limb < off + len) {
+                k.fault_point = point;
+                k.fault_at = (point == 1 ? d_b : point == 3 ? d_c : d_a) + fidx;
+            }
+            // operand sets that cannot stay in the Infinity Cache together: the pieces of fhe_polymul (not with the test hook armed)
+            const SubBatchCut cut = ctx->only_pass < 0 && point < 0 ? sub_batch_cut(ctx, t->log_n, n_poly, len, d_a == d_b ? 2 : 3) : SubBatchCut{0, 0};
+            if (cut.pc) {
+                const size_t npp = (n_poly + cut.pc - 1) / cut.pc, npl = (len + cut.lc - 1) / cut.lc;
+                return for_pieces(ctx, st, npp * npl, 0, [&](hipStream_t sp, size_t i, u64 *) {
+                    const size_t l0 = (i / npp) * cut.lc, p0 = (i % npp) * cut.pc, o = (p0 * limbs + l0) * N;
+                    const size_t lc = std::min(cut.lc, len - l0), pc = std::min(cut.pc, n_poly - p0);
+                    PassArgs w = pa;
+                    w.data = pa.data + o;
+                    w.limb0 = pa.limb0 + (u32)l0;
+                    w.limbs = (u32)lc;
+                    w.units = (u32)(pc * lc);
+                    PolymulChecks kp = k;
+                    rows(kp.s, p0 * limbs + l0);
+                    return launch_polymul_checked(sp, w, d_b + off * N + o, d_c + off * N + o, t->log_n, path, kp);
+                });
+            }
+            hipError_t e = launch_polymul_checked(st, pa, d_b + off * N, d_c + off * N, t->log_n, path, k);
+            return e == hipSuccess ? FHE_OK : hip_fail(e, "launch_polymul_checked");
+        });
+        if (rc) return rc;
+    } else {
+        // unfused sequence (tiny sizes, fused-NTT mode): separate reductions around every step
+        if ((rc = fhe_abft_checksum(ctx, a, 0, d_a, s.ain, n_poly, limbs, start_idx, st))) return rc;
+        if ((rc = ntt_batch(ctx, d_a, t, n_poly, limbs, start_idx, st, false))) return rc;
+        if ((rc = fhe_abft_checksum(ctx, a, 1, d_a, s.aout, n_poly, limbs, start_idx, st))) return rc;
+        if (d_b != d_a) {
+            if ((rc = fhe_abft_checksum(ctx, a, 0, d_b, s.bin, n_poly, limbs, start_idx, st))) return rc;
+            if ((rc = ntt_batch(ctx, d_b, t, n_poly, limbs, start_idx, st, false))) return rc;
+        }
+        if ((rc = fhe_abft_checksum(ctx, a, 1, d_b, s.bout, n_poly, limbs, start_idx, st))) return rc;
+        hipError_t e = launch_weighted_checksum3(st, s.cin, d_a, d_b, a->what.as<u64>(), a->ninv.as<u64>(), t->d_lp.as<LimbParams>(), (u32)start_idx,
+                                                 (u32)limbs, (u32)units, (u32)limbs, t->log_n);
+        if (e != hipSuccess) return hip_fail(e, "launch_weighted_checksum3");
+        if ((rc = pointwise(ctx, d_c, d_a, d_b, t, n_poly, limbs, start_idx, st, false))) return rc;
+        if ((rc = ntt_batch(ctx, d_c, t, n_poly, limbs, start_idx, st, true))) return rc;
+        if ((rc = fhe_abft_checksum(ctx, a, 0, d_c, s.cout, n_poly, limbs, start_idx, st))) return rc;
+    }
+    hipError_t e = launch_compare_polymul(st, d_flags, s, t->d_lp.as<LimbParams>(), (u32)start_idx, (u32)limbs, (u32)units);
+    if (e != hipSuccess) return hip_fail(e, "launch_compare_polymul");
     return FHE_OK;
 }
 

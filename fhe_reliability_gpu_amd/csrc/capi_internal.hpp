@@ -108,6 +108,8 @@ struct fhe_ctx {
     int fault_bit = 0;
     int pfault_pass = -1, pfault_bit = 0;       // one-shot bit flip INSIDE a pass of the per-phase checked transform
     u32 pfault_block = 0, pfault_word = 0;      // (fhe_ctx_inject_fault_in_pass): workgroup and LDS word
+    int pm_fault_point = -1, pm_fault_bit = 0;  // one-shot bit flip inside the next fhe_polymul_checked (fhe_ctx_inject_fault_polymul):
+    long long pm_fault_idx = 0;                 // where (point 0-3), word of the call's [poly][limb][N] window, bit
     int geo = 1;           // column-tile geometry of the two-launch path (ntt_launch.hpp)
     bool resident = false; // 2^13 / 2^14: one LDS-resident pass instead of two launches (opt-in, see ntt_plan.hpp)
     int pingpong = -1;        // "ntt_pingpong": two-launch transforms hand over through a per-stream scratch buffer (both launches out of
@@ -138,6 +140,7 @@ struct fhe_abft {
     DevBuf sum_in, sum_out;     // scratch checksums (grown on demand)
     DevBuf umid, umid8;         // per-phase detector: weights on the hand-off between the two launches, u = P1^-T w (twiddle-encoded / residues)
     DevBuf sum_mid1, sum_mid2;  // hand-off checksums as stored by the column pass / as loaded by the row pass
+    DevBuf psum;                // checked product: the six [units][tiles] partial-sum arrays of PolymulSums (grown on demand)
 };
 
 // Which limbs a rank of a limb-sharded key switch owns: ciphertext limbs [clo, clo + cn) and special limbs

@@ -323,9 +323,10 @@ template <class P> FHE_HD u64 pk_extract(P w, u32 idx)
 }
 
 // Optional observer of a pass ("tap"): sees every element the pass reads from global memory (after the
-// conversion to the arithmetic's element type) and every final word it writes, with the element's index
-// relative to the tile base.  The ABFT detector hangs its weighted checksums here (ntt_kernels.hip), so
-// that checking a transform costs arithmetic only, not two more sweeps over the data.
+// conversion to the arithmetic's element type; for a row pass that stages its input, as its first register
+// step takes the staged words) and every final canonical word it writes, with the element's index relative to
+// the tile base.  The ABFT detector hangs its weighted checksums here (ntt_kernels.hip), so
+// that checking a transform costs arithmetic only, not two more sweeps over the data (taps: abft_taps.hpp).
 // (a tap that declares PRELOAD = true instead offers load(idx) / apply(x, word, ctx): a second input of the pass, see AddSrcTap)
 template <class T, class = void> struct tap_preloads { static constexpr bool value = false; };
 template <class T> struct tap_preloads<T, decltype((void)T::PRELOAD)> { static constexpr bool value = T::PRELOAD; };
@@ -433,6 +434,7 @@ struct ColPass {
                 for (int r = 0; r < R; r++) {
                     u64 *dst = base + (size_t)(g0 + ((u32)r << LOGS)) * STRIDE + col;
                     const u64 out = convert_out<A, OUT_MODE, INVERSE, FOLD>(x[r], c, inv_n);
+                    if constexpr (TAP::ACTIVE && !TAP::STORES && OUT_MODE == IO_CANONICAL) tap->out((g0 + ((u32)r << LOGS)) * STRIDE + col, out, c);
                     if (STREAM && OUT_MODE == IO_CANONICAL) store_stream_u64(dst, out);
                     else *dst = out;
                 }
@@ -660,7 +662,7 @@ struct RowPass {
                         }
                     }
                     convert_in<A, R, IN_MODE>(x, raw, c);
-                    if constexpr (TAP::ACTIVE && FROM_GLOBAL) {
+                    if constexpr (TAP::ACTIVE && (FROM_GLOBAL || STAGE_IN)) {      // (STAGE_IN: the words the copy phase staged)
 #pragma unroll
                         for (int r = 0; r < R; r++) tap->in(row * NPTS + g0 + ((u32)r << LOGS), x[r], c);
                     }
@@ -681,6 +683,7 @@ struct RowPass {
                     for (int r = 0; r < R; r++) {
                         const u64 out = convert_out<A, OUT_MODE, INVERSE, FOLD>(x[r], c, inv_n);
                         if (TO_GLOBAL) {
+                            if constexpr (TAP::ACTIVE && !TAP::STORES && OUT_MODE == IO_CANONICAL) tap->out(row * NPTS + g0 + ((u32)r << LOGS), out, c);
                             if (STREAM && OUT_MODE == IO_CANONICAL) store_stream_u64(grow + g0 + ((u32)r << LOGS), out);
                             else grow[g0 + ((u32)r << LOGS)] = out;
                         }

@@ -5,6 +5,7 @@
 // The butterfly code lives in ntt_core.hpp; this file only binds it to the grid.
 #include "ntt_launch.hpp"
 #include "ntt_plan.hpp"
+#include "abft_taps.hpp"
 
 #include <cstdlib>
 #include <type_traits>
@@ -364,117 +365,12 @@ struct AbftArgs {
     u64 *sum_out;       // [units][tiles of the pass that writes the result]
 };
 
-template <class A, bool IN, bool OUT>
-struct ChecksumTap {
-    static constexpr bool ACTIVE = true;
-    static constexpr bool MID = false;
-    static constexpr bool STORES = false;
-    typedef typename A::elem elem;
-    TwPtr win, wout;                   // ArithU64: Shoup-encoded weights of this limb, offset to the tile's first element
-    const u64 FHE_GLOBAL *wout8;       // ArithF64: output-side weights as plain residues (the quotient factor is one multiply)
-    u32 pos0;                          // index of the tile's first element inside its limb
-    int logp;                          // input-side weight of element i = (i mod 2^logp + 1) + (i div 2^logp + 1)
-    elem acc_in, acc_out;
-    int n_in, n_out;
-    FHE_D void in(u32 idx, elem x, const typename A::Ctx &c)
-    {
-        if constexpr (IN) {
-            if constexpr (A::PATH == PATH_F64) {
-                // generate_weights (negaclic_ntt.py:7-13) computed in place of a table read: small integers
-                const u32 i = pos0 + idx;
-                // (the small integer becomes a double through the exponent trick of from_canonical: one subtraction, no v_cvt_f64_u32)
-                const double w = ArithF64::from_canonical((u64)((i & ((1u << logp) - 1u)) + (i >> logp) + 2u));
-                A::lazy_acc(acc_in, A::mulmod_w(x, w, w * c.ninv, c), ++n_in, c);
-            } else {
-                A::lazy_acc(acc_in, A::mulmod(x, win[idx], c), ++n_in, c);
-            }
-        }
-    }
-    FHE_D void out(u32 idx, u64 v, const typename A::Ctx &c)
-    {
-        if constexpr (OUT) {
-            if constexpr (A::PATH == PATH_F64) {
-                const double w = A::from_canonical(wout8[idx]);
-                A::lazy_acc(acc_out, A::mulmod_w(A::from_canonical(v), w, w * c.ninv, c), ++n_out, c);
-            } else {
-                A::lazy_acc(acc_out, A::mulmod(A::from_canonical(v), wout[idx], c), ++n_out, c);
-            }
-        }
-    }
-};
-
-// Per-phase detector (the reference checks its four-step flow phase by phase: batch_check of the column transforms,
-// check_inter around the twiddle step, batch_check of the row transforms -- rfhe_framewk/src/ntt_test/relia_ntt_sim.cpp:235-292,
-// 331-355; reliability_test/four_step_ntt_prot.py:185-194).  The engine's two launches ARE that flow -- column transforms,
-// then row transforms with the twiddle folded into their butterflies -- so the checks sit at the same three places:
-//   column pass :  sum_i w_i x_i  (words it loads)        ==  sum_i u_i y_i  (words it stores),   u = P1^-T w
-//   hand-off    :  sum_i u_i y_i  (as stored)             ==  sum_i u_i y_i  (as loaded by the row pass)
-//   row pass    :  sum_i u_i y_i  (words it loads)        ==  sum_j w^_j X_j (words it stores),   w^ = T^-T w
-// PASS 0 = column pass (in: w, mid: u), PASS 1 = row pass (in: u, out: w^).
-template <class A, int PASS>
-struct PhaseTap {
-    static constexpr bool ACTIVE = true;
-    static constexpr bool MID = PASS == 0;
-    static constexpr bool STORES = false;
-    typedef typename A::elem elem;
-    TwPtr win, umid, wout;             // ArithU64: Shoup-encoded weights of this limb, offset to the tile's first element
-    const u64 FHE_GLOBAL *umid8, *wout8;   // ArithF64: the same weights as plain residues
-    u32 pos0;
-    int logp;
-    elem acc_a, acc_b;
-    int n_a, n_b;
-    FHE_D void weigh(elem &acc, int &n, elem x, u32 idx, TwPtr tw, const u64 FHE_GLOBAL *tw8, const typename A::Ctx &c)
-    {
-        if constexpr (A::PATH == PATH_F64) {
-            const double w = A::from_canonical(tw8[idx]);
-            A::lazy_acc(acc, A::mulmod_w(x, w, w * c.ninv, c), ++n, c);
-        } else {
-            A::lazy_acc(acc, A::mulmod(x, tw[idx], c), ++n, c);
-        }
-    }
-    FHE_D void in(u32 idx, elem x, const typename A::Ctx &c)
-    {
-        if constexpr (PASS == 0) {
-            if constexpr (A::PATH == PATH_F64) {
-                const u32 i = pos0 + idx;
-                const double w = ArithF64::from_canonical((u64)((i & ((1u << logp) - 1u)) + (i >> logp) + 2u));     // generate_weights, negaclic_ntt.py:7-13
-                A::lazy_acc(acc_a, A::mulmod_w(x, w, w * c.ninv, c), ++n_a, c);
-            } else {
-                A::lazy_acc(acc_a, A::mulmod(x, win[idx], c), ++n_a, c);
-            }
-        } else {
-            weigh(acc_a, n_a, x, idx, umid, umid8, c);
-        }
-    }
-    FHE_D void mid(u32 idx, elem x, const typename A::Ctx &c) { weigh(acc_b, n_b, x, idx, umid, umid8, c); }
-    FHE_D void out(u32 idx, u64 v, const typename A::Ctx &c) { weigh(acc_b, n_b, A::from_canonical(v), idx, wout, wout8, c); }
-};
-
-// modular sum of one canonical value per thread over the workgroup, stored to *dst by one lane
-__device__ __forceinline__ void block_sum_mod(u64 v, u64 q, u64 *dst, u64 *red)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        v += __shfl_down(v, off, 64);
-        v = v >= q ? v - q : v;
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) red[wave] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        u64 s = 0;
-        for (int w = 0; w < NTT_THREADS / 64; w++) {
-            s += red[w];
-            s = s >= q ? s - q : s;
-        }
-        *dst = s;
-    }
-}
-
-template <class PASS, int LOGN, bool IS_COL, bool IN, bool OUT>
+// INV: a pass of the checked inverse transform (InvChecksumTap: w^ on the words loaded, w on the words stored)
+template <class PASS, int LOGN, bool IS_COL, bool IN, bool OUT, bool INV = false>
 __global__ __launch_bounds__(NTT_THREADS) void k_ntt_pass_abft(PassArgs a, AbftArgs ab)
 {
     typedef typename PASS::Arith A;
+    typedef std::conditional_t<INV, InvChecksumTap<A, IN, OUT>, ChecksumTap<A, IN, OUT>> Tap;
     __shared__ __attribute__((aligned(16))) typename PASS::elem lds[PASS::LDS_ELEMS > 0 ? PASS::LDS_ELEMS : 1];
     __shared__ u64 red[2][NTT_THREADS / 64];
     u32 limb, row0 = 0;
@@ -487,10 +383,10 @@ __global__ __launch_bounds__(NTT_THREADS) void k_ntt_pass_abft(PassArgs a, AbftA
     const u32 pos0 = (u32)((base - a.data) & (((size_t)1 << LOGN) - 1));
     const LimbParams &p = a.lp[limb];
     const typename A::Ctx ctx = A::make_ctx(p);
-    const TwPtr tw = as_global(p.fwd);
+    const TwPtr tw = as_global(INV ? p.inv : p.fwd);
     const Tw inv_n = p.inv_n;
     const int tid = threadIdx.x;
-    ChecksumTap<A, IN, OUT> tap{as_global(ab.win) + ((size_t)limb << LOGN) + pos0, as_global(ab.wout) + ((size_t)limb << LOGN) + pos0,
+    Tap tap{as_global(ab.win) + ((size_t)limb << LOGN) + pos0, as_global(ab.wout) + ((size_t)limb << LOGN) + pos0,
                                 (const u64 FHE_GLOBAL *)ab.wout8 + ((size_t)limb << LOGN) + pos0, pos0, ab.logp,
                                 typename A::elem(0), typename A::elem(0), 0, 0};
     const u64 *from = pass_source<PASS, LOGN, IS_COL>(a, base, row0);      // ping-pong hand-off: this launch loads from a.src
@@ -534,6 +430,33 @@ static hipError_t launch_checked(hipStream_t st, const PassArgs &a, const AbftAr
         }
         if (which != 1) hipLaunchKernelGGL((k_ntt_pass_abft<typename PS::Col, LOGN, true, true, false>), dim3(a.units * PS::Col::TILES), dim3(NTT_THREADS), 0, st, first, ab);
         if (which != 0) hipLaunchKernelGGL((k_ntt_pass_abft<typename PS::Row, LOGN, false, false, true>), dim3(a.units * PS::Row::TILES), dim3(NTT_THREADS), 0, st, second, ab);
+    }
+    return hipGetLastError();
+}
+
+// checked inverse: the row pass (first launch) carries the input-side sums, the column pass (last launch) the output-side ones
+template <class A, int LOGN>
+static hipError_t launch_checked_inv(hipStream_t st, const PassArgs &a, const AbftArgs &ab, int which)
+{
+    constexpr int GEO = LOGN >= 13 ? 1 : 0;
+    typedef Passes<A, LOGN, true, GEO> PS;
+    if constexpr (!PS::G::TWO_PASS) {
+        if (which == 1) return hipSuccess;
+        hipLaunchKernelGGL((k_ntt_pass_abft<typename PS::Single, LOGN, false, true, true, true>), dim3(a.units * PS::Single::TILES), dim3(NTT_THREADS), 0, st, a, ab);
+    } else {
+        PassArgs first = a, second = a;
+        if (a.tmp && which == -1) {                // ping-pong: data -> tmp -> data, both launches out of place (launch_transform)
+            first.src = a.data;
+            first.data = a.tmp;
+            second.src = a.tmp;
+        }
+        if (a.stream_hint && GEO == 1) {      // pieces of a batch that streams from HBM: non-temporal accesses on the external side (launch_transform)
+            if (which != 1) hipLaunchKernelGGL((k_ntt_pass_abft<typename PS::RowNt, LOGN, false, true, false, true>), dim3(a.units * PS::Row::TILES), dim3(NTT_THREADS), 0, st, first, ab);
+            if (which != 0) hipLaunchKernelGGL((k_ntt_pass_abft<typename PS::ColNt, LOGN, true, false, true, true>), dim3(a.units * PS::Col::TILES), dim3(NTT_THREADS), 0, st, second, ab);
+            return hipGetLastError();
+        }
+        if (which != 1) hipLaunchKernelGGL((k_ntt_pass_abft<typename PS::Row, LOGN, false, true, false, true>), dim3(a.units * PS::Row::TILES), dim3(NTT_THREADS), 0, st, first, ab);
+        if (which != 0) hipLaunchKernelGGL((k_ntt_pass_abft<typename PS::Col, LOGN, true, false, true, true>), dim3(a.units * PS::Col::TILES), dim3(NTT_THREADS), 0, st, second, ab);
     }
     return hipGetLastError();
 }
@@ -634,21 +557,25 @@ hipError_t launch_ntt_phases(hipStream_t st, const PassArgs &a, const PhaseArgs 
 
 bool ntt_checked_supported(int logn) { return logn >= 5 && logn <= NTT_MAX_LOGN; }
 
-template <int LOGN> static void checked_tiles_t(u32 *tin, u32 *tout)
+template <int LOGN> static void checked_tiles_t(u32 *tin, u32 *tout, bool inverse)
 {
     typedef Passes<ArithF64, LOGN, false, (LOGN >= 13 ? 1 : 0)> PS;
-    if constexpr (!PS::G::TWO_PASS) *tin = *tout = PS::Single::TILES;
-    else {
+    typedef Passes<ArithF64, LOGN, true, (LOGN >= 13 ? 1 : 0)> PI;
+    if constexpr (!PS::G::TWO_PASS) *tin = *tout = inverse ? PI::Single::TILES : PS::Single::TILES;
+    else if (inverse) {
+        *tin = PI::Row::TILES;
+        *tout = PI::Col::TILES;
+    } else {
         *tin = PS::Col::TILES;
         *tout = PS::Row::TILES;
     }
 }
 // partial sums per unit on the input / output side (row lengths of sum_in / sum_out)
-void ntt_checked_tiles(int logn, u32 *tin, u32 *tout)
+void ntt_checked_tiles(int logn, u32 *tin, u32 *tout, bool inverse)
 {
     *tin = *tout = 1;
     switch (logn) {
-#define FHE_CASE(L) case L: checked_tiles_t<L>(tin, tout); break;
+#define FHE_CASE(L) case L: checked_tiles_t<L>(tin, tout, inverse); break;
         FHE_CASE(5) FHE_CASE(6) FHE_CASE(7) FHE_CASE(8) FHE_CASE(9) FHE_CASE(10) FHE_CASE(11) FHE_CASE(12) FHE_CASE(13)
         FHE_CASE(14) FHE_CASE(15) FHE_CASE(16) FHE_CASE(17) FHE_CASE(18) FHE_CASE(19) FHE_CASE(20)
 #undef FHE_CASE
@@ -656,16 +583,18 @@ void ntt_checked_tiles(int logn, u32 *tin, u32 *tout)
     }
 }
 
-// forward transform with the checksums fused in; which as in launch_ntt (the fault hook splits the launches)
+// forward / inverse transform with the checksums fused in; which as in launch_ntt (the fault hook splits the launches)
 hipError_t launch_ntt_checked(hipStream_t st, const PassArgs &a, const Tw *win, const Tw *wout, const u64 *wout8, u64 *sum_in, u64 *sum_out,
-                              int logn, int path, int which)
+                              int logn, int path, int which, bool inverse)
 {
     if (a.units == 0) return hipSuccess;
     if (a.map) return hipErrorInvalidValue;
     const AbftArgs ab{win, wout, wout8, logn / 2, sum_in, sum_out};
     switch (logn) {
-#define FHE_CASE(L) \
-    case L: return path == PATH_F64 ? launch_checked<ArithF64, L>(st, a, ab, which) : launch_checked<ArithU64, L>(st, a, ab, which);
+#define FHE_CASE(L)                                                                                                               \
+    case L:                                                                                                                       \
+        if (inverse) return path == PATH_F64 ? launch_checked_inv<ArithF64, L>(st, a, ab, which) : launch_checked_inv<ArithU64, L>(st, a, ab, which); \
+        return path == PATH_F64 ? launch_checked<ArithF64, L>(st, a, ab, which) : launch_checked<ArithU64, L>(st, a, ab, which);
         FHE_CASE(5) FHE_CASE(6) FHE_CASE(7) FHE_CASE(8) FHE_CASE(9) FHE_CASE(10) FHE_CASE(11) FHE_CASE(12) FHE_CASE(13)
         FHE_CASE(14) FHE_CASE(15) FHE_CASE(16) FHE_CASE(17) FHE_CASE(18) FHE_CASE(19) FHE_CASE(20)
 #undef FHE_CASE
@@ -706,21 +635,6 @@ FHE_D void inv_steps(int tid, u64 *base, typename IR::elem *lds, TwPtr tw, u32 r
         inv_steps<IR, E + 1>(tid, base, lds, tw, row0, ctx, inv_n);
     }
 }
-
-// the row passes of the middle launch: the forward one leaves its results in the LDS image in the arithmetic's LAZY form
-// and the inverse one takes them from there in that form, so the product never goes through canonical words
-template <class A, int LOGN, int GEO>
-struct MidPasses {
-    typedef Passes<A, LOGN, false, GEO> F;
-    typedef Passes<A, LOGN, true, GEO> I;
-    typedef typename F::PL PL;
-    static constexpr bool TWO = F::G::TWO_PASS;
-    static constexpr int TR = TWO ? F::G::TR : 1;
-    static constexpr int SB = BlkStage<LOGN>::value;
-    typedef RowPass<A, typename PL::Row, LOGN, TR, NTT_THREADS, false, TWO ? IO_LAZY : IO_CANONICAL, IO_LAZY, TWO ? F::RED_SECOND : F::RED_FIRST, SB> Fwd;
-    typedef RowPass<A, typename PL::Row, LOGN, TR, NTT_THREADS, true, IO_LAZY, TWO ? IO_LAZY : IO_CANONICAL, I::RED_FIRST, SB> Inv;
-};
-
 template <class A, int LOGN, int GEO>
 __global__ __launch_bounds__(NTT_THREADS) void k_polymul_mid(PolymulArgs pa)
 {

@@ -52,10 +52,37 @@ hipError_t launch_polymul(hipStream_t st, const PassArgs &a, u64 *b, u64 *c, int
 // [units][tin] / [units][tout] partial sums (units in [poly][limb] order; tin, tout from ntt_checked_tiles);
 // win / wout = [table limbs][N] weights in twiddle encoding (used by ArithU64 limbs), wout8 = output-side weights as
 // residues (ArithF64 limbs; their input-side weights are computed in place).  `which` as in launch_ntt.
+// inverse: the checked inverse transform -- the same tables with the sides swapped (sum_in = sum w^ X over the words the
+// row pass loads, sum_out = sum w x over the words the column pass stores; abft_taps.hpp InvChecksumTap).
 bool ntt_checked_supported(int logn);
-void ntt_checked_tiles(int logn, u32 *tin, u32 *tout);
+void ntt_checked_tiles(int logn, u32 *tin, u32 *tout, bool inverse = false);
 hipError_t launch_ntt_checked(hipStream_t st, const PassArgs &a, const Tw *win, const Tw *wout, const u64 *wout8, u64 *sum_in, u64 *sum_out,
-                              int logn, int path, int which = -1);
+                              int logn, int path, int which = -1, bool inverse = false);
+
+// checked negacyclic product (launch_polymul with the detector): per limb-polynomial, in [poly][limb] order,
+//   ain / bin   [units][t_in]  : sum w a, sum w b over the words the forward column passes load (one-launch sizes: the middle launch)
+//   aout / bout [units][t_mid] : sum w^ a^, sum w^ b^ over the forward results as the middle launch multiplies them
+//   cin         [units][t_mid] : sum w^ a^ b^, formed next to the product
+//   cout        [units][t_out] : sum w c over the words the inverse column pass stores (one-launch sizes: the middle launch)
+// Test hook (fault_point >= 0, one word `fault_at` and bit `fault_bit`): 0 / 1 = flip a's / b's word after its column pass,
+// 2 = flip the product value at fault_at's tile position (fault_at points into a) after the multiply, 3 = flip c's word before
+// the inverse column pass.
+struct PolymulSums {
+    u64 *ain, *bin, *aout, *bout, *cin, *cout;
+    u32 t_in, t_mid, t_out;
+};
+struct PolymulChecks {
+    const Tw *win, *wout;
+    const u64 *wout8;
+    PolymulSums s;
+    int fault_point;
+    u64 *fault_at;
+    int fault_bit;
+};
+void polymul_checked_tiles(int logn, u32 *t_in, u32 *t_mid, u32 *t_out);
+hipError_t launch_polymul_checked(hipStream_t st, const PassArgs &a, u64 *b, u64 *c, int logn, int path, const PolymulChecks &k);
+// flags[3 unit + k]: k = 0 / 1 / 2 = sums of a / b / the product differ (PolymulSums; tiles 1 for the unfused sequence)
+hipError_t launch_compare_polymul(hipStream_t st, u32 *flags, const PolymulSums &s, const LimbParams *lp, u32 limb0, u32 limbs, u32 units);
 
 // per-phase detector (two-launch sizes): the column pass accumulates sum w x over what it loads and sum u y over what it
 // stores, the row pass sum u y over what it loads and sum w^ X over what it stores (weights: capi_abft.cpp).  One PhaseArgs
@@ -158,6 +185,9 @@ hipError_t launch_sub_scale(hipStream_t st, const SubScaleArgs &p);
 // checksum of the reference's ECC (rfhe_framewk/src/negaclic_ntt.py:130-149); scal[limb] multiplies the sum
 hipError_t launch_weighted_checksum(hipStream_t st, u64 *out, const u64 *x, const u64 *w, const u64 *scal, const LimbParams *lp,
                                     u32 limb0, u32 limbs, u32 units, u32 poly_stride, int logn);
+// out[unit] = scal[limb] * sum_i w[limb][i] * x[unit][i] * y[unit][i] mod q_limb: the input side of the unfused product's check
+hipError_t launch_weighted_checksum3(hipStream_t st, u64 *out, const u64 *x, const u64 *y, const u64 *w, const u64 *scal, const LimbParams *lp,
+                                     u32 limb0, u32 limbs, u32 units, u32 poly_stride, int logn);
 // flags[unit] = a[unit] != b[unit]
 hipError_t launch_compare_flags(hipStream_t st, u32 *flags, const u64 *a, const u64 *b, u32 units);
 // flags[unit] = (sum of a[unit][0..ta) mod q_l) != (sum of b[unit][0..tb) mod q_l)  (unit = poly * limbs + l)

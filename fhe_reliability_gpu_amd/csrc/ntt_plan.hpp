@@ -142,6 +142,20 @@ struct Passes {
                     INVERSE ? IO_LAZY : IO_CANONICAL, INVERSE ? RED_FIRST : RED_SECOND, SB, 0, true> RowNt;
 };
 
+// the row passes of the negacyclic product's middle launch (ntt_kernels.hip k_polymul_mid): the forward one leaves its results in the LDS image in the arithmetic's LAZY form
+// and the inverse one takes them from there in that form, so the product never goes through canonical words
+template <class A, int LOGN, int GEO>
+struct MidPasses {
+    typedef Passes<A, LOGN, false, GEO> F;
+    typedef Passes<A, LOGN, true, GEO> I;
+    typedef typename F::PL PL;
+    static constexpr bool TWO = F::G::TWO_PASS;
+    static constexpr int TR = TWO ? F::G::TR : 1;
+    static constexpr int SB = BlkStage<LOGN>::value;
+    typedef RowPass<A, typename PL::Row, LOGN, TR, NTT_THREADS, false, TWO ? IO_LAZY : IO_CANONICAL, IO_LAZY, TWO ? F::RED_SECOND : F::RED_FIRST, SB> Fwd;
+    typedef RowPass<A, typename PL::Row, LOGN, TR, NTT_THREADS, true, IO_LAZY, TWO ? IO_LAZY : IO_CANONICAL, I::RED_FIRST, SB> Inv;
+};
+
 // LDS-resident single pass for the sizes just above the 64 KiB static limit (opt-in, "ntt_resident"): a 2^13 / 2^14
 // limb (64 / 128 KiB) still fits one CU's 160 KiB of LDS on gfx950, so the whole transform can run in one workgroup
 // and the limb crosses the fabric once in and once out instead of twice.  Radix-32 register steps (32 points per

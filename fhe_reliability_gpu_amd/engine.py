@@ -528,7 +528,8 @@ class KeySwitch:
 # ABFT detector
 # ---------------------------------------------------------------------------
 class Abft:
-    """Weighted-checksum ECC around the forward NTT (rfhe_framewk/src/negaclic_ntt.py:130-149)."""
+    """Weighted-checksum ECC around the forward NTT, the inverse NTT and the negacyclic product
+    (rfhe_framewk/src/negaclic_ntt.py:130-149)."""
 
     def __init__(self, eng: Engine, t: NttTables):
         self.eng, self.t = eng, t
@@ -555,6 +556,32 @@ class Abft:
         n = n_poly * limbs * 3
         flags = self.eng.alloc((n + 1) // 2)
         check(lib.fhe_ntt_forward_checked_phases(self.eng._h, d.ptr, self.t._h, self._h, n_poly, limbs, start, flags.ptr, None))
+        return flags.download().view(np.uint32)[:n].reshape(n_poly * limbs, 3)
+
+    def inverse_checked(self, d: DeviceArray, n_poly: int = 1, limbs: Optional[int] = None, start: int = 0) -> np.ndarray:
+        """In-place inverse NTT; returns the per-limb-polynomial fault flags.
+
+        The forward detector's weights with the sides swapped: x = F^-1 x_hat gives sum_j w_hat_j x_hat_j = sum_i w_i x_i, the
+        input side weighed with w_hat on the words the first launch loads, the output side with w on the words the last one
+        stores -- the check after the closing transform of rfhe_framewk/src/four_step_ntt_protected.py:219-282."""
+        limbs = len(self.t) - start if limbs is None else limbs
+        flags = self.eng.alloc((n_poly * limbs + 1) // 2)
+        check(lib.fhe_ntt_inverse_checked(self.eng._h, d.ptr, self.t._h, self._h, n_poly, limbs, start, flags.ptr, None))
+        return flags.download().view(np.uint32)[: n_poly * limbs]
+
+    def polymul_checked(self, c: DeviceArray, a: DeviceArray, b: DeviceArray, n_poly: int = 1, limbs: Optional[int] = None,
+                        start: int = 0) -> np.ndarray:
+        """c = a * b mod (x^N + 1, q) as ``NttTables.polymul`` (a and b are scratch, c may alias either); returns
+        flags[unit, 3] = (forward transform of a, forward transform of b, product + inverse).
+
+        The three checks of the protected chain transform -> element-wise product -> transform
+        (rfhe_framewk/src/four_step_ntt_protected.py:219-282): sum w a == sum w_hat a_hat, sum w b == sum w_hat b_hat, and,
+        since c_hat_j = a_hat_j b_hat_j, sum_i w_i c_i == sum_j w_hat_j a_hat_j b_hat_j -- the last sum formed next to the
+        product, not from its result."""
+        limbs = len(self.t) - start if limbs is None else limbs
+        n = n_poly * limbs * 3
+        flags = self.eng.alloc((n + 1) // 2)
+        check(lib.fhe_polymul_checked(self.eng._h, c.ptr, a.ptr, b.ptr, self.t._h, self._h, n_poly, limbs, start, flags.ptr, None))
         return flags.download().view(np.uint32)[:n].reshape(n_poly * limbs, 3)
 
     def __del__(self):

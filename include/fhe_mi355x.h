@@ -375,12 +375,14 @@ int fhe_hmult_shard_finish_end(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0_
 int fhe_ctx_trace(fhe_ctx *ctx, int enable);
 int fhe_ctx_trace_read(fhe_ctx *ctx, char *buf, size_t cap, size_t *len);
 
-/* ---- ABFT detector around the forward NTT ------------------------- */
+/* ---- ABFT detector around the forward NTT, the inverse NTT and the product ---- */
 /* Weighted-checksum ECC of rfhe_framewk/src/negaclic_ntt.py:130-149: with weights w (generate_weights,
  * :7-13: w[i] = (i % p + 1) + (i / p + 1), p = 2^floor(log_n / 2)) and w_hat = V^-T w, a correct
  * transform satisfies sum_i w_i a_i = sum_j w_hat_j a_hat_j (mod q).  w_hat is obtained on the device
  * from the forward transform itself: w_hat = N^-1 * NTT(w_0, -w_{N-1}, ..., -w_1), already in the
- * engine's bit-reversed order.  One weight set per limb of `t`. */
+ * engine's bit-reversed order.  One weight set per limb of `t`.  The same two sets check the inverse transform (sides swapped)
+ * and the product (sum w c = sum w_hat a_hat b_hat).  Not covered: faults already in the input, and a register fault between
+ * a checksum's read of a value and the instruction that consumes the same register. */
 int fhe_abft_create(fhe_ctx *ctx, const fhe_ntt_tables *t, fhe_abft **out);
 int fhe_abft_destroy(fhe_abft *a);
 /* side 0: d_out[unit] = sum_i w_i x_i (input side); side 1: N^-1 sum_j w'_j x_j (output side) */
@@ -405,6 +407,31 @@ int fhe_ntt_forward_checked(fhe_ctx *ctx, uint64_t *d_data, const fhe_ntt_tables
  * launch = one phase: fhe_ntt_forward_checked. */
 int fhe_ntt_forward_checked_phases(fhe_ctx *ctx, uint64_t *d_data, const fhe_ntt_tables *t, const fhe_abft *a, size_t n_poly,
                                    size_t limbs, size_t start_idx, uint32_t *d_flags, void *stream);
+/* Inverse NTT with the detector around it: the same two weight sets with the sides swapped (x = F^-1 x_hat gives
+ * sum_j w_hat_j x_hat_j = sum_i w_i x_i).  d_flags[unit] = 1 where the input-side sum (w_hat, over the words the first launch
+ * loads) differs from the output-side sum (w, over the words the last launch stores).  The output words are those of
+ * fhe_ntt_inverse_inplace, bit for bit.  Same sizes, arithmetic paths, limb windows and sub-batches as the forward detector;
+ * fhe_ctx_inject_fault flips a word between the row pass and the column pass (N >= 2^13). */
+int fhe_ntt_inverse_checked(fhe_ctx *ctx, uint64_t *d_data, const fhe_ntt_tables *t, const fhe_abft *a, size_t n_poly,
+                            size_t limbs, size_t start_idx, uint32_t *d_flags, void *stream);
+/* fhe_polymul with the detector (the protected chain transform -> element-wise product -> transform of
+ * rfhe_framewk/src/four_step_ntt_protected.py:219-282).  Same contract as fhe_polymul: a and b are scratch, c may alias either,
+ * the product words are fhe_polymul's.  Three flags per limb-polynomial, d_flags[3*unit + k]:
+ *   k = 0  forward transform of a : sum w a over the loaded words  !=  sum w_hat a_hat as the product consumes a_hat
+ *   k = 1  the same for b (for a == b it equals k = 0)
+ *   k = 2  product, hand-off and inverse : sum w_hat a_hat b_hat (formed next to the product, not from its result)  !=  sum w c
+ *          over the stored result   (c_hat_j = a_hat_j b_hat_j gives sum_i w_i c_i = sum_j w_hat_j a_hat_j b_hat_j)
+ * For N >= 2^5 the sums ride on the product's own launches (no extra sweep over the data); smaller sizes and the fused-NTT mode
+ * use separate reductions.  Faults already present in a or b are not flagged, and neither is a register fault between a
+ * sum's read of a value and the instruction that consumes the same register. */
+int fhe_polymul_checked(fhe_ctx *ctx, uint64_t *d_c, uint64_t *d_a, uint64_t *d_b, const fhe_ntt_tables *t, const fhe_abft *a,
+                        size_t n_poly, size_t limbs, size_t start_idx, uint32_t *d_flags, void *stream);
+/* Test hook: one bit flip (bit `bit`) inside the next fhe_polymul_checked on this context; `idx` = word of the call's
+ * [poly][limb][N] window.  point 0 / 1: a's / b's column-pass output before the middle launch (N >= 2^13, flags k = 0 / 1);
+ * 2: one product value of unit idx / N inside the middle launch, after the multiply (every fused size, k = 2); 3: c between the
+ * middle launch and the inverse column pass (N >= 2^13, k = 2).  One shot; point < 0 clears it.  A point that does not exist
+ * for the call makes it return FHE_ERR_UNSUPPORTED without launching anything. */
+int fhe_ctx_inject_fault_polymul(fhe_ctx *ctx, int point, long long idx, int bit);
 /* Test hook: a soft error INSIDE a pass of the next fhe_ntt_forward_checked_phases call -- XOR bit `bit` of word `lds_word`
  * (modulo the image size) of workgroup `workgroup`'s LDS image between the pass's first two register steps; pass 0 = column
  * pass, 1 = row pass, < 0 clears it.  One shot.  (The reference injects into butterfly results, relia_ntt_sim.cpp:189-194.) */
