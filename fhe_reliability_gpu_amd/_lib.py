@@ -90,6 +90,10 @@ _SIG = {
     "fhe_ntt_inverse_checked": (ci, [vp, vp, vp, vp, sz, sz, sz, vp, vp]),
     "fhe_polymul_checked": (ci, [vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, vp]),
     "fhe_ctx_inject_fault_polymul": (ci, [vp, ci, C.c_longlong, ci]),
+    "fhe_modmul_checked": (ci, [vp, vp, vp, vp, vp, sz, sz, sz, vp, vp]),
+    "fhe_modmul_acc_checked": (ci, [vp, vp, vp, vp, vp, sz, sz, sz, vp, vp]),
+    "fhe_tensor_product_checked": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, vp, vp]),
+    "fhe_ctx_inject_fault_pointwise": (ci, [vp, ci, C.c_longlong, ci]),
     "fhe_automorphism": (ci, [vp, vp, vp, vp, C.c_uint32, sz, sz, sz, vp]),
     "fhe_automorphism_ntt": (ci, [vp, vp, vp, ci, C.c_uint32, sz, vp]),
     "fhe_keyswitch_create": (ci, [vp, vp, ci, ci, ci, C.POINTER(vp)]),

@@ -1,4 +1,5 @@
-// capi_abft.cpp -- ABFT detector around the forward and inverse transforms and the negacyclic product (part of the C ABI of include/fhe_mi355x.h; shared pieces in capi_internal.hpp)
+// capi_abft.cpp -- ABFT detector around the forward and inverse transforms and the negacyclic product, and the residue-checked
+// element-wise products (part of the C ABI of include/fhe_mi355x.h; shared pieces in capi_internal.hpp)
 #include "capi_internal.hpp"
 
 extern "C" {
@@ -406,6 +407,86 @@ int fhe_ntt_forward_checked_phases(fhe_ctx *ctx, uint64_t *d_data, const fhe_ntt
     hipError_t e = launch_compare_phases(st, d_flags, m->sum_in.as<u64>(), m->sum_mid1.as<u64>(), tc, m->sum_mid2.as<u64>(), m->sum_out.as<u64>(), tr,
                                          t->d_lp.as<LimbParams>(), (u32)start_idx, (u32)limbs, (u32)units);
     if (e != hipSuccess) return hip_fail(e, "launch_compare_phases");
+    return FHE_OK;
+}
+
+// ---------------------------------------------------------------- residue-checked element-wise products
+// (pointwise_checked.hip, residue_check.hpp): no detector object, only the context's one-shot test hook is shared
+int fhe_ctx_inject_fault_pointwise(fhe_ctx *ctx, int point, long long idx, int bit)
+{
+    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
+    if (point < 0) {
+        ctx->pw_fault_point = -1;
+        return FHE_OK;
+    }
+    if (point > 3 || idx < 0 || bit < 0 || bit > 63) return fail(FHE_ERR_INVALID, "bad fault");
+    ctx->pw_fault_point = point;
+    ctx->pw_fault_idx = idx;
+    ctx->pw_fault_bit = bit;
+    return FHE_OK;
+}
+
+// takes the one-shot hook for a call of `elems` elements; point 3 (the running sum) exists only where the call has one
+static int take_pointwise_fault(fhe_ctx *ctx, bool has_sum, size_t elems, PwCheck &k)
+{
+    const int point = ctx->pw_fault_point;
+    ctx->pw_fault_point = -1;
+    if (point < 0) return FHE_OK;
+    if (point == 3 && !has_sum) return fail(FHE_ERR_UNSUPPORTED, "fault point 3 (the running sum) exists only for fhe_modmul_acc_checked and fhe_tensor_product_checked");
+    if ((size_t)ctx->pw_fault_idx >= elems) return fail(FHE_ERR_INVALID, "fault index outside the call's window");
+    k.fault_point = point;
+    k.fault_idx = (u64)ctx->pw_fault_idx;
+    k.fault_mask = (u64)1 << ctx->pw_fault_bit;
+    return FHE_OK;
+}
+
+static int modmul_checked(fhe_ctx *ctx, u64 *c, const u64 *a, const u64 *b, const fhe_ntt_tables *t, size_t n_poly, size_t limbs,
+                          size_t start_idx, uint32_t *d_flags, void *stream, bool acc)
+{
+    if (!ctx || !c || !a || !b || !d_flags) return fail(FHE_ERR_INVALID, "null argument");
+    int rc = check_range(t, n_poly, limbs, start_idx);
+    if (rc) return rc;
+    const size_t units = n_poly * limbs;
+    PwCheck k{d_flags, -1, 0, 0};
+    if ((rc = take_pointwise_fault(ctx, acc, units << t->log_n, k))) return rc;
+    if (!units) return FHE_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = pick(ctx, stream);
+    HIP_TRY(hipMemsetAsync(d_flags, 0, units * sizeof(u32), st));
+    PointwiseArgs p{c, a, b, t->d_lp.as<LimbParams>(), (u32)start_idx, (u32)limbs, (u32)units, (u32)limbs, t->log_n};
+    hipError_t e = launch_modmul_checked(st, p, acc, k);
+    if (e != hipSuccess) return hip_fail(e, "launch_modmul_checked");
+    return FHE_OK;
+}
+
+int fhe_modmul_checked(fhe_ctx *ctx, uint64_t *d_c, const uint64_t *d_a, const uint64_t *d_b, const fhe_ntt_tables *t, size_t n_poly,
+                       size_t limbs, size_t start_idx, uint32_t *d_flags, void *stream)
+{
+    return modmul_checked(ctx, d_c, d_a, d_b, t, n_poly, limbs, start_idx, d_flags, stream, false);
+}
+
+int fhe_modmul_acc_checked(fhe_ctx *ctx, uint64_t *d_c, const uint64_t *d_a, const uint64_t *d_b, const fhe_ntt_tables *t, size_t n_poly,
+                           size_t limbs, size_t start_idx, uint32_t *d_flags, void *stream)
+{
+    return modmul_checked(ctx, d_c, d_a, d_b, t, n_poly, limbs, start_idx, d_flags, stream, true);
+}
+
+int fhe_tensor_product_checked(fhe_ctx *ctx, uint64_t *d_d0, uint64_t *d_d1, uint64_t *d_d2, const uint64_t *d_a0, const uint64_t *d_a1,
+                               const uint64_t *d_b0, const uint64_t *d_b1, const fhe_ntt_tables *t, size_t limbs, size_t start_idx,
+                               uint32_t *d_flags, void *stream)
+{
+    if (!ctx || !d_d0 || !d_d1 || !d_d2 || !d_a0 || !d_a1 || !d_b0 || !d_b1 || !d_flags) return fail(FHE_ERR_INVALID, "null argument");
+    int rc = check_range(t, 1, limbs, start_idx);
+    if (rc) return rc;
+    PwCheck k{d_flags, -1, 0, 0};
+    if ((rc = take_pointwise_fault(ctx, true, limbs << t->log_n, k))) return rc;
+    if (!limbs) return FHE_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = pick(ctx, stream);
+    HIP_TRY(hipMemsetAsync(d_flags, 0, limbs * 3 * sizeof(u32), st));
+    const TensorArgs ta{d_d0, d_d1, d_d2, d_a0, d_a1, d_b0, d_b1, t->d_lp.as<LimbParams>(), (u32)start_idx, (u32)limbs, t->log_n};
+    hipError_t e = launch_tensor_checked(st, ta, k);
+    if (e != hipSuccess) return hip_fail(e, "launch_tensor_checked");
     return FHE_OK;
 }
 

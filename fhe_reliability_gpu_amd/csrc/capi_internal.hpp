@@ -110,6 +110,8 @@ struct fhe_ctx {
     u32 pfault_block = 0, pfault_word = 0;      // (fhe_ctx_inject_fault_in_pass): workgroup and LDS word
     int pm_fault_point = -1, pm_fault_bit = 0;  // one-shot bit flip inside the next fhe_polymul_checked (fhe_ctx_inject_fault_polymul):
     long long pm_fault_idx = 0;                 // where (point 0-3), word of the call's [poly][limb][N] window, bit
+    int pw_fault_point = -1, pw_fault_bit = 0;  // one-shot bit flip inside the next residue-checked pointwise call
+    long long pw_fault_idx = 0;                 // (fhe_ctx_inject_fault_pointwise): point 0-3, element of the call's window, bit
     int geo = 1;           // column-tile geometry of the two-launch path (ntt_launch.hpp)
     bool resident = false; // 2^13 / 2^14: one LDS-resident pass instead of two launches (opt-in, see ntt_plan.hpp)
     int pingpong = -1;        // "ntt_pingpong": two-launch transforms hand over through a per-stream scratch buffer (both launches out of

@@ -185,6 +185,24 @@ class NttTables:
         f = lib.fhe_modmul_acc if acc else lib.fhe_modmul
         check(f(self.eng._h, c.ptr, a.ptr, b.ptr, self._h, n_poly, limbs, start, stream))
 
+    def modmul_checked(self, c: DeviceArray, a: DeviceArray, b: DeviceArray, limbs=None, start=0, n_poly=1, acc=False,
+                       stream=None) -> np.ndarray:
+        """``modmul`` with every word checked; the words are ``modmul``'s, bit for bit.  Returns flags[poly * limbs + l] (uint32):
+        1 = residue identity a b (+ o) = k q + c failed modulo 2^32 - 1, 2 = a result or a reduction intermediate out of its
+        window, 4 = an operand (or, with ``acc``, the old word) not canonical, which the check cannot cover.
+
+        The per-element protections of rfhe_framewk/src/barrett_final.py (Intra, Range, Sum) in one identity, with a 32-bit
+        fold instead of the reference's 4-10-bit ones; the fold checksum that four_step_ntt_protected.py:102-120 puts on the
+        element-wise stage of its pipeline, here per word (residue_check.hpp)."""
+        limbs = len(self) - start if limbs is None else limbs
+        n = n_poly * limbs
+        flags = self.eng.alloc((n + 1) // 2)      # uint32 flags packed in a u64 buffer
+        f = lib.fhe_modmul_acc_checked if acc else lib.fhe_modmul_checked
+        check(f(self.eng._h, c.ptr, a.ptr, b.ptr, self._h, n_poly, limbs, start, flags.ptr, stream))
+        if stream is not None:
+            self.eng.sync(stream)
+        return flags.download().view(np.uint32)[:n].copy()
+
     def polymul(self, c: DeviceArray, a: DeviceArray, b: DeviceArray, limbs=None, start=0, n_poly=1, stream=None):
         limbs = len(self) - start if limbs is None else limbs
         check(lib.fhe_polymul(self.eng._h, c.ptr, a.ptr, b.ptr, self._h, n_poly, limbs, start, stream))
@@ -494,6 +512,19 @@ class KeySwitch:
         d = [self._out(self.L) for _ in range(3)]
         check(lib.fhe_tensor_product(self.eng._h, d[0].ptr, d[1].ptr, d[2].ptr, a0.ptr, a1.ptr, b0.ptr, b1.ptr, self.t._h, self.L, 0, stream))
         return tuple(d)
+
+    def tensor_checked(self, a0: DeviceArray, a1: DeviceArray, b0: DeviceArray, b1: DeviceArray, stream=None):
+        """``tensor`` with every word checked: (d0, d1, d2, flags[L, 3]), flags[l, part] for d0 / d1 / d2 with the bits of
+        ``NttTables.modmul_checked``.  The words are ``tensor``'s, bit for bit (FP64 terms on limbs below 2^50, Barrett above);
+        the residue identity covers the lazy cross term d1 = a0 b1 + a1 b0 as one sum, the reference's Sum check
+        (rfhe_framewk/src/barrett_final.py) and the element-wise fold check of four_step_ntt_protected.py:102-120."""
+        d = [self._out(self.L) for _ in range(3)]
+        flags = self.eng.alloc((3 * self.L + 1) // 2)
+        check(lib.fhe_tensor_product_checked(self.eng._h, d[0].ptr, d[1].ptr, d[2].ptr, a0.ptr, a1.ptr, b0.ptr, b1.ptr, self.t._h, self.L, 0,
+                                             flags.ptr, stream))
+        if stream is not None:
+            self.eng.sync(stream)
+        return d[0], d[1], d[2], flags.download().view(np.uint32)[: 3 * self.L].reshape(self.L, 3).copy()
 
     def relinearize(self, d0: DeviceArray, d1: DeviceArray, d2: DeviceArray, relin_key: DeviceArray, stream=None):
         """``relinearize_inplace`` (dotprod_test.cu:114)."""

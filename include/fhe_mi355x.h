@@ -441,6 +441,41 @@ int fhe_ctx_inject_fault_in_pass(fhe_ctx *ctx, int pass, uint32_t workgroup, uin
  * the in-flight analogue of the host-side flips of reliability_test/ntt_test.cu:104-135. */
 int fhe_ctx_inject_fault(fhe_ctx *ctx, long long idx, int bit);
 
+/* ---- residue-checked element-wise products (SURVEY section 8 f3, next to the detector) -------------------------------------
+ * The protections of rfhe_framewk/src/barrett_final.{py,cpp} (Intra: fold residue of a, b and the product; Range: windows on
+ * the Barrett intermediates; Sum: reduced against unreduced sum) for the coefficient-wise products, which a weighted checksum
+ * cannot cover cheaply.  For canonical operands (a, b < q < 2^61) every product kernel forms a quotient k and a word c with
+ *     a b (+ o, the old word when accumulating) = k q + c,   0 <= c < q,
+ * and the checked calls verify, per word, with 32-bit lane arithmetic independent of the 64-bit multiply that made c,
+ *     r(c) + r(k) r(q) == r(a) r(b) (+ r(o))  (mod m = 2^32 - 1),   r(x) = x mod m folded from the 32-bit halves,
+ * plus the window c < q (for Barrett the same compare as the pre-subtraction window; for the FP64 path also the running sum and
+ * the value after the reduction).  A single-bit flip of the product, of k or of c changes one side by 2^j, never 0 mod m; for
+ * the five primes dividing m (3, 5, 17, 257, 65537) a change of k by a multiple of m / q is left to the window.  A consistent
+ * shift (k - d, value + d q) gives the right word and raises nothing.  Not covered: faults already in the operands, and a
+ * register fault on a or b before both the product and its residue have read it.
+ * Output words are those of fhe_modmul / fhe_modmul_acc / fhe_tensor_product, bit for bit, for every input (Barrett for the
+ * modmul pair, the per-limb FP64 / U64 choice for the tensor product); aliasing and argument rules are theirs as well.
+ * Flags (zeroed on `stream` by the call; a failing word ORs its bits in with a global atomic):
+ *   modmul: d_flags[poly * limbs + l];  tensor product: d_flags[3 * l + part], part 0 / 1 / 2 = d0 / d1 / d2
+ *   bit 1  residue identity failed;  bit 2  a result or a reduction intermediate out of its window;
+ *   bit 4  an operand (or, accumulating, the old word) not canonical -- that word cannot be checked, it raises bit 4 alone
+ *          and is still the unchecked call's word.
+ * No detector object: only q mod m per limb, formed in the kernel.  Calls on different streams may run concurrently. */
+int fhe_modmul_checked(fhe_ctx *ctx, uint64_t *d_c, const uint64_t *d_a, const uint64_t *d_b, const fhe_ntt_tables *t,
+                       size_t n_poly, size_t limbs, size_t start_idx, uint32_t *d_flags, void *stream);
+int fhe_modmul_acc_checked(fhe_ctx *ctx, uint64_t *d_c, const uint64_t *d_a, const uint64_t *d_b, const fhe_ntt_tables *t,
+                           size_t n_poly, size_t limbs, size_t start_idx, uint32_t *d_flags, void *stream);
+int fhe_tensor_product_checked(fhe_ctx *ctx, uint64_t *d_d0, uint64_t *d_d1, uint64_t *d_d2, const uint64_t *d_a0,
+                               const uint64_t *d_a1, const uint64_t *d_b0, const uint64_t *d_b1, const fhe_ntt_tables *t,
+                               size_t limbs, size_t start_idx, uint32_t *d_flags, void *stream);
+/* Test hook: XOR bit `bit` once, in the next checked pointwise call on this context, at element `idx` of the call's
+ * [poly][limb][N] window ([limb][N] for the tensor product, where it lands in d1, the two-term sum).  point 0: the product
+ * before reduction (U64: low word of the 128-bit product; FP64: h); 1: the quotient estimate of the reduction that produces the
+ * word; 2: the result word before its range check and store; 3: the running sum before its final reduction -- only for
+ * fhe_modmul_acc_checked and fhe_tensor_product_checked, elsewhere the call returns FHE_ERR_UNSUPPORTED and launches nothing.
+ * One shot (an unsupported or out-of-window fault is used up as well); point < 0 clears it. */
+int fhe_ctx_inject_fault_pointwise(fhe_ctx *ctx, int point, long long idx, int bit);
+
 /* ---- fault injection ---------------------------------------------------------------- */
 /* _flip_bit_kernel<<<1,1>>> (reliability_test/dotprod_test.cu:31-33,55): data[idx] ^= 1 << bit */
 int fhe_flip_bit(fhe_ctx *ctx, uint64_t *d_data, uint64_t idx, int bit, void *stream);
