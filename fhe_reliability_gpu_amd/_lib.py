@@ -77,6 +77,9 @@ _SIG = {
     "fhe_baseconv_destroy": (ci, [vp]),
     "fhe_baseconv_exact": (ci, [vp, vp, vp, vp, sz, vp]),
     "fhe_baseconv_fast": (ci, [vp, vp, vp, vp, sz, vp]),
+    "fhe_baseconv_exact_checked": (ci, [vp, vp, vp, vp, sz, vp, vp]),
+    "fhe_baseconv_fast_checked": (ci, [vp, vp, vp, vp, sz, vp, vp]),
+    "fhe_ctx_inject_fault_baseconv": (ci, [vp, ci, ci, C.c_longlong, ci]),
     "fhe_crt_garner": (ci, [vp, vp, vp, vp, p64, ci, sz, vp]),
     "fhe_bsgs_hadamard": (ci, [vp, vp, vp, vp, ci, ci, u64, vp]),
     "fhe_flip_bit": (ci, [vp, vp, u64, ci, vp]),

@@ -1,5 +1,23 @@
 // capi_baseconv.cpp -- RNS base conversion, Garner CRT, BSGS Hadamard, bit flip (part of the C ABI of include/fhe_mi355x.h; shared pieces in capi_internal.hpp)
 #include "capi_internal.hpp"
+#include "baseconv_check.hpp"
+
+// takes the one-shot hook of fhe_ctx_inject_fault_baseconv for a call with `units` flag words; terms(unit) = number of terms
+// of that unit's sum (the running-sum point needs two)
+template <class Terms>
+static int take_baseconv_fault(fhe_ctx *ctx, int units, size_t N, Terms terms, BcCheck &k)
+{
+    const int point = ctx->bc_fault_point;
+    ctx->bc_fault_point = -1;
+    if (point < 0) return FHE_OK;
+    if (ctx->bc_fault_unit >= units || (size_t)ctx->bc_fault_coeff >= N) return fail(FHE_ERR_INVALID, "fault unit or coefficient outside the call");
+    if (!bc_point_exists(point, terms(ctx->bc_fault_unit))) return fail(FHE_ERR_UNSUPPORTED, "fault point 3 (the running sum) needs a sum of two terms: not on digit 0, not on a one-limb base");
+    k.fault_point = point;
+    k.fault_unit = (u32)ctx->bc_fault_unit;
+    k.fault_coeff = (u64)ctx->bc_fault_coeff;
+    k.fault_mask = (u64)1 << ctx->bc_fault_bit;
+    return FHE_OK;
+}
 
 extern "C" {
 
@@ -72,6 +90,22 @@ int fhe_baseconv_create(fhe_ctx *ctx, const uint64_t *mod_in, int m, const uint6
     HIP_TRY(p->fp_out.upload(fpo));
     HIP_TRY(p->fast_coef.upload(fc));
     HIP_TRY(p->fast_shoup.upload(fs));
+    // the residue-checked conversion (baseconv_checked.hip) runs the Shoup form on every plan: FP64 plans get dig / hor once more
+    // as Shoup pairs (the double in Tw::a of an ArithF64 constant is the integer itself, below 2^50)
+    if (f64) {
+        std::vector<Tw> sd((size_t)m * m, Tw{0, 0}), sh((size_t)m * k);
+        for (int l = 0; l < m; l++) {
+            for (int j = l; j < m; j++) sd[(size_t)l * m + j] = ArithU64::encode((u64)u64_bits_to_double(dig[(size_t)l * m + j].a), mi[j]);
+            for (int o = 0; o < k; o++) sh[(size_t)l * k + o] = ArithU64::encode((u64)u64_bits_to_double(hor[(size_t)l * k + o].a), mo[o]);
+        }
+        HIP_TRY(p->chk_dig.upload(sd));
+        HIP_TRY(p->chk_hor.upload(sh));
+        p->shoup_dig = p->chk_dig.as<Tw>();
+        p->shoup_hor = p->chk_hor.as<Tw>();
+    } else {
+        p->shoup_dig = p->dig.as<Tw>();
+        p->shoup_hor = p->hor.as<Tw>();
+    }
     if (m <= 16) {
         std::vector<Tw> head((size_t)m * m + m + (m + 1) / 2, Tw{0, 0}), outs((size_t)k * (m + 2), Tw{0, 0});
         for (int i = 0; i < m * m; i++) head[i] = dig[i];
@@ -130,6 +164,64 @@ int fhe_baseconv_fast(fhe_ctx *ctx, uint64_t *d_out, const uint64_t *d_in, const
     HIP_TRY(hipSetDevice(ctx->device));
     hipError_t e = launch_bconv_fast(pick(ctx, stream), d_out, d_in, p->dev, N);
     if (e != hipSuccess) return hip_fail(e, "launch_bconv_fast");
+    return FHE_OK;
+}
+
+// ---------------------------------------------------------------- residue-checked base conversion
+// (baseconv_checked.hip, baseconv_check.hpp): no detector object, only the context's one-shot test hook is shared
+int fhe_ctx_inject_fault_baseconv(fhe_ctx *ctx, int point, int unit, long long coeff, int bit)
+{
+    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
+    if (point < 0) {
+        ctx->bc_fault_point = -1;
+        return FHE_OK;
+    }
+    if (point > 3 || unit < 0 || coeff < 0 || bit < 0 || bit > 63) return fail(FHE_ERR_INVALID, "bad fault");
+    ctx->bc_fault_point = point;
+    ctx->bc_fault_unit = unit;
+    ctx->bc_fault_coeff = coeff;
+    ctx->bc_fault_bit = bit;
+    return FHE_OK;
+}
+
+int fhe_baseconv_exact_checked(fhe_ctx *ctx, uint64_t *d_out, const uint64_t *d_in, const fhe_baseconv *p, size_t N, uint32_t *d_flags,
+                               void *stream)
+{
+    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
+    if (!d_out || !d_in || !p || !d_flags) {
+        ctx->bc_fault_point = -1;       // (a refused call uses the hook up as well)
+        return fail(FHE_ERR_INVALID, "null argument");
+    }
+    BcCheck k{d_flags, -1, 0, 0, 0};
+    const int m = p->m, units = p->m + p->k;
+    int rc = take_baseconv_fault(ctx, units, N, [&](int unit) { return unit < m ? unit + 1 : m; }, k);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = pick(ctx, stream);
+    HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)units * sizeof(u32), st));
+    const BcCheckedJob cj{BcJob{p->dev, d_in, d_out, 0xFFFFFFFFu, 0u, nullptr}, p->shoup_dig, p->shoup_hor, k};
+    hipError_t e = launch_baseconv_exact_checked(st, cj, N);
+    if (e != hipSuccess) return hip_fail(e, "launch_baseconv_exact_checked");
+    return FHE_OK;
+}
+
+int fhe_baseconv_fast_checked(fhe_ctx *ctx, uint64_t *d_out, const uint64_t *d_in, const fhe_baseconv *p, size_t N, uint32_t *d_flags,
+                              void *stream)
+{
+    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
+    if (!d_out || !d_in || !p || !d_flags) {
+        ctx->bc_fault_point = -1;
+        return fail(FHE_ERR_INVALID, "null argument");
+    }
+    BcCheck k{d_flags, -1, 0, 0, 0};
+    int rc = take_baseconv_fault(ctx, p->k, N, [&](int) { return p->m; }, k);
+    if (!p->fast_ok) return fail(FHE_ERR_UNSUPPORTED, "unreduced sum would exceed 64 bits (m * max q >= 2^64)");
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = pick(ctx, stream);
+    HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)p->k * sizeof(u32), st));
+    hipError_t e = launch_bconv_fast_checked(st, d_out, d_in, p->dev, k, N);
+    if (e != hipSuccess) return hip_fail(e, "launch_bconv_fast_checked");
     return FHE_OK;
 }
 

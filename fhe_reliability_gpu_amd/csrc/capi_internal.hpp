@@ -82,6 +82,8 @@ struct fhe_baseconv {
     int m = 0, k = 0;
     bool fast_ok = true;
     DevBuf mod_in, mod_out, dig, hor, fp_in, fp_out, fast_coef, fast_shoup, img_head, img_out, rows_id;
+    DevBuf chk_dig, chk_hor;            // FP64 plans: dig / hor once more as Shoup pairs, for the residue-checked conversion
+    const fhe::Tw *shoup_dig = nullptr, *shoup_hor = nullptr;   // the Shoup-pair tables (integer plans: dig / hor themselves)
     BaseConvPlanDev dev{};
 };
 
@@ -112,6 +114,8 @@ struct fhe_ctx {
     long long pm_fault_idx = 0;                 // where (point 0-3), word of the call's [poly][limb][N] window, bit
     int pw_fault_point = -1, pw_fault_bit = 0;  // one-shot bit flip inside the next residue-checked pointwise call
     long long pw_fault_idx = 0;                 // (fhe_ctx_inject_fault_pointwise): point 0-3, element of the call's window, bit
+    int bc_fault_point = -1, bc_fault_unit = 0, bc_fault_bit = 0;   // one-shot bit flip inside the next residue-checked base
+    long long bc_fault_coeff = 0;                                   // conversion (fhe_ctx_inject_fault_baseconv)
     int geo = 1;           // column-tile geometry of the two-launch path (ntt_launch.hpp)
     bool resident = false; // 2^13 / 2^14: one LDS-resident pass instead of two launches (opt-in, see ntt_plan.hpp)
     int pingpong = -1;        // "ntt_pingpong": two-launch transforms hand over through a per-stream scratch buffer (both launches out of

@@ -363,6 +363,28 @@ class BaseConv:
     def fast(self, out: DeviceArray, inp: DeviceArray, N: int, stream=None):
         check(lib.fhe_baseconv_fast(self.eng._h, out.ptr, inp.ptr, self._h, N, stream))
 
+    def _checked(self, f, units, out, inp, N, stream):
+        flags = self.eng.alloc((units + 1) // 2)      # uint32 flags packed in a u64 buffer
+        check(f(self.eng._h, out.ptr, inp.ptr, self._h, N, flags.ptr, stream))
+        if stream is not None:
+            self.eng.sync(stream)
+        return flags.download().view(np.uint32)[:units].copy()
+
+    def exact_checked(self, out: DeviceArray, inp: DeviceArray, N: int, stream=None) -> np.ndarray:
+        """``exact`` with every mixed-radix digit and every output word checked; the words are ``exact``'s, bit for bit.
+        Returns flags (uint32) of shape ``(m + k,)``: ``flags[j]`` the digit recurrence of input limb j, ``flags[m + o]`` output
+        limb o.  1 = residue identity (r_j A_j - sum c_l D_lj = K p_j + c_j, sum c_l E_lo = K q_o + out_o) failed modulo
+        2^32 - 1, 2 = a digit or word out of its window, 4 = an input word >= p_j, which is folded but not checked.
+
+        The stage motivation/baseConv.py perturbs, with the fold-residue and range detectors of
+        rfhe_framewk/src/barrett_final.py carried through the sums (baseconv_check.hpp)."""
+        return self._checked(lib.fhe_baseconv_exact_checked, self.m + self.k, out, inp, N, stream)
+
+    def fast_checked(self, out: DeviceArray, inp: DeviceArray, N: int, stream=None) -> np.ndarray:
+        """``fast`` with every output word checked (sum_j in_j C_jo = K q_o + out_o modulo 2^32 - 1, every reduced term below
+        q_o, the word below m q_o); flags of shape ``(k,)``, bits as ``exact_checked`` (4 is never raised)."""
+        return self._checked(lib.fhe_baseconv_fast_checked, self.k, out, inp, N, stream)
+
     def __del__(self):
         try:
             if self._h and self.eng._h:

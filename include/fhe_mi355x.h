@@ -476,6 +476,44 @@ int fhe_tensor_product_checked(fhe_ctx *ctx, uint64_t *d_d0, uint64_t *d_d1, uin
  * One shot (an unsupported or out-of-window fault is used up as well); point < 0 clears it. */
 int fhe_ctx_inject_fault_pointwise(fhe_ctx *ctx, int point, long long idx, int bit);
 
+/* ---- residue-checked base conversion --------------------------------------------------------------------------------------
+ * fhe_baseconv_exact / fhe_baseconv_fast with every mixed-radix digit and every output word checked: the stage that
+ * motivation/baseConv.py perturbs (one input residue, then what the conversion does to it) and rfhe_framewk/src/baseConv.{py,cpp,cu}
+ * compute, protected with the fold-residue and range detectors of rfhe_framewk/src/barrett_final.{py,cpp} carried through the sums.
+ * A base conversion is not linear over the coefficient index, so no NTT checksum reaches it, and one wrong digit corrupts every
+ * output limb of its coefficient.  Over the integers
+ *     digit j    r_j A_j - sum_{l<j} c_l D_lj = K_j p_j + c_j      0 <= c_j < p_j   (K_j signed)
+ *     output o   sum_l c_l E_lo               = K_o q_o + out_o    0 <= out_o < q_o
+ *     fast o     sum_j in_j C_jo              = K_o q_o + out_o    every reduced term < q_o, out_o < m q_o (the sum is not reduced)
+ * and the checked calls verify each identity modulo 2^32 - 1 with 32-bit lane arithmetic independent of the 64-bit multiplies
+ * that made the word (the residue of K is carried, K itself can pass 64 bits), plus the windows on the right.
+ * Words: d_out is fhe_baseconv_exact's / fhe_baseconv_fast's, bit for bit, for every input including words >= p_j, on both kinds
+ * of plan (all moduli below 2^50, or not) and for every m, k from 1 to 64; canonical digits and outputs are unique, and the
+ * checked kernels form them as Shoup products on every plan.  Argument rules, FHE_ERR_UNSUPPORTED of the fast form on a plan
+ * whose unreduced sum would pass 64 bits, and the limits are the unchecked calls'.
+ * Flags (zeroed on `stream` by the call; a failing coefficient ORs its bits in with a global atomic):
+ *   exact: d_flags[j], j < m: the digit recurrence of input limb j;  d_flags[m + o]: output limb o.   fast: d_flags[o].
+ *   bit 1  residue identity failed;  bit 2  a digit, word or reduced term out of its window;
+ *   bit 4  (exact only) input word >= p_j on digit unit j: folded, not checked, raised alone; the word is still the unchecked
+ *          call's.  The fast form takes any 64-bit word (its Shoup quotient fits 64 bits) and never raises bit 4.
+ * Localisation: a fault raises the flag of the unit it hit and no other.  A wrong digit changes the later digits and all outputs
+ * consistently, so their units stay clear (the rule of the per-phase NTT flags).
+ * Not covered: faults already in the input, a register fault on a digit between its check and a later use, faults in the plan's
+ * constant tables.  No detector object and no scratch: calls on different streams may run concurrently. */
+int fhe_baseconv_exact_checked(fhe_ctx *ctx, uint64_t *d_out, const uint64_t *d_in, const fhe_baseconv *p, size_t N,
+                               uint32_t *d_flags /* [m + k] */, void *stream);
+int fhe_baseconv_fast_checked(fhe_ctx *ctx, uint64_t *d_out, const uint64_t *d_in, const fhe_baseconv *p, size_t N,
+                              uint32_t *d_flags /* [k] */, void *stream);
+/* Test hook: XOR bit `bit` once, in the next checked base conversion on this context, in coefficient `coeff` of unit `unit` (index
+ * into that call's flags array).  point 0: low word of the 128-bit product of the unit's first term; 1: the Shoup quotient of the
+ * reduction that completes the digit / word (its last term; fast form: the first term's); 2: the digit / word before its window
+ * check and every later use; 3: the running sum with its last term folded in, before the conditional +- q that closes it (fast
+ * form: the sum of all terms but the last) -- needs two terms: on digit 0, or on any output of a one-limb base, the call returns
+ * FHE_ERR_UNSUPPORTED; a unit or coefficient outside the call returns FHE_ERR_INVALID.  Either way nothing is launched.  Where
+ * the outputs are sliced over workgroups, every workgroup sees the same wrong digit.  One shot (a refused call uses it up as
+ * well); point < 0 clears it. */
+int fhe_ctx_inject_fault_baseconv(fhe_ctx *ctx, int point, int unit, long long coeff, int bit);
+
 /* ---- fault injection ---------------------------------------------------------------- */
 /* _flip_bit_kernel<<<1,1>>> (reliability_test/dotprod_test.cu:31-33,55): data[idx] ^= 1 << bit */
 int fhe_flip_bit(fhe_ctx *ctx, uint64_t *d_data, uint64_t idx, int bit, void *stream);
