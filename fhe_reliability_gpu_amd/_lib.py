@@ -111,6 +111,11 @@ _SIG = {
     "fhe_keyswitch_shard_finish": (ci, [vp, vp, vp, vp, vp, vp, vp]),
     "fhe_keyswitch_apply": (ci, [vp, vp, vp, vp, vp, vp, vp]),
     "fhe_rotate": (ci, [vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp]),
+    "fhe_keyswitch_checked_layout": (ci, [vp, C.POINTER(ci)]),
+    "fhe_keyswitch_apply_checked": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "fhe_relinearize_checked": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "fhe_rotate_checked": (ci, [vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp]),
+    "fhe_ctx_inject_fault_keyswitch": (ci, [vp, ci, ci, ci, C.c_longlong, ci]),
     "fhe_galois_key_prepare": (ci, [vp, vp, vp, vp, C.c_uint32, vp]),
     "fhe_rotate_hoisted": (ci, [vp, vp, C.POINTER(vp), C.POINTER(vp), vp, vp, C.POINTER(C.c_uint32), C.POINTER(vp), sz, vp]),
     "fhe_rotate_hoisted_shard_begin": (ci, [vp, vp, vp, vp]),

@@ -116,6 +116,8 @@ struct fhe_ctx {
     long long pw_fault_idx = 0;                 // (fhe_ctx_inject_fault_pointwise): point 0-3, element of the call's window, bit
     int bc_fault_point = -1, bc_fault_unit = 0, bc_fault_bit = 0;   // one-shot bit flip inside the next residue-checked base
     long long bc_fault_coeff = 0;                                   // conversion (fhe_ctx_inject_fault_baseconv)
+    int ksc_fault_stage = -1, ksc_fault_point = 0, ksc_fault_unit = 0, ksc_fault_bit = 0;   // one-shot bit flip inside the next checked key
+    long long ksc_fault_coeff = 0;                                                         // switch (fhe_ctx_inject_fault_keyswitch)
     int geo = 1;           // column-tile geometry of the two-launch path (ntt_launch.hpp)
     bool resident = false; // 2^13 / 2^14: one LDS-resident pass instead of two launches (opt-in, see ntt_plan.hpp)
     int pingpong = -1;        // "ntt_pingpong": two-launch transforms hand over through a per-stream scratch buffer (both launches out of
@@ -208,6 +210,9 @@ struct fhe_keyswitch {
     u64 *hsp_cur() const { return (cur ? hsp2 : hsp).as<u64>(); }
     DevBuf hsp, hdown_rows, hdown_jobs; // hoisted rotations (allocated on first use): [2][K][N] special limbs of sigma(sums) in coefficient form, the mod-down jobs that read them
     u64 t_inv_qlast = 0;               // plain_modulus^-1 mod q_{L-1} (BGV)
+    // checked key switch (capi_keyswitch_checked.cpp), built at the first checked call: the digit extensions' flags in the order of
+    // their conversion jobs, where each goes in the [dnum][M] limb order, and the partial sums of the transforms' detector
+    DevBuf chk_bc_flags, chk_bc_map, chk_sum_in, chk_sum_out;
     ~fhe_keyswitch()
     {
         for (auto *b : up) fhe_baseconv_destroy(b);

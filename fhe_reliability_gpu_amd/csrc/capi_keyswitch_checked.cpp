@@ -1,0 +1,354 @@
+// capi_keyswitch_checked.cpp -- hybrid key switch, relinearisation and rotation with every stage checked and one flag word per
+// (stage, unit) (part of the C ABI of include/fhe_mi355x.h; shared pieces in capi_internal.hpp).
+//
+// The launch list is the "plain" route of capi_keyswitch.cpp with each launch replaced by its checked form -- none of the unchecked
+// call's fusions (k_ks_rowmac, the Galois map and the one-limb conversions riding on loads, the unit-list column pass, the fused
+// k_ntt_row_subscale tail):
+//   0  copy of d_c into the plan's coefficient buffer, checked INTT of its L limbs in place              (launch_ntt_checked, inverse)
+//   1  per digit one checked exact conversion into ext, then one scatter of the flags into limb order    (launch_baseconv_exact_checked)
+//   2  checked forward transform of ext: the K special rows of all digits in one launch per run of an arithmetic path, the
+//      ciphertext rows per digit and contiguous run of rows (the digit's own limbs are skipped)          (launch_ntt_checked)
+//   3  inner product with both key halves                                                                (launch_ks_mac_checked)
+//   4  checked INTT of the K special rows of both halves of acc, in place                                (launch_ntt_checked, inverse)
+//   5  per half one checked exact conversion P -> Q into conv                                            (launch_baseconv_exact_checked)
+//   6  checked forward transform of conv                                                                 (launch_ntt_checked)
+//   7  tail (acc - conv) P^-1 (+ addends)                                                                (launch_sub_scale_checked)
+// Each transform stage ends with launch_compare_sums on its units.  Every stage yields canonical residues and canonical residues are
+// unique, so the outputs are the unchecked call's words whatever its launch list was.
+#include "capi_internal.hpp"
+#include "keyswitch_check.hpp"
+
+namespace {
+
+struct KscLayout {
+    int off[8], total;
+};
+KscLayout ksc_layout(const fhe_keyswitch *p)
+{
+    const int L = p->L, K = p->K, M = L + K, d = p->dnum;
+    const int n[8] = {L, d * M, d * M, 2 * M, 2 * K, 2 * (K + L), 2 * L, 2 * L};
+    KscLayout l{};
+    for (int s = 0; s < 8; s++) {
+        l.off[s] = l.total;
+        l.total += n[s];
+    }
+    return l;
+}
+
+// slots of the plan's scratch sums, one per (polynomial, row) a stage's transforms address: stage 2 the dnum x M rows of ext, stage 4
+// rows L .. M-1 of both halves of acc ([2][M]: up to slot 2 M - 1), stage 6 [2][L], stage 0 [L]
+size_t ksc_slots(const fhe_keyswitch *p) { return (size_t)std::max(p->dnum, 2) * (p->L + p->K); }
+
+struct KscFault {
+    int stage = -1, point = 0, unit = 0, bit = 0;
+    long long coeff = 0;
+};
+
+// the transforms of one checked stage: rows [row0, row0 + count) of n_poly polynomials `stride` rows apart inside base, row r on
+// table limb tl0 + (r - row0); the sums of (polynomial, row) live at slot sum0 + polynomial * stride + row
+struct KscRows {
+    u64 *base;
+    u32 row0, tl0, count, n_poly, stride, sum0;
+};
+
+struct KscNtt {
+    const fhe_keyswitch *p;
+    const fhe_abft *a;
+    hipStream_t st;
+    u32 tin, tout;
+    bool inverse;
+    u64 *sum_in() const { return p->chk_sum_in.as<u64>(); }
+    u64 *sum_out() const { return p->chk_sum_out.as<u64>(); }
+
+    int launch(const KscRows &r, int which) const
+    {
+        const fhe_ntt_tables *t = p->t;
+        const size_t N = (size_t)1 << p->log_n;
+        return for_each_run(t, r.count, r.tl0, [&](size_t off, size_t len, int path) -> int {
+            PassArgs pa{r.base + (r.row0 + off) * N, t->d_lp.as<LimbParams>(), (u32)(r.tl0 + off), (u32)len, (u32)(r.n_poly * len), r.stride, nullptr};
+            // the launch addresses slots slot + polynomial * stride + l, l < len
+            const size_t slot = (size_t)r.sum0 + r.row0 + off;
+            if (slot + (size_t)(r.n_poly - 1) * r.stride + len > ksc_slots(p)) return fail(FHE_ERR_INVALID, "checked key switch: a transform's sums lie outside the plan's scratch");
+            hipError_t e = launch_ntt_checked(st, pa, a->win.as<Tw>(), a->wout.as<Tw>(), a->wout8.as<u64>(), sum_in() + slot * tin, sum_out() + slot * tout,
+                                              p->log_n, path, which, inverse);
+            return e == hipSuccess ? FHE_OK : hip_fail(e, "launch_ntt_checked");
+        });
+    }
+    // all launches of the stage; flip != nullptr (test hook, two-launch sizes): that word is flipped between the stage's two launches
+    int run(const std::vector<KscRows> &rows, u64 *flip, int bit) const
+    {
+        int rc;
+        if (!flip) {
+            for (const KscRows &r : rows)
+                if ((rc = launch(r, -1))) return rc;
+            return FHE_OK;
+        }
+        for (const KscRows &r : rows)
+            if ((rc = launch(r, 0))) return rc;
+        hipError_t e = launch_flip_bit(st, flip, 0, bit);
+        if (e != hipSuccess) return hip_fail(e, "launch_flip_bit");
+        for (const KscRows &r : rows)
+            if ((rc = launch(r, 1))) return rc;
+        return FHE_OK;
+    }
+    // flags[i] = sums of slot (slot0 + i) differ, i < units, unit i on table limb limb0 + i % limbs
+    int compare(u32 *flags, u32 slot0, u32 limb0, u32 limbs, u32 units) const
+    {
+        if ((size_t)slot0 + units > ksc_slots(p)) return fail(FHE_ERR_INVALID, "checked key switch: a comparison's sums lie outside the plan's scratch");
+        hipError_t e = launch_compare_sums(st, flags, sum_in() + (size_t)slot0 * tin, tin, sum_out() + (size_t)slot0 * tout, tout,
+                                           p->t->d_lp.as<LimbParams>(), limb0, limbs, units);
+        return e == hipSuccess ? FHE_OK : hip_fail(e, "launch_compare_sums");
+    }
+};
+
+// the flag map of stage 1, its job-order scratch and the detector's partial sums, once per plan
+int ksc_prepare(fhe_keyswitch *p)
+{
+    if (p->chk_bc_map.p) return FHE_OK;
+    u32 tf[2], ti[2];
+    ntt_checked_tiles(p->log_n, &tf[0], &tf[1], false);
+    ntt_checked_tiles(p->log_n, &ti[0], &ti[1], true);
+    const size_t sum_bytes = ksc_slots(p) * 8 * std::max(std::max(tf[0], tf[1]), std::max(ti[0], ti[1]));
+    HIP_TRY(p->chk_sum_in.alloc(sum_bytes));
+    HIP_TRY(p->chk_sum_out.alloc(sum_bytes));
+    const int L = p->L, M = L + p->K;
+    std::vector<u32> map((size_t)p->dnum * M);
+    for (int d = 0; d < p->dnum; d++) {
+        const int lo = d * p->alpha, hi = std::min(L, lo + p->alpha), m = hi - lo;
+        for (int j = 0; j < M; j++) {
+            const int ju = j >= lo && j < hi ? j - lo : m + (j < lo ? j : j - m);      // unit of limb j in the conversion job's flags
+            map[(size_t)d * M + ju] = (u32)(d * M + j);
+        }
+    }
+    HIP_TRY(p->chk_bc_flags.alloc(map.size() * sizeof(u32)));
+    HIP_TRY(p->chk_bc_map.upload(map));
+    return FHE_OK;
+}
+
+int keyswitch_checked(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk,
+                      const uint64_t *d_add0, const uint64_t *d_add1, const fhe_abft *a, uint32_t *d_flags, hipStream_t st, const KscFault &ft)
+{
+    const fhe_ntt_tables *t = p->t;
+    const int L = p->L, K = p->K, M = L + K, dnum = p->dnum, logn = p->log_n;
+    const size_t N = (size_t)1 << logn;
+    const KscLayout lay = ksc_layout(p);
+    const LimbParams *lp = t->d_lp.as<LimbParams>();
+    u64 *coef = p->coef.as<u64>(), *ext = p->ext.as<u64>(), *acc = p->acc.as<u64>(), *conv = p->conv.as<u64>();
+    int rc;
+    hipError_t e;
+    if ((rc = ksc_prepare(p))) return rc;
+
+    // ---- the test hook, checked against this call before anything is launched
+    const bool tf = ft.stage >= 0 && !(ft.stage & 1);      // a transform stage
+    u64 *flip = nullptr;
+    BcCheck hook{nullptr, -1, 0, 0, 0};                    // stages 1, 3, 5, 7: the armed check record (flags filled in per launch)
+    int hook_job = -1;                                     // stage 1: the digit, stage 5: the half
+    if (ft.stage >= 0) {
+        const int units = (ft.stage == 7 ? lay.total : lay.off[ft.stage + 1]) - lay.off[ft.stage];
+        if (ft.unit >= units || (size_t)ft.coeff >= N) return fail(FHE_ERR_INVALID, "fault unit or coefficient outside the call");
+        if (tf && logn < 13) return fail(FHE_ERR_UNSUPPORTED, "the transform stages' fault point lies between their two launches: two-launch sizes only (N >= 2^13)");
+        const int u = ft.unit;
+        switch (ft.stage) {
+        case 0: flip = coef + (size_t)u * N + ft.coeff; break;
+        case 2: {
+            const int d = u / M, j = u % M;
+            if (j >= d * p->alpha && j < std::min(L, (d + 1) * p->alpha)) return fail(FHE_ERR_INVALID, "fault unit is one of the digit's own limbs, which stage 2 does not transform");
+            flip = ext + (size_t)u * N + ft.coeff;
+            break;
+        }
+        case 4: flip = acc + ((size_t)(u / K) * M + L + u % K) * N + ft.coeff; break;
+        case 6: flip = conv + (size_t)u * N + ft.coeff; break;
+        case 1: {
+            const int d = u / M, j = u % M, lo = d * p->alpha, hi = std::min(L, lo + p->alpha), m = hi - lo;
+            const int ju = j >= lo && j < hi ? j - lo : m + (j < lo ? j : j - m);
+            if (!bc_point_exists(ft.point, ju < m ? ju + 1 : m))
+                return fail(FHE_ERR_UNSUPPORTED, "fault point 3 (the running sum) needs a sum of two terms: not on a digit's first limb, not on a one-limb digit");
+            hook_job = d;
+            hook = BcCheck{nullptr, ft.point, (u32)ju, (u64)ft.coeff, (u64)1 << ft.bit};
+            break;
+        }
+        case 5: {
+            const int ju = u % (K + L);
+            if (!bc_point_exists(ft.point, ju < K ? ju + 1 : K))
+                return fail(FHE_ERR_UNSUPPORTED, "fault point 3 (the running sum) needs a sum of two terms: not on the first special limb, not with K = 1");
+            hook_job = u / (K + L);
+            hook = BcCheck{nullptr, ft.point, (u32)ju, (u64)ft.coeff, (u64)1 << ft.bit};
+            break;
+        }
+        case 3:
+            if (ft.point < 0 || ft.point > 3) return fail(FHE_ERR_INVALID, "bad fault point");
+            hook = BcCheck{nullptr, ft.point, (u32)u, (u64)ft.coeff, (u64)1 << ft.bit};
+            break;
+        default:
+            if (!ks_tail_point_exists(ft.point, (u / L ? d_add1 : d_add0) != nullptr))
+                return fail(FHE_ERR_UNSUPPORTED, "fault point 3 (the running sum) of the tail exists only on a half with an addend");
+            hook = BcCheck{nullptr, ft.point, (u32)u, (u64)ft.coeff, (u64)1 << ft.bit};
+            break;
+        }
+    }
+    auto check_of = [&](int stage, u32 *flags, int job) {
+        BcCheck k{flags, -1, 0, 0, 0};
+        if (ft.stage == stage && hook_job == job) {
+            k = hook;
+            k.flags = flags;
+        }
+        return k;
+    };
+
+    // ---- the detector's partial sums live in the plan (ksc_prepare): the fhe_abft is only read
+    u32 tin_f, tout_f, tin_i, tout_i;
+    ntt_checked_tiles(logn, &tin_f, &tout_f, false);
+    ntt_checked_tiles(logn, &tin_i, &tout_i, true);
+    HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)lay.total * sizeof(u32), st));
+    HIP_TRY(hipMemsetAsync(p->chk_bc_flags.p, 0, (size_t)dnum * M * sizeof(u32), st));
+    const KscNtt fwd{p, a, st, tin_f, tout_f, false}, inv{p, a, st, tin_i, tout_i, true};
+
+    // ---- 0: opening INTT
+    HIP_TRY(hipMemcpyAsync(coef, d_c, (size_t)L * N * 8, hipMemcpyDeviceToDevice, st));
+    if ((rc = inv.run({KscRows{coef, 0, 0, (u32)L, 1, (u32)L, 0}}, ft.stage == 0 ? flip : nullptr, ft.bit))) return rc;
+    if ((rc = inv.compare(d_flags + lay.off[0], 0, 0, (u32)L, (u32)L))) return rc;
+
+    // ---- 1: digit extension
+    for (int d = 0; d < dnum; d++) {
+        const BcCheckedJob cj{p->up_host[d], p->up[d]->shoup_dig, p->up[d]->shoup_hor, check_of(1, p->chk_bc_flags.as<u32>() + (size_t)d * M, d)};
+        if ((e = launch_baseconv_exact_checked(st, cj, N)) != hipSuccess) return hip_fail(e, "launch_baseconv_exact_checked");
+    }
+    if ((e = launch_ks_flags_scatter(st, d_flags + lay.off[1], p->chk_bc_flags.as<u32>(), p->chk_bc_map.as<u32>(), (u32)(dnum * M))) != hipSuccess)
+        return hip_fail(e, "launch_ks_flags_scatter");
+
+    // ---- 2: forward transform of the extended limbs (the sums of the digits' own limbs stay zero on both sides)
+    {
+        HIP_TRY(hipMemsetAsync(p->chk_sum_in.p, 0, (size_t)dnum * M * 8 * tin_f, st));
+        HIP_TRY(hipMemsetAsync(p->chk_sum_out.p, 0, (size_t)dnum * M * 8 * tout_f, st));
+        std::vector<KscRows> rows;
+        rows.push_back(KscRows{ext, (u32)L, (u32)L, (u32)K, (u32)dnum, (u32)M, 0});
+        for (int d = 0; d < dnum; d++) {
+            const int lo = d * p->alpha, hi = std::min(L, lo + p->alpha);
+            u64 *base = ext + (size_t)d * M * N;
+            if (lo > 0) rows.push_back(KscRows{base, 0, 0, (u32)lo, 1, (u32)M, (u32)(d * M)});
+            if (hi < L) rows.push_back(KscRows{base, (u32)hi, (u32)hi, (u32)(L - hi), 1, (u32)M, (u32)(d * M)});
+        }
+        if ((rc = fwd.run(rows, ft.stage == 2 ? flip : nullptr, ft.bit))) return rc;
+        if ((rc = fwd.compare(d_flags + lay.off[2], 0, 0, (u32)M, (u32)(dnum * M)))) return rc;
+    }
+
+    // ---- 3: inner product with the key
+    {
+        const KsMacArgs ka{acc, ext, d_c, d_evk, lp, (u32)L, (u32)M, (u32)dnum, (u32)p->alpha, logn, (u32)L, 0u, 0u};
+        if ((e = launch_ks_mac_checked(st, ka, check_of(3, d_flags + lay.off[3], -1))) != hipSuccess) return hip_fail(e, "launch_ks_mac_checked");
+    }
+
+    // ---- 4: INTT of the special limbs of both halves, in place inside acc
+    if ((rc = inv.run({KscRows{acc, (u32)L, (u32)L, (u32)K, 2, (u32)M, 0}}, ft.stage == 4 ? flip : nullptr, ft.bit))) return rc;
+    for (int h = 0; h < 2; h++)
+        if ((rc = inv.compare(d_flags + lay.off[4] + h * K, (u32)(h * M + L), (u32)L, (u32)K, (u32)K))) return rc;
+
+    // ---- 5: mod-down conversion P -> Q
+    for (int h = 0; h < 2; h++) {
+        const BcJob job{p->down->dev, acc, conv + (size_t)h * L * N, 0xFFFFFFFFu, 0u, p->down_rows.as<u32>() + (size_t)h * K};
+        const BcCheckedJob cj{job, p->down->shoup_dig, p->down->shoup_hor, check_of(5, d_flags + lay.off[5] + h * (K + L), h)};
+        if ((e = launch_baseconv_exact_checked(st, cj, N)) != hipSuccess) return hip_fail(e, "launch_baseconv_exact_checked");
+    }
+
+    // ---- 6: forward transform of the converted limbs
+    if ((rc = fwd.run({KscRows{conv, 0, 0, (u32)L, 2, (u32)L, 0}}, ft.stage == 6 ? flip : nullptr, ft.bit))) return rc;
+    if ((rc = fwd.compare(d_flags + lay.off[6], 0, 0, (u32)L, (u32)(2 * L)))) return rc;
+
+    // ---- 7: tail
+    const SubScaleArgs sa{d_out0, d_out1, acc, conv, d_add0, p->pinv.as<u64>(), (u64)((size_t)M * N), (u64)((size_t)L * N), lp, 0u, (u32)L, logn, d_add1};
+    if ((e = launch_sub_scale_checked(st, sa, check_of(7, d_flags + lay.off[7], -1))) != hipSuccess) return hip_fail(e, "launch_sub_scale_checked");
+    return FHE_OK;
+}
+
+// argument and scope checks shared by the three entry points; takes the one-shot hook whatever the outcome
+int ksc_enter(fhe_ctx *ctx, fhe_keyswitch *p, const fhe_abft *a, uint32_t *d_flags, KscFault &ft)
+{
+    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
+    ft = KscFault{ctx->ksc_fault_stage, ctx->ksc_fault_point, ctx->ksc_fault_unit, ctx->ksc_fault_bit, ctx->ksc_fault_coeff};
+    ctx->ksc_fault_stage = -1;
+    if (!p || !a || !d_flags) return fail(FHE_ERR_INVALID, "null argument");
+    if (a->t != p->t) return fail(FHE_ERR_INVALID, "the detector was made for another table set than the plan's");
+    if (p->sharded) return fail(FHE_ERR_INVALID, "a sharded plan has no checked key switch: the checked call runs the whole switch on one device");
+    if (p->plain_modulus) return fail(FHE_ERR_UNSUPPORTED, "the BGV steps of a plan with a plain modulus have no checked form");
+    if (ctx->mode != 0 || ctx->resident || ctx->packed_on || ctx->only_pass >= 0 || !ntt_checked_supported(p->log_n))
+        return fail(FHE_ERR_UNSUPPORTED, "the checked key switch runs the two-launch transforms: not with ntt_mode=1, ntt_resident, ntt_packed, a single-pass hook, or N < 2^5");
+    if (!p->t->has_inverse) return fail(FHE_ERR_UNSUPPORTED, "table set has no inverse (twiddle or N not invertible)");
+    return FHE_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int fhe_keyswitch_checked_layout(const fhe_keyswitch *p, int out[10])
+{
+    if (!p || !out) return fail(FHE_ERR_INVALID, "null argument");
+    const KscLayout l = ksc_layout(p);
+    for (int s = 0; s < 8; s++) out[s] = l.off[s];
+    out[8] = l.total;
+    out[9] = 0;
+    return FHE_OK;
+}
+
+int fhe_ctx_inject_fault_keyswitch(fhe_ctx *ctx, int stage, int point, int unit, long long coeff, int bit)
+{
+    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
+    if (stage < 0) {
+        ctx->ksc_fault_stage = -1;
+        return FHE_OK;
+    }
+    const bool transform = !(stage & 1);
+    if (stage > 7 || unit < 0 || coeff < 0 || bit < 0 || bit > 63 || (!transform && (point < 0 || point > 3))) return fail(FHE_ERR_INVALID, "bad fault");
+    ctx->ksc_fault_stage = stage;
+    ctx->ksc_fault_point = transform ? 0 : point;
+    ctx->ksc_fault_unit = unit;
+    ctx->ksc_fault_coeff = coeff;
+    ctx->ksc_fault_bit = bit;
+    return FHE_OK;
+}
+
+int fhe_keyswitch_apply_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk,
+                                const uint64_t *d_add0, const uint64_t *d_add1, const fhe_abft *a, uint32_t *d_flags, void *stream)
+{
+    KscFault ft;
+    int rc = ksc_enter(ctx, p, a, d_flags, ft);
+    if (rc) return rc;
+    if (!d_out0 || !d_out1 || !d_c || !d_evk) return fail(FHE_ERR_INVALID, "null argument");
+    if (d_out0 == d_out1) return fail(FHE_ERR_INVALID, "the two output parts must be distinct buffers");
+    HIP_TRY(hipSetDevice(ctx->device));
+    return keyswitch_checked(p, d_out0, d_out1, d_c, d_evk, d_add0, d_add1, a, d_flags, pick(ctx, stream), ft);
+}
+
+int fhe_relinearize_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_d0, const uint64_t *d_d1,
+                            const uint64_t *d_d2, const uint64_t *d_relin_key, const fhe_abft *a, uint32_t *d_flags, void *stream)
+{
+    KscFault ft;
+    int rc = ksc_enter(ctx, p, a, d_flags, ft);
+    if (rc) return rc;
+    if (!d_out0 || !d_out1 || !d_d0 || !d_d1 || !d_d2 || !d_relin_key) return fail(FHE_ERR_INVALID, "null argument");
+    if (d_out0 == d_out1) return fail(FHE_ERR_INVALID, "the two output parts must be distinct buffers");
+    HIP_TRY(hipSetDevice(ctx->device));
+    return keyswitch_checked(p, d_out0, d_out1, d_d2, d_relin_key, d_d0, d_d1, a, d_flags, pick(ctx, stream), ft);
+}
+
+int fhe_rotate_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0, const uint64_t *d_c1,
+                       uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, uint32_t *d_flags, void *stream)
+{
+    KscFault ft;
+    int rc = ksc_enter(ctx, p, a, d_flags, ft);
+    if (rc) return rc;
+    if (!d_out0 || !d_out1 || !d_c0 || !d_c1 || !d_galois_key) return fail(FHE_ERR_INVALID, "null argument");
+    if (d_out0 == d_out1) return fail(FHE_ERR_INVALID, "the two output parts must be distinct buffers");
+    if (!(galois_elt & 1)) return fail(FHE_ERR_INVALID, "Galois elements are odd");
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = pick(ctx, stream);
+    // sigma(c1) and sigma(c0) (NTT domain: permutations of the slots) by one launch into the plan's buffers; the permutation itself is
+    // not checked.  sigma(c1) is switched back to s with the Galois key, sigma(c0) is the first part's addend.
+    const size_t N = (size_t)1 << p->log_n;
+    u64 *sig1 = p->rot.as<u64>(), *sig0 = sig1 + (size_t)p->L * N;
+    hipError_t e = launch_automorphism_ntt(st, sig1, d_c1, (u32)p->L, p->log_n, galois_elt, sig0, d_c0);
+    if (e != hipSuccess) return hip_fail(e, "launch_automorphism_ntt");
+    return keyswitch_checked(p, d_out0, d_out1, sig1, d_galois_key, sig0, nullptr, a, d_flags, st, ft);
+}
+
+} // extern "C"

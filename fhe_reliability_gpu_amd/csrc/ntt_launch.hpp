@@ -299,4 +299,12 @@ struct BcCheckedJob {
 hipError_t launch_baseconv_exact_checked(hipStream_t st, const BcCheckedJob &cj, u64 N);
 hipError_t launch_bconv_fast_checked(hipStream_t st, u64 *out, const u64 *in, const BaseConvPlanDev &pl, const BcCheck &chk, u64 N);
 
+// ---- keyswitch_checked.hip: the key switch's inner product and mod-down tail with a residue check per word (keyswitch_check.hpp) ----
+// launch_ks_mac / launch_sub_scale with a check record: flags [2][M] (half, row) / [halves][limbs], zeroed by the caller;
+// fault_point >= 0: XOR fault_mask at that injection point of unit fault_unit (index into flags), coefficient fault_coeff
+hipError_t launch_ks_mac_checked(hipStream_t st, const KsMacArgs &a, const BcCheck &k);
+hipError_t launch_sub_scale_checked(hipStream_t st, const SubScaleArgs &p, const BcCheck &k);
+// dst[map[i]] = src[i] for the non-zero src[i], i < n
+hipError_t launch_ks_flags_scatter(hipStream_t st, u32 *dst, const u32 *src, const u32 *map, u32 n);
+
 } // namespace fhe

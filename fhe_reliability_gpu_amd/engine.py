@@ -554,6 +554,58 @@ class KeySwitch:
         check(lib.fhe_relinearize(self.eng._h, self._h, o0.ptr, o1.ptr, d0.ptr, d1.ptr, d2.ptr, relin_key.ptr, stream))
         return o0, o1
 
+    # ---- stage-by-stage checked forms (capi_keyswitch_checked.cpp) ----
+    CHECKED_STAGES = ("intt_in", "extend", "ntt_ext", "mac", "intt_special", "moddown", "ntt_conv", "tail")
+
+    def checked_layout(self):
+        """``{stage name: (offset, shape)}`` of the checked calls' flag words plus ``"total"``; M = L + K.  Stage names in order:
+        ``intt_in [L]``, ``extend [dnum][M]``, ``ntt_ext [dnum][M]``, ``mac [2][M]``, ``intt_special [2][K]``,
+        ``moddown [2][K + L]``, ``ntt_conv [2][L]``, ``tail [2][L]``."""
+        out = (C.c_int * 10)()
+        check(lib.fhe_keyswitch_checked_layout(self._h, out))
+        L, K, d = self.L, self.K, self.dnum
+        M = L + K
+        shapes = ((L,), (d, M), (d, M), (2, M), (2, K), (2, K + L), (2, L), (2, L))
+        lay = {name: (int(out[s]), shapes[s]) for s, name in enumerate(self.CHECKED_STAGES)}
+        lay["total"] = int(out[8])
+        return lay
+
+    def _checked(self, call, stream):
+        lay = self.checked_layout()
+        total = lay["total"]
+        o0, o1 = self._out(self.L), self._out(self.L)
+        flags = self.eng.upload(np.full((total + 1) // 2, 0xA5A5A5A5A5A5A5A5, dtype=_U64))      # the call clears them itself
+        check(call(o0, o1, flags))
+        if stream is not None:
+            self.eng.sync(stream)
+        f = flags.download().view(np.uint32)[:total]
+        out = {}
+        for name in self.CHECKED_STAGES:
+            off, shape = lay[name]
+            out[name] = f[off:off + int(np.prod(shape))].reshape(shape).copy()
+        return o0, o1, out
+
+    def apply_checked(self, c: DeviceArray, evk: DeviceArray, abft: "Abft", add0: Optional[DeviceArray] = None,
+                      add1: Optional[DeviceArray] = None, stream=None):
+        """``apply`` (plus the optional addends ``add0`` / ``add1``, [L][N]) with every stage checked: (out0, out1, flags).  The words
+        are ``apply``'s bit for bit; ``flags`` maps each stage name of ``checked_layout`` to a uint32 array of its shape -- the ABFT
+        stages hold 0 / 1, the residue-checked ones the bits 1 (identity), 2 (window), 4 (operand not canonical).  A fault at
+        (stage, unit) raises that word and no other.  ``abft`` must be an ``Abft`` over the plan's tables."""
+        return self._checked(lambda o0, o1, fl: lib.fhe_keyswitch_apply_checked(
+            self.eng._h, self._h, o0.ptr, o1.ptr, c.ptr, evk.ptr, add0.ptr if add0 is not None else None, add1.ptr if add1 is not None else None,
+            abft._h, fl.ptr, stream), stream)
+
+    def relinearize_checked(self, d0: DeviceArray, d1: DeviceArray, d2: DeviceArray, relin_key: DeviceArray, abft: "Abft", stream=None):
+        """``relinearize`` with every stage of its key switch checked: (out0, out1, flags) as ``apply_checked``."""
+        return self._checked(lambda o0, o1, fl: lib.fhe_relinearize_checked(
+            self.eng._h, self._h, o0.ptr, o1.ptr, d0.ptr, d1.ptr, d2.ptr, relin_key.ptr, abft._h, fl.ptr, stream), stream)
+
+    def rotate_checked(self, c0: DeviceArray, c1: DeviceArray, galois_elt: int, galois_key: DeviceArray, abft: "Abft", stream=None):
+        """``rotate`` with every stage of its key switch checked: (out0, out1, flags) as ``apply_checked``.  The Galois permutation
+        of the two parts runs as a launch of its own and is not covered."""
+        return self._checked(lambda o0, o1, fl: lib.fhe_rotate_checked(
+            self.eng._h, self._h, o0.ptr, o1.ptr, c0.ptr, c1.ptr, galois_elt, galois_key.ptr, abft._h, fl.ptr, stream), stream)
+
     def rescale(self, c: DeviceArray, n_parts: int = 2, stream=None) -> DeviceArray:
         """``mod_switch_to_next_inplace`` (dotprod_test.cu:115): [n_parts][L][N] -> [n_parts][L-1][N]."""
         o = self.eng.alloc(n_parts * (self.L - 1) * self.t.N)

@@ -514,6 +514,63 @@ int fhe_baseconv_fast_checked(fhe_ctx *ctx, uint64_t *d_out, const uint64_t *d_i
  * well); point < 0 clears it. */
 int fhe_ctx_inject_fault_baseconv(fhe_ctx *ctx, int point, int unit, long long coeff, int bit);
 
+/* ---- stage-by-stage checked key switch, relinearisation and rotation -------------------------------------
+ * fhe_keyswitch_apply / fhe_relinearize / fhe_rotate with every one of the eight stages of the hybrid key switch checked and one
+ * uint32 flag word per (stage, unit).  d_out0 / d_out1 are the unchecked calls' words, bit for bit: every stage yields canonical
+ * residues and those are unique.  d_add0 / d_add1 (optional, [L][N]) are added to the two output parts as the unchecked core does
+ * (a relinearisation passes d0 and d1, a rotation sigma(c0)).  `a` must be an fhe_abft made for the plan's own table set
+ * (FHE_ERR_INVALID otherwise); it is only read.  The partial sums of the transforms' checks live in the plan (allocated at the plan's
+ * first checked call): one checked call at a time per plan, as for the unchecked calls.
+ * Flags: fhe_keyswitch_checked_layout gives out[s] = offset of stage s (s < 8), out[8] = total words, out[9] = 0 (reserved).  The
+ * call clears them on `stream`; M = L + K:
+ *   stage 0  opening INTT of the L input limbs                 ABFT sums differ: 1                                   [L]
+ *   stage 1  digit extension, an exact conversion per digit    bits 1 / 2 / 4 of fhe_baseconv_exact_checked          [dnum][M]
+ *            entry (d, j): the mixed-radix digit unit of limb j when j belongs to digit d, the output unit of limb j otherwise
+ *   stage 2  forward transform of the extended limbs           ABFT: 1                                               [dnum][M]
+ *            (the digit's own limbs are not transformed: their entries stay 0)
+ *   stage 3  inner product with both key halves                1 residue identity, 2 window, 4 operand >= q          [2][M]
+ *   stage 4  INTT of the K special limbs of both halves        ABFT: 1                                               [2][K]
+ *   stage 5  mod-down conversion P -> Q of both halves         as stage 1                                            [2][K + L]
+ *            per half K digit units, then L output units
+ *   stage 6  forward transform of the converted limbs          ABFT: 1                                               [2][L]
+ *   stage 7  tail (acc - X) P^-1 (+ addend)                    1 / 2 / 4 as stage 3 (4: operand or addend >= q_j)    [2][L]
+ * One-limb digits (dnum = L) and K = 1 make their conversion stage a conversion from one limb, x mod q_j.  There is no mixed-radix
+ * recurrence and no sum to check; what runs is the checked conversion with m = 1, one product with the constant 1 per digit and per
+ * output.  Its flags stay 0 on every clean run; the test hook's points 0-2 exist there and raise their unit's flag like anywhere else
+ * (point 3, the running sum, does not exist: FHE_ERR_UNSUPPORTED).
+ * Localisation: a fault at stage s, unit u raises the flag of (s, u) and no other flag of the call; every later stage is consistent
+ * with the input it was handed.  Bit 4 marks words that could not be checked (only caller-supplied words can be non-canonical: the
+ * digits' own limbs of d_c, the key, the addends); their output words are still the unchecked call's.
+ * Not covered: faults already in the inputs; a word corrupted in memory between one stage's store and the next stage's load (each
+ * check starts from the registers its stage loaded); the Galois permutation of the checked rotation; operands raising bit 4.
+ * Scope: a sharded plan returns FHE_ERR_INVALID; a plan with a plain modulus (BGV) FHE_ERR_UNSUPPORTED; a context with ntt_mode = 1,
+ * ntt_resident or ntt_packed set, or N < 2^5, FHE_ERR_UNSUPPORTED.  Hoisted rotations, the BSGS product and the fused rescale of the
+ * homomorphic multiply have no checked form. */
+int fhe_keyswitch_checked_layout(const fhe_keyswitch *p, int out[10]);
+int fhe_keyswitch_apply_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c,
+                                const uint64_t *d_evk, const uint64_t *d_add0 /* optional */, const uint64_t *d_add1 /* optional */,
+                                const fhe_abft *a, uint32_t *d_flags, void *stream);
+int fhe_relinearize_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_d0,
+                            const uint64_t *d_d1, const uint64_t *d_d2, const uint64_t *d_relin_key, const fhe_abft *a,
+                            uint32_t *d_flags, void *stream);
+/* sigma is applied to both parts by a launch of its own (unchecked), then sigma(c1) is key-switched with sigma(c0) as addend */
+int fhe_rotate_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0, const uint64_t *d_c1,
+                       uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, uint32_t *d_flags, void *stream);
+/* Test hook: one bit flip of a value in flight in the next checked key switch / relinearisation / rotation on this context; `unit`
+ * indexes the stage's flags (so a flip at (stage, unit) is expected to raise exactly that word).  One shot: the next checked call
+ * takes it whatever its outcome; stage < 0 clears it.
+ *   stages 0, 2, 4, 6: word `coeff` of the unit is flipped between the stage's two launches (`point` ignored).  Only two-launch
+ *     sizes have that point: at N < 2^13 the checked call returns FHE_ERR_UNSUPPORTED, launches nothing and leaves nothing armed.
+ *     A stage-2 unit that is one of its digit's own limbs returns FHE_ERR_INVALID.
+ *   stages 1, 5: point / coeff as in the base conversion's hook above; the unit's position in its conversion decides which points exist
+ *     (point 3 needs two terms: FHE_ERR_UNSUPPORTED on a digit's first limb and on every unit of a one-limb conversion).
+ *   stages 3, 7: point 0 the first term's product before reduction (stage 7: the low word of (x - y) P^-1), 1 the quotient estimate
+ *     of the reduction that produces the word, 2 the word before its window check, 3 the running sum before its final reduction
+ *     (stage 7: before the conditional subtraction after the addend -- FHE_ERR_UNSUPPORTED on a half without addend);
+ *     unit = half * M + row (stage 3), half * L + row (stage 7).
+ * A unit or coefficient outside the call returns FHE_ERR_INVALID from the checked call. */
+int fhe_ctx_inject_fault_keyswitch(fhe_ctx *ctx, int stage, int point, int unit, long long coeff, int bit);
+
 /* ---- fault injection ---------------------------------------------------------------- */
 /* _flip_bit_kernel<<<1,1>>> (reliability_test/dotprod_test.cu:31-33,55): data[idx] ^= 1 << bit */
 int fhe_flip_bit(fhe_ctx *ctx, uint64_t *d_data, uint64_t idx, int bit, void *stream);
