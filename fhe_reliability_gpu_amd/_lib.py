@@ -116,6 +116,11 @@ _SIG = {
     "fhe_relinearize_checked": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "fhe_rotate_checked": (ci, [vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp]),
     "fhe_ctx_inject_fault_keyswitch": (ci, [vp, ci, ci, ci, C.c_longlong, ci]),
+    "fhe_rescale_checked_layout": (ci, [vp, sz, C.POINTER(ci)]),
+    "fhe_rescale_checked": (ci, [vp, vp, vp, vp, sz, vp, vp, vp]),
+    "fhe_ctx_inject_fault_rescale": (ci, [vp, ci, ci, ci, C.c_longlong, ci]),
+    "fhe_hmult_checked_layout": (ci, [vp, ci, C.POINTER(ci)]),
+    "fhe_hmult_checked": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp]),
     "fhe_galois_key_prepare": (ci, [vp, vp, vp, vp, C.c_uint32, vp]),
     "fhe_rotate_hoisted": (ci, [vp, vp, C.POINTER(vp), C.POINTER(vp), vp, vp, C.POINTER(C.c_uint32), C.POINTER(vp), sz, vp]),
     "fhe_rotate_hoisted_shard_begin": (ci, [vp, vp, vp, vp]),

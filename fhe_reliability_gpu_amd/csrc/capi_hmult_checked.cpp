@@ -1,0 +1,210 @@
+// capi_hmult_checked.cpp -- rescale and homomorphic multiply with every stage checked and one flag word per (stage, unit)
+// (part of the C ABI of include/fhe_mi355x.h; shared pieces in capi_checked.hpp).
+//
+// The checked rescale is the "plain" route of capi_hmult.cpp with each launch replaced by its checked form -- neither x mod q_j
+// riding on the residues' column pass nor the fused k_ntt_row_subscale tail:
+//   0  copy of each part's last limb into the plan's rs_bc, checked INTT in place                (launch_ntt_checked, inverse)
+//   1  delta_j = x mod q_j for every remaining prime                                              (launch_rescale_reduce_checked)
+//   2  checked forward transform of the residues                                                  (launch_ntt_checked)
+//   3  (c - delta) q_last^-1                                                                      (launch_sub_scale_checked)
+// Each transform stage ends with launch_compare_sums on its units.  Every stage yields canonical residues and those are unique,
+// so the outputs are fhe_rescale's words whichever route it took.  The checked homomorphic multiply is fhe_tensor_product_checked,
+// the checked relinearisation and this rescale in a row: fhe_hmult's words whether or not it fused the mod-down with the rescale.
+#include "capi_checked.hpp"
+#include "keyswitch_check.hpp"
+#include "rescale_check.hpp"
+
+namespace {
+
+struct RscLayout {
+    int off[4], total;
+};
+RscLayout rsc_layout(const fhe_keyswitch *p, size_t n_parts)
+{
+    const int n = (int)n_parts, R = p->L - 1;
+    return RscLayout{{0, n, n + n * R, n + 2 * n * R}, n + 3 * n * R};
+}
+
+KscFault rsc_take_fault(fhe_ctx *ctx)
+{
+    const KscFault ft{ctx->rsc_fault_stage, ctx->rsc_fault_point, ctx->rsc_fault_unit, ctx->rsc_fault_bit, ctx->rsc_fault_coeff};
+    ctx->rsc_fault_stage = -1;
+    return ft;
+}
+
+// d_in = [n_parts][L][N], outs[i] = [L - 1][N]; the caller has checked scope, arguments and overlap
+int rescale_checked(fhe_keyswitch *p, uint64_t *const *outs, const uint64_t *d_in, size_t n_parts, const fhe_abft *a, uint32_t *d_flags, hipStream_t st,
+                    const KscFault &ft)
+{
+    const fhe_ntt_tables *t = p->t;
+    const int L = p->L, R = L - 1, logn = p->log_n;
+    const size_t N = (size_t)1 << logn;
+    const RscLayout lay = rsc_layout(p, n_parts);
+    const LimbParams *lp = t->d_lp.as<LimbParams>();
+    u64 *x = p->rs_bc, *delta = p->rs_delta.as<u64>();
+    int rc;
+    hipError_t e;
+    if ((rc = ksc_prepare(p))) return rc;
+
+    // ---- the test hook, checked against this call before anything is launched
+    u64 *flip = nullptr;
+    BcCheck hook{nullptr, -1, 0, 0, 0};
+    if (ft.stage >= 0) {
+        const int units = (ft.stage == 3 ? lay.total : lay.off[ft.stage + 1]) - lay.off[ft.stage];
+        if (ft.unit >= units || (size_t)ft.coeff >= N) return fail(FHE_ERR_INVALID, "fault unit or coefficient outside the call");
+        if (!(ft.stage & 1)) {
+            if (logn < 13) return fail(FHE_ERR_UNSUPPORTED, "the transform stages' fault point lies between their two launches: two-launch sizes only (N >= 2^13)");
+            flip = (ft.stage == 0 ? x : delta) + (size_t)ft.unit * N + ft.coeff;
+        } else {
+            if (ft.stage == 1 && !rescale_reduce_point_exists(ft.point))
+                return fail(FHE_ERR_UNSUPPORTED, "fault point 3 (the running sum) does not exist on the rescale's residues: x mod q_j has no sum");
+            if (ft.stage == 3 && !ks_tail_point_exists(ft.point, false))
+                return fail(FHE_ERR_UNSUPPORTED, "fault point 3 (the running sum) of the tail exists only with an addend, and the rescale has none");
+            hook = BcCheck{nullptr, ft.point, (u32)ft.unit, (u64)ft.coeff, (u64)1 << ft.bit};
+        }
+    }
+
+    u32 tin_f, tout_f, tin_i, tout_i;
+    ntt_checked_tiles(logn, &tin_f, &tout_f, false);
+    ntt_checked_tiles(logn, &tin_i, &tout_i, true);
+    HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)lay.total * sizeof(u32), st));
+    const KscNtt fwd{p, a, st, tin_f, tout_f, false}, inv{p, a, st, tin_i, tout_i, true};
+
+    // ---- 0: INTT of the last limbs
+    HIP_TRY(hipMemcpy2DAsync(x, N * 8, d_in + (size_t)R * N, (size_t)L * N * 8, N * 8, n_parts, hipMemcpyDeviceToDevice, st));
+    if ((rc = inv.run({KscRows{x, 0, (u32)R, 1, (u32)n_parts, 1, 0}}, ft.stage == 0 ? flip : nullptr, ft.bit))) return rc;
+    if ((rc = inv.compare(d_flags + lay.off[0], 0, (u32)R, 1, (u32)n_parts))) return rc;
+
+    // ---- 1: residues modulo the remaining primes
+    {
+        BcCheck k{d_flags + lay.off[1], -1, 0, 0, 0};
+        if (ft.stage == 1) {
+            k = hook;
+            k.flags = d_flags + lay.off[1];
+        }
+        const RescaleReduceArgs ra{delta, x, lp, (u32)R, (u32)n_parts, logn};
+        if ((e = launch_rescale_reduce_checked(st, ra, k)) != hipSuccess) return hip_fail(e, "launch_rescale_reduce_checked");
+    }
+
+    // ---- 2: forward transform of the residues
+    if ((rc = fwd.run({KscRows{delta, 0, 0, (u32)R, (u32)n_parts, (u32)R, 0}}, ft.stage == 2 ? flip : nullptr, ft.bit))) return rc;
+    if ((rc = fwd.compare(d_flags + lay.off[2], 0, 0, (u32)R, (u32)(n_parts * R)))) return rc;
+
+    // ---- 3: (c - delta) / q_last, two parts per launch
+    for (size_t part = 0; part < n_parts; part += 2) {
+        const bool two = part + 1 < n_parts;
+        const int u0 = (int)part * R, u1 = u0 + (two ? 2 : 1) * R;
+        BcCheck k{d_flags + lay.off[3] + u0, -1, 0, 0, 0};
+        if (ft.stage == 3 && ft.unit >= u0 && ft.unit < u1) {
+            k = hook;
+            k.flags = d_flags + lay.off[3] + u0;
+            k.fault_unit = (u32)(ft.unit - u0);
+        }
+        const SubScaleArgs sa{outs[part], two ? outs[part + 1] : nullptr, d_in + part * L * N, delta + part * R * N, nullptr, p->qlast_inv.as<u64>(),
+                              (u64)((size_t)L * N), (u64)((size_t)R * N), lp, 0u, (u32)R, logn, nullptr};
+        if ((e = launch_sub_scale_checked(st, sa, k)) != hipSuccess) return hip_fail(e, "launch_sub_scale_checked");
+    }
+    return FHE_OK;
+}
+
+int rsc_scope(const fhe_ctx *ctx, const fhe_keyswitch *p, const fhe_abft *a, const uint32_t *d_flags)
+{
+    int rc = ksc_scope(ctx, p, a, d_flags);
+    if (rc) return rc;
+    if (p->L < 2) return fail(FHE_ERR_INVALID, "no prime left to drop");
+    return FHE_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int fhe_rescale_checked_layout(const fhe_keyswitch *p, size_t n_parts, int out[6])
+{
+    if (!p || !out) return fail(FHE_ERR_INVALID, "null argument");
+    if (n_parts < 1 || n_parts > 3) return fail(FHE_ERR_INVALID, "a ciphertext has 1 to 3 parts");
+    if (p->L < 2) return fail(FHE_ERR_INVALID, "no prime left to drop");
+    const RscLayout l = rsc_layout(p, n_parts);
+    for (int s = 0; s < 4; s++) out[s] = l.off[s];
+    out[4] = l.total;
+    out[5] = 0;
+    return FHE_OK;
+}
+
+int fhe_ctx_inject_fault_rescale(fhe_ctx *ctx, int stage, int point, int unit, long long coeff, int bit)
+{
+    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
+    if (stage < 0) {
+        ctx->rsc_fault_stage = -1;
+        return FHE_OK;
+    }
+    const bool transform = !(stage & 1);
+    if (stage > 3 || unit < 0 || coeff < 0 || bit < 0 || bit > 63 || (!transform && (point < 0 || point > 3))) return fail(FHE_ERR_INVALID, "bad fault");
+    ctx->rsc_fault_stage = stage;
+    ctx->rsc_fault_point = transform ? 0 : point;
+    ctx->rsc_fault_unit = unit;
+    ctx->rsc_fault_coeff = coeff;
+    ctx->rsc_fault_bit = bit;
+    return FHE_OK;
+}
+
+int fhe_rescale_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out, const uint64_t *d_in, size_t n_parts, const fhe_abft *a, uint32_t *d_flags,
+                        void *stream)
+{
+    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
+    const KscFault ft = rsc_take_fault(ctx);      // one shot, whatever the outcome
+    int rc = rsc_scope(ctx, p, a, d_flags);
+    if (rc) return rc;
+    if (!d_out || !d_in) return fail(FHE_ERR_INVALID, "null argument");
+    if (n_parts < 1 || n_parts > 3) return fail(FHE_ERR_INVALID, "a ciphertext has 1 to 3 parts");
+    // input parts are L rows apart, output parts L - 1: any overlap of the output with the input is refused, as fhe_rescale does
+    const size_t N = (size_t)1 << p->log_n, step = (size_t)(p->L - 1) * N;
+    if (d_out < d_in + n_parts * p->L * N && d_in < d_out + n_parts * step) return fail(FHE_ERR_INVALID, "rescale is out of place");
+    uint64_t *outs[3] = {d_out, d_out + step, d_out + 2 * step};
+    HIP_TRY(hipSetDevice(ctx->device));
+    return rescale_checked(p, outs, d_in, n_parts, a, d_flags, pick(ctx, stream), ft);
+}
+
+int fhe_hmult_checked_layout(const fhe_keyswitch *p, int rescale, int out[4])
+{
+    if (!p || !out) return fail(FHE_ERR_INVALID, "null argument");
+    if (rescale && p->L < 2) return fail(FHE_ERR_INVALID, "no prime left to drop");
+    out[0] = 0;
+    out[1] = 3 * p->L;
+    out[2] = out[1] + ksc_layout(p).total;
+    out[3] = out[2] + (rescale ? rsc_layout(p, 2).total : 0);
+    return FHE_OK;
+}
+
+int fhe_hmult_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_a0, const uint64_t *d_a1,
+                      const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a, uint32_t *d_flags,
+                      void *stream)
+{
+    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
+    // the one-shot hooks of the steps this call runs belong to it whatever its outcome: the key switch's and (when it rescales) the
+    // rescale's are taken here, the pointwise one by the tensor step (cleared here when the call ends before it)
+    const KscFault kf = ksc_take_fault(ctx), rf = rescale ? rsc_take_fault(ctx) : KscFault{};
+    int rc = rescale ? rsc_scope(ctx, p, a, d_flags) : ksc_scope(ctx, p, a, d_flags);
+    if (!rc && (!d_out0 || !d_out1 || !d_a0 || !d_a1 || !d_b0 || !d_b1 || !d_relin_key)) rc = fail(FHE_ERR_INVALID, "null argument");
+    if (!rc && d_out0 == d_out1) rc = fail(FHE_ERR_INVALID, "the two output parts must be distinct buffers");
+    if (rc) {
+        ctx->pw_fault_point = -1;
+        return rc;
+    }
+    int lay[4];
+    if ((rc = fhe_hmult_checked_layout(p, rescale, lay))) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = pick(ctx, stream);
+    HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)lay[3] * sizeof(u32), st));
+    const size_t N = (size_t)1 << p->log_n, L = p->L;
+    u64 *d0 = p->hm.as<u64>(), *d1 = d0 + L * N, *d2 = d1 + L * N, *pre = p->hm_pre.as<u64>();
+    // (the operands are read by the first step only, the outputs written by the last launches of the last step: an output may reuse
+    // an operand's buffer, as for fhe_hmult)
+    if ((rc = fhe_tensor_product_checked(ctx, d0, d1, d2, d_a0, d_a1, d_b0, d_b1, p->t, L, 0, d_flags + lay[0], st))) return rc;
+    if (!rescale) return keyswitch_checked(p, d_out0, d_out1, d2, d_relin_key, d0, d1, a, d_flags + lay[1], st, kf);
+    if ((rc = keyswitch_checked(p, pre, pre + L * N, d2, d_relin_key, d0, d1, a, d_flags + lay[1], st, kf))) return rc;
+    uint64_t *outs[3] = {d_out0, d_out1, nullptr};
+    return rescale_checked(p, outs, pre, 2, a, d_flags + lay[2], st, rf);
+}
+
+} // extern "C"

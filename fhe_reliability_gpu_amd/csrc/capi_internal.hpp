@@ -118,6 +118,8 @@ struct fhe_ctx {
     long long bc_fault_coeff = 0;                                   // conversion (fhe_ctx_inject_fault_baseconv)
     int ksc_fault_stage = -1, ksc_fault_point = 0, ksc_fault_unit = 0, ksc_fault_bit = 0;   // one-shot bit flip inside the next checked key
     long long ksc_fault_coeff = 0;                                                         // switch (fhe_ctx_inject_fault_keyswitch)
+    int rsc_fault_stage = -1, rsc_fault_point = 0, rsc_fault_unit = 0, rsc_fault_bit = 0;   // one-shot bit flip inside the next checked
+    long long rsc_fault_coeff = 0;                                                         // rescale (fhe_ctx_inject_fault_rescale)
     int geo = 1;           // column-tile geometry of the two-launch path (ntt_launch.hpp)
     bool resident = false; // 2^13 / 2^14: one LDS-resident pass instead of two launches (opt-in, see ntt_plan.hpp)
     int pingpong = -1;        // "ntt_pingpong": two-launch transforms hand over through a per-stream scratch buffer (both launches out of

@@ -15,14 +15,9 @@
 //   7  tail (acc - conv) P^-1 (+ addends)                                                                (launch_sub_scale_checked)
 // Each transform stage ends with launch_compare_sums on its units.  Every stage yields canonical residues and canonical residues are
 // unique, so the outputs are the unchecked call's words whatever its launch list was.
-#include "capi_internal.hpp"
+#include "capi_checked.hpp"
 #include "keyswitch_check.hpp"
 
-namespace {
-
-struct KscLayout {
-    int off[8], total;
-};
 KscLayout ksc_layout(const fhe_keyswitch *p)
 {
     const int L = p->L, K = p->K, M = L + K, d = p->dnum;
@@ -34,72 +29,6 @@ KscLayout ksc_layout(const fhe_keyswitch *p)
     }
     return l;
 }
-
-// slots of the plan's scratch sums, one per (polynomial, row) a stage's transforms address: stage 2 the dnum x M rows of ext, stage 4
-// rows L .. M-1 of both halves of acc ([2][M]: up to slot 2 M - 1), stage 6 [2][L], stage 0 [L]
-size_t ksc_slots(const fhe_keyswitch *p) { return (size_t)std::max(p->dnum, 2) * (p->L + p->K); }
-
-struct KscFault {
-    int stage = -1, point = 0, unit = 0, bit = 0;
-    long long coeff = 0;
-};
-
-// the transforms of one checked stage: rows [row0, row0 + count) of n_poly polynomials `stride` rows apart inside base, row r on
-// table limb tl0 + (r - row0); the sums of (polynomial, row) live at slot sum0 + polynomial * stride + row
-struct KscRows {
-    u64 *base;
-    u32 row0, tl0, count, n_poly, stride, sum0;
-};
-
-struct KscNtt {
-    const fhe_keyswitch *p;
-    const fhe_abft *a;
-    hipStream_t st;
-    u32 tin, tout;
-    bool inverse;
-    u64 *sum_in() const { return p->chk_sum_in.as<u64>(); }
-    u64 *sum_out() const { return p->chk_sum_out.as<u64>(); }
-
-    int launch(const KscRows &r, int which) const
-    {
-        const fhe_ntt_tables *t = p->t;
-        const size_t N = (size_t)1 << p->log_n;
-        return for_each_run(t, r.count, r.tl0, [&](size_t off, size_t len, int path) -> int {
-            PassArgs pa{r.base + (r.row0 + off) * N, t->d_lp.as<LimbParams>(), (u32)(r.tl0 + off), (u32)len, (u32)(r.n_poly * len), r.stride, nullptr};
-            // the launch addresses slots slot + polynomial * stride + l, l < len
-            const size_t slot = (size_t)r.sum0 + r.row0 + off;
-            if (slot + (size_t)(r.n_poly - 1) * r.stride + len > ksc_slots(p)) return fail(FHE_ERR_INVALID, "checked key switch: a transform's sums lie outside the plan's scratch");
-            hipError_t e = launch_ntt_checked(st, pa, a->win.as<Tw>(), a->wout.as<Tw>(), a->wout8.as<u64>(), sum_in() + slot * tin, sum_out() + slot * tout,
-                                              p->log_n, path, which, inverse);
-            return e == hipSuccess ? FHE_OK : hip_fail(e, "launch_ntt_checked");
-        });
-    }
-    // all launches of the stage; flip != nullptr (test hook, two-launch sizes): that word is flipped between the stage's two launches
-    int run(const std::vector<KscRows> &rows, u64 *flip, int bit) const
-    {
-        int rc;
-        if (!flip) {
-            for (const KscRows &r : rows)
-                if ((rc = launch(r, -1))) return rc;
-            return FHE_OK;
-        }
-        for (const KscRows &r : rows)
-            if ((rc = launch(r, 0))) return rc;
-        hipError_t e = launch_flip_bit(st, flip, 0, bit);
-        if (e != hipSuccess) return hip_fail(e, "launch_flip_bit");
-        for (const KscRows &r : rows)
-            if ((rc = launch(r, 1))) return rc;
-        return FHE_OK;
-    }
-    // flags[i] = sums of slot (slot0 + i) differ, i < units, unit i on table limb limb0 + i % limbs
-    int compare(u32 *flags, u32 slot0, u32 limb0, u32 limbs, u32 units) const
-    {
-        if ((size_t)slot0 + units > ksc_slots(p)) return fail(FHE_ERR_INVALID, "checked key switch: a comparison's sums lie outside the plan's scratch");
-        hipError_t e = launch_compare_sums(st, flags, sum_in() + (size_t)slot0 * tin, tin, sum_out() + (size_t)slot0 * tout, tout,
-                                           p->t->d_lp.as<LimbParams>(), limb0, limbs, units);
-        return e == hipSuccess ? FHE_OK : hip_fail(e, "launch_compare_sums");
-    }
-};
 
 // the flag map of stage 1, its job-order scratch and the detector's partial sums, once per plan
 int ksc_prepare(fhe_keyswitch *p)
@@ -260,12 +189,15 @@ int keyswitch_checked(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, cons
     return FHE_OK;
 }
 
-// argument and scope checks shared by the three entry points; takes the one-shot hook whatever the outcome
-int ksc_enter(fhe_ctx *ctx, fhe_keyswitch *p, const fhe_abft *a, uint32_t *d_flags, KscFault &ft)
+KscFault ksc_take_fault(fhe_ctx *ctx)
 {
-    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
-    ft = KscFault{ctx->ksc_fault_stage, ctx->ksc_fault_point, ctx->ksc_fault_unit, ctx->ksc_fault_bit, ctx->ksc_fault_coeff};
+    const KscFault ft{ctx->ksc_fault_stage, ctx->ksc_fault_point, ctx->ksc_fault_unit, ctx->ksc_fault_bit, ctx->ksc_fault_coeff};
     ctx->ksc_fault_stage = -1;
+    return ft;
+}
+
+int ksc_scope(const fhe_ctx *ctx, const fhe_keyswitch *p, const fhe_abft *a, const uint32_t *d_flags)
+{
     if (!p || !a || !d_flags) return fail(FHE_ERR_INVALID, "null argument");
     if (a->t != p->t) return fail(FHE_ERR_INVALID, "the detector was made for another table set than the plan's");
     if (p->sharded) return fail(FHE_ERR_INVALID, "a sharded plan has no checked key switch: the checked call runs the whole switch on one device");
@@ -274,6 +206,16 @@ int ksc_enter(fhe_ctx *ctx, fhe_keyswitch *p, const fhe_abft *a, uint32_t *d_fla
         return fail(FHE_ERR_UNSUPPORTED, "the checked key switch runs the two-launch transforms: not with ntt_mode=1, ntt_resident, ntt_packed, a single-pass hook, or N < 2^5");
     if (!p->t->has_inverse) return fail(FHE_ERR_UNSUPPORTED, "table set has no inverse (twiddle or N not invertible)");
     return FHE_OK;
+}
+
+namespace {
+
+// argument and scope checks shared by the three entry points; takes the one-shot hook whatever the outcome
+int ksc_enter(fhe_ctx *ctx, fhe_keyswitch *p, const fhe_abft *a, uint32_t *d_flags, KscFault &ft)
+{
+    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
+    ft = ksc_take_fault(ctx);
+    return ksc_scope(ctx, p, a, d_flags);
 }
 
 } // namespace

@@ -307,4 +307,16 @@ hipError_t launch_sub_scale_checked(hipStream_t st, const SubScaleArgs &p, const
 // dst[map[i]] = src[i] for the non-zero src[i], i < n
 hipError_t launch_ks_flags_scatter(hipStream_t st, u32 *dst, const u32 *src, const u32 *map, u32 n);
 
+// ---- rescale_checked.hip: the residues of a rescale's dropped limb with a residue check per word (rescale_check.hpp) ----
+// delta[part][j][i] = x[part][i] mod q_j for the table limbs j < R, x = [n_parts][N] words below q_R (the dropped limb in
+// coefficient form); flags [n_parts][R], zeroed by the caller; the check record as for launch_ks_mac_checked
+struct RescaleReduceArgs {
+    u64 *delta;          // [n_parts][R][N]
+    const u64 *x;        // [n_parts][N]
+    const LimbParams *lp;
+    u32 R, n_parts;
+    int logn;
+};
+hipError_t launch_rescale_reduce_checked(hipStream_t st, const RescaleReduceArgs &a, const BcCheck &k);
+
 } // namespace fhe

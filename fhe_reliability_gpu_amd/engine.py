@@ -621,6 +621,68 @@ class KeySwitch:
         check(lib.fhe_hmult(self.eng._h, self._h, o0.ptr, o1.ptr, a0.ptr, a1.ptr, b0.ptr, b1.ptr, relin_key.ptr, 1 if rescale else 0, stream))
         return o0, o1
 
+    # ---- stage-by-stage checked rescale and homomorphic multiply (capi_hmult_checked.cpp) ----
+    RESCALE_CHECKED_STAGES = ("intt_last", "reduce", "ntt_delta", "scale")
+
+    def rescale_checked_layout(self, n_parts: int = 2):
+        """``{stage name: (offset, shape)}`` of ``rescale_checked``'s flag words plus ``"total"``; R = L - 1.  Stage names in
+        order: ``intt_last [n_parts]``, ``reduce [n_parts][R]``, ``ntt_delta [n_parts][R]``, ``scale [n_parts][R]``."""
+        out = (C.c_int * 6)()
+        check(lib.fhe_rescale_checked_layout(self._h, n_parts, out))
+        R = self.L - 1
+        shapes = ((n_parts,), (n_parts, R), (n_parts, R), (n_parts, R))
+        lay = {name: (int(out[s]), shapes[s]) for s, name in enumerate(self.RESCALE_CHECKED_STAGES)}
+        lay["total"] = int(out[4])
+        return lay
+
+    def hmult_checked_layout(self, rescale: bool = True):
+        """``{"tensor": off, "keyswitch": off, "rescale": off, "total": n}`` of ``hmult_checked``'s flag buffer: the tensor block
+        ``[L][3]``, the key-switch block laid out as ``checked_layout``, the rescale block as ``rescale_checked_layout(2)`` (its
+        offset equals the total when ``rescale`` is false)."""
+        out = (C.c_int * 4)()
+        check(lib.fhe_hmult_checked_layout(self._h, 1 if rescale else 0, out))
+        return {"tensor": int(out[0]), "keyswitch": int(out[1]), "rescale": int(out[2]), "total": int(out[3])}
+
+    @staticmethod
+    def _split_flags(f, lay, names, base=0):
+        return {name: f[base + lay[name][0]:base + lay[name][0] + int(np.prod(lay[name][1]))].reshape(lay[name][1]).copy() for name in names}
+
+    def rescale_checked(self, c: DeviceArray, abft: "Abft", n_parts: int = 2, stream=None):
+        """``rescale`` with every stage checked: (out, flags).  The words are ``rescale``'s bit for bit; ``flags`` maps
+        ``intt_last``, ``reduce``, ``ntt_delta`` and ``scale`` to uint32 arrays of the shapes of ``rescale_checked_layout`` -- the ABFT
+        stages hold 0 / 1, the residue-checked ones the bits 1 (identity), 2 (window), 4 (operand not canonical).  A fault at
+        (stage, unit) raises that word and no other."""
+        lay = self.rescale_checked_layout(n_parts)
+        total = lay["total"]
+        o = self.eng.alloc(n_parts * (self.L - 1) * self.t.N)
+        o.shape = (n_parts, self.L - 1, self.t.N)
+        flags = self.eng.upload(np.full((total + 1) // 2, 0xA5A5A5A5A5A5A5A5, dtype=_U64))      # the call clears them itself
+        check(lib.fhe_rescale_checked(self.eng._h, self._h, o.ptr, c.ptr, n_parts, abft._h, flags.ptr, stream))
+        if stream is not None:
+            self.eng.sync(stream)
+        f = flags.download().view(np.uint32)[:total]
+        return o, self._split_flags(f, lay, self.RESCALE_CHECKED_STAGES)
+
+    def hmult_checked(self, a0: DeviceArray, a1: DeviceArray, b0: DeviceArray, b1: DeviceArray, relin_key: DeviceArray, abft: "Abft",
+                      rescale: bool = True, stream=None):
+        """``hmult`` with every step checked -- multiply -> relinearize -> mod_switch_to_next (dotprod_test.cu:113-115) as one
+        protected call: (out0, out1, flags), the words ``hmult``'s bit for bit.  ``flags = {"tensor": [L][3] as tensor_checked,
+        "keyswitch": {the eight stage names of checked_layout}, "rescale": {the four of rescale_checked_layout} or None}``."""
+        lay = self.hmult_checked_layout(rescale)
+        total = lay["total"]
+        limbs = self.L - 1 if rescale else self.L
+        o0, o1 = self._out(limbs), self._out(limbs)
+        flags = self.eng.upload(np.full((total + 1) // 2, 0xA5A5A5A5A5A5A5A5, dtype=_U64))      # the call clears them itself
+        check(lib.fhe_hmult_checked(self.eng._h, self._h, o0.ptr, o1.ptr, a0.ptr, a1.ptr, b0.ptr, b1.ptr, relin_key.ptr, 1 if rescale else 0,
+                                    abft._h, flags.ptr, stream))
+        if stream is not None:
+            self.eng.sync(stream)
+        f = flags.download().view(np.uint32)[:total]
+        out = {"tensor": f[lay["tensor"]:lay["tensor"] + 3 * self.L].reshape(self.L, 3).copy(),
+               "keyswitch": self._split_flags(f, self.checked_layout(), self.CHECKED_STAGES, lay["keyswitch"]),
+               "rescale": self._split_flags(f, self.rescale_checked_layout(2), self.RESCALE_CHECKED_STAGES, lay["rescale"]) if rescale else None}
+        return o0, o1, out
+
     def __del__(self):
         try:
             if self._h and self.eng._h:

@@ -544,8 +544,9 @@ int fhe_ctx_inject_fault_baseconv(fhe_ctx *ctx, int point, int unit, long long c
  * Not covered: faults already in the inputs; a word corrupted in memory between one stage's store and the next stage's load (each
  * check starts from the registers its stage loaded); the Galois permutation of the checked rotation; operands raising bit 4.
  * Scope: a sharded plan returns FHE_ERR_INVALID; a plan with a plain modulus (BGV) FHE_ERR_UNSUPPORTED; a context with ntt_mode = 1,
- * ntt_resident or ntt_packed set, or N < 2^5, FHE_ERR_UNSUPPORTED.  Hoisted rotations, the BSGS product and the fused rescale of the
- * homomorphic multiply have no checked form. */
+ * ntt_resident or ntt_packed set, or N < 2^5, FHE_ERR_UNSUPPORTED.  The rescale and the homomorphic multiply have checked forms of
+ * their own below.  What remains without a checked form: hoisted rotations, fhe_bsgs_matvec, sharded plans, BGV plans (plain
+ * modulus) and the Galois permutation. */
 int fhe_keyswitch_checked_layout(const fhe_keyswitch *p, int out[10]);
 int fhe_keyswitch_apply_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c,
                                 const uint64_t *d_evk, const uint64_t *d_add0 /* optional */, const uint64_t *d_add1 /* optional */,
@@ -570,6 +571,54 @@ int fhe_rotate_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_
  *     unit = half * M + row (stage 3), half * L + row (stage 7).
  * A unit or coefficient outside the call returns FHE_ERR_INVALID from the checked call. */
 int fhe_ctx_inject_fault_keyswitch(fhe_ctx *ctx, int stage, int point, int unit, long long coeff, int bit);
+
+/* ---- stage-by-stage checked rescale and homomorphic multiply ------------------------------------------------
+ * fhe_rescale with every stage checked and one uint32 flag word per (stage, unit).  Argument, shape and overlap rules are
+ * fhe_rescale's: d_in = [n_parts][L][N], d_out = [n_parts][L-1][N], out of place, n_parts 1 to 3.  The output words are
+ * fhe_rescale's bit for bit, floor rounding included, whichever route the unchecked call took: every stage yields canonical
+ * residues and those are unique.  `a` as for the checked key switch; the partial sums live in the plan.
+ * Flags: fhe_rescale_checked_layout gives out[s] = offset of stage s (s < 4), out[4] = total = n_parts (1 + 3 R), out[5] = 0
+ * (reserved); R = L - 1.  The call clears them on `stream`:
+ *   stage 0  INTT of each part's last limb (into the plan)     ABFT sums differ: 1                                   [n_parts]
+ *   stage 1  delta_j = x mod q_j for every remaining prime     1: x = k q_j + delta_j fails modulo 2^32 - 1;         [n_parts][R]
+ *                                                              2: delta_j >= q_j, or the quotient estimate above x / q_j's bound;
+ *                                                              4: x >= q_last -- not checkable, raised alone, the word is
+ *                                                                 still x mod q_j
+ *   stage 2  forward transform of the residues                 ABFT: 1                                               [n_parts][R]
+ *   stage 3  (c - delta) q_last^-1                             bits 1 / 2 / 4 as stage 7 of the checked key switch   [n_parts][R]
+ * Localisation as for the checked key switch: a fault at (stage, unit) raises that word and no other; later stages are consistent
+ * with what they were handed.  Not covered: faults already in the input; a word corrupted in memory between one stage's store
+ * and the next stage's load; operands raising bit 4.
+ * Scope: the checked key switch's -- a sharded plan FHE_ERR_INVALID; a plan with a plain modulus (BGV) FHE_ERR_UNSUPPORTED;
+ * ntt_mode = 1, ntt_resident, ntt_packed, a single-pass hook or N < 2^5 FHE_ERR_UNSUPPORTED; L < 2 FHE_ERR_INVALID; a detector
+ * made for another table set than the plan's FHE_ERR_INVALID. */
+int fhe_rescale_checked_layout(const fhe_keyswitch *p, size_t n_parts, int out[6]);
+int fhe_rescale_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out, const uint64_t *d_in, size_t n_parts, const fhe_abft *a,
+                        uint32_t *d_flags, void *stream);
+/* Test hook: one bit flip of a value in flight in the next fhe_rescale_checked, or in the rescale step of the next
+ * fhe_hmult_checked that rescales, on this context; `unit` indexes the stage's flags.  One shot; stage < 0 clears it.
+ *   stages 0, 2: word `coeff` of the unit is flipped between the transform's two launches (`point` ignored).  N >= 2^13 only: below
+ *     that the checked call returns FHE_ERR_UNSUPPORTED, launches nothing and leaves nothing armed.
+ *   stage 1: point 0 the product that forms the quotient estimate (high word of x times the high word of floor(2^128 / q_j)), 1
+ *     the quotient estimate, 2 the word before its window check.  Point 3 does not exist (no running sum): FHE_ERR_UNSUPPORTED.
+ *   stage 3: the points of stage 7 of the checked key switch; point 3 is FHE_ERR_UNSUPPORTED, the rescale has no addend.
+ * A unit or coefficient outside the call returns FHE_ERR_INVALID from the checked call. */
+int fhe_ctx_inject_fault_rescale(fhe_ctx *ctx, int stage, int point, int unit, long long coeff, int bit);
+
+/* fhe_hmult with every step checked: fhe_tensor_product_checked into the plan, the checked relinearisation, and (rescale != 0)
+ * the checked rescale of the two parts.  The output words are fhe_hmult's bit for bit, whether or not the unchecked call fused
+ * the mod-down with the rescale; aliasing rules are fhe_hmult's (an output may reuse an operand's buffer, d_out0 != d_out1).
+ * Flags, one buffer of out[3] words which the call clears on `stream` (fhe_hmult_checked_layout):
+ *   out[0] = 0   the tensor block [3 L], word 3 l + part, bits of fhe_tensor_product_checked
+ *   out[1]       the key-switch block, laid out as fhe_keyswitch_checked_layout
+ *   out[2]       the rescale block, laid out as fhe_rescale_checked_layout with n_parts = 2 (= out[3] when rescale == 0)
+ *   out[3]       total
+ * The one-shot hooks fhe_ctx_inject_fault_pointwise, fhe_ctx_inject_fault_keyswitch and fhe_ctx_inject_fault_rescale each fire
+ * in their own step.  A status returned by any step ends the call there.  Scope and statuses as above. */
+int fhe_hmult_checked_layout(const fhe_keyswitch *p, int rescale, int out[4]);
+int fhe_hmult_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_a0, const uint64_t *d_a1,
+                      const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a,
+                      uint32_t *d_flags, void *stream);
 
 /* ---- fault injection ---------------------------------------------------------------- */
 /* _flip_bit_kernel<<<1,1>>> (reliability_test/dotprod_test.cu:31-33,55): data[idx] ^= 1 << bit */
