@@ -13,6 +13,7 @@ from .engine import (  # noqa: F401
     BaseConv,
     KeySwitch,
     automorphism,
+    automorphism_checked,
     DeviceArray,
     Engine,
     NttTables,

@@ -99,6 +99,8 @@ _SIG = {
     "fhe_ctx_inject_fault_pointwise": (ci, [vp, ci, C.c_longlong, ci]),
     "fhe_automorphism": (ci, [vp, vp, vp, vp, C.c_uint32, sz, sz, sz, vp]),
     "fhe_automorphism_ntt": (ci, [vp, vp, vp, ci, C.c_uint32, sz, vp]),
+    "fhe_automorphism_ntt_checked": (ci, [vp, vp, vp, ci, C.c_uint32, sz, vp, vp]),
+    "fhe_ctx_inject_fault_galois": (ci, [vp, ci, ci, C.c_longlong, ci]),
     "fhe_keyswitch_create": (ci, [vp, vp, ci, ci, ci, C.POINTER(vp)]),
     "fhe_keyswitch_destroy": (ci, [vp]),
     "fhe_keyswitch_shard_layout": (ci, [ci, ci, ci, ci, C.POINTER(ci)]),
@@ -123,6 +125,9 @@ _SIG = {
     "fhe_hmult_checked": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp]),
     "fhe_galois_key_prepare": (ci, [vp, vp, vp, vp, C.c_uint32, vp]),
     "fhe_rotate_hoisted": (ci, [vp, vp, C.POINTER(vp), C.POINTER(vp), vp, vp, C.POINTER(C.c_uint32), C.POINTER(vp), sz, vp]),
+    "fhe_rotate_hoisted_checked_layout": (ci, [vp, sz, C.POINTER(ci)]),
+    "fhe_rotate_hoisted_checked": (ci, [vp, vp, C.POINTER(vp), C.POINTER(vp), vp, vp, C.POINTER(C.c_uint32), C.POINTER(vp), sz, vp, vp, vp]),
+    "fhe_ctx_inject_fault_rotate_hoisted": (ci, [vp, ci, ci, ci, ci, C.c_longlong, ci]),
     "fhe_rotate_hoisted_shard_begin": (ci, [vp, vp, vp, vp]),
     "fhe_rotate_hoisted_shard_extend": (ci, [vp, vp, vp]),
     "fhe_rotate_hoisted_shard_inner": (ci, [vp, vp, vp, vp, C.c_uint32, vp]),

@@ -1,8 +1,10 @@
 // capi_checked.hpp -- what the stage-by-stage checked composites share (capi_keyswitch_checked.cpp: key switch, relinearisation,
-// rotation; capi_hmult_checked.cpp: rescale, homomorphic multiply): the flag layout of the key switch, the one-shot fault record,
-// the checked-transform helper over the plan's scratch sums, and the checked key switch itself.
+// rotation; capi_hmult_checked.cpp: rescale, homomorphic multiply; capi_rotate_hoisted_checked.cpp: the Galois permutation and
+// hoisted rotations): the flag layout of the key switch, the one-shot fault record, the checked-transform helper over the plan's
+// scratch sums, and the checked key switch itself, whole and as its two halves.
 #pragma once
 #include "capi_internal.hpp"
+#include "galois_check.hpp"
 
 struct KscLayout {
     int off[8], total;
@@ -88,3 +90,38 @@ KscFault ksc_take_fault(fhe_ctx *ctx);
 int ksc_scope(const fhe_ctx *ctx, const fhe_keyswitch *p, const fhe_abft *a, const uint32_t *d_flags);
 int keyswitch_checked(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk, const uint64_t *d_add0,
                       const uint64_t *d_add1, const fhe_abft *a, uint32_t *d_flags, hipStream_t st, const KscFault &ft);
+
+// ---- the checked key switch as two halves (keyswitch_checked = front + back; hoisted rotations: one front, a back per element)
+// where each stage's flag words go: s[0..7] the stages of the key switch, s[8] the Galois permutation of a hoisted rotation.  The
+// caller clears them
+struct KscFlags {
+    u32 *s[9];
+};
+// a KscFault checked against the plan: the word a transform stage flips between its two launches, or the armed check record of a
+// residue stage (job = the digit of stage 1, the half of stage 5)
+struct KscHook {
+    int stage = -1, bit = 0, job = -1;
+    u64 *flip = nullptr;
+    BcCheck chk{nullptr, -1, 0, 0, 0};
+};
+int ksc_hook(const fhe_keyswitch *p, const KscFault &ft, u64 *acc, bool has_add0, bool has_add1, KscHook &h);
+// the permutation step of a hoisted rotation's back half: the sums ([2][M][N]) into acc_to, c0 ([L][N]) into c0_to
+struct KscPerm {
+    u32 galois_elt;
+    const u64 *c0;
+    u64 *acc_to, *c0_to;
+    GaloisFault fault;       // unit = half * M + row for the sums, 2 M + l for c0
+};
+int ksc_front(fhe_keyswitch *p, const uint64_t *d_c, const fhe_abft *a, const KscFlags &fl, hipStream_t st, const KscHook &h);
+int ksc_back(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk, const uint64_t *d_add0,
+             const uint64_t *d_add1, const fhe_abft *a, const KscFlags &fl, hipStream_t st, const KscHook &h, const KscPerm *perm);
+
+// defined in capi_rotate_hoisted_checked.cpp
+// the checked permutation of up to two row ranges that share one flags array (units counted through the segments in order, the
+// fault's unit too); the sums live in the context (grown on demand); every flag word is written
+struct GalSeg {
+    u64 *dst;
+    const u64 *src;
+    u32 units;
+};
+int galois_permute_checked(fhe_ctx *ctx, hipStream_t st, const GalSeg *segs, int n_segs, int logn, u32 galois_elt, u32 *d_flags, const GaloisFault &f);

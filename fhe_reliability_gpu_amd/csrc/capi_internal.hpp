@@ -120,6 +120,11 @@ struct fhe_ctx {
     long long ksc_fault_coeff = 0;                                                         // switch (fhe_ctx_inject_fault_keyswitch)
     int rsc_fault_stage = -1, rsc_fault_point = 0, rsc_fault_unit = 0, rsc_fault_bit = 0;   // one-shot bit flip inside the next checked
     long long rsc_fault_coeff = 0;                                                         // rescale (fhe_ctx_inject_fault_rescale)
+    int gal_fault_point = -1, gal_fault_unit = 0, gal_fault_bit = 0;   // one-shot bit flip inside the next checked Galois permutation
+    long long gal_fault_coeff = 0;                                     // (fhe_ctx_inject_fault_galois)
+    int hrc_fault_rot = 0, hrc_fault_stage = -1, hrc_fault_point = 0, hrc_fault_unit = 0, hrc_fault_bit = 0;   // one-shot bit flip inside the next
+    long long hrc_fault_coeff = 0;                                     // checked hoisted rotations (fhe_ctx_inject_fault_rotate_hoisted)
+    DevBuf gal_sums;       // checked Galois permutation: the units' source-side and destination-side sums, [2][units] (grown on demand)
     int geo = 1;           // column-tile geometry of the two-launch path (ntt_launch.hpp)
     bool resident = false; // 2^13 / 2^14: one LDS-resident pass instead of two launches (opt-in, see ntt_plan.hpp)
     int pingpong = -1;        // "ntt_pingpong": two-launch transforms hand over through a per-stream scratch buffer (both launches out of

@@ -13,6 +13,8 @@
 //   5  per half one checked exact conversion P -> Q into conv                                            (launch_baseconv_exact_checked)
 //   6  checked forward transform of conv                                                                 (launch_ntt_checked)
 //   7  tail (acc - conv) P^-1 (+ addends)                                                                (launch_sub_scale_checked)
+// keyswitch_checked = ksc_front (stages 0-2) + ksc_back (stages 3-7); the hoisted rotations of capi_rotate_hoisted_checked.cpp run the
+// front once and the back once per Galois element, with the checked Galois permutation between stages 3 and 4.
 // Each transform stage ends with launch_compare_sums on its units.  Every stage yields canonical residues and canonical residues are
 // unique, so the outputs are the unchecked call's words whatever its launch list was.
 #include "capi_checked.hpp"
@@ -54,139 +56,186 @@ int ksc_prepare(fhe_keyswitch *p)
     return FHE_OK;
 }
 
-int keyswitch_checked(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk,
-                      const uint64_t *d_add0, const uint64_t *d_add1, const fhe_abft *a, uint32_t *d_flags, hipStream_t st, const KscFault &ft)
+// the test hook of one checked key switch, checked against the call before anything is launched: which word a transform stage flips
+// between its two launches, which check record a residue stage arms.  acc = the sums stages 4 and 5 work on
+int ksc_hook(const fhe_keyswitch *p, const KscFault &ft, u64 *acc, bool has_add0, bool has_add1, KscHook &h)
 {
-    const fhe_ntt_tables *t = p->t;
-    const int L = p->L, K = p->K, M = L + K, dnum = p->dnum, logn = p->log_n;
+    const int L = p->L, K = p->K, M = L + K, logn = p->log_n;
     const size_t N = (size_t)1 << logn;
     const KscLayout lay = ksc_layout(p);
-    const LimbParams *lp = t->d_lp.as<LimbParams>();
-    u64 *coef = p->coef.as<u64>(), *ext = p->ext.as<u64>(), *acc = p->acc.as<u64>(), *conv = p->conv.as<u64>();
+    u64 *coef = p->coef.as<u64>(), *ext = p->ext.as<u64>(), *conv = p->conv.as<u64>();
+    h = KscHook{};
+    if (ft.stage < 0) return FHE_OK;
+    h.stage = ft.stage;
+    h.bit = ft.bit;
+    const bool tf = !(ft.stage & 1);      // a transform stage
+    const int units = (ft.stage == 7 ? lay.total : lay.off[ft.stage + 1]) - lay.off[ft.stage];
+    if (ft.unit >= units || (size_t)ft.coeff >= N) return fail(FHE_ERR_INVALID, "fault unit or coefficient outside the call");
+    if (tf && logn < 13) return fail(FHE_ERR_UNSUPPORTED, "the transform stages' fault point lies between their two launches: two-launch sizes only (N >= 2^13)");
+    const int u = ft.unit;
+    switch (ft.stage) {
+    case 0: h.flip = coef + (size_t)u * N + ft.coeff; break;
+    case 2: {
+        const int d = u / M, j = u % M;
+        if (j >= d * p->alpha && j < std::min(L, (d + 1) * p->alpha)) return fail(FHE_ERR_INVALID, "fault unit is one of the digit's own limbs, which stage 2 does not transform");
+        h.flip = ext + (size_t)u * N + ft.coeff;
+        break;
+    }
+    case 4: h.flip = acc + ((size_t)(u / K) * M + L + u % K) * N + ft.coeff; break;
+    case 6: h.flip = conv + (size_t)u * N + ft.coeff; break;
+    case 1: {
+        const int d = u / M, j = u % M, lo = d * p->alpha, hi = std::min(L, lo + p->alpha), m = hi - lo;
+        const int ju = j >= lo && j < hi ? j - lo : m + (j < lo ? j : j - m);
+        if (!bc_point_exists(ft.point, ju < m ? ju + 1 : m))
+            return fail(FHE_ERR_UNSUPPORTED, "fault point 3 (the running sum) needs a sum of two terms: not on a digit's first limb, not on a one-limb digit");
+        h.job = d;
+        h.chk = BcCheck{nullptr, ft.point, (u32)ju, (u64)ft.coeff, (u64)1 << ft.bit};
+        break;
+    }
+    case 5: {
+        const int ju = u % (K + L);
+        if (!bc_point_exists(ft.point, ju < K ? ju + 1 : K))
+            return fail(FHE_ERR_UNSUPPORTED, "fault point 3 (the running sum) needs a sum of two terms: not on the first special limb, not with K = 1");
+        h.job = u / (K + L);
+        h.chk = BcCheck{nullptr, ft.point, (u32)ju, (u64)ft.coeff, (u64)1 << ft.bit};
+        break;
+    }
+    case 3:
+        if (ft.point < 0 || ft.point > 3) return fail(FHE_ERR_INVALID, "bad fault point");
+        h.chk = BcCheck{nullptr, ft.point, (u32)u, (u64)ft.coeff, (u64)1 << ft.bit};
+        break;
+    default:
+        if (!ks_tail_point_exists(ft.point, u / L ? has_add1 : has_add0))
+            return fail(FHE_ERR_UNSUPPORTED, "fault point 3 (the running sum) of the tail exists only on a half with an addend");
+        h.chk = BcCheck{nullptr, ft.point, (u32)u, (u64)ft.coeff, (u64)1 << ft.bit};
+        break;
+    }
+    return FHE_OK;
+}
+
+namespace {
+
+BcCheck check_of(const KscHook &h, int stage, u32 *flags, int job)
+{
+    BcCheck k{flags, -1, 0, 0, 0};
+    if (h.stage == stage && h.job == job) {
+        k = h.chk;
+        k.flags = flags;
+    }
+    return k;
+}
+
+// the detector's partial sums live in the plan (ksc_prepare): the fhe_abft is only read
+KscNtt ksc_ntt(const fhe_keyswitch *p, const fhe_abft *a, hipStream_t st, bool inverse)
+{
+    u32 tin, tout;
+    ntt_checked_tiles(p->log_n, &tin, &tout, inverse);
+    return KscNtt{p, a, st, tin, tout, inverse};
+}
+
+} // namespace
+
+// stages 0-2: what does not depend on the key (nor, for hoisted rotations, on the Galois element)
+int ksc_front(fhe_keyswitch *p, const uint64_t *d_c, const fhe_abft *a, const KscFlags &fl, hipStream_t st, const KscHook &h)
+{
+    const int L = p->L, K = p->K, M = L + K, dnum = p->dnum;
+    const size_t N = (size_t)1 << p->log_n;
+    u64 *coef = p->coef.as<u64>(), *ext = p->ext.as<u64>();
     int rc;
     hipError_t e;
-    if ((rc = ksc_prepare(p))) return rc;
-
-    // ---- the test hook, checked against this call before anything is launched
-    const bool tf = ft.stage >= 0 && !(ft.stage & 1);      // a transform stage
-    u64 *flip = nullptr;
-    BcCheck hook{nullptr, -1, 0, 0, 0};                    // stages 1, 3, 5, 7: the armed check record (flags filled in per launch)
-    int hook_job = -1;                                     // stage 1: the digit, stage 5: the half
-    if (ft.stage >= 0) {
-        const int units = (ft.stage == 7 ? lay.total : lay.off[ft.stage + 1]) - lay.off[ft.stage];
-        if (ft.unit >= units || (size_t)ft.coeff >= N) return fail(FHE_ERR_INVALID, "fault unit or coefficient outside the call");
-        if (tf && logn < 13) return fail(FHE_ERR_UNSUPPORTED, "the transform stages' fault point lies between their two launches: two-launch sizes only (N >= 2^13)");
-        const int u = ft.unit;
-        switch (ft.stage) {
-        case 0: flip = coef + (size_t)u * N + ft.coeff; break;
-        case 2: {
-            const int d = u / M, j = u % M;
-            if (j >= d * p->alpha && j < std::min(L, (d + 1) * p->alpha)) return fail(FHE_ERR_INVALID, "fault unit is one of the digit's own limbs, which stage 2 does not transform");
-            flip = ext + (size_t)u * N + ft.coeff;
-            break;
-        }
-        case 4: flip = acc + ((size_t)(u / K) * M + L + u % K) * N + ft.coeff; break;
-        case 6: flip = conv + (size_t)u * N + ft.coeff; break;
-        case 1: {
-            const int d = u / M, j = u % M, lo = d * p->alpha, hi = std::min(L, lo + p->alpha), m = hi - lo;
-            const int ju = j >= lo && j < hi ? j - lo : m + (j < lo ? j : j - m);
-            if (!bc_point_exists(ft.point, ju < m ? ju + 1 : m))
-                return fail(FHE_ERR_UNSUPPORTED, "fault point 3 (the running sum) needs a sum of two terms: not on a digit's first limb, not on a one-limb digit");
-            hook_job = d;
-            hook = BcCheck{nullptr, ft.point, (u32)ju, (u64)ft.coeff, (u64)1 << ft.bit};
-            break;
-        }
-        case 5: {
-            const int ju = u % (K + L);
-            if (!bc_point_exists(ft.point, ju < K ? ju + 1 : K))
-                return fail(FHE_ERR_UNSUPPORTED, "fault point 3 (the running sum) needs a sum of two terms: not on the first special limb, not with K = 1");
-            hook_job = u / (K + L);
-            hook = BcCheck{nullptr, ft.point, (u32)ju, (u64)ft.coeff, (u64)1 << ft.bit};
-            break;
-        }
-        case 3:
-            if (ft.point < 0 || ft.point > 3) return fail(FHE_ERR_INVALID, "bad fault point");
-            hook = BcCheck{nullptr, ft.point, (u32)u, (u64)ft.coeff, (u64)1 << ft.bit};
-            break;
-        default:
-            if (!ks_tail_point_exists(ft.point, (u / L ? d_add1 : d_add0) != nullptr))
-                return fail(FHE_ERR_UNSUPPORTED, "fault point 3 (the running sum) of the tail exists only on a half with an addend");
-            hook = BcCheck{nullptr, ft.point, (u32)u, (u64)ft.coeff, (u64)1 << ft.bit};
-            break;
-        }
-    }
-    auto check_of = [&](int stage, u32 *flags, int job) {
-        BcCheck k{flags, -1, 0, 0, 0};
-        if (ft.stage == stage && hook_job == job) {
-            k = hook;
-            k.flags = flags;
-        }
-        return k;
-    };
-
-    // ---- the detector's partial sums live in the plan (ksc_prepare): the fhe_abft is only read
-    u32 tin_f, tout_f, tin_i, tout_i;
-    ntt_checked_tiles(logn, &tin_f, &tout_f, false);
-    ntt_checked_tiles(logn, &tin_i, &tout_i, true);
-    HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)lay.total * sizeof(u32), st));
     HIP_TRY(hipMemsetAsync(p->chk_bc_flags.p, 0, (size_t)dnum * M * sizeof(u32), st));
-    const KscNtt fwd{p, a, st, tin_f, tout_f, false}, inv{p, a, st, tin_i, tout_i, true};
+    const KscNtt fwd = ksc_ntt(p, a, st, false), inv = ksc_ntt(p, a, st, true);
 
     // ---- 0: opening INTT
     HIP_TRY(hipMemcpyAsync(coef, d_c, (size_t)L * N * 8, hipMemcpyDeviceToDevice, st));
-    if ((rc = inv.run({KscRows{coef, 0, 0, (u32)L, 1, (u32)L, 0}}, ft.stage == 0 ? flip : nullptr, ft.bit))) return rc;
-    if ((rc = inv.compare(d_flags + lay.off[0], 0, 0, (u32)L, (u32)L))) return rc;
+    if ((rc = inv.run({KscRows{coef, 0, 0, (u32)L, 1, (u32)L, 0}}, h.stage == 0 ? h.flip : nullptr, h.bit))) return rc;
+    if ((rc = inv.compare(fl.s[0], 0, 0, (u32)L, (u32)L))) return rc;
 
     // ---- 1: digit extension
     for (int d = 0; d < dnum; d++) {
-        const BcCheckedJob cj{p->up_host[d], p->up[d]->shoup_dig, p->up[d]->shoup_hor, check_of(1, p->chk_bc_flags.as<u32>() + (size_t)d * M, d)};
+        const BcCheckedJob cj{p->up_host[d], p->up[d]->shoup_dig, p->up[d]->shoup_hor, check_of(h, 1, p->chk_bc_flags.as<u32>() + (size_t)d * M, d)};
         if ((e = launch_baseconv_exact_checked(st, cj, N)) != hipSuccess) return hip_fail(e, "launch_baseconv_exact_checked");
     }
-    if ((e = launch_ks_flags_scatter(st, d_flags + lay.off[1], p->chk_bc_flags.as<u32>(), p->chk_bc_map.as<u32>(), (u32)(dnum * M))) != hipSuccess)
+    if ((e = launch_ks_flags_scatter(st, fl.s[1], p->chk_bc_flags.as<u32>(), p->chk_bc_map.as<u32>(), (u32)(dnum * M))) != hipSuccess)
         return hip_fail(e, "launch_ks_flags_scatter");
 
     // ---- 2: forward transform of the extended limbs (the sums of the digits' own limbs stay zero on both sides)
-    {
-        HIP_TRY(hipMemsetAsync(p->chk_sum_in.p, 0, (size_t)dnum * M * 8 * tin_f, st));
-        HIP_TRY(hipMemsetAsync(p->chk_sum_out.p, 0, (size_t)dnum * M * 8 * tout_f, st));
-        std::vector<KscRows> rows;
-        rows.push_back(KscRows{ext, (u32)L, (u32)L, (u32)K, (u32)dnum, (u32)M, 0});
-        for (int d = 0; d < dnum; d++) {
-            const int lo = d * p->alpha, hi = std::min(L, lo + p->alpha);
-            u64 *base = ext + (size_t)d * M * N;
-            if (lo > 0) rows.push_back(KscRows{base, 0, 0, (u32)lo, 1, (u32)M, (u32)(d * M)});
-            if (hi < L) rows.push_back(KscRows{base, (u32)hi, (u32)hi, (u32)(L - hi), 1, (u32)M, (u32)(d * M)});
-        }
-        if ((rc = fwd.run(rows, ft.stage == 2 ? flip : nullptr, ft.bit))) return rc;
-        if ((rc = fwd.compare(d_flags + lay.off[2], 0, 0, (u32)M, (u32)(dnum * M)))) return rc;
+    HIP_TRY(hipMemsetAsync(p->chk_sum_in.p, 0, (size_t)dnum * M * 8 * fwd.tin, st));
+    HIP_TRY(hipMemsetAsync(p->chk_sum_out.p, 0, (size_t)dnum * M * 8 * fwd.tout, st));
+    std::vector<KscRows> rows;
+    rows.push_back(KscRows{ext, (u32)L, (u32)L, (u32)K, (u32)dnum, (u32)M, 0});
+    for (int d = 0; d < dnum; d++) {
+        const int lo = d * p->alpha, hi = std::min(L, lo + p->alpha);
+        u64 *base = ext + (size_t)d * M * N;
+        if (lo > 0) rows.push_back(KscRows{base, 0, 0, (u32)lo, 1, (u32)M, (u32)(d * M)});
+        if (hi < L) rows.push_back(KscRows{base, (u32)hi, (u32)hi, (u32)(L - hi), 1, (u32)M, (u32)(d * M)});
     }
+    if ((rc = fwd.run(rows, h.stage == 2 ? h.flip : nullptr, h.bit))) return rc;
+    return fwd.compare(fl.s[2], 0, 0, (u32)M, (u32)(dnum * M));
+}
+
+// stages 3-7 on the digits ksc_front left in the plan.  perm (hoisted rotations): between stages 3 and 4 the sums and perm->c0 go
+// through the checked Galois permutation (stage 8, flags fl.s[8]); stages 4-7 then run on the permuted sums with sigma(c0) as d_add0
+int ksc_back(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk, const uint64_t *d_add0,
+             const uint64_t *d_add1, const fhe_abft *a, const KscFlags &fl, hipStream_t st, const KscHook &h, const KscPerm *perm)
+{
+    const int L = p->L, K = p->K, M = L + K, logn = p->log_n;
+    const size_t N = (size_t)1 << logn;
+    const LimbParams *lp = p->t->d_lp.as<LimbParams>();
+    u64 *acc = p->acc.as<u64>(), *conv = p->conv.as<u64>();
+    int rc;
+    hipError_t e;
+    const KscNtt fwd = ksc_ntt(p, a, st, false), inv = ksc_ntt(p, a, st, true);
 
     // ---- 3: inner product with the key
     {
-        const KsMacArgs ka{acc, ext, d_c, d_evk, lp, (u32)L, (u32)M, (u32)dnum, (u32)p->alpha, logn, (u32)L, 0u, 0u};
-        if ((e = launch_ks_mac_checked(st, ka, check_of(3, d_flags + lay.off[3], -1))) != hipSuccess) return hip_fail(e, "launch_ks_mac_checked");
+        const KsMacArgs ka{acc, p->ext.as<u64>(), d_c, d_evk, lp, (u32)L, (u32)M, (u32)p->dnum, (u32)p->alpha, logn, (u32)L, 0u, 0u};
+        if ((e = launch_ks_mac_checked(st, ka, check_of(h, 3, fl.s[3], -1))) != hipSuccess) return hip_fail(e, "launch_ks_mac_checked");
     }
 
-    // ---- 4: INTT of the special limbs of both halves, in place inside acc
-    if ((rc = inv.run({KscRows{acc, (u32)L, (u32)L, (u32)K, 2, (u32)M, 0}}, ft.stage == 4 ? flip : nullptr, ft.bit))) return rc;
-    for (int h = 0; h < 2; h++)
-        if ((rc = inv.compare(d_flags + lay.off[4] + h * K, (u32)(h * M + L), (u32)L, (u32)K, (u32)K))) return rc;
+    // ---- 8: sigma of the sums and of c0
+    if (perm) {
+        const GalSeg segs[2] = {{perm->acc_to, acc, (u32)(2 * M)}, {perm->c0_to, perm->c0, (u32)L}};
+        if ((rc = galois_permute_checked(p->ctx, st, segs, 2, logn, perm->galois_elt, fl.s[8], perm->fault))) return rc;
+        acc = perm->acc_to;
+        d_add0 = perm->c0_to;
+    }
+
+    // ---- 4: INTT of the special limbs of both halves, in place inside the sums
+    if ((rc = inv.run({KscRows{acc, (u32)L, (u32)L, (u32)K, 2, (u32)M, 0}}, h.stage == 4 ? h.flip : nullptr, h.bit))) return rc;
+    for (int hf = 0; hf < 2; hf++)
+        if ((rc = inv.compare(fl.s[4] + hf * K, (u32)(hf * M + L), (u32)L, (u32)K, (u32)K))) return rc;
 
     // ---- 5: mod-down conversion P -> Q
-    for (int h = 0; h < 2; h++) {
-        const BcJob job{p->down->dev, acc, conv + (size_t)h * L * N, 0xFFFFFFFFu, 0u, p->down_rows.as<u32>() + (size_t)h * K};
-        const BcCheckedJob cj{job, p->down->shoup_dig, p->down->shoup_hor, check_of(5, d_flags + lay.off[5] + h * (K + L), h)};
+    for (int hf = 0; hf < 2; hf++) {
+        const BcJob job{p->down->dev, acc, conv + (size_t)hf * L * N, 0xFFFFFFFFu, 0u, p->down_rows.as<u32>() + (size_t)hf * K};
+        const BcCheckedJob cj{job, p->down->shoup_dig, p->down->shoup_hor, check_of(h, 5, fl.s[5] + hf * (K + L), hf)};
         if ((e = launch_baseconv_exact_checked(st, cj, N)) != hipSuccess) return hip_fail(e, "launch_baseconv_exact_checked");
     }
 
     // ---- 6: forward transform of the converted limbs
-    if ((rc = fwd.run({KscRows{conv, 0, 0, (u32)L, 2, (u32)L, 0}}, ft.stage == 6 ? flip : nullptr, ft.bit))) return rc;
-    if ((rc = fwd.compare(d_flags + lay.off[6], 0, 0, (u32)L, (u32)(2 * L)))) return rc;
+    if ((rc = fwd.run({KscRows{conv, 0, 0, (u32)L, 2, (u32)L, 0}}, h.stage == 6 ? h.flip : nullptr, h.bit))) return rc;
+    if ((rc = fwd.compare(fl.s[6], 0, 0, (u32)L, (u32)(2 * L)))) return rc;
 
     // ---- 7: tail
     const SubScaleArgs sa{d_out0, d_out1, acc, conv, d_add0, p->pinv.as<u64>(), (u64)((size_t)M * N), (u64)((size_t)L * N), lp, 0u, (u32)L, logn, d_add1};
-    if ((e = launch_sub_scale_checked(st, sa, check_of(7, d_flags + lay.off[7], -1))) != hipSuccess) return hip_fail(e, "launch_sub_scale_checked");
+    if ((e = launch_sub_scale_checked(st, sa, check_of(h, 7, fl.s[7], -1))) != hipSuccess) return hip_fail(e, "launch_sub_scale_checked");
     return FHE_OK;
+}
+
+int keyswitch_checked(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk,
+                      const uint64_t *d_add0, const uint64_t *d_add1, const fhe_abft *a, uint32_t *d_flags, hipStream_t st, const KscFault &ft)
+{
+    int rc;
+    if ((rc = ksc_prepare(p))) return rc;
+    KscHook h;
+    if ((rc = ksc_hook(p, ft, p->acc.as<u64>(), d_add0 != nullptr, d_add1 != nullptr, h))) return rc;
+    const KscLayout lay = ksc_layout(p);
+    KscFlags fl{};
+    for (int s = 0; s < 8; s++) fl.s[s] = d_flags + lay.off[s];
+    HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)lay.total * sizeof(u32), st));
+    if ((rc = ksc_front(p, d_c, a, fl, st, h))) return rc;
+    return ksc_back(p, d_out0, d_out1, d_c, d_evk, d_add0, d_add1, a, fl, st, h, nullptr);
 }
 
 KscFault ksc_take_fault(fhe_ctx *ctx)

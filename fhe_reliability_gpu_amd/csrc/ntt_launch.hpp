@@ -319,4 +319,13 @@ struct RescaleReduceArgs {
 };
 hipError_t launch_rescale_reduce_checked(hipStream_t st, const RescaleReduceArgs &a, const BcCheck &k);
 
+// ---- galois_checked.hip: the NTT-domain Galois permutation with a position-weighted sum check per unit (galois_check.hpp) ----
+// launch_automorphism_ntt's words; adds the unit's source-side and destination-side sums into s_in / s_out ([units] each, zeroed by
+// the caller), kinv = k^-1 mod 2N; f.point >= 0: the one-shot test fault.  launch_galois_compare: flags[unit] = the sums differ
+// modulo 2^32 - 1 (every unit's word is written)
+struct GaloisFault;
+hipError_t launch_automorphism_ntt_checked(hipStream_t st, u64 *dst, const u64 *src, u64 *s_in, u64 *s_out, u32 units, int logn, u32 k, u32 kinv,
+                                           const GaloisFault &f);
+hipError_t launch_galois_compare(hipStream_t st, u32 *flags, const u64 *s_in, const u64 *s_out, u32 units);
+
 } // namespace fhe

@@ -459,6 +459,24 @@ def automorphism(eng: Engine, t: NttTables, src: DeviceArray, galois_elt: int, n
     return dst
 
 
+def _permute_checked(eng: Engine, dst: DeviceArray, src: DeviceArray, log_n: int, galois_elt: int, units: int, stream=None) -> np.ndarray:
+    flags = eng.upload(np.full((units + 1) // 2, 0xA5A5A5A5A5A5A5A5, dtype=_U64))      # the call writes every word itself
+    check(lib.fhe_automorphism_ntt_checked(eng._h, dst.ptr, src.ptr, log_n, galois_elt, units, flags.ptr, stream))
+    if stream is not None:
+        eng.sync(stream)
+    return flags.download().view(np.uint32)[:units].copy()
+
+
+def automorphism_checked(eng: Engine, t: NttTables, src: DeviceArray, galois_elt: int, n_poly: int = 1, limbs: Optional[int] = None):
+    """``automorphism(..., ntt_domain=True)`` with one check per unit (row of N words): ``(dst, flags[n_units])``.  The words
+    are the unchecked call's; flags[u] = 1 when the position-weighted sums of what row u read and of what it stored differ
+    modulo 2^32 - 1: every single-bit flip of a moved word, and a wrong source index on all but about N / 2^32 of random words."""
+    limbs = len(t) if limbs is None else limbs
+    dst = eng.alloc(src.size)
+    dst.shape = src.shape
+    return dst, _permute_checked(eng, dst, src, t.log_n, galois_elt, n_poly * limbs)
+
+
 class KeySwitch:
     """Hybrid RNS key switching over the primes of ``t`` (L ciphertext primes then K special primes,
     ``dnum`` digits); operation sequence of the reference's SEAL trace
@@ -605,6 +623,57 @@ class KeySwitch:
         of the two parts runs as a launch of its own and is not covered."""
         return self._checked(lambda o0, o1, fl: lib.fhe_rotate_checked(
             self.eng._h, self._h, o0.ptr, o1.ptr, c0.ptr, c1.ptr, galois_elt, galois_key.ptr, abft._h, fl.ptr, stream), stream)
+
+    # ---- checked hoisted rotations (capi_rotate_hoisted_checked.cpp) ----
+    HOISTED_ROT_STAGES = ("mac", "galois", "intt_special", "moddown", "ntt_conv", "tail")      # in execution order
+
+    def prepare_galois_key_checked(self, galois_key: DeviceArray, galois_elt: int, stream=None):
+        """``prepare_galois_key`` through the checked permutation: ``(key, flags[dnum, 2, M])``, one word per key row."""
+        M = self.L + self.K
+        out = self.eng.alloc(self.dnum * 2 * M * self.t.N)
+        out.shape = (self.dnum, 2, M, self.t.N)
+        kinv = pow(int(galois_elt), -1, 2 * self.t.N)
+        f = _permute_checked(self.eng, out, galois_key, self.t.log_n, kinv, self.dnum * 2 * M, stream)
+        return out, f.reshape(self.dnum, 2, M)
+
+    def rotate_hoisted_checked_layout(self, n_rot: int):
+        """``{"shared": {stage: (offset, shape)}, "rot": {stage: (offset inside a rotation's block, shape)}, "shared_words",
+        "rot_words", "total"}``; rotation r's block starts at ``shared_words + r * rot_words``.  Shared stages: ``intt_in [L]``,
+        ``extend [dnum][M]``, ``ntt_ext [dnum][M]``; per rotation, in execution order: ``mac [2][M]``, ``galois [2 M + L]`` (the sums'
+        rows half * M + row, then c0's rows), ``intt_special [2][K]``, ``moddown [2][K + L]``, ``ntt_conv [2][L]``, ``tail [2][L]``."""
+        out = (C.c_int * 12)()
+        check(lib.fhe_rotate_hoisted_checked_layout(self._h, n_rot, out))
+        L, K, d = self.L, self.K, self.dnum
+        M = L + K
+        shared = ((L,), (d, M), (d, M))
+        rot = ((2, M), (2 * M + L,), (2, K), (2, K + L), (2, L), (2, L))
+        return {"shared": {name: (int(out[s]), shared[s]) for s, name in enumerate(self.CHECKED_STAGES[:3])},
+                "rot": {name: (int(out[3 + i]), rot[i]) for i, name in enumerate(self.HOISTED_ROT_STAGES)},
+                "shared_words": int(out[9]), "rot_words": int(out[10]), "total": int(out[11])}
+
+    def rotate_hoisted_checked(self, c0: DeviceArray, c1: DeviceArray, galois_elts, prepared_keys, abft: "Abft", stream=None):
+        """``rotate_hoisted`` with every stage checked, the Galois permutation included: ``(outs, flags)``.  ``outs`` is a list of
+        (out0, out1) with ``rotate_hoisted``'s words bit for bit; ``flags = {"shared": {intt_in, extend, ntt_ext}, "rot": [{mac,
+        galois, intt_special, moddown, ntt_conv, tail}, ...]}`` as ``rotate_hoisted_checked_layout`` shapes them.  The shared stages
+        run once on the un-rotated c1; a fault there reaches every rotation, a fault in rotation r only its own words."""
+        n = len(galois_elts)
+        lay = self.rotate_hoisted_checked_layout(n)
+        outs = [(self._out(self.L), self._out(self.L)) for _ in range(n)]
+        a0 = (vp * max(1, n))(*[o[0].ptr for o in outs])
+        a1 = (vp * max(1, n))(*[o[1].ptr for o in outs])
+        ks = (vp * max(1, n))(*[k.ptr for k in prepared_keys])
+        ge = (C.c_uint32 * max(1, n))(*[int(g) for g in galois_elts])
+        total = lay["total"]
+        flags = self.eng.upload(np.full((total + 1) // 2, 0xA5A5A5A5A5A5A5A5, dtype=_U64))      # the call clears them itself
+        check(lib.fhe_rotate_hoisted_checked(self.eng._h, self._h, a0, a1, c0.ptr, c1.ptr, ge, ks, n, abft._h, flags.ptr, stream))
+        if stream is not None:
+            self.eng.sync(stream)
+        f = flags.download().view(np.uint32)[:total]
+
+        def cut(stages, base):
+            return {name: f[base + off:base + off + int(np.prod(shape))].reshape(shape).copy() for name, (off, shape) in stages.items()}
+        return outs, {"shared": cut(lay["shared"], 0),
+                      "rot": [cut(lay["rot"], lay["shared_words"] + r * lay["rot_words"]) for r in range(n)]}
 
     def rescale(self, c: DeviceArray, n_parts: int = 2, stream=None) -> DeviceArray:
         """``mod_switch_to_next_inplace`` (dotprod_test.cu:115): [n_parts][L][N] -> [n_parts][L-1][N]."""

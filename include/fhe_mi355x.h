@@ -545,8 +545,10 @@ int fhe_ctx_inject_fault_baseconv(fhe_ctx *ctx, int point, int unit, long long c
  * check starts from the registers its stage loaded); the Galois permutation of the checked rotation; operands raising bit 4.
  * Scope: a sharded plan returns FHE_ERR_INVALID; a plan with a plain modulus (BGV) FHE_ERR_UNSUPPORTED; a context with ntt_mode = 1,
  * ntt_resident or ntt_packed set, or N < 2^5, FHE_ERR_UNSUPPORTED.  The rescale and the homomorphic multiply have checked forms of
- * their own below.  What remains without a checked form: hoisted rotations, fhe_bsgs_matvec, sharded plans, BGV plans (plain
- * modulus) and the Galois permutation. */
+ * their own below, hoisted rotations and the Galois permutation further down.  What remains without a checked form:
+ * fhe_bsgs_matvec, sharded plans, BGV plans (plain modulus) and the permutation inside fhe_rotate_checked.  A caller who wants that
+ * last one checked composes it: fhe_automorphism_ntt_checked on c1 and on c0, then
+ * fhe_keyswitch_apply_checked(sigma(c1), galois key, d_add0 = sigma(c0)). */
 int fhe_keyswitch_checked_layout(const fhe_keyswitch *p, int out[10]);
 int fhe_keyswitch_apply_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c,
                                 const uint64_t *d_evk, const uint64_t *d_add0 /* optional */, const uint64_t *d_add1 /* optional */,
@@ -619,6 +621,55 @@ int fhe_hmult_checked_layout(const fhe_keyswitch *p, int rescale, int out[4]);
 int fhe_hmult_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_a0, const uint64_t *d_a1,
                       const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a,
                       uint32_t *d_flags, void *stream);
+
+/* ---- checked Galois permutation and checked hoisted rotations ----------------------------------------------------
+ * fhe_automorphism_ntt with one check per unit (a row of N words): d_dst[u][j] = d_src[u][pi_k(j)], pi_k the slot map of
+ * fhe_automorphism_ntt.  A permutation computes nothing, so the check is a position-weighted sum per unit modulo m = 2^32 - 1,
+ * r(x) = x mod m, w(j) = j + 1:
+ *     S_out = sum_j w(j) r(word stored at j)          from the register about to be stored and the destination index
+ *     S_in  = sum_i w(pi_kinv(i)) r(d_src[i])         from a second, linear read of d_src; kinv = k^-1 mod 2N, computed on the host
+ * pi_kinv is the inverse permutation, so the sums agree on a clean run; the two sides share neither the gathered register nor the
+ * index computation.  d_flags[u] = 1 where they differ (every word is written by the call, on `stream`).
+ * Coverage: every single-bit flip of a moved word (it shifts S_out by +-w 2^b, never 0 modulo m); a wrong source index that fetches
+ * x' for x unless w(j) (r(x') - r(x)) = 0 modulo m -- on random words with probability at most gcd(w(j), m) / m <= N / m.  Not
+ * covered: a wrong galois_elt handed in by the caller, faults already in d_src, a word corrupted in memory after its store.
+ * Words and argument rules are fhe_automorphism_ntt's: d_dst != d_src, odd element, n_units == 0 is a no-op.  The sums live in the
+ * context (allocated at first use, grown on demand): one checked permutation at a time per context. */
+int fhe_automorphism_ntt_checked(fhe_ctx *ctx, uint64_t *d_dst, const uint64_t *d_src, int log_n, uint32_t galois_elt, size_t n_units,
+                                 uint32_t *d_flags /* [n_units] */, void *stream);
+/* Test hook: one bit flip in the next fhe_automorphism_ntt_checked on this context, at word `coeff` of unit `unit` of the
+ * destination.  point 0: XOR bit `bit` (0-63) into the gathered word before it is stored and summed; point 1: XOR bit `bit`
+ * (< log_n) into the gather's source index.  A unit or coefficient outside the call, or point 1 with bit >= log_n, returns
+ * FHE_ERR_INVALID from the checked call, which launches nothing.  One shot (a refused call uses it up); point < 0 clears it. */
+int fhe_ctx_inject_fault_galois(fhe_ctx *ctx, int point, int unit, long long coeff, int bit);
+
+/* fhe_rotate_hoisted with every stage checked, the Galois permutation included.  sigma is a ring automorphism and the prepared
+ * keys are in the un-rotated frame, so the launch list is: stages 0, 1, 2 of the checked key switch ONCE on the un-rotated d_c1;
+ * then per rotation r stage 3 (inner product of the shared digits with d_prepared_keys[r]), stage 8 (the checked permutation of the
+ * 2 M rows of the sums and of the L rows of d_c0) and stages 4-7 on the rotated sums with sigma(c0) as the first part's addend.  All
+ * on `stream`; no side stream, no fusion.  Every d_out0[r] / d_out1[r] is fhe_rotate_hoisted's word, bit for bit, whichever
+ * route the unchecked call took (fused, grouped, two streams): canonical residues are unique.
+ * Flags (cleared by the call on `stream`), fhe_rotate_hoisted_checked_layout with M = L + K:
+ *   out[0..2]  offsets of stages 0-2 in the shared block, laid out as in fhe_keyswitch_checked_layout
+ *   out[3..8]  offsets inside one rotation's block, in execution order: stage 3 [2][M], stage 8 [2 M + L] (unit half * M + row for
+ *              the sums, then 2 M + l for row l of c0), stages 4 [2][K], 5 [2][K + L], 6 [2][L], 7 [2][L]
+ *   out[9]     words of the shared block, L + 2 dnum M;  out[10]  words of one rotation's block;  out[11]  total
+ * Rotation r's block starts at out[9] + r out[10].  Flag bits per stage as for the checked key switch; stage 8 holds 0 / 1.
+ * Localisation: a fault in a shared stage raises its own word and changes every rotation's output; a fault in rotation r raises
+ * its word in block r and leaves the other rotations' words and flags alone.
+ * Scope and statuses are the checked key switch's; argument rules are fhe_rotate_hoisted's (odd elements, out of place, distinct
+ * parts); n_rot == 0 returns FHE_OK and launches nothing.  The rotated sums use the plan's second set of sums (allocated at the
+ * first call that needs it).  Still without a checked form: fhe_bsgs_matvec, sharded plans, BGV plans. */
+int fhe_rotate_hoisted_checked_layout(const fhe_keyswitch *p, size_t n_rot, int out[12]);
+int fhe_rotate_hoisted_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *const *d_out0, uint64_t *const *d_out1, const uint64_t *d_c0,
+                               const uint64_t *d_c1, const uint32_t *galois_elts, const uint64_t *const *d_prepared_keys, size_t n_rot,
+                               const fhe_abft *a, uint32_t *d_flags, void *stream);
+/* Test hook of fhe_rotate_hoisted_checked, one shot: the next such call takes it whatever its outcome; stage < 0 clears it.  The call
+ * neither takes nor honours the other hooks.  Stages 0-7, their points, units and FHE_ERR_UNSUPPORTED cases are those of
+ * fhe_ctx_inject_fault_keyswitch (stage 7: the first half has an addend, the second has none); stage 8 takes the points of
+ * fhe_ctx_inject_fault_galois with unit indexing the rotation's [2 M + L] words.  `rot` is ignored for stages 0-2 and must be below
+ * n_rot for stages 3-8 (FHE_ERR_INVALID from the checked call otherwise). */
+int fhe_ctx_inject_fault_rotate_hoisted(fhe_ctx *ctx, int rot, int stage, int point, int unit, long long coeff, int bit);
 
 /* ---- fault injection ---------------------------------------------------------------- */
 /* _flip_bit_kernel<<<1,1>>> (reliability_test/dotprod_test.cu:31-33,55): data[idx] ^= 1 << bit */
