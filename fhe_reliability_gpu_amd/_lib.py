@@ -133,6 +133,9 @@ _SIG = {
     "fhe_rotate_hoisted_shard_inner": (ci, [vp, vp, vp, vp, C.c_uint32, vp]),
     "fhe_rotate_hoisted_shard_finish": (ci, [vp, vp, vp, vp, vp, C.c_uint32, vp]),
     "fhe_bsgs_matvec": (ci, [vp, vp, vp, vp, vp, vp, vp, sz, sz, C.POINTER(C.c_uint32), C.POINTER(vp), C.POINTER(C.c_uint32), C.POINTER(vp), vp]),
+    "fhe_bsgs_matvec_checked_layout": (ci, [vp, sz, sz, C.POINTER(ci)]),
+    "fhe_bsgs_matvec_checked": (ci, [vp, vp, vp, vp, vp, vp, vp, sz, sz, C.POINTER(C.c_uint32), C.POINTER(vp), C.POINTER(C.c_uint32), C.POINTER(vp), vp, vp, vp]),
+    "fhe_ctx_inject_fault_bsgs": (ci, [vp, ci, ci, ci, ci, C.c_longlong, ci]),
     "fhe_rotate_shard_begin": (ci, [vp, vp, vp, C.c_uint32, vp]),
     "fhe_rotate_shard_inner": (ci, [vp, vp, vp, vp]),
     "fhe_rotate_shard_finish": (ci, [vp, vp, vp, vp, vp, C.c_uint32, vp]),
@@ -144,6 +147,7 @@ _SIG = {
     "fhe_hmult_shard_finish_begin": (ci, [vp, vp, vp, vp, vp]),
     "fhe_hmult_shard_finish_end": (ci, [vp, vp, vp, vp, vp, vp, vp]),
     "fhe_modadd": (ci, [vp, vp, vp, vp, vp, sz, sz, sz, vp]),
+    "fhe_modadd_checked": (ci, [vp, vp, vp, vp, vp, sz, sz, sz, vp, vp]),
     "fhe_modsub": (ci, [vp, vp, vp, vp, vp, sz, sz, sz, vp]),
     "fhe_scalar_affine": (ci, [vp, vp, vp, p64, p64, vp, sz, sz, sz, vp]),
     "fhe_keyswitch_set_plain_modulus": (ci, [vp, u64]),

@@ -1,6 +1,6 @@
 // capi_checked.hpp -- what the stage-by-stage checked composites share (capi_keyswitch_checked.cpp: key switch, relinearisation,
 // rotation; capi_hmult_checked.cpp: rescale, homomorphic multiply; capi_rotate_hoisted_checked.cpp: the Galois permutation and
-// hoisted rotations): the flag layout of the key switch, the one-shot fault record, the checked-transform helper over the plan's
+// hoisted rotations; capi_bsgs_checked.cpp: the BSGS matrix-vector product and the checked add): the flag layout of the key switch, the one-shot fault record, the checked-transform helper over the plan's
 // scratch sums, and the checked key switch itself, whole and as its two halves.
 #pragma once
 #include "capi_internal.hpp"
@@ -125,3 +125,28 @@ struct GalSeg {
     u32 units;
 };
 int galois_permute_checked(fhe_ctx *ctx, hipStream_t st, const GalSeg *segs, int n_segs, int logn, u32 galois_elt, u32 *d_flags, const GaloisFault &f);
+
+// the checked hoisted rotations as a core (fhe_rotate_hoisted_checked; the baby block of fhe_bsgs_matvec_checked)
+struct HrcLayout {
+    int shared[3], rot[6];      // offsets of stages 0-2 in the shared block; of stages 3, 8, 4, 5, 6, 7 inside a rotation's block
+    int n_shared, n_rot;        // words of the shared block, of one rotation's block
+};
+HrcLayout hrc_layout(const fhe_keyswitch *p);
+struct HrcFault {
+    int rot = 0;
+    KscFault f;
+};
+// takes the context's one-shot hook of the hoisted rotations
+HrcFault hrc_take_fault(fhe_ctx *ctx);
+// an HrcFault checked against the plan and the number of rotations
+struct HrcHook {
+    int stage = -1, rot = 0;
+    KscHook hook;            // stages 0-7
+    GaloisFault gal;         // stage 8
+};
+int galois_fault_check(const GaloisFault &f, size_t units, int logn);
+// the plan's buffers (partial sums, second set of sums) and the hook's validation: before anything is launched
+int hrc_prepare(fhe_keyswitch *p, const HrcFault &ft, size_t n_rot, HrcHook &h);
+// the launches; d_flags = the shared block then one block per rotation (hrc_layout), cleared by the caller
+int hrc_run(fhe_keyswitch *p, uint64_t *const *d_out0, uint64_t *const *d_out1, const uint64_t *d_c0, const uint64_t *d_c1, const uint32_t *galois_elts,
+            const uint64_t *const *d_prepared_keys, size_t n_rot, const fhe_abft *a, uint32_t *d_flags, hipStream_t st, const HrcHook &h);

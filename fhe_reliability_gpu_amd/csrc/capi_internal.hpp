@@ -124,6 +124,8 @@ struct fhe_ctx {
     long long gal_fault_coeff = 0;                                     // (fhe_ctx_inject_fault_galois)
     int hrc_fault_rot = 0, hrc_fault_stage = -1, hrc_fault_point = 0, hrc_fault_unit = 0, hrc_fault_bit = 0;   // one-shot bit flip inside the next
     long long hrc_fault_coeff = 0;                                     // checked hoisted rotations (fhe_ctx_inject_fault_rotate_hoisted)
+    int bsgs_fault_g = 0, bsgs_fault_stage = -1, bsgs_fault_point = 0, bsgs_fault_unit = 0, bsgs_fault_bit = 0;   // one-shot bit flip inside the next
+    long long bsgs_fault_coeff = 0;                                    // checked BSGS product (fhe_ctx_inject_fault_bsgs)
     DevBuf gal_sums;       // checked Galois permutation: the units' source-side and destination-side sums, [2][units] (grown on demand)
     int geo = 1;           // column-tile geometry of the two-launch path (ntt_launch.hpp)
     bool resident = false; // 2^13 / 2^14: one LDS-resident pass instead of two launches (opt-in, see ntt_plan.hpp)

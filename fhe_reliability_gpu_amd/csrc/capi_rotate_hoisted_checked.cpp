@@ -13,13 +13,6 @@
 // residues of the same integers, so the words are fhe_rotate_hoisted's whichever route it took (fused, grouped, two streams).
 #include "capi_checked.hpp"
 
-namespace {
-
-struct HrcLayout {
-    int shared[3], rot[6];      // offsets of stages 0-2 in the shared block; of stages 3, 8, 4, 5, 6, 7 inside a rotation's block
-    int n_shared, n_rot;        // words of the shared block, of one rotation's block
-};
-
 HrcLayout hrc_layout(const fhe_keyswitch *p)
 {
     const int L = p->L, K = p->K, M = L + K;
@@ -34,11 +27,6 @@ HrcLayout hrc_layout(const fhe_keyswitch *p)
     }
     return l;
 }
-
-struct HrcFault {
-    int rot = 0;
-    KscFault f;
-};
 
 HrcFault hrc_take_fault(fhe_ctx *ctx)
 {
@@ -56,8 +44,6 @@ int galois_fault_check(const GaloisFault &f, size_t units, int logn)
     if (!galois_point_exists(f.point, f.bit, logn)) return fail(FHE_ERR_INVALID, "bad fault point: 0 takes a bit of the word, 1 a bit of the source index below log N");
     return FHE_OK;
 }
-
-} // namespace
 
 int galois_permute_checked(fhe_ctx *ctx, hipStream_t st, const GalSeg *segs, int n_segs, int logn, u32 galois_elt, u32 *d_flags, const GaloisFault &f)
 {
@@ -84,6 +70,51 @@ int galois_permute_checked(fhe_ctx *ctx, hipStream_t st, const GalSeg *segs, int
     }
     hipError_t e = launch_galois_compare(st, d_flags, s_in, s_out, (u32)units);
     return e == hipSuccess ? FHE_OK : hip_fail(e, "launch_galois_compare");
+}
+
+// the plan's buffers of the checked hoisted rotations and the test hook, checked against the call before anything is launched
+int hrc_prepare(fhe_keyswitch *p, const HrcFault &ft, size_t n_rot, HrcHook &h)
+{
+    int rc;
+    if ((rc = ksc_prepare(p))) return rc;
+    // the rotated sums go into the plan's second set of sums (the unchecked hoisted rotations' side-stream set; allocated by whichever
+    // call needs it first), sigma(c0) into the rotation buffer
+    if (!p->acc2.p) HIP_TRY(p->acc2.alloc(p->acc.bytes));
+    const int L = p->L, M = L + p->K;
+    h = HrcHook{};
+    if (ft.f.stage < 0) return FHE_OK;
+    if (ft.f.stage >= 3 && (size_t)ft.rot >= n_rot) return fail(FHE_ERR_INVALID, "fault rotation outside the call");
+    h.rot = ft.rot;
+    if (ft.f.stage == 8) {
+        h.gal = GaloisFault{ft.f.point, (u32)ft.f.unit, (u64)ft.f.coeff, ft.f.bit};
+        if ((rc = galois_fault_check(h.gal, (size_t)2 * M + L, p->log_n))) return rc;
+    } else if ((rc = ksc_hook(p, ft.f, p->acc2.as<u64>(), true, false, h.hook))) {
+        return rc;
+    }
+    h.stage = ft.f.stage;
+    return FHE_OK;
+}
+
+// the launches of the checked hoisted rotations; d_flags (the shared block, then one block per rotation) cleared by the caller
+int hrc_run(fhe_keyswitch *p, uint64_t *const *d_out0, uint64_t *const *d_out1, const uint64_t *d_c0, const uint64_t *d_c1, const uint32_t *galois_elts,
+            const uint64_t *const *d_prepared_keys, size_t n_rot, const fhe_abft *a, uint32_t *d_flags, hipStream_t st, const HrcHook &h)
+{
+    const HrcLayout lay = hrc_layout(p);
+    u64 *acc_rot = p->acc2.as<u64>(), *c0_rot = p->rot.as<u64>();
+    int rc;
+    KscFlags fl{};
+    for (int s = 0; s < 3; s++) fl.s[s] = d_flags + lay.shared[s];
+    if ((rc = ksc_front(p, d_c1, a, fl, st, h.hook))) return rc;
+    const KscHook none;
+    static const int stage_of[6] = {3, 8, 4, 5, 6, 7};
+    for (size_t r = 0; r < n_rot; r++) {
+        u32 *block = d_flags + lay.n_shared + r * lay.n_rot;
+        for (int i = 0; i < 6; i++) fl.s[stage_of[i]] = block + lay.rot[i];
+        const bool armed = h.stage >= 3 && (size_t)h.rot == r;
+        const KscPerm perm{galois_elts[r], d_c0, acc_rot, c0_rot, armed ? h.gal : GaloisFault{}};
+        if ((rc = ksc_back(p, d_out0[r], d_out1[r], d_c1, d_prepared_keys[r], nullptr, nullptr, a, fl, st, armed ? h.hook : none, &perm))) return rc;
+    }
+    return FHE_OK;
 }
 
 extern "C" {
@@ -167,42 +198,14 @@ int fhe_rotate_hoisted_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *const *
             return fail(FHE_ERR_INVALID, "rotate is out of place");
     }
     if (!n_rot) return FHE_OK;
-    const int L = p->L, M = L + p->K;
     const HrcLayout lay = hrc_layout(p);
     if (n_rot > (size_t)(0x7FFFFFFF - lay.n_shared) / (size_t)lay.n_rot) return fail(FHE_ERR_INVALID, "too many rotations for one flag buffer");
     HIP_TRY(hipSetDevice(ctx->device));
-    if ((rc = ksc_prepare(p))) return rc;
-    // the rotated sums go into the plan's second set of sums (the unchecked hoisted rotations' side-stream set; allocated by whichever
-    // call needs it first), sigma(c0) into the rotation buffer
-    if (!p->acc2.p) HIP_TRY(p->acc2.alloc(p->acc.bytes));
-    u64 *acc_rot = p->acc2.as<u64>(), *c0_rot = p->rot.as<u64>();
-
-    // ---- the test hook, checked against this call before anything is launched
-    KscHook hook;
-    GaloisFault gal{};
-    if (ft.f.stage >= 3 && (size_t)ft.rot >= n_rot) return fail(FHE_ERR_INVALID, "fault rotation outside the call");
-    if (ft.f.stage == 8) {
-        gal = GaloisFault{ft.f.point, (u32)ft.f.unit, (u64)ft.f.coeff, ft.f.bit};
-        if ((rc = galois_fault_check(gal, (size_t)2 * M + L, p->log_n))) return rc;
-    } else if ((rc = ksc_hook(p, ft.f, acc_rot, true, false, hook))) {
-        return rc;
-    }
-
+    HrcHook hook;
+    if ((rc = hrc_prepare(p, ft, n_rot, hook))) return rc;
     hipStream_t st = pick(ctx, stream);
     HIP_TRY(hipMemsetAsync(d_flags, 0, ((size_t)lay.n_shared + n_rot * lay.n_rot) * sizeof(u32), st));
-    KscFlags fl{};
-    for (int s = 0; s < 3; s++) fl.s[s] = d_flags + lay.shared[s];
-    if ((rc = ksc_front(p, d_c1, a, fl, st, hook))) return rc;
-    const KscHook none;
-    static const int stage_of[6] = {3, 8, 4, 5, 6, 7};
-    for (size_t r = 0; r < n_rot; r++) {
-        u32 *block = d_flags + lay.n_shared + r * lay.n_rot;
-        for (int i = 0; i < 6; i++) fl.s[stage_of[i]] = block + lay.rot[i];
-        const bool armed = ft.f.stage >= 3 && (size_t)ft.rot == r;
-        const KscPerm perm{galois_elts[r], d_c0, acc_rot, c0_rot, armed ? gal : GaloisFault{}};
-        if ((rc = ksc_back(p, d_out0[r], d_out1[r], d_c1, d_prepared_keys[r], nullptr, nullptr, a, fl, st, armed ? hook : none, &perm))) return rc;
-    }
-    return FHE_OK;
+    return hrc_run(p, d_out0, d_out1, d_c0, d_c1, galois_elts, d_prepared_keys, n_rot, a, d_flags, st, hook);
 }
 
 } // extern "C"

@@ -328,4 +328,10 @@ hipError_t launch_automorphism_ntt_checked(hipStream_t st, u64 *dst, const u64 *
                                            const GaloisFault &f);
 hipError_t launch_galois_compare(hipStream_t st, u32 *flags, const u64 *s_in, const u64 *s_out, u32 units);
 
+// ---- bsgs_checked.hip: the inner sum of the BSGS product and the modular add with a residue check per word (bsgs_check.hpp) ----
+// launch_diag_mac / launch_modadd with a check record: flags [2][limbs] (part, limb) / [units] (poly * limbs + l), zeroed by the
+// caller; fault_point >= 0: XOR fault_mask at that injection point of unit fault_unit (index into flags), coefficient fault_coeff
+hipError_t launch_diag_mac_checked(hipStream_t st, const DiagMacArgs &a, const BcCheck &k);
+hipError_t launch_modadd_checked(hipStream_t st, const PointwiseArgs &p, const BcCheck &k);
+
 } // namespace fhe

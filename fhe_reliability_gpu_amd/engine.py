@@ -203,6 +203,18 @@ class NttTables:
             self.eng.sync(stream)
         return flags.download().view(np.uint32)[:n].copy()
 
+    def modadd_checked(self, c: DeviceArray, a: DeviceArray, b: DeviceArray, limbs=None, start=0, n_poly=1, stream=None) -> np.ndarray:
+        """c = (a + b) mod q per limb with every word checked; the words are ``fhe_modadd``'s, bit for bit.  Returns
+        flags[poly * limbs + l] (uint32): 1 = r(c) + e r(q) == r(a) + r(b) failed modulo 2^32 - 1 (e = the conditional subtraction),
+        2 = the word out of its window, 4 = an operand not canonical, which the check cannot cover (bsgs_check.hpp)."""
+        limbs = len(self) - start if limbs is None else limbs
+        n = n_poly * limbs
+        flags = self.eng.upload(np.full((n + 1) // 2, 0xA5A5A5A5A5A5A5A5, dtype=_U64))      # the call clears them itself
+        check(lib.fhe_modadd_checked(self.eng._h, c.ptr, a.ptr, b.ptr, self._h, n_poly, limbs, start, flags.ptr, stream))
+        if stream is not None:
+            self.eng.sync(stream)
+        return flags.download().view(np.uint32)[:n].copy()
+
     def polymul(self, c: DeviceArray, a: DeviceArray, b: DeviceArray, limbs=None, start=0, n_poly=1, stream=None):
         limbs = len(self) - start if limbs is None else limbs
         check(lib.fhe_polymul(self.eng._h, c.ptr, a.ptr, b.ptr, self._h, n_poly, limbs, start, stream))
@@ -674,6 +686,55 @@ class KeySwitch:
             return {name: f[base + off:base + off + int(np.prod(shape))].reshape(shape).copy() for name, (off, shape) in stages.items()}
         return outs, {"shared": cut(lay["shared"], 0),
                       "rot": [cut(lay["rot"], lay["shared_words"] + r * lay["rot_words"]) for r in range(n)]}
+
+    # ---- checked BSGS matrix-vector product (capi_bsgs_checked.cpp) ----
+    BSGS_GIANT_STAGES = ("inner", "galois", "acc", "keyswitch")      # in execution order
+
+    def bsgs_matvec_checked_layout(self, n1: int, n2: int):
+        """``{"baby": 0, "baby_words", "giant0", "giant_words", "giant": {stage: (offset inside a giant block, shape)}, "total"}``.  The
+        baby block is laid out as ``rotate_hoisted_checked_layout(n1 - 1)`` (no words when n1 == 1); giant block g starts at
+        ``giant0 + g * giant_words`` and holds ``inner [2][L]``, ``galois [2 L]``, ``acc [L]`` and the key-switch block of
+        ``checked_layout`` (for g = 0 only ``inner`` runs, the other words stay 0)."""
+        out = (C.c_int * 8)()
+        check(lib.fhe_bsgs_matvec_checked_layout(self._h, n1, n2, out))
+        L = self.L
+        shapes = ((2, L), (2 * L,), (L,), (self.checked_layout()["total"],))
+        return {"baby": int(out[0]), "baby_words": int(out[1]), "giant0": int(out[1]), "giant_words": int(out[2]),
+                "giant": {name: (int(out[3 + i]), shapes[i]) for i, name in enumerate(self.BSGS_GIANT_STAGES)}, "total": int(out[7])}
+
+    def bsgs_matvec_checked(self, c0: DeviceArray, c1: DeviceArray, diags: DeviceArray, n1: int, n2: int, baby_elts, baby_keys_prepared,
+                            giant_elts, giant_keys, abft: "Abft", stream=None):
+        """``bsgs_matvec`` with every stage checked: ``(o0, o1, flags)``, the words ``bsgs_matvec``'s bit for bit.  ``flags = {"baby":
+        <as rotate_hoisted_checked> or None when n1 == 1, "giant": [{"inner": [2][L], "galois": [2 L], "acc": [L], "keyswitch": {the
+        eight stage names of checked_layout}}, ...]}``, one entry per giant step (for g = 0 only ``inner`` runs).  A fault raises the
+        word of the (block, stage, unit) it hit and no other."""
+        lay = self.bsgs_matvec_checked_layout(n1, n2)
+        total = lay["total"]
+        o0, o1 = self._out(self.L), self._out(self.L)
+        be = (C.c_uint32 * max(1, n1 - 1))(*[int(g) for g in baby_elts])
+        ge = (C.c_uint32 * max(1, n2 - 1))(*[int(g) for g in giant_elts])
+        bk = (vp * max(1, n1 - 1))(*[k.ptr for k in baby_keys_prepared])
+        gk = (vp * max(1, n2 - 1))(*[k.ptr for k in giant_keys])
+        flags = self.eng.upload(np.full((total + 1) // 2, 0xA5A5A5A5A5A5A5A5, dtype=_U64))      # the call clears them itself
+        check(lib.fhe_bsgs_matvec_checked(self.eng._h, self._h, o0.ptr, o1.ptr, c0.ptr, c1.ptr, diags.ptr, n1, n2, be, bk, ge, gk, abft._h, flags.ptr,
+                                          stream))
+        if stream is not None:
+            self.eng.sync(stream)
+        f = flags.download().view(np.uint32)[:total]
+
+        def cut(stages, base):
+            return {name: f[base + off:base + off + int(np.prod(shape))].reshape(shape).copy() for name, (off, shape) in stages.items()}
+        baby = None
+        if n1 > 1:
+            hl = self.rotate_hoisted_checked_layout(n1 - 1)
+            baby = {"shared": cut(hl["shared"], 0), "rot": [cut(hl["rot"], hl["shared_words"] + r * hl["rot_words"]) for r in range(n1 - 1)]}
+        giant = []
+        for g in range(n2):
+            base = lay["giant0"] + g * lay["giant_words"]
+            blk = cut({k: v for k, v in lay["giant"].items() if k != "keyswitch"}, base)
+            blk["keyswitch"] = self._split_flags(f, self.checked_layout(), self.CHECKED_STAGES, base + lay["giant"]["keyswitch"][0])
+            giant.append(blk)
+        return o0, o1, {"baby": baby, "giant": giant}
 
     def rescale(self, c: DeviceArray, n_parts: int = 2, stream=None) -> DeviceArray:
         """``mod_switch_to_next_inplace`` (dotprod_test.cu:115): [n_parts][L][N] -> [n_parts][L-1][N]."""

@@ -545,9 +545,9 @@ int fhe_ctx_inject_fault_baseconv(fhe_ctx *ctx, int point, int unit, long long c
  * check starts from the registers its stage loaded); the Galois permutation of the checked rotation; operands raising bit 4.
  * Scope: a sharded plan returns FHE_ERR_INVALID; a plan with a plain modulus (BGV) FHE_ERR_UNSUPPORTED; a context with ntt_mode = 1,
  * ntt_resident or ntt_packed set, or N < 2^5, FHE_ERR_UNSUPPORTED.  The rescale and the homomorphic multiply have checked forms of
- * their own below, hoisted rotations and the Galois permutation further down.  What remains without a checked form:
- * fhe_bsgs_matvec, sharded plans, BGV plans (plain modulus) and the permutation inside fhe_rotate_checked.  A caller who wants that
- * last one checked composes it: fhe_automorphism_ntt_checked on c1 and on c0, then
+ * their own below, hoisted rotations, the Galois permutation and the BSGS product further down.  What remains without a checked
+ * form: sharded plans, BGV plans (plain modulus) and the permutation inside fhe_rotate_checked.  A caller who wants that last one
+ * checked composes it: fhe_automorphism_ntt_checked on c1 and on c0, then
  * fhe_keyswitch_apply_checked(sigma(c1), galois key, d_add0 = sigma(c0)). */
 int fhe_keyswitch_checked_layout(const fhe_keyswitch *p, int out[10]);
 int fhe_keyswitch_apply_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c,
@@ -659,7 +659,7 @@ int fhe_ctx_inject_fault_galois(fhe_ctx *ctx, int point, int unit, long long coe
  * its word in block r and leaves the other rotations' words and flags alone.
  * Scope and statuses are the checked key switch's; argument rules are fhe_rotate_hoisted's (odd elements, out of place, distinct
  * parts); n_rot == 0 returns FHE_OK and launches nothing.  The rotated sums use the plan's second set of sums (allocated at the
- * first call that needs it).  Still without a checked form: fhe_bsgs_matvec, sharded plans, BGV plans. */
+ * first call that needs it).  Still without a checked form: sharded plans, BGV plans. */
 int fhe_rotate_hoisted_checked_layout(const fhe_keyswitch *p, size_t n_rot, int out[12]);
 int fhe_rotate_hoisted_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *const *d_out0, uint64_t *const *d_out1, const uint64_t *d_c0,
                                const uint64_t *d_c1, const uint32_t *galois_elts, const uint64_t *const *d_prepared_keys, size_t n_rot,
@@ -670,6 +670,64 @@ int fhe_rotate_hoisted_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *const *
  * fhe_ctx_inject_fault_galois with unit indexing the rotation's [2 M + L] words.  `rot` is ignored for stages 0-2 and must be below
  * n_rot for stages 3-8 (FHE_ERR_INVALID from the checked call otherwise). */
 int fhe_ctx_inject_fault_rotate_hoisted(fhe_ctx *ctx, int rot, int stage, int point, int unit, long long coeff, int bit);
+
+/* ---- checked modular add and checked BSGS matrix-vector product --------------------------------------------------
+ * fhe_modadd with every word checked: c = a + b - e q with e in {0, 1}, both operands reduced first as k_modadd reduces them.  Per
+ * word, with the 32-bit lane arithmetic of the checked products,
+ *     r(c) + e r(q) == r(a) + r(b)  (mod m = 2^32 - 1)      and the window c < q.
+ * Words are fhe_modadd's bit for bit for every input; argument and aliasing rules are fhe_modadd's (in place allowed).  Flags:
+ * d_flags[poly * limbs + l], cleared by the call on `stream`; bit 1 identity, bit 2 window, bit 4 an operand >= q -- folded as
+ * fhe_modadd folds it, not checked, raised alone.  fhe_ctx_inject_fault_pointwise is honoured with points 2 (the word before its
+ * window check) and 3 (a + b before the conditional subtraction); points 0 and 1 do not exist on an add: FHE_ERR_UNSUPPORTED,
+ * nothing launched.  The hook is used up either way. */
+int fhe_modadd_checked(fhe_ctx *ctx, uint64_t *d_c, const uint64_t *d_a, const uint64_t *d_b, const fhe_ntt_tables *t, size_t n_poly,
+                       size_t limbs, size_t start_idx, uint32_t *d_flags, void *stream);
+
+/* fhe_bsgs_matvec with every stage checked.  The launch list, all on `stream`, no side stream and no fusion:
+ *   baby block (n1 > 1)  the launches of fhe_rotate_hoisted_checked for the n1 - 1 baby elements, into the plan's BSGS scratch
+ *   per giant step g     inner sum  s_h = sum_b diag[g][b] sigma_b(x)_h of both parts h: per word and part
+ *                        r(c) + r(K) r(q) == sum_b r(d_b) r(y_b) (mod 2^32 - 1) and the windows of stage 3 of the checked key switch
+ *                        (the running sums are folded after every eighth term, as the unchecked kernel folds them);
+ *                        written straight into the outputs for g = 0
+ *     g >= 1             the checked Galois permutation of the 2 L rows of the inner sum, rows of part 0 first;
+ *                        the checked add t0 = out0 + sigma(s0);
+ *                        the checked key switch of sigma(s1) with the giant key and the addends (t0, out1), writing (out0, out1)
+ * The running result rides on the addends of the switch's tail, so a giant step needs one add launch, not two.  Every stage yields
+ * canonical residues, so d_out0 / d_out1 are fhe_bsgs_matvec's words bit for bit although the unchecked call adds in another order
+ * and takes sigma on loads.
+ * Flags, one buffer of out[7] words which the call clears on `stream` (fhe_bsgs_matvec_checked_layout):
+ *   out[0] = 0  the baby block, laid out as fhe_rotate_hoisted_checked_layout(n1 - 1); out[1] words, 0 when n1 == 1
+ *   out[1]      start of giant block 0;  out[2]  words of one giant block; block g starts at out[1] + g out[2]
+ *   out[3..6]   offsets inside a giant block: inner sum [2][L] (part * L + l; bits 1 / 2 / 4 as stage 3 of the checked key switch,
+ *               4: a diagonal word >= q on both parts, a ciphertext word >= q on its part), permutation [2 L] (0 / 1),
+ *               accumulate [L] (bits of fhe_modadd_checked), key switch (fhe_keyswitch_checked_layout).  For g = 0 only the
+ *               inner sum runs: the other words of block 0 stay 0.
+ *   out[7]      total
+ * The layout call returns FHE_ERR_INVALID for n1 or n2 outside 1 .. 4096 and for a total above INT_MAX.
+ * Localisation: a fault raises the word of the (block, stage, unit) it hit and no other; a baby-block fault changes the output and
+ * raises only its own word.  Not covered: faults already in the inputs, the diagonals or the keys; a word corrupted in memory
+ * between one stage's store and the next stage's load; operands raising bit 4.
+ * Scope and statuses are the checked key switch's (sharded plan FHE_ERR_INVALID, BGV plan FHE_ERR_UNSUPPORTED, N < 2^5
+ * FHE_ERR_UNSUPPORTED, ...); argument rules are fhe_bsgs_matvec's (out of place, distinct parts, n1, n2 from 1 to 4096).  The call
+ * uses the plan's BSGS scratch, both sets of sums, the rotation buffer and the check sums: one call at a time per plan.
+ * Test hooks: the call takes fhe_ctx_inject_fault_rotate_hoisted (fires in the baby block), fhe_ctx_inject_fault_galois and
+ * fhe_ctx_inject_fault_keyswitch (both fire in giant step g = 1, the key switch there has addends on both halves) and
+ * fhe_ctx_inject_fault_bsgs at entry, whatever its outcome, and validates them before the first launch; an armed hook whose step
+ * the call does not have (n1 == 1, n2 == 1) returns FHE_ERR_INVALID. */
+int fhe_bsgs_matvec_checked_layout(const fhe_keyswitch *p, size_t n1, size_t n2, int out[8]);
+int fhe_bsgs_matvec_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0, const uint64_t *d_c1,
+                            const uint64_t *d_diags, size_t n1, size_t n2, const uint32_t *baby_elts,
+                            const uint64_t *const *d_baby_keys_prepared, const uint32_t *giant_elts, const uint64_t *const *d_giant_keys,
+                            const fhe_abft *a, uint32_t *d_flags, void *stream);
+/* Test hook of the two stages fhe_bsgs_matvec_checked adds, one shot; stage < 0 clears it.  `g` is the giant step.
+ *   stage 0  the inner sum: unit = part * L + l, points 0-3 as stage 3 of fhe_ctx_inject_fault_keyswitch (0 the first term's product,
+ *            1 the final reduction's quotient estimate, 2 the word before its window check, 3 the running sum before its final
+ *            reduction)
+ *   stage 1  the accumulate: unit = l, point 2 the word before its window check, 3 the sum before the conditional subtraction;
+ *            points 0 and 1 return FHE_ERR_UNSUPPORTED from the checked call
+ * A g, unit or coefficient outside the call, and stage 1 with g = 0, return FHE_ERR_INVALID from the checked call.  A refused call
+ * launches nothing and uses the hook up. */
+int fhe_ctx_inject_fault_bsgs(fhe_ctx *ctx, int g, int stage, int point, int unit, long long coeff, int bit);
 
 /* ---- fault injection ---------------------------------------------------------------- */
 /* _flip_bit_kernel<<<1,1>>> (reliability_test/dotprod_test.cu:31-33,55): data[idx] ^= 1 << bit */
