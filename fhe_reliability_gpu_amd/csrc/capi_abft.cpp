@@ -233,15 +233,7 @@ int fhe_ntt_inverse_checked(fhe_ctx *ctx, uint64_t *d_data, const fhe_ntt_tables
 int fhe_ctx_inject_fault_polymul(fhe_ctx *ctx, int point, long long idx, int bit)
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
-    if (point < 0) {
-        ctx->pm_fault_point = -1;
-        return FHE_OK;
-    }
-    if (point > 3 || idx < 0 || bit < 0 || bit > 63) return fail(FHE_ERR_INVALID, "bad fault");
-    ctx->pm_fault_point = point;
-    ctx->pm_fault_idx = idx;
-    ctx->pm_fault_bit = bit;
-    return FHE_OK;
+    return ctx->pm_fault.arm(3, point, 0, idx, bit) ? FHE_OK : fail(FHE_ERR_INVALID, "bad fault");
 }
 
 int fhe_polymul_checked(fhe_ctx *ctx, uint64_t *d_c, uint64_t *d_a, uint64_t *d_b, const fhe_ntt_tables *t, const fhe_abft *a,
@@ -254,13 +246,13 @@ int fhe_polymul_checked(fhe_ctx *ctx, uint64_t *d_c, uint64_t *d_a, uint64_t *d_
     const size_t units = n_poly * limbs, N = (size_t)1 << t->log_n;
     const bool fused = ctx->mode == 0 && polymul_fused_supported(t->log_n);
     // one-shot test hook: check that its point exists for this call before anything is launched
-    const int point = ctx->pm_fault_point;
-    const long long fidx = ctx->pm_fault_idx;
-    ctx->pm_fault_point = -1;
+    const PointFault pf = ctx->pm_fault.take();
+    const int point = pf.point;
+    const u64 fidx = pf.coeff;
     if (point >= 0) {
         if (!fused || (point != 2 && t->log_n < 13))
             return fail(FHE_ERR_UNSUPPORTED, "fault point does not exist at this size / mode (0, 1, 3: two-launch sizes N >= 2^13; 2: the fused product)");
-        if ((size_t)fidx >= units * N) return fail(FHE_ERR_INVALID, "fault index outside the call's window");
+        if (fidx >= units * N) return fail(FHE_ERR_INVALID, "fault index outside the call's window");
     }
     if (!units) return FHE_OK;
     fhe_abft *m = const_cast<fhe_abft *>(a);
@@ -287,7 +279,7 @@ int fhe_polymul_checked(fhe_ctx *ctx, uint64_t *d_c, uint64_t *d_a, uint64_t *d_
         const size_t hit_unit = (size_t)fidx / N, hit_limb = hit_unit % limbs;
         rc = for_each_run(t, limbs, start_idx, [&](size_t off, size_t len, int path) -> int {
             PassArgs pa{d_a + off * N, t->d_lp.as<LimbParams>(), (u32)(start_idx + off), (u32)len, (u32)(n_poly * len), (u32)limbs};
-            PolymulChecks k{a->win.as<Tw>(), a->wout.as<Tw>(), a->wout8.as<u64>(), s, -1, nullptr, ctx->pm_fault_bit};
+            PolymulChecks k{a->win.as<Tw>(), a->wout.as<Tw>(), a->wout8.as<u64>(), s, -1, nullptr, pf.bit};
             auto rows = [&](PolymulSums &r, size_t o) {      // this launch's rows of the sums: unit (p0 * limbs + l0) of the call
                 r.ain += o * r.t_in, r.bin += o * r.t_in, r.aout += o * r.t_mid, r.bout += o * r.t_mid, r.cin += o * r.t_mid, r.cout += o * r.t_out;
             };
@@ -415,29 +407,7 @@ int fhe_ntt_forward_checked_phases(fhe_ctx *ctx, uint64_t *d_data, const fhe_ntt
 int fhe_ctx_inject_fault_pointwise(fhe_ctx *ctx, int point, long long idx, int bit)
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
-    if (point < 0) {
-        ctx->pw_fault_point = -1;
-        return FHE_OK;
-    }
-    if (point > 3 || idx < 0 || bit < 0 || bit > 63) return fail(FHE_ERR_INVALID, "bad fault");
-    ctx->pw_fault_point = point;
-    ctx->pw_fault_idx = idx;
-    ctx->pw_fault_bit = bit;
-    return FHE_OK;
-}
-
-// takes the one-shot hook for a call of `elems` elements; point 3 (the running sum) exists only where the call has one
-static int take_pointwise_fault(fhe_ctx *ctx, bool has_sum, size_t elems, PwCheck &k)
-{
-    const int point = ctx->pw_fault_point;
-    ctx->pw_fault_point = -1;
-    if (point < 0) return FHE_OK;
-    if (point == 3 && !has_sum) return fail(FHE_ERR_UNSUPPORTED, "fault point 3 (the running sum) exists only for fhe_modmul_acc_checked and fhe_tensor_product_checked");
-    if ((size_t)ctx->pw_fault_idx >= elems) return fail(FHE_ERR_INVALID, "fault index outside the call's window");
-    k.fault_point = point;
-    k.fault_idx = (u64)ctx->pw_fault_idx;
-    k.fault_mask = (u64)1 << ctx->pw_fault_bit;
-    return FHE_OK;
+    return ctx->pw_fault.arm(3, point, 0, idx, bit) ? FHE_OK : fail(FHE_ERR_INVALID, "bad fault");
 }
 
 static int modmul_checked(fhe_ctx *ctx, u64 *c, const u64 *a, const u64 *b, const fhe_ntt_tables *t, size_t n_poly, size_t limbs,
@@ -448,7 +418,7 @@ static int modmul_checked(fhe_ctx *ctx, u64 *c, const u64 *a, const u64 *b, cons
     if (rc) return rc;
     const size_t units = n_poly * limbs;
     PwCheck k{d_flags, -1, 0, 0};
-    if ((rc = take_pointwise_fault(ctx, acc, units << t->log_n, k))) return rc;
+    if ((rc = pointwise_fault(ctx->pw_fault.take(), acc, units << t->log_n, k))) return rc;
     if (!units) return FHE_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = pick(ctx, stream);
@@ -479,7 +449,7 @@ int fhe_tensor_product_checked(fhe_ctx *ctx, uint64_t *d_d0, uint64_t *d_d1, uin
     int rc = check_range(t, 1, limbs, start_idx);
     if (rc) return rc;
     PwCheck k{d_flags, -1, 0, 0};
-    if ((rc = take_pointwise_fault(ctx, true, limbs << t->log_n, k))) return rc;
+    if ((rc = pointwise_fault(ctx->pw_fault.take(), true, limbs << t->log_n, k))) return rc;
     if (!limbs) return FHE_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = pick(ctx, stream);

@@ -2,20 +2,15 @@
 #include "capi_internal.hpp"
 #include "baseconv_check.hpp"
 
-// takes the one-shot hook of fhe_ctx_inject_fault_baseconv for a call with `units` flag words; terms(unit) = number of terms
-// of that unit's sum (the running-sum point needs two)
+// the hook of fhe_ctx_inject_fault_baseconv as a call with `units` flag words took it, checked against that call; terms(unit) =
+// number of terms of that unit's sum (the running-sum point needs two)
 template <class Terms>
-static int take_baseconv_fault(fhe_ctx *ctx, int units, size_t N, Terms terms, BcCheck &k)
+static int baseconv_fault(const PointFault &f, int units, size_t N, Terms terms, BcCheck &k)
 {
-    const int point = ctx->bc_fault_point;
-    ctx->bc_fault_point = -1;
-    if (point < 0) return FHE_OK;
-    if (ctx->bc_fault_unit >= units || (size_t)ctx->bc_fault_coeff >= N) return fail(FHE_ERR_INVALID, "fault unit or coefficient outside the call");
-    if (!bc_point_exists(point, terms(ctx->bc_fault_unit))) return fail(FHE_ERR_UNSUPPORTED, "fault point 3 (the running sum) needs a sum of two terms: not on digit 0, not on a one-limb base");
-    k.fault_point = point;
-    k.fault_unit = (u32)ctx->bc_fault_unit;
-    k.fault_coeff = (u64)ctx->bc_fault_coeff;
-    k.fault_mask = (u64)1 << ctx->bc_fault_bit;
+    if (f.point < 0) return FHE_OK;
+    if (f.unit >= (u32)units || f.coeff >= N) return fail(FHE_ERR_INVALID, "fault unit or coefficient outside the call");
+    if (!bc_point_exists(f.point, terms((int)f.unit))) return fail(FHE_ERR_UNSUPPORTED, "fault point 3 (the running sum) needs a sum of two terms: not on digit 0, not on a one-limb base");
+    k = BcCheck{k.flags, f.point, f.unit, f.coeff, (u64)1 << f.bit};
     return FHE_OK;
 }
 
@@ -172,29 +167,18 @@ int fhe_baseconv_fast(fhe_ctx *ctx, uint64_t *d_out, const uint64_t *d_in, const
 int fhe_ctx_inject_fault_baseconv(fhe_ctx *ctx, int point, int unit, long long coeff, int bit)
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
-    if (point < 0) {
-        ctx->bc_fault_point = -1;
-        return FHE_OK;
-    }
-    if (point > 3 || unit < 0 || coeff < 0 || bit < 0 || bit > 63) return fail(FHE_ERR_INVALID, "bad fault");
-    ctx->bc_fault_point = point;
-    ctx->bc_fault_unit = unit;
-    ctx->bc_fault_coeff = coeff;
-    ctx->bc_fault_bit = bit;
-    return FHE_OK;
+    return ctx->bc_fault.arm(3, point, unit, coeff, bit) ? FHE_OK : fail(FHE_ERR_INVALID, "bad fault");
 }
 
 int fhe_baseconv_exact_checked(fhe_ctx *ctx, uint64_t *d_out, const uint64_t *d_in, const fhe_baseconv *p, size_t N, uint32_t *d_flags,
                                void *stream)
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
-    if (!d_out || !d_in || !p || !d_flags) {
-        ctx->bc_fault_point = -1;       // (a refused call uses the hook up as well)
-        return fail(FHE_ERR_INVALID, "null argument");
-    }
+    const PointFault f = ctx->bc_fault.take();       // (a refused call uses the hook up as well)
+    if (!d_out || !d_in || !p || !d_flags) return fail(FHE_ERR_INVALID, "null argument");
     BcCheck k{d_flags, -1, 0, 0, 0};
     const int m = p->m, units = p->m + p->k;
-    int rc = take_baseconv_fault(ctx, units, N, [&](int unit) { return unit < m ? unit + 1 : m; }, k);
+    int rc = baseconv_fault(f, units, N, [&](int unit) { return unit < m ? unit + 1 : m; }, k);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = pick(ctx, stream);
@@ -209,12 +193,10 @@ int fhe_baseconv_fast_checked(fhe_ctx *ctx, uint64_t *d_out, const uint64_t *d_i
                               void *stream)
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
-    if (!d_out || !d_in || !p || !d_flags) {
-        ctx->bc_fault_point = -1;
-        return fail(FHE_ERR_INVALID, "null argument");
-    }
+    const PointFault f = ctx->bc_fault.take();
+    if (!d_out || !d_in || !p || !d_flags) return fail(FHE_ERR_INVALID, "null argument");
     BcCheck k{d_flags, -1, 0, 0, 0};
-    int rc = take_baseconv_fault(ctx, p->k, N, [&](int) { return p->m; }, k);
+    int rc = baseconv_fault(f, p->k, N, [&](int) { return p->m; }, k);
     if (!p->fast_ok) return fail(FHE_ERR_UNSUPPORTED, "unreduced sum would exceed 64 bits (m * max q >= 2^64)");
     if (rc) return rc;
     HIP_TRY(hipSetDevice(ctx->device));

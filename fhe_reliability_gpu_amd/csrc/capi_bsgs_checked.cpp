@@ -41,18 +41,6 @@ BmcLayout bmc_layout(const fhe_keyswitch *p, size_t n1, size_t n2)
     return l;
 }
 
-struct BmcFault {
-    int g = 0, stage = -1, point = 0, unit = 0, bit = 0;
-    long long coeff = 0;
-};
-
-BmcFault bmc_take_fault(fhe_ctx *ctx)
-{
-    const BmcFault f{ctx->bsgs_fault_g, ctx->bsgs_fault_stage, ctx->bsgs_fault_point, ctx->bsgs_fault_unit, ctx->bsgs_fault_bit, ctx->bsgs_fault_coeff};
-    ctx->bsgs_fault_stage = -1;
-    return f;
-}
-
 bool bsgs_shape_ok(size_t n1, size_t n2) { return n1 >= 1 && n2 >= 1 && n1 <= 4096 && n2 <= 4096; }
 
 } // namespace
@@ -64,19 +52,16 @@ int fhe_modadd_checked(fhe_ctx *ctx, uint64_t *c, const uint64_t *a, const uint6
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
     // the one-shot pointwise hook belongs to this call whatever its outcome
-    const int point = ctx->pw_fault_point, bit = ctx->pw_fault_bit;
-    const long long idx = ctx->pw_fault_idx;
-    ctx->pw_fault_point = -1;
+    const PointFault f = ctx->pw_fault.take();
     if (!c || !a || !b || !d_flags) return fail(FHE_ERR_INVALID, "null argument");
     int rc = check_range(t, n_poly, limbs, start_idx);
     if (rc) return rc;
     const size_t units = n_poly * limbs;
-    BcCheck k{d_flags, -1, 0, 0, 0};
-    if (point >= 0) {
-        if (!modadd_point_exists(point)) return fail(FHE_ERR_UNSUPPORTED, "fault points 0 (product) and 1 (quotient) do not exist on an add: 2 is the word, 3 the sum a + b");
-        if ((size_t)idx >= units << t->log_n) return fail(FHE_ERR_INVALID, "fault index outside the call's window");
-        k = BcCheck{d_flags, point, (u32)((size_t)idx >> t->log_n), (u64)idx & (((u64)1 << t->log_n) - 1), (u64)1 << bit};
-    }
+    if (f.point >= 0 && !modadd_point_exists(f.point)) return fail(FHE_ERR_UNSUPPORTED, "fault points 0 (product) and 1 (quotient) do not exist on an add: 2 is the word, 3 the sum a + b");
+    PwCheck pk{d_flags, -1, 0, 0};
+    if ((rc = pointwise_fault(f, true, units << t->log_n, pk))) return rc;
+    // the add's check record addresses (unit, coefficient)
+    const BcCheck k{d_flags, pk.fault_point, (u32)(pk.fault_idx >> t->log_n), pk.fault_idx & (((u64)1 << t->log_n) - 1), pk.fault_mask};
     if (!units) return FHE_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = pick(ctx, stream);
@@ -103,18 +88,7 @@ int fhe_bsgs_matvec_checked_layout(const fhe_keyswitch *p, size_t n1, size_t n2,
 int fhe_ctx_inject_fault_bsgs(fhe_ctx *ctx, int g, int stage, int point, int unit, long long coeff, int bit)
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
-    if (stage < 0) {
-        ctx->bsgs_fault_stage = -1;
-        return FHE_OK;
-    }
-    if (stage > 1 || g < 0 || point < 0 || point > 3 || unit < 0 || coeff < 0 || bit < 0 || bit > 63) return fail(FHE_ERR_INVALID, "bad fault");
-    ctx->bsgs_fault_g = g;
-    ctx->bsgs_fault_stage = stage;
-    ctx->bsgs_fault_point = point;
-    ctx->bsgs_fault_unit = unit;
-    ctx->bsgs_fault_coeff = coeff;
-    ctx->bsgs_fault_bit = bit;
-    return FHE_OK;
+    return ctx->bsgs_fault.arm(BSGS_RULES, g, stage, point, unit, coeff, bit) ? FHE_OK : fail(FHE_ERR_INVALID, "bad fault");
 }
 
 int fhe_bsgs_matvec_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0, const uint64_t *d_c1,
@@ -123,11 +97,8 @@ int fhe_bsgs_matvec_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, ui
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
     // the one-shot hooks of the steps this call runs belong to it whatever its outcome: all are taken here
-    const HrcFault hf = hrc_take_fault(ctx);
-    const KscFault kf = ksc_take_fault(ctx);
-    const GaloisFault gf{ctx->gal_fault_point, (u32)ctx->gal_fault_unit, (u64)ctx->gal_fault_coeff, ctx->gal_fault_bit};
-    ctx->gal_fault_point = -1;
-    const BmcFault bf = bmc_take_fault(ctx);
+    const StagedFault hf = ctx->hrc_fault.take(), kf = ctx->ksc_fault.take(), bf = ctx->bsgs_fault.take();
+    const GaloisFault gf = ctx->gal_fault.take();
     int rc = ksc_scope(ctx, p, a, d_flags);
     if (rc) return rc;
     if (!d_out0 || !d_out1 || !d_c0 || !d_c1 || !d_diags || !bsgs_shape_ok(n1, n2)) return fail(FHE_ERR_INVALID, "bad arguments");
@@ -149,7 +120,7 @@ int fhe_bsgs_matvec_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, ui
         if ((rc = hrc_prepare(p, hf, n1 - 1, hh))) return rc;
     } else {
         if ((rc = ksc_prepare(p))) return rc;
-        if (hf.f.stage >= 0) return fail(FHE_ERR_INVALID, "hoisted-rotation fault outside the call: n1 = 1 has no baby block");
+        if (hf.stage >= 0) return fail(FHE_ERR_INVALID, "hoisted-rotation fault outside the call: n1 = 1 has no baby block");
     }
     if ((kf.stage >= 0 || gf.point >= 0) && n2 < 2) return fail(FHE_ERR_INVALID, "key-switch or Galois fault outside the call: n2 = 1 has no giant rotation");
     if ((rc = galois_fault_check(gf, (size_t)2 * L, logn))) return rc;
@@ -158,7 +129,7 @@ int fhe_bsgs_matvec_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, ui
         if ((rc = ksc_hook(p, kf, p->acc.as<u64>(), true, true, probe))) return rc;
     }
     if (bf.stage >= 0) {
-        if ((size_t)bf.g >= n2 || (bf.stage == 1 && bf.g == 0)) return fail(FHE_ERR_INVALID, "fault giant step outside the call (the accumulate starts at g = 1)");
+        if ((size_t)bf.block >= n2 || (bf.stage == 1 && bf.block == 0)) return fail(FHE_ERR_INVALID, "fault giant step outside the call (the accumulate starts at g = 1)");
         if (bf.unit >= (bf.stage == 0 ? 2 * L : L) || (size_t)bf.coeff >= N) return fail(FHE_ERR_INVALID, "fault unit or coefficient outside the call");
         if (bf.stage == 1 && !modadd_point_exists(bf.point))
             return fail(FHE_ERR_UNSUPPORTED, "fault points 0 (product) and 1 (quotient) do not exist on the accumulate: 2 is the word, 3 the sum a + b");
@@ -185,16 +156,12 @@ int fhe_bsgs_matvec_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, ui
     }
 
     const LimbParams *lp = p->t->d_lp.as<LimbParams>();
-    const auto armed = [&](int stage, size_t g, u32 *flags) {
-        if (bf.stage != stage || (size_t)bf.g != g) return BcCheck{flags, -1, 0, 0, 0};
-        return BcCheck{flags, bf.point, (u32)bf.unit, (u64)bf.coeff, (u64)1 << bf.bit};
-    };
     for (size_t g = 0; g < n2; g++) {
         u32 *block = d_flags + lay.baby + g * lay.giant;
         // ---- inner sum of giant step g: straight into the result for g = 0
         u64 *s0 = g ? inner : d_out0, *s1 = g ? inner + part : d_out1;
         const DiagMacArgs da{s0, s1, d_diags + g * n1 * part, d_c0, d_c1, rot, lp, 0u, (u32)L, (u32)n1, logn};
-        hipError_t e = launch_diag_mac_checked(st, da, armed(0, g, block + lay.off[0]));
+        hipError_t e = launch_diag_mac_checked(st, da, bc_check(bf.at((int)g, 0), block + lay.off[0]));
         if (e != hipSuccess) return hip_fail(e, "launch_diag_mac_checked");
         if (!g) continue;
         // ---- sigma of both parts of the inner sum
@@ -202,9 +169,9 @@ int fhe_bsgs_matvec_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, ui
         if ((rc = galois_permute_checked(ctx, st, &seg, 1, logn, giant_elts[g - 1], block + lay.off[1], g == 1 ? gf : GaloisFault{}))) return rc;
         // ---- t0 = out0 + sigma(s0), in place over sigma(s0)
         const PointwiseArgs pa{tmp, d_out0, tmp, lp, 0u, (u32)L, (u32)L, (u32)L, logn};
-        if ((e = launch_modadd_checked(st, pa, armed(1, g, block + lay.off[2]))) != hipSuccess) return hip_fail(e, "launch_modadd_checked");
+        if ((e = launch_modadd_checked(st, pa, bc_check(bf.at((int)g, 1), block + lay.off[2]))) != hipSuccess) return hip_fail(e, "launch_modadd_checked");
         // ---- (out0, out1) = key switch of sigma(s1) + (t0, out1)
-        if ((rc = keyswitch_checked(p, d_out0, d_out1, tmp + part, d_giant_keys[g - 1], tmp, d_out1, a, block + lay.off[3], st, g == 1 ? kf : KscFault{}))) return rc;
+        if ((rc = keyswitch_checked(p, d_out0, d_out1, tmp + part, d_giant_keys[g - 1], tmp, d_out1, a, block + lay.off[3], st, g == 1 ? kf : StagedFault{}))) return rc;
     }
     return FHE_OK;
 }

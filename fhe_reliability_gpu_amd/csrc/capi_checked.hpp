@@ -1,7 +1,8 @@
 // capi_checked.hpp -- what the stage-by-stage checked composites share (capi_keyswitch_checked.cpp: key switch, relinearisation,
 // rotation; capi_hmult_checked.cpp: rescale, homomorphic multiply; capi_rotate_hoisted_checked.cpp: the Galois permutation and
-// hoisted rotations; capi_bsgs_checked.cpp: the BSGS matrix-vector product and the checked add): the flag layout of the key switch, the one-shot fault record, the checked-transform helper over the plan's
-// scratch sums, and the checked key switch itself, whole and as its two halves.
+// hoisted rotations; capi_bsgs_checked.cpp: the BSGS matrix-vector product and the checked add): the flag layout of the key switch,
+// the checked-transform helper over the plan's scratch sums, and the checked key switch itself, whole and as its two halves.  The
+// one-shot fault records are those of fault_hook.hpp.
 #pragma once
 #include "capi_internal.hpp"
 #include "galois_check.hpp"
@@ -18,11 +19,6 @@ inline size_t ksc_slots(const fhe_keyswitch *p)
 {
     return std::max((size_t)std::max(p->dnum, 2) * (p->L + p->K), (size_t)3 * std::max(p->L - 1, 0));
 }
-
-struct KscFault {
-    int stage = -1, point = 0, unit = 0, bit = 0;
-    long long coeff = 0;
-};
 
 // the transforms of one checked stage: rows [row0, row0 + count) of n_poly polynomials `stride` rows apart inside base, row r on
 // table limb tl0 + (r - row0); the sums of (polynomial, row) live at slot sum0 + polynomial * stride + row
@@ -84,12 +80,12 @@ struct KscNtt {
 // defined in capi_keyswitch_checked.cpp
 // the flag map of stage 1, its job-order scratch and the detector's partial sums, once per plan
 int ksc_prepare(fhe_keyswitch *p);
-// takes the context's one-shot key-switch hook
-KscFault ksc_take_fault(fhe_ctx *ctx);
+// the checked transforms of one direction; the detector's partial sums live in the plan (ksc_prepare): the fhe_abft is only read
+KscNtt ksc_ntt(const fhe_keyswitch *p, const fhe_abft *a, hipStream_t st, bool inverse);
 // scope of every stage-by-stage checked call: the plan, the detector and the context's transform variants
 int ksc_scope(const fhe_ctx *ctx, const fhe_keyswitch *p, const fhe_abft *a, const uint32_t *d_flags);
 int keyswitch_checked(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk, const uint64_t *d_add0,
-                      const uint64_t *d_add1, const fhe_abft *a, uint32_t *d_flags, hipStream_t st, const KscFault &ft);
+                      const uint64_t *d_add1, const fhe_abft *a, uint32_t *d_flags, hipStream_t st, const StagedFault &ft);
 
 // ---- the checked key switch as two halves (keyswitch_checked = front + back; hoisted rotations: one front, a back per element)
 // where each stage's flag words go: s[0..7] the stages of the key switch, s[8] the Galois permutation of a hoisted rotation.  The
@@ -97,14 +93,14 @@ int keyswitch_checked(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, cons
 struct KscFlags {
     u32 *s[9];
 };
-// a KscFault checked against the plan: the word a transform stage flips between its two launches, or the armed check record of a
-// residue stage (job = the digit of stage 1, the half of stage 5)
+// a key-switch fault checked against the plan: the word a transform stage flips between its two launches, or the fault of a residue
+// stage rebased to the launch it hits (block = the conversion job of stages 1 and 5: the digit, the half; unit = the unit inside
+// that job's flags)
 struct KscHook {
-    int stage = -1, bit = 0, job = -1;
+    StagedFault f;
     u64 *flip = nullptr;
-    BcCheck chk{nullptr, -1, 0, 0, 0};
 };
-int ksc_hook(const fhe_keyswitch *p, const KscFault &ft, u64 *acc, bool has_add0, bool has_add1, KscHook &h);
+int ksc_hook(const fhe_keyswitch *p, const StagedFault &ft, u64 *acc, bool has_add0, bool has_add1, KscHook &h);
 // the permutation step of a hoisted rotation's back half: the sums ([2][M][N]) into acc_to, c0 ([L][N]) into c0_to
 struct KscPerm {
     u32 galois_elt;
@@ -132,13 +128,7 @@ struct HrcLayout {
     int n_shared, n_rot;        // words of the shared block, of one rotation's block
 };
 HrcLayout hrc_layout(const fhe_keyswitch *p);
-struct HrcFault {
-    int rot = 0;
-    KscFault f;
-};
-// takes the context's one-shot hook of the hoisted rotations
-HrcFault hrc_take_fault(fhe_ctx *ctx);
-// an HrcFault checked against the plan and the number of rotations
+// the hoisted rotations' fault (block = the rotation) checked against the plan and the number of rotations
 struct HrcHook {
     int stage = -1, rot = 0;
     KscHook hook;            // stages 0-7
@@ -146,7 +136,7 @@ struct HrcHook {
 };
 int galois_fault_check(const GaloisFault &f, size_t units, int logn);
 // the plan's buffers (partial sums, second set of sums) and the hook's validation: before anything is launched
-int hrc_prepare(fhe_keyswitch *p, const HrcFault &ft, size_t n_rot, HrcHook &h);
+int hrc_prepare(fhe_keyswitch *p, const StagedFault &ft, size_t n_rot, HrcHook &h);
 // the launches; d_flags = the shared block then one block per rotation (hrc_layout), cleared by the caller
 int hrc_run(fhe_keyswitch *p, uint64_t *const *d_out0, uint64_t *const *d_out1, const uint64_t *d_c0, const uint64_t *d_c1, const uint32_t *galois_elts,
             const uint64_t *const *d_prepared_keys, size_t n_rot, const fhe_abft *a, uint32_t *d_flags, hipStream_t st, const HrcHook &h);

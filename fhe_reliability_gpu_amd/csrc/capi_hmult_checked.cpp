@@ -25,16 +25,9 @@ RscLayout rsc_layout(const fhe_keyswitch *p, size_t n_parts)
     return RscLayout{{0, n, n + n * R, n + 2 * n * R}, n + 3 * n * R};
 }
 
-KscFault rsc_take_fault(fhe_ctx *ctx)
-{
-    const KscFault ft{ctx->rsc_fault_stage, ctx->rsc_fault_point, ctx->rsc_fault_unit, ctx->rsc_fault_bit, ctx->rsc_fault_coeff};
-    ctx->rsc_fault_stage = -1;
-    return ft;
-}
-
 // d_in = [n_parts][L][N], outs[i] = [L - 1][N]; the caller has checked scope, arguments and overlap
 int rescale_checked(fhe_keyswitch *p, uint64_t *const *outs, const uint64_t *d_in, size_t n_parts, const fhe_abft *a, uint32_t *d_flags, hipStream_t st,
-                    const KscFault &ft)
+                    const StagedFault &ft)
 {
     const fhe_ntt_tables *t = p->t;
     const int L = p->L, R = L - 1, logn = p->log_n;
@@ -48,7 +41,6 @@ int rescale_checked(fhe_keyswitch *p, uint64_t *const *outs, const uint64_t *d_i
 
     // ---- the test hook, checked against this call before anything is launched
     u64 *flip = nullptr;
-    BcCheck hook{nullptr, -1, 0, 0, 0};
     if (ft.stage >= 0) {
         const int units = (ft.stage == 3 ? lay.total : lay.off[ft.stage + 1]) - lay.off[ft.stage];
         if (ft.unit >= units || (size_t)ft.coeff >= N) return fail(FHE_ERR_INVALID, "fault unit or coefficient outside the call");
@@ -60,15 +52,11 @@ int rescale_checked(fhe_keyswitch *p, uint64_t *const *outs, const uint64_t *d_i
                 return fail(FHE_ERR_UNSUPPORTED, "fault point 3 (the running sum) does not exist on the rescale's residues: x mod q_j has no sum");
             if (ft.stage == 3 && !ks_tail_point_exists(ft.point, false))
                 return fail(FHE_ERR_UNSUPPORTED, "fault point 3 (the running sum) of the tail exists only with an addend, and the rescale has none");
-            hook = BcCheck{nullptr, ft.point, (u32)ft.unit, (u64)ft.coeff, (u64)1 << ft.bit};
         }
     }
 
-    u32 tin_f, tout_f, tin_i, tout_i;
-    ntt_checked_tiles(logn, &tin_f, &tout_f, false);
-    ntt_checked_tiles(logn, &tin_i, &tout_i, true);
     HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)lay.total * sizeof(u32), st));
-    const KscNtt fwd{p, a, st, tin_f, tout_f, false}, inv{p, a, st, tin_i, tout_i, true};
+    const KscNtt fwd = ksc_ntt(p, a, st, false), inv = ksc_ntt(p, a, st, true);
 
     // ---- 0: INTT of the last limbs
     HIP_TRY(hipMemcpy2DAsync(x, N * 8, d_in + (size_t)R * N, (size_t)L * N * 8, N * 8, n_parts, hipMemcpyDeviceToDevice, st));
@@ -76,15 +64,8 @@ int rescale_checked(fhe_keyswitch *p, uint64_t *const *outs, const uint64_t *d_i
     if ((rc = inv.compare(d_flags + lay.off[0], 0, (u32)R, 1, (u32)n_parts))) return rc;
 
     // ---- 1: residues modulo the remaining primes
-    {
-        BcCheck k{d_flags + lay.off[1], -1, 0, 0, 0};
-        if (ft.stage == 1) {
-            k = hook;
-            k.flags = d_flags + lay.off[1];
-        }
-        const RescaleReduceArgs ra{delta, x, lp, (u32)R, (u32)n_parts, logn};
-        if ((e = launch_rescale_reduce_checked(st, ra, k)) != hipSuccess) return hip_fail(e, "launch_rescale_reduce_checked");
-    }
+    const RescaleReduceArgs ra{delta, x, lp, (u32)R, (u32)n_parts, logn};
+    if ((e = launch_rescale_reduce_checked(st, ra, bc_check(ft.at(0, 1), d_flags + lay.off[1]))) != hipSuccess) return hip_fail(e, "launch_rescale_reduce_checked");
 
     // ---- 2: forward transform of the residues
     if ((rc = fwd.run({KscRows{delta, 0, 0, (u32)R, (u32)n_parts, (u32)R, 0}}, ft.stage == 2 ? flip : nullptr, ft.bit))) return rc;
@@ -94,12 +75,7 @@ int rescale_checked(fhe_keyswitch *p, uint64_t *const *outs, const uint64_t *d_i
     for (size_t part = 0; part < n_parts; part += 2) {
         const bool two = part + 1 < n_parts;
         const int u0 = (int)part * R, u1 = u0 + (two ? 2 : 1) * R;
-        BcCheck k{d_flags + lay.off[3] + u0, -1, 0, 0, 0};
-        if (ft.stage == 3 && ft.unit >= u0 && ft.unit < u1) {
-            k = hook;
-            k.flags = d_flags + lay.off[3] + u0;
-            k.fault_unit = (u32)(ft.unit - u0);
-        }
+        const BcCheck k = bc_check(ft.at(0, 3), d_flags + lay.off[3] + u0, u0, u1);
         const SubScaleArgs sa{outs[part], two ? outs[part + 1] : nullptr, d_in + part * L * N, delta + part * R * N, nullptr, p->qlast_inv.as<u64>(),
                               (u64)((size_t)L * N), (u64)((size_t)R * N), lp, 0u, (u32)R, logn, nullptr};
         if ((e = launch_sub_scale_checked(st, sa, k)) != hipSuccess) return hip_fail(e, "launch_sub_scale_checked");
@@ -134,25 +110,14 @@ int fhe_rescale_checked_layout(const fhe_keyswitch *p, size_t n_parts, int out[6
 int fhe_ctx_inject_fault_rescale(fhe_ctx *ctx, int stage, int point, int unit, long long coeff, int bit)
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
-    if (stage < 0) {
-        ctx->rsc_fault_stage = -1;
-        return FHE_OK;
-    }
-    const bool transform = !(stage & 1);
-    if (stage > 3 || unit < 0 || coeff < 0 || bit < 0 || bit > 63 || (!transform && (point < 0 || point > 3))) return fail(FHE_ERR_INVALID, "bad fault");
-    ctx->rsc_fault_stage = stage;
-    ctx->rsc_fault_point = transform ? 0 : point;
-    ctx->rsc_fault_unit = unit;
-    ctx->rsc_fault_coeff = coeff;
-    ctx->rsc_fault_bit = bit;
-    return FHE_OK;
+    return ctx->rsc_fault.arm(RSC_RULES, 0, stage, point, unit, coeff, bit) ? FHE_OK : fail(FHE_ERR_INVALID, "bad fault");
 }
 
 int fhe_rescale_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out, const uint64_t *d_in, size_t n_parts, const fhe_abft *a, uint32_t *d_flags,
                         void *stream)
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
-    const KscFault ft = rsc_take_fault(ctx);      // one shot, whatever the outcome
+    const StagedFault ft = ctx->rsc_fault.take();      // one shot, whatever the outcome
     int rc = rsc_scope(ctx, p, a, d_flags);
     if (rc) return rc;
     if (!d_out || !d_in) return fail(FHE_ERR_INVALID, "null argument");
@@ -183,12 +148,12 @@ int fhe_hmult_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
     // the one-shot hooks of the steps this call runs belong to it whatever its outcome: the key switch's and (when it rescales) the
     // rescale's are taken here, the pointwise one by the tensor step (cleared here when the call ends before it)
-    const KscFault kf = ksc_take_fault(ctx), rf = rescale ? rsc_take_fault(ctx) : KscFault{};
+    const StagedFault kf = ctx->ksc_fault.take(), rf = rescale ? ctx->rsc_fault.take() : StagedFault{};
     int rc = rescale ? rsc_scope(ctx, p, a, d_flags) : ksc_scope(ctx, p, a, d_flags);
     if (!rc && (!d_out0 || !d_out1 || !d_a0 || !d_a1 || !d_b0 || !d_b1 || !d_relin_key)) rc = fail(FHE_ERR_INVALID, "null argument");
     if (!rc && d_out0 == d_out1) rc = fail(FHE_ERR_INVALID, "the two output parts must be distinct buffers");
     if (rc) {
-        ctx->pw_fault_point = -1;
+        (void)ctx->pw_fault.take();
         return rc;
     }
     int lay[4];

@@ -110,22 +110,11 @@ struct fhe_ctx {
     int fault_bit = 0;
     int pfault_pass = -1, pfault_bit = 0;       // one-shot bit flip INSIDE a pass of the per-phase checked transform
     u32 pfault_block = 0, pfault_word = 0;      // (fhe_ctx_inject_fault_in_pass): workgroup and LDS word
-    int pm_fault_point = -1, pm_fault_bit = 0;  // one-shot bit flip inside the next fhe_polymul_checked (fhe_ctx_inject_fault_polymul):
-    long long pm_fault_idx = 0;                 // where (point 0-3), word of the call's [poly][limb][N] window, bit
-    int pw_fault_point = -1, pw_fault_bit = 0;  // one-shot bit flip inside the next residue-checked pointwise call
-    long long pw_fault_idx = 0;                 // (fhe_ctx_inject_fault_pointwise): point 0-3, element of the call's window, bit
-    int bc_fault_point = -1, bc_fault_unit = 0, bc_fault_bit = 0;   // one-shot bit flip inside the next residue-checked base
-    long long bc_fault_coeff = 0;                                   // conversion (fhe_ctx_inject_fault_baseconv)
-    int ksc_fault_stage = -1, ksc_fault_point = 0, ksc_fault_unit = 0, ksc_fault_bit = 0;   // one-shot bit flip inside the next checked key
-    long long ksc_fault_coeff = 0;                                                         // switch (fhe_ctx_inject_fault_keyswitch)
-    int rsc_fault_stage = -1, rsc_fault_point = 0, rsc_fault_unit = 0, rsc_fault_bit = 0;   // one-shot bit flip inside the next checked
-    long long rsc_fault_coeff = 0;                                                         // rescale (fhe_ctx_inject_fault_rescale)
-    int gal_fault_point = -1, gal_fault_unit = 0, gal_fault_bit = 0;   // one-shot bit flip inside the next checked Galois permutation
-    long long gal_fault_coeff = 0;                                     // (fhe_ctx_inject_fault_galois)
-    int hrc_fault_rot = 0, hrc_fault_stage = -1, hrc_fault_point = 0, hrc_fault_unit = 0, hrc_fault_bit = 0;   // one-shot bit flip inside the next
-    long long hrc_fault_coeff = 0;                                     // checked hoisted rotations (fhe_ctx_inject_fault_rotate_hoisted)
-    int bsgs_fault_g = 0, bsgs_fault_stage = -1, bsgs_fault_point = 0, bsgs_fault_unit = 0, bsgs_fault_bit = 0;   // one-shot bit flip inside the next
-    long long bsgs_fault_coeff = 0;                                    // checked BSGS product (fhe_ctx_inject_fault_bsgs)
+    // one-shot test hooks of the checked calls (fault_hook.hpp), one per setter: the polynomial product (fhe_ctx_inject_fault_polymul),
+    // the pointwise calls (_pointwise), the base conversions (_baseconv) and the Galois permutation (_galois); the key switch
+    // (_keyswitch), the rescale (_rescale), the hoisted rotations (_rotate_hoisted) and the BSGS product (_bsgs)
+    PointHook pm_fault, pw_fault, bc_fault, gal_fault;
+    StagedFault ksc_fault, rsc_fault, hrc_fault, bsgs_fault;
     DevBuf gal_sums;       // checked Galois permutation: the units' source-side and destination-side sums, [2][units] (grown on demand)
     int geo = 1;           // column-tile geometry of the two-launch path (ntt_launch.hpp)
     bool resident = false; // 2^13 / 2^14: one LDS-resident pass instead of two launches (opt-in, see ntt_plan.hpp)
@@ -322,6 +311,19 @@ struct TraceScope {
         ctx->trace += line;
     }
 };
+
+// the pointwise hook a call of `elems` elements took (ctx->pw_fault.take()), checked against that call; point 3 (the running sum)
+// exists only where the call has one
+inline int pointwise_fault(const PointFault &f, bool has_sum, size_t elems, PwCheck &k)
+{
+    if (f.point < 0) return FHE_OK;
+    if (f.point == 3 && !has_sum) return fail(FHE_ERR_UNSUPPORTED, "fault point 3 (the running sum) exists only for fhe_modmul_acc_checked and fhe_tensor_product_checked");
+    if (f.coeff >= elems) return fail(FHE_ERR_INVALID, "fault index outside the call's window");
+    k.fault_point = f.point;
+    k.fault_idx = f.coeff;
+    k.fault_mask = (u64)1 << f.bit;
+    return FHE_OK;
+}
 
 inline int check_range(const fhe_ntt_tables *t, size_t n_poly, size_t limbs, size_t start_idx)
 {

@@ -58,7 +58,7 @@ int ksc_prepare(fhe_keyswitch *p)
 
 // the test hook of one checked key switch, checked against the call before anything is launched: which word a transform stage flips
 // between its two launches, which check record a residue stage arms.  acc = the sums stages 4 and 5 work on
-int ksc_hook(const fhe_keyswitch *p, const KscFault &ft, u64 *acc, bool has_add0, bool has_add1, KscHook &h)
+int ksc_hook(const fhe_keyswitch *p, const StagedFault &ft, u64 *acc, bool has_add0, bool has_add1, KscHook &h)
 {
     const int L = p->L, K = p->K, M = L + K, logn = p->log_n;
     const size_t N = (size_t)1 << logn;
@@ -66,8 +66,8 @@ int ksc_hook(const fhe_keyswitch *p, const KscFault &ft, u64 *acc, bool has_add0
     u64 *coef = p->coef.as<u64>(), *ext = p->ext.as<u64>(), *conv = p->conv.as<u64>();
     h = KscHook{};
     if (ft.stage < 0) return FHE_OK;
-    h.stage = ft.stage;
-    h.bit = ft.bit;
+    h.f = ft;
+    h.f.block = 0;
     const bool tf = !(ft.stage & 1);      // a transform stage
     const int units = (ft.stage == 7 ? lay.total : lay.off[ft.stage + 1]) - lay.off[ft.stage];
     if (ft.unit >= units || (size_t)ft.coeff >= N) return fail(FHE_ERR_INVALID, "fault unit or coefficient outside the call");
@@ -88,52 +88,35 @@ int ksc_hook(const fhe_keyswitch *p, const KscFault &ft, u64 *acc, bool has_add0
         const int ju = j >= lo && j < hi ? j - lo : m + (j < lo ? j : j - m);
         if (!bc_point_exists(ft.point, ju < m ? ju + 1 : m))
             return fail(FHE_ERR_UNSUPPORTED, "fault point 3 (the running sum) needs a sum of two terms: not on a digit's first limb, not on a one-limb digit");
-        h.job = d;
-        h.chk = BcCheck{nullptr, ft.point, (u32)ju, (u64)ft.coeff, (u64)1 << ft.bit};
+        h.f.block = d;
+        h.f.unit = ju;
         break;
     }
     case 5: {
         const int ju = u % (K + L);
         if (!bc_point_exists(ft.point, ju < K ? ju + 1 : K))
             return fail(FHE_ERR_UNSUPPORTED, "fault point 3 (the running sum) needs a sum of two terms: not on the first special limb, not with K = 1");
-        h.job = u / (K + L);
-        h.chk = BcCheck{nullptr, ft.point, (u32)ju, (u64)ft.coeff, (u64)1 << ft.bit};
+        h.f.block = u / (K + L);
+        h.f.unit = ju;
         break;
     }
     case 3:
         if (ft.point < 0 || ft.point > 3) return fail(FHE_ERR_INVALID, "bad fault point");
-        h.chk = BcCheck{nullptr, ft.point, (u32)u, (u64)ft.coeff, (u64)1 << ft.bit};
         break;
     default:
         if (!ks_tail_point_exists(ft.point, u / L ? has_add1 : has_add0))
             return fail(FHE_ERR_UNSUPPORTED, "fault point 3 (the running sum) of the tail exists only on a half with an addend");
-        h.chk = BcCheck{nullptr, ft.point, (u32)u, (u64)ft.coeff, (u64)1 << ft.bit};
         break;
     }
     return FHE_OK;
 }
 
-namespace {
-
-BcCheck check_of(const KscHook &h, int stage, u32 *flags, int job)
-{
-    BcCheck k{flags, -1, 0, 0, 0};
-    if (h.stage == stage && h.job == job) {
-        k = h.chk;
-        k.flags = flags;
-    }
-    return k;
-}
-
-// the detector's partial sums live in the plan (ksc_prepare): the fhe_abft is only read
 KscNtt ksc_ntt(const fhe_keyswitch *p, const fhe_abft *a, hipStream_t st, bool inverse)
 {
     u32 tin, tout;
     ntt_checked_tiles(p->log_n, &tin, &tout, inverse);
     return KscNtt{p, a, st, tin, tout, inverse};
 }
-
-} // namespace
 
 // stages 0-2: what does not depend on the key (nor, for hoisted rotations, on the Galois element)
 int ksc_front(fhe_keyswitch *p, const uint64_t *d_c, const fhe_abft *a, const KscFlags &fl, hipStream_t st, const KscHook &h)
@@ -148,12 +131,12 @@ int ksc_front(fhe_keyswitch *p, const uint64_t *d_c, const fhe_abft *a, const Ks
 
     // ---- 0: opening INTT
     HIP_TRY(hipMemcpyAsync(coef, d_c, (size_t)L * N * 8, hipMemcpyDeviceToDevice, st));
-    if ((rc = inv.run({KscRows{coef, 0, 0, (u32)L, 1, (u32)L, 0}}, h.stage == 0 ? h.flip : nullptr, h.bit))) return rc;
+    if ((rc = inv.run({KscRows{coef, 0, 0, (u32)L, 1, (u32)L, 0}}, h.f.stage == 0 ? h.flip : nullptr, h.f.bit))) return rc;
     if ((rc = inv.compare(fl.s[0], 0, 0, (u32)L, (u32)L))) return rc;
 
     // ---- 1: digit extension
     for (int d = 0; d < dnum; d++) {
-        const BcCheckedJob cj{p->up_host[d], p->up[d]->shoup_dig, p->up[d]->shoup_hor, check_of(h, 1, p->chk_bc_flags.as<u32>() + (size_t)d * M, d)};
+        const BcCheckedJob cj{p->up_host[d], p->up[d]->shoup_dig, p->up[d]->shoup_hor, bc_check(h.f.at(d, 1), p->chk_bc_flags.as<u32>() + (size_t)d * M)};
         if ((e = launch_baseconv_exact_checked(st, cj, N)) != hipSuccess) return hip_fail(e, "launch_baseconv_exact_checked");
     }
     if ((e = launch_ks_flags_scatter(st, fl.s[1], p->chk_bc_flags.as<u32>(), p->chk_bc_map.as<u32>(), (u32)(dnum * M))) != hipSuccess)
@@ -170,7 +153,7 @@ int ksc_front(fhe_keyswitch *p, const uint64_t *d_c, const fhe_abft *a, const Ks
         if (lo > 0) rows.push_back(KscRows{base, 0, 0, (u32)lo, 1, (u32)M, (u32)(d * M)});
         if (hi < L) rows.push_back(KscRows{base, (u32)hi, (u32)hi, (u32)(L - hi), 1, (u32)M, (u32)(d * M)});
     }
-    if ((rc = fwd.run(rows, h.stage == 2 ? h.flip : nullptr, h.bit))) return rc;
+    if ((rc = fwd.run(rows, h.f.stage == 2 ? h.flip : nullptr, h.f.bit))) return rc;
     return fwd.compare(fl.s[2], 0, 0, (u32)M, (u32)(dnum * M));
 }
 
@@ -190,7 +173,7 @@ int ksc_back(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_
     // ---- 3: inner product with the key
     {
         const KsMacArgs ka{acc, p->ext.as<u64>(), d_c, d_evk, lp, (u32)L, (u32)M, (u32)p->dnum, (u32)p->alpha, logn, (u32)L, 0u, 0u};
-        if ((e = launch_ks_mac_checked(st, ka, check_of(h, 3, fl.s[3], -1))) != hipSuccess) return hip_fail(e, "launch_ks_mac_checked");
+        if ((e = launch_ks_mac_checked(st, ka, bc_check(h.f.at(0, 3), fl.s[3]))) != hipSuccess) return hip_fail(e, "launch_ks_mac_checked");
     }
 
     // ---- 8: sigma of the sums and of c0
@@ -202,29 +185,29 @@ int ksc_back(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_
     }
 
     // ---- 4: INTT of the special limbs of both halves, in place inside the sums
-    if ((rc = inv.run({KscRows{acc, (u32)L, (u32)L, (u32)K, 2, (u32)M, 0}}, h.stage == 4 ? h.flip : nullptr, h.bit))) return rc;
+    if ((rc = inv.run({KscRows{acc, (u32)L, (u32)L, (u32)K, 2, (u32)M, 0}}, h.f.stage == 4 ? h.flip : nullptr, h.f.bit))) return rc;
     for (int hf = 0; hf < 2; hf++)
         if ((rc = inv.compare(fl.s[4] + hf * K, (u32)(hf * M + L), (u32)L, (u32)K, (u32)K))) return rc;
 
     // ---- 5: mod-down conversion P -> Q
     for (int hf = 0; hf < 2; hf++) {
         const BcJob job{p->down->dev, acc, conv + (size_t)hf * L * N, 0xFFFFFFFFu, 0u, p->down_rows.as<u32>() + (size_t)hf * K};
-        const BcCheckedJob cj{job, p->down->shoup_dig, p->down->shoup_hor, check_of(h, 5, fl.s[5] + hf * (K + L), hf)};
+        const BcCheckedJob cj{job, p->down->shoup_dig, p->down->shoup_hor, bc_check(h.f.at(hf, 5), fl.s[5] + hf * (K + L))};
         if ((e = launch_baseconv_exact_checked(st, cj, N)) != hipSuccess) return hip_fail(e, "launch_baseconv_exact_checked");
     }
 
     // ---- 6: forward transform of the converted limbs
-    if ((rc = fwd.run({KscRows{conv, 0, 0, (u32)L, 2, (u32)L, 0}}, h.stage == 6 ? h.flip : nullptr, h.bit))) return rc;
+    if ((rc = fwd.run({KscRows{conv, 0, 0, (u32)L, 2, (u32)L, 0}}, h.f.stage == 6 ? h.flip : nullptr, h.f.bit))) return rc;
     if ((rc = fwd.compare(fl.s[6], 0, 0, (u32)L, (u32)(2 * L)))) return rc;
 
     // ---- 7: tail
     const SubScaleArgs sa{d_out0, d_out1, acc, conv, d_add0, p->pinv.as<u64>(), (u64)((size_t)M * N), (u64)((size_t)L * N), lp, 0u, (u32)L, logn, d_add1};
-    if ((e = launch_sub_scale_checked(st, sa, check_of(h, 7, fl.s[7], -1))) != hipSuccess) return hip_fail(e, "launch_sub_scale_checked");
+    if ((e = launch_sub_scale_checked(st, sa, bc_check(h.f.at(0, 7), fl.s[7]))) != hipSuccess) return hip_fail(e, "launch_sub_scale_checked");
     return FHE_OK;
 }
 
 int keyswitch_checked(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk,
-                      const uint64_t *d_add0, const uint64_t *d_add1, const fhe_abft *a, uint32_t *d_flags, hipStream_t st, const KscFault &ft)
+                      const uint64_t *d_add0, const uint64_t *d_add1, const fhe_abft *a, uint32_t *d_flags, hipStream_t st, const StagedFault &ft)
 {
     int rc;
     if ((rc = ksc_prepare(p))) return rc;
@@ -238,13 +221,6 @@ int keyswitch_checked(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, cons
     return ksc_back(p, d_out0, d_out1, d_c, d_evk, d_add0, d_add1, a, fl, st, h, nullptr);
 }
 
-KscFault ksc_take_fault(fhe_ctx *ctx)
-{
-    const KscFault ft{ctx->ksc_fault_stage, ctx->ksc_fault_point, ctx->ksc_fault_unit, ctx->ksc_fault_bit, ctx->ksc_fault_coeff};
-    ctx->ksc_fault_stage = -1;
-    return ft;
-}
-
 int ksc_scope(const fhe_ctx *ctx, const fhe_keyswitch *p, const fhe_abft *a, const uint32_t *d_flags)
 {
     if (!p || !a || !d_flags) return fail(FHE_ERR_INVALID, "null argument");
@@ -256,18 +232,6 @@ int ksc_scope(const fhe_ctx *ctx, const fhe_keyswitch *p, const fhe_abft *a, con
     if (!p->t->has_inverse) return fail(FHE_ERR_UNSUPPORTED, "table set has no inverse (twiddle or N not invertible)");
     return FHE_OK;
 }
-
-namespace {
-
-// argument and scope checks shared by the three entry points; takes the one-shot hook whatever the outcome
-int ksc_enter(fhe_ctx *ctx, fhe_keyswitch *p, const fhe_abft *a, uint32_t *d_flags, KscFault &ft)
-{
-    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
-    ft = ksc_take_fault(ctx);
-    return ksc_scope(ctx, p, a, d_flags);
-}
-
-} // namespace
 
 extern "C" {
 
@@ -284,25 +248,15 @@ int fhe_keyswitch_checked_layout(const fhe_keyswitch *p, int out[10])
 int fhe_ctx_inject_fault_keyswitch(fhe_ctx *ctx, int stage, int point, int unit, long long coeff, int bit)
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
-    if (stage < 0) {
-        ctx->ksc_fault_stage = -1;
-        return FHE_OK;
-    }
-    const bool transform = !(stage & 1);
-    if (stage > 7 || unit < 0 || coeff < 0 || bit < 0 || bit > 63 || (!transform && (point < 0 || point > 3))) return fail(FHE_ERR_INVALID, "bad fault");
-    ctx->ksc_fault_stage = stage;
-    ctx->ksc_fault_point = transform ? 0 : point;
-    ctx->ksc_fault_unit = unit;
-    ctx->ksc_fault_coeff = coeff;
-    ctx->ksc_fault_bit = bit;
-    return FHE_OK;
+    return ctx->ksc_fault.arm(KSC_RULES, 0, stage, point, unit, coeff, bit) ? FHE_OK : fail(FHE_ERR_INVALID, "bad fault");
 }
 
 int fhe_keyswitch_apply_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk,
                                 const uint64_t *d_add0, const uint64_t *d_add1, const fhe_abft *a, uint32_t *d_flags, void *stream)
 {
-    KscFault ft;
-    int rc = ksc_enter(ctx, p, a, d_flags, ft);
+    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
+    const StagedFault ft = ctx->ksc_fault.take();      // one shot, whatever the outcome
+    int rc = ksc_scope(ctx, p, a, d_flags);
     if (rc) return rc;
     if (!d_out0 || !d_out1 || !d_c || !d_evk) return fail(FHE_ERR_INVALID, "null argument");
     if (d_out0 == d_out1) return fail(FHE_ERR_INVALID, "the two output parts must be distinct buffers");
@@ -313,8 +267,9 @@ int fhe_keyswitch_apply_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0
 int fhe_relinearize_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_d0, const uint64_t *d_d1,
                             const uint64_t *d_d2, const uint64_t *d_relin_key, const fhe_abft *a, uint32_t *d_flags, void *stream)
 {
-    KscFault ft;
-    int rc = ksc_enter(ctx, p, a, d_flags, ft);
+    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
+    const StagedFault ft = ctx->ksc_fault.take();      // one shot, whatever the outcome
+    int rc = ksc_scope(ctx, p, a, d_flags);
     if (rc) return rc;
     if (!d_out0 || !d_out1 || !d_d0 || !d_d1 || !d_d2 || !d_relin_key) return fail(FHE_ERR_INVALID, "null argument");
     if (d_out0 == d_out1) return fail(FHE_ERR_INVALID, "the two output parts must be distinct buffers");
@@ -325,8 +280,9 @@ int fhe_relinearize_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, ui
 int fhe_rotate_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0, const uint64_t *d_c1,
                        uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, uint32_t *d_flags, void *stream)
 {
-    KscFault ft;
-    int rc = ksc_enter(ctx, p, a, d_flags, ft);
+    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
+    const StagedFault ft = ctx->ksc_fault.take();      // one shot, whatever the outcome
+    int rc = ksc_scope(ctx, p, a, d_flags);
     if (rc) return rc;
     if (!d_out0 || !d_out1 || !d_c0 || !d_c1 || !d_galois_key) return fail(FHE_ERR_INVALID, "null argument");
     if (d_out0 == d_out1) return fail(FHE_ERR_INVALID, "the two output parts must be distinct buffers");

@@ -28,14 +28,17 @@ HrcLayout hrc_layout(const fhe_keyswitch *p)
     return l;
 }
 
-HrcFault hrc_take_fault(fhe_ctx *ctx)
+namespace {
+
+// words of the flag buffer of n_rot rotations: the shared block, then one block per rotation
+int hrc_flag_words(const HrcLayout &l, size_t n_rot, size_t *words)
 {
-    HrcFault h;
-    h.rot = ctx->hrc_fault_rot;
-    h.f = KscFault{ctx->hrc_fault_stage, ctx->hrc_fault_point, ctx->hrc_fault_unit, ctx->hrc_fault_bit, ctx->hrc_fault_coeff};
-    ctx->hrc_fault_stage = -1;
-    return h;
+    if (n_rot > (size_t)(0x7FFFFFFF - l.n_shared) / (size_t)l.n_rot) return fail(FHE_ERR_INVALID, "too many rotations for one flag buffer");
+    *words = (size_t)l.n_shared + n_rot * l.n_rot;
+    return FHE_OK;
 }
+
+} // namespace
 
 int galois_fault_check(const GaloisFault &f, size_t units, int logn)
 {
@@ -73,7 +76,7 @@ int galois_permute_checked(fhe_ctx *ctx, hipStream_t st, const GalSeg *segs, int
 }
 
 // the plan's buffers of the checked hoisted rotations and the test hook, checked against the call before anything is launched
-int hrc_prepare(fhe_keyswitch *p, const HrcFault &ft, size_t n_rot, HrcHook &h)
+int hrc_prepare(fhe_keyswitch *p, const StagedFault &ft, size_t n_rot, HrcHook &h)
 {
     int rc;
     if ((rc = ksc_prepare(p))) return rc;
@@ -82,16 +85,16 @@ int hrc_prepare(fhe_keyswitch *p, const HrcFault &ft, size_t n_rot, HrcHook &h)
     if (!p->acc2.p) HIP_TRY(p->acc2.alloc(p->acc.bytes));
     const int L = p->L, M = L + p->K;
     h = HrcHook{};
-    if (ft.f.stage < 0) return FHE_OK;
-    if (ft.f.stage >= 3 && (size_t)ft.rot >= n_rot) return fail(FHE_ERR_INVALID, "fault rotation outside the call");
-    h.rot = ft.rot;
-    if (ft.f.stage == 8) {
-        h.gal = GaloisFault{ft.f.point, (u32)ft.f.unit, (u64)ft.f.coeff, ft.f.bit};
+    if (ft.stage < 0) return FHE_OK;
+    if (ft.stage >= 3 && (size_t)ft.block >= n_rot) return fail(FHE_ERR_INVALID, "fault rotation outside the call");
+    h.rot = ft.block;
+    if (ft.stage == 8) {
+        h.gal = GaloisFault{ft.point, (u32)ft.unit, (u64)ft.coeff, ft.bit};
         if ((rc = galois_fault_check(h.gal, (size_t)2 * M + L, p->log_n))) return rc;
-    } else if ((rc = ksc_hook(p, ft.f, p->acc2.as<u64>(), true, false, h.hook))) {
+    } else if ((rc = ksc_hook(p, ft, p->acc2.as<u64>(), true, false, h.hook))) {
         return rc;
     }
-    h.stage = ft.f.stage;
+    h.stage = ft.stage;
     return FHE_OK;
 }
 
@@ -123,8 +126,7 @@ int fhe_automorphism_ntt_checked(fhe_ctx *ctx, uint64_t *d_dst, const uint64_t *
                                  uint32_t *d_flags, void *stream)
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
-    const GaloisFault f{ctx->gal_fault_point, (u32)ctx->gal_fault_unit, (u64)ctx->gal_fault_coeff, ctx->gal_fault_bit};
-    ctx->gal_fault_point = -1;
+    const GaloisFault f = ctx->gal_fault.take();
     if (!d_dst || !d_src || !d_flags || d_dst == d_src || !(galois_elt & 1) || log_n < 1 || log_n > 30 || n_units > 0xFFFFFFFFull)
         return fail(FHE_ERR_INVALID, "bad automorphism arguments");
     int rc = galois_fault_check(f, n_units, log_n);
@@ -138,48 +140,27 @@ int fhe_automorphism_ntt_checked(fhe_ctx *ctx, uint64_t *d_dst, const uint64_t *
 int fhe_ctx_inject_fault_galois(fhe_ctx *ctx, int point, int unit, long long coeff, int bit)
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
-    if (point < 0) {
-        ctx->gal_fault_point = -1;
-        return FHE_OK;
-    }
-    if (point > GAL_AT_INDEX || unit < 0 || coeff < 0 || bit < 0 || bit > 63) return fail(FHE_ERR_INVALID, "bad fault");
-    ctx->gal_fault_point = point;
-    ctx->gal_fault_unit = unit;
-    ctx->gal_fault_coeff = coeff;
-    ctx->gal_fault_bit = bit;
-    return FHE_OK;
+    return ctx->gal_fault.arm(GAL_AT_INDEX, point, unit, coeff, bit) ? FHE_OK : fail(FHE_ERR_INVALID, "bad fault");
 }
 
 int fhe_rotate_hoisted_checked_layout(const fhe_keyswitch *p, size_t n_rot, int out[12])
 {
     if (!p || !out) return fail(FHE_ERR_INVALID, "null argument");
     const HrcLayout l = hrc_layout(p);
-    if (n_rot > (size_t)(0x7FFFFFFF - l.n_shared) / (size_t)l.n_rot) return fail(FHE_ERR_INVALID, "too many rotations for one flag buffer");
+    size_t words;
+    if (int rc = hrc_flag_words(l, n_rot, &words)) return rc;
     for (int s = 0; s < 3; s++) out[s] = l.shared[s];
     for (int i = 0; i < 6; i++) out[3 + i] = l.rot[i];
     out[9] = l.n_shared;
     out[10] = l.n_rot;
-    out[11] = l.n_shared + (int)n_rot * l.n_rot;
+    out[11] = (int)words;
     return FHE_OK;
 }
 
 int fhe_ctx_inject_fault_rotate_hoisted(fhe_ctx *ctx, int rot, int stage, int point, int unit, long long coeff, int bit)
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
-    if (stage < 0) {
-        ctx->hrc_fault_stage = -1;
-        return FHE_OK;
-    }
-    const bool transform = stage < 8 && !(stage & 1);
-    if (stage > 8 || rot < 0 || unit < 0 || coeff < 0 || bit < 0 || bit > 63 || (!transform && (point < 0 || point > (stage == 8 ? GAL_AT_INDEX : 3))))
-        return fail(FHE_ERR_INVALID, "bad fault");
-    ctx->hrc_fault_rot = rot;
-    ctx->hrc_fault_stage = stage;
-    ctx->hrc_fault_point = transform ? 0 : point;
-    ctx->hrc_fault_unit = unit;
-    ctx->hrc_fault_coeff = coeff;
-    ctx->hrc_fault_bit = bit;
-    return FHE_OK;
+    return ctx->hrc_fault.arm(HRC_RULES, rot, stage, point, unit, coeff, bit) ? FHE_OK : fail(FHE_ERR_INVALID, "bad fault");
 }
 
 int fhe_rotate_hoisted_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *const *d_out0, uint64_t *const *d_out1, const uint64_t *d_c0,
@@ -187,7 +168,7 @@ int fhe_rotate_hoisted_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *const *
                                const fhe_abft *a, uint32_t *d_flags, void *stream)
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
-    const HrcFault ft = hrc_take_fault(ctx);
+    const StagedFault ft = ctx->hrc_fault.take();
     int rc = ksc_scope(ctx, p, a, d_flags);
     if (rc) return rc;
     if (!d_c0 || !d_c1 || (n_rot && (!d_out0 || !d_out1 || !galois_elts || !d_prepared_keys))) return fail(FHE_ERR_INVALID, "null argument");
@@ -198,13 +179,13 @@ int fhe_rotate_hoisted_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *const *
             return fail(FHE_ERR_INVALID, "rotate is out of place");
     }
     if (!n_rot) return FHE_OK;
-    const HrcLayout lay = hrc_layout(p);
-    if (n_rot > (size_t)(0x7FFFFFFF - lay.n_shared) / (size_t)lay.n_rot) return fail(FHE_ERR_INVALID, "too many rotations for one flag buffer");
+    size_t words;
+    if ((rc = hrc_flag_words(hrc_layout(p), n_rot, &words))) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     HrcHook hook;
     if ((rc = hrc_prepare(p, ft, n_rot, hook))) return rc;
     hipStream_t st = pick(ctx, stream);
-    HIP_TRY(hipMemsetAsync(d_flags, 0, ((size_t)lay.n_shared + n_rot * lay.n_rot) * sizeof(u32), st));
+    HIP_TRY(hipMemsetAsync(d_flags, 0, words * sizeof(u32), st));
     return hrc_run(p, d_out0, d_out1, d_c0, d_c1, galois_elts, d_prepared_keys, n_rot, a, d_flags, st, hook);
 }
 

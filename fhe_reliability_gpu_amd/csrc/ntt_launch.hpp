@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "fault_hook.hpp"
 #include "ntt_plan.hpp"
 
 namespace fhe {
@@ -280,14 +281,7 @@ hipError_t launch_bsgs_hadamard(hipStream_t st, u64 *y, const u64 *M_blocks, con
                                 const ModConst *mc /* nullptr: int64 wrap-around like the reference */);
 
 // ---- baseconv_checked.hip: the two conversions with a residue check per digit and per output word (baseconv_check.hpp) ----
-// flags: exact [m + k] (digit units, then output units), fast [k]; fault_point >= 0: XOR fault_mask at that injection point
-// (residue_check.hpp PW_AT_*) of unit fault_unit, coefficient fault_coeff
-struct BcCheck {
-    u32 *flags;
-    int fault_point;
-    u32 fault_unit;
-    u64 fault_coeff, fault_mask;
-};
+// flags: exact [m + k] (digit units, then output units), fast [k]; the check record BcCheck: fault_hook.hpp
 // a conversion as the unchecked launcher describes it (BcJob: output gap, input row map) plus what the check needs: the digit and
 // output tables as Shoup pairs {w, floor(w 2^64 / q)} in the layout of BaseConvPlanDev::dig / hor -- the plan's own tables on
 // integer plans, a second pair of tables on FP64 plans

@@ -124,6 +124,19 @@ class DeviceArray:
             pass
 
 
+def _flag_buffer(eng: Engine, n: int) -> DeviceArray:
+    """``n`` uint32 flag words (packed in a u64 buffer) holding a pattern no check leaves behind: the checked calls clear or
+    write every word themselves."""
+    return eng.upload(np.full((n + 1) // 2, 0xA5A5A5A5A5A5A5A5, dtype=_U64))
+
+
+def _read_flags(flags: DeviceArray, n: int, stream=None) -> np.ndarray:
+    """The ``n`` flag words once the call's stream (when one was given) has finished: a view into the download, to be copied."""
+    if stream is not None:
+        flags.eng.sync(stream)
+    return flags.download().view(np.uint32)[:n]
+
+
 def create_moduli(N: int, bits: Sequence[int]) -> List[int]:
     """``CoeffModulus::Create(N, {bits...})`` (reliability_test/ntt_test.cu:44)."""
     b = (C.c_int * len(bits))(*bits)
@@ -199,9 +212,7 @@ class NttTables:
         flags = self.eng.alloc((n + 1) // 2)      # uint32 flags packed in a u64 buffer
         f = lib.fhe_modmul_acc_checked if acc else lib.fhe_modmul_checked
         check(f(self.eng._h, c.ptr, a.ptr, b.ptr, self._h, n_poly, limbs, start, flags.ptr, stream))
-        if stream is not None:
-            self.eng.sync(stream)
-        return flags.download().view(np.uint32)[:n].copy()
+        return _read_flags(flags, n, stream).copy()
 
     def modadd_checked(self, c: DeviceArray, a: DeviceArray, b: DeviceArray, limbs=None, start=0, n_poly=1, stream=None) -> np.ndarray:
         """c = (a + b) mod q per limb with every word checked; the words are ``fhe_modadd``'s, bit for bit.  Returns
@@ -209,11 +220,9 @@ class NttTables:
         2 = the word out of its window, 4 = an operand not canonical, which the check cannot cover (bsgs_check.hpp)."""
         limbs = len(self) - start if limbs is None else limbs
         n = n_poly * limbs
-        flags = self.eng.upload(np.full((n + 1) // 2, 0xA5A5A5A5A5A5A5A5, dtype=_U64))      # the call clears them itself
+        flags = _flag_buffer(self.eng, n)
         check(lib.fhe_modadd_checked(self.eng._h, c.ptr, a.ptr, b.ptr, self._h, n_poly, limbs, start, flags.ptr, stream))
-        if stream is not None:
-            self.eng.sync(stream)
-        return flags.download().view(np.uint32)[:n].copy()
+        return _read_flags(flags, n, stream).copy()
 
     def polymul(self, c: DeviceArray, a: DeviceArray, b: DeviceArray, limbs=None, start=0, n_poly=1, stream=None):
         limbs = len(self) - start if limbs is None else limbs
@@ -378,9 +387,7 @@ class BaseConv:
     def _checked(self, f, units, out, inp, N, stream):
         flags = self.eng.alloc((units + 1) // 2)      # uint32 flags packed in a u64 buffer
         check(f(self.eng._h, out.ptr, inp.ptr, self._h, N, flags.ptr, stream))
-        if stream is not None:
-            self.eng.sync(stream)
-        return flags.download().view(np.uint32)[:units].copy()
+        return _read_flags(flags, units, stream).copy()
 
     def exact_checked(self, out: DeviceArray, inp: DeviceArray, N: int, stream=None) -> np.ndarray:
         """``exact`` with every mixed-radix digit and every output word checked; the words are ``exact``'s, bit for bit.
@@ -472,11 +479,9 @@ def automorphism(eng: Engine, t: NttTables, src: DeviceArray, galois_elt: int, n
 
 
 def _permute_checked(eng: Engine, dst: DeviceArray, src: DeviceArray, log_n: int, galois_elt: int, units: int, stream=None) -> np.ndarray:
-    flags = eng.upload(np.full((units + 1) // 2, 0xA5A5A5A5A5A5A5A5, dtype=_U64))      # the call writes every word itself
+    flags = _flag_buffer(eng, units)
     check(lib.fhe_automorphism_ntt_checked(eng._h, dst.ptr, src.ptr, log_n, galois_elt, units, flags.ptr, stream))
-    if stream is not None:
-        eng.sync(stream)
-    return flags.download().view(np.uint32)[:units].copy()
+    return _read_flags(flags, units, stream).copy()
 
 
 def automorphism_checked(eng: Engine, t: NttTables, src: DeviceArray, galois_elt: int, n_poly: int = 1, limbs: Optional[int] = None):
@@ -571,12 +576,10 @@ class KeySwitch:
         the residue identity covers the lazy cross term d1 = a0 b1 + a1 b0 as one sum, the reference's Sum check
         (rfhe_framewk/src/barrett_final.py) and the element-wise fold check of four_step_ntt_protected.py:102-120."""
         d = [self._out(self.L) for _ in range(3)]
-        flags = self.eng.alloc((3 * self.L + 1) // 2)
+        flags = _flag_buffer(self.eng, 3 * self.L)
         check(lib.fhe_tensor_product_checked(self.eng._h, d[0].ptr, d[1].ptr, d[2].ptr, a0.ptr, a1.ptr, b0.ptr, b1.ptr, self.t._h, self.L, 0,
                                              flags.ptr, stream))
-        if stream is not None:
-            self.eng.sync(stream)
-        return d[0], d[1], d[2], flags.download().view(np.uint32)[: 3 * self.L].reshape(self.L, 3).copy()
+        return d[0], d[1], d[2], _read_flags(flags, 3 * self.L, stream).reshape(self.L, 3).copy()
 
     def relinearize(self, d0: DeviceArray, d1: DeviceArray, d2: DeviceArray, relin_key: DeviceArray, stream=None):
         """``relinearize_inplace`` (dotprod_test.cu:114)."""
@@ -602,18 +605,10 @@ class KeySwitch:
 
     def _checked(self, call, stream):
         lay = self.checked_layout()
-        total = lay["total"]
         o0, o1 = self._out(self.L), self._out(self.L)
-        flags = self.eng.upload(np.full((total + 1) // 2, 0xA5A5A5A5A5A5A5A5, dtype=_U64))      # the call clears them itself
+        flags = _flag_buffer(self.eng, lay["total"])
         check(call(o0, o1, flags))
-        if stream is not None:
-            self.eng.sync(stream)
-        f = flags.download().view(np.uint32)[:total]
-        out = {}
-        for name in self.CHECKED_STAGES:
-            off, shape = lay[name]
-            out[name] = f[off:off + int(np.prod(shape))].reshape(shape).copy()
-        return o0, o1, out
+        return o0, o1, self._split_flags(_read_flags(flags, lay["total"], stream), lay, self.CHECKED_STAGES)
 
     def apply_checked(self, c: DeviceArray, evk: DeviceArray, abft: "Abft", add0: Optional[DeviceArray] = None,
                       add1: Optional[DeviceArray] = None, stream=None):
@@ -669,23 +664,21 @@ class KeySwitch:
         galois, intt_special, moddown, ntt_conv, tail}, ...]}`` as ``rotate_hoisted_checked_layout`` shapes them.  The shared stages
         run once on the un-rotated c1; a fault there reaches every rotation, a fault in rotation r only its own words."""
         n = len(galois_elts)
-        lay = self.rotate_hoisted_checked_layout(n)
+        total = self.rotate_hoisted_checked_layout(n)["total"]
         outs = [(self._out(self.L), self._out(self.L)) for _ in range(n)]
         a0 = (vp * max(1, n))(*[o[0].ptr for o in outs])
         a1 = (vp * max(1, n))(*[o[1].ptr for o in outs])
         ks = (vp * max(1, n))(*[k.ptr for k in prepared_keys])
         ge = (C.c_uint32 * max(1, n))(*[int(g) for g in galois_elts])
-        total = lay["total"]
-        flags = self.eng.upload(np.full((total + 1) // 2, 0xA5A5A5A5A5A5A5A5, dtype=_U64))      # the call clears them itself
+        flags = _flag_buffer(self.eng, total)
         check(lib.fhe_rotate_hoisted_checked(self.eng._h, self._h, a0, a1, c0.ptr, c1.ptr, ge, ks, n, abft._h, flags.ptr, stream))
-        if stream is not None:
-            self.eng.sync(stream)
-        f = flags.download().view(np.uint32)[:total]
+        return outs, self._hoisted_flags(_read_flags(flags, total, stream), n)
 
-        def cut(stages, base):
-            return {name: f[base + off:base + off + int(np.prod(shape))].reshape(shape).copy() for name, (off, shape) in stages.items()}
-        return outs, {"shared": cut(lay["shared"], 0),
-                      "rot": [cut(lay["rot"], lay["shared_words"] + r * lay["rot_words"]) for r in range(n)]}
+    def _hoisted_flags(self, f, n_rot, base=0):
+        """The flag dictionary of ``n_rot`` checked hoisted rotations whose words start at ``f[base]``."""
+        lay = self.rotate_hoisted_checked_layout(n_rot)
+        return {"shared": self._split_flags(f, lay["shared"], lay["shared"], base),
+                "rot": [self._split_flags(f, lay["rot"], lay["rot"], base + lay["shared_words"] + r * lay["rot_words"]) for r in range(n_rot)]}
 
     # ---- checked BSGS matrix-vector product (capi_bsgs_checked.cpp) ----
     BSGS_GIANT_STAGES = ("inner", "galois", "acc", "keyswitch")      # in execution order
@@ -715,23 +708,15 @@ class KeySwitch:
         ge = (C.c_uint32 * max(1, n2 - 1))(*[int(g) for g in giant_elts])
         bk = (vp * max(1, n1 - 1))(*[k.ptr for k in baby_keys_prepared])
         gk = (vp * max(1, n2 - 1))(*[k.ptr for k in giant_keys])
-        flags = self.eng.upload(np.full((total + 1) // 2, 0xA5A5A5A5A5A5A5A5, dtype=_U64))      # the call clears them itself
+        flags = _flag_buffer(self.eng, total)
         check(lib.fhe_bsgs_matvec_checked(self.eng._h, self._h, o0.ptr, o1.ptr, c0.ptr, c1.ptr, diags.ptr, n1, n2, be, bk, ge, gk, abft._h, flags.ptr,
                                           stream))
-        if stream is not None:
-            self.eng.sync(stream)
-        f = flags.download().view(np.uint32)[:total]
-
-        def cut(stages, base):
-            return {name: f[base + off:base + off + int(np.prod(shape))].reshape(shape).copy() for name, (off, shape) in stages.items()}
-        baby = None
-        if n1 > 1:
-            hl = self.rotate_hoisted_checked_layout(n1 - 1)
-            baby = {"shared": cut(hl["shared"], 0), "rot": [cut(hl["rot"], hl["shared_words"] + r * hl["rot_words"]) for r in range(n1 - 1)]}
+        f = _read_flags(flags, total, stream)
+        baby = self._hoisted_flags(f, n1 - 1, lay["baby"]) if n1 > 1 else None
         giant = []
         for g in range(n2):
             base = lay["giant0"] + g * lay["giant_words"]
-            blk = cut({k: v for k, v in lay["giant"].items() if k != "keyswitch"}, base)
+            blk = self._split_flags(f, lay["giant"], self.BSGS_GIANT_STAGES[:3], base)
             blk["keyswitch"] = self._split_flags(f, self.checked_layout(), self.CHECKED_STAGES, base + lay["giant"]["keyswitch"][0])
             giant.append(blk)
         return o0, o1, {"baby": baby, "giant": giant}
@@ -786,12 +771,9 @@ class KeySwitch:
         total = lay["total"]
         o = self.eng.alloc(n_parts * (self.L - 1) * self.t.N)
         o.shape = (n_parts, self.L - 1, self.t.N)
-        flags = self.eng.upload(np.full((total + 1) // 2, 0xA5A5A5A5A5A5A5A5, dtype=_U64))      # the call clears them itself
+        flags = _flag_buffer(self.eng, total)
         check(lib.fhe_rescale_checked(self.eng._h, self._h, o.ptr, c.ptr, n_parts, abft._h, flags.ptr, stream))
-        if stream is not None:
-            self.eng.sync(stream)
-        f = flags.download().view(np.uint32)[:total]
-        return o, self._split_flags(f, lay, self.RESCALE_CHECKED_STAGES)
+        return o, self._split_flags(_read_flags(flags, total, stream), lay, self.RESCALE_CHECKED_STAGES)
 
     def hmult_checked(self, a0: DeviceArray, a1: DeviceArray, b0: DeviceArray, b1: DeviceArray, relin_key: DeviceArray, abft: "Abft",
                       rescale: bool = True, stream=None):
@@ -802,12 +784,10 @@ class KeySwitch:
         total = lay["total"]
         limbs = self.L - 1 if rescale else self.L
         o0, o1 = self._out(limbs), self._out(limbs)
-        flags = self.eng.upload(np.full((total + 1) // 2, 0xA5A5A5A5A5A5A5A5, dtype=_U64))      # the call clears them itself
+        flags = _flag_buffer(self.eng, total)
         check(lib.fhe_hmult_checked(self.eng._h, self._h, o0.ptr, o1.ptr, a0.ptr, a1.ptr, b0.ptr, b1.ptr, relin_key.ptr, 1 if rescale else 0,
                                     abft._h, flags.ptr, stream))
-        if stream is not None:
-            self.eng.sync(stream)
-        f = flags.download().view(np.uint32)[:total]
+        f = _read_flags(flags, total, stream)
         out = {"tensor": f[lay["tensor"]:lay["tensor"] + 3 * self.L].reshape(self.L, 3).copy(),
                "keyswitch": self._split_flags(f, self.checked_layout(), self.CHECKED_STAGES, lay["keyswitch"]),
                "rescale": self._split_flags(f, self.rescale_checked_layout(2), self.RESCALE_CHECKED_STAGES, lay["rescale"]) if rescale else None}

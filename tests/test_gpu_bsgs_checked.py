@@ -7,6 +7,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from helpers.checked_plan import checked_plan
+
 pytestmark = pytest.mark.gpu
 
 INVALID, UNSUPPORTED = 1, 3
@@ -27,24 +29,12 @@ def eng(F):
     return F.default_engine()
 
 
-def _limb_bits(kind, L, K):
-    """ciphertext limbs of one kind, special primes of the OTHER arithmetic path (mixed: alternating, specials alternating too)"""
-    if kind == "50":
-        return [50] * L + [61] * K
-    if kind == "61":
-        return [61] * L + [50] * K
-    if kind == "50/50":
-        return [50] * (L + K)
-    return [50 if i % 2 == 0 else 61 for i in range(L)] + [61 if i % 2 == 0 else 50 for i in range(K)]
-
-
 class _Case:
     def __init__(self, F, eng, logn, L, K, dnum, n1, n2, kind, seed):
         self.eng, self.logn, self.L, self.K, self.dnum, self.n1, self.n2 = eng, logn, L, K, dnum, n1, n2
         N = self.N = 1 << logn
-        qs = self.qs = F.create_moduli(N, _limb_bits(kind, L, K))
-        self.t = eng.tables(logn, qs)
-        rng = np.random.default_rng(seed)
+        qs, self.t, self.ks, self.ab, rng = checked_plan(F, eng, logn, L, K, dnum, kind, seed)
+        self.qs = qs
         mk = lambda rows: np.stack([rng.integers(0, q, N, dtype=np.uint64) for q in qs[:rows]])
         key = lambda: np.stack([np.stack([mk(L + K) for _ in range(2)]) for _ in range(dnum)])
         self.c0, self.c1 = mk(L), mk(L)
@@ -52,7 +42,6 @@ class _Case:
         self.baby_elts = [pow(3, b, 2 * N) for b in range(1, n1)]
         self.giant_elts = [pow(3, g * n1, 2 * N) for g in range(1, n2)]
         self.baby_keys, self.giant_keys = [key() for _ in self.baby_elts], [key() for _ in self.giant_elts]
-        self.ks, self.ab = F.KeySwitch(eng, self.t, L, K, dnum), F.Abft(eng, self.t)
         self.prepared = [self.ks.prepare_galois_key(eng.upload(k), e) for k, e in zip(self.baby_keys, self.baby_elts)]
         self.d_giant = [eng.upload(k) for k in self.giant_keys]
         self.d0, self.d1, self.dd = eng.upload(self.c0), eng.upload(self.c1), eng.upload(self.diags)

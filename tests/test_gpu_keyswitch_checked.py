@@ -7,6 +7,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from helpers.checked_plan import checked_plan
+
 pytestmark = pytest.mark.gpu
 
 INVALID, UNSUPPORTED = 1, 3
@@ -25,28 +27,13 @@ def eng(F):
     return F.default_engine()
 
 
-def _limb_bits(kind, L, K):
-    """ciphertext limbs of one kind, special primes of the OTHER arithmetic path (mixed: alternating, specials alternating too)"""
-    if kind == "50":
-        return [50] * L + [61] * K
-    if kind == "61":
-        return [61] * L + [50] * K
-    if kind == "50/50":
-        return [50] * (L + K)
-    if kind == "61/61":
-        return [61] * (L + K)
-    return [50 if i % 2 == 0 else 61 for i in range(L)] + [61 if i % 2 == 0 else 50 for i in range(K)]
-
-
 def _setup(F, eng, logn, L, K, dnum, kind, seed):
     N = 1 << logn
-    qs = F.create_moduli(N, _limb_bits(kind, L, K))
-    t = eng.tables(logn, qs)
-    rng = np.random.default_rng(seed)
+    qs, t, ks, ab, rng = checked_plan(F, eng, logn, L, K, dnum, kind, seed)
     poly = lambda: np.stack([rng.integers(0, q, N, dtype=np.uint64) for q in qs[:L]])
     c0, c1, c2 = poly(), poly(), poly()
     evk = np.stack([np.stack([np.stack([rng.integers(0, q, N, dtype=np.uint64) for q in qs]) for _ in range(2)]) for _ in range(dnum)])
-    return qs, t, F.KeySwitch(eng, t, L, K, dnum), F.Abft(eng, t), (c0, c1, c2), evk
+    return qs, t, ks, ab, (c0, c1, c2), evk
 
 
 def _clean(flags):
