@@ -174,13 +174,18 @@ int fhe_modmul(fhe_ctx *ctx, uint64_t *d_c, const uint64_t *d_a, const uint64_t 
 /* c = (c + a*b) mod q: keyswitch / BSGS inner-product accumulate (motivation/bsgs.py:50) */
 int fhe_modmul_acc(fhe_ctx *ctx, uint64_t *d_c, const uint64_t *d_a, const uint64_t *d_b, const fhe_ntt_tables *t,
                    size_t n_poly, size_t limbs, size_t start_idx, void *stream);
-/* c = (a + b) mod q per limb (phantom::add_inplace, reliability_test/dotprod_test.cu:147) */
+/* c = (a + b) mod q per limb (phantom::add_inplace, reliability_test/dotprod_test.cu:147); fhe_modsub: c = (a - b) mod q.
+ * Operands need not be canonical: any 64-bit word stands for its residue modulo q_l, the result is in [0, q_l).  Buffers are
+ * [n_poly][limbs][N] (dense in the window's limbs when start_idx > 0); c may alias a or b, and a may alias b. */
 int fhe_modadd(fhe_ctx *ctx, uint64_t *d_c, const uint64_t *d_a, const uint64_t *d_b, const fhe_ntt_tables *t, size_t n_poly,
                size_t limbs, size_t start_idx, void *stream);
 int fhe_modsub(fhe_ctx *ctx, uint64_t *d_c, const uint64_t *d_a, const uint64_t *d_b, const fhe_ntt_tables *t, size_t n_poly,
                size_t limbs, size_t start_idx, void *stream);
 /* c = a * mul[l] + add[l] mod q_l with one host-side scalar pair per limb (either array may be NULL:
- * mul defaults to 1, add to 0); limbs <= 64.  Scalar steps of mod-switching and BGV decryption
+ * mul defaults to 1, add to 0); limbs <= 64, more is FHE_ERR_UNSUPPORTED with nothing launched.  Neither the words of a nor the
+ * scalars need be canonical: any 64-bit value stands for its residue modulo q_l (the scalars are reduced on the host, the words in
+ * the kernel), so with both arrays NULL the call is c = a mod q.  The result is in [0, q_l); c may alias a.  Scalar steps of
+ * mod-switching and BGV decryption
  * (phantom::mod_switch_to_next_inplace / PhantomSecretKey::decrypt, dotprod_test.cu:115,119). */
 int fhe_scalar_affine(fhe_ctx *ctx, uint64_t *d_c, const uint64_t *d_a, const uint64_t *mul, const uint64_t *add,
                       const fhe_ntt_tables *t, size_t n_poly, size_t limbs, size_t start_idx, void *stream);
