@@ -16,6 +16,7 @@ from .engine import (  # noqa: F401
     automorphism_checked,
     DeviceArray,
     Engine,
+    FourStep,
     NttTables,
     bConv,
     base_conv_fixed,
@@ -24,6 +25,7 @@ from .engine import (  # noqa: F401
     default_engine,
     diag_block_hadamard_matvec,
     four_step_ntt,
+    four_step_with_protection_vector,
     intt,
     intt_nthroot,
     min_primitive_root,

@@ -70,6 +70,10 @@ _SIG = {
     "fhe_fourstep_destroy": (ci, [vp]),
     "fhe_fourstep_ntt": (ci, [vp, vp, vp, vp, vp]),
     "fhe_fourstep_ntt_batch": (ci, [vp, vp, vp, vp, sz, vp]),
+    "fhe_fourstep_prepare_checked": (ci, [vp, vp, vp]),
+    "fhe_fourstep_checksum": (ci, [vp, vp, ci, vp, vp, sz, vp]),
+    "fhe_fourstep_ntt_checked": (ci, [vp, vp, vp, vp, sz, vp, vp]),
+    "fhe_fourstep_ntt_checked_phases": (ci, [vp, vp, vp, vp, sz, vp, vp]),
     "fhe_modmul": (ci, [vp, vp, vp, vp, vp, sz, sz, sz, vp]),
     "fhe_modmul_acc": (ci, [vp, vp, vp, vp, vp, sz, sz, sz, vp]),
     "fhe_polymul": (ci, [vp, vp, vp, vp, vp, sz, sz, sz, vp]),

@@ -8,6 +8,7 @@
 //   forward  X = F x           :  sum_i w_i x_i  ==  sum_j w^_j X_j
 //   inverse  x = F^-1 X        :  sum_j w^_j X_j ==  sum_i w_i x_i         (the same two tables, sides swapped)
 //   product  C_j = A_j B_j     :  sum_i w_i c_i  ==  sum_j w^_j A_j B_j    (c = F^-1 C)
+//   natural-order (four-step) transform y = W x :  sum u x == sum m z == sum v y    (GsTap below)
 // A fault between a tap's read of a register and the instruction that consumes the same register is not covered.
 #pragma once
 #include "ntt_plan.hpp"   // (NTT_THREADS)
@@ -140,6 +141,71 @@ struct PhaseTap {
     }
     FHE_D void mid(u32 idx, elem x, const typename A::Ctx &c) { weigh(acc_b, n_b, x, idx, umid, umid8, c); }
     FHE_D void out(u32 idx, u64 v, const typename A::Ctx &c) { weigh(acc_b, n_b, A::from_canonical(v), idx, wout, wout8, c); }
+};
+
+// Checked natural-order transform (the four-step flow, reliability_test/four_step_ntt_prot.py:185-252: its two stages are checked
+// with sum(C) == col_sums(A) . row_sums(B) and reported as stage1 / stage2).  y = W x, W[kappa][t] = omega^(kappa t), runs as the
+// transposed network F^T of the forward one (F = R W, R the bit reversal): launch 1 = the gathering inverse row pass (RowPass
+// ROWMODE 1), launch 2 = the inverse column pass; E1 = 2^S0 columns, E2 = 2^P points.  Weights (capi_fourstep_checked.cpp):
+//   v  on the natural-order words launch 2 stores: v_kappa = (kappa mod 2^logp + 1) + (kappa div 2^logp + 1)  (generate_weights,
+//      negaclic_ntt.py:7-13; the reference's all-ones weights would weigh x_0 only, W 1 = N delta_0);
+//   u = W^T v = W v  on the words launch 1 gathers, at their NATURAL source index -- network position (local row, column k) of the
+//      tile that starts at row0 holds src[brev_P(k) 2^S0 + row0 + row] (RowPass::gather_in);
+//   m = B^T v, B = launch 2's map, on the hand-off words.  Launch 1 leaves, at hand-off address brev_S0(c) E2 + k,
+//      Z[c][k] = omega^(c k) sum_rho x[rho E1 + c] omega^(E1 k rho)  -- the twiddle omega^(c k) rides on the butterflies of LAUNCH 1,
+//      whose stages' table entries carry the row index -- in the arithmetic's lazy form, and y[kappa] = sum_c omega^(E2 j c) Z[c][k]
+//      for kappa = k + E2 j.  So m[c][k] = sum_{j < E1} v[k + E2 j] (omega^(E2 c))^j: the forward column pass of v.
+// Identities per vector (two-launch sizes):  sum u x == sum m z (launch 1),  sum m z as stored == as loaded (hand-off),
+// sum m z == sum v y (launch 2); single-launch sizes and the whole-transform form: sum u x == sum v y.
+// Not covered: faults already in the input, a fault between a tap's read of a register and the instruction that consumes the same
+// register, a wrong plan handed in by the caller; a fault e at a word is invisible exactly when e * weight == 0 (mod q), which is why
+// preparation refuses a plan with a zero entry in u, m or v.
+// LAUNCH 0: in = u (acc_a), mid = m (acc_b; single-launch sizes: out = v); LAUNCH 1: in = m (acc_a), out = v (acc_b).
+// pos0: LAUNCH 0 = the tile's first row (row0), LAUNCH 1 = address of the tile's first word inside the vector.
+template <class A, int LAUNCH, int P, int S0, bool WITH_A, bool WITH_B>
+struct GsTap {
+    static constexpr bool ACTIVE = true;
+    static constexpr bool MID = LAUNCH == 0 && WITH_B;
+    static constexpr bool STORES = false;
+    typedef typename A::elem elem;
+    TwPtr u, m, v;                       // ArithU64: Shoup-encoded weights, from the vector's first word
+    const u64 FHE_GLOBAL *u8, *m8;       // ArithF64: u and m as plain residues (v is made in registers)
+    u32 pos0;
+    int logp;
+    elem acc_a, acc_b;
+    int n_a, n_b;
+    FHE_D void weigh(elem &acc, int &n, elem x, u32 at, TwPtr tw, const u64 FHE_GLOBAL *tw8, const typename A::Ctx &c)
+    {
+        if constexpr (A::PATH == PATH_F64) {
+            const double w = A::from_canonical(tw8[at]);
+            A::lazy_acc(acc, A::mulmod_w(x, w, w * c.ninv, c), ++n, c);
+        } else {
+            A::lazy_acc(acc, A::mulmod(x, tw[at], c), ++n, c);
+        }
+    }
+    FHE_D void in(u32 idx, elem x, const typename A::Ctx &c)
+    {
+        if constexpr (WITH_A) {
+            if constexpr (LAUNCH == 0) weigh(acc_a, n_a, x, (brev_bits(idx & ((1u << P) - 1u), P) << S0) + pos0 + (idx >> P), u, u8, c);
+            else weigh(acc_a, n_a, x, pos0 + idx, m, m8, c);
+        }
+    }
+    FHE_D void mid(u32 idx, elem x, const typename A::Ctx &c)
+    {
+        if constexpr (WITH_B) weigh(acc_b, n_b, x, (brev_bits(pos0 + (idx >> P), S0) << P) + (idx & ((1u << P) - 1u)), m, m8, c);
+    }
+    FHE_D void out(u32 idx, u64 y, const typename A::Ctx &c)
+    {
+        if constexpr (WITH_B) {
+            const u32 i = LAUNCH == 0 ? idx : pos0 + idx;      // (LAUNCH 0 stores canonical words only as a single launch: one tile, row 0)
+            if constexpr (A::PATH == PATH_F64) {
+                const double w = ArithF64::from_canonical((u64)((i & ((1u << logp) - 1u)) + (i >> logp) + 2u));
+                A::lazy_acc(acc_b, A::mulmod_w(A::from_canonical(y), w, w * c.ninv, c), ++n_b, c);
+            } else {
+                A::lazy_acc(acc_b, A::mulmod(A::from_canonical(y), v[i], c), ++n_b, c);
+            }
+        }
+    }
 };
 
 // Checked product, the middle launch (k_polymul_mid_checked): for every point j of the tile, with a^_j and b^_j as the forward

@@ -230,6 +230,16 @@ struct fhe_fourstep {
     bool big = false;
     int log1 = 0, log2 = 0, lo_bits = 0;
     DevBuf tw_lo, tw_hi, buf0, buf1;
+    // checked calls (capi_fourstep_checked.cpp), built by fhe_fourstep_prepare_checked: the weights v (output side), u = W v (input
+    // side, natural source index) and m (hand-off words, two-launch sizes) as residues and in twiddle encoding, the partial sums
+    // (sum u x, sum m z as stored, sum m z as loaded, sum v y; grown on demand) and, for N < 32, the modulus' constants for the
+    // reduction launches.  checked_ready is set only after the last upload succeeded.
+    struct Checked {
+        DevBuf u8, m8, v8, eu, em, ev, sums[4];
+        std::unique_ptr<fhe_ntt_tables> small;
+    };
+    std::unique_ptr<Checked> chk;
+    bool checked_ready = false;
 };
 
 

@@ -332,7 +332,7 @@ template <class T, class = void> struct tap_preloads { static constexpr bool val
 template <class T> struct tap_preloads<T, decltype((void)T::PRELOAD)> { static constexpr bool value = T::PRELOAD; };
 struct NoTap {
     static constexpr bool ACTIVE = false;
-    static constexpr bool MID = false;    // MID: the tap also sees the lazy words a column pass hands to the next launch
+    static constexpr bool MID = false;    // MID: the tap also sees the lazy words a pass hands to the next launch
     static constexpr bool STORES = false; // STORES: the tap writes the forward row pass's results itself (an epilogue fused into the pass)
 };
 
@@ -679,6 +679,12 @@ struct RowPass {
                 } else if constexpr (INVERSE) radix_inv<A, K, RED, U0, SBLK, FOLD>(x, tw, S0 + DONE, prefix, c, &inv_n);
                 else radix_fwd<A, K, RED, U0, SBLK>(x, tw, S0 + DONE, prefix, c);
                 if (LAST) {
+                    if constexpr (TAP::ACTIVE && TAP::MID) {      // (the lazy words an inverse row pass hands to the next launch)
+                        if constexpr (TO_GLOBAL && OUT_MODE == IO_LAZY) {
+#pragma unroll
+                            for (int r = 0; r < R; r++) tap->mid(row * NPTS + g0 + ((u32)r << LOGS), x[r], c);
+                        }
+                    }
 #pragma unroll
                     for (int r = 0; r < R; r++) {
                         const u64 out = convert_out<A, OUT_MODE, INVERSE, FOLD>(x[r], c, inv_n);

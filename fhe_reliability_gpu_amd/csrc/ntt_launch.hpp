@@ -106,6 +106,26 @@ hipError_t launch_ntt_phases(hipStream_t st, const PassArgs &a, const PhaseArgs 
 hipError_t launch_compare_phases(hipStream_t st, u32 *flags, const u64 *s_in, const u64 *s_mid1, u32 tc, const u64 *s_mid2, const u64 *s_out, u32 tr,
                                  const LimbParams *lp, u32 limb0, u32 limbs, u32 units);
 
+// ---- fourstep_checked.hip: launch_ntt_gs with the detector (abft_taps.hpp GsTap), one modulus (a.limbs == 1, unit = vector) ----
+// One GsCheckArgs per launch.  u / m / v = [N] weights in twiddle encoding (integer path), u8 / m8 = u and m as residues (FP64 path,
+// which makes v in registers); m may be null for single-launch sizes.  sum_a / sum_b = that launch's [vectors][tiles] partial sums
+// (tiles from ntt_gs_checked_tiles): launch 1 sum u x / sum m z (single-launch sizes: sum v y), launch 2 sum m z / sum v y.
+// phases = false (whole-transform form): launch 1 fills only sum_a, launch 2 only sum_b.  fault_*: test hook of the per-phase form,
+// a bit flip in the LDS image of workgroup fault_block of launch fault_pass between its first two register steps (< 0: off).
+// which as in launch_ntt (the between-launch hook splits the launches).
+struct GsCheckArgs {
+    const Tw *u, *m, *v;
+    const u64 *u8, *m8;
+    int logp;
+    u64 *sum_a, *sum_b;
+    int fault_pass;
+    u32 fault_block, fault_word;
+    int fault_bit;
+};
+void ntt_gs_checked_tiles(int logn, u32 *t1, u32 *t2);
+hipError_t launch_ntt_gs_checked(hipStream_t st, const PassArgs &a, u64 *tmp, const GsCheckArgs &c1, const GsCheckArgs &c2, int logn, int path,
+                                 bool phases, int which = -1);
+
 // packed hand-off between the two launches (forward 2^16, FP64 limbs): when PassArgs::scratch is set (ntt_packed_scratch_words()
 // 64-bit words per unit) the intermediate travels as 50-bit residues in 16x16 blocks instead of 8-byte words in place
 bool ntt_packed_supported(int logn, bool inverse, int path);

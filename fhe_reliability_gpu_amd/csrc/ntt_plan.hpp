@@ -142,6 +142,19 @@ struct Passes {
                     INVERSE ? IO_LAZY : IO_CANONICAL, INVERSE ? RED_FIRST : RED_SECOND, SB, 0, true> RowNt;
 };
 
+// The two launches of the natural-order transform (ntt_kernels.hip launch_gs_t, the four-step flow): the gathering inverse row pass
+// (RowPass ROWMODE 1) and the inverse column pass; single-launch sizes (2^5 .. 2^12) are the first one alone, writing canonical words.
+template <class A, int LOGN>
+struct GsPasses {
+    static constexpr int GEO = LOGN >= 13 ? 1 : 0;
+    typedef Passes<A, LOGN, true, GEO> PS;
+    static constexpr bool TWO = PS::G::TWO_PASS;
+    typedef RowPass<A, typename PS::PL::Row, LOGN, TWO ? PS::G::TR : 1, NTT_THREADS, true, IO_CANONICAL, TWO ? IO_LAZY : IO_CANONICAL, PS::RED_FIRST,
+                    PS::SB, 0, false, false, 1> First;
+    typedef typename PS::Col Second;
+    typedef typename PS::ColNt SecondNt;     // pieces of a batch that streams from HBM: non-temporal stores
+};
+
 // the row passes of the negacyclic product's middle launch (ntt_kernels.hip k_polymul_mid): the forward one leaves its results in the LDS image in the arithmetic's LAZY form
 // and the inverse one takes them from there in that form, so the product never goes through canonical words
 template <class A, int LOGN, int GEO>

@@ -368,6 +368,88 @@ def four_step_ntt(a, N: int, mod: int = 998244353, g: int = 3, n1: Optional[int]
         lib.fhe_fourstep_destroy(h)
 
 
+class FourStep:
+    """Four-step plan of N = n1 * n2 points (reliability_test/four_step_ntt_prot.py:71-79) with the unchecked and the
+    ABFT-checked natural-order transform of batches ``[n_vec][N]``.  One plan, one stream at a time."""
+
+    def __init__(self, eng: Engine, n1: int, n2: int, mod: int = 998244353, g: int = 3):
+        self.eng, self.n1, self.n2, self.N, self.mod, self.g = eng, n1, n2, n1 * n2, mod, g
+        h = vp()
+        check(lib.fhe_fourstep_create(eng._h, n1, n2, mod, g, C.byref(h)))
+        self._h = h
+
+    def prepare_checked(self, stream=None):
+        """Build the weight tables of the checked calls now (they do it on first use otherwise)."""
+        check(lib.fhe_fourstep_prepare_checked(self.eng._h, self._h, stream))
+
+    def ntt(self, src: DeviceArray, dst: DeviceArray, n_vec: int = 1, stream=None):
+        """``four_step_ntt`` of every vector (four_step_ntt_prot.py:71-109); ``dst`` may be ``src``."""
+        check(lib.fhe_fourstep_ntt_batch(self.eng._h, dst.ptr, src.ptr, self._h, n_vec, stream))
+
+    def checksum(self, d: DeviceArray, side: int, n_vec: int = 1, stream=None) -> np.ndarray:
+        """Per vector: sum u x over input vectors (side 0) or sum v y over output vectors (side 1) modulo ``mod``, the two sides
+        of the whole-transform check (``fhe_fourstep_checksum``)."""
+        out = self.eng.alloc(n_vec)
+        check(lib.fhe_fourstep_checksum(self.eng._h, self._h, side, d.ptr, out.ptr, n_vec, stream))
+        if stream is not None:
+            self.eng.sync(stream)
+        return out.download()
+
+    def ntt_checked(self, src: DeviceArray, dst: DeviceArray, n_vec: int = 1, stream=None) -> np.ndarray:
+        """``ntt`` with the whole-transform check sum u x == sum v y riding on the launches; the words are ``ntt``'s, bit for
+        bit.  Returns flags[n_vec] (uint32, 0 / 1)."""
+        flags = _flag_buffer(self.eng, n_vec)
+        check(lib.fhe_fourstep_ntt_checked(self.eng._h, dst.ptr, src.ptr, self._h, n_vec, flags.ptr, stream))
+        return _read_flags(flags, n_vec, stream).copy()
+
+    def ntt_checked_phases(self, src: DeviceArray, dst: DeviceArray, n_vec: int = 1, stream=None) -> np.ndarray:
+        """``ntt`` with one check per phase (N >= 2^13): flags[n_vec, 3] = launch 1 (the reference's stage 1), the hand-off
+        between the launches, launch 2 (stage 2)."""
+        flags = _flag_buffer(self.eng, 3 * n_vec)
+        check(lib.fhe_fourstep_ntt_checked_phases(self.eng._h, dst.ptr, src.ptr, self._h, n_vec, flags.ptr, stream))
+        return _read_flags(flags, 3 * n_vec, stream).reshape(n_vec, 3).copy()
+
+    def close(self):
+        if getattr(self, "_h", None) and self.eng._h:
+            lib.fhe_fourstep_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def four_step_with_protection_vector(a, N: int, mod: int = 998244353, g: int = 3, n1: Optional[int] = None, eng: Optional[Engine] = None):
+    """``four_step_with_protection_vector(a, N, mod, g)`` of reliability_test/four_step_ntt_prot.py:196-252: the four-step
+    transform of ``a`` with its stages checked.  Returns ``(y, checks)``; for N >= 2^13
+    ``checks = {"stage1": {"ok": bool}, "handoff": {"ok": bool}, "stage2": {"ok": bool}}`` (the engine's two launches are the
+    reference's two stages, and the buffer between them is checked as well), below that ``{"transform": {"ok": bool}}``.
+
+    Differences from the reference: the checksums are weighted sums with the weights of ``generate_weights``
+    (rfhe_framewk/src/negaclic_ntt.py:7-13) on the output, their transposed images on the hand-off and on the input, instead
+    of the reference's all-ones vectors, under which only x_0 would be weighed (W 1 = N delta_0; the reference calls its own
+    check weak); and the ``lhs`` / ``rhs`` values of the reference's dictionaries are not returned, the comparison happens on
+    the device."""
+    eng = eng or default_engine()
+    log_n = _log2(N)
+    if n1 is None:
+        n1 = 1 << (log_n // 2)
+    fs = FourStep(eng, n1, N // n1, mod, g)
+    try:
+        src = eng.upload(_arr(a).reshape(N))
+        dst = eng.alloc(N)
+        if log_n >= 13:
+            f = fs.ntt_checked_phases(src, dst)[0]
+            checks = {"stage1": {"ok": not f[0]}, "handoff": {"ok": not f[1]}, "stage2": {"ok": not f[2]}}
+        else:
+            checks = {"transform": {"ok": not fs.ntt_checked(src, dst)[0]}}
+        return [int(x) for x in dst.download()], checks
+    finally:
+        fs.close()
+
+
 class BaseConv:
     """Base-conversion plan for (moduli_in -> moduli_out)."""
 

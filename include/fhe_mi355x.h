@@ -165,6 +165,33 @@ int fhe_fourstep_ntt(fhe_ctx *ctx, uint64_t *d_dst, const uint64_t *d_src, fhe_f
  * transforms read the input's columns directly (no transpose pass), the row transforms carry the twiddle step in their
  * butterflies and write natural order. */
 int fhe_fourstep_ntt_batch(fhe_ctx *ctx, uint64_t *d_dst, const uint64_t *d_src, fhe_fourstep *p, size_t n_vec, void *stream);
+/* ABFT-checked four-step transform (four_step_with_protection_vector, reliability_test/four_step_ntt_prot.py:185-252, which checks
+ * its two stages with sum(C) == col_sums(A) . row_sums(B) and reports stage1 / stage2).  The words written are those of
+ * fhe_fourstep_ntt_batch, bit for bit; the weighted checksums ride on the two launches (no extra sweep over the data):
+ *   v_kappa = (kappa mod 2^(logN/2) + 1) + (kappa div 2^(logN/2) + 1) on the natural-order output (generate_weights,
+ *   rfhe_framewk/src/negaclic_ntt.py:7-13 -- not the reference's all-ones weights, which weigh x_0 only), u = W v on the input,
+ *   m = (launch 2)^T v on the hand-off words between the launches; per vector
+ *     launch 1: sum u x == sum m z,   hand-off: sum m z as stored == as loaded,   launch 2: sum m z == sum v y.
+ * Not covered: faults already in the input, a fault between a tap's read of a register and the instruction that consumes it, a wrong
+ * plan handed in by the caller.  A fault e at a word is invisible exactly when e * weight == 0 modulo `mod`: preparation fails with
+ * FHE_ERR_UNSUPPORTED (naming the table and the index) when an entry of u, m or v is 0 modulo `mod` -- tiny moduli do this.
+ * Plans past N = 2^20 return FHE_ERR_UNSUPPORTED; n_vec == 0 returns FHE_OK and touches nothing; d_dst may equal d_src.  Batches
+ * that fhe_fourstep_ntt_batch cuts are cut the same way (never while a test hook is armed).
+ * _prepare_checked builds the weight tables (one unchecked transform of v and one column pass); the other calls run it on first
+ * use, except inside a stream capture, where they return FHE_ERR_INVALID when the tables (or the batch's scratch) are missing.
+ * _checksum: d_out[vector] = sum u x (side 0, d_data = input vectors) or sum v y (side 1, d_data = output vectors) modulo `mod`.
+ * _ntt_checked: d_flags = one uint32 per vector (0 / 1), sum u x != sum v y; N = 2 .. 2^20 (below 32: separate reduction launches).
+ * _ntt_checked_phases: d_flags = [n_vec][3], launch 1 / hand-off / launch 2; N >= 2^13, FHE_ERR_UNSUPPORTED below.
+ * Test hooks (no setter of their own): fhe_ctx_inject_fault(idx, bit) flips word idx of the hand-off buffer [n_vec][N] between the
+ * two launches; fhe_ctx_inject_fault_in_pass(pass, workgroup, lds_word, bit) flips a word of that workgroup's LDS image between the
+ * first two register steps of launch `pass` (per-phase call only).  Both are read and disarmed by either checked call whatever its
+ * outcome; a call without such a point (single-launch sizes, the in-pass hook on the whole-transform call) returns
+ * FHE_ERR_UNSUPPORTED, an index outside the call's window FHE_ERR_INVALID, before anything is launched. */
+int fhe_fourstep_prepare_checked(fhe_ctx *ctx, fhe_fourstep *p, void *stream);
+int fhe_fourstep_checksum(fhe_ctx *ctx, fhe_fourstep *p, int side, const uint64_t *d_data, uint64_t *d_out, size_t n_vec, void *stream);
+int fhe_fourstep_ntt_checked(fhe_ctx *ctx, uint64_t *d_dst, const uint64_t *d_src, fhe_fourstep *p, size_t n_vec, uint32_t *d_flags, void *stream);
+int fhe_fourstep_ntt_checked_phases(fhe_ctx *ctx, uint64_t *d_dst, const uint64_t *d_src, fhe_fourstep *p, size_t n_vec, uint32_t *d_flags,
+                                    void *stream);
 
 /* ---- coefficient-wise products (a4, a5) ------------------------------------------ */
 /* C_hat[i] = A_hat[i] * B_hat[i] % mod (rfhe_framewk/src/negaclic_ntt.py:126), per limb;
