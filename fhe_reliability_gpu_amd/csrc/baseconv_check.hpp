@@ -30,8 +30,6 @@
 
 namespace fhe {
 
-FHE_HD u32 res_sub(u32 a, u32 b) { return res_add(a, ~b); }      // one's complement: -b = ~b (mod m)
-
 // a w mod q with the residue of its quotient: a w = k q + t over the integers, 0 <= t < q for any 64-bit a (w < q,
 // ws = floor(w 2^64 / q), q < 2^62).  rk = r(k); k <= a fits 64 bits, but qh + 1 is never formed (a faulted qh may be 2^64 - 1).
 FHE_HD u64 bc_shoup_k(u64 a, u64 w, u64 ws, u64 q, u32 &rk, const PwFault &f, bool first, bool closing)

@@ -3,22 +3,12 @@
 // own, so that the base-conversion kernels of aux_kernels.hip compile exactly as before.  One lane = one coefficient, limb
 // rows read and written at stride N as the unchecked kernels do; a failing lane ORs its unit's flag word with a global
 // atomic, a clean run stores nothing extra.
-#include "ntt_launch.hpp"
+#include "checked_kernel.hpp"
 #include "baseconv_check.hpp"
 
 namespace fhe {
 
 constexpr int BCC_MAX_LIMBS = 64;
-
-// HOOK: the one-shot test fault of fhe_ctx_inject_fault_baseconv is armed (a separate instantiation, so that the clean
-// kernels carry no compare against the fault's unit and coefficient).  The fault is a function of (unit, coefficient)
-// alone: every workgroup that recomputes a digit for its slice of the outputs sees the same wrong digit.
-template <bool HOOK>
-__device__ __forceinline__ PwFault bc_fault_at(const BcCheck &k, u32 unit, u64 coeff)
-{
-    if (!HOOK) return PwFault{-1, 0};
-    return PwFault{k.fault_point, unit == k.fault_unit && coeff == k.fault_coeff ? k.fault_mask : 0};
-}
 
 // the constants in LDS are invariant in the coefficient loop: without this the compiler hoists every read out of it
 __device__ __forceinline__ void bcc_no_hoist() { __asm__ volatile("" ::: "memory"); }
@@ -64,7 +54,7 @@ __global__ __launch_bounds__(256) void k_bc_exact_checked(BcCheckedJob cj, u64 N
                 u32 fl;
                 c[j] = bc_checked_digit<UNR>(in[row * N + i], j, c, rc,
                                         [&](int l) -> Tw { if (FIXED) return s_dig[l * M + j]; const Tw t = dig[l * m + j]; return t; }, p, res64(p), fl,
-                                        bc_fault_at<HOOK>(cj.chk, (u32)j, i));
+                                        fault_at<HOOK>(cj.chk, (u32)j, i));
                 rc[j] = res64(c[j]);
                 if (fl) atomicOr(cj.chk.flags + j, fl);
             }
@@ -74,7 +64,7 @@ __global__ __launch_bounds__(256) void k_bc_exact_checked(BcCheckedJob cj, u64 N
             const u64 q = FIXED ? s_q[o - o0] : mod_out[o];
             u32 fl;
             const u64 w = bc_checked_out<UNR>(m, c, rc, [&](int l) -> Tw { if (FIXED) return s_hor[(o - o0) * M + l]; const Tw t = hor[l * k + o]; return t; }, q,
-                                         res64(q), fl, bc_fault_at<HOOK>(cj.chk, (u32)(m + o), i));
+                                         res64(q), fl, fault_at<HOOK>(cj.chk, (u32)(m + o), i));
             out[(u64)((u32)o < job.gap_at ? o : o + job.gap) * N + i] = w;
             if (fl) atomicOr(cj.chk.flags + m + o, fl);
         }
@@ -94,7 +84,7 @@ __global__ __launch_bounds__(256) void k_bconv_fast_checked(u64 *__restrict__ ou
             const u64 q = mod_out[o];
             u32 fl;
             out[(u64)o * N + i] = bc_checked_fast(m, [&](int j) { return in[(u64)j * N + i]; }, [&](int j) { return Tw{coef[j * k + o], shoup[j * k + o]}; }, q,
-                                                  res64(q), q * (u64)m, fl, bc_fault_at<HOOK>(chk, (u32)o, i));
+                                                  res64(q), q * (u64)m, fl, fault_at<HOOK>(chk, (u32)o, i));
             if (fl) atomicOr(chk.flags + o, fl);
         }
     }
@@ -109,15 +99,17 @@ static u32 bcc_slices(u32 gx, int m, int k, u32 target)
     return slices;
 }
 
+// the instantiation for a base of m limbs
+using BcExactKernel = void (*)(BcCheckedJob, u64, u32);
 template <bool HOOK>
-static void launch_exact_checked(hipStream_t st, dim3 grid, const BcCheckedJob &cj, u64 N, u32 oc)
+static BcExactKernel bc_exact_kernel(int m)
 {
-    switch (cj.job.pl.m <= 16 ? cj.job.pl.m : 0) {
-#define FHE_BCC(MM) case MM: hipLaunchKernelGGL((k_bc_exact_checked<MM, HOOK>), grid, dim3(256), 0, st, cj, N, oc); break;
+    switch (m <= 16 ? m : 0) {
+#define FHE_BCC(MM) case MM: return k_bc_exact_checked<MM, HOOK>;
         FHE_BCC(1) FHE_BCC(2) FHE_BCC(3) FHE_BCC(4) FHE_BCC(5) FHE_BCC(6) FHE_BCC(7) FHE_BCC(8)
         FHE_BCC(9) FHE_BCC(10) FHE_BCC(11) FHE_BCC(12) FHE_BCC(13) FHE_BCC(14) FHE_BCC(15) FHE_BCC(16)
 #undef FHE_BCC
-    default: hipLaunchKernelGGL((k_bc_exact_checked<0, HOOK>), grid, dim3(256), 0, st, cj, N, oc); break;
+    default: return k_bc_exact_checked<0, HOOK>;
     }
 }
 
@@ -126,24 +118,17 @@ hipError_t launch_baseconv_exact_checked(hipStream_t st, const BcCheckedJob &cj,
     const BaseConvPlanDev &pl = cj.job.pl;
     if (pl.m < 1 || pl.k < 1 || pl.m > BCC_MAX_LIMBS || pl.k > 64) return hipErrorInvalidValue;
     if (!N) return hipSuccess;
-    const u64 want = (N + 255) / 256;
-    const u32 gx = (u32)(want > 16384 ? 16384 : want);
+    const u32 gx = checked_grid(N, 16384);
     const u32 slices = bcc_slices(gx, pl.m, pl.k, 1024), oc = ((u32)pl.k + slices - 1) / slices;
     const dim3 grid(gx, ((u32)pl.k + oc - 1) / oc);
-    if (cj.chk.fault_point >= 0) launch_exact_checked<true>(st, grid, cj, N, oc);
-    else launch_exact_checked<false>(st, grid, cj, N, oc);
-    return hipGetLastError();
+    return launch_checked(bc_exact_kernel<false>(pl.m), bc_exact_kernel<true>(pl.m), cj.chk, grid, st, cj, N, oc);
 }
 
 hipError_t launch_bconv_fast_checked(hipStream_t st, u64 *out, const u64 *in, const BaseConvPlanDev &pl, const BcCheck &chk, u64 N)
 {
     if (pl.m < 1 || pl.k < 1 || pl.m > BCC_MAX_LIMBS || pl.k > 64) return hipErrorInvalidValue;
     if (!N) return hipSuccess;
-    const u64 want = (N + 255) / 256;
-    const dim3 g((u32)(want > 4096 ? 4096 : want)), b(256);
-    if (chk.fault_point >= 0) hipLaunchKernelGGL(k_bconv_fast_checked<true>, g, b, 0, st, out, in, pl, chk, N);
-    else hipLaunchKernelGGL(k_bconv_fast_checked<false>, g, b, 0, st, out, in, pl, chk, N);
-    return hipGetLastError();
+    return launch_checked(k_bconv_fast_checked<false>, k_bconv_fast_checked<true>, chk, dim3(checked_grid(N, 4096)), st, out, in, pl, chk, N);
 }
 
 } // namespace fhe

@@ -4,19 +4,10 @@
 // as before.  Both stream from HBM, one element per lane, same loops, grids, loads and stores as the unchecked kernels; the residue
 // work is 32-bit lane arithmetic beside the 64-bit products; a failing lane ORs its unit's flag word with a global atomic, a clean
 // run stores nothing extra.  No LDS.
-#include "ntt_launch.hpp"
+#include "checked_kernel.hpp"
 #include "bsgs_check.hpp"
 
 namespace fhe {
-
-// HOOK: the one-shot test fault is armed (a separate instantiation, so that the clean kernels carry no compare against the fault's
-// unit and coefficient)
-template <bool HOOK>
-__device__ __forceinline__ PwFault bsgs_fault_at(const BcCheck &k, u32 unit, u64 coeff)
-{
-    if (!HOOK) return PwFault{-1, 0};
-    return PwFault{k.fault_point, unit == k.fault_unit && coeff == k.fault_coeff ? k.fault_mask : 0};
-}
 
 template <class D, bool HOOK>
 __device__ __forceinline__ void diag_mac_elem_checked(const DiagMacArgs &a, const BcCheck &k, u64 e, const LimbParams &p)
@@ -24,7 +15,7 @@ __device__ __forceinline__ void diag_mac_elem_checked(const DiagMacArgs &a, cons
     const u64 part = (u64)a.limbs << a.logn;
     const u32 l = (u32)(e >> a.logn);
     const u64 i = e & (((u64)1 << a.logn) - 1);
-    const PwFault f0 = bsgs_fault_at<HOOK>(k, l, i), f1 = bsgs_fault_at<HOOK>(k, a.limbs + l, i);
+    const PwFault f0 = fault_at<HOOK>(k, l, i), f1 = fault_at<HOOK>(k, a.limbs + l, i);
     DiagDot<D> s;
     for (u32 b = 0; b < a.n1; b++) {
         const u64 d = a.diag[(u64)b * part + e];
@@ -66,7 +57,7 @@ __global__ __launch_bounds__(256) void k_modadd_checked(PointwiseArgs p, BcCheck
         const u64 q = lp.q;
         const u64 i = (((u64)poly * p.poly_stride + l) << p.logn) + (i_ & (n - 1));
         u32 fl;
-        p.c[i] = checked_modadd(p.a[i], p.b[i], q, lp.barrett_lo, lp.barrett_hi, res64(q), fl, bsgs_fault_at<HOOK>(k, unit, i_ & (n - 1)));
+        p.c[i] = checked_modadd(p.a[i], p.b[i], q, lp.barrett_lo, lp.barrett_hi, res64(q), fl, fault_at<HOOK>(k, unit, i_ & (n - 1)));
         if (fl) atomicOr(k.flags + unit, fl);
     }
 }
@@ -75,22 +66,14 @@ hipError_t launch_diag_mac_checked(hipStream_t st, const DiagMacArgs &a, const B
 {
     const u64 total = (u64)a.limbs << a.logn;
     if (!total || !a.n1) return hipSuccess;
-    const u64 want = (total + 255) / 256;
-    const dim3 g((u32)(want > 16384 ? 16384 : want)), b(256);
-    if (k.fault_point >= 0) hipLaunchKernelGGL(k_diag_mac_checked<true>, g, b, 0, st, a, k);
-    else hipLaunchKernelGGL(k_diag_mac_checked<false>, g, b, 0, st, a, k);
-    return hipGetLastError();
+    return launch_checked(k_diag_mac_checked<false>, k_diag_mac_checked<true>, k, dim3(checked_grid(total, 16384)), st, a, k);
 }
 
 hipError_t launch_modadd_checked(hipStream_t st, const PointwiseArgs &p, const BcCheck &k)
 {
     const u64 total = (u64)p.units << p.logn;
     if (!total) return hipSuccess;
-    const u64 want = (total + 255) / 256;
-    const dim3 g((u32)(want > 8192 ? 8192 : want)), b(256);
-    if (k.fault_point >= 0) hipLaunchKernelGGL(k_modadd_checked<true>, g, b, 0, st, p, k);
-    else hipLaunchKernelGGL(k_modadd_checked<false>, g, b, 0, st, p, k);
-    return hipGetLastError();
+    return launch_checked(k_modadd_checked<false>, k_modadd_checked<true>, k, dim3(checked_grid(total, 8192)), st, p, k);
 }
 
 } // namespace fhe

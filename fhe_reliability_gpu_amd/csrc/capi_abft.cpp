@@ -417,8 +417,8 @@ static int modmul_checked(fhe_ctx *ctx, u64 *c, const u64 *a, const u64 *b, cons
     int rc = check_range(t, n_poly, limbs, start_idx);
     if (rc) return rc;
     const size_t units = n_poly * limbs;
-    PwCheck k{d_flags, -1, 0, 0};
-    if ((rc = pointwise_fault(ctx->pw_fault.take(), acc, units << t->log_n, k))) return rc;
+    BcCheck k{d_flags, -1, 0, 0, 0};
+    if ((rc = pointwise_fault(ctx->pw_fault.take(), acc, units << t->log_n, t->log_n, k))) return rc;
     if (!units) return FHE_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = pick(ctx, stream);
@@ -448,8 +448,8 @@ int fhe_tensor_product_checked(fhe_ctx *ctx, uint64_t *d_d0, uint64_t *d_d1, uin
     if (!ctx || !d_d0 || !d_d1 || !d_d2 || !d_a0 || !d_a1 || !d_b0 || !d_b1 || !d_flags) return fail(FHE_ERR_INVALID, "null argument");
     int rc = check_range(t, 1, limbs, start_idx);
     if (rc) return rc;
-    PwCheck k{d_flags, -1, 0, 0};
-    if ((rc = pointwise_fault(ctx->pw_fault.take(), true, limbs << t->log_n, k))) return rc;
+    BcCheck k{d_flags, -1, 0, 0, 0};
+    if ((rc = pointwise_fault(ctx->pw_fault.take(), true, limbs << t->log_n, t->log_n, k))) return rc;
     if (!limbs) return FHE_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = pick(ctx, stream);

@@ -58,10 +58,8 @@ int fhe_modadd_checked(fhe_ctx *ctx, uint64_t *c, const uint64_t *a, const uint6
     if (rc) return rc;
     const size_t units = n_poly * limbs;
     if (f.point >= 0 && !modadd_point_exists(f.point)) return fail(FHE_ERR_UNSUPPORTED, "fault points 0 (product) and 1 (quotient) do not exist on an add: 2 is the word, 3 the sum a + b");
-    PwCheck pk{d_flags, -1, 0, 0};
-    if ((rc = pointwise_fault(f, true, units << t->log_n, pk))) return rc;
-    // the add's check record addresses (unit, coefficient)
-    const BcCheck k{d_flags, pk.fault_point, (u32)(pk.fault_idx >> t->log_n), pk.fault_idx & (((u64)1 << t->log_n) - 1), pk.fault_mask};
+    BcCheck k{d_flags, -1, 0, 0, 0};
+    if ((rc = pointwise_fault(f, true, units << t->log_n, t->log_n, k))) return rc;
     if (!units) return FHE_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = pick(ctx, stream);

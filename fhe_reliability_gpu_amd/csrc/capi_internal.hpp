@@ -322,15 +322,16 @@ struct TraceScope {
     }
 };
 
-// the pointwise hook a call of `elems` elements took (ctx->pw_fault.take()), checked against that call; point 3 (the running sum)
-// exists only where the call has one
-inline int pointwise_fault(const PointFault &f, bool has_sum, size_t elems, PwCheck &k)
+// the pointwise hook a call of `elems` elements of 2^log_n-word units took (ctx->pw_fault.take()), checked against that call;
+// point 3 (the running sum) exists only where the call has one.  The hook's element index becomes the record's (unit, coefficient)
+inline int pointwise_fault(const PointFault &f, bool has_sum, size_t elems, int log_n, BcCheck &k)
 {
     if (f.point < 0) return FHE_OK;
     if (f.point == 3 && !has_sum) return fail(FHE_ERR_UNSUPPORTED, "fault point 3 (the running sum) exists only for fhe_modmul_acc_checked and fhe_tensor_product_checked");
     if (f.coeff >= elems) return fail(FHE_ERR_INVALID, "fault index outside the call's window");
     k.fault_point = f.point;
-    k.fault_idx = f.coeff;
+    k.fault_unit = (u32)(f.coeff >> log_n);
+    k.fault_coeff = f.coeff & (((u64)1 << log_n) - 1);
     k.fault_mask = (u64)1 << f.bit;
     return FHE_OK;
 }

@@ -3,19 +3,10 @@
 // translation unit of its own, so that the kernels of aux_kernels.hip compile exactly as before.  Both stream from HBM, one
 // element per lane, same loops and grids as the unchecked kernels; the residue work is 32-bit lane arithmetic beside the 64-bit
 // products; a failing lane ORs its unit's flag word with a global atomic, a clean run stores nothing extra.  No LDS.
-#include "ntt_launch.hpp"
+#include "checked_kernel.hpp"
 #include "keyswitch_check.hpp"
 
 namespace fhe {
-
-// HOOK: the one-shot test fault of fhe_ctx_inject_fault_keyswitch is armed (a separate instantiation, so that the clean
-// kernels carry no compare against the fault's unit and coefficient)
-template <bool HOOK>
-__device__ __forceinline__ PwFault ks_fault_at(const BcCheck &k, u32 unit, u64 coeff)
-{
-    if (!HOOK) return PwFault{-1, 0};
-    return PwFault{k.fault_point, unit == k.fault_unit && coeff == k.fault_coeff ? k.fault_mask : 0};
-}
 
 // the key is read once: non-temporal, so that it does not push the digits (read by both halves' neighbours) out of the caches
 __device__ __forceinline__ u64 ks_load_key(const u64 *p) { return __builtin_nontemporal_load(p); }
@@ -25,7 +16,7 @@ __device__ __forceinline__ void ks_mac_limb_checked(const KsMacArgs &a, const Bc
 {
     const u64 N = (u64)1 << a.logn;
     D s0, s1;
-    const PwFault f0 = ks_fault_at<HOOK>(k, j, i), f1 = ks_fault_at<HOOK>(k, a.M + j, i);
+    const PwFault f0 = fault_at<HOOK>(k, j, i), f1 = fault_at<HOOK>(k, a.M + j, i);
     const u32 tl = j < a.cn ? a.clo + j : 0xFFFFFFFFu;     // table limb when the row is a ciphertext limb
     for (u32 d = 0; d < a.dnum; d++) {
         const u32 lo = d * a.alpha, hi = lo + a.alpha < a.L ? lo + a.alpha : a.L;
@@ -69,7 +60,7 @@ __global__ __launch_bounds__(256) void k_sub_scale_checked(SubScaleArgs p, BcChe
         const u64 q = lp.q;
         u32 fl;
         out[i] = checked_sub_scale(a ? a[i] : 0, a != nullptr, b ? b[i] : 0, b != nullptr, p.scal[l], add ? add[i] : 0, add != nullptr, q, lp.barrett_lo,
-                                   lp.barrett_hi, res64(q), fl, ks_fault_at<HOOK>(k, h * p.limbs + l, i & (((u64)1 << p.logn) - 1)));
+                                   lp.barrett_hi, res64(q), fl, fault_at<HOOK>(k, h * p.limbs + l, i & (((u64)1 << p.logn) - 1)));
         if (fl) atomicOr(k.flags + h * p.limbs + l, fl);
     }
 }
@@ -89,22 +80,14 @@ hipError_t launch_ks_mac_checked(hipStream_t st, const KsMacArgs &a, const BcChe
 {
     const u64 total = (u64)a.M << a.logn;
     if (!total) return hipSuccess;
-    const u64 want = (total + 255) / 256;
-    const dim3 g((u32)(want > 16384 ? 16384 : want)), b(256);
-    if (k.fault_point >= 0) hipLaunchKernelGGL(k_ks_mac_checked<true>, g, b, 0, st, a, k);
-    else hipLaunchKernelGGL(k_ks_mac_checked<false>, g, b, 0, st, a, k);
-    return hipGetLastError();
+    return launch_checked(k_ks_mac_checked<false>, k_ks_mac_checked<true>, k, dim3(checked_grid(total, 16384)), st, a, k);
 }
 
 hipError_t launch_sub_scale_checked(hipStream_t st, const SubScaleArgs &p, const BcCheck &k)
 {
     const u64 total = (u64)p.limbs << p.logn;
     if (!total) return hipSuccess;
-    const u64 want = (total + 255) / 256;
-    const dim3 g((u32)(want > 8192 ? 8192 : want), p.out1 ? 2 : 1), b(256);
-    if (k.fault_point >= 0) hipLaunchKernelGGL(k_sub_scale_checked<true>, g, b, 0, st, p, k);
-    else hipLaunchKernelGGL(k_sub_scale_checked<false>, g, b, 0, st, p, k);
-    return hipGetLastError();
+    return launch_checked(k_sub_scale_checked<false>, k_sub_scale_checked<true>, k, dim3(checked_grid(total, 8192), p.out1 ? 2 : 1), st, p, k);
 }
 
 hipError_t launch_ks_flags_scatter(hipStream_t st, u32 *dst, const u32 *src, const u32 *map, u32 n)

@@ -161,15 +161,10 @@ struct TensorArgs {
 hipError_t launch_tensor(hipStream_t st, const TensorArgs &p);
 // ---- pointwise_checked.hip: the same products with a residue check per word (residue_check.hpp) --------
 // flags: one uint32 per limb-polynomial (modmul) or [limb][3] (tensor), zeroed by the caller; a word that fails ORs in
-// its flag bits.  fault_point >= 0 arms the test hook: XOR fault_mask at that point of element fault_idx of the window
-// ([poly][limb][N] for modmul, [limb][N] and the d1 sum for the tensor product)
-struct PwCheck {
-    u32 *flags;
-    int fault_point;
-    u64 fault_idx, fault_mask;
-};
-hipError_t launch_modmul_checked(hipStream_t st, const PointwiseArgs &p, bool accumulate, const PwCheck &k);
-hipError_t launch_tensor_checked(hipStream_t st, const TensorArgs &p, const PwCheck &k);
+// its flag bits.  The check record BcCheck: fault_hook.hpp; its unit is the limb-polynomial poly * limbs + l (modmul) or the
+// limb, where the fault hits the d1 sum (tensor product)
+hipError_t launch_modmul_checked(hipStream_t st, const PointwiseArgs &p, bool accumulate, const BcCheck &k);
+hipError_t launch_tensor_checked(hipStream_t st, const TensorArgs &p, const BcCheck &k);
 // inner sum of a BSGS matrix-vector product: out_h = sum_b diag[b] * R_b,h per limb (aux_kernels.hip k_diag_mac); diag = [n1][limbs][N],
 // R_0 = (x0, x1), R_b = rot + (b - 1) * 2 * limbs * N ([n1 - 1][2][limbs][N])
 struct DiagMacArgs {

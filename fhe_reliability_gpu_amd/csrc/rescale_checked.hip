@@ -4,19 +4,10 @@
 // loads x once and stores its R residues (consecutive lanes, consecutive words of each limb), the residue work is 32-bit lane
 // arithmetic beside the 64-bit Barrett step, the limb constants are uniform across the wavefront; a failing lane ORs its unit's
 // flag word with a global atomic, a clean run stores nothing extra.  No LDS.
-#include "ntt_launch.hpp"
+#include "checked_kernel.hpp"
 #include "rescale_check.hpp"
 
 namespace fhe {
-
-// HOOK: the one-shot test fault of fhe_ctx_inject_fault_rescale is armed (a separate instantiation, so that the clean kernel
-// carries no compare against the fault's unit and coefficient)
-template <bool HOOK>
-__device__ __forceinline__ PwFault rs_fault_at(const BcCheck &k, u32 unit, u64 coeff)
-{
-    if (!HOOK) return PwFault{-1, 0};
-    return PwFault{k.fault_point, unit == k.fault_unit && coeff == k.fault_coeff ? k.fault_mask : 0};
-}
 
 // k.flags = [n_parts][R] (part, limb)
 template <bool HOOK>
@@ -33,7 +24,7 @@ __global__ __launch_bounds__(256) void k_rescale_reduce_checked(RescaleReduceArg
         for (u32 j = 0; j < a.R; j++) {
             const LimbParams &p = a.lp[j];
             u32 fl;
-            out[(u64)j << a.logn] = checked_reduce_word(x, qlast, p.q, p.barrett_lo, p.barrett_hi, rx, res64(p.q), fl, rs_fault_at<HOOK>(k, part * a.R + j, i));
+            out[(u64)j << a.logn] = checked_reduce_word(x, qlast, p.q, p.barrett_lo, p.barrett_hi, rx, res64(p.q), fl, fault_at<HOOK>(k, part * a.R + j, i));
             if (fl) atomicOr(k.flags + part * a.R + j, fl);
         }
     }
@@ -43,11 +34,7 @@ hipError_t launch_rescale_reduce_checked(hipStream_t st, const RescaleReduceArgs
 {
     const u64 total = (u64)a.n_parts << a.logn;
     if (!total || !a.R) return hipSuccess;
-    const u64 want = (total + 255) / 256;
-    const dim3 g((u32)(want > 16384 ? 16384 : want)), b(256);
-    if (k.fault_point >= 0) hipLaunchKernelGGL(k_rescale_reduce_checked<true>, g, b, 0, st, a, k);
-    else hipLaunchKernelGGL(k_rescale_reduce_checked<false>, g, b, 0, st, a, k);
-    return hipGetLastError();
+    return launch_checked(k_rescale_reduce_checked<false>, k_rescale_reduce_checked<true>, k, dim3(checked_grid(total, 16384)), st, a, k);
 }
 
 } // namespace fhe

@@ -137,6 +137,13 @@ def _read_flags(flags: DeviceArray, n: int, stream=None) -> np.ndarray:
     return flags.download().view(np.uint32)[:n]
 
 
+def _checked_flags(eng: Engine, n: int, call, stream=None) -> np.ndarray:
+    """The ``n`` flag words (uint32, an array of its own) of the checked call ``call(flags)``, which returns the C status."""
+    flags = _flag_buffer(eng, n)
+    check(call(flags))
+    return _read_flags(flags, n, stream).copy()
+
+
 def create_moduli(N: int, bits: Sequence[int]) -> List[int]:
     """``CoeffModulus::Create(N, {bits...})`` (reliability_test/ntt_test.cu:44)."""
     b = (C.c_int * len(bits))(*bits)
@@ -209,10 +216,8 @@ class NttTables:
         element-wise stage of its pipeline, here per word (residue_check.hpp)."""
         limbs = len(self) - start if limbs is None else limbs
         n = n_poly * limbs
-        flags = self.eng.alloc((n + 1) // 2)      # uint32 flags packed in a u64 buffer
         f = lib.fhe_modmul_acc_checked if acc else lib.fhe_modmul_checked
-        check(f(self.eng._h, c.ptr, a.ptr, b.ptr, self._h, n_poly, limbs, start, flags.ptr, stream))
-        return _read_flags(flags, n, stream).copy()
+        return _checked_flags(self.eng, n, lambda fl: f(self.eng._h, c.ptr, a.ptr, b.ptr, self._h, n_poly, limbs, start, fl.ptr, stream), stream)
 
     def modadd_checked(self, c: DeviceArray, a: DeviceArray, b: DeviceArray, limbs=None, start=0, n_poly=1, stream=None) -> np.ndarray:
         """c = (a + b) mod q per limb with every word checked; the words are ``fhe_modadd``'s, bit for bit.  Returns
@@ -220,9 +225,8 @@ class NttTables:
         2 = the word out of its window, 4 = an operand not canonical, which the check cannot cover (bsgs_check.hpp)."""
         limbs = len(self) - start if limbs is None else limbs
         n = n_poly * limbs
-        flags = _flag_buffer(self.eng, n)
-        check(lib.fhe_modadd_checked(self.eng._h, c.ptr, a.ptr, b.ptr, self._h, n_poly, limbs, start, flags.ptr, stream))
-        return _read_flags(flags, n, stream).copy()
+        return _checked_flags(self.eng, n, lambda fl: lib.fhe_modadd_checked(self.eng._h, c.ptr, a.ptr, b.ptr, self._h, n_poly, limbs, start, fl.ptr, stream),
+                              stream)
 
     def polymul(self, c: DeviceArray, a: DeviceArray, b: DeviceArray, limbs=None, start=0, n_poly=1, stream=None):
         limbs = len(self) - start if limbs is None else limbs
@@ -398,16 +402,13 @@ class FourStep:
     def ntt_checked(self, src: DeviceArray, dst: DeviceArray, n_vec: int = 1, stream=None) -> np.ndarray:
         """``ntt`` with the whole-transform check sum u x == sum v y riding on the launches; the words are ``ntt``'s, bit for
         bit.  Returns flags[n_vec] (uint32, 0 / 1)."""
-        flags = _flag_buffer(self.eng, n_vec)
-        check(lib.fhe_fourstep_ntt_checked(self.eng._h, dst.ptr, src.ptr, self._h, n_vec, flags.ptr, stream))
-        return _read_flags(flags, n_vec, stream).copy()
+        return _checked_flags(self.eng, n_vec, lambda fl: lib.fhe_fourstep_ntt_checked(self.eng._h, dst.ptr, src.ptr, self._h, n_vec, fl.ptr, stream), stream)
 
     def ntt_checked_phases(self, src: DeviceArray, dst: DeviceArray, n_vec: int = 1, stream=None) -> np.ndarray:
         """``ntt`` with one check per phase (N >= 2^13): flags[n_vec, 3] = launch 1 (the reference's stage 1), the hand-off
         between the launches, launch 2 (stage 2)."""
-        flags = _flag_buffer(self.eng, 3 * n_vec)
-        check(lib.fhe_fourstep_ntt_checked_phases(self.eng._h, dst.ptr, src.ptr, self._h, n_vec, flags.ptr, stream))
-        return _read_flags(flags, 3 * n_vec, stream).reshape(n_vec, 3).copy()
+        return _checked_flags(self.eng, 3 * n_vec, lambda fl: lib.fhe_fourstep_ntt_checked_phases(self.eng._h, dst.ptr, src.ptr, self._h, n_vec, fl.ptr, stream),
+                              stream).reshape(n_vec, 3)
 
     def close(self):
         if getattr(self, "_h", None) and self.eng._h:
@@ -467,9 +468,7 @@ class BaseConv:
         check(lib.fhe_baseconv_fast(self.eng._h, out.ptr, inp.ptr, self._h, N, stream))
 
     def _checked(self, f, units, out, inp, N, stream):
-        flags = self.eng.alloc((units + 1) // 2)      # uint32 flags packed in a u64 buffer
-        check(f(self.eng._h, out.ptr, inp.ptr, self._h, N, flags.ptr, stream))
-        return _read_flags(flags, units, stream).copy()
+        return _checked_flags(self.eng, units, lambda fl: f(self.eng._h, out.ptr, inp.ptr, self._h, N, fl.ptr, stream), stream)
 
     def exact_checked(self, out: DeviceArray, inp: DeviceArray, N: int, stream=None) -> np.ndarray:
         """``exact`` with every mixed-radix digit and every output word checked; the words are ``exact``'s, bit for bit.
@@ -561,9 +560,7 @@ def automorphism(eng: Engine, t: NttTables, src: DeviceArray, galois_elt: int, n
 
 
 def _permute_checked(eng: Engine, dst: DeviceArray, src: DeviceArray, log_n: int, galois_elt: int, units: int, stream=None) -> np.ndarray:
-    flags = _flag_buffer(eng, units)
-    check(lib.fhe_automorphism_ntt_checked(eng._h, dst.ptr, src.ptr, log_n, galois_elt, units, flags.ptr, stream))
-    return _read_flags(flags, units, stream).copy()
+    return _checked_flags(eng, units, lambda fl: lib.fhe_automorphism_ntt_checked(eng._h, dst.ptr, src.ptr, log_n, galois_elt, units, fl.ptr, stream), stream)
 
 
 def automorphism_checked(eng: Engine, t: NttTables, src: DeviceArray, galois_elt: int, n_poly: int = 1, limbs: Optional[int] = None):
@@ -658,10 +655,9 @@ class KeySwitch:
         the residue identity covers the lazy cross term d1 = a0 b1 + a1 b0 as one sum, the reference's Sum check
         (rfhe_framewk/src/barrett_final.py) and the element-wise fold check of four_step_ntt_protected.py:102-120."""
         d = [self._out(self.L) for _ in range(3)]
-        flags = _flag_buffer(self.eng, 3 * self.L)
-        check(lib.fhe_tensor_product_checked(self.eng._h, d[0].ptr, d[1].ptr, d[2].ptr, a0.ptr, a1.ptr, b0.ptr, b1.ptr, self.t._h, self.L, 0,
-                                             flags.ptr, stream))
-        return d[0], d[1], d[2], _read_flags(flags, 3 * self.L, stream).reshape(self.L, 3).copy()
+        f = _checked_flags(self.eng, 3 * self.L, lambda fl: lib.fhe_tensor_product_checked(
+            self.eng._h, d[0].ptr, d[1].ptr, d[2].ptr, a0.ptr, a1.ptr, b0.ptr, b1.ptr, self.t._h, self.L, 0, fl.ptr, stream), stream)
+        return d[0], d[1], d[2], f.reshape(self.L, 3)
 
     def relinearize(self, d0: DeviceArray, d1: DeviceArray, d2: DeviceArray, relin_key: DeviceArray, stream=None):
         """``relinearize_inplace`` (dotprod_test.cu:114)."""
@@ -688,9 +684,8 @@ class KeySwitch:
     def _checked(self, call, stream):
         lay = self.checked_layout()
         o0, o1 = self._out(self.L), self._out(self.L)
-        flags = _flag_buffer(self.eng, lay["total"])
-        check(call(o0, o1, flags))
-        return o0, o1, self._split_flags(_read_flags(flags, lay["total"], stream), lay, self.CHECKED_STAGES)
+        f = _checked_flags(self.eng, lay["total"], lambda fl: call(o0, o1, fl), stream)
+        return o0, o1, self._split_flags(f, lay, self.CHECKED_STAGES)
 
     def apply_checked(self, c: DeviceArray, evk: DeviceArray, abft: "Abft", add0: Optional[DeviceArray] = None,
                       add1: Optional[DeviceArray] = None, stream=None):
@@ -752,9 +747,9 @@ class KeySwitch:
         a1 = (vp * max(1, n))(*[o[1].ptr for o in outs])
         ks = (vp * max(1, n))(*[k.ptr for k in prepared_keys])
         ge = (C.c_uint32 * max(1, n))(*[int(g) for g in galois_elts])
-        flags = _flag_buffer(self.eng, total)
-        check(lib.fhe_rotate_hoisted_checked(self.eng._h, self._h, a0, a1, c0.ptr, c1.ptr, ge, ks, n, abft._h, flags.ptr, stream))
-        return outs, self._hoisted_flags(_read_flags(flags, total, stream), n)
+        f = _checked_flags(self.eng, total, lambda fl: lib.fhe_rotate_hoisted_checked(self.eng._h, self._h, a0, a1, c0.ptr, c1.ptr, ge, ks, n, abft._h, fl.ptr,
+                                                                                     stream), stream)
+        return outs, self._hoisted_flags(f, n)
 
     def _hoisted_flags(self, f, n_rot, base=0):
         """The flag dictionary of ``n_rot`` checked hoisted rotations whose words start at ``f[base]``."""
@@ -790,10 +785,8 @@ class KeySwitch:
         ge = (C.c_uint32 * max(1, n2 - 1))(*[int(g) for g in giant_elts])
         bk = (vp * max(1, n1 - 1))(*[k.ptr for k in baby_keys_prepared])
         gk = (vp * max(1, n2 - 1))(*[k.ptr for k in giant_keys])
-        flags = _flag_buffer(self.eng, total)
-        check(lib.fhe_bsgs_matvec_checked(self.eng._h, self._h, o0.ptr, o1.ptr, c0.ptr, c1.ptr, diags.ptr, n1, n2, be, bk, ge, gk, abft._h, flags.ptr,
-                                          stream))
-        f = _read_flags(flags, total, stream)
+        f = _checked_flags(self.eng, total, lambda fl: lib.fhe_bsgs_matvec_checked(
+            self.eng._h, self._h, o0.ptr, o1.ptr, c0.ptr, c1.ptr, diags.ptr, n1, n2, be, bk, ge, gk, abft._h, fl.ptr, stream), stream)
         baby = self._hoisted_flags(f, n1 - 1, lay["baby"]) if n1 > 1 else None
         giant = []
         for g in range(n2):
@@ -853,9 +846,8 @@ class KeySwitch:
         total = lay["total"]
         o = self.eng.alloc(n_parts * (self.L - 1) * self.t.N)
         o.shape = (n_parts, self.L - 1, self.t.N)
-        flags = _flag_buffer(self.eng, total)
-        check(lib.fhe_rescale_checked(self.eng._h, self._h, o.ptr, c.ptr, n_parts, abft._h, flags.ptr, stream))
-        return o, self._split_flags(_read_flags(flags, total, stream), lay, self.RESCALE_CHECKED_STAGES)
+        f = _checked_flags(self.eng, total, lambda fl: lib.fhe_rescale_checked(self.eng._h, self._h, o.ptr, c.ptr, n_parts, abft._h, fl.ptr, stream), stream)
+        return o, self._split_flags(f, lay, self.RESCALE_CHECKED_STAGES)
 
     def hmult_checked(self, a0: DeviceArray, a1: DeviceArray, b0: DeviceArray, b1: DeviceArray, relin_key: DeviceArray, abft: "Abft",
                       rescale: bool = True, stream=None):
@@ -866,10 +858,8 @@ class KeySwitch:
         total = lay["total"]
         limbs = self.L - 1 if rescale else self.L
         o0, o1 = self._out(limbs), self._out(limbs)
-        flags = _flag_buffer(self.eng, total)
-        check(lib.fhe_hmult_checked(self.eng._h, self._h, o0.ptr, o1.ptr, a0.ptr, a1.ptr, b0.ptr, b1.ptr, relin_key.ptr, 1 if rescale else 0,
-                                    abft._h, flags.ptr, stream))
-        f = _read_flags(flags, total, stream)
+        f = _checked_flags(self.eng, total, lambda fl: lib.fhe_hmult_checked(
+            self.eng._h, self._h, o0.ptr, o1.ptr, a0.ptr, a1.ptr, b0.ptr, b1.ptr, relin_key.ptr, 1 if rescale else 0, abft._h, fl.ptr, stream), stream)
         out = {"tensor": f[lay["tensor"]:lay["tensor"] + 3 * self.L].reshape(self.L, 3).copy(),
                "keyswitch": self._split_flags(f, self.checked_layout(), self.CHECKED_STAGES, lay["keyswitch"]),
                "rescale": self._split_flags(f, self.rescale_checked_layout(2), self.RESCALE_CHECKED_STAGES, lay["rescale"]) if rescale else None}
@@ -905,17 +895,15 @@ class Abft:
     def forward_checked(self, d: DeviceArray, n_poly: int = 1, limbs: Optional[int] = None, start: int = 0) -> np.ndarray:
         """In-place forward NTT; returns the per-limb-polynomial fault flags."""
         limbs = len(self.t) - start if limbs is None else limbs
-        flags = self.eng.alloc((n_poly * limbs + 1) // 2)      # uint32 flags packed in a u64 buffer
-        check(lib.fhe_ntt_forward_checked(self.eng._h, d.ptr, self.t._h, self._h, n_poly, limbs, start, flags.ptr, None))
-        return flags.download().view(np.uint32)[: n_poly * limbs]
+        return _checked_flags(self.eng, n_poly * limbs, lambda fl: lib.fhe_ntt_forward_checked(self.eng._h, d.ptr, self.t._h, self._h, n_poly, limbs, start, fl.ptr,
+                                                                                               None))
 
     def forward_checked_phases(self, d: DeviceArray, n_poly: int = 1, limbs: Optional[int] = None, start: int = 0) -> np.ndarray:
         """In-place forward NTT with the per-phase detector; returns flags[unit, 3] = (column pass, hand-off, row pass)."""
         limbs = len(self.t) - start if limbs is None else limbs
         n = n_poly * limbs * 3
-        flags = self.eng.alloc((n + 1) // 2)
-        check(lib.fhe_ntt_forward_checked_phases(self.eng._h, d.ptr, self.t._h, self._h, n_poly, limbs, start, flags.ptr, None))
-        return flags.download().view(np.uint32)[:n].reshape(n_poly * limbs, 3)
+        return _checked_flags(self.eng, n, lambda fl: lib.fhe_ntt_forward_checked_phases(self.eng._h, d.ptr, self.t._h, self._h, n_poly, limbs, start, fl.ptr,
+                                                                                         None)).reshape(n_poly * limbs, 3)
 
     def inverse_checked(self, d: DeviceArray, n_poly: int = 1, limbs: Optional[int] = None, start: int = 0) -> np.ndarray:
         """In-place inverse NTT; returns the per-limb-polynomial fault flags.
@@ -924,9 +912,8 @@ class Abft:
         input side weighed with w_hat on the words the first launch loads, the output side with w on the words the last one
         stores -- the check after the closing transform of rfhe_framewk/src/four_step_ntt_protected.py:219-282."""
         limbs = len(self.t) - start if limbs is None else limbs
-        flags = self.eng.alloc((n_poly * limbs + 1) // 2)
-        check(lib.fhe_ntt_inverse_checked(self.eng._h, d.ptr, self.t._h, self._h, n_poly, limbs, start, flags.ptr, None))
-        return flags.download().view(np.uint32)[: n_poly * limbs]
+        return _checked_flags(self.eng, n_poly * limbs, lambda fl: lib.fhe_ntt_inverse_checked(self.eng._h, d.ptr, self.t._h, self._h, n_poly, limbs, start, fl.ptr,
+                                                                                               None))
 
     def polymul_checked(self, c: DeviceArray, a: DeviceArray, b: DeviceArray, n_poly: int = 1, limbs: Optional[int] = None,
                         start: int = 0) -> np.ndarray:
@@ -939,9 +926,8 @@ class Abft:
         product, not from its result."""
         limbs = len(self.t) - start if limbs is None else limbs
         n = n_poly * limbs * 3
-        flags = self.eng.alloc((n + 1) // 2)
-        check(lib.fhe_polymul_checked(self.eng._h, c.ptr, a.ptr, b.ptr, self.t._h, self._h, n_poly, limbs, start, flags.ptr, None))
-        return flags.download().view(np.uint32)[:n].reshape(n_poly * limbs, 3)
+        return _checked_flags(self.eng, n, lambda fl: lib.fhe_polymul_checked(self.eng._h, c.ptr, a.ptr, b.ptr, self.t._h, self._h, n_poly, limbs, start, fl.ptr,
+                                                                              None)).reshape(n_poly * limbs, 3)
 
     def __del__(self):
         try:

@@ -283,6 +283,51 @@ def test_modmul_hook_flags_exactly_the_changed_unit(F, eng, L, acc, bits):
     assert rc == 0 and not _read_flags(flags, polys * limbs).any() and (dc.download().ravel() == clean).all()
 
 
+@pytest.mark.parametrize("acc", [False, True])
+@pytest.mark.parametrize("elem", ["last of the last unit", "a lane's second word"])
+def test_modmul_hook_addresses_unit_and_coefficient_at_the_smallest_shape(F, eng, L, acc, elem):
+    # N = 2: one lane holds a whole unit, so the hook's element index has to split into (unit, coefficient) exactly; the window
+    # starts at limb 1 of the tables, so a unit is not a table limb either
+    logn, N = 1, 2
+    qs = F.create_moduli(N, [50, 61, 50])
+    t = eng.tables(logn, qs)
+    start, limbs, polys = 1, 2, 2
+    w = qs[start:start + limbs]
+    rng = np.random.default_rng(41 + acc)
+    a, b, o = (_rand(rng, w, polys, N) for _ in range(3))
+    da, db = eng.upload(a), eng.upload(b)
+    clean = _ref_modmul(a, b, o, w, acc).ravel()
+    idx = polys * limbs * N - 1 if elem == "last of the last unit" else 1
+    unit = idx // N
+    dc = eng.upload(o)
+    _arm(L, 2, idx, 0)                                       # the word itself, lowest bit: it always changes
+    rc, flags = _modmul_checked(eng, L, t, dc, da, db, polys, limbs, start, acc)
+    assert rc == 0
+    got = dc.download().ravel()
+    assert np.nonzero(got != clean)[0].tolist() == [idx] and int(got[idx]) == int(clean[idx]) ^ 1
+    f = _read_flags(flags, polys * limbs)
+    assert f[unit] and not (f[unit] & OPERAND) and not np.delete(f, unit).any()
+
+
+@pytest.mark.parametrize("bits", [[50, 61], [61, 50]])
+def test_tensor_hook_addresses_limb_and_coefficient_at_the_smallest_shape(F, eng, L, bits):
+    logn, N, limbs = 1, 2, 2
+    qs = F.create_moduli(N, bits)
+    t = eng.tables(logn, qs)
+    rng = np.random.default_rng(sum(bits) + bits[0])
+    ops = [eng.upload(np.stack([rng.integers(0, q, N, dtype=np.uint64) for q in qs])) for _ in range(4)]
+    rc, clean, flags = _tensor_checked(eng, L, t, limbs, 0, ops)
+    assert rc == 0 and not _read_flags(flags, 3 * limbs).any()
+    idx = limbs * N - 1                                      # the last element: limb 1, coefficient 1
+    _arm(L, 2, idx, 0)
+    rc, got, flags = _tensor_checked(eng, L, t, limbs, 0, ops)
+    assert rc == 0
+    assert (got[0] == clean[0]).all() and (got[2] == clean[2]).all()
+    assert np.nonzero(got[1].ravel() != clean[1].ravel())[0].tolist() == [idx] and int(got[1][1, 1]) == int(clean[1][1, 1]) ^ 1
+    f = _read_flags(flags, 3 * limbs).reshape(limbs, 3)
+    assert f[1, 1] and not np.delete(f.ravel(), 3 * 1 + 1).any()
+
+
 def test_modmul_hook_point_3_needs_a_running_sum(F, eng, L):
     logn, N = 8, 1 << 8
     qs = F.create_moduli(N, [50])
