@@ -175,6 +175,32 @@ def nwt_inverse(a, q: int, rp) -> np.ndarray:
     return a
 
 
+def nwt_forward_stage(a, s: int, q: int, rp) -> np.ndarray:
+    """Stage ``s`` alone of the network nwt_forward runs (2^s blocks, pairs t = N >> (s + 1) apart, factor rp[2^s + block]):
+    (U, V) -> (U + V S, U - V S), canonical residues in and out."""
+    a, rp = _a(a), _a(rp)
+    N = a.size
+    m, t = 1 << s, N >> (s + 1)
+    v = a.reshape(m, 2, t)
+    V = modmul(v[:, 1, :].ravel(), np.repeat(rp[m:2 * m], t), q).reshape(m, t)
+    U = v[:, 0, :]
+    Q = np.uint64(q)
+    return np.stack([(U + V) % Q, (U + Q - V) % Q], axis=1).reshape(N)
+
+
+def nwt_inverse_stage(a, s: int, q: int, rp_inv) -> np.ndarray:
+    """The Gentleman-Sande step that undoes forward stage ``s`` up to a factor 2: (X, Y) -> (X + Y, (X - Y) S^-1) with
+    ``rp_inv`` the table of inverse factors (root_powers of psi^-1).  nwt_inverse is these for s = logN - 1 .. 0, times N^-1."""
+    a, rp_inv = _a(a), _a(rp_inv)
+    N = a.size
+    m, t = 1 << s, N >> (s + 1)
+    v = a.reshape(m, 2, t)
+    Q = np.uint64(q)
+    X, Y = v[:, 0, :], v[:, 1, :]
+    D = modmul(((X + Q - Y) % Q).ravel(), np.repeat(rp_inv[m:2 * m], t), q).reshape(m, t)
+    return np.stack([(X + Y) % Q, D], axis=1).reshape(N)
+
+
 def nwt_forward_batch(a, qs, rps) -> np.ndarray:
     """a: (L, N); qs: L moduli; rps: (L, N) tables."""
     a = _a(a).copy()

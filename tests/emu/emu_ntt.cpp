@@ -11,14 +11,64 @@
 
 #include <array>
 #include <cmath>
+#include <utility>
 #include <vector>
 
 using namespace fhe;
 
 namespace {
 
-// largest |value| (in units of q) any FP64 register held, to validate the lazy schedule
-double g_max_ratio = 0.0;
+// Largest |value| (units of q) any FP64 register held where the arithmetic reads or produces it, and the largest pair sum
+// |X| + |Y| an inverse butterfly was given: the lazy schedule keeps both at or below 8 (q < 2^50: exact integers below 2^53).
+double g_max_ratio = 0.0, g_max_pair = 0.0;
+
+// ArithF64 with every operand watched.  It delegates to ArithF64 unchanged, so the words are the kernels' words; what it adds is
+// the view of the registers BEFORE a butterfly, a product or a fold, which no LDS image after a pass can give.
+struct TrackF64 : ArithF64 {
+    static void see(double x, const Ctx &c)
+    {
+        const double r = std::fabs(x) / c.n;
+        if (!(r <= g_max_ratio)) g_max_ratio = r;          // (a NaN sticks)
+    }
+    static void see_pair(double x, double y, const Ctx &c)
+    {
+        const double r = (std::fabs(x) + std::fabs(y)) / c.n;
+        if (!(r <= g_max_pair)) g_max_pair = r;
+    }
+    static void reduce(elem &x, const Ctx &c)
+    {
+        see(x, c);
+        ArithF64::reduce(x, c);
+    }
+    static u64 canonical(elem x, const Ctx &c)
+    {
+        see(x, c);
+        return ArithF64::canonical(x, c);
+    }
+    static elem mulmod(elem a, const Tw &t, const Ctx &c)
+    {
+        see(a, c);
+        return ArithF64::mulmod(a, t, c);
+    }
+    static void bfly_fwd(elem &X, elem &Y, const Tw &t, const Ctx &c)
+    {
+        see(X, c), see(Y, c);
+        ArithF64::bfly_fwd(X, Y, t, c);
+        see(X, c), see(Y, c);
+    }
+    static void bfly_inv(elem &X, elem &Y, const Tw &t, const Ctx &c)
+    {
+        see(X, c), see(Y, c), see_pair(X, Y, c);
+        ArithF64::bfly_inv(X, Y, t, c);
+        see(X, c), see(Y, c);
+    }
+    static void bfly_inv_scaled(elem &X, elem &Y, const Tw &n, const Tw &wn, const Ctx &c)
+    {
+        see(X, c), see(Y, c), see_pair(X, Y, c);
+        ArithF64::bfly_inv_scaled(X, Y, n, wn, c);
+        see(X, c), see(Y, c);
+    }
+};
 
 template <class PASS, int LOGN, bool INV, bool IS_COL>
 void emu_pass(const PassArgs &a)
@@ -43,12 +93,6 @@ void emu_pass(const PassArgs &a)
             for (int tid = 0; tid < PASS::THREADS; tid++) PASS::template phase<3>(tid, base, lds.data(), tw, row0, ctx, p.inv_n);
         if constexpr (PASS::NPHASE > 4)
             for (int tid = 0; tid < PASS::THREADS; tid++) PASS::template phase<4>(tid, base, lds.data(), tw, row0, ctx, p.inv_n);
-        if constexpr (A::PATH == PATH_F64 && false) {
-            for (auto v : lds) {
-                double r = std::fabs((double)v) / p.n;
-                if (r > g_max_ratio) g_max_ratio = r;
-            }
-        }
     }
 }
 
@@ -276,23 +320,25 @@ extern "C" int emu_ntt(u64 *data, int logn, int inverse, int n_poly, int limbs, 
         for (int u = n_poly * limbs - 1; u >= 0; u--) map.push_back(UnitRef{(u32)u, (u32)(u % limbs)});
         a.map = map.data();
     }
-    g_max_ratio = 0.0;
+    g_max_ratio = g_max_pair = 0.0;      // the maxima are per call
     if (fused_dist == -3) {          // forward transform with the packed hand-off (2^16, FP64 path)
-        if (logn == 16 && path == PATH_F64 && !inverse) return emu_packed<ArithF64, 16>(a);
+        if (logn == 16 && path == PATH_F64 && !inverse) return emu_packed<TrackF64, 16>(a);
         return -1;
     }
     if (fused_dist == -2) {          // resident pass
-        if (logn == 13) return path == PATH_F64 ? emu_resident<ArithF64, 13>(a, inverse) : emu_resident<ArithU64, 13>(a, inverse);
-        if (logn == 14) return path == PATH_F64 ? emu_resident<ArithF64, 14>(a, inverse) : emu_resident<ArithU64, 14>(a, inverse);
+        if (logn == 13) return path == PATH_F64 ? emu_resident<TrackF64, 13>(a, inverse) : emu_resident<ArithU64, 13>(a, inverse);
+        if (logn == 14) return path == PATH_F64 ? emu_resident<TrackF64, 14>(a, inverse) : emu_resident<ArithU64, 14>(a, inverse);
         return -1;
     }
     if (fused_dist > 0)
-        return path == PATH_F64 ? emu_fused_size<ArithF64>(a, logn, inverse, (u32)fused_dist)
+        return path == PATH_F64 ? emu_fused_size<TrackF64>(a, logn, inverse, (u32)fused_dist)
                                 : emu_fused_size<ArithU64>(a, logn, inverse, (u32)fused_dist);
-    return path == PATH_F64 ? emu_size<ArithF64>(a, logn, inverse) : emu_size<ArithU64>(a, logn, inverse);
+    return path == PATH_F64 ? emu_size<TrackF64>(a, logn, inverse) : emu_size<ArithU64>(a, logn, inverse);
 }
 
+// maxima of the last emu_ntt call (path 0; the integer path leaves them 0): register values, and inverse pair sums
 extern "C" double emu_max_ratio() { return g_max_ratio; }
+extern "C" double emu_max_pair() { return g_max_pair; }
 
 // the per-register lazy-range plan of K inverse stages (ntt_core.hpp inv_lazy_plan), as the kernels' templates evaluate it
 template <int K> static void dump_plan(int in8, int exit8, int fold, uint32_t *before, uint32_t *at_exit, int *out8)
@@ -320,4 +366,126 @@ extern "C" int emu_inv_lazy_chain(int k0, int k1, int k2, int in8, int se)
     if (k0 == 4 && k1 == 4) return inv_lazy_step_in8<Steps<4, 4, 0>>(in8, se);
     if (k0 == 4 && k1 == 3) return inv_lazy_step_in8<Steps<4, 3, 0>>(in8, se);
     return -1;
+}
+
+// ---------------------------------------------------------------------------
+// The fold schedule of every pass as its template arguments fix it, for the exact-fraction walks of tests/test_ntt_worst_case.py.
+// A pass writes 6 ints { kind (0 row, 1 column), steps, input mode, output mode, lazy inverse plan?, its declared entry bound in
+// eighths of q } and then 5 ints per register step in execution order { K, fold mask of its K stages (bit v = before executed
+// stage v; -1 under the per-register plan), entry bound and exit bound in eighths of q (per-register plan), N^-1 folded into
+// the last stage? }.  The step formulas are those of ColPass::phase / RowPass::phase.
+// ---------------------------------------------------------------------------
+namespace {
+
+struct SchedOut {
+    int *out, cap, n;
+    void put(int v)
+    {
+        if (n < cap) out[n] = v;
+        n++;
+    }
+};
+
+template <class A, class ST, int S0, bool INV, int IN_MODE, int OUT_MODE, u32 RED, int... SE>
+void sched_steps(SchedOut &o, int kind, int in_mode, int out_mode, std::integer_sequence<int, SE...>)
+{
+    constexpr bool LAZY = INV && (RED & INV_LAZY) != 0 && A::PATH == PATH_F64;
+    o.put(kind), o.put(ST::NSTEP), o.put(in_mode), o.put(out_mode), o.put(LAZY), o.put(LAZY ? (int)(RED & 0xFFu) : 0);
+    auto step = [&](auto se_c) {
+        constexpr int E = decltype(se_c)::value;
+        constexpr int F = INV ? ST::NSTEP - 1 - E : E, K = ST::k(F), DONE = ST::done(F);
+        constexpr int U0 = INV ? (ST::P - DONE - K) : DONE;
+        constexpr bool LAST = E == ST::NSTEP - 1;
+        constexpr bool FOLD = INV && LAST && OUT_MODE == IO_CANONICAL && S0 + DONE == 0;
+        o.put(K);
+        o.put(LAZY ? -1 : (int)((RED >> U0) & ((1u << K) - 1u)));
+        o.put(LAZY ? inv_lazy_step_in8<ST>((int)(RED & 0xFFu), E) : 0);
+        o.put(LAZY ? ((LAST && OUT_MODE == IO_CANONICAL) ? INV_LAZY_LIMIT8 : INV_LAZY_EXIT8) : 0);
+        o.put(FOLD);
+    };
+    (step(std::integral_constant<int, SE>{}), ...);
+}
+
+template <class T> struct PassInfo;
+template <class A, class ST, int LOGN, int TR, int NT, bool INV, int IN_MODE, int OUT_MODE, u32 RED, int SBLK, int CO, bool STREAM, bool SBOTH, int RM>
+struct PassInfo<RowPass<A, ST, LOGN, TR, NT, INV, IN_MODE, OUT_MODE, RED, SBLK, CO, STREAM, SBOTH, RM>> {
+    static void dump(SchedOut &o, int in_mode = IN_MODE, int out_mode = OUT_MODE)
+    {
+        sched_steps<A, ST, LOGN - ST::P, INV, IN_MODE, OUT_MODE, RED>(o, 0, in_mode, out_mode, std::make_integer_sequence<int, ST::NSTEP>{});
+    }
+};
+template <class A, class ST, int LOGN, int S0, int TC, int NT, bool INV, int IN_MODE, int OUT_MODE, u32 RED, int SBLK, int CO, bool STREAM>
+struct PassInfo<ColPass<A, ST, LOGN, S0, TC, NT, INV, IN_MODE, OUT_MODE, RED, SBLK, CO, STREAM>> {
+    static void dump(SchedOut &o, int in_mode = IN_MODE, int out_mode = OUT_MODE)
+    {
+        sched_steps<A, ST, S0, INV, IN_MODE, OUT_MODE, RED>(o, 1, in_mode, out_mode, std::make_integer_sequence<int, ST::NSTEP>{});
+    }
+};
+
+// form 0: Passes (both launches), 1: FusedPasses, 2: ResidentPass, 3: MidPasses (forward row pass, then inverse row pass),
+// 4: Passes forward with the packed hand-off (canonical residues between the launches)
+template <int LOGN, bool INV> int sched_form(SchedOut &o, int form)
+{
+    typedef ArithF64 A;
+    constexpr int GEO = LOGN >= 13 ? 1 : 0;
+    typedef Passes<A, LOGN, INV, GEO> PS;
+    if (form == 0) {
+        if constexpr (!PS::G::TWO_PASS) PassInfo<typename PS::Single>::dump(o);
+        else if constexpr (!INV) PassInfo<typename PS::Col>::dump(o), PassInfo<typename PS::Row>::dump(o);
+        else PassInfo<typename PS::Row>::dump(o), PassInfo<typename PS::Col>::dump(o);
+        return 0;
+    }
+    if (form == 1) {
+        if constexpr (LOGN >= 13 && LOGN <= 17) {
+            typedef FusedPasses<A, LOGN, INV> FP;
+            if constexpr (!INV) PassInfo<typename FP::Col>::dump(o), PassInfo<typename FP::Row>::dump(o);
+            else PassInfo<typename FP::Row>::dump(o), PassInfo<typename FP::Col>::dump(o);
+            return 0;
+        }
+        return -1;
+    }
+    if (form == 2) {
+        if constexpr (ResidentPlan<LOGN>::OK) {
+            PassInfo<typename ResidentPass<A, LOGN, INV>::Pass>::dump(o);
+            return 0;
+        }
+        return -1;
+    }
+    if (form == 3) {
+        typedef MidPasses<A, LOGN, GEO> MP;
+        if constexpr (!INV) PassInfo<typename MP::Fwd>::dump(o);
+        else PassInfo<typename MP::Inv>::dump(o);
+        return 0;
+    }
+    if (form == 4) {
+        if constexpr (LOGN == 16 && !INV) {
+            PassInfo<typename PS::Col>::dump(o, IO_CANONICAL, IO_CANONICAL);
+            PassInfo<typename PS::Row>::dump(o, IO_CANONICAL, IO_CANONICAL);
+            return 0;
+        }
+        return -1;
+    }
+    return -1;
+}
+
+} // namespace
+
+// returns the number of ints the schedule takes (written up to cap), or a negative value where the form does not exist at that size
+extern "C" int emu_fold_schedule(int form, int logn, int inverse, int *out, int cap)
+{
+    SchedOut o{out, cap, 0};
+    int rc = -1;
+    switch (logn) {
+#define CASE(L) case L: rc = inverse ? sched_form<L, true>(o, form) : sched_form<L, false>(o, form); break;
+        CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10)
+        CASE(11) CASE(12) CASE(13) CASE(14) CASE(15) CASE(16) CASE(17) CASE(18) CASE(19) CASE(20)
+#undef CASE
+    default: break;
+    }
+    return rc < 0 ? rc : o.n;
+}
+// the stage budgets the masks above were built from
+extern "C" void emu_f64_budgets(int *b)
+{
+    b[0] = ArithF64::FWD_FIRST, b[1] = ArithF64::FWD_NEXT, b[2] = ArithF64::INV_FIRST, b[3] = ArithF64::INV_NEXT;
 }
