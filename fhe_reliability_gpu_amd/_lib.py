@@ -154,7 +154,18 @@ _SIG = {
     "fhe_modadd_checked": (ci, [vp, vp, vp, vp, vp, sz, sz, sz, vp, vp]),
     "fhe_modsub": (ci, [vp, vp, vp, vp, vp, sz, sz, sz, vp]),
     "fhe_scalar_affine": (ci, [vp, vp, vp, p64, p64, vp, sz, sz, sz, vp]),
+    "fhe_scalar_affine_checked": (ci, [vp, vp, vp, p64, p64, vp, sz, sz, sz, vp, vp]),
     "fhe_keyswitch_set_plain_modulus": (ci, [vp, u64]),
+    "fhe_bgv_keyswitch_checked_layout": (ci, [vp, C.POINTER(ci)]),
+    "fhe_bgv_keyswitch_apply_checked": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "fhe_bgv_relinearize_checked": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "fhe_bgv_rotate_checked": (ci, [vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp]),
+    "fhe_ctx_inject_fault_bgv_keyswitch": (ci, [vp, ci, ci, ci, C.c_longlong, ci]),
+    "fhe_bgv_mod_switch_checked_layout": (ci, [vp, sz, C.POINTER(ci)]),
+    "fhe_bgv_mod_switch_checked": (ci, [vp, vp, vp, vp, sz, vp, vp, vp]),
+    "fhe_ctx_inject_fault_bgv_mod_switch": (ci, [vp, ci, ci, ci, C.c_longlong, ci]),
+    "fhe_bgv_hmult_checked_layout": (ci, [vp, ci, C.POINTER(ci)]),
+    "fhe_bgv_hmult_checked": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp]),
     "fhe_ctx_trace": (ci, [vp, ci]),
     "fhe_ctx_trace_read": (ci, [vp, C.c_char_p, sz, C.POINTER(sz)]),
 }

@@ -1,6 +1,7 @@
 // capi_checked.hpp -- what the stage-by-stage checked composites share (capi_keyswitch_checked.cpp: key switch, relinearisation,
 // rotation; capi_hmult_checked.cpp: rescale, homomorphic multiply; capi_rotate_hoisted_checked.cpp: the Galois permutation and
-// hoisted rotations; capi_bsgs_checked.cpp: the BSGS matrix-vector product and the checked add): the flag layout of the key switch,
+// hoisted rotations; capi_bsgs_checked.cpp: the BSGS matrix-vector product and the checked add; capi_bgv_checked.cpp: the BGV forms
+// of key switch, mod switch and multiply, and the checked scalar multiply): the flag layout of the key switch,
 // the checked-transform helper over the plan's scratch sums, and the checked key switch itself, whole and as its two halves.  The
 // one-shot fault records are those of fault_hook.hpp.
 #pragma once
@@ -82,8 +83,9 @@ struct KscNtt {
 int ksc_prepare(fhe_keyswitch *p);
 // the checked transforms of one direction; the detector's partial sums live in the plan (ksc_prepare): the fhe_abft is only read
 KscNtt ksc_ntt(const fhe_keyswitch *p, const fhe_abft *a, hipStream_t st, bool inverse);
-// scope of every stage-by-stage checked call: the plan, the detector and the context's transform variants
-int ksc_scope(const fhe_ctx *ctx, const fhe_keyswitch *p, const fhe_abft *a, const uint32_t *d_flags);
+// scope of every stage-by-stage checked call: the plan, the detector and the context's transform variants.  bgv: the scope of the
+// BGV calls -- the same rules, but the plan must HAVE a plain modulus (FHE_ERR_INVALID without one)
+int ksc_scope(const fhe_ctx *ctx, const fhe_keyswitch *p, const fhe_abft *a, const uint32_t *d_flags, bool bgv = false);
 int keyswitch_checked(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk, const uint64_t *d_add0,
                       const uint64_t *d_add1, const fhe_abft *a, uint32_t *d_flags, hipStream_t st, const StagedFault &ft);
 
@@ -108,9 +110,37 @@ struct KscPerm {
     u64 *acc_to, *c0_to;
     GaloisFault fault;       // unit = half * M + row for the sums, 2 M + l for c0
 };
+// the BGV hand-over of ksc_back and rescale_checked (plans with a plain modulus t): where the flag words of the two word-wise scalar
+// stages go -- `inv`: times t^-1 on the limbs about to be converted, in coefficient form (key switch stage 9 [2][K], mod switch stage
+// 4 [n_parts]); `mul`: times t on the converted limbs (stage 10 [2][L], stage 5 [n_parts][L - 1]) -- and their fault: f.stage = 0
+// addresses `inv`, 1 `mul`, < 0 none (the caller has checked unit, coefficient and point).  Without
+// a hand-over (nullptr) both functions launch exactly the CKKS-form list.
+struct BgvStages {
+    u32 *inv, *mul;
+    StagedFault f;
+};
 int ksc_front(fhe_keyswitch *p, const uint64_t *d_c, const fhe_abft *a, const KscFlags &fl, hipStream_t st, const KscHook &h);
 int ksc_back(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk, const uint64_t *d_add0,
-             const uint64_t *d_add1, const fhe_abft *a, const KscFlags &fl, hipStream_t st, const KscHook &h, const KscPerm *perm);
+             const uint64_t *d_add1, const fhe_abft *a, const KscFlags &fl, hipStream_t st, const KscHook &h, const KscPerm *perm,
+             const BgvStages *bgv = nullptr);
+
+// defined in capi_bgv_checked.cpp
+// one scalar stage: `limbs` rows from data on, of n_poly polynomials poly_stride rows apart (row l of polynomial i at data + (i
+// poly_stride + l) N), times scal[l] mod q_(limb0 + l), in place (launch_scalar_affine_checked); flags [n_poly][limbs]
+int bgv_scalar_stage(const fhe_keyswitch *p, hipStream_t st, u64 *data, const u64 *scal, u32 limb0, u32 limbs, u32 n_poly, u32 poly_stride, u32 *flags,
+                     const StagedFault &f);
+
+// defined in capi_hmult_checked.cpp
+struct RscLayout {
+    int off[4], total;
+};
+RscLayout rsc_layout(const fhe_keyswitch *p, size_t n_parts);
+// the rescale's fault checked against the plan and the number of parts; *flip = the word a transform stage flips
+int rsc_hook(const fhe_keyswitch *p, const StagedFault &ft, size_t n_parts, u64 **flip);
+// d_in = [n_parts][L][N], outs[i] = [L - 1][N]; the caller has checked scope, arguments and overlap.  Clears the lay.total words
+// of stages 0-3 at d_flags and, with a hand-over, the scalar stages' words ([n_parts], [n_parts][L - 1])
+int rescale_checked(fhe_keyswitch *p, uint64_t *const *outs, const uint64_t *d_in, size_t n_parts, const fhe_abft *a, uint32_t *d_flags, hipStream_t st,
+                    const StagedFault &ft, const BgvStages *bgv = nullptr);
 
 // defined in capi_rotate_hoisted_checked.cpp
 // the checked permutation of up to two row ranges that share one flags array (units counted through the segments in order, the

@@ -14,20 +14,40 @@
 #include "keyswitch_check.hpp"
 #include "rescale_check.hpp"
 
-namespace {
-
-struct RscLayout {
-    int off[4], total;
-};
 RscLayout rsc_layout(const fhe_keyswitch *p, size_t n_parts)
 {
     const int n = (int)n_parts, R = p->L - 1;
     return RscLayout{{0, n, n + n * R, n + 2 * n * R}, n + 3 * n * R};
 }
 
-// d_in = [n_parts][L][N], outs[i] = [L - 1][N]; the caller has checked scope, arguments and overlap
+// the test hook of one checked rescale, checked against the call before anything is launched; *flip = the word a transform stage
+// flips between its two launches
+int rsc_hook(const fhe_keyswitch *p, const StagedFault &ft, size_t n_parts, u64 **flip)
+{
+    const RscLayout lay = rsc_layout(p, n_parts);
+    const int logn = p->log_n;
+    const size_t N = (size_t)1 << logn;
+    *flip = nullptr;
+    if (ft.stage >= 0) {
+        const int units = (ft.stage == 3 ? lay.total : lay.off[ft.stage + 1]) - lay.off[ft.stage];
+        if (ft.unit >= units || (size_t)ft.coeff >= N) return fail(FHE_ERR_INVALID, "fault unit or coefficient outside the call");
+        if (!(ft.stage & 1)) {
+            if (logn < 13) return fail(FHE_ERR_UNSUPPORTED, "the transform stages' fault point lies between their two launches: two-launch sizes only (N >= 2^13)");
+            *flip = (ft.stage == 0 ? p->rs_bc : p->rs_delta.as<u64>()) + (size_t)ft.unit * N + ft.coeff;
+        } else {
+            if (ft.stage == 1 && !rescale_reduce_point_exists(ft.point))
+                return fail(FHE_ERR_UNSUPPORTED, "fault point 3 (the running sum) does not exist on the rescale's residues: x mod q_j has no sum");
+            if (ft.stage == 3 && !ks_tail_point_exists(ft.point, false))
+                return fail(FHE_ERR_UNSUPPORTED, "fault point 3 (the running sum) of the tail exists only with an addend, and the rescale has none");
+        }
+    }
+    return FHE_OK;
+}
+
+// bgv (plans with a plain modulus t): the last limbs times t^-1 mod q_last between stages 0 and 1, the residues times t mod q_j
+// between stages 1 and 2, so that the part the switch removes is t [c t^-1]_{q_last}
 int rescale_checked(fhe_keyswitch *p, uint64_t *const *outs, const uint64_t *d_in, size_t n_parts, const fhe_abft *a, uint32_t *d_flags, hipStream_t st,
-                    const StagedFault &ft)
+                    const StagedFault &ft, const BgvStages *bgv)
 {
     const fhe_ntt_tables *t = p->t;
     const int L = p->L, R = L - 1, logn = p->log_n;
@@ -40,22 +60,14 @@ int rescale_checked(fhe_keyswitch *p, uint64_t *const *outs, const uint64_t *d_i
     if ((rc = ksc_prepare(p))) return rc;
 
     // ---- the test hook, checked against this call before anything is launched
-    u64 *flip = nullptr;
-    if (ft.stage >= 0) {
-        const int units = (ft.stage == 3 ? lay.total : lay.off[ft.stage + 1]) - lay.off[ft.stage];
-        if (ft.unit >= units || (size_t)ft.coeff >= N) return fail(FHE_ERR_INVALID, "fault unit or coefficient outside the call");
-        if (!(ft.stage & 1)) {
-            if (logn < 13) return fail(FHE_ERR_UNSUPPORTED, "the transform stages' fault point lies between their two launches: two-launch sizes only (N >= 2^13)");
-            flip = (ft.stage == 0 ? x : delta) + (size_t)ft.unit * N + ft.coeff;
-        } else {
-            if (ft.stage == 1 && !rescale_reduce_point_exists(ft.point))
-                return fail(FHE_ERR_UNSUPPORTED, "fault point 3 (the running sum) does not exist on the rescale's residues: x mod q_j has no sum");
-            if (ft.stage == 3 && !ks_tail_point_exists(ft.point, false))
-                return fail(FHE_ERR_UNSUPPORTED, "fault point 3 (the running sum) of the tail exists only with an addend, and the rescale has none");
-        }
-    }
+    u64 *flip;
+    if ((rc = rsc_hook(p, ft, n_parts, &flip))) return rc;
 
     HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)lay.total * sizeof(u32), st));
+    if (bgv) {
+        HIP_TRY(hipMemsetAsync(bgv->inv, 0, n_parts * sizeof(u32), st));
+        HIP_TRY(hipMemsetAsync(bgv->mul, 0, n_parts * R * sizeof(u32), st));
+    }
     const KscNtt fwd = ksc_ntt(p, a, st, false), inv = ksc_ntt(p, a, st, true);
 
     // ---- 0: INTT of the last limbs
@@ -63,9 +75,15 @@ int rescale_checked(fhe_keyswitch *p, uint64_t *const *outs, const uint64_t *d_i
     if ((rc = inv.run({KscRows{x, 0, (u32)R, 1, (u32)n_parts, 1, 0}}, ft.stage == 0 ? flip : nullptr, ft.bit))) return rc;
     if ((rc = inv.compare(d_flags + lay.off[0], 0, (u32)R, 1, (u32)n_parts))) return rc;
 
+    // ---- BGV: last limbs times t^-1
+    if (bgv && (rc = bgv_scalar_stage(p, st, x, &p->t_inv_qlast, (u32)R, 1, (u32)n_parts, 1, bgv->inv, bgv->f.at(0, 0)))) return rc;
+
     // ---- 1: residues modulo the remaining primes
     const RescaleReduceArgs ra{delta, x, lp, (u32)R, (u32)n_parts, logn};
     if ((e = launch_rescale_reduce_checked(st, ra, bc_check(ft.at(0, 1), d_flags + lay.off[1]))) != hipSuccess) return hip_fail(e, "launch_rescale_reduce_checked");
+
+    // ---- BGV: residues times t
+    if (bgv && (rc = bgv_scalar_stage(p, st, delta, p->t_mod_Q.data(), 0, (u32)R, (u32)n_parts, (u32)R, bgv->mul, bgv->f.at(0, 1)))) return rc;
 
     // ---- 2: forward transform of the residues
     if ((rc = fwd.run({KscRows{delta, 0, 0, (u32)R, (u32)n_parts, (u32)R, 0}}, ft.stage == 2 ? flip : nullptr, ft.bit))) return rc;
@@ -82,6 +100,8 @@ int rescale_checked(fhe_keyswitch *p, uint64_t *const *outs, const uint64_t *d_i
     }
     return FHE_OK;
 }
+
+namespace {
 
 int rsc_scope(const fhe_ctx *ctx, const fhe_keyswitch *p, const fhe_abft *a, const uint32_t *d_flags)
 {

@@ -112,9 +112,10 @@ struct fhe_ctx {
     u32 pfault_block = 0, pfault_word = 0;      // (fhe_ctx_inject_fault_in_pass): workgroup and LDS word
     // one-shot test hooks of the checked calls (fault_hook.hpp), one per setter: the polynomial product (fhe_ctx_inject_fault_polymul),
     // the pointwise calls (_pointwise), the base conversions (_baseconv) and the Galois permutation (_galois); the key switch
-    // (_keyswitch), the rescale (_rescale), the hoisted rotations (_rotate_hoisted) and the BSGS product (_bsgs)
+    // (_keyswitch), the rescale (_rescale), the hoisted rotations (_rotate_hoisted), the BSGS product (_bsgs) and the BGV key switch
+    // and mod switch (_bgv_keyswitch, _bgv_mod_switch)
     PointHook pm_fault, pw_fault, bc_fault, gal_fault;
-    StagedFault ksc_fault, rsc_fault, hrc_fault, bsgs_fault;
+    StagedFault ksc_fault, rsc_fault, hrc_fault, bsgs_fault, bgv_ksc_fault, bgv_rsc_fault;
     DevBuf gal_sums;       // checked Galois permutation: the units' source-side and destination-side sums, [2][units] (grown on demand)
     int geo = 1;           // column-tile geometry of the two-launch path (ntt_launch.hpp)
     bool resident = false; // 2^13 / 2^14: one LDS-resident pass instead of two launches (opt-in, see ntt_plan.hpp)

@@ -158,9 +158,12 @@ int ksc_front(fhe_keyswitch *p, const uint64_t *d_c, const fhe_abft *a, const Ks
 }
 
 // stages 3-7 on the digits ksc_front left in the plan.  perm (hoisted rotations): between stages 3 and 4 the sums and perm->c0 go
-// through the checked Galois permutation (stage 8, flags fl.s[8]); stages 4-7 then run on the permuted sums with sigma(c0) as d_add0
+// through the checked Galois permutation (stage 8, flags fl.s[8]); stages 4-7 then run on the permuted sums with sigma(c0) as d_add0.
+// bgv (plans with a plain modulus t): the special limbs times t^-1 mod p_k between stages 4 and 5, the converted limbs times t mod q_j
+// between stages 5 and 6, so that the part the mod-down removes is t [acc t^-1]_P
 int ksc_back(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk, const uint64_t *d_add0,
-             const uint64_t *d_add1, const fhe_abft *a, const KscFlags &fl, hipStream_t st, const KscHook &h, const KscPerm *perm)
+             const uint64_t *d_add1, const fhe_abft *a, const KscFlags &fl, hipStream_t st, const KscHook &h, const KscPerm *perm,
+             const BgvStages *bgv)
 {
     const int L = p->L, K = p->K, M = L + K, logn = p->log_n;
     const size_t N = (size_t)1 << logn;
@@ -189,12 +192,18 @@ int ksc_back(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_
     for (int hf = 0; hf < 2; hf++)
         if ((rc = inv.compare(fl.s[4] + hf * K, (u32)(hf * M + L), (u32)L, (u32)K, (u32)K))) return rc;
 
+    // ---- BGV: special limbs of both halves times t^-1, in place inside the sums
+    if (bgv && (rc = bgv_scalar_stage(p, st, acc + (size_t)L * N, p->t_inv_P.data(), (u32)L, (u32)K, 2, (u32)M, bgv->inv, bgv->f.at(0, 0)))) return rc;
+
     // ---- 5: mod-down conversion P -> Q
     for (int hf = 0; hf < 2; hf++) {
         const BcJob job{p->down->dev, acc, conv + (size_t)hf * L * N, 0xFFFFFFFFu, 0u, p->down_rows.as<u32>() + (size_t)hf * K};
         const BcCheckedJob cj{job, p->down->shoup_dig, p->down->shoup_hor, bc_check(h.f.at(hf, 5), fl.s[5] + hf * (K + L))};
         if ((e = launch_baseconv_exact_checked(st, cj, N)) != hipSuccess) return hip_fail(e, "launch_baseconv_exact_checked");
     }
+
+    // ---- BGV: converted limbs of both halves times t
+    if (bgv && (rc = bgv_scalar_stage(p, st, conv, p->t_mod_Q.data(), 0, (u32)L, 2, (u32)L, bgv->mul, bgv->f.at(0, 1)))) return rc;
 
     // ---- 6: forward transform of the converted limbs
     if ((rc = fwd.run({KscRows{conv, 0, 0, (u32)L, 2, (u32)L, 0}}, h.f.stage == 6 ? h.flip : nullptr, h.f.bit))) return rc;
@@ -221,12 +230,13 @@ int keyswitch_checked(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, cons
     return ksc_back(p, d_out0, d_out1, d_c, d_evk, d_add0, d_add1, a, fl, st, h, nullptr);
 }
 
-int ksc_scope(const fhe_ctx *ctx, const fhe_keyswitch *p, const fhe_abft *a, const uint32_t *d_flags)
+int ksc_scope(const fhe_ctx *ctx, const fhe_keyswitch *p, const fhe_abft *a, const uint32_t *d_flags, bool bgv)
 {
     if (!p || !a || !d_flags) return fail(FHE_ERR_INVALID, "null argument");
     if (a->t != p->t) return fail(FHE_ERR_INVALID, "the detector was made for another table set than the plan's");
     if (p->sharded) return fail(FHE_ERR_INVALID, "a sharded plan has no checked key switch: the checked call runs the whole switch on one device");
-    if (p->plain_modulus) return fail(FHE_ERR_UNSUPPORTED, "the BGV steps of a plan with a plain modulus have no checked form");
+    if (!bgv && p->plain_modulus) return fail(FHE_ERR_UNSUPPORTED, "the BGV steps of a plan with a plain modulus have no checked form");
+    if (bgv && !p->plain_modulus) return fail(FHE_ERR_INVALID, "the plan has no plain modulus: use the existing checked calls");
     if (ctx->mode != 0 || ctx->resident || ctx->packed_on || ctx->only_pass >= 0 || !ntt_checked_supported(p->log_n))
         return fail(FHE_ERR_UNSUPPORTED, "the checked key switch runs the two-launch transforms: not with ntt_mode=1, ntt_resident, ntt_packed, a single-pass hook, or N < 2^5");
     if (!p->t->has_inverse) return fail(FHE_ERR_UNSUPPORTED, "table set has no inverse (twiddle or N not invertible)");

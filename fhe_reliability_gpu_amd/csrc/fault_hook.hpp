@@ -48,15 +48,20 @@ struct PointHook : PointFault {
 // ---- hooks of a composite call, which address one of its stages: stage < 0 = disarmed
 // per stage the highest injection point, or HOOK_TRANSFORM: a transform stage, whose one point lies between its two launches
 // (the setter ignores `point` and stores 0)
-constexpr int HOOK_TRANSFORM = -1;
+// HOOK_NONE: a stage number the call does not have
+constexpr int HOOK_TRANSFORM = -1, HOOK_NONE = -2;
 struct StagedRules {
     int n_stages;
-    int max_point[9];
+    int max_point[11];
 };
 constexpr StagedRules KSC_RULES{8, {HOOK_TRANSFORM, 3, HOOK_TRANSFORM, 3, HOOK_TRANSFORM, 3, HOOK_TRANSFORM, 3}};                   // key switch
 constexpr StagedRules RSC_RULES{4, {HOOK_TRANSFORM, 3, HOOK_TRANSFORM, 3}};                                                         // rescale
 constexpr StagedRules HRC_RULES{9, {HOOK_TRANSFORM, 3, HOOK_TRANSFORM, 3, HOOK_TRANSFORM, 3, HOOK_TRANSFORM, 3, GAL_AT_INDEX}};     // hoisted rotations
 constexpr StagedRules BSGS_RULES{2, {3, 3}};                                                                                        // BSGS product
+// BGV key switch: the key switch's stages plus 9 and 10, the two scalar stages (8 stays the hoisted rotations' permutation number);
+// BGV mod switch: the rescale's plus 4 and 5.  Point 3 of a scalar stage passes the setter and is refused by the call (no addend)
+constexpr StagedRules BGV_KSC_RULES{11, {HOOK_TRANSFORM, 3, HOOK_TRANSFORM, 3, HOOK_TRANSFORM, 3, HOOK_TRANSFORM, 3, HOOK_NONE, 3, 3}};
+constexpr StagedRules BGV_RSC_RULES{6, {HOOK_TRANSFORM, 3, HOOK_TRANSFORM, 3, 3, 3}};
 
 struct StagedFault {
     int block = 0;       // the rotation (hoisted rotations) or giant step (BSGS) the stage belongs to; 0 where there is none
@@ -76,7 +81,7 @@ struct StagedFault {
             take();
             return true;
         }
-        if (st >= r.n_stages || blk < 0 || u < 0 || c < 0 || b < 0 || b > 63) return false;
+        if (st >= r.n_stages || r.max_point[st] == HOOK_NONE || blk < 0 || u < 0 || c < 0 || b < 0 || b > 63) return false;
         const bool transform = r.max_point[st] == HOOK_TRANSFORM;
         if (!transform && (pt < 0 || pt > r.max_point[st])) return false;
         *this = StagedFault{blk, st, transform ? 0 : pt, u, b, c};

@@ -343,4 +343,10 @@ hipError_t launch_galois_compare(hipStream_t st, u32 *flags, const u64 *s_in, co
 hipError_t launch_diag_mac_checked(hipStream_t st, const DiagMacArgs &a, const BcCheck &k);
 hipError_t launch_modadd_checked(hipStream_t st, const PointwiseArgs &p, const BcCheck &k);
 
+// ---- scalar_checked.hip: the scalar multiply / affine map with a residue check per word (scalar_check.hpp) ----
+// launch_scalar_affine with a check record (p.b unused; add == nullptr: no addend, and no injection point 3): flags [units]
+// (poly * limbs + l), zeroed by the caller; fault_point >= 0: XOR fault_mask at that injection point of unit fault_unit (index
+// into flags), coefficient fault_coeff
+hipError_t launch_scalar_affine_checked(hipStream_t st, const PointwiseArgs &p, const ScalarVec &mul, const ScalarVec *add, const BcCheck &k);
+
 } // namespace fhe

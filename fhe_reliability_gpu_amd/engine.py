@@ -228,6 +228,19 @@ class NttTables:
         return _checked_flags(self.eng, n, lambda fl: lib.fhe_modadd_checked(self.eng._h, c.ptr, a.ptr, b.ptr, self._h, n_poly, limbs, start, fl.ptr, stream),
                               stream)
 
+    def scalar_affine_checked(self, c: DeviceArray, a: DeviceArray, mul=None, add=None, limbs=None, start=0, n_poly=1, stream=None) -> np.ndarray:
+        """c = a * mul[l] + add[l] mod q_l per limb (``mul`` None: 1, ``add`` None: 0; c may be a) with every word checked; the words
+        are ``fhe_scalar_affine``'s, bit for bit.  Returns flags[poly * limbs + l] (uint32): 1 = a s (+ o) = k q + c failed modulo
+        2^32 - 1, 2 = the word or the quotient out of its window, 4 = a word of ``a`` not canonical, which the check cannot cover
+        (scalar_check.hpp)."""
+        limbs = len(self) - start if limbs is None else limbs
+        n = n_poly * limbs
+        m = _arr(mul) if mul is not None else None
+        o = _arr(add) if add is not None else None
+        return _checked_flags(self.eng, n, lambda fl: lib.fhe_scalar_affine_checked(
+            self.eng._h, c.ptr, a.ptr, _ptr(m) if m is not None else None, _ptr(o) if o is not None else None, self._h, n_poly, limbs, start, fl.ptr,
+            stream), stream)
+
     def polymul(self, c: DeviceArray, a: DeviceArray, b: DeviceArray, limbs=None, start=0, n_poly=1, stream=None):
         limbs = len(self) - start if limbs is None else limbs
         check(lib.fhe_polymul(self.eng._h, c.ptr, a.ptr, b.ptr, self._h, n_poly, limbs, start, stream))
@@ -863,6 +876,91 @@ class KeySwitch:
         out = {"tensor": f[lay["tensor"]:lay["tensor"] + 3 * self.L].reshape(self.L, 3).copy(),
                "keyswitch": self._split_flags(f, self.checked_layout(), self.CHECKED_STAGES, lay["keyswitch"]),
                "rescale": self._split_flags(f, self.rescale_checked_layout(2), self.RESCALE_CHECKED_STAGES, lay["rescale"]) if rescale else None}
+        return o0, o1, out
+
+    # ---- BGV forms of the checked calls: plans with a plain modulus (capi_bgv_checked.cpp) ----
+    BGV_CHECKED_STAGES = CHECKED_STAGES + ("scale_special", "scale_conv")                # stages 0-7, then 9 and 10
+    BGV_MOD_SWITCH_CHECKED_STAGES = RESCALE_CHECKED_STAGES + ("scale_last", "scale_delta")   # stages 0-3, then 4 and 5
+
+    def bgv_checked_layout(self):
+        """``checked_layout`` of the BGV key switch: the eight stages at the same offsets, then ``scale_special [2][K]`` (stage 9: the
+        special limbs times t^-1, run between ``intt_special`` and ``moddown``) and ``scale_conv [2][L]`` (stage 10: the converted
+        limbs times t, run between ``moddown`` and ``ntt_conv``), plus ``"total"``."""
+        out = (C.c_int * 12)()
+        check(lib.fhe_bgv_keyswitch_checked_layout(self._h, out))
+        L, K, d = self.L, self.K, self.dnum
+        M = L + K
+        shapes = ((L,), (d, M), (d, M), (2, M), (2, K), (2, K + L), (2, L), (2, L), (2, K), (2, L))
+        lay = {name: (int(out[s]), shapes[s]) for s, name in enumerate(self.BGV_CHECKED_STAGES)}
+        lay["total"] = int(out[10])
+        return lay
+
+    def _bgv_checked(self, call, stream):
+        lay = self.bgv_checked_layout()
+        o0, o1 = self._out(self.L), self._out(self.L)
+        f = _checked_flags(self.eng, lay["total"], lambda fl: call(o0, o1, fl), stream)
+        return o0, o1, self._split_flags(f, lay, self.BGV_CHECKED_STAGES)
+
+    def bgv_apply_checked(self, c: DeviceArray, evk: DeviceArray, abft: "Abft", add0: Optional[DeviceArray] = None,
+                          add1: Optional[DeviceArray] = None, stream=None):
+        """``apply`` on a plan with a plain modulus with every stage checked, the two BGV scalar stages included: (out0, out1,
+        flags) as ``apply_checked``, ``flags`` keyed by the ten names of ``bgv_checked_layout``."""
+        return self._bgv_checked(lambda o0, o1, fl: lib.fhe_bgv_keyswitch_apply_checked(
+            self.eng._h, self._h, o0.ptr, o1.ptr, c.ptr, evk.ptr, add0.ptr if add0 is not None else None, add1.ptr if add1 is not None else None,
+            abft._h, fl.ptr, stream), stream)
+
+    def bgv_relinearize_checked(self, d0: DeviceArray, d1: DeviceArray, d2: DeviceArray, relin_key: DeviceArray, abft: "Abft", stream=None):
+        """``relinearize`` on a BGV plan with every stage checked: (out0, out1, flags) as ``bgv_apply_checked``."""
+        return self._bgv_checked(lambda o0, o1, fl: lib.fhe_bgv_relinearize_checked(
+            self.eng._h, self._h, o0.ptr, o1.ptr, d0.ptr, d1.ptr, d2.ptr, relin_key.ptr, abft._h, fl.ptr, stream), stream)
+
+    def bgv_rotate_checked(self, c0: DeviceArray, c1: DeviceArray, galois_elt: int, galois_key: DeviceArray, abft: "Abft", stream=None):
+        """``rotate`` on a BGV plan with every stage of its key switch checked: (out0, out1, flags) as ``bgv_apply_checked``.  The
+        Galois permutation runs as a launch of its own and is not covered, as for ``rotate_checked``."""
+        return self._bgv_checked(lambda o0, o1, fl: lib.fhe_bgv_rotate_checked(
+            self.eng._h, self._h, o0.ptr, o1.ptr, c0.ptr, c1.ptr, galois_elt, galois_key.ptr, abft._h, fl.ptr, stream), stream)
+
+    def bgv_mod_switch_checked_layout(self, n_parts: int = 2):
+        """``rescale_checked_layout`` of the BGV mod switch: the four stages at the same offsets, then ``scale_last [n_parts]``
+        (stage 4: the last limbs times t^-1, run between ``intt_last`` and ``reduce``) and ``scale_delta [n_parts][R]`` (stage 5: the
+        residues times t, run between ``reduce`` and ``ntt_delta``), plus ``"total"``."""
+        out = (C.c_int * 8)()
+        check(lib.fhe_bgv_mod_switch_checked_layout(self._h, n_parts, out))
+        R = self.L - 1
+        shapes = ((n_parts,), (n_parts, R), (n_parts, R), (n_parts, R), (n_parts,), (n_parts, R))
+        lay = {name: (int(out[s]), shapes[s]) for s, name in enumerate(self.BGV_MOD_SWITCH_CHECKED_STAGES)}
+        lay["total"] = int(out[6])
+        return lay
+
+    def bgv_mod_switch_checked(self, c: DeviceArray, abft: "Abft", n_parts: int = 2, stream=None):
+        """``rescale`` on a BGV plan (``mod_switch_to_next_inplace``, dotprod_test.cu:115) with every stage checked: (out, flags) as
+        ``rescale_checked``, ``flags`` keyed by the six names of ``bgv_mod_switch_checked_layout``."""
+        lay = self.bgv_mod_switch_checked_layout(n_parts)
+        o = self.eng.alloc(n_parts * (self.L - 1) * self.t.N)
+        o.shape = (n_parts, self.L - 1, self.t.N)
+        f = _checked_flags(self.eng, lay["total"], lambda fl: lib.fhe_bgv_mod_switch_checked(self.eng._h, self._h, o.ptr, c.ptr, n_parts, abft._h, fl.ptr,
+                                                                                          stream), stream)
+        return o, self._split_flags(f, lay, self.BGV_MOD_SWITCH_CHECKED_STAGES)
+
+    def bgv_hmult_checked_layout(self, rescale: bool = True):
+        """``hmult_checked_layout`` with the two BGV layouts: ``{"tensor": off, "keyswitch": off, "rescale": off, "total": n}``."""
+        out = (C.c_int * 4)()
+        check(lib.fhe_bgv_hmult_checked_layout(self._h, 1 if rescale else 0, out))
+        return {"tensor": int(out[0]), "keyswitch": int(out[1]), "rescale": int(out[2]), "total": int(out[3])}
+
+    def bgv_hmult_checked(self, a0: DeviceArray, a1: DeviceArray, b0: DeviceArray, b1: DeviceArray, relin_key: DeviceArray, abft: "Abft",
+                          rescale: bool = True, stream=None):
+        """``hmult`` on a BGV plan with every step checked -- the reference's multiply -> relinearize_inplace ->
+        mod_switch_to_next_inplace (dotprod_test.cu:113-115) as one protected call: (out0, out1, flags) as ``hmult_checked``, the
+        key-switch and mod-switch blocks keyed by the names of ``bgv_checked_layout`` / ``bgv_mod_switch_checked_layout``."""
+        lay = self.bgv_hmult_checked_layout(rescale)
+        limbs = self.L - 1 if rescale else self.L
+        o0, o1 = self._out(limbs), self._out(limbs)
+        f = _checked_flags(self.eng, lay["total"], lambda fl: lib.fhe_bgv_hmult_checked(
+            self.eng._h, self._h, o0.ptr, o1.ptr, a0.ptr, a1.ptr, b0.ptr, b1.ptr, relin_key.ptr, 1 if rescale else 0, abft._h, fl.ptr, stream), stream)
+        out = {"tensor": f[lay["tensor"]:lay["tensor"] + 3 * self.L].reshape(self.L, 3).copy(),
+               "keyswitch": self._split_flags(f, self.bgv_checked_layout(), self.BGV_CHECKED_STAGES, lay["keyswitch"]),
+               "rescale": self._split_flags(f, self.bgv_mod_switch_checked_layout(2), self.BGV_MOD_SWITCH_CHECKED_STAGES, lay["rescale"]) if rescale else None}
         return o0, o1, out
 
     def __del__(self):

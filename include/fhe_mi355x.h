@@ -577,8 +577,9 @@ int fhe_ctx_inject_fault_baseconv(fhe_ctx *ctx, int point, int unit, long long c
  * check starts from the registers its stage loaded); the Galois permutation of the checked rotation; operands raising bit 4.
  * Scope: a sharded plan returns FHE_ERR_INVALID; a plan with a plain modulus (BGV) FHE_ERR_UNSUPPORTED; a context with ntt_mode = 1,
  * ntt_resident or ntt_packed set, or N < 2^5, FHE_ERR_UNSUPPORTED.  The rescale and the homomorphic multiply have checked forms of
- * their own below, hoisted rotations, the Galois permutation and the BSGS product further down.  What remains without a checked
- * form: sharded plans, BGV plans (plain modulus) and the permutation inside fhe_rotate_checked.  A caller who wants that last one
+ * their own below, hoisted rotations, the Galois permutation and the BSGS product further down; BGV plans (plain modulus) have
+ * the fhe_bgv_*_checked calls at the end of this header.  What remains without a checked form: sharded plans, the BGV forms of the
+ * hoisted rotations and of the BSGS product, and the permutation inside fhe_rotate_checked.  A caller who wants that last one
  * checked composes it: fhe_automorphism_ntt_checked on c1 and on c0, then
  * fhe_keyswitch_apply_checked(sigma(c1), galois key, d_add0 = sigma(c0)). */
 int fhe_keyswitch_checked_layout(const fhe_keyswitch *p, int out[10]);
@@ -623,9 +624,9 @@ int fhe_ctx_inject_fault_keyswitch(fhe_ctx *ctx, int stage, int point, int unit,
  * Localisation as for the checked key switch: a fault at (stage, unit) raises that word and no other; later stages are consistent
  * with what they were handed.  Not covered: faults already in the input; a word corrupted in memory between one stage's store
  * and the next stage's load; operands raising bit 4.
- * Scope: the checked key switch's -- a sharded plan FHE_ERR_INVALID; a plan with a plain modulus (BGV) FHE_ERR_UNSUPPORTED;
- * ntt_mode = 1, ntt_resident, ntt_packed, a single-pass hook or N < 2^5 FHE_ERR_UNSUPPORTED; L < 2 FHE_ERR_INVALID; a detector
- * made for another table set than the plan's FHE_ERR_INVALID. */
+ * Scope: the checked key switch's -- a sharded plan FHE_ERR_INVALID; a plan with a plain modulus (BGV) FHE_ERR_UNSUPPORTED (its
+ * forms are fhe_bgv_mod_switch_checked / fhe_bgv_hmult_checked); ntt_mode = 1, ntt_resident, ntt_packed, a single-pass hook or
+ * N < 2^5 FHE_ERR_UNSUPPORTED; L < 2 FHE_ERR_INVALID; a detector made for another table set than the plan's FHE_ERR_INVALID. */
 int fhe_rescale_checked_layout(const fhe_keyswitch *p, size_t n_parts, int out[6]);
 int fhe_rescale_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out, const uint64_t *d_in, size_t n_parts, const fhe_abft *a,
                         uint32_t *d_flags, void *stream);
@@ -691,7 +692,7 @@ int fhe_ctx_inject_fault_galois(fhe_ctx *ctx, int point, int unit, long long coe
  * its word in block r and leaves the other rotations' words and flags alone.
  * Scope and statuses are the checked key switch's; argument rules are fhe_rotate_hoisted's (odd elements, out of place, distinct
  * parts); n_rot == 0 returns FHE_OK and launches nothing.  The rotated sums use the plan's second set of sums (allocated at the
- * first call that needs it).  Still without a checked form: sharded plans, BGV plans. */
+ * first call that needs it).  Still without a checked form: sharded plans, hoisted rotations on BGV plans. */
 int fhe_rotate_hoisted_checked_layout(const fhe_keyswitch *p, size_t n_rot, int out[12]);
 int fhe_rotate_hoisted_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *const *d_out0, uint64_t *const *d_out1, const uint64_t *d_c0,
                                const uint64_t *d_c1, const uint32_t *galois_elts, const uint64_t *const *d_prepared_keys, size_t n_rot,
@@ -760,6 +761,85 @@ int fhe_bsgs_matvec_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, ui
  * A g, unit or coefficient outside the call, and stage 1 with g = 0, return FHE_ERR_INVALID from the checked call.  A refused call
  * launches nothing and uses the hook up. */
 int fhe_ctx_inject_fault_bsgs(fhe_ctx *ctx, int g, int stage, int point, int unit, long long coeff, int bit);
+
+/* ---- checked scalar multiply and the BGV forms of the checked key switch, mod switch and multiply -----------------
+ * fhe_scalar_affine with every word checked: c = a s_l + o_l mod q_l, one scalar pair per limb.  Per word, for canonical a, s, o,
+ *     a s (+ o) = k q + c,   0 <= c < q,      checked as   r(c) + r(k) r(q) == r(a) r(s) (+ r(o))  (mod m = 2^32 - 1)
+ * with the 32-bit lane arithmetic of the checked products, plus two windows: c < q, and k within 2^24 of the FP64 estimate
+ * a s / q.  The second one is what sees a quotient moved so far that the 64-bit remainder wraps by a multiple of m words and
+ * lands in [0, q) again (2^46 (2^50 - 2^18 + 1) = m 2^64 + 2^46): a product's quotient is as large as a, so no bound taken from
+ * the operand's size separates the two.  A flag is raised exactly when the stored word differs from the clean one; an estimate one
+ * or two too low, which the conditional subtractions absorb, gives the right word and raises nothing.
+ * Words are fhe_scalar_affine's bit for bit for every input; argument rules are its own (mul == NULL: 1, add == NULL: 0, scalars
+ * reduced by the call, limbs <= 64 else FHE_ERR_UNSUPPORTED with nothing launched and the flags untouched, d_c may alias d_a).
+ * Flags: d_flags[poly * limbs + l], cleared by the call on `stream`; bit 1 identity, bit 2 a window, bit 4 the word a >= q --
+ * multiplied as fhe_scalar_affine multiplies it, not checked, raised alone.  fhe_ctx_inject_fault_pointwise is honoured: point 0 the
+ * low word of the 128-bit product, 1 the Barrett quotient estimate, 2 the word before its window check, 3 the sum a s mod q + o
+ * before the conditional subtraction -- only with an addend, FHE_ERR_UNSUPPORTED and nothing launched without one.  The hook is
+ * used up either way.  Not covered: faults already in d_a, a register fault on a word before the product, its residue and the
+ * estimate have all read it, faults in the limb constants or the scalars. */
+int fhe_scalar_affine_checked(fhe_ctx *ctx, uint64_t *d_c, const uint64_t *d_a, const uint64_t *mul, const uint64_t *add,
+                              const fhe_ntt_tables *t, size_t n_poly, size_t limbs, size_t start_idx,
+                              uint32_t *d_flags /* [n_poly][limbs] */, void *stream);
+
+/* The checked key switch, relinearisation and rotation on a plan WITH a plain modulus t (fhe_keyswitch_set_plain_modulus): the
+ * scheme of reliability_test/dotprod_test.cu:113-148.  A BGV mod-down removes t [acc t^-1]_P instead of [acc]_P, so the launch list
+ * is stages 0-7 of the checked key switch plus two word-wise scalar stages, both in place, both the kernel of
+ * fhe_scalar_affine_checked:
+ *   stage 9   special limbs of both halves of the sums times t^-1 mod p_k (coefficient form)     between stages 4 and 5   [2][K]
+ *   stage 10  converted limbs of both halves times t mod q_j (coefficient form)                  between stages 5 and 6   [2][L]
+ * (8 stays the hoisted rotations' permutation number and is not used here.)  Signatures, argument rules and d_add0 / d_add1 are
+ * those of fhe_keyswitch_apply_checked / fhe_relinearize_checked / fhe_rotate_checked; fhe_bgv_rotate_checked applies sigma
+ * unchecked, as fhe_rotate_checked does.  d_out0 / d_out1 are the words of fhe_keyswitch_apply / fhe_relinearize / fhe_rotate on
+ * the same plan, bit for bit, whichever route the unchecked call took (t riding on the fused tail, or a launch of its own).
+ * Flags: fhe_bgv_keyswitch_checked_layout gives out[0..7] = the offsets of fhe_keyswitch_checked_layout, out[8] = offset of stage 9
+ * (the CKKS-form total), out[9] = offset of stage 10, out[10] = total, out[11] = 0 (reserved).  Stages 9 and 10: unit = half * K + k
+ * / half * L + j; bit 1 identity, 2 window, 4 operand >= q -- never raised on a clean run, both inputs are stage outputs.
+ * Localisation: as for the checked key switch, a fault at (stage, unit) raises that word and no other.
+ * Not covered: what the checked key switch does not cover; faults in the plan's scalars t^-1 mod p_k, t mod q_j.
+ * Scope: a plan WITHOUT a plain modulus returns FHE_ERR_INVALID (use the calls above); otherwise the checked key switch's -- a
+ * sharded plan FHE_ERR_INVALID, ntt_mode = 1, ntt_resident, ntt_packed, a single-pass hook or N < 2^5 FHE_ERR_UNSUPPORTED, a
+ * detector made for another table set FHE_ERR_INVALID -- and L, K <= 64 (FHE_ERR_UNSUPPORTED).  Still without a checked form:
+ * the BGV forms of fhe_rotate_hoisted_checked and fhe_bsgs_matvec_checked, sharded plans. */
+int fhe_bgv_keyswitch_checked_layout(const fhe_keyswitch *p, int out[12]);
+int fhe_bgv_keyswitch_apply_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c,
+                                    const uint64_t *d_evk, const uint64_t *d_add0 /* optional */, const uint64_t *d_add1 /* optional */,
+                                    const fhe_abft *a, uint32_t *d_flags, void *stream);
+int fhe_bgv_relinearize_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_d0,
+                                const uint64_t *d_d1, const uint64_t *d_d2, const uint64_t *d_relin_key, const fhe_abft *a,
+                                uint32_t *d_flags, void *stream);
+int fhe_bgv_rotate_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0,
+                           const uint64_t *d_c1, uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a,
+                           uint32_t *d_flags, void *stream);
+/* mod_switch_to_next on a BGV plan (fhe_rescale's words there, bit for bit): the checked rescale's stages 0-3 plus
+ *   stage 4  each part's last limb in coefficient form times t^-1 mod q_last                      between stages 0 and 1   [n_parts]
+ *   stage 5  the residues times t mod q_j                                                         between stages 1 and 2   [n_parts][R]
+ * so that the removed part is t [c t^-1]_{q_last}.  Arguments of fhe_rescale_checked.  fhe_bgv_mod_switch_checked_layout gives
+ * out[0..3] as fhe_rescale_checked_layout, out[4] / out[5] = offsets of stages 4 / 5, out[6] = total, out[7] = 0.  Flag bits of
+ * stages 4 and 5 as stages 9 and 10 above; scope as above, and L < 2 FHE_ERR_INVALID. */
+int fhe_bgv_mod_switch_checked_layout(const fhe_keyswitch *p, size_t n_parts, int out[8]);
+int fhe_bgv_mod_switch_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out, const uint64_t *d_in, size_t n_parts, const fhe_abft *a,
+                               uint32_t *d_flags, void *stream);
+/* fhe_hmult on a BGV plan with every step checked -- multiply -> relinearize_inplace -> mod_switch_to_next_inplace as the
+ * reference's dot product runs them: fhe_tensor_product_checked, the BGV checked relinearisation, and (rescale != 0) the BGV
+ * checked mod switch of both parts.  Arguments and aliasing rules of fhe_hmult_checked; the words are fhe_hmult's on the same plan.
+ * Blocks as in fhe_hmult_checked_layout with the two BGV layouts: out[0] = 0 tensor [3 L], out[1] the key-switch block
+ * (fhe_bgv_keyswitch_checked_layout), out[2] the mod-switch block (fhe_bgv_mod_switch_checked_layout, n_parts = 2; = out[3] when
+ * rescale == 0), out[3] total. */
+int fhe_bgv_hmult_checked_layout(const fhe_keyswitch *p, int rescale, int out[4]);
+int fhe_bgv_hmult_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_a0, const uint64_t *d_a1,
+                          const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a,
+                          uint32_t *d_flags, void *stream);
+/* Test hooks of the BGV calls, one shot each, with records of their own: the BGV calls take only these (fhe_bgv_hmult_checked
+ * also fhe_ctx_inject_fault_pointwise for its tensor step) and neither take nor honour fhe_ctx_inject_fault_keyswitch / _rescale;
+ * the calls above do not take these.  A hook is checked against the call before its first launch; a refused call launches
+ * nothing and uses the hook up.  stage < 0 clears.
+ *   _bgv_keyswitch: stages 0-7 as fhe_ctx_inject_fault_keyswitch; stages 9 and 10: point 0 the low word of the product, 1 the
+ *     quotient estimate, 2 the word before its window check; point 3 returns FHE_ERR_UNSUPPORTED from the checked call (no addend,
+ *     no sum).  Stage 8 is refused by the setter: FHE_ERR_INVALID.
+ *   _bgv_mod_switch: stages 0-3 as fhe_ctx_inject_fault_rescale; stages 4 and 5 as stages 9 and 10. */
+int fhe_ctx_inject_fault_bgv_keyswitch(fhe_ctx *ctx, int stage, int point, int unit, long long coeff, int bit);
+int fhe_ctx_inject_fault_bgv_mod_switch(fhe_ctx *ctx, int stage, int point, int unit, long long coeff, int bit);
 
 /* ---- fault injection ---------------------------------------------------------------- */
 /* _flip_bit_kernel<<<1,1>>> (reliability_test/dotprod_test.cu:31-33,55): data[idx] ^= 1 << bit */
