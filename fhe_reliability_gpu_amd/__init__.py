@@ -18,6 +18,9 @@ from .engine import (  # noqa: F401
     Engine,
     FourStep,
     NttTables,
+    SEAL_P,
+    SEAL_RANGE,
+    SEAL_SUM,
     bConv,
     base_conv_fixed,
     create_moduli,

@@ -166,6 +166,13 @@ _SIG = {
     "fhe_ctx_inject_fault_bgv_mod_switch": (ci, [vp, ci, ci, ci, C.c_longlong, ci]),
     "fhe_bgv_hmult_checked_layout": (ci, [vp, ci, C.POINTER(ci)]),
     "fhe_bgv_hmult_checked": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp]),
+    "fhe_seal": (ci, [vp, vp, vp, vp, sz, sz, sz, vp]),
+    "fhe_seal_verify": (ci, [vp, vp, vp, vp, sz, sz, sz, vp, vp]),
+    "fhe_ctx_inject_fault_seal": (ci, [vp, ci, C.c_longlong, ci]),
+    "fhe_hmult_sealed_layout": (ci, [vp, ci, C.POINTER(ci)]),
+    "fhe_hmult_sealed": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, C.POINTER(vp), vp, C.POINTER(vp), vp, vp]),
+    "fhe_rotate_sealed_layout": (ci, [vp, C.POINTER(ci)]),
+    "fhe_rotate_sealed": (ci, [vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp, C.POINTER(vp), vp, C.POINTER(vp), vp, vp]),
     "fhe_ctx_trace": (ci, [vp, ci]),
     "fhe_ctx_trace_read": (ci, [vp, C.c_char_p, sz, C.POINTER(sz)]),
 }

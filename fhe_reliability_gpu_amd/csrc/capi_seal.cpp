@@ -1,0 +1,246 @@
+// capi_seal.cpp -- seals of operands at rest (seal_check.hpp, seal_checked.hip): fhe_seal, fhe_seal_verify, their test hook, and the
+// sealed homomorphic multiply and rotation (part of the C ABI of include/fhe_mi355x.h).
+//
+// The checked calls do not cover faults already in their inputs.  A sealed composite closes that gap around an existing checked
+// call without touching it: it verifies every seal it was given (operands, key), runs the checked call unchanged -- the CKKS or the
+// BGV form, by the plan's plain modulus -- and seals both outputs, all on one stream.  The flag buffer is
+//     [input rows, in argument order][key rows][the checked call's own block, exactly its layout]
+// and a raised input flag does not stop the call: flags are read by the caller afterwards, as everywhere else.
+#include "capi_checked.hpp"
+#include "seal_check.hpp"
+
+#include <cstdint>
+
+namespace {
+
+// the partial-sum scratch of the context, at least `words` long
+int seal_scratch(fhe_ctx *ctx, size_t words, u64 **out)
+{
+    if (ctx->seal_part.bytes < words * 8) HIP_TRY(ctx->seal_part.alloc(words * 8));
+    *out = ctx->seal_part.as<u64>();
+    return FHE_OK;
+}
+
+int seal_window(const fhe_ntt_tables *t, const uint64_t *d_words, size_t n_poly, size_t limbs, size_t start_idx)
+{
+    int rc = check_range(t, n_poly, limbs, start_idx);
+    if (rc) return rc;
+    if (t->log_n < 1) return fail(FHE_ERR_UNSUPPORTED, "a sealed row has at least two words");
+    if ((uintptr_t)d_words % 16) return fail(FHE_ERR_INVALID, "sealed rows are read 16 bytes at a time: the buffer must be 16-byte aligned");
+    return FHE_OK;
+}
+
+SealArgs seal_args(const fhe_ntt_tables *t, const uint64_t *d_words, size_t n_poly, size_t limbs, size_t start_idx)
+{
+    return SealArgs{d_words, t->d_lp.as<LimbParams>(), (u32)start_idx, (u32)limbs, (u32)(n_poly * limbs), (u32)limbs, t->log_n};
+}
+
+// the seal hook a call of `units` rows took, checked against that call
+int seal_fault(const PointFault &f, size_t units, int log_n, BcCheck &k)
+{
+    if (f.point < 0) return FHE_OK;
+    if (f.unit >= units || f.coeff >> log_n) return fail(FHE_ERR_INVALID, "fault row or word outside the call");
+    k.fault_point = 0;
+    k.fault_unit = f.unit;
+    k.fault_coeff = f.coeff;
+    k.fault_mask = (u64)1 << f.bit;
+    return FHE_OK;
+}
+
+// one operand of a sealed composite: `limbs` rows from table limb 0 on, n_poly polynomials; a null seal is skipped
+struct SealedRows {
+    const uint64_t *words, *seal;
+    size_t n_poly, limbs;
+    int flag_off;
+};
+
+int verify_rows(hipStream_t st, const fhe_ntt_tables *t, const SealedRows &r, uint32_t *d_flags, u64 *part)
+{
+    if (!r.seal) return FHE_OK;
+    hipError_t e = launch_seal_verify(st, seal_args(t, r.words, r.n_poly, r.limbs, 0), part, r.seal, BcCheck{d_flags + r.flag_off, -1, 0, 0, 0});
+    return e == hipSuccess ? FHE_OK : hip_fail(e, "launch_seal_verify");
+}
+
+int seal_outputs(hipStream_t st, const fhe_ntt_tables *t, uint64_t *const *d_seal_out, const uint64_t *d_out0, const uint64_t *d_out1, size_t limbs, u64 *part)
+{
+    const uint64_t *outs[2] = {d_out0, d_out1};
+    for (int h = 0; h < 2; h++) {
+        if (!d_seal_out || !d_seal_out[h]) continue;
+        hipError_t e = launch_seal(st, seal_args(t, outs[h], 1, limbs, 0), part, d_seal_out[h], BcCheck{nullptr, -1, 0, 0, 0});
+        if (e != hipSuccess) return hip_fail(e, "launch_seal");
+    }
+    return FHE_OK;
+}
+
+// what must hold before the first verifying launch, so that a call outside the checked call's scope launches nothing: false = let
+// the checked call itself refuse (it returns the status and takes its hooks)
+bool sealed_scope_ok(const fhe_ctx *ctx, const fhe_keyswitch *p, const fhe_abft *a, const uint32_t *d_flags, bool mod_switch)
+{
+    if (!p) return false;
+    const bool bgv = p->plain_modulus != 0;
+    if (ksc_scope(ctx, p, a, d_flags, bgv)) return false;
+    if (bgv && (p->L > SCALAR_MAX_LIMBS || p->K > SCALAR_MAX_LIMBS)) return false;
+    return !(mod_switch && p->L < 2);
+}
+
+size_t key_rows(const fhe_keyswitch *p) { return (size_t)p->dnum * 2 * (p->L + p->K); }
+
+// scratch for the largest launch of a sealed composite (the key's rows), before anything is launched
+int sealed_scratch(fhe_ctx *ctx, const fhe_keyswitch *p, u64 **part) { return seal_scratch(ctx, seal_part_words((u32)key_rows(p), p->log_n), part); }
+
+bool misaligned(std::initializer_list<const void *> ptrs)
+{
+    for (const void *q : ptrs)
+        if ((uintptr_t)q % 16) return true;
+    return false;
+}
+
+} // namespace
+
+extern "C" {
+
+int fhe_ctx_inject_fault_seal(fhe_ctx *ctx, int row, long long coeff, int bit)
+{
+    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
+    return ctx->seal_fault.arm(0, row < 0 ? -1 : 0, row, coeff, bit) ? FHE_OK : fail(FHE_ERR_INVALID, "bad fault");
+}
+
+int fhe_seal(fhe_ctx *ctx, uint64_t *d_seal, const uint64_t *d_words, const fhe_ntt_tables *t, size_t n_poly, size_t limbs, size_t start_idx,
+             void *stream)
+{
+    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
+    const PointFault f = ctx->seal_fault.take();      // one shot, whatever the outcome
+    if (!d_seal || !d_words) return fail(FHE_ERR_INVALID, "null argument");
+    int rc = seal_window(t, d_words, n_poly, limbs, start_idx);
+    if (rc) return rc;
+    const size_t units = n_poly * limbs;
+    BcCheck k{nullptr, -1, 0, 0, 0};
+    if ((rc = seal_fault(f, units, t->log_n, k))) return rc;
+    if (!units) return FHE_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    u64 *part;
+    if ((rc = seal_scratch(ctx, seal_part_words((u32)units, t->log_n), &part))) return rc;
+    hipError_t e = launch_seal(pick(ctx, stream), seal_args(t, d_words, n_poly, limbs, start_idx), part, d_seal, k);
+    return e == hipSuccess ? FHE_OK : hip_fail(e, "launch_seal");
+}
+
+int fhe_seal_verify(fhe_ctx *ctx, const uint64_t *d_words, const uint64_t *d_seal, const fhe_ntt_tables *t, size_t n_poly, size_t limbs,
+                    size_t start_idx, uint32_t *d_flags, void *stream)
+{
+    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
+    const PointFault f = ctx->seal_fault.take();      // one shot, whatever the outcome
+    if (!d_seal || !d_words || !d_flags) return fail(FHE_ERR_INVALID, "null argument");
+    int rc = seal_window(t, d_words, n_poly, limbs, start_idx);
+    if (rc) return rc;
+    const size_t units = n_poly * limbs;
+    BcCheck k{d_flags, -1, 0, 0, 0};
+    if ((rc = seal_fault(f, units, t->log_n, k))) return rc;
+    if (!units) return FHE_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = pick(ctx, stream);
+    u64 *part;
+    if ((rc = seal_scratch(ctx, seal_part_words((u32)units, t->log_n), &part))) return rc;
+    HIP_TRY(hipMemsetAsync(d_flags, 0, units * sizeof(u32), st));
+    hipError_t e = launch_seal_verify(st, seal_args(t, d_words, n_poly, limbs, start_idx), part, d_seal, k);
+    return e == hipSuccess ? FHE_OK : hip_fail(e, "launch_seal_verify");
+}
+
+int fhe_hmult_sealed_layout(const fhe_keyswitch *p, int rescale, int out[8])
+{
+    if (!p || !out) return fail(FHE_ERR_INVALID, "null argument");
+    int inner[4];
+    int rc = p->plain_modulus ? fhe_bgv_hmult_checked_layout(p, rescale, inner) : fhe_hmult_checked_layout(p, rescale, inner);
+    if (rc) return rc;
+    for (int i = 0; i < 4; i++) out[i] = i * p->L;
+    out[4] = 4 * p->L;
+    out[5] = out[4] + (int)key_rows(p);
+    out[6] = out[5] + inner[3];
+    out[7] = 0;
+    return FHE_OK;
+}
+
+int fhe_hmult_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_a0, const uint64_t *d_a1,
+                     const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a,
+                     const uint64_t *const *d_seal_in, const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
+{
+    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
+    const bool bgv = p && p->plain_modulus;
+    auto checked = [&](uint32_t *flags) {
+        return (bgv ? fhe_bgv_hmult_checked : fhe_hmult_checked)(ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, flags, stream);
+    };
+    if (!sealed_scope_ok(ctx, p, a, d_flags, rescale != 0) || !d_out0 || !d_out1 || d_out0 == d_out1 || !d_a0 || !d_a1 || !d_b0 || !d_b1 || !d_relin_key) {
+        const int rc = checked(d_flags);      // refuses before its first launch
+        return rc ? rc : fail(FHE_ERR_INVALID, "sealed multiply: bad argument");
+    }
+    if (misaligned({d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key})) {
+        (void)checked(nullptr);      // takes the hooks, launches nothing
+        return fail(FHE_ERR_INVALID, "sealed rows are read 16 bytes at a time: the buffers must be 16-byte aligned");
+    }
+    int lay[8], rc;
+    if ((rc = fhe_hmult_sealed_layout(p, rescale, lay))) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = pick(ctx, stream);
+    u64 *part;
+    if ((rc = sealed_scratch(ctx, p, &part))) return rc;
+    HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)lay[5] * sizeof(u32), st));
+    const size_t L = p->L;
+    const uint64_t *ops[4] = {d_a0, d_a1, d_b0, d_b1};
+    for (int i = 0; i < 4; i++)
+        if ((rc = verify_rows(st, p->t, SealedRows{ops[i], d_seal_in ? d_seal_in[i] : nullptr, 1, L, lay[i]}, d_flags, part))) return rc;
+    if ((rc = verify_rows(st, p->t, SealedRows{d_relin_key, d_seal_key, (size_t)p->dnum * 2, L + p->K, lay[4]}, d_flags, part))) return rc;
+    if ((rc = checked(d_flags + lay[5]))) return rc;
+    return seal_outputs(st, p->t, d_seal_out, d_out0, d_out1, rescale ? L - 1 : L, part);
+}
+
+int fhe_rotate_sealed_layout(const fhe_keyswitch *p, int out[6])
+{
+    if (!p || !out) return fail(FHE_ERR_INVALID, "null argument");
+    out[0] = 0;
+    out[1] = p->L;
+    out[2] = 2 * p->L;
+    out[3] = out[2] + (int)key_rows(p);
+    if (p->plain_modulus) {
+        int inner[12];
+        int rc = fhe_bgv_keyswitch_checked_layout(p, inner);
+        if (rc) return rc;
+        out[4] = out[3] + inner[10];
+    } else
+        out[4] = out[3] + ksc_layout(p).total;
+    out[5] = 0;
+    return FHE_OK;
+}
+
+int fhe_rotate_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0, const uint64_t *d_c1,
+                      uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, const uint64_t *const *d_seal_in,
+                      const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
+{
+    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
+    const bool bgv = p && p->plain_modulus;
+    auto checked = [&](uint32_t *flags) {
+        return (bgv ? fhe_bgv_rotate_checked : fhe_rotate_checked)(ctx, p, d_out0, d_out1, d_c0, d_c1, galois_elt, d_galois_key, a, flags, stream);
+    };
+    if (!sealed_scope_ok(ctx, p, a, d_flags, false) || !d_out0 || !d_out1 || d_out0 == d_out1 || !d_c0 || !d_c1 || !d_galois_key || !(galois_elt & 1)) {
+        const int rc = checked(d_flags);      // refuses before its first launch
+        return rc ? rc : fail(FHE_ERR_INVALID, "sealed rotation: bad argument");
+    }
+    if (misaligned({d_out0, d_out1, d_c0, d_c1, d_galois_key})) {
+        (void)checked(nullptr);      // takes the hook, launches nothing
+        return fail(FHE_ERR_INVALID, "sealed rows are read 16 bytes at a time: the buffers must be 16-byte aligned");
+    }
+    int lay[6], rc;
+    if ((rc = fhe_rotate_sealed_layout(p, lay))) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = pick(ctx, stream);
+    u64 *part;
+    if ((rc = sealed_scratch(ctx, p, &part))) return rc;
+    HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)lay[3] * sizeof(u32), st));
+    const size_t L = p->L;
+    const uint64_t *ops[2] = {d_c0, d_c1};
+    for (int i = 0; i < 2; i++)
+        if ((rc = verify_rows(st, p->t, SealedRows{ops[i], d_seal_in ? d_seal_in[i] : nullptr, 1, L, lay[i]}, d_flags, part))) return rc;
+    if ((rc = verify_rows(st, p->t, SealedRows{d_galois_key, d_seal_key, (size_t)p->dnum * 2, L + p->K, lay[2]}, d_flags, part))) return rc;
+    if ((rc = checked(d_flags + lay[3]))) return rc;
+    return seal_outputs(st, p->t, d_seal_out, d_out0, d_out1, L, part);
+}
+
+} // extern "C"

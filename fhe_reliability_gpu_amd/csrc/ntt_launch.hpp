@@ -349,4 +349,20 @@ hipError_t launch_modadd_checked(hipStream_t st, const PointwiseArgs &p, const B
 // into flags), coefficient fault_coeff
 hipError_t launch_scalar_affine_checked(hipStream_t st, const PointwiseArgs &p, const ScalarVec &mul, const ScalarVec *add, const BcCheck &k);
 
+// ---- seal_checked.hip: seals of rows at rest, two weighted sums modulo 2^61 - 1 per row (seal_check.hpp) ----
+// the rows of a window of limbs of n_poly polynomials poly_stride rows apart, addressed as PointwiseArgs addresses them; x is
+// 16-byte aligned and logn >= 1 (a lane loads two words)
+struct SealArgs {
+    const u64 *x;
+    const LimbParams *lp;
+    u32 limb0, limbs, units, poly_stride;
+    int logn;
+};
+// words of the partial-sum scratch a launch needs: [units][chunks per row][2]
+size_t seal_part_words(u32 units, int logn);
+// seal[unit] = {S0, S1}, canonical; fault_point >= 0: XOR fault_mask into word fault_coeff of row fault_unit in the register
+hipError_t launch_seal(hipStream_t st, const SealArgs &p, u64 *part, u64 *seal, const BcCheck &k);
+// k.flags[unit] |= SEAL_SUM where the row's sums differ from seal[unit], SEAL_RANGE where a word is >= q_l; zeroed by the caller
+hipError_t launch_seal_verify(hipStream_t st, const SealArgs &p, u64 *part, const u64 *seal, const BcCheck &k);
+
 } // namespace fhe

@@ -17,6 +17,10 @@ from ._lib import check, lib, p64, u64, vp
 
 _U64 = np.uint64
 
+# seals of rows at rest (seal_check.hpp): the modulus of the two sums, and the flag bits of a verification
+SEAL_P = (1 << 61) - 1
+SEAL_SUM, SEAL_RANGE = 1, 2
+
 
 def _arr(x) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(x, dtype=_U64))
@@ -240,6 +244,25 @@ class NttTables:
         return _checked_flags(self.eng, n, lambda fl: lib.fhe_scalar_affine_checked(
             self.eng._h, c.ptr, a.ptr, _ptr(m) if m is not None else None, _ptr(o) if o is not None else None, self._h, n_poly, limbs, start, fl.ptr,
             stream), stream)
+
+    def seal(self, d: DeviceArray, limbs=None, start=0, n_poly=1, stream=None) -> DeviceArray:
+        """The seals of the rows of ``d`` = [n_poly][limbs][N]: a device array ``[n_poly * limbs][2]`` of (S0, S1) with
+        S0 = sum x_j, S1 = sum (j + 1) x_j modulo 2^61 - 1, canonical.  An integrity record that travels with a ciphertext or key
+        between calls (``seal_verify``, ``KeySwitch.hmult_sealed`` / ``rotate_sealed``): the checked calls do not cover faults
+        already in their inputs -- the flips of reliability_test/dotprod_test.cu:31-61."""
+        limbs = len(self) - start if limbs is None else limbs
+        out = self.eng.alloc(n_poly * limbs * 2)
+        out.shape = (n_poly * limbs, 2)
+        check(lib.fhe_seal(self.eng._h, out.ptr, d.ptr, self._h, n_poly, limbs, start, stream))
+        return out
+
+    def seal_verify(self, d: DeviceArray, seal: DeviceArray, limbs=None, start=0, n_poly=1, stream=None) -> np.ndarray:
+        """Sweep the rows of ``d`` against ``seal``: flags[poly * limbs + l] (uint32), ``SEAL_SUM`` (1) = a sum differs,
+        ``SEAL_RANGE`` (2) = some word >= q_l.  A change confined to one or two words of a row is caught with certainty
+        (seal_check.hpp)."""
+        limbs = len(self) - start if limbs is None else limbs
+        return _checked_flags(self.eng, n_poly * limbs, lambda fl: lib.fhe_seal_verify(self.eng._h, d.ptr, seal.ptr, self._h, n_poly, limbs, start, fl.ptr,
+                                                                                       stream), stream)
 
     def polymul(self, c: DeviceArray, a: DeviceArray, b: DeviceArray, limbs=None, start=0, n_poly=1, stream=None):
         limbs = len(self) - start if limbs is None else limbs
@@ -593,6 +616,7 @@ class KeySwitch:
 
     def __init__(self, eng: Engine, t: NttTables, L: int, K: int, dnum: int):
         self.eng, self.t, self.L, self.K, self.dnum = eng, t, L, K, dnum
+        self.plain_modulus = 0
         h = vp()
         check(lib.fhe_keyswitch_create(eng._h, t._h, L, K, dnum, C.byref(h)))
         self._h = h
@@ -650,6 +674,7 @@ class KeySwitch:
     def set_plain_modulus(self, t: int):
         """BGV form of the mod-down and of the rescale (0 = CKKS-style flooring)."""
         check(lib.fhe_keyswitch_set_plain_modulus(self._h, t))
+        self.plain_modulus = int(t)
 
     def _out(self, limbs: int) -> DeviceArray:
         o = self.eng.alloc(limbs * self.t.N)
@@ -962,6 +987,86 @@ class KeySwitch:
                "keyswitch": self._split_flags(f, self.bgv_checked_layout(), self.BGV_CHECKED_STAGES, lay["keyswitch"]),
                "rescale": self._split_flags(f, self.bgv_mod_switch_checked_layout(2), self.BGV_MOD_SWITCH_CHECKED_STAGES, lay["rescale"]) if rescale else None}
         return o0, o1, out
+
+    # ---- operands sealed at rest: the checked multiply and rotation behind seal verification (capi_seal.cpp) ----
+    def seal_key(self, key: DeviceArray, stream=None) -> DeviceArray:
+        """The seal of a relinearisation or Galois key ``[dnum][2][L + K][N]``: ``[dnum * 2 * (L + K)][2]``."""
+        return self.t.seal(key, limbs=self.L + self.K, start=0, n_poly=2 * self.dnum, stream=stream)
+
+    def _sealed_layout(self, out, names, checked, total):
+        L, M = self.L, self.L + self.K
+        lay = {name: (int(out[i]), (L,)) for i, name in enumerate(names)}
+        lay["key"] = (int(out[len(names)]), (self.dnum, 2, M))
+        lay["checked"], lay["total"] = int(out[checked]), int(out[total])
+        return lay
+
+    def hmult_sealed_layout(self, rescale: bool = True):
+        """``{"a0", "a1", "b0", "b1": (offset, (L,)), "key": (offset, (dnum, 2, M)), "checked": offset, "total": n}`` of
+        ``hmult_sealed``'s flag buffer: the input rows in argument order, the key's rows, then the checked multiply's own block
+        (``hmult_checked_layout``, or ``bgv_hmult_checked_layout`` on a plan with a plain modulus)."""
+        out = (C.c_int * 8)()
+        check(lib.fhe_hmult_sealed_layout(self._h, 1 if rescale else 0, out))
+        return self._sealed_layout(out, ("a0", "a1", "b0", "b1"), 5, 6)
+
+    def rotate_sealed_layout(self):
+        """``{"c0", "c1": (offset, (L,)), "key": (offset, (dnum, 2, M)), "checked": offset, "total": n}`` of ``rotate_sealed``'s
+        flag buffer; the checked block is laid out as ``checked_layout`` (``bgv_checked_layout`` with a plain modulus)."""
+        out = (C.c_int * 6)()
+        check(lib.fhe_rotate_sealed_layout(self._h, out))
+        return self._sealed_layout(out, ("c0", "c1"), 3, 4)
+
+    def _sealed(self, lay, names, limbs, seals, call, stream):
+        """Run ``call(o0, o1, seal_in, seal_out, flags)``; returns (o0, o1, (seal0, seal1), flat flags)."""
+        o0, o1 = self._out(limbs), self._out(limbs)
+        so = [self.eng.alloc(2 * limbs) for _ in range(2)]
+        for x in so:
+            x.shape = (limbs, 2)
+        seals = tuple(seals) if seals is not None else (None,) * len(names)
+        sin = (vp * len(names))(*[x.ptr if x is not None else None for x in seals])
+        sout = (vp * 2)(so[0].ptr, so[1].ptr)
+        f = _checked_flags(self.eng, lay["total"], lambda fl: call(o0, o1, sin, sout, fl), stream)
+        return o0, o1, tuple(so), f
+
+    def hmult_sealed(self, a0: DeviceArray, a1: DeviceArray, b0: DeviceArray, b1: DeviceArray, relin_key: DeviceArray, abft: "Abft",
+                     seals=None, key_seal: Optional[DeviceArray] = None, rescale: bool = True, stream=None):
+        """``hmult_checked`` (``bgv_hmult_checked`` on a plan with a plain modulus) with the operands protected at rest: every given
+        seal is verified, the checked multiply runs unchanged, both outputs are sealed: ``(out0, out1, (seal0, seal1), flags)``.
+        ``seals`` = the seals of (a0, a1, b0, b1) from ``NttTables.seal`` (an entry, or all, may be None: not verified),
+        ``key_seal`` from ``seal_key``.  ``flags = {"a0", "a1", "b0", "b1": [L], "key": [dnum][2][M], "checked": <the flags of the
+        checked multiply>}``, input words with the bits of ``seal_verify``.  A raised input flag does not stop the call; the checked
+        block and the output seals are then meaningless.  The words are ``hmult``'s, bit for bit."""
+        names = ("a0", "a1", "b0", "b1")
+        lay = self.hmult_sealed_layout(rescale)
+        o0, o1, so, f = self._sealed(lay, names, self.L - 1 if rescale else self.L, seals, lambda o0, o1, sin, sout, fl: lib.fhe_hmult_sealed(
+            self.eng._h, self._h, o0.ptr, o1.ptr, a0.ptr, a1.ptr, b0.ptr, b1.ptr, relin_key.ptr, 1 if rescale else 0, abft._h, sin,
+            key_seal.ptr if key_seal is not None else None, sout, fl.ptr, stream), stream)
+        flags = self._split_flags(f, lay, names + ("key",))
+        base = lay["checked"]
+        if self.plain_modulus:
+            hl, kl, ks_names = self.bgv_hmult_checked_layout(rescale), self.bgv_checked_layout(), self.BGV_CHECKED_STAGES
+            rl, rs_names = (self.bgv_mod_switch_checked_layout(2), self.BGV_MOD_SWITCH_CHECKED_STAGES) if rescale else (None, None)
+        else:
+            hl, kl, ks_names = self.hmult_checked_layout(rescale), self.checked_layout(), self.CHECKED_STAGES
+            rl, rs_names = (self.rescale_checked_layout(2), self.RESCALE_CHECKED_STAGES) if rescale else (None, None)
+        flags["checked"] = {"tensor": f[base + hl["tensor"]:base + hl["tensor"] + 3 * self.L].reshape(self.L, 3).copy(),
+                            "keyswitch": self._split_flags(f, kl, ks_names, base + hl["keyswitch"]),
+                            "rescale": self._split_flags(f, rl, rs_names, base + hl["rescale"]) if rescale else None}
+        return o0, o1, so, flags
+
+    def rotate_sealed(self, c0: DeviceArray, c1: DeviceArray, galois_elt: int, galois_key: DeviceArray, abft: "Abft", seals=None,
+                      key_seal: Optional[DeviceArray] = None, stream=None):
+        """``rotate_checked`` (``bgv_rotate_checked`` on a plan with a plain modulus) with the operands protected at rest:
+        ``(out0, out1, (seal0, seal1), flags)`` as ``hmult_sealed``; ``seals`` = the seals of (c0, c1), ``flags = {"c0", "c1": [L],
+        "key": [dnum][2][M], "checked": {the stage names of checked_layout / bgv_checked_layout}}``."""
+        names = ("c0", "c1")
+        lay = self.rotate_sealed_layout()
+        o0, o1, so, f = self._sealed(lay, names, self.L, seals, lambda o0, o1, sin, sout, fl: lib.fhe_rotate_sealed(
+            self.eng._h, self._h, o0.ptr, o1.ptr, c0.ptr, c1.ptr, galois_elt, galois_key.ptr, abft._h, sin,
+            key_seal.ptr if key_seal is not None else None, sout, fl.ptr, stream), stream)
+        flags = self._split_flags(f, lay, names + ("key",))
+        kl, ks_names = (self.bgv_checked_layout(), self.BGV_CHECKED_STAGES) if self.plain_modulus else (self.checked_layout(), self.CHECKED_STAGES)
+        flags["checked"] = self._split_flags(f, kl, ks_names, lay["checked"])
+        return o0, o1, so, flags
 
     def __del__(self):
         try:

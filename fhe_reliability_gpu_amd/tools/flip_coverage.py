@@ -1,0 +1,126 @@
+"""The reference's bit-flip experiment with a detector verdict next to its corruption count.
+
+reliability_test/dotprod_test.cu:31-61 flips ``bits_per_symbol`` bits in each of ``num_symbols`` words of an encrypted operand in
+memory, then runs multiply -> relinearize -> mod_switch (:113-115) and log2(row) rounds of rotate + add (:143-148).  Here the same
+chain runs on a BGV plan of the same shape (default N = 2^14, six 50-bit primes of which two are special, plain modulus 65537,
+:199-204) through the sealed calls: the operands and keys are sealed, one operand is flipped at rest with ``fhe_flip_bit``, then
+    hmult_sealed (rescale)  ->  log2(row) x [ rotate_sealed  ->  seal_verify of both summands, modadd_checked, seal of the sum ]
+and per trial the tool prints how many words of the final ciphertext differ from the clean run's, how many flag words were raised
+anywhere in the chain, and whether the fault was detected.  The operands are uniformly random residues, not encryptions: the tool
+measures detection, it decrypts nothing.  Unlike the reference, the bits flipped in one word are distinct, so that every trial with
+a flip changes memory.  Trial 0 flips nothing (control).  The product has L - 1 limbs, so the rotation rounds run on a second plan
+over the remaining primes.  Exit status 1 when a trial with at least one flip was not detected.
+
+python -m fhe_reliability_gpu_amd.tools.flip_coverage [--trials 32] [--num-symbols 1] [--bits-per-symbol 1] [--logn 14] [--row 8] [--seed 1]"""
+import argparse
+import sys
+
+import numpy as np
+
+import fhe_reliability_gpu_amd as F
+from fhe_reliability_gpu_amd._lib import check, lib
+
+PLAIN_MODULUS = 65537
+L, K, DNUM = 4, 2, 2
+
+
+def nonzero(flags):
+    """raised flag words of a (nested) flag dictionary or array"""
+    if flags is None:
+        return 0
+    if isinstance(flags, dict):
+        return sum(nonzero(v) for v in flags.values())
+    return int(np.count_nonzero(flags))
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--trials", type=int, default=32)
+    ap.add_argument("--num-symbols", type=int, default=1)
+    ap.add_argument("--bits-per-symbol", type=int, default=1)
+    ap.add_argument("--logn", type=int, default=14)
+    ap.add_argument("--row", type=int, default=8, help="slots summed by the rotate-and-add rounds (a power of two)")
+    ap.add_argument("--seed", type=int, default=1)
+    a = ap.parse_args()
+    if a.row < 1 or a.row & (a.row - 1) or not 1 <= a.bits_per_symbol <= 64 or a.num_symbols < 0:
+        ap.error("row is a power of two, bits-per-symbol 1..64, num-symbols >= 0")
+    eng = F.Engine(0)
+    N, R = 1 << a.logn, L - 1
+    qs = F.create_moduli(N, [50] * (L + K))
+    rng = np.random.default_rng(a.seed)
+    t = eng.tables(a.logn, qs)
+    ks, ab = F.KeySwitch(eng, t, L, K, DNUM), F.Abft(eng, t)
+    ks.set_plain_modulus(PLAIN_MODULUS)
+    # the level below: the product's primes and the special ones
+    qs2 = qs[:R] + qs[L:]
+    t2 = eng.tables(a.logn, qs2)
+    ks2, ab2 = F.KeySwitch(eng, t2, R, K, DNUM), F.Abft(eng, t2)
+    ks2.set_plain_modulus(PLAIN_MODULUS)
+    poly = lambda moduli: np.stack([rng.integers(0, q, N, dtype=np.uint64) for q in moduli])
+    key = lambda moduli: np.stack([np.stack([poly(moduli) for _ in range(2)]) for _ in range(DNUM)])
+    ct_a, ct_b = np.stack([poly(qs[:L]), poly(qs[:L])]), np.stack([poly(qs[:L]), poly(qs[:L])])
+    rounds = a.row.bit_length() - 1
+    elts = [pow(5, 1 << r, 2 * N) for r in range(rounds)]
+    d_b, d_rlk = eng.upload(ct_b), eng.upload(key(qs))
+    d_gk = [eng.upload(key(qs2)) for _ in elts]
+    # seals, taken once of the clean data: what travels with the ciphertexts and keys
+    s_b = t.seal(d_b, limbs=L, n_poly=2)
+    s_rlk, s_gk = ks.seal_key(d_rlk), [ks2.seal_key(g) for g in d_gk]
+    s_a = t.seal(eng.upload(ct_a), limbs=L, n_poly=2)
+    part = lambda d, i, limbs: _view(eng, d, i * limbs * N, limbs * N)
+    seal_part = lambda s, i, limbs: _view(eng, s, i * limbs * 2, limbs * 2)
+
+    def chain(d_a):
+        """the sealed chain on operand d_a (sealed as s_a); returns the final parts and the raised flag words"""
+        raised = 0
+        o0, o1, so, fl = ks.hmult_sealed(part(d_a, 0, L), part(d_a, 1, L), part(d_b, 0, L), part(d_b, 1, L), d_rlk, ab,
+                                         seals=[seal_part(s_a, 0, L), seal_part(s_a, 1, L), seal_part(s_b, 0, L), seal_part(s_b, 1, L)], key_seal=s_rlk)
+        raised += nonzero(fl)
+        c, sc = [o0, o1], list(so)
+        for elt, gk, sgk in zip(elts, d_gk, s_gk):
+            r0, r1, sr, fl = ks2.rotate_sealed(c[0], c[1], elt, gk, ab2, seals=sc, key_seal=sgk)
+            raised += nonzero(fl)
+            for h, (rot, srot) in enumerate(((r0, sr[0]), (r1, sr[1]))):
+                raised += nonzero(t2.seal_verify(c[h], sc[h], limbs=R)) + nonzero(t2.seal_verify(rot, srot, limbs=R))
+                raised += nonzero(t2.modadd_checked(c[h], c[h], rot, limbs=R))
+                sc[h] = t2.seal(c[h], limbs=R)
+        return np.concatenate([c[0].download().reshape(-1), c[1].download().reshape(-1)]), raised
+
+    clean, raised = chain(eng.upload(ct_a))
+    assert raised == 0, "the clean chain raised a flag"
+    print(f"N = 2^{a.logn}, L = {L}, K = {K}, dnum = {DNUM}, plain modulus {PLAIN_MODULUS}; {rounds} rotate-and-add rounds; "
+          f"{a.num_symbols} symbols x {a.bits_per_symbol} bits per trial")
+    missed = 0
+    for trial in range(a.trials):
+        d_a = eng.upload(ct_a)
+        n_sym = 0 if trial == 0 else a.num_symbols
+        for idx in rng.integers(0, ct_a.size, n_sym):
+            for bit in rng.choice(64, a.bits_per_symbol, replace=False):
+                check(lib.fhe_flip_bit(eng._h, d_a.ptr, int(idx), int(bit), None))
+        flipped = int(np.count_nonzero(d_a.download().reshape(-1) != ct_a.reshape(-1)))
+        out, raised = chain(d_a)
+        corrupted = int(np.count_nonzero(out != clean))
+        detected = raised > 0
+        missed += flipped > 0 and not detected
+        assert flipped > 0 or (corrupted == 0 and not detected), "the control trial differs from the clean run"
+        print(f"trial {trial:3d}: flipped words {flipped:3d}, corrupted output words {corrupted:7d} of {out.size}, raised flag words {raised:4d}, "
+              f"detected {'yes' if detected else 'no'}", flush=True)
+    eng.check()
+    print(f"summary: {a.trials} trials, {missed} with a flip and no flag")
+    return 1 if missed else 0
+
+
+class _View:
+    """words [off, off + n) of a device array, as the wrappers take operands (a pointer; nothing is owned)"""
+
+    def __init__(self, eng, d, off, n):
+        import ctypes as C
+        self.eng, self.ptr, self.size, self.shape, self._keep = eng, C.c_void_p(d.ptr.value + 8 * off), n, (n,), d
+
+
+def _view(eng, d, off, n):
+    return _View(eng, d, off, n)
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -573,8 +573,9 @@ int fhe_ctx_inject_fault_baseconv(fhe_ctx *ctx, int point, int unit, long long c
  * Localisation: a fault at stage s, unit u raises the flag of (s, u) and no other flag of the call; every later stage is consistent
  * with the input it was handed.  Bit 4 marks words that could not be checked (only caller-supplied words can be non-canonical: the
  * digits' own limbs of d_c, the key, the addends); their output words are still the unchecked call's.
- * Not covered: faults already in the inputs; a word corrupted in memory between one stage's store and the next stage's load (each
- * check starts from the registers its stage loaded); the Galois permutation of the checked rotation; operands raising bit 4.
+ * Not covered: faults already in the inputs (the sealed calls at the end of this header verify them at rest, these calls still do
+ * not); a word corrupted in memory between one stage's store and the next stage's load (each check starts from the registers its
+ * stage loaded); the Galois permutation of the checked rotation; operands raising bit 4.
  * Scope: a sharded plan returns FHE_ERR_INVALID; a plan with a plain modulus (BGV) FHE_ERR_UNSUPPORTED; a context with ntt_mode = 1,
  * ntt_resident or ntt_packed set, or N < 2^5, FHE_ERR_UNSUPPORTED.  The rescale and the homomorphic multiply have checked forms of
  * their own below, hoisted rotations, the Galois permutation and the BSGS product further down; BGV plans (plain modulus) have
@@ -622,7 +623,7 @@ int fhe_ctx_inject_fault_keyswitch(fhe_ctx *ctx, int stage, int point, int unit,
  *   stage 2  forward transform of the residues                 ABFT: 1                                               [n_parts][R]
  *   stage 3  (c - delta) q_last^-1                             bits 1 / 2 / 4 as stage 7 of the checked key switch   [n_parts][R]
  * Localisation as for the checked key switch: a fault at (stage, unit) raises that word and no other; later stages are consistent
- * with what they were handed.  Not covered: faults already in the input; a word corrupted in memory between one stage's store
+ * with what they were handed.  Not covered: faults already in the input (see fhe_hmult_sealed); a word corrupted in memory between one stage's store
  * and the next stage's load; operands raising bit 4.
  * Scope: the checked key switch's -- a sharded plan FHE_ERR_INVALID; a plan with a plain modulus (BGV) FHE_ERR_UNSUPPORTED (its
  * forms are fhe_bgv_mod_switch_checked / fhe_bgv_hmult_checked); ntt_mode = 1, ntt_resident, ntt_packed, a single-pass hook or
@@ -796,7 +797,8 @@ int fhe_scalar_affine_checked(fhe_ctx *ctx, uint64_t *d_c, const uint64_t *d_a, 
  * (the CKKS-form total), out[9] = offset of stage 10, out[10] = total, out[11] = 0 (reserved).  Stages 9 and 10: unit = half * K + k
  * / half * L + j; bit 1 identity, 2 window, 4 operand >= q -- never raised on a clean run, both inputs are stage outputs.
  * Localisation: as for the checked key switch, a fault at (stage, unit) raises that word and no other.
- * Not covered: what the checked key switch does not cover; faults in the plan's scalars t^-1 mod p_k, t mod q_j.
+ * Not covered: what the checked key switch does not cover (inputs at rest: fhe_hmult_sealed / fhe_rotate_sealed); faults in the plan's
+ * scalars t^-1 mod p_k, t mod q_j.
  * Scope: a plan WITHOUT a plain modulus returns FHE_ERR_INVALID (use the calls above); otherwise the checked key switch's -- a
  * sharded plan FHE_ERR_INVALID, ntt_mode = 1, ntt_resident, ntt_packed, a single-pass hook or N < 2^5 FHE_ERR_UNSUPPORTED, a
  * detector made for another table set FHE_ERR_INVALID -- and L, K <= 64 (FHE_ERR_UNSUPPORTED).  Still without a checked form:
@@ -840,6 +842,70 @@ int fhe_bgv_hmult_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint
  *   _bgv_mod_switch: stages 0-3 as fhe_ctx_inject_fault_rescale; stages 4 and 5 as stages 9 and 10. */
 int fhe_ctx_inject_fault_bgv_keyswitch(fhe_ctx *ctx, int stage, int point, int unit, long long coeff, int bit);
 int fhe_ctx_inject_fault_bgv_mod_switch(fhe_ctx *ctx, int stage, int point, int unit, long long coeff, int bit);
+
+/* ---- seals: operands protected at rest, sealed multiply and rotation ---------------------------------------------
+ * Every checked call above ends its coverage note with "faults already in the inputs": a word that is wrong in memory before the
+ * call loads it -- the bit flips of reliability_test/dotprod_test.cu:31-61 in the limbs of an encrypted operand, a word that rots
+ * between one call's store and the next call's load, a flipped word of a switching key -- is a consistent input to every stage and
+ * raises nothing.  A seal is an integrity record that travels with a ciphertext or key between calls: per row of N words of limb l,
+ * with p = 2^61 - 1 (prime),
+ *     S0 = sum_j x_j mod p,      S1 = sum_j (j + 1) x_j mod p,      and the window x_j < q_l,
+ * stored as uint64_t [rows][2] = {S0, S1}, canonical in [0, p) (p itself is 0); rows in [poly][limb] order like fhe_modadd_checked.
+ * Not the 2^32 - 1 fold of the checked products: that modulus is composite and 2^32 = 1 in it, so +2^b - 2^(b+32) inside one word
+ * is invisible, and the reference flips several bits per symbol.  With p prime and every canonical word below q < 2^61 <= p:
+ *   a change confined to one word of a row is caught with certainty (the new word is >= q: window; else 0 < |d| < p moves S0);
+ *   a change confined to two words j1 != j2 is caught with certainty (d1 + d2 = 0 and (j1 - j2) d1 = 0 force d1 = 0, 0 < |j1 - j2| < p);
+ *   wider corruption escapes with probability about 2^-61 per sum on random data.
+ * fhe_seal writes the seals of d_words = [n_poly][limbs][N] (limb i on modulus start_idx + i) to d_seal = [n_poly * limbs][2].
+ * fhe_seal_verify sweeps the same rows and ORs into d_flags[row] (uint32, cleared by the call on `stream`): bit 1 a sum differs from
+ * d_seal[row], bit 2 some word >= q_l.  n_poly == 0 or limbs == 0 is a no-op; a range outside the table set FHE_ERR_INVALID; d_words
+ * must be 16-byte aligned (FHE_ERR_INVALID), N >= 2.  Integer arithmetic modulo p throughout: the seal does not depend on how the
+ * rows are spread over the chip, reruns give identical seals.  The chunks' partial sums live in the context (grown on demand): one
+ * seal call or sealed composite at a time per context.
+ * Test hook: fhe_ctx_inject_fault_seal(row, coeff, bit) flips bit `bit` of word `coeff` of row `row` of the next fhe_seal or
+ * fhe_seal_verify on this context in the register, after the load and before it is summed and held against q: memory stays clean.
+ * One shot, taken by that call whatever its outcome; a row or word outside the call returns FHE_ERR_INVALID from it, with nothing
+ * launched; row < 0 clears.  The sealed composites below neither take nor honour it. */
+int fhe_seal(fhe_ctx *ctx, uint64_t *d_seal, const uint64_t *d_words, const fhe_ntt_tables *t, size_t n_poly, size_t limbs, size_t start_idx,
+             void *stream);
+int fhe_seal_verify(fhe_ctx *ctx, const uint64_t *d_words, const uint64_t *d_seal, const fhe_ntt_tables *t, size_t n_poly, size_t limbs,
+                    size_t start_idx, uint32_t *d_flags, void *stream);
+int fhe_ctx_inject_fault_seal(fhe_ctx *ctx, int row, long long coeff, int bit);
+/* The checked multiply and the checked rotation with their operands protected at rest.  One name for both schemes: on a plan with a
+ * plain modulus the call runs fhe_bgv_hmult_checked / fhe_bgv_rotate_checked, otherwise fhe_hmult_checked / fhe_rotate_checked.  Order
+ * of work, all on `stream`: verify every given seal, run the checked call unchanged, seal both outputs.  Arguments are the checked
+ * call's, plus
+ *   d_seal_in   HOST array of device pointers to the seals of a0, a1, b0, b1 (multiply) / c0, c1 (rotation), each [L][2]; an entry,
+ *               or the array, may be NULL: that operand is unsealed and not verified, its flag words stay 0
+ *   d_seal_key  seal of the relinearisation / Galois key, [dnum][2][L + K][2] over the plan's whole table set
+ *               (fhe_seal(key, t, dnum * 2, L + K, 0)); may be NULL
+ *   d_seal_out  HOST array of two device pointers, [L][2] each ([L - 1][2] after a rescale): the seals of d_out0 and d_out1 as the
+ *               call stored them; an entry, or the array, may be NULL
+ * Flags, one buffer which the call clears on `stream`:
+ *   fhe_hmult_sealed_layout   out[0..3] the rows of a0, a1, b0, b1 ([L] each), out[4] the key's rows [dnum][2][L + K], out[5] the
+ *                             checked call's own block, exactly fhe_hmult_checked_layout's / fhe_bgv_hmult_checked_layout's, out[6]
+ *                             total, out[7] = 0 (reserved)
+ *   fhe_rotate_sealed_layout  out[0..1] the rows of c0, c1, out[2] the key's rows, out[3] the checked call's block
+ *                             (fhe_keyswitch_checked_layout / fhe_bgv_keyswitch_checked_layout), out[4] total, out[5] = 0
+ * Input and key words hold the bits of fhe_seal_verify.  A raised input flag does not stop the call: the caller reads the flags
+ * afterwards, as everywhere else -- the flags of the checked block and the output seals are then meaningless, the call computed on a
+ * corrupted operand and sealed what came out.  The output words are fhe_hmult's / fhe_rotate's on the same plan, bit for bit.
+ * Scope, statuses, aliasing rules and test hooks are the underlying checked call's; a call outside its scope returns its status
+ * with nothing launched.  A status from the checked call after the verifying launches (a refused hook) leaves the input and key flags
+ * written and no output seal.  Every buffer must be 16-byte aligned (FHE_ERR_INVALID).
+ * Still not covered: the verifying read and the consuming read are two loads, so a transient fault on the second one alone is not
+ * seen; neither is a word corrupted between the checked call's final store and the sealing launch's load.  Taking the digest from
+ * the register about to be stored, and verifying on the consumer's own load, are later changes.  Sharded plans, the hoisted
+ * rotations and the BSGS product have no sealed form. */
+int fhe_hmult_sealed_layout(const fhe_keyswitch *p, int rescale, int out[8]);
+int fhe_hmult_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_a0, const uint64_t *d_a1,
+                     const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a,
+                     const uint64_t *const *d_seal_in /* [4] */, const uint64_t *d_seal_key, uint64_t *const *d_seal_out /* [2] */,
+                     uint32_t *d_flags, void *stream);
+int fhe_rotate_sealed_layout(const fhe_keyswitch *p, int out[6]);
+int fhe_rotate_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0, const uint64_t *d_c1,
+                      uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, const uint64_t *const *d_seal_in /* [2] */,
+                      const uint64_t *d_seal_key, uint64_t *const *d_seal_out /* [2] */, uint32_t *d_flags, void *stream);
 
 /* ---- fault injection ---------------------------------------------------------------- */
 /* _flip_bit_kernel<<<1,1>>> (reliability_test/dotprod_test.cu:31-33,55): data[idx] ^= 1 << bit */
