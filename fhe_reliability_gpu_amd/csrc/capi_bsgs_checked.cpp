@@ -34,7 +34,7 @@ BmcLayout bmc_layout(const fhe_keyswitch *p, size_t n1, size_t n2)
     l.off[1] = 2 * L;
     l.off[2] = 4 * L;
     l.off[3] = 5 * L;
-    l.giant = 5 * L + ksc_layout(p).total;
+    l.giant = 5 * L + ksc_layout(p, KsForm::CKKS).total;
     const unsigned long long total = baby + (unsigned long long)n2 * l.giant;
     l.baby = (int)baby;
     l.total = total > (unsigned long long)INT_MAX ? -1 : (int)total;
@@ -97,7 +97,7 @@ int fhe_bsgs_matvec_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, ui
     // the one-shot hooks of the steps this call runs belong to it whatever its outcome: all are taken here
     const StagedFault hf = ctx->hrc_fault.take(), kf = ctx->ksc_fault.take(), bf = ctx->bsgs_fault.take();
     const GaloisFault gf = ctx->gal_fault.take();
-    int rc = ksc_scope(ctx, p, a, d_flags);
+    int rc = ksc_scope(ctx, p, a, d_flags, KsForm::CKKS, false);
     if (rc) return rc;
     if (!d_out0 || !d_out1 || !d_c0 || !d_c1 || !d_diags || !bsgs_shape_ok(n1, n2)) return fail(FHE_ERR_INVALID, "bad arguments");
     if ((n1 > 1 && (!baby_elts || !d_baby_keys_prepared)) || (n2 > 1 && (!giant_elts || !d_giant_keys))) return fail(FHE_ERR_INVALID, "null argument");
@@ -124,7 +124,7 @@ int fhe_bsgs_matvec_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, ui
     if ((rc = galois_fault_check(gf, (size_t)2 * L, logn))) return rc;
     {
         KscHook probe;
-        if ((rc = ksc_hook(p, kf, p->acc.as<u64>(), true, true, probe))) return rc;
+        if ((rc = ksc_hook(p, KsForm::CKKS, kf, p->acc.as<u64>(), true, true, probe))) return rc;
     }
     if (bf.stage >= 0) {
         if ((size_t)bf.block >= n2 || (bf.stage == 1 && bf.block == 0)) return fail(FHE_ERR_INVALID, "fault giant step outside the call (the accumulate starts at g = 1)");
@@ -169,7 +169,7 @@ int fhe_bsgs_matvec_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, ui
         const PointwiseArgs pa{tmp, d_out0, tmp, lp, 0u, (u32)L, (u32)L, (u32)L, logn};
         if ((e = launch_modadd_checked(st, pa, bc_check(bf.at((int)g, 1), block + lay.off[2]))) != hipSuccess) return hip_fail(e, "launch_modadd_checked");
         // ---- (out0, out1) = key switch of sigma(s1) + (t0, out1)
-        if ((rc = keyswitch_checked(p, d_out0, d_out1, tmp + part, d_giant_keys[g - 1], tmp, d_out1, a, block + lay.off[3], st, g == 1 ? kf : StagedFault{}))) return rc;
+        if ((rc = keyswitch_checked(p, KsForm::CKKS, d_out0, d_out1, tmp + part, d_giant_keys[g - 1], tmp, d_out1, a, block + lay.off[3], st, g == 1 ? kf : StagedFault{}))) return rc;
     }
     return FHE_OK;
 }

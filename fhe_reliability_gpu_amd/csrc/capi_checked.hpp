@@ -1,17 +1,29 @@
 // capi_checked.hpp -- what the stage-by-stage checked composites share (capi_keyswitch_checked.cpp: key switch, relinearisation,
-// rotation; capi_hmult_checked.cpp: rescale, homomorphic multiply; capi_rotate_hoisted_checked.cpp: the Galois permutation and
-// hoisted rotations; capi_bsgs_checked.cpp: the BSGS matrix-vector product and the checked add; capi_bgv_checked.cpp: the BGV forms
-// of key switch, mod switch and multiply, and the checked scalar multiply): the flag layout of the key switch,
-// the checked-transform helper over the plan's scratch sums, and the checked key switch itself, whole and as its two halves.  The
-// one-shot fault records are those of fault_hook.hpp.
+// rotation; capi_hmult_checked.cpp: rescale / mod switch, homomorphic multiply; capi_rotate_hoisted_checked.cpp: the Galois
+// permutation and hoisted rotations; capi_bsgs_checked.cpp: the BSGS matrix-vector product and the checked add;
+// capi_bgv_checked.cpp: the checked scalar multiply; capi_seal.cpp: the sealed multiply and rotation): the flag layouts, the
+// checked-transform helper over the plan's scratch sums, the scope and hook checks, and the checked key switch and rescale
+// themselves.  The one-shot fault records are those of fault_hook.hpp.
+//
+// Each composite exists once and takes its form (KsForm) as a parameter: the CKKS form, or the BGV form of a plan with a plain
+// modulus t, which is the same launch list plus two word-wise scalar stages (key switch: 9 and 10, mod switch: 4 and 5; numbered
+// after the stages both forms share, 8 being the hoisted rotations' permutation).  The entry point chooses the form and names
+// the context's hook record it takes -- fhe_*_checked the CKKS form, fhe_bgv_*_checked the BGV form, the sealed calls by the
+// plan's plain modulus -- and the plan must agree with it (ksc_scope); the hoisted rotations and the BSGS product run the CKKS form.
 #pragma once
 #include "capi_internal.hpp"
 #include "galois_check.hpp"
 
+enum class KsForm { CKKS, BGV };
+// the context's record an entry point takes its key-switch or rescale hook from: each form has records of its own
+using KsHookSlot = StagedFault fhe_ctx::*;
+
+// offsets by stage number; a stage the form does not have (8; 9 and 10 in the CKKS form) has no words
 struct KscLayout {
-    int off[8], total;
+    int off[11], total;
+    int units(int stage) const { return (stage == 10 ? total : off[stage + 1]) - off[stage]; }
 };
-KscLayout ksc_layout(const fhe_keyswitch *p);
+KscLayout ksc_layout(const fhe_keyswitch *p, KsForm form);
 
 // slots of the plan's scratch sums, one per (polynomial, row) a stage's transforms address.  Key switch: stage 2 the dnum x M rows of
 // ext, stage 4 rows L .. M-1 of both halves of acc ([2][M]: up to slot 2 M - 1), stage 6 [2][L], stage 0 [L].  Rescale: the residues
@@ -83,17 +95,21 @@ struct KscNtt {
 int ksc_prepare(fhe_keyswitch *p);
 // the checked transforms of one direction; the detector's partial sums live in the plan (ksc_prepare): the fhe_abft is only read
 KscNtt ksc_ntt(const fhe_keyswitch *p, const fhe_abft *a, hipStream_t st, bool inverse);
-// scope of every stage-by-stage checked call: the plan, the detector and the context's transform variants.  bgv: the scope of the
-// BGV calls -- the same rules, but the plan must HAVE a plain modulus (FHE_ERR_INVALID without one)
-int ksc_scope(const fhe_ctx *ctx, const fhe_keyswitch *p, const fhe_abft *a, const uint32_t *d_flags, bool bgv = false);
-int keyswitch_checked(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk, const uint64_t *d_add0,
-                      const uint64_t *d_add1, const fhe_abft *a, uint32_t *d_flags, hipStream_t st, const StagedFault &ft);
+// scope of every stage-by-stage checked call: the plan, the detector and the context's transform variants.  The CKKS form refuses
+// a plan with a plain modulus (FHE_ERR_UNSUPPORTED), the BGV form one without (FHE_ERR_INVALID) or with more than 64 limbs per
+// scalar stage; mod_switch: the call drops a prime
+int ksc_scope(const fhe_ctx *ctx, const fhe_keyswitch *p, const fhe_abft *a, const uint32_t *d_flags, KsForm form, bool mod_switch);
+int keyswitch_checked(fhe_keyswitch *p, KsForm form, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk,
+                      const uint64_t *d_add0, const uint64_t *d_add1, const fhe_abft *a, uint32_t *d_flags, hipStream_t st, const StagedFault &ft);
+// the whole rotation behind an entry point (fhe_rotate_checked, fhe_bgv_rotate_checked, fhe_rotate_sealed)
+int rotate_checked(KsForm form, KsHookSlot hook, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0,
+                   const uint64_t *d_c1, uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, uint32_t *d_flags, void *stream);
 
 // ---- the checked key switch as two halves (keyswitch_checked = front + back; hoisted rotations: one front, a back per element)
-// where each stage's flag words go: s[0..7] the stages of the key switch, s[8] the Galois permutation of a hoisted rotation.  The
-// caller clears them
+// where each stage's flag words go: s[0..7] the stages of the key switch, s[8] the Galois permutation of a hoisted rotation, s[9]
+// and s[10] the scalar stages of the BGV form (null in the CKKS form).  The caller clears them
 struct KscFlags {
-    u32 *s[9];
+    u32 *s[11];
 };
 // a key-switch fault checked against the plan: the word a transform stage flips between its two launches, or the fault of a residue
 // stage rebased to the launch it hits (block = the conversion job of stages 1 and 5: the digit, the half; unit = the unit inside
@@ -102,7 +118,7 @@ struct KscHook {
     StagedFault f;
     u64 *flip = nullptr;
 };
-int ksc_hook(const fhe_keyswitch *p, const StagedFault &ft, u64 *acc, bool has_add0, bool has_add1, KscHook &h);
+int ksc_hook(const fhe_keyswitch *p, KsForm form, const StagedFault &ft, u64 *acc, bool has_add0, bool has_add1, KscHook &h);
 // the permutation step of a hoisted rotation's back half: the sums ([2][M][N]) into acc_to, c0 ([L][N]) into c0_to
 struct KscPerm {
     u32 galois_elt;
@@ -110,19 +126,9 @@ struct KscPerm {
     u64 *acc_to, *c0_to;
     GaloisFault fault;       // unit = half * M + row for the sums, 2 M + l for c0
 };
-// the BGV hand-over of ksc_back and rescale_checked (plans with a plain modulus t): where the flag words of the two word-wise scalar
-// stages go -- `inv`: times t^-1 on the limbs about to be converted, in coefficient form (key switch stage 9 [2][K], mod switch stage
-// 4 [n_parts]); `mul`: times t on the converted limbs (stage 10 [2][L], stage 5 [n_parts][L - 1]) -- and their fault: f.stage = 0
-// addresses `inv`, 1 `mul`, < 0 none (the caller has checked unit, coefficient and point).  Without
-// a hand-over (nullptr) both functions launch exactly the CKKS-form list.
-struct BgvStages {
-    u32 *inv, *mul;
-    StagedFault f;
-};
 int ksc_front(fhe_keyswitch *p, const uint64_t *d_c, const fhe_abft *a, const KscFlags &fl, hipStream_t st, const KscHook &h);
 int ksc_back(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk, const uint64_t *d_add0,
-             const uint64_t *d_add1, const fhe_abft *a, const KscFlags &fl, hipStream_t st, const KscHook &h, const KscPerm *perm,
-             const BgvStages *bgv = nullptr);
+             const uint64_t *d_add1, const fhe_abft *a, const KscFlags &fl, hipStream_t st, const KscHook &h, const KscPerm *perm, KsForm form);
 
 // defined in capi_bgv_checked.cpp
 // one scalar stage: `limbs` rows from data on, of n_poly polynomials poly_stride rows apart (row l of polynomial i at data + (i
@@ -132,15 +138,21 @@ int bgv_scalar_stage(const fhe_keyswitch *p, hipStream_t st, u64 *data, const u6
 
 // defined in capi_hmult_checked.cpp
 struct RscLayout {
-    int off[4], total;
+    int off[6], total;
+    int units(int stage) const { return (stage == 5 ? total : off[stage + 1]) - off[stage]; }
 };
-RscLayout rsc_layout(const fhe_keyswitch *p, size_t n_parts);
+RscLayout rsc_layout(const fhe_keyswitch *p, size_t n_parts, KsForm form);
 // the rescale's fault checked against the plan and the number of parts; *flip = the word a transform stage flips
-int rsc_hook(const fhe_keyswitch *p, const StagedFault &ft, size_t n_parts, u64 **flip);
+int rsc_hook(const fhe_keyswitch *p, KsForm form, const StagedFault &ft, size_t n_parts, u64 **flip);
 // d_in = [n_parts][L][N], outs[i] = [L - 1][N]; the caller has checked scope, arguments and overlap.  Clears the lay.total words
-// of stages 0-3 at d_flags and, with a hand-over, the scalar stages' words ([n_parts], [n_parts][L - 1])
-int rescale_checked(fhe_keyswitch *p, uint64_t *const *outs, const uint64_t *d_in, size_t n_parts, const fhe_abft *a, uint32_t *d_flags, hipStream_t st,
-                    const StagedFault &ft, const BgvStages *bgv = nullptr);
+// at d_flags
+int rescale_checked(fhe_keyswitch *p, KsForm form, uint64_t *const *outs, const uint64_t *d_in, size_t n_parts, const fhe_abft *a, uint32_t *d_flags,
+                    hipStream_t st, const StagedFault &ft);
+// the multiply behind an entry point (fhe_hmult_checked, fhe_bgv_hmult_checked, fhe_hmult_sealed) and its layout
+int hmult_checked_layout(const fhe_keyswitch *p, KsForm form, int rescale, int out[4]);
+int hmult_checked(KsForm form, KsHookSlot ks_hook, KsHookSlot rs_hook, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1,
+                  const uint64_t *d_a0, const uint64_t *d_a1, const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale,
+                  const fhe_abft *a, uint32_t *d_flags, void *stream);
 
 // defined in capi_rotate_hoisted_checked.cpp
 // the checked permutation of up to two row ranges that share one flags array (units counted through the segments in order, the

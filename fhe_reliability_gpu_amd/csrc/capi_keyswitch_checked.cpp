@@ -15,17 +15,24 @@
 //   7  tail (acc - conv) P^-1 (+ addends)                                                                (launch_sub_scale_checked)
 // keyswitch_checked = ksc_front (stages 0-2) + ksc_back (stages 3-7); the hoisted rotations of capi_rotate_hoisted_checked.cpp run the
 // front once and the back once per Galois element, with the checked Galois permutation between stages 3 and 4.
+// The BGV form (plans with a plain modulus t; fhe_bgv_*_checked) removes t [acc t^-1]_P instead of [acc]_P, so that what is removed
+// vanishes modulo t: two word-wise scalar stages more, both in place and both launch_scalar_affine_checked (bgv_scalar_stage):
+//   9  special limbs of both halves of the sums times t^-1 mod p_k (coefficient form)                    between stages 4 and 5
+//  10  converted limbs of both halves times t mod q_j (coefficient form)                                 between stages 5 and 6
+// The unchecked call has t riding on the fused tail (RowEpiArgs::pre) or a launch of its own.  The CKKS entry points refuse a
+// plan with a plain modulus, the BGV ones a plan without; each form has a hook of its own and neither takes nor honours the other's.
 // Each transform stage ends with launch_compare_sums on its units.  Every stage yields canonical residues and canonical residues are
 // unique, so the outputs are the unchecked call's words whatever its launch list was.
 #include "capi_checked.hpp"
 #include "keyswitch_check.hpp"
+#include "scalar_check.hpp"
 
-KscLayout ksc_layout(const fhe_keyswitch *p)
+KscLayout ksc_layout(const fhe_keyswitch *p, KsForm form)
 {
-    const int L = p->L, K = p->K, M = L + K, d = p->dnum;
-    const int n[8] = {L, d * M, d * M, 2 * M, 2 * K, 2 * (K + L), 2 * L, 2 * L};
+    const int L = p->L, K = p->K, M = L + K, d = p->dnum, bgv = form == KsForm::BGV;
+    const int n[11] = {L, d * M, d * M, 2 * M, 2 * K, 2 * (K + L), 2 * L, 2 * L, 0, bgv * 2 * K, bgv * 2 * L};
     KscLayout l{};
-    for (int s = 0; s < 8; s++) {
+    for (int s = 0; s < 11; s++) {
         l.off[s] = l.total;
         l.total += n[s];
     }
@@ -58,19 +65,18 @@ int ksc_prepare(fhe_keyswitch *p)
 
 // the test hook of one checked key switch, checked against the call before anything is launched: which word a transform stage flips
 // between its two launches, which check record a residue stage arms.  acc = the sums stages 4 and 5 work on
-int ksc_hook(const fhe_keyswitch *p, const StagedFault &ft, u64 *acc, bool has_add0, bool has_add1, KscHook &h)
+int ksc_hook(const fhe_keyswitch *p, KsForm form, const StagedFault &ft, u64 *acc, bool has_add0, bool has_add1, KscHook &h)
 {
     const int L = p->L, K = p->K, M = L + K, logn = p->log_n;
     const size_t N = (size_t)1 << logn;
-    const KscLayout lay = ksc_layout(p);
+    const KscLayout lay = ksc_layout(p, form);
     u64 *coef = p->coef.as<u64>(), *ext = p->ext.as<u64>(), *conv = p->conv.as<u64>();
     h = KscHook{};
     if (ft.stage < 0) return FHE_OK;
     h.f = ft;
     h.f.block = 0;
-    const bool tf = !(ft.stage & 1);      // a transform stage
-    const int units = (ft.stage == 7 ? lay.total : lay.off[ft.stage + 1]) - lay.off[ft.stage];
-    if (ft.unit >= units || (size_t)ft.coeff >= N) return fail(FHE_ERR_INVALID, "fault unit or coefficient outside the call");
+    const bool tf = ft.stage < 8 && !(ft.stage & 1);      // a transform stage
+    if (ft.unit >= lay.units(ft.stage) || (size_t)ft.coeff >= N) return fail(FHE_ERR_INVALID, "fault unit or coefficient outside the call");
     if (tf && logn < 13) return fail(FHE_ERR_UNSUPPORTED, "the transform stages' fault point lies between their two launches: two-launch sizes only (N >= 2^13)");
     const int u = ft.unit;
     switch (ft.stage) {
@@ -103,9 +109,13 @@ int ksc_hook(const fhe_keyswitch *p, const StagedFault &ft, u64 *acc, bool has_a
     case 3:
         if (ft.point < 0 || ft.point > 3) return fail(FHE_ERR_INVALID, "bad fault point");
         break;
-    default:
+    case 7:
         if (!ks_tail_point_exists(ft.point, u / L ? has_add1 : has_add0))
             return fail(FHE_ERR_UNSUPPORTED, "fault point 3 (the running sum) of the tail exists only on a half with an addend");
+        break;
+    default:      // 9, 10
+        if (!scalar_affine_point_exists(ft.point, false))
+            return fail(FHE_ERR_UNSUPPORTED, "fault point 3 (the running sum) does not exist on the BGV scalar stages: they have no addend");
         break;
     }
     return FHE_OK;
@@ -159,11 +169,11 @@ int ksc_front(fhe_keyswitch *p, const uint64_t *d_c, const fhe_abft *a, const Ks
 
 // stages 3-7 on the digits ksc_front left in the plan.  perm (hoisted rotations): between stages 3 and 4 the sums and perm->c0 go
 // through the checked Galois permutation (stage 8, flags fl.s[8]); stages 4-7 then run on the permuted sums with sigma(c0) as d_add0.
-// bgv (plans with a plain modulus t): the special limbs times t^-1 mod p_k between stages 4 and 5, the converted limbs times t mod q_j
-// between stages 5 and 6, so that the part the mod-down removes is t [acc t^-1]_P
+// BGV form: the special limbs times t^-1 mod p_k between stages 4 and 5 (stage 9), the converted limbs times t mod q_j between
+// stages 5 and 6 (stage 10), so that the part the mod-down removes is t [acc t^-1]_P
 int ksc_back(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk, const uint64_t *d_add0,
              const uint64_t *d_add1, const fhe_abft *a, const KscFlags &fl, hipStream_t st, const KscHook &h, const KscPerm *perm,
-             const BgvStages *bgv)
+             KsForm form)
 {
     const int L = p->L, K = p->K, M = L + K, logn = p->log_n;
     const size_t N = (size_t)1 << logn;
@@ -172,6 +182,7 @@ int ksc_back(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_
     int rc;
     hipError_t e;
     const KscNtt fwd = ksc_ntt(p, a, st, false), inv = ksc_ntt(p, a, st, true);
+    const bool bgv = form == KsForm::BGV;
 
     // ---- 3: inner product with the key
     {
@@ -192,8 +203,8 @@ int ksc_back(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_
     for (int hf = 0; hf < 2; hf++)
         if ((rc = inv.compare(fl.s[4] + hf * K, (u32)(hf * M + L), (u32)L, (u32)K, (u32)K))) return rc;
 
-    // ---- BGV: special limbs of both halves times t^-1, in place inside the sums
-    if (bgv && (rc = bgv_scalar_stage(p, st, acc + (size_t)L * N, p->t_inv_P.data(), (u32)L, (u32)K, 2, (u32)M, bgv->inv, bgv->f.at(0, 0)))) return rc;
+    // ---- 9 (BGV): special limbs of both halves times t^-1, in place inside the sums
+    if (bgv && (rc = bgv_scalar_stage(p, st, acc + (size_t)L * N, p->t_inv_P.data(), (u32)L, (u32)K, 2, (u32)M, fl.s[9], h.f.at(0, 9)))) return rc;
 
     // ---- 5: mod-down conversion P -> Q
     for (int hf = 0; hf < 2; hf++) {
@@ -202,8 +213,8 @@ int ksc_back(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_
         if ((e = launch_baseconv_exact_checked(st, cj, N)) != hipSuccess) return hip_fail(e, "launch_baseconv_exact_checked");
     }
 
-    // ---- BGV: converted limbs of both halves times t
-    if (bgv && (rc = bgv_scalar_stage(p, st, conv, p->t_mod_Q.data(), 0, (u32)L, 2, (u32)L, bgv->mul, bgv->f.at(0, 1)))) return rc;
+    // ---- 10 (BGV): converted limbs of both halves times t
+    if (bgv && (rc = bgv_scalar_stage(p, st, conv, p->t_mod_Q.data(), 0, (u32)L, 2, (u32)L, fl.s[10], h.f.at(0, 10)))) return rc;
 
     // ---- 6: forward transform of the converted limbs
     if ((rc = fwd.run({KscRows{conv, 0, 0, (u32)L, 2, (u32)L, 0}}, h.f.stage == 6 ? h.flip : nullptr, h.f.bit))) return rc;
@@ -215,23 +226,25 @@ int ksc_back(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_
     return FHE_OK;
 }
 
-int keyswitch_checked(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk,
+int keyswitch_checked(fhe_keyswitch *p, KsForm form, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk,
                       const uint64_t *d_add0, const uint64_t *d_add1, const fhe_abft *a, uint32_t *d_flags, hipStream_t st, const StagedFault &ft)
 {
     int rc;
     if ((rc = ksc_prepare(p))) return rc;
     KscHook h;
-    if ((rc = ksc_hook(p, ft, p->acc.as<u64>(), d_add0 != nullptr, d_add1 != nullptr, h))) return rc;
-    const KscLayout lay = ksc_layout(p);
+    if ((rc = ksc_hook(p, form, ft, p->acc.as<u64>(), d_add0 != nullptr, d_add1 != nullptr, h))) return rc;
+    const KscLayout lay = ksc_layout(p, form);
     KscFlags fl{};
-    for (int s = 0; s < 8; s++) fl.s[s] = d_flags + lay.off[s];
+    for (int s = 0; s < 11; s++)
+        if (lay.units(s)) fl.s[s] = d_flags + lay.off[s];
     HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)lay.total * sizeof(u32), st));
     if ((rc = ksc_front(p, d_c, a, fl, st, h))) return rc;
-    return ksc_back(p, d_out0, d_out1, d_c, d_evk, d_add0, d_add1, a, fl, st, h, nullptr);
+    return ksc_back(p, d_out0, d_out1, d_c, d_evk, d_add0, d_add1, a, fl, st, h, nullptr, form);
 }
 
-int ksc_scope(const fhe_ctx *ctx, const fhe_keyswitch *p, const fhe_abft *a, const uint32_t *d_flags, bool bgv)
+int ksc_scope(const fhe_ctx *ctx, const fhe_keyswitch *p, const fhe_abft *a, const uint32_t *d_flags, KsForm form, bool mod_switch)
 {
+    const bool bgv = form == KsForm::BGV;
     if (!p || !a || !d_flags) return fail(FHE_ERR_INVALID, "null argument");
     if (a->t != p->t) return fail(FHE_ERR_INVALID, "the detector was made for another table set than the plan's");
     if (p->sharded) return fail(FHE_ERR_INVALID, "a sharded plan has no checked key switch: the checked call runs the whole switch on one device");
@@ -240,59 +253,47 @@ int ksc_scope(const fhe_ctx *ctx, const fhe_keyswitch *p, const fhe_abft *a, con
     if (ctx->mode != 0 || ctx->resident || ctx->packed_on || ctx->only_pass >= 0 || !ntt_checked_supported(p->log_n))
         return fail(FHE_ERR_UNSUPPORTED, "the checked key switch runs the two-launch transforms: not with ntt_mode=1, ntt_resident, ntt_packed, a single-pass hook, or N < 2^5");
     if (!p->t->has_inverse) return fail(FHE_ERR_UNSUPPORTED, "table set has no inverse (twiddle or N not invertible)");
+    if (bgv && (p->L > SCALAR_MAX_LIMBS || p->K > SCALAR_MAX_LIMBS)) return fail(FHE_ERR_UNSUPPORTED, "the scalar stages take at most 64 limbs");
+    if (mod_switch && p->L < 2) return fail(FHE_ERR_INVALID, "no prime left to drop");
     return FHE_OK;
 }
 
-extern "C" {
+namespace {
 
-int fhe_keyswitch_checked_layout(const fhe_keyswitch *p, int out[10])
+int layout_call(const fhe_keyswitch *p, KsForm form, int *out)
 {
     if (!p || !out) return fail(FHE_ERR_INVALID, "null argument");
-    const KscLayout l = ksc_layout(p);
-    for (int s = 0; s < 8; s++) out[s] = l.off[s];
-    out[8] = l.total;
-    out[9] = 0;
+    const KscLayout l = ksc_layout(p, form);
+    int n = 0;
+    for (int s = 0; s < 11; s++)
+        if (s < 8 || l.units(s)) out[n++] = l.off[s];
+    out[n++] = l.total;
+    out[n] = 0;
     return FHE_OK;
 }
 
-int fhe_ctx_inject_fault_keyswitch(fhe_ctx *ctx, int stage, int point, int unit, long long coeff, int bit)
+// apply, and relinearisation (need_add: d_d0 and d_d1 are its addends, d_d2 what is switched)
+int apply_checked(KsForm form, KsHookSlot hook, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c,
+                  const uint64_t *d_evk, const uint64_t *d_add0, const uint64_t *d_add1, bool need_add, const fhe_abft *a, uint32_t *d_flags, void *stream)
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
-    return ctx->ksc_fault.arm(KSC_RULES, 0, stage, point, unit, coeff, bit) ? FHE_OK : fail(FHE_ERR_INVALID, "bad fault");
-}
-
-int fhe_keyswitch_apply_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk,
-                                const uint64_t *d_add0, const uint64_t *d_add1, const fhe_abft *a, uint32_t *d_flags, void *stream)
-{
-    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
-    const StagedFault ft = ctx->ksc_fault.take();      // one shot, whatever the outcome
-    int rc = ksc_scope(ctx, p, a, d_flags);
+    const StagedFault ft = (ctx->*hook).take();      // one shot, whatever the outcome
+    int rc = ksc_scope(ctx, p, a, d_flags, form, false);
     if (rc) return rc;
-    if (!d_out0 || !d_out1 || !d_c || !d_evk) return fail(FHE_ERR_INVALID, "null argument");
+    if (!d_out0 || !d_out1 || !d_c || !d_evk || (need_add && (!d_add0 || !d_add1))) return fail(FHE_ERR_INVALID, "null argument");
     if (d_out0 == d_out1) return fail(FHE_ERR_INVALID, "the two output parts must be distinct buffers");
     HIP_TRY(hipSetDevice(ctx->device));
-    return keyswitch_checked(p, d_out0, d_out1, d_c, d_evk, d_add0, d_add1, a, d_flags, pick(ctx, stream), ft);
+    return keyswitch_checked(p, form, d_out0, d_out1, d_c, d_evk, d_add0, d_add1, a, d_flags, pick(ctx, stream), ft);
 }
 
-int fhe_relinearize_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_d0, const uint64_t *d_d1,
-                            const uint64_t *d_d2, const uint64_t *d_relin_key, const fhe_abft *a, uint32_t *d_flags, void *stream)
-{
-    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
-    const StagedFault ft = ctx->ksc_fault.take();      // one shot, whatever the outcome
-    int rc = ksc_scope(ctx, p, a, d_flags);
-    if (rc) return rc;
-    if (!d_out0 || !d_out1 || !d_d0 || !d_d1 || !d_d2 || !d_relin_key) return fail(FHE_ERR_INVALID, "null argument");
-    if (d_out0 == d_out1) return fail(FHE_ERR_INVALID, "the two output parts must be distinct buffers");
-    HIP_TRY(hipSetDevice(ctx->device));
-    return keyswitch_checked(p, d_out0, d_out1, d_d2, d_relin_key, d_d0, d_d1, a, d_flags, pick(ctx, stream), ft);
-}
+} // namespace
 
-int fhe_rotate_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0, const uint64_t *d_c1,
-                       uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, uint32_t *d_flags, void *stream)
+int rotate_checked(KsForm form, KsHookSlot hook, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0,
+                   const uint64_t *d_c1, uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, uint32_t *d_flags, void *stream)
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
-    const StagedFault ft = ctx->ksc_fault.take();      // one shot, whatever the outcome
-    int rc = ksc_scope(ctx, p, a, d_flags);
+    const StagedFault ft = (ctx->*hook).take();      // one shot, whatever the outcome
+    int rc = ksc_scope(ctx, p, a, d_flags, form, false);
     if (rc) return rc;
     if (!d_out0 || !d_out1 || !d_c0 || !d_c1 || !d_galois_key) return fail(FHE_ERR_INVALID, "null argument");
     if (d_out0 == d_out1) return fail(FHE_ERR_INVALID, "the two output parts must be distinct buffers");
@@ -305,7 +306,54 @@ int fhe_rotate_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_
     u64 *sig1 = p->rot.as<u64>(), *sig0 = sig1 + (size_t)p->L * N;
     hipError_t e = launch_automorphism_ntt(st, sig1, d_c1, (u32)p->L, p->log_n, galois_elt, sig0, d_c0);
     if (e != hipSuccess) return hip_fail(e, "launch_automorphism_ntt");
-    return keyswitch_checked(p, d_out0, d_out1, sig1, d_galois_key, sig0, nullptr, a, d_flags, st, ft);
+    return keyswitch_checked(p, form, d_out0, d_out1, sig1, d_galois_key, sig0, nullptr, a, d_flags, st, ft);
+}
+
+extern "C" {
+
+int fhe_keyswitch_checked_layout(const fhe_keyswitch *p, int out[10]) { return layout_call(p, KsForm::CKKS, out); }
+int fhe_bgv_keyswitch_checked_layout(const fhe_keyswitch *p, int out[12]) { return layout_call(p, KsForm::BGV, out); }
+
+int fhe_ctx_inject_fault_keyswitch(fhe_ctx *ctx, int stage, int point, int unit, long long coeff, int bit)
+{
+    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
+    return ctx->ksc_fault.arm(KSC_RULES, 0, stage, point, unit, coeff, bit) ? FHE_OK : fail(FHE_ERR_INVALID, "bad fault");
+}
+
+int fhe_keyswitch_apply_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk,
+                                const uint64_t *d_add0, const uint64_t *d_add1, const fhe_abft *a, uint32_t *d_flags, void *stream)
+{
+    return apply_checked(KsForm::CKKS, &fhe_ctx::ksc_fault, ctx, p, d_out0, d_out1, d_c, d_evk, d_add0, d_add1, false, a, d_flags, stream);
+}
+
+int fhe_bgv_keyswitch_apply_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk,
+                                    const uint64_t *d_add0, const uint64_t *d_add1, const fhe_abft *a, uint32_t *d_flags, void *stream)
+{
+    return apply_checked(KsForm::BGV, &fhe_ctx::bgv_ksc_fault, ctx, p, d_out0, d_out1, d_c, d_evk, d_add0, d_add1, false, a, d_flags, stream);
+}
+
+int fhe_relinearize_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_d0, const uint64_t *d_d1,
+                            const uint64_t *d_d2, const uint64_t *d_relin_key, const fhe_abft *a, uint32_t *d_flags, void *stream)
+{
+    return apply_checked(KsForm::CKKS, &fhe_ctx::ksc_fault, ctx, p, d_out0, d_out1, d_d2, d_relin_key, d_d0, d_d1, true, a, d_flags, stream);
+}
+
+int fhe_bgv_relinearize_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_d0, const uint64_t *d_d1,
+                                const uint64_t *d_d2, const uint64_t *d_relin_key, const fhe_abft *a, uint32_t *d_flags, void *stream)
+{
+    return apply_checked(KsForm::BGV, &fhe_ctx::bgv_ksc_fault, ctx, p, d_out0, d_out1, d_d2, d_relin_key, d_d0, d_d1, true, a, d_flags, stream);
+}
+
+int fhe_rotate_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0, const uint64_t *d_c1,
+                       uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, uint32_t *d_flags, void *stream)
+{
+    return rotate_checked(KsForm::CKKS, &fhe_ctx::ksc_fault, ctx, p, d_out0, d_out1, d_c0, d_c1, galois_elt, d_galois_key, a, d_flags, stream);
+}
+
+int fhe_bgv_rotate_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0, const uint64_t *d_c1,
+                           uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, uint32_t *d_flags, void *stream)
+{
+    return rotate_checked(KsForm::BGV, &fhe_ctx::bgv_ksc_fault, ctx, p, d_out0, d_out1, d_c0, d_c1, galois_elt, d_galois_key, a, d_flags, stream);
 }
 
 } // extern "C"

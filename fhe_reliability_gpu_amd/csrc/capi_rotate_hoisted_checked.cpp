@@ -16,7 +16,7 @@
 HrcLayout hrc_layout(const fhe_keyswitch *p)
 {
     const int L = p->L, K = p->K, M = L + K;
-    const KscLayout k = ksc_layout(p);
+    const KscLayout k = ksc_layout(p, KsForm::CKKS);
     const int n[6] = {2 * M, 2 * M + L, 2 * K, 2 * (K + L), 2 * L, 2 * L};
     HrcLayout l{};
     for (int s = 0; s < 3; s++) l.shared[s] = k.off[s];
@@ -91,7 +91,7 @@ int hrc_prepare(fhe_keyswitch *p, const StagedFault &ft, size_t n_rot, HrcHook &
     if (ft.stage == 8) {
         h.gal = GaloisFault{ft.point, (u32)ft.unit, (u64)ft.coeff, ft.bit};
         if ((rc = galois_fault_check(h.gal, (size_t)2 * M + L, p->log_n))) return rc;
-    } else if ((rc = ksc_hook(p, ft, p->acc2.as<u64>(), true, false, h.hook))) {
+    } else if ((rc = ksc_hook(p, KsForm::CKKS, ft, p->acc2.as<u64>(), true, false, h.hook))) {
         return rc;
     }
     h.stage = ft.stage;
@@ -115,7 +115,7 @@ int hrc_run(fhe_keyswitch *p, uint64_t *const *d_out0, uint64_t *const *d_out1, 
         for (int i = 0; i < 6; i++) fl.s[stage_of[i]] = block + lay.rot[i];
         const bool armed = h.stage >= 3 && (size_t)h.rot == r;
         const KscPerm perm{galois_elts[r], d_c0, acc_rot, c0_rot, armed ? h.gal : GaloisFault{}};
-        if ((rc = ksc_back(p, d_out0[r], d_out1[r], d_c1, d_prepared_keys[r], nullptr, nullptr, a, fl, st, armed ? h.hook : none, &perm))) return rc;
+        if ((rc = ksc_back(p, d_out0[r], d_out1[r], d_c1, d_prepared_keys[r], nullptr, nullptr, a, fl, st, armed ? h.hook : none, &perm, KsForm::CKKS))) return rc;
     }
     return FHE_OK;
 }
@@ -169,7 +169,7 @@ int fhe_rotate_hoisted_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *const *
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
     const StagedFault ft = ctx->hrc_fault.take();
-    int rc = ksc_scope(ctx, p, a, d_flags);
+    int rc = ksc_scope(ctx, p, a, d_flags, KsForm::CKKS, false);
     if (rc) return rc;
     if (!d_c0 || !d_c1 || (n_rot && (!d_out0 || !d_out1 || !galois_elts || !d_prepared_keys))) return fail(FHE_ERR_INVALID, "null argument");
     for (size_t r = 0; r < n_rot; r++) {

@@ -2,8 +2,9 @@
 // sealed homomorphic multiply and rotation (part of the C ABI of include/fhe_mi355x.h).
 //
 // The checked calls do not cover faults already in their inputs.  A sealed composite closes that gap around an existing checked
-// call without touching it: it verifies every seal it was given (operands, key), runs the checked call unchanged -- the CKKS or the
-// BGV form, by the plan's plain modulus -- and seals both outputs, all on one stream.  The flag buffer is
+// call without touching it: it verifies every seal it was given (operands, key), runs the checked call's own body (hmult_checked,
+// rotate_checked of capi_checked.hpp) -- in the CKKS or the BGV form and with that form's hooks, by the plan's plain modulus -- and
+// seals both outputs, all on one stream.  The flag buffer is
 //     [input rows, in argument order][key rows][the checked call's own block, exactly its layout]
 // and a raised input flag does not stop the call: flags are read by the caller afterwards, as everywhere else.
 #include "capi_checked.hpp"
@@ -72,15 +73,15 @@ int seal_outputs(hipStream_t st, const fhe_ntt_tables *t, uint64_t *const *d_sea
     return FHE_OK;
 }
 
-// what must hold before the first verifying launch, so that a call outside the checked call's scope launches nothing: false = let
-// the checked call itself refuse (it returns the status and takes its hooks)
-bool sealed_scope_ok(const fhe_ctx *ctx, const fhe_keyswitch *p, const fhe_abft *a, const uint32_t *d_flags, bool mod_switch)
+// the form of the checked call a sealed composite runs, with that form's hook records
+struct SealedForm {
+    KsForm form;
+    KsHookSlot ks_hook, rs_hook;
+};
+SealedForm sealed_form(const fhe_keyswitch *p)
 {
-    if (!p) return false;
-    const bool bgv = p->plain_modulus != 0;
-    if (ksc_scope(ctx, p, a, d_flags, bgv)) return false;
-    if (bgv && (p->L > SCALAR_MAX_LIMBS || p->K > SCALAR_MAX_LIMBS)) return false;
-    return !(mod_switch && p->L < 2);
+    if (p && p->plain_modulus) return SealedForm{KsForm::BGV, &fhe_ctx::bgv_ksc_fault, &fhe_ctx::bgv_rsc_fault};
+    return SealedForm{KsForm::CKKS, &fhe_ctx::ksc_fault, &fhe_ctx::rsc_fault};
 }
 
 size_t key_rows(const fhe_keyswitch *p) { return (size_t)p->dnum * 2 * (p->L + p->K); }
@@ -149,7 +150,7 @@ int fhe_hmult_sealed_layout(const fhe_keyswitch *p, int rescale, int out[8])
 {
     if (!p || !out) return fail(FHE_ERR_INVALID, "null argument");
     int inner[4];
-    int rc = p->plain_modulus ? fhe_bgv_hmult_checked_layout(p, rescale, inner) : fhe_hmult_checked_layout(p, rescale, inner);
+    int rc = hmult_checked_layout(p, sealed_form(p).form, rescale, inner);
     if (rc) return rc;
     for (int i = 0; i < 4; i++) out[i] = i * p->L;
     out[4] = 4 * p->L;
@@ -164,11 +165,13 @@ int fhe_hmult_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t 
                      const uint64_t *const *d_seal_in, const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
-    const bool bgv = p && p->plain_modulus;
+    const SealedForm f = sealed_form(p);
     auto checked = [&](uint32_t *flags) {
-        return (bgv ? fhe_bgv_hmult_checked : fhe_hmult_checked)(ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, flags, stream);
+        return hmult_checked(f.form, f.ks_hook, f.rs_hook, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, flags, stream);
     };
-    if (!sealed_scope_ok(ctx, p, a, d_flags, rescale != 0) || !d_out0 || !d_out1 || d_out0 == d_out1 || !d_a0 || !d_a1 || !d_b0 || !d_b1 || !d_relin_key) {
+    // what must hold before the first verifying launch, so that a call outside the checked call's scope launches nothing: the
+    // checked call itself then refuses (it returns the status and takes its hooks)
+    if (ksc_scope(ctx, p, a, d_flags, f.form, rescale != 0) || !d_out0 || !d_out1 || d_out0 == d_out1 || !d_a0 || !d_a1 || !d_b0 || !d_b1 || !d_relin_key) {
         const int rc = checked(d_flags);      // refuses before its first launch
         return rc ? rc : fail(FHE_ERR_INVALID, "sealed multiply: bad argument");
     }
@@ -199,13 +202,7 @@ int fhe_rotate_sealed_layout(const fhe_keyswitch *p, int out[6])
     out[1] = p->L;
     out[2] = 2 * p->L;
     out[3] = out[2] + (int)key_rows(p);
-    if (p->plain_modulus) {
-        int inner[12];
-        int rc = fhe_bgv_keyswitch_checked_layout(p, inner);
-        if (rc) return rc;
-        out[4] = out[3] + inner[10];
-    } else
-        out[4] = out[3] + ksc_layout(p).total;
+    out[4] = out[3] + ksc_layout(p, sealed_form(p).form).total;
     out[5] = 0;
     return FHE_OK;
 }
@@ -215,11 +212,11 @@ int fhe_rotate_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t
                       const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
-    const bool bgv = p && p->plain_modulus;
+    const SealedForm f = sealed_form(p);
     auto checked = [&](uint32_t *flags) {
-        return (bgv ? fhe_bgv_rotate_checked : fhe_rotate_checked)(ctx, p, d_out0, d_out1, d_c0, d_c1, galois_elt, d_galois_key, a, flags, stream);
+        return rotate_checked(f.form, f.ks_hook, ctx, p, d_out0, d_out1, d_c0, d_c1, galois_elt, d_galois_key, a, flags, stream);
     };
-    if (!sealed_scope_ok(ctx, p, a, d_flags, false) || !d_out0 || !d_out1 || d_out0 == d_out1 || !d_c0 || !d_c1 || !d_galois_key || !(galois_elt & 1)) {
+    if (ksc_scope(ctx, p, a, d_flags, f.form, false) || !d_out0 || !d_out1 || d_out0 == d_out1 || !d_c0 || !d_c1 || !d_galois_key || !(galois_elt & 1)) {
         const int rc = checked(d_flags);      // refuses before its first launch
         return rc ? rc : fail(FHE_ERR_INVALID, "sealed rotation: bad argument");
     }

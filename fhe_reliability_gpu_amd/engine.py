@@ -710,20 +710,42 @@ class KeySwitch:
         """``{stage name: (offset, shape)}`` of the checked calls' flag words plus ``"total"``; M = L + K.  Stage names in order:
         ``intt_in [L]``, ``extend [dnum][M]``, ``ntt_ext [dnum][M]``, ``mac [2][M]``, ``intt_special [2][K]``,
         ``moddown [2][K + L]``, ``ntt_conv [2][L]``, ``tail [2][L]``."""
-        out = (C.c_int * 10)()
-        check(lib.fhe_keyswitch_checked_layout(self._h, out))
+        return self._ks_layout(False)
+
+    # Each checked composite below exists once, with its form as a parameter (bgv = False: the CKKS form, True: the BGV form of a
+    # plan with a plain modulus); the public methods choose the form.
+    @staticmethod
+    def _c(bgv, name):
+        """The C call ``name`` of a form: ``fhe_<name>``, or ``fhe_bgv_<name>`` with the rescale called mod_switch."""
+        return getattr(lib, "fhe_bgv_" + name.replace("rescale", "mod_switch") if bgv else "fhe_" + name)
+
+    def _ks_layout(self, bgv):
+        names = self.BGV_CHECKED_STAGES if bgv else self.CHECKED_STAGES
+        out = (C.c_int * 12)()
+        check(self._c(bgv, "keyswitch_checked_layout")(self._h, out))
         L, K, d = self.L, self.K, self.dnum
         M = L + K
-        shapes = ((L,), (d, M), (d, M), (2, M), (2, K), (2, K + L), (2, L), (2, L))
-        lay = {name: (int(out[s]), shapes[s]) for s, name in enumerate(self.CHECKED_STAGES)}
-        lay["total"] = int(out[8])
+        shapes = ((L,), (d, M), (d, M), (2, M), (2, K), (2, K + L), (2, L), (2, L), (2, K), (2, L))
+        lay = {name: (int(out[s]), shapes[s]) for s, name in enumerate(names)}
+        lay["total"] = int(out[len(names)])
         return lay
 
-    def _checked(self, call, stream):
-        lay = self.checked_layout()
+    def _checked(self, bgv, name, *args, stream=None):
+        """Run the key-switch call ``name`` of a form on (out0, out1, *args, flags): (out0, out1, flags by stage name)."""
+        lay = self._ks_layout(bgv)
         o0, o1 = self._out(self.L), self._out(self.L)
-        f = _checked_flags(self.eng, lay["total"], lambda fl: call(o0, o1, fl), stream)
-        return o0, o1, self._split_flags(f, lay, self.CHECKED_STAGES)
+        f = _checked_flags(self.eng, lay["total"], lambda fl: self._c(bgv, name)(self.eng._h, self._h, o0.ptr, o1.ptr, *args, fl.ptr, stream), stream)
+        return o0, o1, self._split_flags(f, lay)
+
+    def _apply_checked(self, bgv, c, evk, abft, add0, add1, stream):
+        return self._checked(bgv, "keyswitch_apply_checked", c.ptr, evk.ptr, add0.ptr if add0 is not None else None,
+                             add1.ptr if add1 is not None else None, abft._h, stream=stream)
+
+    def _relinearize_checked(self, bgv, d0, d1, d2, relin_key, abft, stream):
+        return self._checked(bgv, "relinearize_checked", d0.ptr, d1.ptr, d2.ptr, relin_key.ptr, abft._h, stream=stream)
+
+    def _rotate_checked(self, bgv, c0, c1, galois_elt, galois_key, abft, stream):
+        return self._checked(bgv, "rotate_checked", c0.ptr, c1.ptr, galois_elt, galois_key.ptr, abft._h, stream=stream)
 
     def apply_checked(self, c: DeviceArray, evk: DeviceArray, abft: "Abft", add0: Optional[DeviceArray] = None,
                       add1: Optional[DeviceArray] = None, stream=None):
@@ -731,20 +753,16 @@ class KeySwitch:
         are ``apply``'s bit for bit; ``flags`` maps each stage name of ``checked_layout`` to a uint32 array of its shape -- the ABFT
         stages hold 0 / 1, the residue-checked ones the bits 1 (identity), 2 (window), 4 (operand not canonical).  A fault at
         (stage, unit) raises that word and no other.  ``abft`` must be an ``Abft`` over the plan's tables."""
-        return self._checked(lambda o0, o1, fl: lib.fhe_keyswitch_apply_checked(
-            self.eng._h, self._h, o0.ptr, o1.ptr, c.ptr, evk.ptr, add0.ptr if add0 is not None else None, add1.ptr if add1 is not None else None,
-            abft._h, fl.ptr, stream), stream)
+        return self._apply_checked(False, c, evk, abft, add0, add1, stream)
 
     def relinearize_checked(self, d0: DeviceArray, d1: DeviceArray, d2: DeviceArray, relin_key: DeviceArray, abft: "Abft", stream=None):
         """``relinearize`` with every stage of its key switch checked: (out0, out1, flags) as ``apply_checked``."""
-        return self._checked(lambda o0, o1, fl: lib.fhe_relinearize_checked(
-            self.eng._h, self._h, o0.ptr, o1.ptr, d0.ptr, d1.ptr, d2.ptr, relin_key.ptr, abft._h, fl.ptr, stream), stream)
+        return self._relinearize_checked(False, d0, d1, d2, relin_key, abft, stream)
 
     def rotate_checked(self, c0: DeviceArray, c1: DeviceArray, galois_elt: int, galois_key: DeviceArray, abft: "Abft", stream=None):
         """``rotate`` with every stage of its key switch checked: (out0, out1, flags) as ``apply_checked``.  The Galois permutation
         of the two parts runs as a launch of its own and is not covered."""
-        return self._checked(lambda o0, o1, fl: lib.fhe_rotate_checked(
-            self.eng._h, self._h, o0.ptr, o1.ptr, c0.ptr, c1.ptr, galois_elt, galois_key.ptr, abft._h, fl.ptr, stream), stream)
+        return self._rotate_checked(False, c0, c1, galois_elt, galois_key, abft, stream)
 
     # ---- checked hoisted rotations (capi_rotate_hoisted_checked.cpp) ----
     HOISTED_ROT_STAGES = ("mac", "galois", "intt_special", "moddown", "ntt_conv", "tail")      # in execution order
@@ -855,55 +873,74 @@ class KeySwitch:
     def rescale_checked_layout(self, n_parts: int = 2):
         """``{stage name: (offset, shape)}`` of ``rescale_checked``'s flag words plus ``"total"``; R = L - 1.  Stage names in
         order: ``intt_last [n_parts]``, ``reduce [n_parts][R]``, ``ntt_delta [n_parts][R]``, ``scale [n_parts][R]``."""
-        out = (C.c_int * 6)()
-        check(lib.fhe_rescale_checked_layout(self._h, n_parts, out))
-        R = self.L - 1
-        shapes = ((n_parts,), (n_parts, R), (n_parts, R), (n_parts, R))
-        lay = {name: (int(out[s]), shapes[s]) for s, name in enumerate(self.RESCALE_CHECKED_STAGES)}
-        lay["total"] = int(out[4])
-        return lay
+        return self._rs_layout(False, n_parts)
 
     def hmult_checked_layout(self, rescale: bool = True):
         """``{"tensor": off, "keyswitch": off, "rescale": off, "total": n}`` of ``hmult_checked``'s flag buffer: the tensor block
         ``[L][3]``, the key-switch block laid out as ``checked_layout``, the rescale block as ``rescale_checked_layout(2)`` (its
         offset equals the total when ``rescale`` is false)."""
-        out = (C.c_int * 4)()
-        check(lib.fhe_hmult_checked_layout(self._h, 1 if rescale else 0, out))
-        return {"tensor": int(out[0]), "keyswitch": int(out[1]), "rescale": int(out[2]), "total": int(out[3])}
+        return self._hm_layout(False, rescale)
 
     @staticmethod
-    def _split_flags(f, lay, names, base=0):
+    def _split_flags(f, lay, names=None, base=0):
+        """The flag words of the stages ``names`` of a layout (default: all of them) as arrays of their shapes."""
+        names = [n for n in lay if n != "total"] if names is None else names
         return {name: f[base + lay[name][0]:base + lay[name][0] + int(np.prod(lay[name][1]))].reshape(lay[name][1]).copy() for name in names}
+
+    def _rs_layout(self, bgv, n_parts):
+        names = self.BGV_MOD_SWITCH_CHECKED_STAGES if bgv else self.RESCALE_CHECKED_STAGES
+        out = (C.c_int * 8)()
+        check(self._c(bgv, "rescale_checked_layout")(self._h, n_parts, out))
+        R = self.L - 1
+        shapes = ((n_parts,), (n_parts, R), (n_parts, R), (n_parts, R), (n_parts,), (n_parts, R))
+        lay = {name: (int(out[s]), shapes[s]) for s, name in enumerate(names)}
+        lay["total"] = int(out[len(names)])
+        return lay
+
+    def _hm_layout(self, bgv, rescale):
+        out = (C.c_int * 4)()
+        check(self._c(bgv, "hmult_checked_layout")(self._h, 1 if rescale else 0, out))
+        return {"tensor": int(out[0]), "keyswitch": int(out[1]), "rescale": int(out[2]), "total": int(out[3])}
+
+    def _rescale_checked(self, bgv, c, abft, n_parts, stream):
+        lay = self._rs_layout(bgv, n_parts)
+        o = self.eng.alloc(n_parts * (self.L - 1) * self.t.N)
+        o.shape = (n_parts, self.L - 1, self.t.N)
+        f = _checked_flags(self.eng, lay["total"], lambda fl: self._c(bgv, "rescale_checked")(
+            self.eng._h, self._h, o.ptr, c.ptr, n_parts, abft._h, fl.ptr, stream), stream)
+        return o, self._split_flags(f, lay)
+
+    def _hmult_flags(self, bgv, f, rescale, base=0):
+        """The flags of a form's checked multiply, whose block starts at word ``base`` of ``f``, by step and stage name."""
+        lay, kl = self._hm_layout(bgv, rescale), self._ks_layout(bgv)
+        rl = self._rs_layout(bgv, 2) if rescale else None
+        t0 = base + lay["tensor"]
+        return {"tensor": f[t0:t0 + 3 * self.L].reshape(self.L, 3).copy(),
+                "keyswitch": self._split_flags(f, kl, base=base + lay["keyswitch"]),
+                "rescale": self._split_flags(f, rl, base=base + lay["rescale"]) if rescale else None}
+
+    def _hmult_checked(self, bgv, a0, a1, b0, b1, relin_key, abft, rescale, stream):
+        limbs = self.L - 1 if rescale else self.L
+        o0, o1 = self._out(limbs), self._out(limbs)
+        f = _checked_flags(self.eng, self._hm_layout(bgv, rescale)["total"], lambda fl: self._c(bgv, "hmult_checked")(
+            self.eng._h, self._h, o0.ptr, o1.ptr, a0.ptr, a1.ptr, b0.ptr, b1.ptr, relin_key.ptr, 1 if rescale else 0, abft._h, fl.ptr, stream), stream)
+        return o0, o1, self._hmult_flags(bgv, f, rescale)
 
     def rescale_checked(self, c: DeviceArray, abft: "Abft", n_parts: int = 2, stream=None):
         """``rescale`` with every stage checked: (out, flags).  The words are ``rescale``'s bit for bit; ``flags`` maps
         ``intt_last``, ``reduce``, ``ntt_delta`` and ``scale`` to uint32 arrays of the shapes of ``rescale_checked_layout`` -- the ABFT
         stages hold 0 / 1, the residue-checked ones the bits 1 (identity), 2 (window), 4 (operand not canonical).  A fault at
         (stage, unit) raises that word and no other."""
-        lay = self.rescale_checked_layout(n_parts)
-        total = lay["total"]
-        o = self.eng.alloc(n_parts * (self.L - 1) * self.t.N)
-        o.shape = (n_parts, self.L - 1, self.t.N)
-        f = _checked_flags(self.eng, total, lambda fl: lib.fhe_rescale_checked(self.eng._h, self._h, o.ptr, c.ptr, n_parts, abft._h, fl.ptr, stream), stream)
-        return o, self._split_flags(f, lay, self.RESCALE_CHECKED_STAGES)
+        return self._rescale_checked(False, c, abft, n_parts, stream)
 
     def hmult_checked(self, a0: DeviceArray, a1: DeviceArray, b0: DeviceArray, b1: DeviceArray, relin_key: DeviceArray, abft: "Abft",
                       rescale: bool = True, stream=None):
         """``hmult`` with every step checked -- multiply -> relinearize -> mod_switch_to_next (dotprod_test.cu:113-115) as one
         protected call: (out0, out1, flags), the words ``hmult``'s bit for bit.  ``flags = {"tensor": [L][3] as tensor_checked,
         "keyswitch": {the eight stage names of checked_layout}, "rescale": {the four of rescale_checked_layout} or None}``."""
-        lay = self.hmult_checked_layout(rescale)
-        total = lay["total"]
-        limbs = self.L - 1 if rescale else self.L
-        o0, o1 = self._out(limbs), self._out(limbs)
-        f = _checked_flags(self.eng, total, lambda fl: lib.fhe_hmult_checked(
-            self.eng._h, self._h, o0.ptr, o1.ptr, a0.ptr, a1.ptr, b0.ptr, b1.ptr, relin_key.ptr, 1 if rescale else 0, abft._h, fl.ptr, stream), stream)
-        out = {"tensor": f[lay["tensor"]:lay["tensor"] + 3 * self.L].reshape(self.L, 3).copy(),
-               "keyswitch": self._split_flags(f, self.checked_layout(), self.CHECKED_STAGES, lay["keyswitch"]),
-               "rescale": self._split_flags(f, self.rescale_checked_layout(2), self.RESCALE_CHECKED_STAGES, lay["rescale"]) if rescale else None}
-        return o0, o1, out
+        return self._hmult_checked(False, a0, a1, b0, b1, relin_key, abft, rescale, stream)
 
-    # ---- BGV forms of the checked calls: plans with a plain modulus (capi_bgv_checked.cpp) ----
+    # ---- BGV forms of the checked calls: plans with a plain modulus ----
     BGV_CHECKED_STAGES = CHECKED_STAGES + ("scale_special", "scale_conv")                # stages 0-7, then 9 and 10
     BGV_MOD_SWITCH_CHECKED_STAGES = RESCALE_CHECKED_STAGES + ("scale_last", "scale_delta")   # stages 0-3, then 4 and 5
 
@@ -911,82 +948,44 @@ class KeySwitch:
         """``checked_layout`` of the BGV key switch: the eight stages at the same offsets, then ``scale_special [2][K]`` (stage 9: the
         special limbs times t^-1, run between ``intt_special`` and ``moddown``) and ``scale_conv [2][L]`` (stage 10: the converted
         limbs times t, run between ``moddown`` and ``ntt_conv``), plus ``"total"``."""
-        out = (C.c_int * 12)()
-        check(lib.fhe_bgv_keyswitch_checked_layout(self._h, out))
-        L, K, d = self.L, self.K, self.dnum
-        M = L + K
-        shapes = ((L,), (d, M), (d, M), (2, M), (2, K), (2, K + L), (2, L), (2, L), (2, K), (2, L))
-        lay = {name: (int(out[s]), shapes[s]) for s, name in enumerate(self.BGV_CHECKED_STAGES)}
-        lay["total"] = int(out[10])
-        return lay
-
-    def _bgv_checked(self, call, stream):
-        lay = self.bgv_checked_layout()
-        o0, o1 = self._out(self.L), self._out(self.L)
-        f = _checked_flags(self.eng, lay["total"], lambda fl: call(o0, o1, fl), stream)
-        return o0, o1, self._split_flags(f, lay, self.BGV_CHECKED_STAGES)
+        return self._ks_layout(True)
 
     def bgv_apply_checked(self, c: DeviceArray, evk: DeviceArray, abft: "Abft", add0: Optional[DeviceArray] = None,
                           add1: Optional[DeviceArray] = None, stream=None):
         """``apply`` on a plan with a plain modulus with every stage checked, the two BGV scalar stages included: (out0, out1,
         flags) as ``apply_checked``, ``flags`` keyed by the ten names of ``bgv_checked_layout``."""
-        return self._bgv_checked(lambda o0, o1, fl: lib.fhe_bgv_keyswitch_apply_checked(
-            self.eng._h, self._h, o0.ptr, o1.ptr, c.ptr, evk.ptr, add0.ptr if add0 is not None else None, add1.ptr if add1 is not None else None,
-            abft._h, fl.ptr, stream), stream)
+        return self._apply_checked(True, c, evk, abft, add0, add1, stream)
 
     def bgv_relinearize_checked(self, d0: DeviceArray, d1: DeviceArray, d2: DeviceArray, relin_key: DeviceArray, abft: "Abft", stream=None):
         """``relinearize`` on a BGV plan with every stage checked: (out0, out1, flags) as ``bgv_apply_checked``."""
-        return self._bgv_checked(lambda o0, o1, fl: lib.fhe_bgv_relinearize_checked(
-            self.eng._h, self._h, o0.ptr, o1.ptr, d0.ptr, d1.ptr, d2.ptr, relin_key.ptr, abft._h, fl.ptr, stream), stream)
+        return self._relinearize_checked(True, d0, d1, d2, relin_key, abft, stream)
 
     def bgv_rotate_checked(self, c0: DeviceArray, c1: DeviceArray, galois_elt: int, galois_key: DeviceArray, abft: "Abft", stream=None):
         """``rotate`` on a BGV plan with every stage of its key switch checked: (out0, out1, flags) as ``bgv_apply_checked``.  The
         Galois permutation runs as a launch of its own and is not covered, as for ``rotate_checked``."""
-        return self._bgv_checked(lambda o0, o1, fl: lib.fhe_bgv_rotate_checked(
-            self.eng._h, self._h, o0.ptr, o1.ptr, c0.ptr, c1.ptr, galois_elt, galois_key.ptr, abft._h, fl.ptr, stream), stream)
+        return self._rotate_checked(True, c0, c1, galois_elt, galois_key, abft, stream)
 
     def bgv_mod_switch_checked_layout(self, n_parts: int = 2):
         """``rescale_checked_layout`` of the BGV mod switch: the four stages at the same offsets, then ``scale_last [n_parts]``
         (stage 4: the last limbs times t^-1, run between ``intt_last`` and ``reduce``) and ``scale_delta [n_parts][R]`` (stage 5: the
         residues times t, run between ``reduce`` and ``ntt_delta``), plus ``"total"``."""
-        out = (C.c_int * 8)()
-        check(lib.fhe_bgv_mod_switch_checked_layout(self._h, n_parts, out))
-        R = self.L - 1
-        shapes = ((n_parts,), (n_parts, R), (n_parts, R), (n_parts, R), (n_parts,), (n_parts, R))
-        lay = {name: (int(out[s]), shapes[s]) for s, name in enumerate(self.BGV_MOD_SWITCH_CHECKED_STAGES)}
-        lay["total"] = int(out[6])
-        return lay
+        return self._rs_layout(True, n_parts)
 
     def bgv_mod_switch_checked(self, c: DeviceArray, abft: "Abft", n_parts: int = 2, stream=None):
         """``rescale`` on a BGV plan (``mod_switch_to_next_inplace``, dotprod_test.cu:115) with every stage checked: (out, flags) as
         ``rescale_checked``, ``flags`` keyed by the six names of ``bgv_mod_switch_checked_layout``."""
-        lay = self.bgv_mod_switch_checked_layout(n_parts)
-        o = self.eng.alloc(n_parts * (self.L - 1) * self.t.N)
-        o.shape = (n_parts, self.L - 1, self.t.N)
-        f = _checked_flags(self.eng, lay["total"], lambda fl: lib.fhe_bgv_mod_switch_checked(self.eng._h, self._h, o.ptr, c.ptr, n_parts, abft._h, fl.ptr,
-                                                                                          stream), stream)
-        return o, self._split_flags(f, lay, self.BGV_MOD_SWITCH_CHECKED_STAGES)
+        return self._rescale_checked(True, c, abft, n_parts, stream)
 
     def bgv_hmult_checked_layout(self, rescale: bool = True):
         """``hmult_checked_layout`` with the two BGV layouts: ``{"tensor": off, "keyswitch": off, "rescale": off, "total": n}``."""
-        out = (C.c_int * 4)()
-        check(lib.fhe_bgv_hmult_checked_layout(self._h, 1 if rescale else 0, out))
-        return {"tensor": int(out[0]), "keyswitch": int(out[1]), "rescale": int(out[2]), "total": int(out[3])}
+        return self._hm_layout(True, rescale)
 
     def bgv_hmult_checked(self, a0: DeviceArray, a1: DeviceArray, b0: DeviceArray, b1: DeviceArray, relin_key: DeviceArray, abft: "Abft",
                           rescale: bool = True, stream=None):
         """``hmult`` on a BGV plan with every step checked -- the reference's multiply -> relinearize_inplace ->
         mod_switch_to_next_inplace (dotprod_test.cu:113-115) as one protected call: (out0, out1, flags) as ``hmult_checked``, the
         key-switch and mod-switch blocks keyed by the names of ``bgv_checked_layout`` / ``bgv_mod_switch_checked_layout``."""
-        lay = self.bgv_hmult_checked_layout(rescale)
-        limbs = self.L - 1 if rescale else self.L
-        o0, o1 = self._out(limbs), self._out(limbs)
-        f = _checked_flags(self.eng, lay["total"], lambda fl: lib.fhe_bgv_hmult_checked(
-            self.eng._h, self._h, o0.ptr, o1.ptr, a0.ptr, a1.ptr, b0.ptr, b1.ptr, relin_key.ptr, 1 if rescale else 0, abft._h, fl.ptr, stream), stream)
-        out = {"tensor": f[lay["tensor"]:lay["tensor"] + 3 * self.L].reshape(self.L, 3).copy(),
-               "keyswitch": self._split_flags(f, self.bgv_checked_layout(), self.BGV_CHECKED_STAGES, lay["keyswitch"]),
-               "rescale": self._split_flags(f, self.bgv_mod_switch_checked_layout(2), self.BGV_MOD_SWITCH_CHECKED_STAGES, lay["rescale"]) if rescale else None}
-        return o0, o1, out
+        return self._hmult_checked(True, a0, a1, b0, b1, relin_key, abft, rescale, stream)
 
     # ---- operands sealed at rest: the checked multiply and rotation behind seal verification (capi_seal.cpp) ----
     def seal_key(self, key: DeviceArray, stream=None) -> DeviceArray:
@@ -1041,16 +1040,7 @@ class KeySwitch:
             self.eng._h, self._h, o0.ptr, o1.ptr, a0.ptr, a1.ptr, b0.ptr, b1.ptr, relin_key.ptr, 1 if rescale else 0, abft._h, sin,
             key_seal.ptr if key_seal is not None else None, sout, fl.ptr, stream), stream)
         flags = self._split_flags(f, lay, names + ("key",))
-        base = lay["checked"]
-        if self.plain_modulus:
-            hl, kl, ks_names = self.bgv_hmult_checked_layout(rescale), self.bgv_checked_layout(), self.BGV_CHECKED_STAGES
-            rl, rs_names = (self.bgv_mod_switch_checked_layout(2), self.BGV_MOD_SWITCH_CHECKED_STAGES) if rescale else (None, None)
-        else:
-            hl, kl, ks_names = self.hmult_checked_layout(rescale), self.checked_layout(), self.CHECKED_STAGES
-            rl, rs_names = (self.rescale_checked_layout(2), self.RESCALE_CHECKED_STAGES) if rescale else (None, None)
-        flags["checked"] = {"tensor": f[base + hl["tensor"]:base + hl["tensor"] + 3 * self.L].reshape(self.L, 3).copy(),
-                            "keyswitch": self._split_flags(f, kl, ks_names, base + hl["keyswitch"]),
-                            "rescale": self._split_flags(f, rl, rs_names, base + hl["rescale"]) if rescale else None}
+        flags["checked"] = self._hmult_flags(bool(self.plain_modulus), f, rescale, lay["checked"])
         return o0, o1, so, flags
 
     def rotate_sealed(self, c0: DeviceArray, c1: DeviceArray, galois_elt: int, galois_key: DeviceArray, abft: "Abft", seals=None,
@@ -1064,8 +1054,8 @@ class KeySwitch:
             self.eng._h, self._h, o0.ptr, o1.ptr, c0.ptr, c1.ptr, galois_elt, galois_key.ptr, abft._h, sin,
             key_seal.ptr if key_seal is not None else None, sout, fl.ptr, stream), stream)
         flags = self._split_flags(f, lay, names + ("key",))
-        kl, ks_names = (self.bgv_checked_layout(), self.BGV_CHECKED_STAGES) if self.plain_modulus else (self.checked_layout(), self.CHECKED_STAGES)
-        flags["checked"] = self._split_flags(f, kl, ks_names, lay["checked"])
+        kl = self._ks_layout(bool(self.plain_modulus))
+        flags["checked"] = self._split_flags(f, kl, base=lay["checked"])
         return o0, o1, so, flags
 
     def __del__(self):

@@ -650,7 +650,8 @@ int fhe_ctx_inject_fault_rescale(fhe_ctx *ctx, int stage, int point, int unit, l
  *   out[2]       the rescale block, laid out as fhe_rescale_checked_layout with n_parts = 2 (= out[3] when rescale == 0)
  *   out[3]       total
  * The one-shot hooks fhe_ctx_inject_fault_pointwise, fhe_ctx_inject_fault_keyswitch and fhe_ctx_inject_fault_rescale each fire
- * in their own step.  A status returned by any step ends the call there.  Scope and statuses as above. */
+ * in their own step.  All three are checked against the call before its first launch: a refused hook launches nothing and leaves
+ * the flag buffer and the outputs untouched.  A status returned by any step ends the call there.  Scope and statuses as above. */
 int fhe_hmult_checked_layout(const fhe_keyswitch *p, int rescale, int out[4]);
 int fhe_hmult_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_a0, const uint64_t *d_a1,
                       const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a,

@@ -261,6 +261,40 @@ def test_one_flip_in_the_mod_switch_raises_exactly_its_own_word(F, eng, cases):
     eng.check()
 
 
+def test_a_call_clears_exactly_its_own_flag_words(F, eng, cases):
+    """the mod switch and the key switch clear the words of their layout -- the scalar stages' included -- and not one word more"""
+    from fhe_reliability_gpu_amd._lib import check, lib
+    c = cases("A")
+    ks, ab, N, L, R = c.ks, c.ab, c.N, c.L, c.R
+    pattern = GARBAGE & 0xFFFFFFFF
+
+    def flat_flags(total, call):
+        """the call on a buffer of total + 2 patterned words: (the first total words, the two behind them)"""
+        flb = eng.upload(np.full(total + 2 + total % 2, pattern, dtype=np.uint32).view(np.uint64))
+        check(call(flb))
+        f = flb.download().view(np.uint32)
+        return f[:total], f[total:total + 2]
+
+    with plain_modulus(ks, 65537):
+        for n in (1, 3):
+            lay = ks.bgv_mod_switch_checked_layout(n)
+            o = eng.alloc(n * R * N)
+            mod_switch = lambda flb: lib.fhe_bgv_mod_switch_checked(eng._h, ks._h, o.ptr, c.dc3.ptr, n, ab._h, flb.ptr, None)
+            own, behind = flat_flags(lay["total"], mod_switch)
+            assert not own.any() and (behind == pattern).all(), n
+        # a fault on the last unit of the last stage: the last word of the layout, and only that one
+        unit = 3 * R - 1
+        check(lib.fhe_ctx_inject_fault_bgv_mod_switch(eng._h, 5, RESULT, unit, N - 1, 30))
+        own, behind = flat_flags(lay["total"], mod_switch)
+        assert np.flatnonzero(own).tolist() == [lay["scale_delta"][0] + unit] == [lay["total"] - 1] and (behind == pattern).all()
+        lay = ks.bgv_checked_layout()
+        o0, o1 = eng.alloc(L * N), eng.alloc(L * N)
+        own, behind = flat_flags(lay["total"], lambda flb: lib.fhe_bgv_keyswitch_apply_checked(
+            eng._h, ks._h, o0.ptr, o1.ptr, c.d[0].ptr, c.dk.ptr, None, None, ab._h, flb.ptr, None))
+        assert not own.any() and (behind == pattern).all()
+    eng.check()
+
+
 def test_each_hook_fires_in_its_own_block_of_the_multiply(F, eng, cases):
     from fhe_reliability_gpu_amd._lib import check, lib
     c = cases("B")

@@ -239,6 +239,30 @@ def test_one_flip_per_block_inside_hmult_checked(F, eng, logn, kind):
     eng.check()
 
 
+def test_a_refused_rescale_hook_stops_the_multiply_before_its_first_launch(F, eng):
+    """every hook is checked against the call before anything is enqueued: a rescale hook the call refuses leaves the flag buffer
+    and both outputs as they were, and the next call is clean"""
+    from fhe_reliability_gpu_amd._lib import check, lib
+    logn, L, K, dnum = 10, 4, 2, 2
+    N, R = 1 << logn, L - 1
+    qs, t, ks, ab, ops, rlk = _setup(F, eng, logn, L, K, dnum, "mixed", 41)
+    d, dk = [eng.upload(v) for v in ops], eng.upload(rlk)
+    o0, o1, fl = ks.hmult_checked(*d, dk, ab)
+    _clean_hmult(fl, True)
+    want = o0.download(), o1.download()
+    pattern = 0x5A5A5A5A5A5A5A5A
+    total = ks.hmult_checked_layout(True)["total"]
+    flb, p0, p1 = (eng.upload(np.full(n, pattern, dtype=np.uint64)) for n in ((total + 1) // 2, R * N, R * N))
+    check(lib.fhe_ctx_inject_fault_rescale(eng._h, 1, SUM, 0, 0, 30))      # x mod q_j has no running sum
+    assert lib.fhe_hmult_checked(eng._h, ks._h, p0.ptr, p1.ptr, d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, dk.ptr, 1, ab._h, flb.ptr, None) == UNSUPPORTED
+    eng.sync()
+    assert all((x.download() == pattern).all() for x in (flb, p0, p1))
+    o0, o1, fl = ks.hmult_checked(*d, dk, ab)
+    _clean_hmult(fl, True)
+    assert (o0.download() == want[0]).all() and (o1.download() == want[1]).all()
+    eng.check()
+
+
 def test_scope_limits_are_error_statuses(F, eng):
     from fhe_reliability_gpu_amd._lib import check, lib, vp
     logn, L, K, dnum = 10, 4, 2, 2
