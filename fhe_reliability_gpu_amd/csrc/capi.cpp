@@ -350,7 +350,36 @@ int cyclic_tables(fhe_ctx *ctx, int log_n, u64 mod, u64 root, int convention, u6
     return FHE_OK;
 }
 
-// lengths below 2^5: the forward network with a cyclic table, then the bit-reversal gather (three tiny launches)
+// The natural-order launches run the TRANSPOSED network.  It is ntt.py's transform wherever the stage roots form one tower:
+// wlen(2) = -1 and wlen(2 len)^2 = wlen(len), i.e. wlen(n) is an n-th root of unity whose n/2-th power is -1.  A root that is no
+// generator, or a modulus with n not dividing mod - 1 (every even one above 2: (mod - 1) / len is rounded down and the wlen are
+// unrelated powers), has no tower.  The tower is SUFFICIENT, not necessary -- some towerless sets happen to give the same words --
+// and the test is deliberately conservative: whatever fails it goes to cyclic_small, which is ntt.py's definition for any table.
+// The answer is cached per context with the tables it guards.
+static bool cyclic_tower(u64 mod, int log_n, u64 root, bool nth_root_convention)
+{
+    const u64 n = (u64)1 << log_n;
+    u64 prev = 0;
+    for (int s = 0; s < log_n; s++) {
+        const u64 len = (u64)2 << s;
+        const u64 w = nth_root_convention ? host::pow_mod(root, n / len, mod) : host::pow_mod(root, (mod - 1) / len, mod);
+        if (s == 0 ? w != (mod - 1) % mod : host::mul_mod(w, w, mod) != prev) return false;
+        prev = w;
+    }
+    return true;
+}
+static bool cyclic_tower_cached(fhe_ctx *ctx, u64 mod, int log_n, u64 root, int convention)
+{
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    const auto key = std::make_tuple(log_n, mod, root, convention);
+    auto it = ctx->cyclic_tower.find(key);
+    if (it == ctx->cyclic_tower.end()) it = ctx->cyclic_tower.emplace(key, cyclic_tower(mod, log_n, root, convention == 1)).first;
+    return it->second;
+}
+
+// The forward network with a cyclic table, then the bit-reversal gather (three launches).  Stage for stage this is ntt.py's own
+// network with its positions relabelled by the bit reversal -- same pairs, same factor wlen^j, same (u + v, u - v) -- so it holds for
+// ANY modulus and root.  It serves the lengths below 2^5 and every call whose roots form no tower (cyclic_tower).
 static int cyclic_small(fhe_ctx *ctx, u64 *d_data, u64 *d_scratch, int log_n, size_t n_vec, u64 mod, u64 root, int convention, u64 scale, bool do_scale,
                         void *stream)
 {
@@ -692,12 +721,17 @@ int fhe_ntt_cyclic(fhe_ctx *ctx, uint64_t *d_data, uint64_t *d_scratch, int log_
         use_root = host::pow_mod(root, mod - 2, mod);
         scale = host::pow_mod(n % mod, mod - 2, mod);
     }
-    if (!ntt_gs_supported(log_n)) return cyclic_small(ctx, d_data, d_scratch, log_n, n_vec, mod, use_root, convention, scale, inverse != 0, stream);
+    // (the trace names the route a call took: tests hold the designed primes to the natural-order launches with it)
+    if (!ntt_gs_supported(log_n) || !cyclic_tower_cached(ctx, mod, log_n, use_root, convention)) {
+        TraceScope tr(ctx, pick(ctx, stream), "NTT_CYCLIC_FORWARD_NETWORK");
+        return cyclic_small(ctx, d_data, d_scratch, log_n, n_vec, mod, use_root, convention, scale, inverse != 0, stream);
+    }
     fhe_ntt_tables *t = nullptr;
     int rc = cyclic_tables(ctx, log_n, mod, use_root, convention, scale, &t);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = pick(ctx, stream);
+    TraceScope tr(ctx, st, "NTT_CYCLIC_NATURAL_ORDER");
     // two launches, the bit reversal folded into the first one's loads, the scale into the last stage: d_data -> d_scratch -> d_data
     return gs_batch(ctx, st, d_data, d_data, t, log_n, n_vec, d_scratch);
 }
@@ -716,6 +750,10 @@ int fhe_fourstep_create(fhe_ctx *ctx, uint64_t n1, uint64_t n2, uint64_t mod, ui
         return fail(FHE_ERR_INVALID, "n1 and n2 must be powers of two, 2 <= n1, n2 <= 2^20, n1 * n2 <= 2^26");
     const u64 N = n1 * n2;
     if ((mod - 1) % N) return fail(FHE_ERR_INVALID, "N must divide mod - 1");
+    // four_step_ntt_prot.py is the direct DFT with w = g^((mod-1)/N); the engine's network is that DFT only where w^(N/2) = -1
+    // (N | mod - 1 makes the rest of the tower), which a g that generates nothing -- a quadratic residue -- does not give
+    if (!cyclic_tower(mod, l1 + l2, g % mod, false))
+        return fail(FHE_ERR_INVALID, "g^((mod-1)/N) must be a primitive N-th root whose N/2-th power is -1 (g a quadratic non-residue)");
     if (mod >= ((u64)1 << 61)) return fail(FHE_ERR_UNSUPPORTED, "modulus must be below 2^61");
     std::unique_ptr<fhe_fourstep> p(new fhe_fourstep);
     p->ctx = ctx;

@@ -137,6 +137,7 @@ struct fhe_ctx {
     int fused_variant = 7;   // handoff*2 + stream hint (ntt_launch.hpp); 7 = acquire + nt streaming
     // cyclic tables keyed by (log_n, mod, root, convention * 2 + natural-order form, scale folded into the last stage)
     std::map<std::tuple<int, u64, u64, int, u64>, std::unique_ptr<fhe_ntt_tables>> cyclic;
+    std::map<std::tuple<int, u64, u64, int>, bool> cyclic_tower;   // (log_n, mod, root, convention) -> the stage roots form a tower (capi.cpp)
     std::map<std::vector<u64>, std::unique_ptr<GarnerTables>> garner;
 };
 

@@ -145,6 +145,13 @@ int fhe_bitrev_permute(fhe_ctx *ctx, uint64_t *d_dst, const uint64_t *d_src, int
  * convention 1 selects rfhe_framewk/src/negaclic_ntt.py:38-57 (root is a primitive
  * n-th root, wlen = root^(n/len)).  inverse != 0 gives intt(): transform with
  * root^(mod-2), then times n^(mod-2) (motivation/bsgs.py:31-36).
+ * The result is that definition's for EVERY (mod, root), the degenerate ones included (n not dividing
+ * mod - 1, an even modulus, a root that generates nothing: the exponents are rounded down as the
+ * reference rounds them).  Where the stage roots form a tower -- wlen(2) = -1, wlen(2 len)^2 = wlen(len),
+ * a sufficient condition, applied conservatively -- lengths from 2^5 run as the two natural-order launches;
+ * every other call runs the forward network with the same table and a bit-reversal gather (three
+ * launches), which is the definition itself relabelled.  The operation trace names the route taken
+ * (NTT_CYCLIC_NATURAL_ORDER / NTT_CYCLIC_FORWARD_NETWORK).
  * d_data: n_vec vectors of 2^log_n words, in place; d_scratch: same size. */
 int fhe_ntt_cyclic(fhe_ctx *ctx, uint64_t *d_data, uint64_t *d_scratch, int log_n, size_t n_vec, uint64_t mod,
                    uint64_t root, int convention, int inverse, void *stream);
@@ -152,7 +159,9 @@ int fhe_ntt_cyclic(fhe_ctx *ctx, uint64_t *d_data, uint64_t *d_scratch, int log_
 /* ---- four-step transform (a6) -------------------------------------------------- */
 /* four_step_ntt(a, N) of reliability_test/four_step_ntt_prot.py:71-109 with N = n1*n2
  * (both powers of two, n1 != n2 allowed): column transforms, twiddle w^(k2 t1), row
- * transforms, transposed output; equals ntt_direct (:49-58).  g = generator (G=3, :17). */
+ * transforms, transposed output; equals ntt_direct (:49-58).  g = generator (G=3, :17): fhe_fourstep_create
+ * returns FHE_ERR_INVALID unless N divides mod - 1 and w = g^((mod-1)/N) has w^(N/2) = -1 (g a quadratic
+ * non-residue of a prime modulus), the plans on which the engine's network is that direct DFT. */
 /* Range: 2 <= n1, n2 <= 2^20, n1 * n2 <= 2^26, mod < 2^61 (FHE_ERR_INVALID / FHE_ERR_UNSUPPORTED beyond).  Up to N = 2^20 the whole flow
  * is ONE natural-order transform of the engine (two launches, no transpose pass); from 2^21 to 2^26 (the reference's default modulus
  * 998244353 admits N up to 2^23) it is the reference's composition itself: transpose, n1 transforms of length n2, the twiddle on the

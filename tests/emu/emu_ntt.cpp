@@ -266,6 +266,42 @@ int emu_fused_size(const PassArgs &a, int logn, int inverse, u32 dist)
     }
 }
 
+// The two launches of the natural-order transform as launch_gs_t makes them (ntt_plan.hpp GsPasses): the gathering inverse row pass
+// fed from the natural-order source, then the inverse column pass on the hand-off buffer; single-launch sizes are the first alone.
+template <class PASS, int E = 0>
+void gs_phases(u64 *base, typename PASS::elem *lds, TwPtr tw, u32 row0, const typename PASS::Arith::Ctx &ctx, const Tw &inv_n, const u64 *from)
+{
+    if constexpr (E < PASS::NPHASE) {
+        for (int tid = 0; tid < PASS::THREADS; tid++) PASS::template phase<E>(tid, base, lds, tw, row0, ctx, inv_n, (NoTap *)nullptr, from);
+        gs_phases<PASS, E + 1>(base, lds, tw, row0, ctx, inv_n, from);
+    }
+}
+
+template <class A, int LOGN>
+void emu_gs(u64 *dst, const u64 *src, const LimbParams &p)
+{
+    typedef GsPasses<A, LOGN> GP;
+    typedef typename GP::First First;
+    const auto ctx = A::make_ctx(p);
+    const TwPtr tw = as_global(p.inv);
+    std::vector<u64> tmp((size_t)1 << LOGN);
+    u64 *first_out = GP::TWO ? tmp.data() : dst;
+    {
+        std::vector<typename First::elem> lds(First::LDS_ELEMS);
+        for (u32 tile = 0; tile < (u32)First::TILES; tile++) gs_phases<First>(first_out, lds.data(), tw, tile * First::TROWS, ctx, p.inv_n, src);
+    }
+    if constexpr (GP::TWO) {
+        typedef typename GP::Second Col;
+        std::vector<typename Col::elem> lds(Col::LDS_ELEMS);
+        PassArgs a{dst, &p, 0u, 1u, 1u, 1u};
+        for (u32 b = 0; b < (u32)Col::TILES; b++) {
+            u32 limb;
+            u64 *base = col_tile<Col, LOGN>(b, a, limb);
+            gs_phases<Col>(base, lds.data(), tw, 0u, ctx, p.inv_n, tmp.data() + (base - dst));
+        }
+    }
+}
+
 u64 invmod(u64 a, u64 m)
 {
     __int128 t = 0, nt = 1, r = m, nr = a % m;
@@ -336,7 +372,35 @@ extern "C" int emu_ntt(u64 *data, int logn, int inverse, int n_poly, int limbs, 
     return path == PATH_F64 ? emu_size<TrackF64>(a, logn, inverse) : emu_size<ArithU64>(a, logn, inverse);
 }
 
-// maxima of the last emu_ntt call (path 0; the integer path leaves them 0): register values, and inverse pair sums
+// Natural-order transform of one vector under the tracker (FP64 path, q < 2^50): dst = scale * W src, src and dst in natural order
+// (dst may equal src).  tw: the cyclic table in canonical residues, tw[2^s + bitrev(k, s)] = w_s^k, laid out and scaled as capi.cpp
+// build_tables does with gs_scale: entry 0 = scale * tw[1], inv_n = scale.
+extern "C" int emu_ntt_gs(u64 *dst, const u64 *src, int logn, u64 q, const u64 *tw, u64 scale)
+{
+    if (logn < 5 || logn > 20 || q < 2 || q >= ((u64)1 << 50)) return -1;
+    const size_t N = (size_t)1 << logn;
+    std::vector<Tw> inv(N);
+    for (size_t k = 1; k < N; k++) inv[tw_stored_index(logn, (u32)k)] = ArithF64::encode(tw[k] % q, q);
+    inv[0] = ArithF64::encode((u64)((unsigned __int128)(scale % q) * (tw[1] % q) % q), q);
+    LimbParams p{};
+    p.q = q;
+    p.two_q = 2 * q;
+    p.n = (double)q;
+    p.ninv = 1.0 / p.n;
+    p.inv_n = ArithF64::encode(scale % q, q);
+    p.fwd = inv.data();
+    p.inv = inv.data();
+    p.path = PATH_F64;
+    g_max_ratio = g_max_pair = 0.0;
+    switch (logn) {
+#define CASE(L) case L: emu_gs<TrackF64, L>(dst, src, p); return 0;
+        CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10) CASE(11) CASE(12) CASE(13) CASE(14) CASE(15) CASE(16) CASE(17) CASE(18) CASE(19) CASE(20)
+#undef CASE
+    default: return -1;
+    }
+}
+
+// maxima of the last emu_ntt / emu_ntt_gs call (path 0; the integer path leaves them 0): register values, and inverse pair sums
 extern "C" double emu_max_ratio() { return g_max_ratio; }
 extern "C" double emu_max_pair() { return g_max_pair; }
 
@@ -423,7 +487,8 @@ struct PassInfo<ColPass<A, ST, LOGN, S0, TC, NT, INV, IN_MODE, OUT_MODE, RED, SB
 };
 
 // form 0: Passes (both launches), 1: FusedPasses, 2: ResidentPass, 3: MidPasses (forward row pass, then inverse row pass),
-// 4: Passes forward with the packed hand-off (canonical residues between the launches)
+// 4: Passes forward with the packed hand-off (canonical residues between the launches),
+// 5: GsPasses, the natural-order route (inverse network only, 2^5 and up): the gathering first launch, then the column pass
 template <int LOGN, bool INV> int sched_form(SchedOut &o, int form)
 {
     typedef ArithF64 A;
@@ -461,6 +526,15 @@ template <int LOGN, bool INV> int sched_form(SchedOut &o, int form)
         if constexpr (LOGN == 16 && !INV) {
             PassInfo<typename PS::Col>::dump(o, IO_CANONICAL, IO_CANONICAL);
             PassInfo<typename PS::Row>::dump(o, IO_CANONICAL, IO_CANONICAL);
+            return 0;
+        }
+        return -1;
+    }
+    if (form == 5) {
+        if constexpr (INV && LOGN >= 5) {
+            typedef GsPasses<A, LOGN> GP;
+            PassInfo<typename GP::First>::dump(o);
+            if constexpr (GP::TWO) PassInfo<typename GP::Second>::dump(o);
             return 0;
         }
         return -1;

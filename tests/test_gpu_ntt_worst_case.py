@@ -1,12 +1,15 @@
 """The FP64 transform on the inputs of tests/helpers/ntt_worst_case.py -- ladders, pulses and the soak patterns, built for the
 largest 50-bit prime and a 30-bit one -- in every form the engine has: the default, the LDS-resident pass, the fused launch, the
-packed hand-off, the fused product, the natural-order four-step and the checked calls.  Every comparison is == against the oracle.
+packed hand-off, the fused product and the checked calls.  The natural-order four-step takes the vectors built for its own table
+(tests/helpers/gs_worst_case.py; tests/test_gpu_natural_order_worst_case.py holds the rest of that route).  Every comparison is ==
+against the oracle.
 
 Sizes: 2^4, 2^9, 2^12 (one, two, three register steps), 2^13 / 2^14 (resident, fused), 2^16 (packed, two-step rows), 2^17
 (three-step rows, last fused size), 2^18 (a fourth stretch of forward stages)."""
 import numpy as np
 import pytest
 
+from helpers import gs_worst_case as G
 from helpers import ntt_worst_case as W
 
 pytestmark = pytest.mark.gpu
@@ -139,21 +142,26 @@ def test_polymul_on_designed_vectors(F, eng, O, logn):
 @pytest.mark.parametrize("n1,n2", [(16, 32), (256, 256)])
 @pytest.mark.parametrize("bits", [50, 30])
 def test_fourstep_on_ladders_and_pulses(F, eng, O, n1, n2, bits):
-    """the natural-order transform (the inverse-structured network with a gathering first launch) on every ladder and every pulse,
-    plain and checked: same words, every flag present and zero.  The oracle's four_step_ntt is the length-N transform with the root
-    g^((q-1)/N); that is checked on the first vector, and the rest are compared with the oracle's O(N log N) form of the same sum."""
+    """the natural-order transform (the inverse-structured network with a gathering first launch) on the vectors designed for ITS
+    table (helpers/gs_worst_case.py: a pulse for every stage of the network, the constant and alternating patterns on its pair
+    structure, spikes, words next to q), plain and checked: same words, every flag present and zero.  The negacyclic ladders and
+    pulses this test once borrowed are solved through other tables and steer nothing here; its name is kept.  The oracle's
+    four_step_ntt is the length-N transform with the root g^((q-1)/N); that is checked on the first vector, and the rest are compared
+    with the oracle's O(N log N) form of the same sum and with the images the designed vectors come with (the cyclic transform)."""
     N = n1 * n2
     logn = N.bit_length() - 1
-    c = _case(O, logn)
-    l = 0 if bits == 50 else 1
-    q = c["qs"][l]
+    L = G.GsLimb(logn, bits)
+    q = L.q
     g = next(x for x in range(2, 1000) if pow(x, (q - 1) // 2, q) == q - 1)
-    idx = [p for p, n in enumerate(c["names"]) if "ladder" in n or "pulse" in n]
+    assert g == L.g
+    fam = G.families(L)
+    idx = list(range(len(fam)))
     assert len(idx) >= 2 * logn + 2
-    x = np.ascontiguousarray(c["data"][idx, l])
+    x = np.stack([v for _, v, *_ in fam])
     w = pow(g, (q - 1) // N, q)
     want = np.stack([O.ntt_nthroot(v, w, q) for v in x])
     assert (want[0] == O.four_step_ntt(x[0], n1, n2, q, g)).all()
+    assert (want == np.stack([L.oracle(v) for v in x])).all()
     fs = F.FourStep(eng, n1, n2, q, g)
     src, dst = eng.upload(x), eng.alloc(x.size)
     fs.ntt(src, dst, len(idx))

@@ -106,12 +106,13 @@ def test_helper_vectors_reach_the_dictated_states(limbs, logn, bits):
 
 
 def test_helper_restates_the_inverse_schedule(emu):
-    """the helper's own statement of the inverse fold schedule (it imports nothing) against what the templates produce"""
+    """the helper's own statement of the inverse fold schedule (it imports nothing) against what the templates produce; form 5 is the
+    natural-order route (GsPasses), whose designed inputs (helpers/gs_worst_case.py) lean on the same "plan" restatement"""
     u32p = C.POINTER(C.c_uint32)
     emu.emu_inv_lazy_plan.restype = C.c_int
     emu.emu_inv_lazy_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, u32p, u32p, C.POINTER(C.c_int)]
     for logn in range(1, 21):
-        for form, kind in ((0, "plan"), (1, "mask"), (2, "resident")):
+        for form, kind in ((0, "plan"), (1, "mask"), (2, "resident"), (5, "plan")):
             passes = _schedule(emu, form, logn, 1)
             if passes is None:
                 continue
