@@ -18,9 +18,14 @@ from .engine import (  # noqa: F401
     Engine,
     FourStep,
     NttTables,
+    SEAL_CLEAN,
     SEAL_P,
     SEAL_RANGE,
+    SEAL_REPAIRED,
     SEAL_SUM,
+    SEAL_SUSPECT,
+    SEAL_TRANSIENT,
+    SEAL_UNCORRECTABLE,
     bConv,
     base_conv_fixed,
     create_moduli,

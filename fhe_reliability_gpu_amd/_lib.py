@@ -173,6 +173,14 @@ _SIG = {
     "fhe_hmult_sealed": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, C.POINTER(vp), vp, C.POINTER(vp), vp, vp]),
     "fhe_rotate_sealed_layout": (ci, [vp, C.POINTER(ci)]),
     "fhe_rotate_sealed": (ci, [vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp, C.POINTER(vp), vp, C.POINTER(vp), vp, vp]),
+    "fhe_seal_locator": (ci, [vp, vp, vp, vp, sz, sz, sz, vp]),
+    "fhe_seal_repair": (ci, [vp, vp, vp, vp, vp, sz, sz, sz, vp, vp, vp]),
+    "fhe_hmult_sealed_repair_layout": (ci, [vp, ci, C.POINTER(ci)]),
+    "fhe_hmult_sealed_repair": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, C.POINTER(vp), C.POINTER(vp), vp, vp, C.POINTER(vp), C.POINTER(vp),
+                                     vp, vp]),
+    "fhe_rotate_sealed_repair_layout": (ci, [vp, C.POINTER(ci)]),
+    "fhe_rotate_sealed_repair": (ci, [vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp, C.POINTER(vp), C.POINTER(vp), vp, vp, C.POINTER(vp), C.POINTER(vp),
+                                      vp, vp]),
     "fhe_ctx_trace": (ci, [vp, ci]),
     "fhe_ctx_trace_read": (ci, [vp, C.c_char_p, sz, C.POINTER(sz)]),
 }

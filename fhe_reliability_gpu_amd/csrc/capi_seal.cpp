@@ -7,6 +7,11 @@
 // seals both outputs, all on one stream.  The flag buffer is
 //     [input rows, in argument order][key rows][the checked call's own block, exactly its layout]
 // and a raised input flag does not stop the call: flags are read by the caller afterwards, as everywhere else.
+//
+// Repair (seal_repair.hip): fhe_seal_locator writes the third sum of a row, fhe_seal_repair is fhe_seal_verify's sweep followed by
+// k_row_repair, and the repairing composites are the sealed composites' own bodies in another mode (RepairMode): each given
+// (seal, locator) pair is repaired in place instead of only verified, the outputs get locators when asked, and one report block
+// follows the flags, covering the input and key rows in the order of their flag words.
 #include "capi_checked.hpp"
 #include "seal_check.hpp"
 
@@ -48,30 +53,62 @@ int seal_fault(const PointFault &f, size_t units, int log_n, BcCheck &k)
     return FHE_OK;
 }
 
-// one operand of a sealed composite: `limbs` rows from table limb 0 on, n_poly polynomials; a null seal is skipped
+// the mode of a sealed composite that repairs its operands and key instead of only verifying them: the locators that go with the
+// seals (HOST arrays as the seals'; entries may be null) -- a null RepairMode is the verifying call
+struct RepairMode {
+    const uint64_t *const *loc_in;
+    const uint64_t *loc_key;
+    uint64_t *const *loc_out;
+};
+
+// one operand of a sealed composite: `limbs` rows from table limb 0 on, n_poly polynomials; a null seal is skipped, a locator
+// makes the rows repaired in place (the words are then written)
 struct SealedRows {
-    const uint64_t *words, *seal;
+    const uint64_t *words, *seal, *locator;
     size_t n_poly, limbs;
     int flag_off;
 };
 
-int verify_rows(hipStream_t st, const fhe_ntt_tables *t, const SealedRows &r, uint32_t *d_flags, u64 *part)
+// d_report = the report block of the whole call, one record of four words per flag word of the input and key rows
+int verify_rows(hipStream_t st, const fhe_ntt_tables *t, const SealedRows &r, uint32_t *d_flags, uint64_t *d_report, u64 *part)
 {
     if (!r.seal) return FHE_OK;
-    hipError_t e = launch_seal_verify(st, seal_args(t, r.words, r.n_poly, r.limbs, 0), part, r.seal, BcCheck{d_flags + r.flag_off, -1, 0, 0, 0});
-    return e == hipSuccess ? FHE_OK : hip_fail(e, "launch_seal_verify");
+    const SealArgs sa = seal_args(t, r.words, r.n_poly, r.limbs, 0);
+    hipError_t e = launch_seal_verify(st, sa, part, r.seal, BcCheck{d_flags + r.flag_off, -1, 0, 0, 0});
+    if (e != hipSuccess) return hip_fail(e, "launch_seal_verify");
+    if (!r.locator) return FHE_OK;
+    e = launch_seal_repair(st, sa, r.seal, r.locator, d_flags + r.flag_off, d_report + 4 * (size_t)r.flag_off);
+    return e == hipSuccess ? FHE_OK : hip_fail(e, "launch_seal_repair");
 }
 
-int seal_outputs(hipStream_t st, const fhe_ntt_tables *t, uint64_t *const *d_seal_out, const uint64_t *d_out0, const uint64_t *d_out1, size_t limbs, u64 *part)
+int seal_outputs(hipStream_t st, const fhe_ntt_tables *t, uint64_t *const *d_seal_out, uint64_t *const *d_loc_out, const uint64_t *d_out0,
+                 const uint64_t *d_out1, size_t limbs, u64 *part)
 {
     const uint64_t *outs[2] = {d_out0, d_out1};
     for (int h = 0; h < 2; h++) {
-        if (!d_seal_out || !d_seal_out[h]) continue;
-        hipError_t e = launch_seal(st, seal_args(t, outs[h], 1, limbs, 0), part, d_seal_out[h], BcCheck{nullptr, -1, 0, 0, 0});
-        if (e != hipSuccess) return hip_fail(e, "launch_seal");
+        if (d_seal_out && d_seal_out[h]) {
+            hipError_t e = launch_seal(st, seal_args(t, outs[h], 1, limbs, 0), part, d_seal_out[h], BcCheck{nullptr, -1, 0, 0, 0});
+            if (e != hipSuccess) return hip_fail(e, "launch_seal");
+        }
+        if (d_loc_out && d_loc_out[h]) {
+            hipError_t e = launch_seal_locator(st, seal_args(t, outs[h], 1, limbs, 0), part, d_loc_out[h]);
+            if (e != hipSuccess) return hip_fail(e, "launch_seal_locator");
+        }
     }
     return FHE_OK;
 }
+
+// a repairing call takes seal and locator of an operand together or not at all
+bool unpaired(const RepairMode *rm, const uint64_t *const *d_seal_in, int n, const uint64_t *d_seal_key)
+{
+    if (!rm) return false;
+    for (int i = 0; i < n; i++)
+        if (!(d_seal_in && d_seal_in[i]) != !(rm->loc_in && rm->loc_in[i])) return true;
+    return !d_seal_key != !rm->loc_key;
+}
+
+// where the report block of a repairing composite starts, in flag words: 16-byte aligned after the sealed call's layout
+int report_offset(int sealed_total) { return (sealed_total + 3) & ~3; }
 
 // the form of the checked call a sealed composite runs, with that form's hook records
 struct SealedForm {
@@ -146,6 +183,47 @@ int fhe_seal_verify(fhe_ctx *ctx, const uint64_t *d_words, const uint64_t *d_sea
     return e == hipSuccess ? FHE_OK : hip_fail(e, "launch_seal_verify");
 }
 
+int fhe_seal_locator(fhe_ctx *ctx, uint64_t *d_locator, const uint64_t *d_words, const fhe_ntt_tables *t, size_t n_poly, size_t limbs, size_t start_idx,
+                     void *stream)
+{
+    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
+    if (!d_locator || !d_words) return fail(FHE_ERR_INVALID, "null argument");
+    int rc = seal_window(t, d_words, n_poly, limbs, start_idx);
+    if (rc) return rc;
+    const size_t units = n_poly * limbs;
+    if (!units) return FHE_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    u64 *part;
+    if ((rc = seal_scratch(ctx, seal_part_words((u32)units, t->log_n), &part))) return rc;
+    hipError_t e = launch_seal_locator(pick(ctx, stream), seal_args(t, d_words, n_poly, limbs, start_idx), part, d_locator);
+    return e == hipSuccess ? FHE_OK : hip_fail(e, "launch_seal_locator");
+}
+
+int fhe_seal_repair(fhe_ctx *ctx, uint64_t *d_words, const uint64_t *d_seal, const uint64_t *d_locator, const fhe_ntt_tables *t, size_t n_poly,
+                    size_t limbs, size_t start_idx, uint32_t *d_flags, uint64_t *d_report, void *stream)
+{
+    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
+    const PointFault f = ctx->seal_fault.take();      // one shot, whatever the outcome
+    if (!d_seal || !d_words || !d_flags || !d_locator || !d_report) return fail(FHE_ERR_INVALID, "null argument");
+    int rc = seal_window(t, d_words, n_poly, limbs, start_idx);
+    if (rc) return rc;
+    if ((uintptr_t)d_report % 16) return fail(FHE_ERR_INVALID, "a report record is written 16 bytes at a time: the buffer must be 16-byte aligned");
+    const size_t units = n_poly * limbs;
+    BcCheck k{d_flags, -1, 0, 0, 0};
+    if ((rc = seal_fault(f, units, t->log_n, k))) return rc;
+    if (!units) return FHE_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = pick(ctx, stream);
+    u64 *part;
+    if ((rc = seal_scratch(ctx, seal_part_words((u32)units, t->log_n), &part))) return rc;
+    HIP_TRY(hipMemsetAsync(d_flags, 0, units * sizeof(u32), st));
+    const SealArgs sa = seal_args(t, d_words, n_poly, limbs, start_idx);
+    hipError_t e = launch_seal_verify(st, sa, part, d_seal, k);      // the hook lives in this sweep only
+    if (e != hipSuccess) return hip_fail(e, "launch_seal_verify");
+    e = launch_seal_repair(st, sa, d_seal, d_locator, d_flags, d_report);
+    return e == hipSuccess ? FHE_OK : hip_fail(e, "launch_seal_repair");
+}
+
 int fhe_hmult_sealed_layout(const fhe_keyswitch *p, int rescale, int out[8])
 {
     if (!p || !out) return fail(FHE_ERR_INVALID, "null argument");
@@ -160,9 +238,10 @@ int fhe_hmult_sealed_layout(const fhe_keyswitch *p, int rescale, int out[8])
     return FHE_OK;
 }
 
-int fhe_hmult_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_a0, const uint64_t *d_a1,
-                     const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a,
-                     const uint64_t *const *d_seal_in, const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
+// fhe_hmult_sealed (rm == nullptr) and fhe_hmult_sealed_repair
+static int hmult_sealed_body(const RepairMode *rm, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_a0,
+                             const uint64_t *d_a1, const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a,
+                             const uint64_t *const *d_seal_in, const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
     const SealedForm f = sealed_form(p);
@@ -175,9 +254,13 @@ int fhe_hmult_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t 
         const int rc = checked(d_flags);      // refuses before its first launch
         return rc ? rc : fail(FHE_ERR_INVALID, "sealed multiply: bad argument");
     }
-    if (misaligned({d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key})) {
+    if (misaligned({d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rm ? d_flags : nullptr})) {
         (void)checked(nullptr);      // takes the hooks, launches nothing
         return fail(FHE_ERR_INVALID, "sealed rows are read 16 bytes at a time: the buffers must be 16-byte aligned");
+    }
+    if (unpaired(rm, d_seal_in, 4, d_seal_key)) {
+        (void)checked(nullptr);
+        return fail(FHE_ERR_INVALID, "a repairing call takes an operand's seal and locator together");
     }
     int lay[8], rc;
     if ((rc = fhe_hmult_sealed_layout(p, rescale, lay))) return rc;
@@ -186,13 +269,46 @@ int fhe_hmult_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t 
     u64 *part;
     if ((rc = sealed_scratch(ctx, p, &part))) return rc;
     HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)lay[5] * sizeof(u32), st));
+    uint64_t *d_report = rm ? reinterpret_cast<uint64_t *>(d_flags + report_offset(lay[6])) : nullptr;
+    if (rm) HIP_TRY(hipMemsetAsync(d_report, 0, (size_t)lay[5] * 4 * sizeof(u64), st));      // rows without a seal report CLEAN
     const size_t L = p->L;
     const uint64_t *ops[4] = {d_a0, d_a1, d_b0, d_b1};
-    for (int i = 0; i < 4; i++)
-        if ((rc = verify_rows(st, p->t, SealedRows{ops[i], d_seal_in ? d_seal_in[i] : nullptr, 1, L, lay[i]}, d_flags, part))) return rc;
-    if ((rc = verify_rows(st, p->t, SealedRows{d_relin_key, d_seal_key, (size_t)p->dnum * 2, L + p->K, lay[4]}, d_flags, part))) return rc;
+    for (int i = 0; i < 4; i++) {
+        const SealedRows r{ops[i], d_seal_in ? d_seal_in[i] : nullptr, rm && rm->loc_in ? rm->loc_in[i] : nullptr, 1, L, lay[i]};
+        if ((rc = verify_rows(st, p->t, r, d_flags, d_report, part))) return rc;
+    }
+    const SealedRows key{d_relin_key, d_seal_key, rm ? rm->loc_key : nullptr, (size_t)p->dnum * 2, L + p->K, lay[4]};
+    if ((rc = verify_rows(st, p->t, key, d_flags, d_report, part))) return rc;
     if ((rc = checked(d_flags + lay[5]))) return rc;
-    return seal_outputs(st, p->t, d_seal_out, d_out0, d_out1, rescale ? L - 1 : L, part);
+    return seal_outputs(st, p->t, d_seal_out, rm ? rm->loc_out : nullptr, d_out0, d_out1, rescale ? L - 1 : L, part);
+}
+
+int fhe_hmult_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_a0, const uint64_t *d_a1,
+                     const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a,
+                     const uint64_t *const *d_seal_in, const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
+{
+    return hmult_sealed_body(nullptr, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, d_seal_in, d_seal_key, d_seal_out, d_flags,
+                             stream);
+}
+
+int fhe_hmult_sealed_repair_layout(const fhe_keyswitch *p, int rescale, int out[10])
+{
+    int rc = fhe_hmult_sealed_layout(p, rescale, out);
+    if (rc) return rc;
+    out[7] = report_offset(out[6]);
+    out[8] = out[7] + 8 * out[5];
+    out[9] = 0;
+    return FHE_OK;
+}
+
+int fhe_hmult_sealed_repair(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, uint64_t *d_a0, uint64_t *d_a1, uint64_t *d_b0,
+                            uint64_t *d_b1, uint64_t *d_relin_key, int rescale, const fhe_abft *a, const uint64_t *const *d_seal_in,
+                            const uint64_t *const *d_locator_in, const uint64_t *d_seal_key, const uint64_t *d_locator_key,
+                            uint64_t *const *d_seal_out, uint64_t *const *d_locator_out, uint32_t *d_flags, void *stream)
+{
+    const RepairMode rm{d_locator_in, d_locator_key, d_locator_out};
+    return hmult_sealed_body(&rm, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, d_seal_in, d_seal_key, d_seal_out, d_flags,
+                             stream);
 }
 
 int fhe_rotate_sealed_layout(const fhe_keyswitch *p, int out[6])
@@ -207,9 +323,10 @@ int fhe_rotate_sealed_layout(const fhe_keyswitch *p, int out[6])
     return FHE_OK;
 }
 
-int fhe_rotate_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0, const uint64_t *d_c1,
-                      uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, const uint64_t *const *d_seal_in,
-                      const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
+// fhe_rotate_sealed (rm == nullptr) and fhe_rotate_sealed_repair
+static int rotate_sealed_body(const RepairMode *rm, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0,
+                              const uint64_t *d_c1, uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, const uint64_t *const *d_seal_in,
+                              const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
     const SealedForm f = sealed_form(p);
@@ -220,9 +337,13 @@ int fhe_rotate_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t
         const int rc = checked(d_flags);      // refuses before its first launch
         return rc ? rc : fail(FHE_ERR_INVALID, "sealed rotation: bad argument");
     }
-    if (misaligned({d_out0, d_out1, d_c0, d_c1, d_galois_key})) {
+    if (misaligned({d_out0, d_out1, d_c0, d_c1, d_galois_key, rm ? d_flags : nullptr})) {
         (void)checked(nullptr);      // takes the hook, launches nothing
         return fail(FHE_ERR_INVALID, "sealed rows are read 16 bytes at a time: the buffers must be 16-byte aligned");
+    }
+    if (unpaired(rm, d_seal_in, 2, d_seal_key)) {
+        (void)checked(nullptr);
+        return fail(FHE_ERR_INVALID, "a repairing call takes an operand's seal and locator together");
     }
     int lay[6], rc;
     if ((rc = fhe_rotate_sealed_layout(p, lay))) return rc;
@@ -231,13 +352,44 @@ int fhe_rotate_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t
     u64 *part;
     if ((rc = sealed_scratch(ctx, p, &part))) return rc;
     HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)lay[3] * sizeof(u32), st));
+    uint64_t *d_report = rm ? reinterpret_cast<uint64_t *>(d_flags + report_offset(lay[4])) : nullptr;
+    if (rm) HIP_TRY(hipMemsetAsync(d_report, 0, (size_t)lay[3] * 4 * sizeof(u64), st));      // rows without a seal report CLEAN
     const size_t L = p->L;
     const uint64_t *ops[2] = {d_c0, d_c1};
-    for (int i = 0; i < 2; i++)
-        if ((rc = verify_rows(st, p->t, SealedRows{ops[i], d_seal_in ? d_seal_in[i] : nullptr, 1, L, lay[i]}, d_flags, part))) return rc;
-    if ((rc = verify_rows(st, p->t, SealedRows{d_galois_key, d_seal_key, (size_t)p->dnum * 2, L + p->K, lay[2]}, d_flags, part))) return rc;
+    for (int i = 0; i < 2; i++) {
+        const SealedRows r{ops[i], d_seal_in ? d_seal_in[i] : nullptr, rm && rm->loc_in ? rm->loc_in[i] : nullptr, 1, L, lay[i]};
+        if ((rc = verify_rows(st, p->t, r, d_flags, d_report, part))) return rc;
+    }
+    const SealedRows key{d_galois_key, d_seal_key, rm ? rm->loc_key : nullptr, (size_t)p->dnum * 2, L + p->K, lay[2]};
+    if ((rc = verify_rows(st, p->t, key, d_flags, d_report, part))) return rc;
     if ((rc = checked(d_flags + lay[3]))) return rc;
-    return seal_outputs(st, p->t, d_seal_out, d_out0, d_out1, L, part);
+    return seal_outputs(st, p->t, d_seal_out, rm ? rm->loc_out : nullptr, d_out0, d_out1, L, part);
+}
+
+int fhe_rotate_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0, const uint64_t *d_c1,
+                      uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, const uint64_t *const *d_seal_in,
+                      const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
+{
+    return rotate_sealed_body(nullptr, ctx, p, d_out0, d_out1, d_c0, d_c1, galois_elt, d_galois_key, a, d_seal_in, d_seal_key, d_seal_out, d_flags, stream);
+}
+
+int fhe_rotate_sealed_repair_layout(const fhe_keyswitch *p, int out[8])
+{
+    int rc = fhe_rotate_sealed_layout(p, out);
+    if (rc) return rc;
+    out[5] = report_offset(out[4]);
+    out[6] = out[5] + 8 * out[3];
+    out[7] = 0;
+    return FHE_OK;
+}
+
+int fhe_rotate_sealed_repair(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, uint64_t *d_c0, uint64_t *d_c1, uint32_t galois_elt,
+                             uint64_t *d_galois_key, const fhe_abft *a, const uint64_t *const *d_seal_in, const uint64_t *const *d_locator_in,
+                             const uint64_t *d_seal_key, const uint64_t *d_locator_key, uint64_t *const *d_seal_out, uint64_t *const *d_locator_out,
+                             uint32_t *d_flags, void *stream)
+{
+    const RepairMode rm{d_locator_in, d_locator_key, d_locator_out};
+    return rotate_sealed_body(&rm, ctx, p, d_out0, d_out1, d_c0, d_c1, galois_elt, d_galois_key, a, d_seal_in, d_seal_key, d_seal_out, d_flags, stream);
 }
 
 } // extern "C"

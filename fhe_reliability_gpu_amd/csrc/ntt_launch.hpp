@@ -365,4 +365,12 @@ hipError_t launch_seal(hipStream_t st, const SealArgs &p, u64 *part, u64 *seal, 
 // k.flags[unit] |= SEAL_SUM where the row's sums differ from seal[unit], SEAL_RANGE where a word is >= q_l; zeroed by the caller
 hipError_t launch_seal_verify(hipStream_t st, const SealArgs &p, u64 *part, const u64 *seal, const BcCheck &k);
 
+// ---- seal_repair.hip: the locator sum S2 per row and the repair of one corrupted word per row (seal_check.hpp) ----
+// locator[unit] = S2, canonical; part as launch_seal's (half of it is used)
+hipError_t launch_seal_locator(hipStream_t st, const SealArgs &p, u64 *part, u64 *locator);
+// after launch_seal_verify filled flags: every row with a raised flag is re-read, decided (seal_decide) and, where exactly one word
+// is named, corrected in place and confirmed; flags[unit] = 0 after a confirmed repair or a clean re-read, untouched otherwise;
+// report[unit] = {status, index, word before, word after}.  p.x is written: the caller owns it as mutable memory
+hipError_t launch_seal_repair(hipStream_t st, const SealArgs &p, const u64 *seal, const u64 *locator, u32 *flags, u64 *report);
+
 } // namespace fhe

@@ -18,9 +18,6 @@
 
 namespace fhe {
 
-// chunks per row, as a shift
-__host__ __device__ inline int seal_log_chunks(int logn) { return logn > SEAL_LOG_CHUNK ? logn - SEAL_LOG_CHUNK : 0; }
-
 size_t seal_part_words(u32 units, int logn) { return ((size_t)units << seal_log_chunks(logn)) * 2; }
 
 // k.flags = [units] (VERIFY only); k.fault_unit = the row, k.fault_coeff = the word; part = [units][chunks][2]

@@ -20,6 +20,8 @@ _U64 = np.uint64
 # seals of rows at rest (seal_check.hpp): the modulus of the two sums, and the flag bits of a verification
 SEAL_P = (1 << 61) - 1
 SEAL_SUM, SEAL_RANGE = 1, 2
+# outcomes of a repair, per row (FHE_SEAL_* of fhe_mi355x.h): word 0 of a report record {outcome, index, word before, word after}
+SEAL_CLEAN, SEAL_REPAIRED, SEAL_UNCORRECTABLE, SEAL_TRANSIENT, SEAL_SUSPECT = 0, 1, 2, 3, 4
 
 
 def _arr(x) -> np.ndarray:
@@ -263,6 +265,27 @@ class NttTables:
         limbs = len(self) - start if limbs is None else limbs
         return _checked_flags(self.eng, n_poly * limbs, lambda fl: lib.fhe_seal_verify(self.eng._h, d.ptr, seal.ptr, self._h, n_poly, limbs, start, fl.ptr,
                                                                                        stream), stream)
+
+    def seal_locator(self, d: DeviceArray, limbs=None, start=0, n_poly=1, stream=None) -> DeviceArray:
+        """The locator sums of the rows of ``d``: a device array ``[n_poly * limbs]`` of S2 = sum (j + 1)^2 x_j modulo 2^61 - 1,
+        canonical.  Kept beside the seal, it makes a row's three sums a single-error-correcting code (``seal_repair``)."""
+        limbs = len(self) - start if limbs is None else limbs
+        out = self.eng.alloc(n_poly * limbs)
+        check(lib.fhe_seal_locator(self.eng._h, out.ptr, d.ptr, self._h, n_poly, limbs, start, stream))
+        return out
+
+    def seal_repair(self, d: DeviceArray, seal: DeviceArray, locator: DeviceArray, limbs=None, start=0, n_poly=1, stream=None):
+        """``seal_verify`` followed by the repair of every flagged row, in place, on the device: ``(flags, report)``.  ``report`` is
+        uint64 ``[rows][4]`` = {outcome, index, word before, word after} with the outcomes ``SEAL_CLEAN`` / ``SEAL_REPAIRED`` /
+        ``SEAL_UNCORRECTABLE`` / ``SEAL_TRANSIENT`` / ``SEAL_SUSPECT``; ``flags`` are ``seal_verify``'s, cleared again for repaired
+        and transient rows.  One corrupted word per row, any 64-bit pattern, is restored exactly; two corrupted words in a row are
+        never written to; a corrupted seal or locator word never causes a write (seal_check.hpp)."""
+        limbs = len(self) - start if limbs is None else limbs
+        rows = n_poly * limbs
+        report = self.eng.upload(np.full(max(rows, 1) * 4, 0xA5A5A5A5A5A5A5A5, dtype=_U64))
+        flags = _checked_flags(self.eng, rows, lambda fl: lib.fhe_seal_repair(self.eng._h, d.ptr, seal.ptr, locator.ptr, self._h, n_poly, limbs, start,
+                                                                              fl.ptr, report.ptr, stream), stream)
+        return flags, report.download()[:rows * 4].reshape(rows, 4)
 
     def polymul(self, c: DeviceArray, a: DeviceArray, b: DeviceArray, limbs=None, start=0, n_poly=1, stream=None):
         limbs = len(self) - start if limbs is None else limbs
@@ -1057,6 +1080,78 @@ class KeySwitch:
         kl = self._ks_layout(bool(self.plain_modulus))
         flags["checked"] = self._split_flags(f, kl, base=lay["checked"])
         return o0, o1, so, flags
+
+    # ---- the same composites repairing their operands and key in place (seal_repair.hip) ----
+    def seal_key_locator(self, key: DeviceArray, stream=None) -> DeviceArray:
+        """The locator sums of a relinearisation or Galois key: ``[dnum * 2 * (L + K)]``, beside ``seal_key``."""
+        return self.t.seal_locator(key, limbs=self.L + self.K, start=0, n_poly=2 * self.dnum, stream=stream)
+
+    def _repair_layout(self, out, lay, n):
+        lay["report"], lay["flags_total"], lay["total"] = int(out[n]), lay["total"], int(out[n + 1])
+        return lay
+
+    def hmult_sealed_repair_layout(self, rescale: bool = True):
+        """``hmult_sealed_layout`` plus ``"report"``: the offset, in flag words, of the report block ``[rows][4]`` uint64 over the
+        input and key rows in the order of their flag words; ``"flags_total"`` is the sealed layout's total, ``"total"`` includes
+        the report block."""
+        out = (C.c_int * 10)()
+        check(lib.fhe_hmult_sealed_repair_layout(self._h, 1 if rescale else 0, out))
+        return self._repair_layout(out, self._sealed_layout(out, ("a0", "a1", "b0", "b1"), 5, 6), 7)
+
+    def rotate_sealed_repair_layout(self):
+        """``rotate_sealed_layout`` plus the report block, as ``hmult_sealed_repair_layout``."""
+        out = (C.c_int * 8)()
+        check(lib.fhe_rotate_sealed_repair_layout(self._h, out))
+        return self._repair_layout(out, self._sealed_layout(out, ("c0", "c1"), 3, 4), 5)
+
+    def _sealed_repair(self, lay, names, limbs, seals, locators, call, stream):
+        """Run ``call(o0, o1, seal_in, loc_in, seal_out, loc_out, flags)``; returns (o0, o1, seals, locators, flat flags, reports)."""
+        o0, o1 = self._out(limbs), self._out(limbs)
+        so, lo = [self.eng.alloc(2 * limbs) for _ in range(2)], [self.eng.alloc(limbs) for _ in range(2)]
+        for x in so:
+            x.shape = (limbs, 2)
+        ptrs = lambda xs: (vp * len(names))(*[x.ptr if x is not None else None for x in (tuple(xs) if xs is not None else (None,) * len(names))])
+        sout, lout = (vp * 2)(so[0].ptr, so[1].ptr), (vp * 2)(lo[0].ptr, lo[1].ptr)
+        flags = _flag_buffer(self.eng, lay["total"])
+        check(call(o0, o1, ptrs(seals), ptrs(locators), sout, lout, flags))
+        raw = _read_flags(flags, lay["total"], stream).copy()
+        rows = lay["checked"]
+        report = raw[lay["report"]:lay["report"] + 8 * rows].view(np.uint64).reshape(rows, 4)
+        reports = {name: report[lay[name][0]:lay[name][0] + int(np.prod(lay[name][1]))].reshape(lay[name][1] + (4,)).copy() for name in names + ("key",)}
+        return o0, o1, tuple(so), tuple(lo), raw, reports
+
+    def hmult_sealed_repair(self, a0: DeviceArray, a1: DeviceArray, b0: DeviceArray, b1: DeviceArray, relin_key: DeviceArray, abft: "Abft",
+                            seals=None, locators=None, key_seal: Optional[DeviceArray] = None, key_locator: Optional[DeviceArray] = None,
+                            rescale: bool = True, stream=None):
+        """``hmult_sealed`` with every given (seal, locator) pair repaired in place instead of only verified -- the operands and the
+        key may be WRITTEN: ``(out0, out1, (seal0, seal1), (locator0, locator1), flags, reports)``.  ``locators`` go with ``seals``
+        entry by entry (``NttTables.seal_locator``), ``key_locator`` with ``key_seal`` (``seal_key_locator``).  ``flags`` as
+        ``hmult_sealed``: a repaired row's flag is clear again, an uncorrectable or suspect row's stays raised and does not stop the
+        call.  ``reports = {"a0", ..., "key": [...][4]}`` = {outcome, index, word before, word after} per row."""
+        names = ("a0", "a1", "b0", "b1")
+        lay = self.hmult_sealed_repair_layout(rescale)
+        o0, o1, so, lo, f, rep = self._sealed_repair(lay, names, self.L - 1 if rescale else self.L, seals, locators,
+                                                     lambda o0, o1, sin, lin, sout, lout, fl: lib.fhe_hmult_sealed_repair(
+            self.eng._h, self._h, o0.ptr, o1.ptr, a0.ptr, a1.ptr, b0.ptr, b1.ptr, relin_key.ptr, 1 if rescale else 0, abft._h, sin, lin,
+            key_seal.ptr if key_seal is not None else None, key_locator.ptr if key_locator is not None else None, sout, lout, fl.ptr, stream), stream)
+        flags = self._split_flags(f, lay, names + ("key",))
+        flags["checked"] = self._hmult_flags(bool(self.plain_modulus), f, rescale, lay["checked"])
+        return o0, o1, so, lo, flags, rep
+
+    def rotate_sealed_repair(self, c0: DeviceArray, c1: DeviceArray, galois_elt: int, galois_key: DeviceArray, abft: "Abft", seals=None, locators=None,
+                             key_seal: Optional[DeviceArray] = None, key_locator: Optional[DeviceArray] = None, stream=None):
+        """``rotate_sealed`` with every given (seal, locator) pair repaired in place: ``(out0, out1, seals, locators, flags,
+        reports)`` as ``hmult_sealed_repair``."""
+        names = ("c0", "c1")
+        lay = self.rotate_sealed_repair_layout()
+        o0, o1, so, lo, f, rep = self._sealed_repair(lay, names, self.L, seals, locators,
+                                                     lambda o0, o1, sin, lin, sout, lout, fl: lib.fhe_rotate_sealed_repair(
+            self.eng._h, self._h, o0.ptr, o1.ptr, c0.ptr, c1.ptr, galois_elt, galois_key.ptr, abft._h, sin, lin,
+            key_seal.ptr if key_seal is not None else None, key_locator.ptr if key_locator is not None else None, sout, lout, fl.ptr, stream), stream)
+        flags = self._split_flags(f, lay, names + ("key",))
+        kl = self._ks_layout(bool(self.plain_modulus))
+        flags["checked"] = self._split_flags(f, kl, base=lay["checked"])
+        return o0, o1, so, lo, flags, rep
 
     def __del__(self):
         try:

@@ -11,7 +11,13 @@ measures detection, it decrypts nothing.  Unlike the reference, the bits flipped
 a flip changes memory.  Trial 0 flips nothing (control).  The product has L - 1 limbs, so the rotation rounds run on a second plan
 over the remaining primes.  Exit status 1 when a trial with at least one flip was not detected.
 
-python -m fhe_reliability_gpu_amd.tools.flip_coverage [--trials 32] [--num-symbols 1] [--bits-per-symbol 1] [--logn 14] [--row 8] [--seed 1]"""
+--repair runs the same experiment through the repairing composites (hmult_sealed_repair, rotate_sealed_repair): operands and keys
+carry locators beside their seals, and per trial the tool prints how many rows were corrected, how many were left uncorrectable or
+suspect, whether the trial was missed (a flip, no repair and no flag), and whether the final words equal the fault-free run's bit for
+bit.  One flipped word per row is corrected and the chain then computes the clean result; two or more symbols in one row stay
+uncorrectable, as the flags say.  Exit status 1 when a trial was missed, or was reported all corrected with a final result that differs.
+
+python -m fhe_reliability_gpu_amd.tools.flip_coverage [--repair] [--trials 32] [--num-symbols 1] [--bits-per-symbol 1] [--logn 14] [--row 8] [--seed 1]"""
 import argparse
 import sys
 
@@ -41,6 +47,7 @@ def main():
     ap.add_argument("--logn", type=int, default=14)
     ap.add_argument("--row", type=int, default=8, help="slots summed by the rotate-and-add rounds (a power of two)")
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--repair", action="store_true", help="run the chain through the repairing composites and report corrections")
     a = ap.parse_args()
     if a.row < 1 or a.row & (a.row - 1) or not 1 <= a.bits_per_symbol <= 64 or a.num_symbols < 0:
         ap.error("row is a power of two, bits-per-symbol 1..64, num-symbols >= 0")
@@ -67,6 +74,9 @@ def main():
     s_b = t.seal(d_b, limbs=L, n_poly=2)
     s_rlk, s_gk = ks.seal_key(d_rlk), [ks2.seal_key(g) for g in d_gk]
     s_a = t.seal(eng.upload(ct_a), limbs=L, n_poly=2)
+    if a.repair:      # the locators that travel with the seals
+        l_b, l_a = t.seal_locator(d_b, limbs=L, n_poly=2), t.seal_locator(eng.upload(ct_a), limbs=L, n_poly=2)
+        l_rlk, l_gk = ks.seal_key_locator(d_rlk), [ks2.seal_key_locator(g) for g in d_gk]
     part = lambda d, i, limbs: _view(eng, d, i * limbs * N, limbs * N)
     seal_part = lambda s, i, limbs: _view(eng, s, i * limbs * 2, limbs * 2)
 
@@ -86,8 +96,39 @@ def main():
                 sc[h] = t2.seal(c[h], limbs=R)
         return np.concatenate([c[0].download().reshape(-1), c[1].download().reshape(-1)]), raised
 
+    def outcomes(reports, tally):
+        for rep in reports.values():
+            for status in np.asarray(rep).reshape(-1, 4)[:, 0].tolist():
+                tally[int(status)] = tally.get(int(status), 0) + 1
+
+    def chain_repair(d_a):
+        """the same chain through the repairing composites; returns the final parts, the raised flag words and the outcome tally"""
+        raised, tally = 0, {}
+        loc_part = lambda s, i, limbs: _view(eng, s, i * limbs, limbs)
+        o0, o1, so, lo, fl, rep = ks.hmult_sealed_repair(
+            part(d_a, 0, L), part(d_a, 1, L), part(d_b, 0, L), part(d_b, 1, L), d_rlk, ab,
+            seals=[seal_part(s_a, 0, L), seal_part(s_a, 1, L), seal_part(s_b, 0, L), seal_part(s_b, 1, L)],
+            locators=[loc_part(l_a, 0, L), loc_part(l_a, 1, L), loc_part(l_b, 0, L), loc_part(l_b, 1, L)], key_seal=s_rlk, key_locator=l_rlk)
+        raised += nonzero(fl)
+        outcomes(rep, tally)
+        c, sc, lc = [o0, o1], list(so), list(lo)
+        for elt, gk, sgk, lgk in zip(elts, d_gk, s_gk, l_gk):
+            r0, r1, sr, lr, fl, rep = ks2.rotate_sealed_repair(c[0], c[1], elt, gk, ab2, seals=sc, locators=lc, key_seal=sgk, key_locator=lgk)
+            raised += nonzero(fl)
+            outcomes(rep, tally)
+            for h, (rot, srot, lrot) in enumerate(((r0, sr[0], lr[0]), (r1, sr[1], lr[1]))):
+                for words, seal, loc in ((c[h], sc[h], lc[h]), (rot, srot, lrot)):
+                    f, rp = t2.seal_repair(words, seal, loc, limbs=R)
+                    raised += nonzero(f)
+                    outcomes({"rows": rp}, tally)
+                raised += nonzero(t2.modadd_checked(c[h], c[h], rot, limbs=R))
+                sc[h], lc[h] = t2.seal(c[h], limbs=R), t2.seal_locator(c[h], limbs=R)
+        return np.concatenate([c[0].download().reshape(-1), c[1].download().reshape(-1)]), raised, tally
+
     clean, raised = chain(eng.upload(ct_a))
     assert raised == 0, "the clean chain raised a flag"
+    if a.repair:
+        return main_repair(a, eng, rng, ct_a, clean, chain_repair)
     print(f"N = 2^{a.logn}, L = {L}, K = {K}, dnum = {DNUM}, plain modulus {PLAIN_MODULUS}; {rounds} rotate-and-add rounds; "
           f"{a.num_symbols} symbols x {a.bits_per_symbol} bits per trial")
     missed = 0
@@ -108,6 +149,39 @@ def main():
     eng.check()
     print(f"summary: {a.trials} trials, {missed} with a flip and no flag")
     return 1 if missed else 0
+
+
+def main_repair(a, eng, rng, ct_a, clean, chain_repair):
+    """the trials of --repair: the same flips, the chain through the repairing composites"""
+    out, raised, tally = chain_repair(eng.upload(ct_a))
+    assert raised == 0 and (out == clean).all() and set(tally) <= {F.SEAL_CLEAN}, "the clean repairing chain differs from the sealed chain"
+    print(f"N = 2^{a.logn}, L = {L}, K = {K}, dnum = {DNUM}, plain modulus {PLAIN_MODULUS}; repairing chain; {a.num_symbols} symbols x {a.bits_per_symbol} bits per trial")
+    missed = wrong = 0
+    totals = {"corrected": 0, "uncorrectable": 0, "missed": 0, "exact": 0}
+    for trial in range(a.trials):
+        d_a = eng.upload(ct_a)
+        n_sym = 0 if trial == 0 else a.num_symbols
+        for idx in rng.integers(0, ct_a.size, n_sym):
+            for bit in rng.choice(64, a.bits_per_symbol, replace=False):
+                check(lib.fhe_flip_bit(eng._h, d_a.ptr, int(idx), int(bit), None))
+        flipped = int(np.count_nonzero(d_a.download().reshape(-1) != ct_a.reshape(-1)))
+        out, raised, tally = chain_repair(d_a)
+        corrected = tally.get(F.SEAL_REPAIRED, 0)
+        refused = tally.get(F.SEAL_UNCORRECTABLE, 0) + tally.get(F.SEAL_SUSPECT, 0)
+        exact = bool((out == clean).all())
+        miss = flipped > 0 and corrected == 0 and raised == 0
+        missed += miss
+        wrong += flipped > 0 and raised == 0 and not exact      # said to be all corrected, yet the result differs
+        assert flipped > 0 or (exact and corrected == 0 and raised == 0), "the control trial differs from the clean run"
+        verdict = "missed" if miss else "uncorrectable" if raised else "corrected" if corrected else "clean"
+        for k, v in (("corrected", verdict == "corrected"), ("uncorrectable", verdict == "uncorrectable"), ("missed", miss), ("exact", exact)):
+            totals[k] += int(v)
+        print(f"trial {trial:3d}: flipped words {flipped:3d}, rows corrected {corrected:3d}, rows uncorrectable or suspect {refused:3d}, raised flag words {raised:4d}, "
+              f"{verdict}, final words equal the fault-free run: {'yes' if exact else 'no'}", flush=True)
+    eng.check()
+    print(f"summary: {a.trials} trials (one control): {totals['corrected']} corrected, {totals['uncorrectable']} uncorrectable, {totals['missed']} missed; "
+          f"{totals['exact']} final results equal the fault-free run bit for bit; {wrong} reported corrected with a differing result")
+    return 1 if missed or wrong else 0
 
 
 class _View:

@@ -917,6 +917,66 @@ int fhe_rotate_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t
                       uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, const uint64_t *const *d_seal_in /* [2] */,
                       const uint64_t *d_seal_key, uint64_t *const *d_seal_out /* [2] */, uint32_t *d_flags, void *stream);
 
+/* ---- repair: locate and correct one corrupted word per sealed row ------------------------------------------------
+ * A raised seal flag so far left the caller nothing to do but discard the operand.  A third sum per row, the locator
+ *     S2 = sum_j (j + 1)^2 x_j mod p,
+ * kept beside the seal as uint64_t [rows] (canonical), makes {S0, S1, S2} a single-error-correcting code.  With the syndromes
+ * D_i = (sum of the row as it is now) - (stored sum), a change d in one word j gives D0 = d, D1 = w d, D2 = w^2 d with w = j + 1:
+ * w = D1 / D0 names the word and x = x' - d restores it exactly, since x < q < p.  The locator is required because two sums are not
+ * safe: the same bit set in words j1, j2 with j1 + j2 even gives D1 / D0 = the midpoint's weight, and an intact word would be
+ * "corrected" into a row that passes its seal.  For two changed words D1^2 - D0 D2 = -d1 d2 (w1 - w2)^2 is non-zero modulo the prime
+ * p, so the consistency test D1^2 = D0 D2 fails with certainty.
+ * Guarantees, per row:
+ *   one corrupted word, any 64-bit pattern: restored exactly (x' = x + k p, which no sum sees, through the window);
+ *   two corrupted words: never written to, with certainty;
+ *   three or more corrupted words: miscorrected with probability about N / p on random data;
+ *   a corrupted seal or locator word beside an intact row moves one sum: FHE_SEAL_SUSPECT; beside a corrupted row the syndromes are
+ *     inconsistent: FHE_SEAL_UNCORRECTABLE.  Neither writes.  A row is examined only when fhe_seal_verify's sweep raises it, so a
+ *     corrupted locator beside an intact row and seal goes unnoticed (FHE_SEAL_CLEAN) until that row is first flagged.
+ * Outcomes (report word 0): */
+#define FHE_SEAL_CLEAN 0         /* the row was not flagged */
+#define FHE_SEAL_REPAIRED 1      /* one word corrected and confirmed by a second sweep; the flag is cleared */
+#define FHE_SEAL_UNCORRECTABLE 2 /* inconsistent syndromes, index out of range, restored word >= q, window disagreement or a failed
+                                    confirmation: the row is as it was found, the flag stays raised */
+#define FHE_SEAL_TRANSIENT 3     /* flagged by the first sweep, but the re-read finds every sum equal and every word in its window:
+                                    nothing written, the flag is cleared */
+#define FHE_SEAL_SUSPECT 4       /* exactly one of the three sums differs and every word is in its window: row corruption that leaves
+                                    two sums alone needs three or more words, so the stored sum is the likely casualty; the row is
+                                    untouched and the flag stays raised -- the caller decides whether to reseal */
+/* fhe_seal_locator writes the locators of d_words = [n_poly][limbs][N] to d_locator = [n_poly * limbs]; arguments and rules as
+ * fhe_seal; it neither takes nor honours the seal hook.
+ * fhe_seal_repair is fhe_seal_verify's sweep followed by the repair, asynchronous on `stream` with no host decision (usable inside a
+ * stream capture once the context's scratch exists): d_words is WRITTEN where a row is repaired; d_flags[row] as fhe_seal_verify,
+ * cleared again for REPAIRED and TRANSIENT rows; d_report = uint64_t [rows][4] = {outcome, index of the word, the word before, the
+ * word after} (zeros beyond the outcome unless REPAIRED), 16-byte aligned.  Argument rules are fhe_seal_verify's; a null locator or
+ * report is FHE_ERR_INVALID.  It takes the one-shot hook fhe_ctx_inject_fault_seal and honours it in its first sweep only: the
+ * re-read then finds memory clean -- the source of FHE_SEAL_TRANSIENT. */
+int fhe_seal_locator(fhe_ctx *ctx, uint64_t *d_locator, const uint64_t *d_words, const fhe_ntt_tables *t, size_t n_poly, size_t limbs,
+                     size_t start_idx, void *stream);
+int fhe_seal_repair(fhe_ctx *ctx, uint64_t *d_words, const uint64_t *d_seal, const uint64_t *d_locator, const fhe_ntt_tables *t, size_t n_poly,
+                    size_t limbs, size_t start_idx, uint32_t *d_flags, uint64_t *d_report, void *stream);
+/* fhe_hmult_sealed / fhe_rotate_sealed with every given (seal, locator) pair repaired in place instead of only verified; the same
+ * body otherwise, so the operand and key pointers are not const.  d_locator_in / d_locator_key go with d_seal_in / d_seal_key, entry
+ * by entry: both given or both NULL (FHE_ERR_INVALID otherwise, nothing launched).  d_locator_out: HOST array of two device pointers
+ * ([L] or [L - 1] words each) for the locators of the outputs; an entry, or the array, may be NULL.  d_flags is 16-byte aligned and
+ * holds the sealed call's layout followed by one report block of four uint64_t per input and key row, in the order of their flag
+ * words; rows without a seal report FHE_SEAL_CLEAN:
+ *   fhe_hmult_sealed_repair_layout   out[0..6] = fhe_hmult_sealed_layout's, out[7] the report block's offset in flag words (a
+ *                                    multiple of 4), out[8] the total in flag words, out[9] = 0
+ *   fhe_rotate_sealed_repair_layout  out[0..4] = fhe_rotate_sealed_layout's, out[5] the report block, out[6] the total, out[7] = 0
+ * A row left UNCORRECTABLE or SUSPECT does not stop the call.  Not covered: faults in flight in the checked body (flags only, as
+ * before), sharded plans, hoisted rotations, the BSGS product. */
+int fhe_hmult_sealed_repair_layout(const fhe_keyswitch *p, int rescale, int out[10]);
+int fhe_hmult_sealed_repair(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, uint64_t *d_a0, uint64_t *d_a1, uint64_t *d_b0,
+                            uint64_t *d_b1, uint64_t *d_relin_key, int rescale, const fhe_abft *a, const uint64_t *const *d_seal_in /* [4] */,
+                            const uint64_t *const *d_locator_in /* [4] */, const uint64_t *d_seal_key, const uint64_t *d_locator_key,
+                            uint64_t *const *d_seal_out /* [2] */, uint64_t *const *d_locator_out /* [2] */, uint32_t *d_flags, void *stream);
+int fhe_rotate_sealed_repair_layout(const fhe_keyswitch *p, int out[8]);
+int fhe_rotate_sealed_repair(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, uint64_t *d_c0, uint64_t *d_c1, uint32_t galois_elt,
+                             uint64_t *d_galois_key, const fhe_abft *a, const uint64_t *const *d_seal_in /* [2] */,
+                             const uint64_t *const *d_locator_in /* [2] */, const uint64_t *d_seal_key, const uint64_t *d_locator_key,
+                             uint64_t *const *d_seal_out /* [2] */, uint64_t *const *d_locator_out /* [2] */, uint32_t *d_flags, void *stream);
+
 /* ---- fault injection ---------------------------------------------------------------- */
 /* _flip_bit_kernel<<<1,1>>> (reliability_test/dotprod_test.cu:31-33,55): data[idx] ^= 1 << bit */
 int fhe_flip_bit(fhe_ctx *ctx, uint64_t *d_data, uint64_t idx, int bit, void *stream);
