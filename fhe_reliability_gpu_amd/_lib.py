@@ -181,6 +181,12 @@ _SIG = {
     "fhe_rotate_sealed_repair_layout": (ci, [vp, C.POINTER(ci)]),
     "fhe_rotate_sealed_repair": (ci, [vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp, C.POINTER(vp), C.POINTER(vp), vp, vp, C.POINTER(vp), C.POINTER(vp),
                                       vp, vp]),
+    "fhe_modadd_sealed": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, vp]),
+    "fhe_modsub_sealed": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, vp]),
+    "fhe_ctx_inject_fault_seal_carry": (ci, [vp, ci, ci, ci, C.c_longlong, ci]),
+    "fhe_rotate_sum_sealed_layout": (ci, [vp, ci, C.POINTER(ci)]),
+    "fhe_rotate_sum_sealed": (ci, [vp, vp, vp, vp, vp, vp, ci, C.POINTER(C.c_uint32), C.POINTER(vp), vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                                   vp, vp]),
     "fhe_ctx_trace": (ci, [vp, ci]),
     "fhe_ctx_trace_read": (ci, [vp, C.c_char_p, sz, C.POINTER(sz)]),
 }

@@ -117,7 +117,9 @@ struct fhe_ctx {
     PointHook pm_fault, pw_fault, bc_fault, gal_fault;
     StagedFault ksc_fault, rsc_fault, hrc_fault, bsgs_fault, bgv_ksc_fault, bgv_rsc_fault;
     PointHook seal_fault;  // fhe_ctx_inject_fault_seal: unit = the row, coeff = the word (point 0 when armed)
-    DevBuf seal_part;      // fhe_seal / fhe_seal_verify and the sealed composites: the chunks' partial sums, [rows][chunks][2] (grown on demand)
+    PointHook carry_fault; // fhe_ctx_inject_fault_seal_carry: point = CARRY_AT_*, unit = the row, coeff = the word; taken by the carry launch
+    int carry_skip = 0;    // that finds carry_skip == 0, every earlier one counts it down
+    DevBuf seal_part;      // fhe_seal / fhe_seal_verify and the sealed composites: the chunks' partial sums, [rows][chunks][2] (the carried adds: [4] or [6]; grown on demand)
     DevBuf gal_sums;       // checked Galois permutation: the units' source-side and destination-side sums, [2][units] (grown on demand)
     int geo = 1;           // column-tile geometry of the two-launch path (ntt_launch.hpp)
     bool resident = false; // 2^13 / 2^14: one LDS-resident pass instead of two launches (opt-in, see ntt_plan.hpp)

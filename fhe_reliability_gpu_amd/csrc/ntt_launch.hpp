@@ -373,4 +373,14 @@ hipError_t launch_seal_locator(hipStream_t st, const SealArgs &p, u64 *part, u64
 // report[unit] = {status, index, word before, word after}.  p.x is written: the caller owns it as mutable memory
 hipError_t launch_seal_repair(hipStream_t st, const SealArgs &p, const u64 *seal, const u64 *locator, u32 *flags, u64 *report);
 
+// ---- seal_carry.hip: the modular add / subtract that carries its operands' seals to the result (seal_carry.hpp) ----
+// words of the partial-sum scratch a launch needs: [units][chunks per row][4, or 6 with locators]
+size_t carry_part_words(u32 units, int logn, bool loc);
+// launch_modadd's / launch_modsub's words (p.a, p.b, p.c 16-byte aligned, logn >= 1; c may be a or b); seal_c[unit] = the sums
+// predicted from seal_a, seal_b and the wraps, and loc_c[unit] from loc_a, loc_b when loc_c != nullptr; k.flags[unit] |= SEAL_SUM
+// where the digest of c as stored differs from the prediction, SEAL_RANGE where an operand word is >= q_l; zeroed by the caller.
+// k.fault_point >= 0: the test fault at that point (CARRY_AT_*) of word fault_coeff of row fault_unit, in the register
+hipError_t launch_modadd_carry(hipStream_t st, const PointwiseArgs &p, bool sub, u64 *part, const u64 *seal_a, const u64 *seal_b, u64 *seal_c,
+                               const u64 *loc_a, const u64 *loc_b, u64 *loc_c, const BcCheck &k);
+
 } // namespace fhe

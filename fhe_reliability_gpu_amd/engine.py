@@ -287,6 +287,37 @@ class NttTables:
                                                                               fl.ptr, report.ptr, stream), stream)
         return flags, report.download()[:rows * 4].reshape(rows, 4)
 
+    def _carried(self, f, c, a, b, seal_a, seal_b, seal_c, locators, limbs, start, n_poly, stream):
+        limbs = len(self) - start if limbs is None else limbs
+        rows = n_poly * limbs
+        if seal_c is None:
+            seal_c = self.eng.alloc(rows * 2)
+            seal_c.shape = (rows, 2)
+        loc = list(locators) if locators is not None else [None] * 3
+        if locators is not None and len(loc) == 2:
+            loc.append(self.eng.alloc(rows))
+        lp = [x.ptr if x is not None else None for x in loc]
+        flags = _checked_flags(self.eng, rows, lambda fl: f(self.eng._h, c.ptr, a.ptr, b.ptr, seal_c.ptr, seal_a.ptr, seal_b.ptr, lp[2], lp[0], lp[1], self._h,
+                                                            n_poly, limbs, start, fl.ptr, stream), stream)
+        return (seal_c, flags) if locators is None else (seal_c, loc[2], flags)
+
+    def modadd_sealed(self, c: DeviceArray, a: DeviceArray, b: DeviceArray, seal_a: DeviceArray, seal_b: DeviceArray, seal_c: Optional[DeviceArray] = None,
+                      locators=None, limbs=None, start=0, n_poly=1, stream=None):
+        """c = (a + b) mod q per limb with the operands' seals carried to the result in the same sweep: ``(seal_c, flags)``, or
+        ``(seal_c, locator_c, flags)`` with ``locators = (locator_a, locator_b[, locator_c])``.  The words are ``fhe_modadd``'s, bit
+        for bit.  The seal is linear: S_i(c) = S_i(a) + S_i(b) - q E_i with E_i the weighted count of the wraps, so the digest of
+        the words about to be stored is held against the sums predicted from ``seal_a`` and ``seal_b``; flags[poly * limbs + l]
+        (uint32): ``SEAL_SUM`` (1) = they differ -- an operand word that is not the sealed one, a fault in the adder or in the wrap
+        count -- ``SEAL_RANGE`` (2) = an operand word >= q_l.  ``seal_c`` always receives the predicted sums, so a raised row stays
+        raised through later carried adds and a fault after the digest is caught by the next verification.  ``c`` may be ``a`` or
+        ``b`` and ``seal_c`` may be ``seal_a`` or ``seal_b`` (seal_carry.hpp)."""
+        return self._carried(lib.fhe_modadd_sealed, c, a, b, seal_a, seal_b, seal_c, locators, limbs, start, n_poly, stream)
+
+    def modsub_sealed(self, c: DeviceArray, a: DeviceArray, b: DeviceArray, seal_a: DeviceArray, seal_b: DeviceArray, seal_c: Optional[DeviceArray] = None,
+                      locators=None, limbs=None, start=0, n_poly=1, stream=None):
+        """c = (a - b) mod q per limb, otherwise ``modadd_sealed``: S_i(c) = S_i(a) - S_i(b) + q E_i; the words are ``fhe_modsub``'s."""
+        return self._carried(lib.fhe_modsub_sealed, c, a, b, seal_a, seal_b, seal_c, locators, limbs, start, n_poly, stream)
+
     def polymul(self, c: DeviceArray, a: DeviceArray, b: DeviceArray, limbs=None, start=0, n_poly=1, stream=None):
         limbs = len(self) - start if limbs is None else limbs
         check(lib.fhe_polymul(self.eng._h, c.ptr, a.ptr, b.ptr, self._h, n_poly, limbs, start, stream))
@@ -1080,6 +1111,47 @@ class KeySwitch:
         kl = self._ks_layout(bool(self.plain_modulus))
         flags["checked"] = self._split_flags(f, kl, base=lay["checked"])
         return o0, o1, so, flags
+
+    def rotate_sum_sealed_layout(self, n_steps: int):
+        """``{"stride": words per step, "add": offset of the add rows inside a step's block, "total": n, "rotate": the layout of
+        rotate_sealed_layout, which a step's block starts with}`` of ``rotate_sum_sealed``'s flag buffer."""
+        out = (C.c_int * 4)()
+        check(lib.fhe_rotate_sum_sealed_layout(self._h, n_steps, out))
+        return {"stride": int(out[0]), "add": int(out[1]), "total": int(out[2]), "rotate": self.rotate_sealed_layout()}
+
+    def rotate_sum_sealed(self, c0: DeviceArray, c1: DeviceArray, galois_elts: Sequence[int], galois_keys: Sequence[DeviceArray], abft: "Abft", seals,
+                          key_seals=None, stream=None):
+        """The tail of the reference's dot product (dotprod_test.cu:143-148: per step rotated = xy; rotate_inplace(rotated, step);
+        add_inplace(xy, rotated)) as one protected call: per step ``rotate_sealed`` from the accumulators into a rotated copy, then
+        one carried add per half back into them (``NttTables.modadd_sealed``), the seals updated in place.  Works on copies of
+        (c0, c1) and of ``seals``: ``(out0, out1, (seal0, seal1), flags)`` with ``flags`` a list with one dictionary per step,
+        ``rotate_sealed``'s plus ``"add0"``, ``"add1"``: [L] (the bits of ``modadd_sealed``).  ``key_seals``: one per step, entries
+        or all may be None.  Every load in it is a verified load: step s + 1 verifies on entry what step s's adds stored."""
+        n, L = len(galois_elts), self.L
+        lay = self.rotate_sum_sealed_layout(n)
+        acc, tmp = [self._out(L), self._out(L)], [self._out(L), self._out(L)]
+        sl, st = [self.eng.alloc(2 * L) for _ in range(2)], [self.eng.alloc(2 * L) for _ in range(2)]
+        for h, (src, seal) in enumerate(zip((c0, c1), seals)):
+            acc[h].copy_from(src)
+            sl[h].copy_from(seal)
+            sl[h].shape = (L, 2)
+        self.eng.sync()
+        elts = (C.c_uint32 * n)(*galois_elts)
+        keys = (vp * n)(*[k.ptr for k in galois_keys])
+        ksl = (vp * n)(*[x.ptr if x is not None else None for x in key_seals]) if key_seals is not None else None
+        f = _checked_flags(self.eng, lay["total"], lambda fl: lib.fhe_rotate_sum_sealed(
+            self.eng._h, self._h, acc[0].ptr, acc[1].ptr, tmp[0].ptr, tmp[1].ptr, n, elts, keys, abft._h, (vp * 2)(sl[0].ptr, sl[1].ptr), ksl,
+            (vp * 2)(st[0].ptr, st[1].ptr), fl.ptr, stream), stream)
+        rl, kl = lay["rotate"], self._ks_layout(bool(self.plain_modulus))
+        steps = []
+        for s in range(n):
+            base = s * lay["stride"]
+            d = self._split_flags(f, rl, ("c0", "c1", "key"), base=base)
+            d["checked"] = self._split_flags(f, kl, base=base + rl["checked"])
+            d["add0"] = f[base + lay["add"]:base + lay["add"] + L].copy()
+            d["add1"] = f[base + lay["add"] + L:base + lay["add"] + 2 * L].copy()
+            steps.append(d)
+        return acc[0], acc[1], tuple(sl), steps
 
     # ---- the same composites repairing their operands and key in place (seal_repair.hip) ----
     def seal_key_locator(self, key: DeviceArray, stream=None) -> DeviceArray:

@@ -17,7 +17,11 @@ suspect, whether the trial was missed (a flip, no repair and no flag), and wheth
 bit.  One flipped word per row is corrected and the chain then computes the clean result; two or more symbols in one row stay
 uncorrectable, as the flags say.  Exit status 1 when a trial was missed, or was reported all corrected with a final result that differs.
 
-python -m fhe_reliability_gpu_amd.tools.flip_coverage [--repair] [--trials 32] [--num-symbols 1] [--bits-per-symbol 1] [--logn 14] [--row 8] [--seed 1]"""
+--rotate-sum runs the reference's whole experiment, its tail included, through two protected calls: hmult_sealed, then
+rotate_sum_sealed, whose carried adds verify their operands on the load that feeds the adder and hand the seals on without a sealing
+or verifying launch in between.  Output and exit status as in the default mode; the fault-free words equal the default chain's.
+
+python -m fhe_reliability_gpu_amd.tools.flip_coverage [--repair | --rotate-sum] [--trials 32] [--num-symbols 1] [--bits-per-symbol 1] [--logn 14] [--row 8] [--seed 1]"""
 import argparse
 import sys
 
@@ -48,7 +52,10 @@ def main():
     ap.add_argument("--row", type=int, default=8, help="slots summed by the rotate-and-add rounds (a power of two)")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--repair", action="store_true", help="run the chain through the repairing composites and report corrections")
+    ap.add_argument("--rotate-sum", action="store_true", help="run the rotate-and-add rounds as one rotate_sum_sealed call")
     a = ap.parse_args()
+    if a.repair and a.rotate_sum:
+        ap.error("--repair and --rotate-sum exclude each other: the composite has no repairing form")
     if a.row < 1 or a.row & (a.row - 1) or not 1 <= a.bits_per_symbol <= 64 or a.num_symbols < 0:
         ap.error("row is a power of two, bits-per-symbol 1..64, num-symbols >= 0")
     eng = F.Engine(0)
@@ -96,6 +103,18 @@ def main():
                 sc[h] = t2.seal(c[h], limbs=R)
         return np.concatenate([c[0].download().reshape(-1), c[1].download().reshape(-1)]), raised
 
+    def chain_sum(d_a):
+        """the same chain with its tail as one call: hmult_sealed, then rotate_sum_sealed on its outputs and their seals"""
+        o0, o1, so, fl = ks.hmult_sealed(part(d_a, 0, L), part(d_a, 1, L), part(d_b, 0, L), part(d_b, 1, L), d_rlk, ab,
+                                         seals=[seal_part(s_a, 0, L), seal_part(s_a, 1, L), seal_part(s_b, 0, L), seal_part(s_b, 1, L)], key_seal=s_rlk)
+        raised = nonzero(fl)
+        if elts:
+            o0, o1, so, steps = ks2.rotate_sum_sealed(o0, o1, elts, d_gk, ab2, so, key_seals=s_gk)
+            raised += sum(nonzero(st) for st in steps)
+        # the seals the chain hands on are those of the words it hands on, unless a flag says otherwise
+        raised += nonzero(t2.seal_verify(o0, so[0], limbs=R)) + nonzero(t2.seal_verify(o1, so[1], limbs=R))
+        return np.concatenate([o0.download().reshape(-1), o1.download().reshape(-1)]), raised
+
     def outcomes(reports, tally):
         for rep in reports.values():
             for status in np.asarray(rep).reshape(-1, 4)[:, 0].tolist():
@@ -129,8 +148,12 @@ def main():
     assert raised == 0, "the clean chain raised a flag"
     if a.repair:
         return main_repair(a, eng, rng, ct_a, clean, chain_repair)
-    print(f"N = 2^{a.logn}, L = {L}, K = {K}, dnum = {DNUM}, plain modulus {PLAIN_MODULUS}; {rounds} rotate-and-add rounds; "
-          f"{a.num_symbols} symbols x {a.bits_per_symbol} bits per trial")
+    if a.rotate_sum:
+        out, raised = chain_sum(eng.upload(ct_a))
+        assert raised == 0 and (out == clean).all(), "the clean rotate-and-sum chain differs from the sealed chain"
+        chain = chain_sum
+    print(f"N = 2^{a.logn}, L = {L}, K = {K}, dnum = {DNUM}, plain modulus {PLAIN_MODULUS}; {rounds} rotate-and-add rounds"
+          f"{' as one rotate_sum_sealed call' if a.rotate_sum else ''}; {a.num_symbols} symbols x {a.bits_per_symbol} bits per trial")
     missed = 0
     for trial in range(a.trials):
         d_a = eng.upload(ct_a)

@@ -903,10 +903,11 @@ int fhe_ctx_inject_fault_seal(fhe_ctx *ctx, int row, long long coeff, int bit);
  * Scope, statuses, aliasing rules and test hooks are the underlying checked call's; a call outside its scope returns its status
  * with nothing launched.  A status from the checked call after the verifying launches (a refused hook) leaves the input and key flags
  * written and no output seal.  Every buffer must be 16-byte aligned (FHE_ERR_INVALID).
- * Still not covered: the verifying read and the consuming read are two loads, so a transient fault on the second one alone is not
- * seen; neither is a word corrupted between the checked call's final store and the sealing launch's load.  Taking the digest from
- * the register about to be stored, and verifying on the consumer's own load, are later changes.  Sharded plans, the hoisted
- * rotations and the BSGS product have no sealed form. */
+ * Still not covered, for multiply and rotation: the verifying read and the consuming read are two loads, so a transient fault on the
+ * second one alone is not seen; neither is a word corrupted between the checked call's final store and the sealing launch's load.
+ * For add and subtract both gaps are closed (fhe_modadd_sealed / fhe_modsub_sealed below: the digest is taken from the register
+ * about to be stored, and the operands are verified on the consumer's own load).  Sharded plans, the hoisted rotations and the
+ * BSGS product have no sealed form. */
 int fhe_hmult_sealed_layout(const fhe_keyswitch *p, int rescale, int out[8]);
 int fhe_hmult_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_a0, const uint64_t *d_a1,
                      const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a,
@@ -976,6 +977,55 @@ int fhe_rotate_sealed_repair(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, u
                              uint64_t *d_galois_key, const fhe_abft *a, const uint64_t *const *d_seal_in /* [2] */,
                              const uint64_t *const *d_locator_in /* [2] */, const uint64_t *d_seal_key, const uint64_t *d_locator_key,
                              uint64_t *const *d_seal_out /* [2] */, uint64_t *const *d_locator_out /* [2] */, uint32_t *d_flags, void *stream);
+
+/* ---- seals carried through add and subtract; sealed rotate-and-sum ------------------------------------------------
+ * The seal is linear and so are these two operations.  With canonical operands c_j = a_j + b_j - e_j q, e_j in {0, 1}, hence for
+ * i = 0, 1, 2 and the weights w_j = j + 1
+ *     S_i(c) = S_i(a) + S_i(b) - q E_i   (mod p),      E_i = sum_j w_j^i e_j,
+ * and for the subtract c = a - b + e q: S_i(c) = S_i(a) - S_i(b) + q E_i.  fhe_modadd_sealed / fhe_modsub_sealed are fhe_modadd /
+ * fhe_modsub (the same words for every 64-bit input, bit for bit) in one sweep that loads each operand word once, counts the wraps,
+ * digests c from the register it then stores, and holds that digest against the sums predicted from the operands' seals.  Caught in
+ * the same pass, on the consumer's own load: a word of a or b that differs from what was sealed, a fault in the adder, a fault in
+ * the wrap count.  d_flags[row] (uint32 [n_poly * limbs], cleared by the call on `stream`): bit 1 the digest differs from the
+ * prediction (or a stored sum of an operand is not canonical), bit 2 an operand word >= q_l -- such a word is reduced as fhe_modadd
+ * reduces it and, where the sealed word was canonical, raises bit 1 as well.
+ * d_seal_c / d_locator_c receive the PREDICTED sums, matched or not: a fault after the digest (the store, memory) is caught by the
+ * next verification of c, and a raised row stays raised through every later carried operation.  On a clean run they equal fhe_seal /
+ * fhe_seal_locator of c.  d_c may be d_a or d_b, d_seal_c may be d_seal_a or d_seal_b (likewise the locators), d_a may be d_b.
+ * Locators are given all three or none (FHE_ERR_INVALID); a null seal is FHE_ERR_INVALID; alignment, N >= 2, the range rule and the
+ * context's scratch are fhe_seal's.  Memory traffic is fhe_modadd's, 24 N bytes per row.
+ * Test hook: fhe_ctx_inject_fault_seal_carry(call, point, row, coeff, bit) flips bit `bit` at word `coeff` of row `row` in the
+ * call-th carry launch on this context after arming (0 = the next; fhe_modadd_sealed / fhe_modsub_sealed are one launch each, the
+ * adds of fhe_rotate_sum_sealed are numbered 2 s + h), in registers: point 0 the word of a after its load, 1 the word of b, 2 c
+ * before the digest and the store, 3 c after the digest and before the store (nothing is raised in that call; the next verification
+ * of c raises bit 1), 4 the wrap bit as counted (`bit` is ignored).  One shot; a row or word outside the call that takes it returns
+ * FHE_ERR_INVALID from that call, with nothing launched; row < 0 clears. */
+int fhe_modadd_sealed(fhe_ctx *ctx, uint64_t *d_c, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_seal_c, const uint64_t *d_seal_a,
+                      const uint64_t *d_seal_b, uint64_t *d_locator_c, const uint64_t *d_locator_a, const uint64_t *d_locator_b,
+                      const fhe_ntt_tables *t, size_t n_poly, size_t limbs, size_t start_idx, uint32_t *d_flags, void *stream);
+int fhe_modsub_sealed(fhe_ctx *ctx, uint64_t *d_c, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_seal_c, const uint64_t *d_seal_a,
+                      const uint64_t *d_seal_b, uint64_t *d_locator_c, const uint64_t *d_locator_a, const uint64_t *d_locator_b,
+                      const fhe_ntt_tables *t, size_t n_poly, size_t limbs, size_t start_idx, uint32_t *d_flags, void *stream);
+int fhe_ctx_inject_fault_seal_carry(fhe_ctx *ctx, int call, int point, int row, long long coeff, int bit);
+/* The tail of the reference's dot product (reliability_test/dotprod_test.cu:143-148: rotated = xy; rotate_inplace(rotated, step);
+ * add_inplace(xy, rotated), per step) as one protected call in which every load is a verified load.  Per step s < n_steps:
+ *   1. fhe_rotate_sealed from (d_c0, d_c1) into (d_tmp0, d_tmp1) with galois_elts[s] and d_galois_keys[s]: it verifies the carried
+ *      seals d_seal[0..1] and the key's seal d_seal_keys[s] (the array, or an entry, may be NULL: not verified), runs the checked
+ *      rotation in the plan's CKKS or BGV form and seals the rotated copy into d_seal_tmp[0..1];
+ *   2. two carried adds d_c<h> += d_tmp<h>, the seals d_seal[h] updated in place.
+ * d_c0, d_c1 are in/out accumulators [L][N], d_tmp0, d_tmp1 [L][N] hold the last rotated copy; galois_elts, d_galois_keys, d_seal,
+ * d_seal_keys and d_seal_tmp are HOST arrays (of n_steps, n_steps, 2, n_steps and 2 entries), seals [L][2].
+ * Flags: fhe_rotate_sum_sealed_layout gives out[0] the stride between the steps' blocks, out[1] the offset of the add rows inside a
+ * step's block, out[2] the total, out[3] = 0; a step's block is fhe_rotate_sealed_layout's block followed by the add rows of c0 [L]
+ * and of c1 [L], with the bits above.  Step s + 1 verifies on entry what step s's adds stored, and the final seals are handed back
+ * for the next sealed call, so there is no closing sweep.  The words are those of the chain fhe_rotate + fhe_modadd, bit for bit.
+ * A call outside the checked rotation's scope returns that call's status with nothing launched, as does an even Galois element, a
+ * null key or a misaligned buffer in any step; a null seal pointer is FHE_ERR_INVALID.  The checked call's one-shot hooks fire in
+ * the first step that takes them.  Not in this change: a repairing form of this composite, and sharded plans. */
+int fhe_rotate_sum_sealed_layout(const fhe_keyswitch *p, int n_steps, int out[4]);
+int fhe_rotate_sum_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_c0, uint64_t *d_c1, uint64_t *d_tmp0, uint64_t *d_tmp1, int n_steps,
+                          const uint32_t *galois_elts, const uint64_t *const *d_galois_keys, const fhe_abft *a, uint64_t *const *d_seal /* [2] */,
+                          const uint64_t *const *d_seal_keys /* [n_steps] */, uint64_t *const *d_seal_tmp /* [2] */, uint32_t *d_flags, void *stream);
 
 /* ---- fault injection ---------------------------------------------------------------- */
 /* _flip_bit_kernel<<<1,1>>> (reliability_test/dotprod_test.cu:31-33,55): data[idx] ^= 1 << bit */
