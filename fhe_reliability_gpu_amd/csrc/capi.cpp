@@ -569,7 +569,8 @@ int fhe_memset(fhe_ctx *ctx, void *dst, int byte, size_t bytes, void *stream)
 // ---------------------------------------------------------------- host tables
 int fhe_moduli_create(uint64_t N, const int *bits, int count, uint64_t *out_q)
 {
-    if (!bits || !out_q || count < 1 || N < 1 || (N & (N - 1))) return fail(FHE_ERR_INVALID, "bad arguments");
+    // N <= 2^59: 2N + 1 is the smallest candidate and must stay below 2^61 (and 2N must not wrap)
+    if (!bits || !out_q || count < 1 || N < 1 || (N & (N - 1)) || N > ((u64)1 << 59)) return fail(FHE_ERR_INVALID, "bad arguments");
     for (int i = 0; i < count; i++)
         if (bits[i] < 2 || bits[i] > 61) return fail(FHE_ERR_UNSUPPORTED, "bit sizes must be in [2, 61]");
     if (!host::create_moduli(N, bits, count, out_q)) return fail(FHE_ERR_INVALID, "not enough primes of the requested size");
@@ -585,7 +586,10 @@ int fhe_modulus_const_ratio(uint64_t q, uint64_t out[3])
 
 int fhe_min_primitive_root(uint64_t q, uint64_t order, uint64_t *out)
 {
-    if (!out || !host::min_primitive_root(q, order, *out)) return fail(FHE_ERR_INVALID, "no primitive root of that order");
+    if (!out) return fail(FHE_ERR_INVALID, "null out");
+    // the search for the minimum walks order / 2 products
+    if (order > ((u64)1 << 31)) return fail(FHE_ERR_UNSUPPORTED, "order above 2^31");
+    if (!host::min_primitive_root(q, order, *out)) return fail(FHE_ERR_INVALID, "no primitive root of that order");
     return FHE_OK;
 }
 

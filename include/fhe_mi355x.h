@@ -91,11 +91,16 @@ int fhe_memset(fhe_ctx *ctx, void *dst, int byte, size_t bytes, void *stream);
 
 /* ---- moduli and host tables (a10) ---------------------------------------- */
 /* phantom::arith::CoeffModulus::Create(N, {bits...}) (ntt_test.cu:44): for each bit
- * size the largest primes p < 2^bits with p = 1 mod 2N, handed out smallest first. */
+ * size the largest primes p < 2^bits with p = 1 mod 2N, handed out smallest first.
+ * N is a power of two, 1 <= N <= 2^59 (2N + 1, the smallest candidate, must stay below 2^61); bit sizes are in [2, 61], anything
+ * else is FHE_ERR_UNSUPPORTED; a size whose interval (2^(bits-1), 2^bits) holds fewer such primes than the list asks for, a bad N
+ * and count < 1 are FHE_ERR_INVALID. */
 int fhe_moduli_create(uint64_t N, const int *bits, int count, uint64_t *out_q);
 /* Modulus::const_ratio() (ntt_test.cu:51-52): out = {floor(2^128/q) lo, hi, 2^128 mod q} */
 int fhe_modulus_const_ratio(uint64_t q, uint64_t out[3]);
-/* minimal primitive `order`-th root of unity mod q (what phantom::arith::NTT picks) */
+/* minimal primitive `order`-th root of unity mod q (what phantom::arith::NTT picks).  q is a prime, `order` a power of two that
+ * divides q - 1, at most 2^31 (the search for the minimum walks order / 2 products: seconds at the top); a larger order is
+ * FHE_ERR_UNSUPPORTED, a composite q or an order that does not divide q - 1 FHE_ERR_INVALID. */
 int fhe_min_primitive_root(uint64_t q, uint64_t order, uint64_t *out);
 /* NTT::get_from_root_powers() / get_from_root_powers_shoup() (ntt_test.cu:60-64):
  * rp[bitrev(i)] = psi^i, shoup[k] = floor(rp[k] 2^64 / q); either pointer may be NULL */
@@ -104,11 +109,13 @@ int fhe_root_powers(uint64_t q, int log_n, uint64_t *rp, uint64_t *rp_shoup);
 /* ---- NTT tables (device) -------------------------------------------------- */
 /* DModulus::set + DNTTTable::init/set for `count` limbs (ntt_test.cu:47-69) with the
  * tables of phantom::arith::NTT(log_n, q[i]).  Limb i uses FHE_PATH_F64 when
- * q[i] < 2^50, else FHE_PATH_U64 (q[i] < 2^61). */
+ * q[i] < 2^50, else FHE_PATH_U64 (q[i] < 2^61).  Every q[i] is a prime that is 1 mod 2N, from the smallest such prime up:
+ * q[i] >= 2^61 is FHE_ERR_UNSUPPORTED, a composite modulus or one without a 2N-th root FHE_ERR_INVALID. */
 int fhe_ntt_tables_create(fhe_ctx *ctx, int log_n, const uint64_t *q, int count, fhe_ntt_tables **out);
 /* Same, from caller-supplied forward root powers (count x N, entry k = psi^bitrev(k)):
  * the DNTTTable::set(..., twiddle, twiddle_shoup, ...) path of ntt_test.cu:61-69.
- * force_path: -1 = choose by modulus size, else FHE_PATH_*. */
+ * force_path: -1 = choose by modulus size, else FHE_PATH_*.  Either path takes every modulus below 2^50, however small;
+ * FHE_PATH_F64 with q[i] >= 2^50 is FHE_ERR_UNSUPPORTED. */
 int fhe_ntt_tables_create_from_roots(fhe_ctx *ctx, int log_n, const uint64_t *q, int count,
                                      const uint64_t *root_powers, int force_path, fhe_ntt_tables **out);
 int fhe_ntt_tables_destroy(fhe_ntt_tables *t);
