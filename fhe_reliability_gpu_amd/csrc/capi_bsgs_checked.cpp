@@ -13,10 +13,17 @@
 // same lane and the two halves touch disjoint buffers, so d_out1 == d_add1 is in-place safe; t0 overwrites sigma(s0) in scratch
 // (k_modadd_checked: c == b, same lane).  The unchecked call adds in another order (out + (tail + sigma(s0))) and takes sigma on
 // loads; every stage yields canonical residues and those are unique, so the words are fhe_bsgs_matvec's bit for bit.
+//
+// fhe_bsgs_matvec_sealed is the same body in another mode (SealedMode, the RepairMode pattern of capi_seal.cpp): it verifies the
+// given seals of c0, c1 and of every baby (as prepared) and giant key with sweeps of their own, runs the baby block unchanged, runs
+// per giant step the inner sum that digests each diagonal word from the register it multiplies (launch_diag_mac_sealed; n1 > 16: a
+// verifying sweep over the step's diagonal rows, then launch_diag_mac_checked) and seals both outputs.  Its flag buffer is
+//     [c0 L][c1 L][baby keys (n1 - 1) key_rows][giant keys (n2 - 1) key_rows][diagonals n2 n1 L][the checked call's own block]
 #include "capi_checked.hpp"
-#include "bsgs_check.hpp"
+#include "bsgs_seal.hpp"
 
 #include <climits>
+#include <cstdint>
 
 namespace {
 
@@ -42,6 +49,65 @@ BmcLayout bmc_layout(const fhe_keyswitch *p, size_t n1, size_t n2)
 }
 
 bool bsgs_shape_ok(size_t n1, size_t n2) { return n1 >= 1 && n2 >= 1 && n1 <= 4096 && n2 <= 4096; }
+
+// the mode of the body that is fhe_bsgs_matvec_sealed: the seals that come with the operands (HOST arrays of device pointers; an
+// array or an entry may be null: that operand is not verified) and where the outputs' seals go -- a null SealedMode is the checked call
+struct SealedMode {
+    const uint64_t *const *seal_in;          // [2]: c0, c1, [L][2] each
+    const uint64_t *const *seal_baby;        // [n1 - 1]: the prepared baby keys, [key_rows][2] each
+    const uint64_t *const *seal_giant;       // [n2 - 1]: the giant keys
+    const uint64_t *seal_diag;               // [n2][n1][L][2]
+    uint64_t *const *seal_out;               // [2]
+};
+
+size_t bsgs_key_rows(const fhe_keyswitch *p) { return (size_t)p->dnum * 2 * (p->L + p->K); }
+
+// offsets of c0, c1, the baby keys, the giant keys, the diagonals and the checked block; total (-1: too large)
+struct BmsLayout {
+    int off[6], total;
+};
+
+BmsLayout bms_layout(const fhe_keyswitch *p, size_t n1, size_t n2)
+{
+    const unsigned long long L = p->L, kr = bsgs_key_rows(p);
+    const BmcLayout c = bmc_layout(p, n1, n2);
+    unsigned long long o[7];
+    o[0] = 0;
+    o[1] = L;
+    o[2] = 2 * L;
+    o[3] = o[2] + (n1 - 1) * kr;
+    o[4] = o[3] + (n2 - 1) * kr;
+    o[5] = o[4] + (unsigned long long)n2 * n1 * L;
+    o[6] = o[5] + (c.total < 0 ? 0 : c.total);
+    BmsLayout l{};
+    for (int i = 0; i < 6; i++) l.off[i] = o[i] > (unsigned long long)INT_MAX ? INT_MAX : (int)o[i];
+    l.total = c.total < 0 || o[6] > (unsigned long long)INT_MAX ? -1 : (int)o[6];
+    return l;
+}
+
+bool misaligned(std::initializer_list<const void *> ptrs)
+{
+    for (const void *q : ptrs)
+        if ((uintptr_t)q % 16) return true;
+    return false;
+}
+
+// rows [n_poly][limbs][N] from table limb 0 on against their seal, flags at d_flags; a null seal is skipped
+int verify_rows(hipStream_t st, const fhe_keyswitch *p, const uint64_t *words, const uint64_t *seal, size_t n_poly, size_t limbs, u32 *d_flags, u64 *part,
+                const BcCheck *hook = nullptr)
+{
+    if (!seal) return FHE_OK;
+    const SealArgs sa{words, p->t->d_lp.as<LimbParams>(), 0u, (u32)limbs, (u32)(n_poly * limbs), (u32)limbs, p->log_n};
+    BcCheck k = hook ? *hook : BcCheck{nullptr, -1, 0, 0, 0};
+    k.flags = d_flags;
+    hipError_t e = launch_seal_verify(st, sa, part, seal, k);
+    return e == hipSuccess ? FHE_OK : hip_fail(e, "launch_seal_verify");
+}
+
+// fhe_bsgs_matvec_checked (sm == nullptr) and fhe_bsgs_matvec_sealed
+int bsgs_body(const SealedMode *sm, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0, const uint64_t *d_c1,
+              const uint64_t *d_diags, size_t n1, size_t n2, const uint32_t *baby_elts, const uint64_t *const *d_baby_keys_prepared,
+              const uint32_t *giant_elts, const uint64_t *const *d_giant_keys, const fhe_abft *a, uint32_t *d_flags, void *stream);
 
 } // namespace
 
@@ -93,10 +159,60 @@ int fhe_bsgs_matvec_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, ui
                             const uint64_t *d_diags, size_t n1, size_t n2, const uint32_t *baby_elts, const uint64_t *const *d_baby_keys_prepared,
                             const uint32_t *giant_elts, const uint64_t *const *d_giant_keys, const fhe_abft *a, uint32_t *d_flags, void *stream)
 {
+    return bsgs_body(nullptr, ctx, p, d_out0, d_out1, d_c0, d_c1, d_diags, n1, n2, baby_elts, d_baby_keys_prepared, giant_elts, d_giant_keys, a, d_flags, stream);
+}
+
+int fhe_bsgs_matvec_sealed_layout(const fhe_keyswitch *p, size_t n1, size_t n2, int out[8])
+{
+    if (!p || !out) return fail(FHE_ERR_INVALID, "null argument");
+    if (!bsgs_shape_ok(n1, n2)) return fail(FHE_ERR_INVALID, "n1 and n2 are 1 to 4096");
+    const BmsLayout l = bms_layout(p, n1, n2);
+    if (l.total < 0) return fail(FHE_ERR_INVALID, "too many steps for one flag buffer");
+    for (int i = 0; i < 6; i++) out[i] = l.off[i];
+    out[6] = l.total;
+    out[7] = 0;
+    return FHE_OK;
+}
+
+int fhe_ctx_inject_fault_bsgs_sealed(fhe_ctx *ctx, int g, int b, int limb, long long coeff, int bit)
+{
+    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
+    if (g < 0) {
+        (void)ctx->bsgs_seal_fault.take();
+        return FHE_OK;
+    }
+    if (b < 0 || limb < 0 || coeff < 0 || bit < 0 || bit > 63) return fail(FHE_ERR_INVALID, "bad fault");
+    ctx->bsgs_seal_fault.g = g;
+    ctx->bsgs_seal_fault.b = b;
+    ctx->bsgs_seal_fault.limb = limb;
+    ctx->bsgs_seal_fault.coeff = coeff;
+    ctx->bsgs_seal_fault.bit = bit;
+    return FHE_OK;
+}
+
+int fhe_bsgs_matvec_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0, const uint64_t *d_c1,
+                           const uint64_t *d_diags, size_t n1, size_t n2, const uint32_t *baby_elts, const uint64_t *const *d_baby_keys_prepared,
+                           const uint32_t *giant_elts, const uint64_t *const *d_giant_keys, const fhe_abft *a, const uint64_t *const *d_seal_in,
+                           const uint64_t *const *d_seal_baby_keys, const uint64_t *const *d_seal_giant_keys, const uint64_t *d_seal_diags,
+                           uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
+{
+    const SealedMode sm{d_seal_in, d_seal_baby_keys, d_seal_giant_keys, d_seal_diags, d_seal_out};
+    return bsgs_body(&sm, ctx, p, d_out0, d_out1, d_c0, d_c1, d_diags, n1, n2, baby_elts, d_baby_keys_prepared, giant_elts, d_giant_keys, a, d_flags, stream);
+}
+
+} // extern "C"
+
+namespace {
+
+int bsgs_body(const SealedMode *sm, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0, const uint64_t *d_c1,
+              const uint64_t *d_diags, size_t n1, size_t n2, const uint32_t *baby_elts, const uint64_t *const *d_baby_keys_prepared,
+              const uint32_t *giant_elts, const uint64_t *const *d_giant_keys, const fhe_abft *a, uint32_t *d_flags, void *stream)
+{
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
     // the one-shot hooks of the steps this call runs belong to it whatever its outcome: all are taken here
     const StagedFault hf = ctx->hrc_fault.take(), kf = ctx->ksc_fault.take(), bf = ctx->bsgs_fault.take();
     const GaloisFault gf = ctx->gal_fault.take();
+    const fhe_ctx::DiagSealFault sf = sm ? ctx->bsgs_seal_fault.take() : fhe_ctx::DiagSealFault{};
     int rc = ksc_scope(ctx, p, a, d_flags, KsForm::CKKS, false);
     if (rc) return rc;
     if (!d_out0 || !d_out1 || !d_c0 || !d_c1 || !d_diags || !bsgs_shape_ok(n1, n2)) return fail(FHE_ERR_INVALID, "bad arguments");
@@ -108,9 +224,23 @@ int fhe_bsgs_matvec_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, ui
     if (d_out0 == d_c0 || d_out0 == d_c1 || d_out1 == d_c0 || d_out1 == d_c1 || d_out0 == d_out1) return fail(FHE_ERR_INVALID, "the product is out of place");
     const BmcLayout lay = bmc_layout(p, n1, n2);
     if (lay.total < 0) return fail(FHE_ERR_INVALID, "too many steps for one flag buffer");
-    HIP_TRY(hipSetDevice(ctx->device));
     const int L = p->L, logn = p->log_n;
     const size_t N = (size_t)1 << logn, part = (size_t)L * N;
+    BmsLayout sl{};
+    if (sm) {
+        sl = bms_layout(p, n1, n2);
+        if (sl.total < 0) return fail(FHE_ERR_INVALID, "too many steps for one flag buffer");
+        bool bad = misaligned({d_out0, d_out1, d_c0, d_c1, d_diags});
+        for (size_t b = 0; b + 1 < n1; b++) bad = bad || misaligned({d_baby_keys_prepared[b]});
+        for (size_t g = 0; g + 1 < n2; g++) bad = bad || misaligned({d_giant_keys[g]});
+        if (bad) return fail(FHE_ERR_INVALID, "sealed rows are read 16 bytes at a time: the buffers must be 16-byte aligned");
+        if (sf.g >= 0) {
+            if ((size_t)sf.g >= n2 || (size_t)sf.b >= n1 || sf.limb >= L || (size_t)sf.coeff >= N)
+                return fail(FHE_ERR_INVALID, "sealed-diagonal fault outside the call");
+            if (!sm->seal_diag) return fail(FHE_ERR_INVALID, "sealed-diagonal fault outside the call: no diagonal seals were given");
+        }
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
 
     // ---- the test hooks, checked against this call before anything is launched
     HrcHook hh;
@@ -141,6 +271,34 @@ int fhe_bsgs_matvec_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, ui
         HIP_TRY(p->bsgs.alloc(need));
     }
     u64 *rot = p->bsgs.as<u64>(), *inner = rot + (n1 - 1) * 2 * part, *tmp = inner + 2 * part;
+    const bool fused = sm && sm->seal_diag && n1 <= DIAG_SEAL_MAX_NB;
+    u64 *spart = nullptr;
+    u32 *d_sealed = d_flags;      // the sealed call's buffer; d_flags becomes the checked call's own block inside it
+    if (sm) {
+        // the partial-sum scratch of the context, sized once for the largest sweep of the call, before the first launch
+        size_t words = std::max(seal_part_words((u32)bsgs_key_rows(p), logn), seal_part_words((u32)L, logn));
+        if (sm->seal_diag) words = std::max(words, fused ? diag_seal_part_words((u32)L, logn, diag_seal_nb((u32)n1)) : seal_part_words((u32)(n1 * L), logn));
+        if (ctx->seal_part.bytes < words * 8) {
+            HIP_TRY(hipStreamSynchronize(st));        // (growing frees the old block)
+            HIP_TRY(ctx->seal_part.alloc(words * 8));
+        }
+        spart = ctx->seal_part.as<u64>();
+        HIP_TRY(hipMemsetAsync(d_sealed, 0, (size_t)sl.off[5] * sizeof(u32), st));
+        d_flags = d_sealed + sl.off[5];
+        // ---- the operands and keys at rest: a raised flag does not stop the call
+        const uint64_t *ops[2] = {d_c0, d_c1};
+        for (int h = 0; h < 2; h++)
+            if ((rc = verify_rows(st, p, ops[h], sm->seal_in ? sm->seal_in[h] : nullptr, 1, L, d_sealed + sl.off[h], spart))) return rc;
+        const size_t kr = bsgs_key_rows(p);
+        for (size_t b = 0; b + 1 < n1; b++)
+            if ((rc = verify_rows(st, p, d_baby_keys_prepared[b], sm->seal_baby ? sm->seal_baby[b] : nullptr, (size_t)p->dnum * 2, L + p->K,
+                                  d_sealed + sl.off[2] + b * kr, spart)))
+                return rc;
+        for (size_t g = 0; g + 1 < n2; g++)
+            if ((rc = verify_rows(st, p, d_giant_keys[g], sm->seal_giant ? sm->seal_giant[g] : nullptr, (size_t)p->dnum * 2, L + p->K,
+                                  d_sealed + sl.off[3] + g * kr, spart)))
+                return rc;
+    }
     HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)lay.total * sizeof(u32), st));
 
     // ---- baby block
@@ -159,8 +317,23 @@ int fhe_bsgs_matvec_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, ui
         // ---- inner sum of giant step g: straight into the result for g = 0
         u64 *s0 = g ? inner : d_out0, *s1 = g ? inner + part : d_out1;
         const DiagMacArgs da{s0, s1, d_diags + g * n1 * part, d_c0, d_c1, rot, lp, 0u, (u32)L, (u32)n1, logn};
-        hipError_t e = launch_diag_mac_checked(st, da, bc_check(bf.at((int)g, 0), block + lay.off[0]));
-        if (e != hipSuccess) return hip_fail(e, "launch_diag_mac_checked");
+        hipError_t e;
+        if (sm && sm->seal_diag) {
+            // ---- the diagonal rows of this step against their seals: on the load that feeds the product, or (n1 > 16) in a sweep before it
+            u32 *dflags = d_sealed + sl.off[4] + g * n1 * L;
+            const u64 *dseal = sm->seal_diag + g * n1 * L * 2;
+            const bool hit = sf.g == (int)g;
+            if (fused) {
+                const DiagHit dh{(u32)sf.b, (u32)sf.limb, (u64)sf.coeff, hit ? (u64)1 << sf.bit : 0};
+                if ((e = launch_diag_mac_sealed(st, da, spart, dseal, dflags, bc_check(bf.at((int)g, 0), block + lay.off[0]), dh)) != hipSuccess)
+                    return hip_fail(e, "launch_diag_mac_sealed");
+            } else {
+                const BcCheck hook{nullptr, hit ? 0 : -1, (u32)(sf.b * L + sf.limb), (u64)sf.coeff, (u64)1 << sf.bit};
+                if ((rc = verify_rows(st, p, da.diag, dseal, n1, L, dflags, spart, &hook))) return rc;
+            }
+        }
+        if (!fused && (e = launch_diag_mac_checked(st, da, bc_check(bf.at((int)g, 0), block + lay.off[0]))) != hipSuccess)
+            return hip_fail(e, "launch_diag_mac_checked");
         if (!g) continue;
         // ---- sigma of both parts of the inner sum
         const GalSeg seg{tmp, inner, (u32)(2 * L)};
@@ -171,7 +344,16 @@ int fhe_bsgs_matvec_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, ui
         // ---- (out0, out1) = key switch of sigma(s1) + (t0, out1)
         if ((rc = keyswitch_checked(p, KsForm::CKKS, d_out0, d_out1, tmp + part, d_giant_keys[g - 1], tmp, d_out1, a, block + lay.off[3], st, g == 1 ? kf : StagedFault{}))) return rc;
     }
+    if (!sm || !sm->seal_out) return FHE_OK;
+    // ---- both outputs sealed for the next sealed call
+    const uint64_t *outs[2] = {d_out0, d_out1};
+    for (int h = 0; h < 2; h++) {
+        if (!sm->seal_out[h]) continue;
+        const SealArgs sa{outs[h], lp, 0u, (u32)L, (u32)L, (u32)L, logn};
+        hipError_t e = launch_seal(st, sa, spart, sm->seal_out[h], BcCheck{nullptr, -1, 0, 0, 0});
+        if (e != hipSuccess) return hip_fail(e, "launch_seal");
+    }
     return FHE_OK;
 }
 
-} // extern "C"
+} // namespace

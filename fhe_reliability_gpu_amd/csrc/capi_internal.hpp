@@ -119,6 +119,17 @@ struct fhe_ctx {
     PointHook seal_fault;  // fhe_ctx_inject_fault_seal: unit = the row, coeff = the word (point 0 when armed)
     PointHook carry_fault; // fhe_ctx_inject_fault_seal_carry: point = CARRY_AT_*, unit = the row, coeff = the word; taken by the carry launch
     int carry_skip = 0;    // that finds carry_skip == 0, every earlier one counts it down
+    // fhe_ctx_inject_fault_bsgs_sealed: one bit of diagonal word (g, b, limb, coeff) as fhe_bsgs_matvec_sealed loads it; g < 0 = disarmed
+    struct DiagSealFault {
+        int g = -1, b = 0, limb = 0, bit = 0;
+        long long coeff = 0;
+        DiagSealFault take()
+        {
+            const DiagSealFault f = *this;
+            g = -1;
+            return f;
+        }
+    } bsgs_seal_fault;
     DevBuf seal_part;      // fhe_seal / fhe_seal_verify and the sealed composites: the chunks' partial sums, [rows][chunks][2] (the carried adds: [4] or [6]; grown on demand)
     DevBuf gal_sums;       // checked Galois permutation: the units' source-side and destination-side sums, [2][units] (grown on demand)
     int geo = 1;           // column-tile geometry of the two-launch path (ntt_launch.hpp)

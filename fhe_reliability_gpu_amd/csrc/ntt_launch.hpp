@@ -383,4 +383,16 @@ size_t carry_part_words(u32 units, int logn, bool loc);
 hipError_t launch_modadd_carry(hipStream_t st, const PointwiseArgs &p, bool sub, u64 *part, const u64 *seal_a, const u64 *seal_b, u64 *seal_c,
                                const u64 *loc_a, const u64 *loc_b, u64 *loc_c, const BcCheck &k);
 
+// ---- bsgs_sealed.hip: the inner sum of the BSGS product with the diagonals' seals verified on the consuming load (bsgs_seal.hpp) ----
+// the compile-time bound on the baby steps the launch picks for n1 <= DIAG_SEAL_MAX_NB: the smallest of 4, 8, 16 that holds n1
+u32 diag_seal_nb(u32 n1);
+// words of the partial-sum scratch a launch needs: [limbs][chunks per row][nb][2]
+size_t diag_seal_part_words(u32 limbs, int logn, u32 nb);
+// launch_diag_mac_checked's words and flags (k) with every buffer of a 16-byte aligned, logn >= 1 and n1 <= DIAG_SEAL_MAX_NB;
+// seal = [n1 * limbs][2] the stored seals of this giant step's diagonal rows (row b * limbs + l); seal_flags[b * limbs + l] |=
+// SEAL_SUM where the row as loaded differs from its seal, SEAL_RANGE where a word is >= q_l; zeroed by the caller.  hit.mask != 0:
+// the sealed call's test fault, in the register as loaded
+struct DiagHit;
+hipError_t launch_diag_mac_sealed(hipStream_t st, const DiagMacArgs &a, u64 *part, const u64 *seal, u32 *seal_flags, const BcCheck &k, const DiagHit &hit);
+
 } // namespace fhe

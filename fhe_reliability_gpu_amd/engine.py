@@ -897,14 +897,7 @@ class KeySwitch:
         gk = (vp * max(1, n2 - 1))(*[k.ptr for k in giant_keys])
         f = _checked_flags(self.eng, total, lambda fl: lib.fhe_bsgs_matvec_checked(
             self.eng._h, self._h, o0.ptr, o1.ptr, c0.ptr, c1.ptr, diags.ptr, n1, n2, be, bk, ge, gk, abft._h, fl.ptr, stream), stream)
-        baby = self._hoisted_flags(f, n1 - 1, lay["baby"]) if n1 > 1 else None
-        giant = []
-        for g in range(n2):
-            base = lay["giant0"] + g * lay["giant_words"]
-            blk = self._split_flags(f, lay["giant"], self.BSGS_GIANT_STAGES[:3], base)
-            blk["keyswitch"] = self._split_flags(f, self.checked_layout(), self.CHECKED_STAGES, base + lay["giant"]["keyswitch"][0])
-            giant.append(blk)
-        return o0, o1, {"baby": baby, "giant": giant}
+        return o0, o1, self._bsgs_checked_flags(f, n1, n2)
 
     def rescale(self, c: DeviceArray, n_parts: int = 2, stream=None) -> DeviceArray:
         """``mod_switch_to_next_inplace`` (dotprod_test.cu:115): [n_parts][L][N] -> [n_parts][L-1][N]."""
@@ -1152,6 +1145,62 @@ class KeySwitch:
             d["add1"] = f[base + lay["add"] + L:base + lay["add"] + 2 * L].copy()
             steps.append(d)
         return acc[0], acc[1], tuple(sl), steps
+
+    # ---- sealed BSGS matrix-vector product: the diagonals verified on the load that multiplies them (bsgs_sealed.hip) ----
+    def seal_diagonals(self, diags: DeviceArray, n1: int, n2: int, stream=None) -> DeviceArray:
+        """The seals of the diagonals ``[n2][n1][L][N]``: ``[n2 * n1 * L][2]``, row ``(g * n1 + b) * L + l``."""
+        return self.t.seal(diags, limbs=self.L, start=0, n_poly=n1 * n2, stream=stream)
+
+    def bsgs_matvec_sealed_layout(self, n1: int, n2: int):
+        """``{"c0", "c1": (offset, (L,)), "baby_keys": (offset, (n1 - 1, dnum, 2, M)), "giant_keys": (offset, (n2 - 1, dnum, 2, M)),
+        "diags": (offset, (n2, n1, L)), "checked": offset, "total": n}`` of ``bsgs_matvec_sealed``'s flag buffer; the checked block
+        is laid out as ``bsgs_matvec_checked_layout(n1, n2)``."""
+        out = (C.c_int * 8)()
+        check(lib.fhe_bsgs_matvec_sealed_layout(self._h, n1, n2, out))
+        L, M, d = self.L, self.L + self.K, self.dnum
+        shapes = ((L,), (L,), (n1 - 1, d, 2, M), (n2 - 1, d, 2, M), (n2, n1, L))
+        lay = {name: (int(out[i]), shapes[i]) for i, name in enumerate(("c0", "c1", "baby_keys", "giant_keys", "diags"))}
+        lay["checked"], lay["total"] = int(out[5]), int(out[6])
+        return lay
+
+    def _bsgs_checked_flags(self, f, n1, n2, base=0):
+        """The flag dictionary of ``bsgs_matvec_checked`` from its block, which starts at ``f[base]``."""
+        lay = self.bsgs_matvec_checked_layout(n1, n2)
+        baby = self._hoisted_flags(f, n1 - 1, base + lay["baby"]) if n1 > 1 else None
+        giant = []
+        for g in range(n2):
+            b0 = base + lay["giant0"] + g * lay["giant_words"]
+            blk = self._split_flags(f, lay["giant"], self.BSGS_GIANT_STAGES[:3], b0)
+            blk["keyswitch"] = self._split_flags(f, self.checked_layout(), self.CHECKED_STAGES, b0 + lay["giant"]["keyswitch"][0])
+            giant.append(blk)
+        return {"baby": baby, "giant": giant}
+
+    def bsgs_matvec_sealed(self, c0: DeviceArray, c1: DeviceArray, diags: DeviceArray, n1: int, n2: int, baby_elts, baby_keys_prepared,
+                           giant_elts, giant_keys, abft: "Abft", seals=None, baby_key_seals=None, giant_key_seals=None,
+                           diag_seal: Optional[DeviceArray] = None, stream=None):
+        """``bsgs_matvec_checked`` with the operands protected at rest: ``(o0, o1, (seal0, seal1), flags)``, the words
+        ``bsgs_matvec``'s bit for bit.  ``seals`` = the seals of (c0, c1), ``baby_key_seals`` = ``seal_key`` of each PREPARED baby key,
+        ``giant_key_seals`` = ``seal_key`` of each giant key, ``diag_seal`` = ``seal_diagonals``; any of them, or an entry, may be
+        None: not verified.  c0, c1 and the keys are verified by sweeps of their own; every diagonal word is digested from the
+        register that multiplies it, so no diagonal word is read twice and the verified load is the consuming load (n1 > 16: a
+        verifying sweep per giant step instead).  ``flags = {"c0", "c1": [L], "baby_keys": [n1 - 1][dnum][2][M], "giant_keys":
+        [n2 - 1][dnum][2][M], "diags": [n2][n1][L], "checked": <bsgs_matvec_checked's dict>}``, input words with the bits of
+        ``seal_verify``.  A raised input flag does not stop the call."""
+        lay = self.bsgs_matvec_sealed_layout(n1, n2)
+        be = (C.c_uint32 * max(1, n1 - 1))(*[int(g) for g in baby_elts])
+        ge = (C.c_uint32 * max(1, n2 - 1))(*[int(g) for g in giant_elts])
+        bk = (vp * max(1, n1 - 1))(*[k.ptr for k in baby_keys_prepared])
+        gk = (vp * max(1, n2 - 1))(*[k.ptr for k in giant_keys])
+
+        def ptrs(xs, n):
+            return (vp * max(1, n))(*[x.ptr if x is not None else None for x in xs]) if xs is not None else None
+        bs, gs = ptrs(baby_key_seals, n1 - 1), ptrs(giant_key_seals, n2 - 1)
+        o0, o1, so, f = self._sealed(lay, ("c0", "c1"), self.L, seals, lambda o0, o1, sin, sout, fl: lib.fhe_bsgs_matvec_sealed(
+            self.eng._h, self._h, o0.ptr, o1.ptr, c0.ptr, c1.ptr, diags.ptr, n1, n2, be, bk, ge, gk, abft._h, sin, bs, gs,
+            diag_seal.ptr if diag_seal is not None else None, sout, fl.ptr, stream), stream)
+        flags = self._split_flags(f, lay, ("c0", "c1", "baby_keys", "giant_keys", "diags"))
+        flags["checked"] = self._bsgs_checked_flags(f, n1, n2, lay["checked"])
+        return o0, o1, so, flags
 
     # ---- the same composites repairing their operands and key in place (seal_repair.hip) ----
     def seal_key_locator(self, key: DeviceArray, stream=None) -> DeviceArray:

@@ -21,7 +21,12 @@ uncorrectable, as the flags say.  Exit status 1 when a trial was missed, or was 
 rotate_sum_sealed, whose carried adds verify their operands on the load that feeds the adder and hand the seals on without a sealing
 or verifying launch in between.  Output and exit status as in the default mode; the fault-free words equal the default chain's.
 
-python -m fhe_reliability_gpu_amd.tools.flip_coverage [--repair | --rotate-sum] [--trials 32] [--num-symbols 1] [--bits-per-symbol 1] [--logn 14] [--row 8] [--seed 1]"""
+--bsgs applies the same fault model to the operands a linear layer keeps longest: a CKKS plan of the same shape runs
+bsgs_matvec_sealed (n1 = n2 = 4) with every operand sealed, and each trial flips its bits in a diagonal (odd trials) or in a giant key
+(even trials) at rest.  Per trial the tool prints which flag groups were raised; a diagonal is caught by the inner sum itself, on
+the load that multiplies it.  Exit status as in the default mode.
+
+python -m fhe_reliability_gpu_amd.tools.flip_coverage [--repair | --rotate-sum | --bsgs] [--trials 32] [--num-symbols 1] [--bits-per-symbol 1] [--logn 14] [--row 8] [--seed 1]"""
 import argparse
 import sys
 
@@ -40,6 +45,8 @@ def nonzero(flags):
         return 0
     if isinstance(flags, dict):
         return sum(nonzero(v) for v in flags.values())
+    if isinstance(flags, (list, tuple)):
+        return sum(nonzero(v) for v in flags)
     return int(np.count_nonzero(flags))
 
 
@@ -53,12 +60,17 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--repair", action="store_true", help="run the chain through the repairing composites and report corrections")
     ap.add_argument("--rotate-sum", action="store_true", help="run the rotate-and-add rounds as one rotate_sum_sealed call")
+    ap.add_argument("--bsgs", action="store_true", help="flip a diagonal or a giant key of a sealed BSGS matrix-vector product")
     a = ap.parse_args()
     if a.repair and a.rotate_sum:
         ap.error("--repair and --rotate-sum exclude each other: the composite has no repairing form")
+    if a.bsgs and (a.repair or a.rotate_sum):
+        ap.error("--bsgs is a mode of its own")
     if a.row < 1 or a.row & (a.row - 1) or not 1 <= a.bits_per_symbol <= 64 or a.num_symbols < 0:
         ap.error("row is a power of two, bits-per-symbol 1..64, num-symbols >= 0")
     eng = F.Engine(0)
+    if a.bsgs:
+        return main_bsgs(a, eng)
     N, R = 1 << a.logn, L - 1
     qs = F.create_moduli(N, [50] * (L + K))
     rng = np.random.default_rng(a.seed)
@@ -205,6 +217,61 @@ def main_repair(a, eng, rng, ct_a, clean, chain_repair):
     print(f"summary: {a.trials} trials (one control): {totals['corrected']} corrected, {totals['uncorrectable']} uncorrectable, {totals['missed']} missed; "
           f"{totals['exact']} final results equal the fault-free run bit for bit; {wrong} reported corrected with a differing result")
     return 1 if missed or wrong else 0
+
+
+def main_bsgs(a, eng):
+    """the trials of --bsgs: the reference's flips in a diagonal or a giant key at rest, through bsgs_matvec_sealed"""
+    N, n1, n2 = 1 << a.logn, 4, 4
+    qs = F.create_moduli(N, [50] * (L + K))
+    rng = np.random.default_rng(a.seed)
+    t = eng.tables(a.logn, qs)
+    ks, ab = F.KeySwitch(eng, t, L, K, DNUM), F.Abft(eng, t)
+    poly = lambda moduli: np.stack([rng.integers(0, q, N, dtype=np.uint64) for q in moduli])
+    key = lambda: np.stack([np.stack([poly(qs) for _ in range(2)]) for _ in range(DNUM)])
+    c0, c1 = eng.upload(poly(qs[:L])), eng.upload(poly(qs[:L]))
+    diags = np.stack([np.stack([poly(qs[:L]) for _ in range(n1)]) for _ in range(n2)])
+    baby_elts, giant_elts = [pow(5, b, 2 * N) for b in range(1, n1)], [pow(5, g * n1, 2 * N) for g in range(1, n2)]
+    prepared = [ks.prepare_galois_key(eng.upload(key()), e) for e in baby_elts]
+    giant = [key() for _ in giant_elts]
+    d_diags, d_giant = eng.upload(diags), [eng.upload(k) for k in giant]
+    # seals, taken once of the clean data: what travels with the ciphertext, the keys and the diagonals
+    seals = (t.seal(c0, limbs=L), t.seal(c1, limbs=L))
+    s_baby, s_giant, s_diag = [ks.seal_key(k) for k in prepared], [ks.seal_key(k) for k in d_giant], ks.seal_diagonals(d_diags, n1, n2)
+
+    def run(dd, dg):
+        o0, o1, _, fl = ks.bsgs_matvec_sealed(c0, c1, dd, n1, n2, baby_elts, prepared, giant_elts, dg, ab, seals=seals, baby_key_seals=s_baby,
+                                              giant_key_seals=s_giant, diag_seal=s_diag)
+        return np.concatenate([o0.download().reshape(-1), o1.download().reshape(-1)]), {k: nonzero(v) for k, v in fl.items()}
+
+    clean, groups = run(d_diags, d_giant)
+    assert not any(groups.values()), "the clean call raised a flag"
+    print(f"N = 2^{a.logn}, L = {L}, K = {K}, dnum = {DNUM}, n1 = {n1}, n2 = {n2}: bsgs_matvec_sealed; {a.num_symbols} symbols x {a.bits_per_symbol} bits per trial")
+    missed, tally = 0, {"diagonal": [0, 0], "giant key": [0, 0]}
+    for trial in range(a.trials):
+        target = "diagonal" if trial % 2 else "giant key"
+        which = int(rng.integers(0, len(giant)))
+        src = diags if target == "diagonal" else giant[which]
+        d = eng.upload(src)
+        n_sym = 0 if trial == 0 else a.num_symbols
+        for idx in rng.integers(0, src.size, n_sym):
+            for bit in rng.choice(64, a.bits_per_symbol, replace=False):
+                check(lib.fhe_flip_bit(eng._h, d.ptr, int(idx), int(bit), None))
+        flipped = int(np.count_nonzero(d.download().reshape(-1) != src.reshape(-1)))
+        out, groups = run(d if target == "diagonal" else d_diags, d_giant if target == "diagonal" else d_giant[:which] + [d] + d_giant[which + 1:])
+        corrupted = int(np.count_nonzero(out != clean))
+        own = groups["diags" if target == "diagonal" else "giant_keys"]
+        detected = own > 0
+        missed += flipped > 0 and not detected
+        if flipped:
+            tally[target][0] += 1
+            tally[target][1] += int(detected)
+        assert flipped > 0 or (corrupted == 0 and not any(groups.values())), "the control trial differs from the clean run"
+        print(f"trial {trial:3d}: {target:9s} flipped words {flipped:3d}, corrupted output words {corrupted:7d} of {out.size}, raised flag words "
+              f"{', '.join(f'{k} {v}' for k, v in groups.items() if v) or 'none'}, detected {'yes' if detected else 'no'}", flush=True)
+    eng.check()
+    print(f"summary: {a.trials} trials (one control): " + ", ".join(f"{k} {v[1]} of {v[0]} detected on its own rows" for k, v in tally.items())
+          + f"; {missed} with a flip and no flag")
+    return 1 if missed else 0
 
 
 class _View:

@@ -1033,6 +1033,44 @@ int fhe_rotate_sum_sealed_layout(const fhe_keyswitch *p, int n_steps, int out[4]
 int fhe_rotate_sum_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_c0, uint64_t *d_c1, uint64_t *d_tmp0, uint64_t *d_tmp1, int n_steps,
                           const uint32_t *galois_elts, const uint64_t *const *d_galois_keys, const fhe_abft *a, uint64_t *const *d_seal /* [2] */,
                           const uint64_t *const *d_seal_keys /* [n_steps] */, uint64_t *const *d_seal_tmp /* [2] */, uint32_t *d_flags, void *stream);
+/* fhe_bsgs_matvec_checked with its operands protected at rest, and the diagonals -- the largest and longest-lived operand of the
+ * call -- verified on the very load that multiplies them.  CKKS plans only, the scope of fhe_bsgs_matvec_checked.  On `stream`:
+ *   1. sweeps of their own (fhe_seal_verify's) over c0 and c1 against d_seal_in[0..1] ([L][2]), over every prepared baby key against
+ *      d_seal_baby_keys[b] and every giant key against d_seal_giant_keys[g] ([dnum 2 (L + K)][2]; seal the PREPARED baby key, as the
+ *      caller holds it);
+ *   2. the baby block of fhe_bsgs_matvec_checked, unchanged;
+ *   3. per giant step the inner sum of fhe_bsgs_matvec_checked -- same terms, order, folds, residue flags and fault points -- in a
+ *      kernel that digests every diagonal word from the register it hands to the product, with the weight of its index in the row,
+ *      and holds each row's two sums and the window word < q_l against d_seal_diags[(g n1 + b) L + l][2] (fhe_seal of d_diags with
+ *      n_poly = n1 n2).  No diagonal word is read twice, and a transient fault on the consuming load is seen.  n1 > 16: a verifying
+ *      sweep over the step's n1 L diagonal rows precedes the checked inner sum instead; the flags are laid out the same.  The rest
+ *      of the giant step is fhe_bsgs_matvec_checked's;
+ *   4. fhe_seal of both outputs into d_seal_out[0..1] ([L][2]; the array or an entry may be NULL).
+ * The seal arrays are HOST arrays of device pointers; an array, or an entry, may be NULL: that operand is not verified (NULL
+ * d_seal_diags: the inner sum is fhe_bsgs_matvec_checked's).  A raised input flag does not stop the call.  The words are
+ * fhe_bsgs_matvec's, bit for bit.
+ * Flags, cleared by the call: [c0: L][c1: L][baby keys: (n1 - 1) key rows][giant keys: (n2 - 1) key rows][diagonals: n2 n1 L]
+ * [fhe_bsgs_matvec_checked's own block, exactly its layout], input words with the bits of fhe_seal_verify (1 a sum differs or a
+ * stored sum is not canonical, 2 a word >= q_l).  fhe_bsgs_matvec_sealed_layout gives the six offsets in out[0..5], the total in
+ * out[6], out[7] = 0; FHE_ERR_INVALID for n1 or n2 outside 1 .. 4096 and for a total above INT_MAX.
+ * Every buffer (outputs, c0, c1, diagonals, keys) must be 16-byte aligned, else FHE_ERR_INVALID before any launch; otherwise the
+ * statuses and argument rules are fhe_bsgs_matvec_checked's, and its hooks are taken and fire as there.
+ * Test hook: fhe_ctx_inject_fault_bsgs_sealed(g, b, limb, coeff, bit), one shot, g < 0 clears; taken by the next
+ * fhe_bsgs_matvec_sealed whatever its outcome.  n1 <= 16: the bit of diagonal word (g, b, limb, coeff) is flipped in the register as
+ * loaded, before both the digest and the product read it -- a fault on the consuming load: the (g, b, limb) word is raised and the
+ * product changes, while the residue flags stay 0.  n1 > 16: the flip lives in the verifying sweep's load only, as
+ * fhe_ctx_inject_fault_seal's.  A hook outside the call (g >= n2, b >= n1, limb >= L, coeff >= N, or no diagonal seals) returns
+ * FHE_ERR_INVALID with nothing launched.
+ * Not covered: the baby rotations, which sit in the plan's scratch and are re-read by every giant step; the key rows are verified
+ * by a sweep of their own, not on the key switch's loads; no repairing form; BGV and sharded plans. */
+int fhe_bsgs_matvec_sealed_layout(const fhe_keyswitch *p, size_t n1, size_t n2, int out[8]);
+int fhe_bsgs_matvec_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0, const uint64_t *d_c1,
+                           const uint64_t *d_diags, size_t n1, size_t n2, const uint32_t *baby_elts,
+                           const uint64_t *const *d_baby_keys_prepared, const uint32_t *giant_elts, const uint64_t *const *d_giant_keys,
+                           const fhe_abft *a, const uint64_t *const *d_seal_in /* [2] */, const uint64_t *const *d_seal_baby_keys /* [n1 - 1] */,
+                           const uint64_t *const *d_seal_giant_keys /* [n2 - 1] */, const uint64_t *d_seal_diags, uint64_t *const *d_seal_out /* [2] */,
+                           uint32_t *d_flags, void *stream);
+int fhe_ctx_inject_fault_bsgs_sealed(fhe_ctx *ctx, int g, int b, int limb, long long coeff, int bit);
 
 /* ---- fault injection ---------------------------------------------------------------- */
 /* _flip_bit_kernel<<<1,1>>> (reliability_test/dotprod_test.cu:31-33,55): data[idx] ^= 1 << bit */
