@@ -191,6 +191,10 @@ _SIG = {
     "fhe_bsgs_matvec_sealed": (ci, [vp, vp, vp, vp, vp, vp, vp, sz, sz, C.POINTER(C.c_uint32), C.POINTER(vp), C.POINTER(C.c_uint32), C.POINTER(vp), vp,
                                     C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, C.POINTER(vp), vp, vp]),
     "fhe_ctx_inject_fault_bsgs_sealed": (ci, [vp, ci, ci, ci, C.c_longlong, ci]),
+    "fhe_tensor_product_sealed_layout": (ci, [sz, sz, C.POINTER(ci)]),
+    "fhe_tensor_product_sealed": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, C.POINTER(vp), C.POINTER(vp), vp, vp]),
+    "fhe_ctx_inject_fault_tensor_sealed": (ci, [vp, ci, ci, C.c_longlong, ci]),
+    "fhe_hmult_sealed_fused": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, C.POINTER(vp), vp, C.POINTER(vp), vp, vp]),
     "fhe_ctx_trace": (ci, [vp, ci]),
     "fhe_ctx_trace_read": (ci, [vp, C.c_char_p, sz, C.POINTER(sz)]),
 }

@@ -148,11 +148,30 @@ int rsc_hook(const fhe_keyswitch *p, KsForm form, const StagedFault &ft, size_t 
 // at d_flags
 int rescale_checked(fhe_keyswitch *p, KsForm form, uint64_t *const *outs, const uint64_t *d_in, size_t n_parts, const fhe_abft *a, uint32_t *d_flags,
                     hipStream_t st, const StagedFault &ft);
-// the multiply behind an entry point (fhe_hmult_checked, fhe_bgv_hmult_checked, fhe_hmult_sealed) and its layout
+// the multiply behind an entry point (fhe_hmult_checked, fhe_bgv_hmult_checked, fhe_hmult_sealed, fhe_hmult_sealed_fused) and its
+// layout.  sealed != nullptr (fhe_hmult_sealed_fused): the tensor step is the sealed one (tensor_sealed.hip) instead of
+// fhe_tensor_product_checked -- same words, same residue flags at the same place -- and the call takes the sealed tensor product's
+// hook as well; absent, the launch list is the checked multiply's own
+struct SealedTensorStep {
+    const uint64_t *const *seal_in;      // HOST array of the seals of a0, a1, b0, b1; an entry or the array may be null
+    uint32_t *flags_op[4];               // the operands' row flags, [L] each, zeroed by the caller
+};
 int hmult_checked_layout(const fhe_keyswitch *p, KsForm form, int rescale, int out[4]);
 int hmult_checked(KsForm form, KsHookSlot ks_hook, KsHookSlot rs_hook, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1,
                   const uint64_t *d_a0, const uint64_t *d_a1, const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale,
-                  const fhe_abft *a, uint32_t *d_flags, void *stream);
+                  const fhe_abft *a, uint32_t *d_flags, void *stream, const SealedTensorStep *sealed = nullptr);
+
+// defined in capi_tensor_sealed.cpp
+// the sealed tensor product's hook as a call of `units` rows took it (ctx->tensor_seal_fault), checked against that call
+int tensor_seal_hit(const fhe_ctx::TensorSealFault &f, size_t units, int log_n, TensorSealHit &hit);
+// words of ctx->seal_part the sealed tensor product of `units` rows needs
+size_t tensor_sealed_scratch_words(size_t units, int log_n, bool out);
+// the launches of the sealed tensor product over rows [n_poly][limbs]: d = {d0, d1, d2}, ops = {a0, a1, b0, b1}, all 16-byte
+// aligned and log_n >= 1 (the caller has checked both, the limb range and the hooks); seal_in / seal_out: HOST arrays as the entry
+// point takes them; flags_op[o] = [rows], k.flags = [rows][3], all zeroed by the caller; grows ctx->seal_part where it is too small
+int tensor_sealed_run(fhe_ctx *ctx, hipStream_t st, uint64_t *const d[3], const uint64_t *const ops[4], const fhe_ntt_tables *t, size_t n_poly, size_t limbs,
+                      size_t start_idx, const uint64_t *const *seal_in, uint64_t *const *seal_out, uint32_t *const flags_op[4], const BcCheck &k,
+                      const TensorSealHit &hit);
 
 // defined in capi_rotate_hoisted_checked.cpp
 // the checked permutation of up to two row ranges that share one flags array (units counted through the segments in order, the

@@ -182,14 +182,20 @@ int hmult_validate(KsForm form, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0
 
 int hmult_checked(KsForm form, KsHookSlot ks_hook, KsHookSlot rs_hook, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1,
                   const uint64_t *d_a0, const uint64_t *d_a1, const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale,
-                  const fhe_abft *a, uint32_t *d_flags, void *stream)
+                  const fhe_abft *a, uint32_t *d_flags, void *stream, const SealedTensorStep *sealed)
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
     // the one-shot hooks of the steps this call runs belong to it whatever its outcome: the key switch's and (when it rescales) the
-    // rescale's are taken here, the pointwise one by the tensor step (cleared here when the call ends before it)
+    // rescale's are taken here, the pointwise one by the tensor step (cleared here when the call ends before it), and so is the
+    // sealed tensor product's when that is the tensor step
     const StagedFault kf = (ctx->*ks_hook).take(), rf = rescale ? (ctx->*rs_hook).take() : StagedFault{};
     int lay[4];
     int rc = hmult_validate(form, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, d_flags, kf, rf, lay);
+    TensorSealHit hit{-1, 0, 0, 0};
+    if (sealed) {
+        const fhe_ctx::TensorSealFault tf = ctx->tensor_seal_fault.take();
+        if (!rc) rc = tensor_seal_hit(tf, (size_t)p->L, p->log_n, hit);
+    }
     if (rc) {
         (void)ctx->pw_fault.take();
         return rc;
@@ -200,7 +206,13 @@ int hmult_checked(KsForm form, KsHookSlot ks_hook, KsHookSlot rs_hook, fhe_ctx *
     u64 *d0 = p->hm.as<u64>(), *d1 = d0 + L * N, *d2 = d1 + L * N, *pre = p->hm_pre.as<u64>();
     // (the operands are read by the first step only, the outputs written by the last launches of the last step: an output may reuse
     // an operand's buffer, as for fhe_hmult)
-    if ((rc = fhe_tensor_product_checked(ctx, d0, d1, d2, d_a0, d_a1, d_b0, d_b1, p->t, L, 0, d_flags + lay[0], st))) return rc;
+    if (sealed) {
+        BcCheck k{d_flags + lay[0], -1, 0, 0, 0};
+        if ((rc = pointwise_fault(ctx->pw_fault.take(), true, L << p->log_n, p->log_n, k))) return rc;      // validated above
+        uint64_t *const d[3] = {d0, d1, d2};
+        const uint64_t *const ops[4] = {d_a0, d_a1, d_b0, d_b1};
+        if ((rc = tensor_sealed_run(ctx, st, d, ops, p->t, 1, L, 0, sealed->seal_in, nullptr, sealed->flags_op, k, hit))) return rc;
+    } else if ((rc = fhe_tensor_product_checked(ctx, d0, d1, d2, d_a0, d_a1, d_b0, d_b1, p->t, L, 0, d_flags + lay[0], st))) return rc;
     if (!rescale) return keyswitch_checked(p, form, d_out0, d_out1, d2, d_relin_key, d0, d1, a, d_flags + lay[1], st, kf);
     if ((rc = keyswitch_checked(p, form, pre, pre + L * N, d2, d_relin_key, d0, d1, a, d_flags + lay[1], st, kf))) return rc;
     uint64_t *outs[3] = {d_out0, d_out1, nullptr};

@@ -130,7 +130,19 @@ struct fhe_ctx {
             return f;
         }
     } bsgs_seal_fault;
-    DevBuf seal_part;      // fhe_seal / fhe_seal_verify and the sealed composites: the chunks' partial sums, [rows][chunks][2] (the carried adds: [4] or [6]; grown on demand)
+    // fhe_ctx_inject_fault_tensor_sealed: one bit of word coeff of row `row` of operand op (a0, a1, b0, b1) as fhe_tensor_product_sealed
+    // or fhe_hmult_sealed_fused loads it; op < 0 = disarmed
+    struct TensorSealFault {
+        int op = -1, row = 0, bit = 0;
+        long long coeff = 0;
+        TensorSealFault take()
+        {
+            const TensorSealFault f = *this;
+            op = -1;
+            return f;
+        }
+    } tensor_seal_fault;
+    DevBuf seal_part;      // fhe_seal / fhe_seal_verify and the sealed composites: the chunks' partial sums, [rows][chunks][2] (the carried adds: [4] or [6], the sealed tensor product: [8] or [14]; grown on demand)
     DevBuf gal_sums;       // checked Galois permutation: the units' source-side and destination-side sums, [2][units] (grown on demand)
     int geo = 1;           // column-tile geometry of the two-launch path (ntt_launch.hpp)
     bool resident = false; // 2^13 / 2^14: one LDS-resident pass instead of two launches (opt-in, see ntt_plan.hpp)

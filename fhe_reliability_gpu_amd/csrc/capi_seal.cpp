@@ -123,8 +123,13 @@ SealedForm sealed_form(const fhe_keyswitch *p)
 
 size_t key_rows(const fhe_keyswitch *p) { return (size_t)p->dnum * 2 * (p->L + p->K); }
 
-// scratch for the largest launch of a sealed composite (the key's rows), before anything is launched
-int sealed_scratch(fhe_ctx *ctx, const fhe_keyswitch *p, u64 **part) { return seal_scratch(ctx, seal_part_words((u32)key_rows(p), p->log_n), part); }
+// scratch for the largest launch of a sealed composite (the key's rows; tensor: or the sealed tensor step's), before anything is
+// launched
+int sealed_scratch(fhe_ctx *ctx, const fhe_keyswitch *p, bool tensor, u64 **part)
+{
+    const size_t key = seal_part_words((u32)key_rows(p), p->log_n);
+    return seal_scratch(ctx, tensor ? std::max(key, tensor_sealed_scratch_words((size_t)p->L, p->log_n, false)) : key, part);
+}
 
 bool misaligned(std::initializer_list<const void *> ptrs)
 {
@@ -238,15 +243,20 @@ int fhe_hmult_sealed_layout(const fhe_keyswitch *p, int rescale, int out[8])
     return FHE_OK;
 }
 
-// fhe_hmult_sealed (rm == nullptr) and fhe_hmult_sealed_repair
-static int hmult_sealed_body(const RepairMode *rm, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_a0,
+// fhe_hmult_sealed (rm == nullptr), fhe_hmult_sealed_repair and fhe_hmult_sealed_fused (fused, never with rm: repair needs the
+// sweep).  fused: the four operand sweeps are gone and the checked multiply's tensor step is the sealed tensor product
+// (capi_tensor_sealed.cpp), which verifies a0, a1, b0, b1 on the load that multiplies them and writes their row flags where the
+// sweeps wrote them; the key's sweep, the key switch, the rescale and the output seals are the same launches
+static int hmult_sealed_body(const RepairMode *rm, bool fused, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_a0,
                              const uint64_t *d_a1, const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a,
                              const uint64_t *const *d_seal_in, const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
     const SealedForm f = sealed_form(p);
+    SealedTensorStep step{d_seal_in, {nullptr, nullptr, nullptr, nullptr}};
     auto checked = [&](uint32_t *flags) {
-        return hmult_checked(f.form, f.ks_hook, f.rs_hook, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, flags, stream);
+        return hmult_checked(f.form, f.ks_hook, f.rs_hook, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, flags, stream,
+                             fused ? &step : nullptr);
     };
     // what must hold before the first verifying launch, so that a call outside the checked call's scope launches nothing: the
     // checked call itself then refuses (it returns the status and takes its hooks)
@@ -264,16 +274,25 @@ static int hmult_sealed_body(const RepairMode *rm, fhe_ctx *ctx, fhe_keyswitch *
     }
     int lay[8], rc;
     if ((rc = fhe_hmult_sealed_layout(p, rescale, lay))) return rc;
+    if (fused) {
+        // the sealed tensor product's hook is checked against the call before the key's sweep is launched
+        TensorSealHit hit;
+        if (tensor_seal_hit(ctx->tensor_seal_fault, (size_t)p->L, p->log_n, hit)) {
+            (void)checked(nullptr);      // takes the hooks, launches nothing
+            return fail(FHE_ERR_INVALID, "fault row or word outside the call");
+        }
+        for (int i = 0; i < 4; i++) step.flags_op[i] = d_flags + lay[i];
+    }
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = pick(ctx, stream);
     u64 *part;
-    if ((rc = sealed_scratch(ctx, p, &part))) return rc;
+    if ((rc = sealed_scratch(ctx, p, fused, &part))) return rc;
     HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)lay[5] * sizeof(u32), st));
     uint64_t *d_report = rm ? reinterpret_cast<uint64_t *>(d_flags + report_offset(lay[6])) : nullptr;
     if (rm) HIP_TRY(hipMemsetAsync(d_report, 0, (size_t)lay[5] * 4 * sizeof(u64), st));      // rows without a seal report CLEAN
     const size_t L = p->L;
     const uint64_t *ops[4] = {d_a0, d_a1, d_b0, d_b1};
-    for (int i = 0; i < 4; i++) {
+    for (int i = 0; i < 4 && !fused; i++) {
         const SealedRows r{ops[i], d_seal_in ? d_seal_in[i] : nullptr, rm && rm->loc_in ? rm->loc_in[i] : nullptr, 1, L, lay[i]};
         if ((rc = verify_rows(st, p->t, r, d_flags, d_report, part))) return rc;
     }
@@ -283,11 +302,19 @@ static int hmult_sealed_body(const RepairMode *rm, fhe_ctx *ctx, fhe_keyswitch *
     return seal_outputs(st, p->t, d_seal_out, rm ? rm->loc_out : nullptr, d_out0, d_out1, rescale ? L - 1 : L, part);
 }
 
+int fhe_hmult_sealed_fused(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_a0, const uint64_t *d_a1,
+                           const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a,
+                           const uint64_t *const *d_seal_in, const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
+{
+    return hmult_sealed_body(nullptr, true, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, d_seal_in, d_seal_key, d_seal_out,
+                             d_flags, stream);
+}
+
 int fhe_hmult_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_a0, const uint64_t *d_a1,
                      const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a,
                      const uint64_t *const *d_seal_in, const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
 {
-    return hmult_sealed_body(nullptr, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, d_seal_in, d_seal_key, d_seal_out, d_flags,
+    return hmult_sealed_body(nullptr, false, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, d_seal_in, d_seal_key, d_seal_out, d_flags,
                              stream);
 }
 
@@ -307,7 +334,7 @@ int fhe_hmult_sealed_repair(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, ui
                             uint64_t *const *d_seal_out, uint64_t *const *d_locator_out, uint32_t *d_flags, void *stream)
 {
     const RepairMode rm{d_locator_in, d_locator_key, d_locator_out};
-    return hmult_sealed_body(&rm, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, d_seal_in, d_seal_key, d_seal_out, d_flags,
+    return hmult_sealed_body(&rm, false, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, d_seal_in, d_seal_key, d_seal_out, d_flags,
                              stream);
 }
 
@@ -350,7 +377,7 @@ static int rotate_sealed_body(const RepairMode *rm, fhe_ctx *ctx, fhe_keyswitch 
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = pick(ctx, stream);
     u64 *part;
-    if ((rc = sealed_scratch(ctx, p, &part))) return rc;
+    if ((rc = sealed_scratch(ctx, p, false, &part))) return rc;
     HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)lay[3] * sizeof(u32), st));
     uint64_t *d_report = rm ? reinterpret_cast<uint64_t *>(d_flags + report_offset(lay[4])) : nullptr;
     if (rm) HIP_TRY(hipMemsetAsync(d_report, 0, (size_t)lay[3] * 4 * sizeof(u64), st));      // rows without a seal report CLEAN

@@ -395,4 +395,34 @@ size_t diag_seal_part_words(u32 limbs, int logn, u32 nb);
 struct DiagHit;
 hipError_t launch_diag_mac_sealed(hipStream_t st, const DiagMacArgs &a, u64 *part, const u64 *seal, u32 *seal_flags, const BcCheck &k, const DiagHit &hit);
 
+// ---- tensor_sealed.hip: the tensor product with its operands' seals verified on the multiplying load (tensor_seal.hpp) ----
+// launch_tensor_checked's words over rows [units] = [n_poly][limbs] (row u on table limb limb0 + u % limbs, at word u << logn of
+// every buffer), every buffer 16-byte aligned, logn >= 1.  seal_in[o] = [units][2] the stored seal of operand o (a0, a1, b0, b1) or
+// null: not compared; flags_op[o][u] |= SEAL_SUM where the row as loaded differs from it, SEAL_RANGE where a word is >= q_l (always
+// checked).  seal_out[i] = [units][2] receives the digest of d_i as stored, or null; all null: nothing is digested
+struct TensorSealArgs {
+    u64 *d0, *d1, *d2;
+    const u64 *a0, *a1, *b0, *b1;
+    const LimbParams *lp;
+    u32 limb0, limbs, units;
+    int logn;
+    const u64 *seal_in[4];
+    u64 *seal_out[3];
+    u32 *flags_op[4];
+};
+// the sealed call's test fault as a launch reads it: XOR mask into word coeff of row `row` of operand op, in the register as loaded
+// (mask == 0: not armed)
+struct TensorSealHit {
+    int op;
+    u32 row;
+    u64 coeff, mask;
+};
+// the launcher's cap on the workgroups of the job loop
+constexpr u32 TENSOR_SEAL_GRID_CAP = 8192;
+// words of the partial-sum scratch a launch needs: [units][chunks per row][8, or 14 with output seals]
+size_t tensor_seal_part_words(u32 units, int logn, bool out);
+// k.flags = [units][3] the residue flags of d0, d1, d2 (zeroed by the caller, as flags_op); k's fault: the d1 sum of word fault_coeff
+// of row fault_unit
+hipError_t launch_tensor_sealed(hipStream_t st, const TensorSealArgs &t, u64 *part, const BcCheck &k, const TensorSealHit &hit);
+
 } // namespace fhe

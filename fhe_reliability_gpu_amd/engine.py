@@ -59,6 +59,12 @@ class Engine:
         check(lib.fhe_ctx_trace_read(self._h, buf, n.value + 1, None))
         return buf.value.decode("utf-8")
 
+    def inject_fault_tensor_sealed(self, operand: int, row: int = 0, coeff: int = 0, bit: int = 0):
+        """One-shot test hook of ``KeySwitch.tensor_sealed`` / ``hmult_sealed_fused``: flip ``bit`` of word ``coeff`` of row ``row``
+        of operand 0..3 (a0, a1, b0, b1) in the register as the next such call loads it, before the window, the digest and the
+        product read it; memory stays clean.  A negative ``operand`` disarms."""
+        check(lib.fhe_ctx_inject_fault_tensor_sealed(self._h, operand, row, coeff, bit))
+
     def check(self):
         """Synchronise and raise if a fused-NTT launch reported a timed-out wait."""
         check(lib.fhe_ctx_check(self._h))
@@ -1081,14 +1087,60 @@ class KeySwitch:
         ``key_seal`` from ``seal_key``.  ``flags = {"a0", "a1", "b0", "b1": [L], "key": [dnum][2][M], "checked": <the flags of the
         checked multiply>}``, input words with the bits of ``seal_verify``.  A raised input flag does not stop the call; the checked
         block and the output seals are then meaningless.  The words are ``hmult``'s, bit for bit."""
+        return self._hmult_sealed(lib.fhe_hmult_sealed, a0, a1, b0, b1, relin_key, abft, seals, key_seal, rescale, stream)
+
+    def _hmult_sealed(self, call, a0, a1, b0, b1, relin_key, abft, seals, key_seal, rescale, stream):
         names = ("a0", "a1", "b0", "b1")
         lay = self.hmult_sealed_layout(rescale)
-        o0, o1, so, f = self._sealed(lay, names, self.L - 1 if rescale else self.L, seals, lambda o0, o1, sin, sout, fl: lib.fhe_hmult_sealed(
+        o0, o1, so, f = self._sealed(lay, names, self.L - 1 if rescale else self.L, seals, lambda o0, o1, sin, sout, fl: call(
             self.eng._h, self._h, o0.ptr, o1.ptr, a0.ptr, a1.ptr, b0.ptr, b1.ptr, relin_key.ptr, 1 if rescale else 0, abft._h, sin,
             key_seal.ptr if key_seal is not None else None, sout, fl.ptr, stream), stream)
         flags = self._split_flags(f, lay, names + ("key",))
         flags["checked"] = self._hmult_flags(bool(self.plain_modulus), f, rescale, lay["checked"])
         return o0, o1, so, flags
+
+    # ---- sealed tensor product: the operands verified on the load that multiplies them (tensor_sealed.hip) ----
+    def tensor_sealed_layout(self):
+        """``{"a0", "a1", "b0", "b1": (offset, (L,)), "tensor": (offset, (L, 3)), "total": n}`` of ``tensor_sealed``'s flag buffer."""
+        out = (C.c_int * 6)()
+        check(lib.fhe_tensor_product_sealed_layout(1, self.L, out))
+        lay = {name: (int(out[i]), (self.L,)) for i, name in enumerate(("a0", "a1", "b0", "b1"))}
+        lay["tensor"], lay["total"] = (int(out[4]), (self.L, 3)), int(out[5])
+        return lay
+
+    def tensor_sealed(self, a0: DeviceArray, a1: DeviceArray, b0: DeviceArray, b1: DeviceArray, seals=None, seal_out: bool = True, stream=None):
+        """``tensor_checked`` with the operands verified on the very load that multiplies them, and the results sealed from the
+        registers that are stored: ``(d0, d1, d2, (s0, s1, s2) or None, flags)``.  ``seals`` = the seals of (a0, a1, b0, b1) from
+        ``NttTables.seal`` (an entry, or all, may be None: not compared -- the window word < q_l is checked all the same);
+        ``seal_out = False``: no result is digested.  ``flags = {"a0", "a1", "b0", "b1": [L], "tensor": [L, 3]}``: operand words
+        with the bits of ``seal_verify``, the tensor block with those of ``tensor_checked``.  The words are ``tensor``'s, bit for
+        bit, also for an operand word that is not canonical: it is flagged, not fixed.
+
+        Covered: a change confined to one or two words of an operand row, at rest or on this call's own load, with certainty
+        (seal_check.hpp); no operand word is read twice.  A changed operand raises its row and not the tensor block: the residue
+        identity holds on the operand as loaded.  Not covered: a fault after the results' digest (the store, memory) -- whoever
+        verifies (s0, s1, s2) next sees it; an output may be an operand's buffer, and a may be b."""
+        names = ("a0", "a1", "b0", "b1")
+        lay = self.tensor_sealed_layout()
+        d = [self._out(self.L) for _ in range(3)]
+        so = [self.eng.alloc(2 * self.L) for _ in range(3)] if seal_out else None
+        for x in so or ():
+            x.shape = (self.L, 2)
+        seals = tuple(seals) if seals is not None else (None,) * 4
+        sin = (vp * 4)(*[x.ptr if x is not None else None for x in seals])
+        sout = (vp * 3)(*[x.ptr for x in so]) if seal_out else None
+        f = _checked_flags(self.eng, lay["total"], lambda fl: lib.fhe_tensor_product_sealed(
+            self.eng._h, d[0].ptr, d[1].ptr, d[2].ptr, a0.ptr, a1.ptr, b0.ptr, b1.ptr, self.t._h, 1, self.L, 0, sin, sout, fl.ptr, stream), stream)
+        return d[0], d[1], d[2], tuple(so) if seal_out else None, self._split_flags(f, lay, names + ("tensor",))
+
+    def hmult_sealed_fused(self, a0: DeviceArray, a1: DeviceArray, b0: DeviceArray, b1: DeviceArray, relin_key: DeviceArray, abft: "Abft",
+                           seals=None, key_seal: Optional[DeviceArray] = None, rescale: bool = True, stream=None):
+        """``hmult_sealed`` -- same arguments, same result structure, same words and flag layout -- without the four operand sweeps:
+        the multiply's tensor step is ``tensor_sealed``'s kernel, so a0, a1, b0, b1 are verified on the load that multiplies them
+        and a fault on that load raises the operand's row.  An operand without a seal is not compared, but its window is still
+        checked.  Not covered on the consuming load: the key (verified by its sweep, loaded again by the key switch) and the
+        plan's d0, d1, d2, which the key switch re-reads; no repairing form."""
+        return self._hmult_sealed(lib.fhe_hmult_sealed_fused, a0, a1, b0, b1, relin_key, abft, seals, key_seal, rescale, stream)
 
     def rotate_sealed(self, c0: DeviceArray, c1: DeviceArray, galois_elt: int, galois_key: DeviceArray, abft: "Abft", seals=None,
                       key_seal: Optional[DeviceArray] = None, stream=None):

@@ -26,7 +26,11 @@ bsgs_matvec_sealed (n1 = n2 = 4) with every operand sealed, and each trial flips
 (even trials) at rest.  Per trial the tool prints which flag groups were raised; a diagonal is caught by the inner sum itself, on
 the load that multiplies it.  Exit status as in the default mode.
 
-python -m fhe_reliability_gpu_amd.tools.flip_coverage [--repair | --rotate-sum | --bsgs] [--trials 32] [--num-symbols 1] [--bits-per-symbol 1] [--logn 14] [--row 8] [--seed 1]"""
+--fused runs the default chain (or, with --rotate-sum, that one) with hmult_sealed_fused in the place of hmult_sealed: the four operand
+sweeps are gone and the flipped operand is caught by the tensor step itself, on the load that multiplies it.  The fault-free words
+are held against the sweep-based chain's first.  Output and exit status as in the default mode.
+
+python -m fhe_reliability_gpu_amd.tools.flip_coverage [--repair | --rotate-sum | --bsgs | --fused] [--trials 32] [--num-symbols 1] [--bits-per-symbol 1] [--logn 14] [--row 8] [--seed 1]"""
 import argparse
 import sys
 
@@ -61,7 +65,10 @@ def main():
     ap.add_argument("--repair", action="store_true", help="run the chain through the repairing composites and report corrections")
     ap.add_argument("--rotate-sum", action="store_true", help="run the rotate-and-add rounds as one rotate_sum_sealed call")
     ap.add_argument("--bsgs", action="store_true", help="flip a diagonal or a giant key of a sealed BSGS matrix-vector product")
+    ap.add_argument("--fused", action="store_true", help="run the multiply as hmult_sealed_fused: operands verified on the multiplying load")
     a = ap.parse_args()
+    if a.fused and (a.repair or a.bsgs):
+        ap.error("--fused goes with the default chain or with --rotate-sum: the fused multiply has no repairing form")
     if a.repair and a.rotate_sum:
         ap.error("--repair and --rotate-sum exclude each other: the composite has no repairing form")
     if a.bsgs and (a.repair or a.rotate_sum):
@@ -99,10 +106,12 @@ def main():
     part = lambda d, i, limbs: _view(eng, d, i * limbs * N, limbs * N)
     seal_part = lambda s, i, limbs: _view(eng, s, i * limbs * 2, limbs * 2)
 
+    hmult = ks.hmult_sealed
+
     def chain(d_a):
         """the sealed chain on operand d_a (sealed as s_a); returns the final parts and the raised flag words"""
         raised = 0
-        o0, o1, so, fl = ks.hmult_sealed(part(d_a, 0, L), part(d_a, 1, L), part(d_b, 0, L), part(d_b, 1, L), d_rlk, ab,
+        o0, o1, so, fl = hmult(part(d_a, 0, L), part(d_a, 1, L), part(d_b, 0, L), part(d_b, 1, L), d_rlk, ab,
                                          seals=[seal_part(s_a, 0, L), seal_part(s_a, 1, L), seal_part(s_b, 0, L), seal_part(s_b, 1, L)], key_seal=s_rlk)
         raised += nonzero(fl)
         c, sc = [o0, o1], list(so)
@@ -117,7 +126,7 @@ def main():
 
     def chain_sum(d_a):
         """the same chain with its tail as one call: hmult_sealed, then rotate_sum_sealed on its outputs and their seals"""
-        o0, o1, so, fl = ks.hmult_sealed(part(d_a, 0, L), part(d_a, 1, L), part(d_b, 0, L), part(d_b, 1, L), d_rlk, ab,
+        o0, o1, so, fl = hmult(part(d_a, 0, L), part(d_a, 1, L), part(d_b, 0, L), part(d_b, 1, L), d_rlk, ab,
                                          seals=[seal_part(s_a, 0, L), seal_part(s_a, 1, L), seal_part(s_b, 0, L), seal_part(s_b, 1, L)], key_seal=s_rlk)
         raised = nonzero(fl)
         if elts:
@@ -158,6 +167,10 @@ def main():
 
     clean, raised = chain(eng.upload(ct_a))
     assert raised == 0, "the clean chain raised a flag"
+    if a.fused:
+        hmult = ks.hmult_sealed_fused
+        out, raised = chain(eng.upload(ct_a))
+        assert raised == 0 and (out == clean).all(), "the clean chain with the fused multiply differs from the sealed chain"
     if a.repair:
         return main_repair(a, eng, rng, ct_a, clean, chain_repair)
     if a.rotate_sum:
@@ -165,7 +178,7 @@ def main():
         assert raised == 0 and (out == clean).all(), "the clean rotate-and-sum chain differs from the sealed chain"
         chain = chain_sum
     print(f"N = 2^{a.logn}, L = {L}, K = {K}, dnum = {DNUM}, plain modulus {PLAIN_MODULUS}; {rounds} rotate-and-add rounds"
-          f"{' as one rotate_sum_sealed call' if a.rotate_sum else ''}; {a.num_symbols} symbols x {a.bits_per_symbol} bits per trial")
+          f"{' as one rotate_sum_sealed call' if a.rotate_sum else ''}{'; multiply: hmult_sealed_fused' if a.fused else ''}; {a.num_symbols} symbols x {a.bits_per_symbol} bits per trial")
     missed = 0
     for trial in range(a.trials):
         d_a = eng.upload(ct_a)

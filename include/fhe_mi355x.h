@@ -1072,6 +1072,52 @@ int fhe_bsgs_matvec_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uin
                            uint32_t *d_flags, void *stream);
 int fhe_ctx_inject_fault_bsgs_sealed(fhe_ctx *ctx, int g, int b, int limb, long long coeff, int bit);
 
+/* ---- sealed tensor product: operands verified on the load that multiplies them ----------------------------------------------
+ * fhe_hmult_sealed verifies a0, a1, b0, b1 in four sweeps and then multiplies from a second load of the same words: a word that is
+ * wrong on that second load only passes the seal, is a consistent operand of the residue identity, and gives a wrong product with
+ * no flag.  The tensor product reads each operand word exactly once, so here the seal is digested from the register that is handed
+ * to the product.
+ *
+ * fhe_tensor_product_sealed: fhe_tensor_product_checked over rows [n_poly][limbs] (row u on table limb start_idx + u % limbs) --
+ * same terms, order, arithmetic paths, residue flags and pointwise fault points -- in one kernel that digests every word of a0, a1,
+ * b0, b1 from the register as loaded, with the weight of its index in the row, and a finish launch that holds each row's two sums
+ * word for word against d_seal_in[0..3] ([rows][2], fhe_seal's).  d_seal_in is a HOST array of device pointers; a NULL entry, or a
+ * NULL array, is not compared -- the window word < q_l is always checked.  d_seal_out: a HOST array of three device pointers
+ * ([rows][2]) that receive the seals of d0, d1, d2, digested from the registers that are stored: a fault after the store is the next
+ * verification's to catch.  A NULL entry is skipped; a NULL array or three NULL entries: no result is digested.  The words are
+ * fhe_tensor_product's, bit for bit, also where an operand word is not canonical: such a word is flagged, not fixed.
+ * Flags, cleared by the call, with R = n_poly limbs: [a0: R][a1: R][b0: R][b1: R][tensor: R x 3]; operand words with the bits of
+ * fhe_seal_verify (1 the row as loaded is not the row that was sealed, or a stored sum is not canonical; 2 a word >= q_l), the
+ * tensor block with the bits of fhe_tensor_product_checked, word 3 u + part.  A changed operand word raises its row and NOT the
+ * tensor block: the residue identity holds on the operand as loaded.  fhe_tensor_product_sealed_layout gives the five offsets
+ * {0, R, 2R, 3R, 4R} in out[0..4] and the total 7R in out[5].
+ * Guarantees (seal_check.hpp): a change confined to one or two words of an operand row -- at rest, or on this call's own load --
+ * is caught with certainty; wider corruption escapes with probability about 2^-61 per sum on random data.
+ * An output may be exactly an operand's buffer, and a and b may be the same ciphertext.  FHE_ERR_INVALID with nothing launched
+ * for a NULL argument, a limb range outside the tables, or a data buffer that is not 16-byte aligned; FHE_ERR_UNSUPPORTED for
+ * log_n < 1.  The call takes the pointwise hook (fhe_ctx_inject_fault_pointwise: idx = row N + coefficient, on the d1 sum) and the
+ * hook below, one shot, whatever its outcome.
+ * Test hook: fhe_ctx_inject_fault_tensor_sealed(operand, row, coeff, bit), operand 0..3 = a0, a1, b0, b1, negative clears; taken by
+ * the next fhe_tensor_product_sealed or fhe_hmult_sealed_fused.  The bit of that operand word is flipped in the register as loaded,
+ * before window, digest and product read it; memory stays clean.  FHE_ERR_INVALID for operand > 3, a negative row or coeff, or a
+ * bit outside 0..63; a row or coeff outside the call that takes it makes that call return FHE_ERR_INVALID with nothing launched.
+ *
+ * fhe_hmult_sealed_fused: fhe_hmult_sealed (same arguments, same flag layout: fhe_hmult_sealed_layout, same words) with the four
+ * operand sweeps gone and the checked multiply's tensor step replaced by the kernel above, which writes the operands' row flags
+ * where the sweeps wrote them and the residue flags where fhe_tensor_product_checked writes them.  The key is still verified by a
+ * sweep; key switch, rescale and output seals are unchanged; CKKS or BGV form by the plan's plain modulus, with that form's hooks.
+ * A NULL operand seal is not compared, but the window of that operand is still checked (fhe_hmult_sealed skips such an operand).
+ * Not covered: the key rows, verified by a sweep and loaded again by the key switch; the plan's d0, d1, d2, which the key switch
+ * re-reads; no repairing form (repair needs the sweep); sharded plans. */
+int fhe_tensor_product_sealed_layout(size_t n_poly, size_t limbs, int out[6]);
+int fhe_tensor_product_sealed(fhe_ctx *ctx, uint64_t *d_d0, uint64_t *d_d1, uint64_t *d_d2, const uint64_t *d_a0, const uint64_t *d_a1,
+                              const uint64_t *d_b0, const uint64_t *d_b1, const fhe_ntt_tables *t, size_t n_poly, size_t limbs, size_t start_idx,
+                              const uint64_t *const *d_seal_in /* [4] */, uint64_t *const *d_seal_out /* [3] */, uint32_t *d_flags, void *stream);
+int fhe_ctx_inject_fault_tensor_sealed(fhe_ctx *ctx, int operand, int row, long long coeff, int bit);
+int fhe_hmult_sealed_fused(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_a0, const uint64_t *d_a1,
+                           const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a,
+                           const uint64_t *const *d_seal_in, const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream);
+
 /* ---- fault injection ---------------------------------------------------------------- */
 /* _flip_bit_kernel<<<1,1>>> (reliability_test/dotprod_test.cu:31-33,55): data[idx] ^= 1 << bit */
 int fhe_flip_bit(fhe_ctx *ctx, uint64_t *d_data, uint64_t idx, int bit, void *stream);
