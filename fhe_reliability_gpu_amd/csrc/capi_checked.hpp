@@ -99,11 +99,22 @@ KscNtt ksc_ntt(const fhe_keyswitch *p, const fhe_abft *a, hipStream_t st, bool i
 // a plan with a plain modulus (FHE_ERR_UNSUPPORTED), the BGV form one without (FHE_ERR_INVALID) or with more than 64 limbs per
 // scalar stage; mod_switch: the call drops a prime
 int ksc_scope(const fhe_ctx *ctx, const fhe_keyswitch *p, const fhe_abft *a, const uint32_t *d_flags, KsForm form, bool mod_switch);
+// key != nullptr (fhe_keyswitch_apply_sealed, fhe_rotate_sealed_fused, fhe_hmult_sealed_fused_key): stage 3 is the sealed inner
+// product (keyswitch_sealed.hip) instead of launch_ks_mac_checked -- same words, same residue flags at the same place -- which
+// verifies the key on the load that multiplies it; absent, every launch list is the checked call's own
+struct SealedKeyStep {
+    const uint64_t *seal_key;      // DEVICE [dnum 2 M][2] the stored seals of the key's rows, or null: not compared
+    uint32_t *flags_key;           // the key rows' flags, [dnum][2][M], zeroed by the caller
+    u64 *part;                     // ctx->seal_part, at least ks_sealed_scratch_words(p) long
+    KsSealHit hit;                 // the sealed call's hook, checked against the plan (ks_seal_hit)
+};
 int keyswitch_checked(fhe_keyswitch *p, KsForm form, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk,
-                      const uint64_t *d_add0, const uint64_t *d_add1, const fhe_abft *a, uint32_t *d_flags, hipStream_t st, const StagedFault &ft);
-// the whole rotation behind an entry point (fhe_rotate_checked, fhe_bgv_rotate_checked, fhe_rotate_sealed)
+                      const uint64_t *d_add0, const uint64_t *d_add1, const fhe_abft *a, uint32_t *d_flags, hipStream_t st, const StagedFault &ft,
+                      const SealedKeyStep *key = nullptr);
+// the whole rotation behind an entry point (fhe_rotate_checked, fhe_bgv_rotate_checked, fhe_rotate_sealed, fhe_rotate_sealed_fused)
 int rotate_checked(KsForm form, KsHookSlot hook, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0,
-                   const uint64_t *d_c1, uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, uint32_t *d_flags, void *stream);
+                   const uint64_t *d_c1, uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, uint32_t *d_flags, void *stream,
+                   const SealedKeyStep *key = nullptr);
 
 // ---- the checked key switch as two halves (keyswitch_checked = front + back; hoisted rotations: one front, a back per element)
 // where each stage's flag words go: s[0..7] the stages of the key switch, s[8] the Galois permutation of a hoisted rotation, s[9]
@@ -128,7 +139,20 @@ struct KscPerm {
 };
 int ksc_front(fhe_keyswitch *p, const uint64_t *d_c, const fhe_abft *a, const KscFlags &fl, hipStream_t st, const KscHook &h);
 int ksc_back(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk, const uint64_t *d_add0,
-             const uint64_t *d_add1, const fhe_abft *a, const KscFlags &fl, hipStream_t st, const KscHook &h, const KscPerm *perm, KsForm form);
+             const uint64_t *d_add1, const fhe_abft *a, const KscFlags &fl, hipStream_t st, const KscHook &h, const KscPerm *perm, KsForm form,
+             const SealedKeyStep *key = nullptr);
+
+// defined in capi_keyswitch_sealed.cpp
+// does the plan take the fused route (dnum <= KS_SEAL_MAX_DNUM), or the sweep followed by the checked inner product
+bool ks_sealed_fused(const fhe_keyswitch *p);
+// words of ctx->seal_part the sealed stage needs on either route
+size_t ks_sealed_scratch_words(const fhe_keyswitch *p);
+// the sealed key switch's hook as a call took it (ctx->ks_seal_fault), checked against the plan: the key row and the word exist,
+// and the plan takes the fused route (above the cap there is no fused load to hit)
+int ks_seal_hit(const fhe_ctx::KsSealFault &f, const fhe_keyswitch *p, KsSealHit &hit);
+// stage 3 of a key switch with a sealed key: the fused launch, or above the cap launch_seal_verify over the key's rows followed by
+// launch_ks_mac_checked; k = the residue check record of stage 3, its flags [2][M]
+int ks_mac_sealed_stage(const fhe_keyswitch *p, hipStream_t st, const KsMacArgs &ka, const BcCheck &k, const SealedKeyStep &key);
 
 // defined in capi_bgv_checked.cpp
 // one scalar stage: `limbs` rows from data on, of n_poly polynomials poly_stride rows apart (row l of polynomial i at data + (i
@@ -151,7 +175,8 @@ int rescale_checked(fhe_keyswitch *p, KsForm form, uint64_t *const *outs, const 
 // the multiply behind an entry point (fhe_hmult_checked, fhe_bgv_hmult_checked, fhe_hmult_sealed, fhe_hmult_sealed_fused) and its
 // layout.  sealed != nullptr (fhe_hmult_sealed_fused): the tensor step is the sealed one (tensor_sealed.hip) instead of
 // fhe_tensor_product_checked -- same words, same residue flags at the same place -- and the call takes the sealed tensor product's
-// hook as well; absent, the launch list is the checked multiply's own
+// hook as well; absent, the launch list is the checked multiply's own.  key != nullptr (fhe_hmult_sealed_fused_key): the key switch's
+// inner product is the sealed one (SealedKeyStep)
 struct SealedTensorStep {
     const uint64_t *const *seal_in;      // HOST array of the seals of a0, a1, b0, b1; an entry or the array may be null
     uint32_t *flags_op[4];               // the operands' row flags, [L] each, zeroed by the caller
@@ -159,7 +184,7 @@ struct SealedTensorStep {
 int hmult_checked_layout(const fhe_keyswitch *p, KsForm form, int rescale, int out[4]);
 int hmult_checked(KsForm form, KsHookSlot ks_hook, KsHookSlot rs_hook, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1,
                   const uint64_t *d_a0, const uint64_t *d_a1, const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale,
-                  const fhe_abft *a, uint32_t *d_flags, void *stream, const SealedTensorStep *sealed = nullptr);
+                  const fhe_abft *a, uint32_t *d_flags, void *stream, const SealedTensorStep *sealed = nullptr, const SealedKeyStep *key = nullptr);
 
 // defined in capi_tensor_sealed.cpp
 // the sealed tensor product's hook as a call of `units` rows took it (ctx->tensor_seal_fault), checked against that call

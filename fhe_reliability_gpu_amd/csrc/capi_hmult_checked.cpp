@@ -182,7 +182,7 @@ int hmult_validate(KsForm form, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0
 
 int hmult_checked(KsForm form, KsHookSlot ks_hook, KsHookSlot rs_hook, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1,
                   const uint64_t *d_a0, const uint64_t *d_a1, const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale,
-                  const fhe_abft *a, uint32_t *d_flags, void *stream, const SealedTensorStep *sealed)
+                  const fhe_abft *a, uint32_t *d_flags, void *stream, const SealedTensorStep *sealed, const SealedKeyStep *key)
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
     // the one-shot hooks of the steps this call runs belong to it whatever its outcome: the key switch's and (when it rescales) the
@@ -213,8 +213,8 @@ int hmult_checked(KsForm form, KsHookSlot ks_hook, KsHookSlot rs_hook, fhe_ctx *
         const uint64_t *const ops[4] = {d_a0, d_a1, d_b0, d_b1};
         if ((rc = tensor_sealed_run(ctx, st, d, ops, p->t, 1, L, 0, sealed->seal_in, nullptr, sealed->flags_op, k, hit))) return rc;
     } else if ((rc = fhe_tensor_product_checked(ctx, d0, d1, d2, d_a0, d_a1, d_b0, d_b1, p->t, L, 0, d_flags + lay[0], st))) return rc;
-    if (!rescale) return keyswitch_checked(p, form, d_out0, d_out1, d2, d_relin_key, d0, d1, a, d_flags + lay[1], st, kf);
-    if ((rc = keyswitch_checked(p, form, pre, pre + L * N, d2, d_relin_key, d0, d1, a, d_flags + lay[1], st, kf))) return rc;
+    if (!rescale) return keyswitch_checked(p, form, d_out0, d_out1, d2, d_relin_key, d0, d1, a, d_flags + lay[1], st, kf, key);
+    if ((rc = keyswitch_checked(p, form, pre, pre + L * N, d2, d_relin_key, d0, d1, a, d_flags + lay[1], st, kf, key))) return rc;
     uint64_t *outs[3] = {d_out0, d_out1, nullptr};
     return rescale_checked(p, form, outs, pre, 2, a, d_flags + lay[2], st, rf);
 }

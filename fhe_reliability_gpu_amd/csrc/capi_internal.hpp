@@ -142,6 +142,18 @@ struct fhe_ctx {
             return f;
         }
     } tensor_seal_fault;
+    // fhe_ctx_inject_fault_keyswitch_sealed: one bit of word coeff of key row key_row = (d 2 + h) M + j as the inner product of
+    // fhe_keyswitch_apply_sealed, fhe_rotate_sealed_fused or fhe_hmult_sealed_fused_key loads it; key_row < 0 = disarmed
+    struct KsSealFault {
+        int key_row = -1, bit = 0;
+        long long coeff = 0;
+        KsSealFault take()
+        {
+            const KsSealFault f = *this;
+            key_row = -1;
+            return f;
+        }
+    } ks_seal_fault;
     DevBuf seal_part;      // fhe_seal / fhe_seal_verify and the sealed composites: the chunks' partial sums, [rows][chunks][2] (the carried adds: [4] or [6], the sealed tensor product: [8] or [14]; grown on demand)
     DevBuf gal_sums;       // checked Galois permutation: the units' source-side and destination-side sums, [2][units] (grown on demand)
     int geo = 1;           // column-tile geometry of the two-launch path (ntt_launch.hpp)

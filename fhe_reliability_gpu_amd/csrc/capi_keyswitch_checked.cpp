@@ -173,7 +173,7 @@ int ksc_front(fhe_keyswitch *p, const uint64_t *d_c, const fhe_abft *a, const Ks
 // stages 5 and 6 (stage 10), so that the part the mod-down removes is t [acc t^-1]_P
 int ksc_back(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk, const uint64_t *d_add0,
              const uint64_t *d_add1, const fhe_abft *a, const KscFlags &fl, hipStream_t st, const KscHook &h, const KscPerm *perm,
-             KsForm form)
+             KsForm form, const SealedKeyStep *key)
 {
     const int L = p->L, K = p->K, M = L + K, logn = p->log_n;
     const size_t N = (size_t)1 << logn;
@@ -184,10 +184,12 @@ int ksc_back(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_
     const KscNtt fwd = ksc_ntt(p, a, st, false), inv = ksc_ntt(p, a, st, true);
     const bool bgv = form == KsForm::BGV;
 
-    // ---- 3: inner product with the key
+    // ---- 3: inner product with the key (key: its seal verified on these loads, capi_keyswitch_sealed.cpp)
     {
         const KsMacArgs ka{acc, p->ext.as<u64>(), d_c, d_evk, lp, (u32)L, (u32)M, (u32)p->dnum, (u32)p->alpha, logn, (u32)L, 0u, 0u};
-        if ((e = launch_ks_mac_checked(st, ka, bc_check(h.f.at(0, 3), fl.s[3]))) != hipSuccess) return hip_fail(e, "launch_ks_mac_checked");
+        if (key) {
+            if ((rc = ks_mac_sealed_stage(p, st, ka, bc_check(h.f.at(0, 3), fl.s[3]), *key))) return rc;
+        } else if ((e = launch_ks_mac_checked(st, ka, bc_check(h.f.at(0, 3), fl.s[3]))) != hipSuccess) return hip_fail(e, "launch_ks_mac_checked");
     }
 
     // ---- 8: sigma of the sums and of c0
@@ -227,7 +229,8 @@ int ksc_back(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_
 }
 
 int keyswitch_checked(fhe_keyswitch *p, KsForm form, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk,
-                      const uint64_t *d_add0, const uint64_t *d_add1, const fhe_abft *a, uint32_t *d_flags, hipStream_t st, const StagedFault &ft)
+                      const uint64_t *d_add0, const uint64_t *d_add1, const fhe_abft *a, uint32_t *d_flags, hipStream_t st, const StagedFault &ft,
+                      const SealedKeyStep *key)
 {
     int rc;
     if ((rc = ksc_prepare(p))) return rc;
@@ -239,7 +242,7 @@ int keyswitch_checked(fhe_keyswitch *p, KsForm form, uint64_t *d_out0, uint64_t 
         if (lay.units(s)) fl.s[s] = d_flags + lay.off[s];
     HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)lay.total * sizeof(u32), st));
     if ((rc = ksc_front(p, d_c, a, fl, st, h))) return rc;
-    return ksc_back(p, d_out0, d_out1, d_c, d_evk, d_add0, d_add1, a, fl, st, h, nullptr, form);
+    return ksc_back(p, d_out0, d_out1, d_c, d_evk, d_add0, d_add1, a, fl, st, h, nullptr, form, key);
 }
 
 int ksc_scope(const fhe_ctx *ctx, const fhe_keyswitch *p, const fhe_abft *a, const uint32_t *d_flags, KsForm form, bool mod_switch)
@@ -289,7 +292,8 @@ int apply_checked(KsForm form, KsHookSlot hook, fhe_ctx *ctx, fhe_keyswitch *p, 
 } // namespace
 
 int rotate_checked(KsForm form, KsHookSlot hook, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0,
-                   const uint64_t *d_c1, uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, uint32_t *d_flags, void *stream)
+                   const uint64_t *d_c1, uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, uint32_t *d_flags, void *stream,
+                   const SealedKeyStep *key)
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
     const StagedFault ft = (ctx->*hook).take();      // one shot, whatever the outcome
@@ -306,7 +310,7 @@ int rotate_checked(KsForm form, KsHookSlot hook, fhe_ctx *ctx, fhe_keyswitch *p,
     u64 *sig1 = p->rot.as<u64>(), *sig0 = sig1 + (size_t)p->L * N;
     hipError_t e = launch_automorphism_ntt(st, sig1, d_c1, (u32)p->L, p->log_n, galois_elt, sig0, d_c0);
     if (e != hipSuccess) return hip_fail(e, "launch_automorphism_ntt");
-    return keyswitch_checked(p, form, d_out0, d_out1, sig1, d_galois_key, sig0, nullptr, a, d_flags, st, ft);
+    return keyswitch_checked(p, form, d_out0, d_out1, sig1, d_galois_key, sig0, nullptr, a, d_flags, st, ft, key);
 }
 
 extern "C" {

@@ -246,17 +246,22 @@ int fhe_hmult_sealed_layout(const fhe_keyswitch *p, int rescale, int out[8])
 // fhe_hmult_sealed (rm == nullptr), fhe_hmult_sealed_repair and fhe_hmult_sealed_fused (fused, never with rm: repair needs the
 // sweep).  fused: the four operand sweeps are gone and the checked multiply's tensor step is the sealed tensor product
 // (capi_tensor_sealed.cpp), which verifies a0, a1, b0, b1 on the load that multiplies them and writes their row flags where the
-// sweeps wrote them; the key's sweep, the key switch, the rescale and the output seals are the same launches
-static int hmult_sealed_body(const RepairMode *rm, bool fused, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_a0,
+// sweeps wrote them; the key's sweep, the key switch, the rescale and the output seals are the same launches.  fused_key
+// (fhe_hmult_sealed_fused_key, with fused): the key's sweep is gone as well and the key switch's inner product is the sealed one
+// (capi_keyswitch_sealed.cpp), which verifies the key on the load that multiplies it and writes the key rows' flags where the
+// sweep wrote them; the call takes that step's hook
+static int hmult_sealed_body(const RepairMode *rm, bool fused, bool fused_key, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_a0,
                              const uint64_t *d_a1, const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a,
                              const uint64_t *const *d_seal_in, const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
     const SealedForm f = sealed_form(p);
     SealedTensorStep step{d_seal_in, {nullptr, nullptr, nullptr, nullptr}};
+    SealedKeyStep kstep{d_seal_key, nullptr, nullptr, KsSealHit{0, 0, 0}};
+    const fhe_ctx::KsSealFault kf = fused_key ? ctx->ks_seal_fault.take() : fhe_ctx::KsSealFault{};      // one shot, whatever the outcome
     auto checked = [&](uint32_t *flags) {
         return hmult_checked(f.form, f.ks_hook, f.rs_hook, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, flags, stream,
-                             fused ? &step : nullptr);
+                             fused ? &step : nullptr, fused_key ? &kstep : nullptr);
     };
     // what must hold before the first verifying launch, so that a call outside the checked call's scope launches nothing: the
     // checked call itself then refuses (it returns the status and takes its hooks)
@@ -283,10 +288,16 @@ static int hmult_sealed_body(const RepairMode *rm, bool fused, fhe_ctx *ctx, fhe
         }
         for (int i = 0; i < 4; i++) step.flags_op[i] = d_flags + lay[i];
     }
+    if (fused_key && ks_seal_hit(kf, p, kstep.hit)) {
+        (void)checked(nullptr);      // takes the hooks, launches nothing
+        return fail(FHE_ERR_INVALID, "fault key row or word outside the call");
+    }
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = pick(ctx, stream);
     u64 *part;
     if ((rc = sealed_scratch(ctx, p, fused, &part))) return rc;
+    kstep.flags_key = d_flags + lay[4];
+    kstep.part = part;
     HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)lay[5] * sizeof(u32), st));
     uint64_t *d_report = rm ? reinterpret_cast<uint64_t *>(d_flags + report_offset(lay[6])) : nullptr;
     if (rm) HIP_TRY(hipMemsetAsync(d_report, 0, (size_t)lay[5] * 4 * sizeof(u64), st));      // rows without a seal report CLEAN
@@ -297,7 +308,7 @@ static int hmult_sealed_body(const RepairMode *rm, bool fused, fhe_ctx *ctx, fhe
         if ((rc = verify_rows(st, p->t, r, d_flags, d_report, part))) return rc;
     }
     const SealedRows key{d_relin_key, d_seal_key, rm ? rm->loc_key : nullptr, (size_t)p->dnum * 2, L + p->K, lay[4]};
-    if ((rc = verify_rows(st, p->t, key, d_flags, d_report, part))) return rc;
+    if (!fused_key && (rc = verify_rows(st, p->t, key, d_flags, d_report, part))) return rc;
     if ((rc = checked(d_flags + lay[5]))) return rc;
     return seal_outputs(st, p->t, d_seal_out, rm ? rm->loc_out : nullptr, d_out0, d_out1, rescale ? L - 1 : L, part);
 }
@@ -306,7 +317,15 @@ int fhe_hmult_sealed_fused(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uin
                            const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a,
                            const uint64_t *const *d_seal_in, const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
 {
-    return hmult_sealed_body(nullptr, true, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, d_seal_in, d_seal_key, d_seal_out,
+    return hmult_sealed_body(nullptr, true, false, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, d_seal_in, d_seal_key, d_seal_out,
+                             d_flags, stream);
+}
+
+int fhe_hmult_sealed_fused_key(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_a0, const uint64_t *d_a1,
+                               const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a,
+                               const uint64_t *const *d_seal_in, const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
+{
+    return hmult_sealed_body(nullptr, true, true, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, d_seal_in, d_seal_key, d_seal_out,
                              d_flags, stream);
 }
 
@@ -314,7 +333,7 @@ int fhe_hmult_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t 
                      const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a,
                      const uint64_t *const *d_seal_in, const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
 {
-    return hmult_sealed_body(nullptr, false, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, d_seal_in, d_seal_key, d_seal_out, d_flags,
+    return hmult_sealed_body(nullptr, false, false, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, d_seal_in, d_seal_key, d_seal_out, d_flags,
                              stream);
 }
 
@@ -334,7 +353,7 @@ int fhe_hmult_sealed_repair(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, ui
                             uint64_t *const *d_seal_out, uint64_t *const *d_locator_out, uint32_t *d_flags, void *stream)
 {
     const RepairMode rm{d_locator_in, d_locator_key, d_locator_out};
-    return hmult_sealed_body(&rm, false, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, d_seal_in, d_seal_key, d_seal_out, d_flags,
+    return hmult_sealed_body(&rm, false, false, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, d_seal_in, d_seal_key, d_seal_out, d_flags,
                              stream);
 }
 
@@ -350,15 +369,19 @@ int fhe_rotate_sealed_layout(const fhe_keyswitch *p, int out[6])
     return FHE_OK;
 }
 
-// fhe_rotate_sealed (rm == nullptr) and fhe_rotate_sealed_repair
-static int rotate_sealed_body(const RepairMode *rm, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0,
+// fhe_rotate_sealed (rm == nullptr), fhe_rotate_sealed_repair and fhe_rotate_sealed_fused (fused_key, never with rm: repair needs
+// the sweep).  fused_key: the sweeps over c0 and c1 stay, the key's sweep is gone and the key switch's inner product is the sealed
+// one (capi_keyswitch_sealed.cpp), which writes the key rows' flags where the sweep wrote them; the call takes that step's hook
+static int rotate_sealed_body(const RepairMode *rm, bool fused_key, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0,
                               const uint64_t *d_c1, uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, const uint64_t *const *d_seal_in,
                               const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
     const SealedForm f = sealed_form(p);
+    SealedKeyStep kstep{d_seal_key, nullptr, nullptr, KsSealHit{0, 0, 0}};
+    const fhe_ctx::KsSealFault kf = fused_key ? ctx->ks_seal_fault.take() : fhe_ctx::KsSealFault{};      // one shot, whatever the outcome
     auto checked = [&](uint32_t *flags) {
-        return rotate_checked(f.form, f.ks_hook, ctx, p, d_out0, d_out1, d_c0, d_c1, galois_elt, d_galois_key, a, flags, stream);
+        return rotate_checked(f.form, f.ks_hook, ctx, p, d_out0, d_out1, d_c0, d_c1, galois_elt, d_galois_key, a, flags, stream, fused_key ? &kstep : nullptr);
     };
     if (ksc_scope(ctx, p, a, d_flags, f.form, false) || !d_out0 || !d_out1 || d_out0 == d_out1 || !d_c0 || !d_c1 || !d_galois_key || !(galois_elt & 1)) {
         const int rc = checked(d_flags);      // refuses before its first launch
@@ -374,10 +397,16 @@ static int rotate_sealed_body(const RepairMode *rm, fhe_ctx *ctx, fhe_keyswitch 
     }
     int lay[6], rc;
     if ((rc = fhe_rotate_sealed_layout(p, lay))) return rc;
+    if (fused_key && ks_seal_hit(kf, p, kstep.hit)) {
+        (void)checked(nullptr);      // takes the hook, launches nothing
+        return fail(FHE_ERR_INVALID, "fault key row or word outside the call");
+    }
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = pick(ctx, stream);
     u64 *part;
     if ((rc = sealed_scratch(ctx, p, false, &part))) return rc;
+    kstep.flags_key = d_flags + lay[2];
+    kstep.part = part;
     HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)lay[3] * sizeof(u32), st));
     uint64_t *d_report = rm ? reinterpret_cast<uint64_t *>(d_flags + report_offset(lay[4])) : nullptr;
     if (rm) HIP_TRY(hipMemsetAsync(d_report, 0, (size_t)lay[3] * 4 * sizeof(u64), st));      // rows without a seal report CLEAN
@@ -388,7 +417,7 @@ static int rotate_sealed_body(const RepairMode *rm, fhe_ctx *ctx, fhe_keyswitch 
         if ((rc = verify_rows(st, p->t, r, d_flags, d_report, part))) return rc;
     }
     const SealedRows key{d_galois_key, d_seal_key, rm ? rm->loc_key : nullptr, (size_t)p->dnum * 2, L + p->K, lay[2]};
-    if ((rc = verify_rows(st, p->t, key, d_flags, d_report, part))) return rc;
+    if (!fused_key && (rc = verify_rows(st, p->t, key, d_flags, d_report, part))) return rc;
     if ((rc = checked(d_flags + lay[3]))) return rc;
     return seal_outputs(st, p->t, d_seal_out, rm ? rm->loc_out : nullptr, d_out0, d_out1, L, part);
 }
@@ -397,7 +426,14 @@ int fhe_rotate_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t
                       uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, const uint64_t *const *d_seal_in,
                       const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
 {
-    return rotate_sealed_body(nullptr, ctx, p, d_out0, d_out1, d_c0, d_c1, galois_elt, d_galois_key, a, d_seal_in, d_seal_key, d_seal_out, d_flags, stream);
+    return rotate_sealed_body(nullptr, false, ctx, p, d_out0, d_out1, d_c0, d_c1, galois_elt, d_galois_key, a, d_seal_in, d_seal_key, d_seal_out, d_flags, stream);
+}
+
+int fhe_rotate_sealed_fused(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0, const uint64_t *d_c1,
+                            uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, const uint64_t *const *d_seal_in,
+                            const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
+{
+    return rotate_sealed_body(nullptr, true, ctx, p, d_out0, d_out1, d_c0, d_c1, galois_elt, d_galois_key, a, d_seal_in, d_seal_key, d_seal_out, d_flags, stream);
 }
 
 int fhe_rotate_sealed_repair_layout(const fhe_keyswitch *p, int out[8])
@@ -416,7 +452,7 @@ int fhe_rotate_sealed_repair(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, u
                              uint32_t *d_flags, void *stream)
 {
     const RepairMode rm{d_locator_in, d_locator_key, d_locator_out};
-    return rotate_sealed_body(&rm, ctx, p, d_out0, d_out1, d_c0, d_c1, galois_elt, d_galois_key, a, d_seal_in, d_seal_key, d_seal_out, d_flags, stream);
+    return rotate_sealed_body(&rm, false, ctx, p, d_out0, d_out1, d_c0, d_c1, galois_elt, d_galois_key, a, d_seal_in, d_seal_key, d_seal_out, d_flags, stream);
 }
 
 } // extern "C"

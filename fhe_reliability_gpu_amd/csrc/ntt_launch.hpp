@@ -425,4 +425,20 @@ size_t tensor_seal_part_words(u32 units, int logn, bool out);
 // of row fault_unit
 hipError_t launch_tensor_sealed(hipStream_t st, const TensorSealArgs &t, u64 *part, const BcCheck &k, const TensorSealHit &hit);
 
+// ---- keyswitch_sealed.hip: the key switch's inner product with the key's seal verified on the multiplying load (ks_seal.hpp) ----
+// the sealed call's test fault as a launch reads it: XOR mask into word coeff of key row key_row = (d 2 + h) M + j, in the register
+// as loaded (mask == 0: not armed)
+struct KsSealHit {
+    u32 key_row;
+    u64 coeff, mask;
+};
+// the compile-time bound on the digits the launch picks for dnum <= KS_SEAL_MAX_DNUM: the smallest of 2, 4, 8, 12 that holds dnum
+u32 ks_seal_nd(u32 dnum);
+// words of the partial-sum scratch a launch needs: [M][chunks per row][2 dnum][2] -- what a sweep over the key's rows needs
+size_t ks_seal_part_words(u32 M, int logn, u32 dnum);
+// launch_ks_mac_checked's words and flags (k) with a.c, a.ext, a.evk and a.acc 16-byte aligned, logn >= 1 and dnum <=
+// KS_SEAL_MAX_DNUM; seal_key = [dnum 2 M][2] the stored seals of the key's rows or null: not compared; flags_key[(d 2 + h) M + j] |=
+// SEAL_SUM where the row as loaded differs from its seal, SEAL_RANGE where a word is >= q_j (always checked); zeroed by the caller
+hipError_t launch_ks_mac_sealed(hipStream_t st, const KsMacArgs &a, u64 *part, const u64 *seal_key, u32 *flags_key, const BcCheck &k, const KsSealHit &hit);
+
 } // namespace fhe

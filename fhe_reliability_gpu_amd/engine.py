@@ -65,6 +65,12 @@ class Engine:
         product read it; memory stays clean.  A negative ``operand`` disarms."""
         check(lib.fhe_ctx_inject_fault_tensor_sealed(self._h, operand, row, coeff, bit))
 
+    def inject_fault_keyswitch_sealed(self, key_row: int, coeff: int = 0, bit: int = 0):
+        """One-shot test hook of ``KeySwitch.apply_sealed`` / ``rotate_sealed_fused`` / ``hmult_sealed_fused_key``: flip ``bit`` of
+        word ``coeff`` of key row ``key_row = (d * 2 + h) * M + j`` in the register as the next such call's inner product loads it,
+        before the window, the digest and the product read it; memory stays clean.  A negative ``key_row`` disarms."""
+        check(lib.fhe_ctx_inject_fault_keyswitch_sealed(self._h, key_row, coeff, bit))
+
     def check(self):
         """Synchronise and raise if a fused-NTT launch reported a timed-out wait."""
         check(lib.fhe_ctx_check(self._h))
@@ -1147,15 +1153,62 @@ class KeySwitch:
         """``rotate_checked`` (``bgv_rotate_checked`` on a plan with a plain modulus) with the operands protected at rest:
         ``(out0, out1, (seal0, seal1), flags)`` as ``hmult_sealed``; ``seals`` = the seals of (c0, c1), ``flags = {"c0", "c1": [L],
         "key": [dnum][2][M], "checked": {the stage names of checked_layout / bgv_checked_layout}}``."""
+        return self._rotate_sealed(lib.fhe_rotate_sealed, c0, c1, galois_elt, galois_key, abft, seals, key_seal, stream)
+
+    def _rotate_sealed(self, call, c0, c1, galois_elt, galois_key, abft, seals, key_seal, stream):
         names = ("c0", "c1")
         lay = self.rotate_sealed_layout()
-        o0, o1, so, f = self._sealed(lay, names, self.L, seals, lambda o0, o1, sin, sout, fl: lib.fhe_rotate_sealed(
+        o0, o1, so, f = self._sealed(lay, names, self.L, seals, lambda o0, o1, sin, sout, fl: call(
             self.eng._h, self._h, o0.ptr, o1.ptr, c0.ptr, c1.ptr, galois_elt, galois_key.ptr, abft._h, sin,
             key_seal.ptr if key_seal is not None else None, sout, fl.ptr, stream), stream)
         flags = self._split_flags(f, lay, names + ("key",))
         kl = self._ks_layout(bool(self.plain_modulus))
         flags["checked"] = self._split_flags(f, kl, base=lay["checked"])
         return o0, o1, so, flags
+
+    # ---- sealed key-switch inner product: the key verified on the load that multiplies it (keyswitch_sealed.hip) ----
+    def apply_sealed_layout(self):
+        """``{"key": (offset, (dnum, 2, M)), "checked": offset, "total": n, "fused": bool}`` of ``apply_sealed``'s flag buffer; the
+        checked block is laid out as ``checked_layout`` (``bgv_checked_layout`` with a plain modulus).  ``fused``: the plan's
+        ``dnum`` has a fused instantiation (at most 12 digits); otherwise the key is swept before the checked inner product."""
+        out = (C.c_int * 4)()
+        check(lib.fhe_keyswitch_sealed_layout(self._h, out))
+        return {"key": (int(out[0]), (self.dnum, 2, self.L + self.K)), "checked": int(out[1]), "total": int(out[2]), "fused": bool(out[3])}
+
+    def apply_sealed(self, c: DeviceArray, evk: DeviceArray, abft: "Abft", key_seal: Optional[DeviceArray] = None,
+                     add0: Optional[DeviceArray] = None, add1: Optional[DeviceArray] = None, stream=None):
+        """``apply_checked`` (``bgv_apply_checked`` on a plan with a plain modulus) with the key verified on the very load that
+        multiplies it: ``(out0, out1, flags)``, ``flags = {"key": [dnum][2][M], "checked": {the stage names of checked_layout /
+        bgv_checked_layout}}``, key words with the bits of ``seal_verify``.  ``key_seal`` from ``seal_key`` (None: not compared --
+        the window word < q_j is checked all the same).  The words are ``apply``'s, bit for bit, also for a key word that is not
+        canonical: it is flagged, not fixed.
+
+        Covered: a change confined to one or two words of a key row, at rest or on the inner product's own load, with certainty
+        (seal_check.hpp); no key word is read twice.  A changed key word raises its row and not ``checked["mac"]``: the residue
+        identity holds on the key as loaded.  Not covered on the consuming load: ``c`` (its loads are inside transform kernels)
+        and the plan's digits, which the inner product also loads."""
+        lay = self.apply_sealed_layout()
+        o0, o1 = self._out(self.L), self._out(self.L)
+        f = _checked_flags(self.eng, lay["total"], lambda fl: lib.fhe_keyswitch_apply_sealed(
+            self.eng._h, self._h, o0.ptr, o1.ptr, c.ptr, evk.ptr, add0.ptr if add0 is not None else None, add1.ptr if add1 is not None else None,
+            abft._h, key_seal.ptr if key_seal is not None else None, fl.ptr, stream), stream)
+        flags = self._split_flags(f, lay, ("key",))
+        flags["checked"] = self._split_flags(f, self._ks_layout(bool(self.plain_modulus)), base=lay["checked"])
+        return o0, o1, flags
+
+    def rotate_sealed_fused(self, c0: DeviceArray, c1: DeviceArray, galois_elt: int, galois_key: DeviceArray, abft: "Abft", seals=None,
+                            key_seal: Optional[DeviceArray] = None, stream=None):
+        """``rotate_sealed`` -- same arguments, same result structure, same words and flag layout -- without the key's sweep: the key
+        switch's inner product is ``apply_sealed``'s kernel, so the Galois key is verified on the load that multiplies it and a
+        fault on that load raises the key's row.  The sweeps over c0 and c1 stay.  No repairing form."""
+        return self._rotate_sealed(lib.fhe_rotate_sealed_fused, c0, c1, galois_elt, galois_key, abft, seals, key_seal, stream)
+
+    def hmult_sealed_fused_key(self, a0: DeviceArray, a1: DeviceArray, b0: DeviceArray, b1: DeviceArray, relin_key: DeviceArray, abft: "Abft",
+                               seals=None, key_seal: Optional[DeviceArray] = None, rescale: bool = True, stream=None):
+        """``hmult_sealed_fused`` -- same arguments, same result structure, same words and flag layout -- with the relinearisation
+        key fused as well: no input is swept at all.  Not covered on the consuming load: the plan's d0, d1, d2 and digits, which
+        the key switch re-reads; no repairing form."""
+        return self._hmult_sealed(lib.fhe_hmult_sealed_fused_key, a0, a1, b0, b1, relin_key, abft, seals, key_seal, rescale, stream)
 
     def rotate_sum_sealed_layout(self, n_steps: int):
         """``{"stride": words per step, "add": offset of the add rows inside a step's block, "total": n, "rotate": the layout of

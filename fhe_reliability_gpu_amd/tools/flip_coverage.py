@@ -30,7 +30,12 @@ the load that multiplies it.  Exit status as in the default mode.
 sweeps are gone and the flipped operand is caught by the tensor step itself, on the load that multiplies it.  The fault-free words
 are held against the sweep-based chain's first.  Output and exit status as in the default mode.
 
-python -m fhe_reliability_gpu_amd.tools.flip_coverage [--repair | --rotate-sum | --bsgs | --fused] [--trials 32] [--num-symbols 1] [--bits-per-symbol 1] [--logn 14] [--row 8] [--seed 1]"""
+--fused-key applies the same fault model to the relinearisation key at rest, the largest and longest-lived operand of the multiply,
+and runs hmult_sealed_fused_key: no input is swept at all, and the flipped key word is caught by the key switch's inner product
+itself, on the load that multiplies it.  The fault-free words and flags are held against hmult_sealed's first.  Per trial the tool
+prints which key rows were raised.  Exit status as in the default mode.
+
+python -m fhe_reliability_gpu_amd.tools.flip_coverage [--repair | --rotate-sum | --bsgs | --fused | --fused-key] [--trials 32] [--num-symbols 1] [--bits-per-symbol 1] [--logn 14] [--row 8] [--seed 1]"""
 import argparse
 import sys
 
@@ -66,7 +71,10 @@ def main():
     ap.add_argument("--rotate-sum", action="store_true", help="run the rotate-and-add rounds as one rotate_sum_sealed call")
     ap.add_argument("--bsgs", action="store_true", help="flip a diagonal or a giant key of a sealed BSGS matrix-vector product")
     ap.add_argument("--fused", action="store_true", help="run the multiply as hmult_sealed_fused: operands verified on the multiplying load")
+    ap.add_argument("--fused-key", action="store_true", help="flip the relinearisation key at rest and run hmult_sealed_fused_key")
     a = ap.parse_args()
+    if a.fused_key and (a.repair or a.bsgs or a.rotate_sum or a.fused):
+        ap.error("--fused-key is a mode of its own")
     if a.fused and (a.repair or a.bsgs):
         ap.error("--fused goes with the default chain or with --rotate-sum: the fused multiply has no repairing form")
     if a.repair and a.rotate_sum:
@@ -78,6 +86,8 @@ def main():
     eng = F.Engine(0)
     if a.bsgs:
         return main_bsgs(a, eng)
+    if a.fused_key:
+        return main_fused_key(a, eng)
     N, R = 1 << a.logn, L - 1
     qs = F.create_moduli(N, [50] * (L + K))
     rng = np.random.default_rng(a.seed)
@@ -230,6 +240,55 @@ def main_repair(a, eng, rng, ct_a, clean, chain_repair):
     print(f"summary: {a.trials} trials (one control): {totals['corrected']} corrected, {totals['uncorrectable']} uncorrectable, {totals['missed']} missed; "
           f"{totals['exact']} final results equal the fault-free run bit for bit; {wrong} reported corrected with a differing result")
     return 1 if missed or wrong else 0
+
+
+def main_fused_key(a, eng):
+    """the reference's fault model on the relinearisation key at rest, through hmult_sealed_fused_key"""
+    N, M = 1 << a.logn, L + K
+    qs = F.create_moduli(N, [50] * M)
+    rng = np.random.default_rng(a.seed)
+    t = eng.tables(a.logn, qs)
+    ks, ab = F.KeySwitch(eng, t, L, K, DNUM), F.Abft(eng, t)
+    ks.set_plain_modulus(PLAIN_MODULUS)
+    assert ks.apply_sealed_layout()["fused"]
+    poly = lambda moduli: np.stack([rng.integers(0, q, N, dtype=np.uint64) for q in moduli])
+    ops = [eng.upload(poly(qs[:L])) for _ in range(4)]
+    rlk = np.stack([np.stack([poly(qs) for _ in range(2)]) for _ in range(DNUM)])
+    seals = [t.seal(d, limbs=L) for d in ops]
+    s_rlk = ks.seal_key(eng.upload(rlk))
+
+    def run(call, d_rlk):
+        o0, o1, so, fl = call(*ops, d_rlk, ab, seals=seals, key_seal=s_rlk)
+        return np.concatenate([o0.download().reshape(-1), o1.download().reshape(-1)]), fl
+
+    clean, fl = run(ks.hmult_sealed_fused_key, eng.upload(rlk))
+    ref, rfl = run(ks.hmult_sealed, eng.upload(rlk))
+    assert nonzero(fl) == 0 and nonzero(rfl) == 0 and (clean == ref).all(), "the clean fused multiply differs from the sealed multiply"
+    print(f"N = 2^{a.logn}, L = {L}, K = {K}, dnum = {DNUM}, plain modulus {PLAIN_MODULUS}; multiply: hmult_sealed_fused_key, flips in the relinearisation key "
+          f"at rest; {a.num_symbols} symbols x {a.bits_per_symbol} bits per trial")
+    missed = 0
+    for trial in range(a.trials):
+        d_rlk = eng.upload(rlk)
+        n_sym = 0 if trial == 0 else a.num_symbols
+        hit = set()
+        for idx in rng.integers(0, rlk.size, n_sym):
+            hit.add(int(idx) // N)
+            for bit in rng.choice(64, a.bits_per_symbol, replace=False):
+                check(lib.fhe_flip_bit(eng._h, d_rlk.ptr, int(idx), int(bit), None))
+        flipped = int(np.count_nonzero(d_rlk.download().reshape(-1) != rlk.reshape(-1)))
+        out, fl = run(ks.hmult_sealed_fused_key, d_rlk)
+        corrupted = int(np.count_nonzero(out != clean))
+        rows = np.flatnonzero(np.asarray(fl["key"]).reshape(-1)).tolist()
+        raised = nonzero(fl)
+        detected = raised > 0
+        missed += flipped > 0 and not detected
+        assert flipped > 0 or (corrupted == 0 and not detected), "the control trial differs from the clean run"
+        assert rows == sorted(hit) or flipped == 0, "the raised key rows are not the rows that were flipped"
+        print(f"trial {trial:3d}: flipped words {flipped:3d}, corrupted output words {corrupted:7d} of {out.size}, raised flag words {raised:4d}, key rows raised "
+              f"{rows}, detected {'yes' if detected else 'no'}", flush=True)
+    eng.check()
+    print(f"summary: {a.trials} trials, {missed} with a flip and no flag")
+    return 1 if missed else 0
 
 
 def main_bsgs(a, eng):

@@ -1118,6 +1118,52 @@ int fhe_hmult_sealed_fused(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uin
                            const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a,
                            const uint64_t *const *d_seal_in, const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream);
 
+/* ---- sealed key-switch inner product: the switching key verified on the load that multiplies it -----------------------------
+ * The sealed composites verify the key's rows in a sweep of their own and the checked key switch then loads the key a second time
+ * for its inner product (stage 3): a key word that is wrong on that second load only passes the seal, is a consistent operand of
+ * the residue identity, and pollutes both halves of the result with no flag.  The inner product reads each key word exactly once,
+ * so here the seal is digested from the register that is handed to the product, one digest per (digit, half) of the row, and a
+ * finish launch holds each key row's two sums word for word against d_seal_key ([dnum 2 M][2], fhe_seal's over the key as
+ * [dnum 2][M] rows, M = L + K).  Same terms, order, arithmetic paths, residue flags and fault points as the checked stage 3.
+ *
+ * fhe_keyswitch_apply_sealed: fhe_keyswitch_apply_checked with stage 3 replaced by that kernel; CKKS or BGV form by the plan's
+ * plain modulus, with that form's hook.  Flags, cleared by the call: [key rows: dnum 2 M, word (d 2 + h) M + j][the checked key
+ * switch's own block, exactly its layout]; key words with the bits of fhe_seal_verify (1 the row as loaded is not the row that was
+ * sealed, or a stored sum is not canonical; 2 a word >= q_j).  A NULL d_seal_key is not compared, but the window is still checked.
+ * A changed key word raises its row and NOT the stage-3 residue flags: the identity holds on the key as loaded; the words are then
+ * the product with the key as loaded (a word >= q_j is flagged, not fixed).  The words are fhe_keyswitch_apply's, bit for bit.
+ * d_c is not sealed here: its consuming loads are inside the transform kernels of stage 0.
+ * fhe_keyswitch_sealed_layout: out = {0, offset of the checked block = dnum 2 M, total, 1 if the plan takes the fused route}.
+ * The fused kernel exists for dnum <= 12; above, stage 3 is the verifying sweep over the key's rows followed by the checked inner
+ * product, writing the same flag words (a NULL d_seal_key is then not swept at all).
+ * FHE_ERR_INVALID / FHE_ERR_UNSUPPORTED with nothing launched and the flag buffer untouched: outside fhe_keyswitch_apply_checked's
+ * scope, a NULL argument, d_out0 == d_out1, a buffer that is not 16-byte aligned, a hook outside the call.  No repairing form:
+ * repair needs the sweep.
+ *
+ * fhe_rotate_sealed_fused: fhe_rotate_sealed (same arguments, flag layout fhe_rotate_sealed_layout, same words) with the key's sweep
+ * gone and stage 3 as above, which writes the key rows' flags where the sweep wrote them; the sweeps over c0 and c1 stay.
+ * fhe_hmult_sealed_fused_key: fhe_hmult_sealed_fused (same arguments, flag layout fhe_hmult_sealed_layout, same words) with the key
+ * fused as well: no input is swept at all.
+ * Not covered on the consuming load: the plan's digits (ext) and the input limbs, which the inner product also loads; the prepared
+ * keys of hoisted rotations and the giant keys of the BSGS product; sharded plans.
+ * Test hook: fhe_ctx_inject_fault_keyswitch_sealed(key_row, coeff, bit), key_row = (d 2 + h) M + j, negative clears; taken, one
+ * shot and whatever the outcome, by the next of the three calls above.  The bit of that key word is flipped in the register as
+ * loaded, before window, digest and product read it; memory stays clean.  A key row or coeff outside the call that takes it, or a
+ * plan above the fused cap (there is no fused load to hit), makes that call return FHE_ERR_INVALID with nothing launched.  The
+ * sweep-based calls do not take the hook. */
+int fhe_keyswitch_sealed_layout(const fhe_keyswitch *p, int out[4]);
+int fhe_keyswitch_apply_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk,
+                               const uint64_t *d_add0, const uint64_t *d_add1, const fhe_abft *a, const uint64_t *d_seal_key, uint32_t *d_flags,
+                               void *stream);
+int fhe_rotate_sealed_fused(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0, const uint64_t *d_c1,
+                            uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, const uint64_t *const *d_seal_in,
+                            const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream);
+int fhe_hmult_sealed_fused_key(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_a0, const uint64_t *d_a1,
+                               const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a,
+                               const uint64_t *const *d_seal_in, const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags,
+                               void *stream);
+int fhe_ctx_inject_fault_keyswitch_sealed(fhe_ctx *ctx, int key_row, long long coeff, int bit);
+
 /* ---- fault injection ---------------------------------------------------------------- */
 /* _flip_bit_kernel<<<1,1>>> (reliability_test/dotprod_test.cu:31-33,55): data[idx] ^= 1 << bit */
 int fhe_flip_bit(fhe_ctx *ctx, uint64_t *d_data, uint64_t idx, int bit, void *stream);
