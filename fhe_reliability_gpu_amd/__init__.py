@@ -14,6 +14,7 @@ from .engine import (  # noqa: F401
     KeySwitch,
     automorphism,
     automorphism_checked,
+    automorphism_sealed,
     DeviceArray,
     Engine,
     FourStep,

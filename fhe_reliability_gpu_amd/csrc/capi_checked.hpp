@@ -136,6 +136,13 @@ struct KscPerm {
     const u64 *c0;
     u64 *acc_to, *c0_to;
     GaloisFault fault;       // unit = half * M + row for the sums, 2 M + l for c0
+    // fhe_rotate_hoisted_sealed with c0's seal: the L rows of c0 go through the sealed permutation (galois_sealed.hip) instead, which
+    // verifies them on its own gather -- their verdict lands in flags_c0 ([L], zeroed by the caller), their L words of the stage-8
+    // block stay zero.  Null (every other call): c0 goes through the checked permutation with the sums
+    const u64 *seal_c0 = nullptr;      // DEVICE [L][2]
+    u32 *flags_c0 = nullptr;
+    u64 *part = nullptr;               // at least galois_seal_part_words(L, log_n, false) long
+    GalSealHit hit{-1, 0, 0, 0};       // the sealed permutation's hook, checked against the call
 };
 int ksc_front(fhe_keyswitch *p, const uint64_t *d_c, const fhe_abft *a, const KscFlags &fl, hipStream_t st, const KscHook &h);
 int ksc_back(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk, const uint64_t *d_add0,
@@ -223,6 +230,19 @@ struct HrcHook {
 int galois_fault_check(const GaloisFault &f, size_t units, int logn);
 // the plan's buffers (partial sums, second set of sums) and the hook's validation: before anything is launched
 int hrc_prepare(fhe_keyswitch *p, const StagedFault &ft, size_t n_rot, HrcHook &h);
+// fhe_rotate_hoisted_sealed's additions to the launch list (capi_galois_sealed.cpp); absent, hrc_run's list is what it was.  Rotation
+// r's input flags are flags_in + r * stride: [c0 rows L][key rows dnum 2 M], zeroed by the caller.  Stage 3 runs through a
+// SealedKeyStep with seal_keys[r]; c0 through the sealed permutation when seal_c0 is given
+struct HrcSealed {
+    const uint64_t *seal_c0;               // DEVICE [L][2], or null: c0 goes through the checked permutation
+    const uint64_t *const *seal_keys;      // HOST [n_rot] of DEVICE [dnum 2 M][2]; the array or an entry may be null
+    u32 *flags_in;
+    size_t stride;
+    u64 *part;                             // ctx->seal_part, long enough for the key step and the sealed permutation
+    GalSealHit hit;                        // the sealed permutation's hook, for rotation hit_rot
+    size_t hit_rot;
+};
 // the launches; d_flags = the shared block then one block per rotation (hrc_layout), cleared by the caller
 int hrc_run(fhe_keyswitch *p, uint64_t *const *d_out0, uint64_t *const *d_out1, const uint64_t *d_c0, const uint64_t *d_c1, const uint32_t *galois_elts,
-            const uint64_t *const *d_prepared_keys, size_t n_rot, const fhe_abft *a, uint32_t *d_flags, hipStream_t st, const HrcHook &h);
+            const uint64_t *const *d_prepared_keys, size_t n_rot, const fhe_abft *a, uint32_t *d_flags, hipStream_t st, const HrcHook &h,
+            const HrcSealed *sealed = nullptr);

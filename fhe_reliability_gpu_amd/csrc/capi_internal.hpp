@@ -154,6 +154,19 @@ struct fhe_ctx {
             return f;
         }
     } ks_seal_fault;
+    // fhe_ctx_inject_fault_galois_sealed: one bit at destination word coeff of row `row` of the sealed permutation of
+    // fhe_automorphism_ntt_sealed (rot = 0) or of c0 in rotation `rot` of fhe_rotate_hoisted_sealed; point = GAL_AT_WORD or
+    // GAL_AT_INDEX, point < 0 = disarmed
+    struct GalSealFault {
+        int rot = 0, point = -1, row = 0, bit = 0;
+        long long coeff = 0;
+        GalSealFault take()
+        {
+            const GalSealFault f = *this;
+            point = -1;
+            return f;
+        }
+    } gal_seal_fault;
     DevBuf seal_part;      // fhe_seal / fhe_seal_verify and the sealed composites: the chunks' partial sums, [rows][chunks][2] (the carried adds: [4] or [6], the sealed tensor product: [8] or [14]; grown on demand)
     DevBuf gal_sums;       // checked Galois permutation: the units' source-side and destination-side sums, [2][units] (grown on demand)
     int geo = 1;           // column-tile geometry of the two-launch path (ntt_launch.hpp)

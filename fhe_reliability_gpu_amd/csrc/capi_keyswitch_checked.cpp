@@ -195,7 +195,13 @@ int ksc_back(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_
     // ---- 8: sigma of the sums and of c0
     if (perm) {
         const GalSeg segs[2] = {{perm->acc_to, acc, (u32)(2 * M)}, {perm->c0_to, perm->c0, (u32)L}};
-        if ((rc = galois_permute_checked(p->ctx, st, segs, 2, logn, perm->galois_elt, fl.s[8], perm->fault))) return rc;
+        if ((rc = galois_permute_checked(p->ctx, st, segs, perm->seal_c0 ? 1 : 2, logn, perm->galois_elt, fl.s[8], perm->fault))) return rc;
+        if (perm->seal_c0) {
+            // c0 verified on the permutation's own gather (galois_sealed.hip); its words of fl.s[8] stay zero
+            const GalSealArgs ga{perm->c0_to, perm->c0, lp, 0u, (u32)L, (u32)L, (u32)L, logn, perm->galois_elt};
+            if ((e = launch_automorphism_ntt_sealed(st, ga, perm->part, perm->seal_c0, nullptr, perm->flags_c0, perm->hit)) != hipSuccess)
+                return hip_fail(e, "launch_automorphism_ntt_sealed");
+        }
         acc = perm->acc_to;
         d_add0 = perm->c0_to;
     }

@@ -100,7 +100,8 @@ int hrc_prepare(fhe_keyswitch *p, const StagedFault &ft, size_t n_rot, HrcHook &
 
 // the launches of the checked hoisted rotations; d_flags (the shared block, then one block per rotation) cleared by the caller
 int hrc_run(fhe_keyswitch *p, uint64_t *const *d_out0, uint64_t *const *d_out1, const uint64_t *d_c0, const uint64_t *d_c1, const uint32_t *galois_elts,
-            const uint64_t *const *d_prepared_keys, size_t n_rot, const fhe_abft *a, uint32_t *d_flags, hipStream_t st, const HrcHook &h)
+            const uint64_t *const *d_prepared_keys, size_t n_rot, const fhe_abft *a, uint32_t *d_flags, hipStream_t st, const HrcHook &h,
+            const HrcSealed *sealed)
 {
     const HrcLayout lay = hrc_layout(p);
     u64 *acc_rot = p->acc2.as<u64>(), *c0_rot = p->rot.as<u64>();
@@ -114,8 +115,22 @@ int hrc_run(fhe_keyswitch *p, uint64_t *const *d_out0, uint64_t *const *d_out1, 
         u32 *block = d_flags + lay.n_shared + r * lay.n_rot;
         for (int i = 0; i < 6; i++) fl.s[stage_of[i]] = block + lay.rot[i];
         const bool armed = h.stage >= 3 && (size_t)h.rot == r;
-        const KscPerm perm{galois_elts[r], d_c0, acc_rot, c0_rot, armed ? h.gal : GaloisFault{}};
-        if ((rc = ksc_back(p, d_out0[r], d_out1[r], d_c1, d_prepared_keys[r], nullptr, nullptr, a, fl, st, armed ? h.hook : none, &perm, KsForm::CKKS))) return rc;
+        KscPerm perm{galois_elts[r], d_c0, acc_rot, c0_rot, armed ? h.gal : GaloisFault{}};
+        if (!sealed) {
+            if ((rc = ksc_back(p, d_out0[r], d_out1[r], d_c1, d_prepared_keys[r], nullptr, nullptr, a, fl, st, armed ? h.hook : none, &perm, KsForm::CKKS))) return rc;
+            continue;
+        }
+        // the sealed call: the key verified on the inner product's load, c0 on the permutation's gather
+        u32 *in = sealed->flags_in + r * sealed->stride;
+        const SealedKeyStep key{sealed->seal_keys ? sealed->seal_keys[r] : nullptr, in + p->L, sealed->part, KsSealHit{0, 0, 0}};
+        if (sealed->seal_c0) {
+            perm.seal_c0 = sealed->seal_c0;
+            perm.flags_c0 = in;
+            perm.part = sealed->part;
+            if (sealed->hit.point >= 0 && sealed->hit_rot == r) perm.hit = sealed->hit;
+        }
+        if ((rc = ksc_back(p, d_out0[r], d_out1[r], d_c1, d_prepared_keys[r], nullptr, nullptr, a, fl, st, armed ? h.hook : none, &perm, KsForm::CKKS, &key)))
+            return rc;
     }
     return FHE_OK;
 }

@@ -441,4 +441,29 @@ size_t ks_seal_part_words(u32 M, int logn, u32 dnum);
 // SEAL_SUM where the row as loaded differs from its seal, SEAL_RANGE where a word is >= q_j (always checked); zeroed by the caller
 hipError_t launch_ks_mac_sealed(hipStream_t st, const KsMacArgs &a, u64 *part, const u64 *seal_key, u32 *flags_key, const BcCheck &k, const KsSealHit &hit);
 
+// ---- galois_sealed.hip: the Galois permutation with the source's seal verified and the destination's written on its one gather (galois_seal.hpp) ----
+// rows addressed as SealArgs addresses them; dst and src 16-byte aligned and distinct, logn >= 1 (a lane stores two words), k odd
+struct GalSealArgs {
+    u64 *dst;
+    const u64 *src;
+    const LimbParams *lp;
+    u32 limb0, limbs, units, poly_stride;
+    int logn;
+    u32 k;
+};
+// the sealed permutation's test fault as a launch reads it: point < 0 = not armed; mask = the bit, of the gathered word (GAL_AT_WORD)
+// or of the source index (GAL_AT_INDEX, below 2^logn), at destination word coeff of row `row`
+struct GalSealHit {
+    int point;
+    u32 row, coeff;
+    u64 mask;
+};
+// words of the partial-sum scratch a launch needs: [units][chunks per row][3, or 4 with a destination seal]
+size_t galois_seal_part_words(u32 units, int logn, bool out);
+// launch_automorphism_ntt's words; flags[unit] |= SEAL_SUM where the row as gathered differs from seal_src[unit] ([units][2],
+// required), SEAL_RANGE where a word is >= q_l; zeroed by the caller.  seal_dst != nullptr: seal_dst[unit] = {seal_src[unit][0] as
+// stored, the digested S1 of the destination} (may be seal_src)
+hipError_t launch_automorphism_ntt_sealed(hipStream_t st, const GalSealArgs &a, u64 *part, const u64 *seal_src, u64 *seal_dst, u32 *flags,
+                                          const GalSealHit &hit);
+
 } // namespace fhe

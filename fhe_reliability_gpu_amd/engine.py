@@ -71,6 +71,13 @@ class Engine:
         before the window, the digest and the product read it; memory stays clean.  A negative ``key_row`` disarms."""
         check(lib.fhe_ctx_inject_fault_keyswitch_sealed(self._h, key_row, coeff, bit))
 
+    def inject_fault_galois_sealed(self, rot: int, point: int, row: int = 0, coeff: int = 0, bit: int = 0):
+        """One-shot test hook of ``automorphism_sealed`` (``rot`` = 0) / ``KeySwitch.rotate_hoisted_sealed`` (c0 in rotation ``rot``):
+        at destination word ``coeff`` of row ``row``, point 0 flips ``bit`` of the gathered word in the register, before both digests
+        and the store; point 1 flips ``bit`` (< log N) of its source index, before the load.  Memory stays clean.  A negative
+        ``point`` disarms."""
+        check(lib.fhe_ctx_inject_fault_galois_sealed(self._h, rot, point, row, coeff, bit))
+
     def check(self):
         """Synchronise and raise if a fused-NTT launch reported a timed-out wait."""
         check(lib.fhe_ctx_check(self._h))
@@ -675,6 +682,29 @@ def automorphism_checked(eng: Engine, t: NttTables, src: DeviceArray, galois_elt
     return dst, _permute_checked(eng, dst, src, t.log_n, galois_elt, n_poly * limbs)
 
 
+def automorphism_sealed(eng: Engine, t: NttTables, src: DeviceArray, seal_src: DeviceArray, galois_elt: int, n_poly: int = 1,
+                        limbs: Optional[int] = None, seal_out: bool = True, start: int = 0, stream=None):
+    """``automorphism(..., ntt_domain=True)`` with the source's seal verified on the permutation's own gather: ``(dst, seal_dst,
+    flags)``.  Each source word is loaded once, and the register that is stored is the register that is digested -- with its source
+    weight against ``seal_src`` (from ``NttTables.seal``), with its destination weight for ``seal_dst`` (None when ``seal_out`` is
+    false).  flags[poly * limbs + l] (uint32) carry ``seal_verify``'s bits: ``SEAL_SUM`` (1) the row as gathered is not the row
+    that was sealed, ``SEAL_RANGE`` (2) a word >= q_l.  ``seal_dst`` is {S0 as stored in ``seal_src``, the digested S1}: a row whose
+    S0 moved on this load keeps failing every later verification of ``dst``.  Not covered: a source change that keeps S0 and moves
+    S1 alone raises the flag here but does not poison ``seal_dst`` (galois_seal.hpp)."""
+    limbs = len(t) - start if limbs is None else limbs
+    rows = n_poly * limbs
+    dst = eng.alloc(src.size)
+    dst.shape = src.shape
+    seal_dst = None
+    if seal_out:
+        seal_dst = eng.alloc(rows * 2)
+        seal_dst.shape = (rows, 2)
+    flags = _checked_flags(eng, rows, lambda fl: lib.fhe_automorphism_ntt_sealed(
+        eng._h, dst.ptr, src.ptr, seal_dst.ptr if seal_dst is not None else None, seal_src.ptr if seal_src is not None else None, t._h, n_poly, limbs, start,
+        galois_elt, fl.ptr, stream), stream)
+    return dst, seal_dst, flags
+
+
 class KeySwitch:
     """Hybrid RNS key switching over the primes of ``t`` (L ciphertext primes then K special primes,
     ``dnum`` digits); operation sequence of the reference's SEAL trace
@@ -878,6 +908,56 @@ class KeySwitch:
         lay = self.rotate_hoisted_checked_layout(n_rot)
         return {"shared": self._split_flags(f, lay["shared"], lay["shared"], base),
                 "rot": [self._split_flags(f, lay["rot"], lay["rot"], base + lay["shared_words"] + r * lay["rot_words"]) for r in range(n_rot)]}
+
+    # ---- sealed hoisted rotations (capi_galois_sealed.cpp) ----
+    def rotate_hoisted_sealed_layout(self, n_rot: int):
+        """``{"c1": (0, (L,)), "rot0": offset of rotation 0's input block, "rot_words": words per rotation input block, "c0": (offset
+        inside a rotation's input block, (L,)), "key": (offset inside it, (dnum, 2, M)), "checked": offset of the block laid out as
+        rotate_hoisted_checked_layout, "total": n, "fused": the keys are verified on the inner product's load}`` of
+        ``rotate_hoisted_sealed``'s flag buffer; rotation r's input block starts at ``rot0 + r * rot_words``."""
+        out = (C.c_int * 6)()
+        check(lib.fhe_rotate_hoisted_sealed_layout(self._h, n_rot, out))
+        L, M = self.L, self.L + self.K
+        return {"c1": (int(out[0]), (L,)), "rot0": int(out[1]), "rot_words": int(out[2]), "c0": (0, (L,)), "key": (L, (self.dnum, 2, M)),
+                "checked": int(out[3]), "total": int(out[4]), "fused": bool(out[5])}
+
+    def rotate_hoisted_sealed(self, c0: DeviceArray, c1: DeviceArray, galois_elts, prepared_keys, abft: "Abft", seals=None, key_seals=None,
+                              seal_outputs: bool = True, stream=None):
+        """``rotate_hoisted_checked`` with the operands protected at rest: ``(outs, out_seals, flags)``.  ``seals`` = the seals of
+        (c0, c1) (either may be None), ``key_seals`` = one ``seal_key`` of each PREPARED key (entries may be None); ``out_seals`` is a
+        list of (seal0, seal1), None entries when ``seal_outputs`` is false.  ``flags = {"c1": [L], "rot_in": [{"c0": [L], "key":
+        [dnum][2][M]}, ...], "checked": <as rotate_hoisted_checked>}``.
+
+        Each prepared key is verified on the inner product's own load (above 12 digits: by a sweep), and with c0's seal EVERY
+        rotation verifies c0 on the gather of its own permutation: no sweep over c0 exists, and the c0 words of
+        ``checked["rot"][r]["galois"]`` stay zero.  Without c0's seal c0 goes through the checked permutation as before.  c1 is swept
+        once: its consuming load is inside the transform kernels.  Not covered on the consuming load: c1, sigma(c0) (re-read by the
+        tail), the sums; no BGV, sharded or repairing form."""
+        n = len(galois_elts)
+        lay = self.rotate_hoisted_sealed_layout(n)
+        outs = [(self._out(self.L), self._out(self.L)) for _ in range(n)]
+
+        def seal_buf():
+            s = self.eng.alloc(self.L * 2)
+            s.shape = (self.L, 2)
+            return s
+        out_seals = [(seal_buf(), seal_buf()) if seal_outputs else (None, None) for _ in range(n)]
+        m = max(1, n)
+        ptr = lambda x: x.ptr if x is not None else None
+        a0 = (vp * m)(*[o[0].ptr for o in outs])
+        a1 = (vp * m)(*[o[1].ptr for o in outs])
+        ks = (vp * m)(*[k.ptr for k in prepared_keys])
+        ge = (C.c_uint32 * m)(*[int(g) for g in galois_elts])
+        sin = (vp * 2)(*[ptr(x) for x in (seals if seals is not None else (None, None))])
+        sk = (vp * m)(*[ptr(x) for x in (key_seals if key_seals is not None else [None] * n)])
+        s0 = (vp * m)(*[ptr(x[0]) for x in out_seals])
+        s1 = (vp * m)(*[ptr(x[1]) for x in out_seals])
+        f = _checked_flags(self.eng, lay["total"], lambda fl: lib.fhe_rotate_hoisted_sealed(
+            self.eng._h, self._h, a0, a1, c0.ptr, c1.ptr, ge, ks, n, abft._h, sin, sk, s0, s1, fl.ptr, stream), stream)
+        flags = {"c1": self._split_flags(f, lay, ("c1",))["c1"],
+                 "rot_in": [self._split_flags(f, lay, ("c0", "key"), lay["rot0"] + r * lay["rot_words"]) for r in range(n)],
+                 "checked": self._hoisted_flags(f, n, lay["checked"])}
+        return outs, out_seals, flags
 
     # ---- checked BSGS matrix-vector product (capi_bsgs_checked.cpp) ----
     BSGS_GIANT_STAGES = ("inner", "galois", "acc", "keyswitch")      # in execution order

@@ -1164,6 +1164,55 @@ int fhe_hmult_sealed_fused_key(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0,
                                void *stream);
 int fhe_ctx_inject_fault_keyswitch_sealed(fhe_ctx *ctx, int key_row, long long coeff, int bit);
 
+/* ---- sealed Galois permutation and sealed hoisted rotations: the source verified on the permutation's own gather -------------
+ * fhe_automorphism_ntt_checked compares two residue sums modulo 2^32 - 1 (blind to +2^b - 2^(b+32) inside a word) from two reads of
+ * the source, and says nothing about a word that was already wrong in memory.  A permutation gathers each source word exactly
+ * once, so here the register that is stored is the register that is digested with the sums of fhe_seal (modulo 2^61 - 1): with its
+ * SOURCE weight against the source's seal, with its DESTINATION weight for the destination's seal.  16 N bytes per row against the
+ * 40 N of fhe_seal_verify + fhe_automorphism_ntt_checked + fhe_seal.
+ *
+ * fhe_automorphism_ntt_sealed: d_dst = sigma_k(d_src) over the rows [n_poly][limbs] of table limbs start_idx .. (fhe_seal's row
+ * convention), out of place, both buffers 16-byte aligned, galois_elt odd.  d_seal_src ([rows][2], required: without it nothing
+ * would check the permutation) is held word for word against the digest of the words as gathered; d_flags [rows], cleared by the
+ * call, with fhe_seal_verify's bits (1 the row as gathered is not the row that was sealed, 2 a word >= q_l).  d_seal_dst ([rows][2],
+ * may be NULL, may be d_seal_src) receives {S0 as STORED in d_seal_src, the digested S1 of the destination}: S0 is carried, since a
+ * permutation leaves it alone, so a row whose S0 moved on this call's load keeps failing every later verification of d_dst.  The
+ * hole that is left: a source change that keeps S0 and moves S1 alone raises the source's flag here but does not poison
+ * d_seal_dst.  On clean data the words are fhe_automorphism_ntt's, bit for bit; a raised flag does not stop the stores.
+ *
+ * fhe_rotate_hoisted_sealed: fhe_rotate_hoisted_checked (its arguments first, CKKS form only) with the operands protected at rest.
+ * d_seal_in = HOST [2] the seals of c0, c1 ([L][2] each; the array or an entry may be NULL); d_seal_keys = HOST [n_rot] the seals of
+ * the PREPARED keys ([dnum 2 M][2], fhe_seal over the key as [dnum 2][M] rows; the array or an entry may be NULL); d_seal_out0 /
+ * d_seal_out1 = HOST [n_rot] each, where the outputs' seals go ([L][2]; NULL: not sealed).  Flags, cleared by the call:
+ *     [c1 rows L][per rotation r: [c0 rows L][key rows dnum 2 M]][fhe_rotate_hoisted_checked's block, exactly its layout]
+ * c1 is verified once by a sweep (its consuming load is inside the transform kernels of stage 0).  Per rotation the inner product
+ * verifies the prepared key on the load that multiplies it (as fhe_keyswitch_apply_sealed; above 12 digits a sweep followed by the
+ * checked inner product), and with c0's seal the L rows of c0 go through the sealed permutation: EVERY rotation verifies c0 on its
+ * own gather, no sweep over c0 exists, the verdict lands in that rotation's [c0 rows] and the c0 words of the checked block's
+ * permutation stage stay zero.  With a NULL c0 seal c0 goes through the checked permutation exactly as in the checked call and the
+ * [c0 rows] stay zero.  A raised input flag does not stop the call.  Words are fhe_rotate_hoisted's, bit for bit.
+ * fhe_rotate_hoisted_sealed_layout: out = {offset of the c1 rows = 0, offset of rotation 0's input block = L, words per rotation
+ * input block = L + dnum 2 M, offset of the checked block, total, 1 if the keys take the fused route}.
+ * Not covered on the consuming load: c1; sigma(c0), which sits in the plan and is re-read by the tail; the sums; BGV and sharded
+ * plans; no repairing form.
+ *
+ * Test hook: fhe_ctx_inject_fault_galois_sealed(rot, point, row, coeff, bit), a negative point clears; taken, one shot and whatever
+ * the outcome, by the next of the two calls above.  Point 0 flips the bit of the word gathered for destination word coeff of `row`
+ * in the register, before both digests and the store; point 1 flips a bit (< log N) of its source index, before the load and before
+ * the source weight is formed.  rot names the rotation of the hoisted call, row a row of c0; the standalone call takes rot = 0 only.
+ * A rotation, row or word outside the call, point 1 with bit >= log N, or a NULL c0 seal in the hoisted call make that call return
+ * FHE_ERR_INVALID with nothing launched.  fhe_rotate_hoisted_sealed also takes fhe_ctx_inject_fault_rotate_hoisted's hook; a
+ * permutation-stage fault on a c0 row is refused when c0's seal is given.  The checked calls do not take this hook. */
+int fhe_automorphism_ntt_sealed(fhe_ctx *ctx, uint64_t *d_dst, const uint64_t *d_src, uint64_t *d_seal_dst, const uint64_t *d_seal_src,
+                                const fhe_ntt_tables *t, size_t n_poly, size_t limbs, size_t start_idx, uint32_t galois_elt, uint32_t *d_flags,
+                                void *stream);
+int fhe_rotate_hoisted_sealed_layout(const fhe_keyswitch *p, size_t n_rot, int out[6]);
+int fhe_rotate_hoisted_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *const *d_out0, uint64_t *const *d_out1, const uint64_t *d_c0,
+                              const uint64_t *d_c1, const uint32_t *galois_elts, const uint64_t *const *d_prepared_keys, size_t n_rot,
+                              const fhe_abft *a, const uint64_t *const *d_seal_in, const uint64_t *const *d_seal_keys,
+                              uint64_t *const *d_seal_out0, uint64_t *const *d_seal_out1, uint32_t *d_flags, void *stream);
+int fhe_ctx_inject_fault_galois_sealed(fhe_ctx *ctx, int rot, int point, int row, long long coeff, int bit);
+
 /* ---- fault injection ---------------------------------------------------------------- */
 /* _flip_bit_kernel<<<1,1>>> (reliability_test/dotprod_test.cu:31-33,55): data[idx] ^= 1 << bit */
 int fhe_flip_bit(fhe_ctx *ctx, uint64_t *d_data, uint64_t idx, int bit, void *stream);
