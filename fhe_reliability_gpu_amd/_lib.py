@@ -205,6 +205,12 @@ _SIG = {
     "fhe_rotate_hoisted_sealed": (ci, [vp, vp, C.POINTER(vp), C.POINTER(vp), vp, vp, C.POINTER(C.c_uint32), C.POINTER(vp), sz, vp, C.POINTER(vp), C.POINTER(vp),
                                        C.POINTER(vp), C.POINTER(vp), vp, vp]),
     "fhe_ctx_inject_fault_galois_sealed": (ci, [vp, ci, ci, ci, C.c_longlong, ci]),
+    "fhe_ntt_inverse_sealed": (ci, [vp, vp, vp, vp, vp, sz, sz, sz, vp, vp, vp]),
+    "fhe_ctx_inject_fault_ntt_sealed": (ci, [vp, ci, C.c_longlong, ci]),
+    "fhe_keyswitch_sealed_in_layout": (ci, [vp, C.POINTER(ci)]),
+    "fhe_keyswitch_apply_sealed_in": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "fhe_rotate_sealed_in_layout": (ci, [vp, C.POINTER(ci)]),
+    "fhe_rotate_sealed_in": (ci, [vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp, C.POINTER(vp), vp, C.POINTER(vp), vp, vp]),
     "fhe_ctx_trace": (ci, [vp, ci]),
     "fhe_ctx_trace_read": (ci, [vp, C.c_char_p, sz, C.POINTER(sz)]),
 }

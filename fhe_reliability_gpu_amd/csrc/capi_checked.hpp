@@ -33,6 +33,18 @@ inline size_t ksc_slots(const fhe_keyswitch *p)
     return std::max((size_t)std::max(p->dnum, 2) * (p->L + p->K), (size_t)3 * std::max(p->L - 1, 0));
 }
 
+// in != nullptr (fhe_keyswitch_apply_sealed_in, fhe_rotate_sealed_in; capi_ntt_sealed.cpp): stage 0 is the sealed inverse transform
+// (ntt_sealed.hip) out of place from d_c into the plan's coefficient buffer instead of the copy followed by the checked inverse in
+// place -- same words, same ABFT flags at the same place -- which verifies d_c's seal on the transform's own load; absent, every
+// launch list is the checked call's own
+struct SealedInputStep {
+    const uint64_t *seal;          // DEVICE [L][2] the stored seals of d_c's rows, or null: not compared (the window still is)
+    uint32_t *flags;               // the rows' flags, [L]: every word is written by stage 0
+    u64 *part;                     // at least ntt_seal_part_words(L, log_n) words, not shared with a launch that runs before stage 0 ends
+    u32 hit_row, hit_coeff;        // the sealed transform's hook, checked against the call (ntt_seal_hit); hit_mask == 0: not armed
+    u64 hit_mask;
+};
+
 // the transforms of one checked stage: rows [row0, row0 + count) of n_poly polynomials `stride` rows apart inside base, row r on
 // table limb tl0 + (r - row0); the sums of (polynomial, row) live at slot sum0 + polynomial * stride + row
 struct KscRows {
@@ -62,6 +74,18 @@ struct KscNtt {
                                               p->log_n, path, which, inverse);
             return e == hipSuccess ? FHE_OK : hip_fail(e, "launch_ntt_checked");
         });
+    }
+    // the inverse transform of one row range with its input's seal verified on the transform's own load (ntt_sealed.hip): out of
+    // place from src (the rows as r addresses them inside src) into r.base, one polynomial; the rows' seal verdicts go to in.flags
+    int launch_sealed(const KscRows &r, const u64 *src, const SealedInputStep &in, int which) const;
+    int run_sealed(const KscRows &r, const u64 *src, const SealedInputStep &in, u64 *flip, int bit) const
+    {
+        int rc;
+        if (!flip) return launch_sealed(r, src, in, -1);
+        if ((rc = launch_sealed(r, src, in, 0))) return rc;
+        hipError_t e = launch_flip_bit(st, flip, 0, bit);
+        if (e != hipSuccess) return hip_fail(e, "launch_flip_bit");
+        return launch_sealed(r, src, in, 1);
     }
     // all launches of the stage; flip != nullptr (test hook, two-launch sizes): that word is flipped between the stage's two launches
     int run(const std::vector<KscRows> &rows, u64 *flip, int bit) const
@@ -108,9 +132,10 @@ struct SealedKeyStep {
     u64 *part;                     // ctx->seal_part, at least ks_sealed_scratch_words(p) long
     KsSealHit hit;                 // the sealed call's hook, checked against the plan (ks_seal_hit)
 };
+// in != nullptr: stage 0 is the sealed inverse transform (SealedInputStep above); absent, every launch list is the checked call's own
 int keyswitch_checked(fhe_keyswitch *p, KsForm form, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk,
                       const uint64_t *d_add0, const uint64_t *d_add1, const fhe_abft *a, uint32_t *d_flags, hipStream_t st, const StagedFault &ft,
-                      const SealedKeyStep *key = nullptr);
+                      const SealedKeyStep *key = nullptr, const SealedInputStep *in = nullptr);
 // the whole rotation behind an entry point (fhe_rotate_checked, fhe_bgv_rotate_checked, fhe_rotate_sealed, fhe_rotate_sealed_fused)
 int rotate_checked(KsForm form, KsHookSlot hook, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0,
                    const uint64_t *d_c1, uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, uint32_t *d_flags, void *stream,
@@ -144,7 +169,8 @@ struct KscPerm {
     u64 *part = nullptr;               // at least galois_seal_part_words(L, log_n, false) long
     GalSealHit hit{-1, 0, 0, 0};       // the sealed permutation's hook, checked against the call
 };
-int ksc_front(fhe_keyswitch *p, const uint64_t *d_c, const fhe_abft *a, const KscFlags &fl, hipStream_t st, const KscHook &h);
+int ksc_front(fhe_keyswitch *p, const uint64_t *d_c, const fhe_abft *a, const KscFlags &fl, hipStream_t st, const KscHook &h,
+              const SealedInputStep *in = nullptr);
 int ksc_back(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk, const uint64_t *d_add0,
              const uint64_t *d_add1, const fhe_abft *a, const KscFlags &fl, hipStream_t st, const KscHook &h, const KscPerm *perm, KsForm form,
              const SealedKeyStep *key = nullptr);
@@ -160,6 +186,10 @@ int ks_seal_hit(const fhe_ctx::KsSealFault &f, const fhe_keyswitch *p, KsSealHit
 // stage 3 of a key switch with a sealed key: the fused launch, or above the cap launch_seal_verify over the key's rows followed by
 // launch_ks_mac_checked; k = the residue check record of stage 3, its flags [2][M]
 int ks_mac_sealed_stage(const fhe_keyswitch *p, hipStream_t st, const KsMacArgs &ka, const BcCheck &k, const SealedKeyStep &key);
+
+// defined in capi_ntt_sealed.cpp
+// the sealed transform's hook as a call of `rows` rows took it (ctx->ntt_seal_fault), checked against that call
+int ntt_seal_hit(const fhe_ctx::NttSealFault &f, size_t rows, int log_n, SealedInputStep &in);
 
 // defined in capi_bgv_checked.cpp
 // one scalar stage: `limbs` rows from data on, of n_poly polynomials poly_stride rows apart (row l of polynomial i at data + (i

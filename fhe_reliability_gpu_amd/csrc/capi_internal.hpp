@@ -167,7 +167,19 @@ struct fhe_ctx {
             return f;
         }
     } gal_seal_fault;
-    DevBuf seal_part;      // fhe_seal / fhe_seal_verify and the sealed composites: the chunks' partial sums, [rows][chunks][2] (the carried adds: [4] or [6], the sealed tensor product: [8] or [14]; grown on demand)
+    // fhe_ctx_inject_fault_ntt_sealed: one bit of word coeff of row `row` as the sealed inverse transform of fhe_ntt_inverse_sealed,
+    // fhe_keyswitch_apply_sealed_in or fhe_rotate_sealed_in loads it; row < 0 = disarmed
+    struct NttSealFault {
+        int row = -1, bit = 0;
+        long long coeff = 0;
+        NttSealFault take()
+        {
+            const NttSealFault f = *this;
+            row = -1;
+            return f;
+        }
+    } ntt_seal_fault;
+    DevBuf seal_part;     // fhe_seal / fhe_seal_verify and the sealed composites: the chunks' partial sums, [rows][chunks][2] (the carried adds: [4] or [6], the sealed tensor product: [8] or [14]; grown on demand)
     DevBuf gal_sums;       // checked Galois permutation: the units' source-side and destination-side sums, [2][units] (grown on demand)
     int geo = 1;           // column-tile geometry of the two-launch path (ntt_launch.hpp)
     bool resident = false; // 2^13 / 2^14: one LDS-resident pass instead of two launches (opt-in, see ntt_plan.hpp)

@@ -129,7 +129,7 @@ KscNtt ksc_ntt(const fhe_keyswitch *p, const fhe_abft *a, hipStream_t st, bool i
 }
 
 // stages 0-2: what does not depend on the key (nor, for hoisted rotations, on the Galois element)
-int ksc_front(fhe_keyswitch *p, const uint64_t *d_c, const fhe_abft *a, const KscFlags &fl, hipStream_t st, const KscHook &h)
+int ksc_front(fhe_keyswitch *p, const uint64_t *d_c, const fhe_abft *a, const KscFlags &fl, hipStream_t st, const KscHook &h, const SealedInputStep *in)
 {
     const int L = p->L, K = p->K, M = L + K, dnum = p->dnum;
     const size_t N = (size_t)1 << p->log_n;
@@ -139,9 +139,13 @@ int ksc_front(fhe_keyswitch *p, const uint64_t *d_c, const fhe_abft *a, const Ks
     HIP_TRY(hipMemsetAsync(p->chk_bc_flags.p, 0, (size_t)dnum * M * sizeof(u32), st));
     const KscNtt fwd = ksc_ntt(p, a, st, false), inv = ksc_ntt(p, a, st, true);
 
-    // ---- 0: opening INTT
-    HIP_TRY(hipMemcpyAsync(coef, d_c, (size_t)L * N * 8, hipMemcpyDeviceToDevice, st));
-    if ((rc = inv.run({KscRows{coef, 0, 0, (u32)L, 1, (u32)L, 0}}, h.f.stage == 0 ? h.flip : nullptr, h.f.bit))) return rc;
+    // ---- 0: opening INTT (in: no copy, d_c's seal verified on the transform's own load, capi_ntt_sealed.cpp)
+    if (in) {
+        if ((rc = inv.run_sealed(KscRows{coef, 0, 0, (u32)L, 1, (u32)L, 0}, d_c, *in, h.f.stage == 0 ? h.flip : nullptr, h.f.bit))) return rc;
+    } else {
+        HIP_TRY(hipMemcpyAsync(coef, d_c, (size_t)L * N * 8, hipMemcpyDeviceToDevice, st));
+        if ((rc = inv.run({KscRows{coef, 0, 0, (u32)L, 1, (u32)L, 0}}, h.f.stage == 0 ? h.flip : nullptr, h.f.bit))) return rc;
+    }
     if ((rc = inv.compare(fl.s[0], 0, 0, (u32)L, (u32)L))) return rc;
 
     // ---- 1: digit extension
@@ -236,7 +240,7 @@ int ksc_back(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_
 
 int keyswitch_checked(fhe_keyswitch *p, KsForm form, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk,
                       const uint64_t *d_add0, const uint64_t *d_add1, const fhe_abft *a, uint32_t *d_flags, hipStream_t st, const StagedFault &ft,
-                      const SealedKeyStep *key)
+                      const SealedKeyStep *key, const SealedInputStep *in)
 {
     int rc;
     if ((rc = ksc_prepare(p))) return rc;
@@ -247,7 +251,7 @@ int keyswitch_checked(fhe_keyswitch *p, KsForm form, uint64_t *d_out0, uint64_t 
     for (int s = 0; s < 11; s++)
         if (lay.units(s)) fl.s[s] = d_flags + lay.off[s];
     HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)lay.total * sizeof(u32), st));
-    if ((rc = ksc_front(p, d_c, a, fl, st, h))) return rc;
+    if ((rc = ksc_front(p, d_c, a, fl, st, h, in))) return rc;
     return ksc_back(p, d_out0, d_out1, d_c, d_evk, d_add0, d_add1, a, fl, st, h, nullptr, form, key);
 }
 

@@ -1,0 +1,273 @@
+// capi_ntt_sealed.cpp -- the inverse transform that verifies its input's seal on its own load (ntt_seal_tap.hpp, ntt_sealed.hip):
+// fhe_ntt_inverse_sealed and its test hook, and the key switch and rotation whose input limbs are verified on the opening
+// transform's load -- fhe_keyswitch_apply_sealed_in, fhe_rotate_sealed_in and their layouts (part of the C ABI of
+// include/fhe_mi355x.h).
+//
+// fhe_keyswitch_apply_sealed does not seal d_c, and the sealed rotations sweep c0 and c1 and then move them through the unchecked
+// permutation: the verifying sweep, the copy into the plan and the opening transform's load are separate loads, and a word that is
+// wrong on a later one passes the seal and is a consistent input of the ABFT identity.  Here stage 0 of the checked key switch is the
+// sealed inverse transform, out of place from the caller's rows into the plan's coefficient buffer (SealedInputStep,
+// capi_checked.hpp): no sweep, no copy.  The rotation is a chain of custody: c0 and c1 are verified on the sealed permutation's
+// gather (galois_sealed.hip), sigma(c1)'s seal is written from the registers that are stored, and stage 0 verifies sigma(c1) against
+// that seal on the transform's load.  A raised input flag does not stop a call.
+#include "capi_checked.hpp"
+#include "galois_seal.hpp"
+#include "seal_check.hpp"
+
+#include <cstdint>
+
+int ntt_seal_hit(const fhe_ctx::NttSealFault &f, size_t rows, int log_n, SealedInputStep &in)
+{
+    in.hit_row = in.hit_coeff = 0;
+    in.hit_mask = 0;
+    if (f.row < 0) return FHE_OK;
+    if ((size_t)f.row >= rows || (u64)f.coeff >> log_n) return fail(FHE_ERR_INVALID, "fault row or word outside the call");
+    in.hit_row = (u32)f.row;
+    in.hit_coeff = (u32)f.coeff;
+    in.hit_mask = (u64)1 << f.bit;
+    return FHE_OK;
+}
+
+// one launch per run of an arithmetic path; the seal, the flags, the partials and the hook's row move with the run
+int KscNtt::launch_sealed(const KscRows &r, const u64 *src, const SealedInputStep &in, int which) const
+{
+    const fhe_ntt_tables *t = p->t;
+    const size_t N = (size_t)1 << p->log_n;
+    return for_each_run(t, r.count, r.tl0, [&](size_t off, size_t len, int path) -> int {
+        PassArgs pa{r.base + (r.row0 + off) * N, t->d_lp.as<LimbParams>(), (u32)(r.tl0 + off), (u32)len, (u32)len, r.stride, nullptr};
+        pa.src = src + (r.row0 + off) * N;
+        const size_t slot = (size_t)r.sum0 + r.row0 + off;
+        if (r.n_poly != 1 || slot + len > ksc_slots(p)) return fail(FHE_ERR_INVALID, "checked call: a transform's sums lie outside the plan's scratch");
+        NttSealIn s{in.seal ? in.seal + 2 * off : nullptr, in.flags + off, in.part + off * tin * 3};
+        if (in.hit_mask && in.hit_row >= off && in.hit_row < off + len) {
+            s.hit_row = in.hit_row - (u32)off;
+            s.hit_coeff = in.hit_coeff;
+            s.hit_mask = in.hit_mask;
+        }
+        hipError_t e = launch_ntt_sealed_inv(st, pa, a->win.as<Tw>(), a->wout.as<Tw>(), a->wout8.as<u64>(), sum_in() + slot * tin, sum_out() + slot * tout, p->log_n,
+                                             path, which, s);
+        return e == hipSuccess ? FHE_OK : hip_fail(e, "launch_ntt_sealed_inv");
+    });
+}
+
+namespace {
+
+KsForm plan_form(const fhe_keyswitch *p) { return p && p->plain_modulus ? KsForm::BGV : KsForm::CKKS; }
+StagedFault take_ks_hook(fhe_ctx *ctx, const fhe_keyswitch *p) { return (p && p->plain_modulus ? ctx->bgv_ksc_fault : ctx->ksc_fault).take(); }
+size_t key_rows(const fhe_keyswitch *p) { return (size_t)p->dnum * 2 * (p->L + p->K); }
+
+bool misaligned(std::initializer_list<const void *> ptrs)
+{
+    for (const void *q : ptrs)
+        if ((uintptr_t)q % 16) return true;
+    return false;
+}
+
+// the context's partial-sum scratch, at least `words` long
+int scratch(fhe_ctx *ctx, size_t words, u64 **out)
+{
+    if (ctx->seal_part.bytes < words * 8) HIP_TRY(ctx->seal_part.alloc(words * 8));
+    *out = ctx->seal_part.as<u64>();
+    return FHE_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int fhe_ctx_inject_fault_ntt_sealed(fhe_ctx *ctx, int row, long long coeff, int bit)
+{
+    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
+    if (row < 0) {
+        (void)ctx->ntt_seal_fault.take();
+        return FHE_OK;
+    }
+    if (coeff < 0 || bit < 0 || bit > 63) return fail(FHE_ERR_INVALID, "bad fault");
+    ctx->ntt_seal_fault = fhe_ctx::NttSealFault{row, bit, coeff};
+    return FHE_OK;
+}
+
+int fhe_ntt_inverse_sealed(fhe_ctx *ctx, uint64_t *d_dst, const uint64_t *d_src, const fhe_ntt_tables *t, const fhe_abft *a, size_t n_poly, size_t limbs,
+                           size_t start_idx, const uint64_t *d_seal_src, uint32_t *d_flags, void *stream)
+{
+    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
+    const fhe_ctx::NttSealFault nf = ctx->ntt_seal_fault.take();      // one shot, whatever the outcome
+    if (!d_dst || !d_src || !t || !a || !d_flags) return fail(FHE_ERR_INVALID, "null argument");
+    if (a->t != t) return fail(FHE_ERR_INVALID, "the detector was made for another table set");
+    int rc = check_range(t, n_poly, limbs, start_idx);
+    if (rc) return rc;
+    if (!t->has_inverse) return fail(FHE_ERR_UNSUPPORTED, "table set has no inverse (twiddle or N not invertible)");
+    if (ctx->mode != 0 || ctx->resident || ctx->packed_on || ctx->only_pass >= 0 || !ntt_checked_supported(t->log_n))
+        return fail(FHE_ERR_UNSUPPORTED, "the sealed inverse transform runs the checked two-launch transform: not with ntt_mode=1, ntt_resident, ntt_packed, a single-pass hook, or N < 2^5");
+    const size_t units = n_poly * limbs, N = (size_t)1 << t->log_n;
+    SealedInputStep hit{};
+    if ((rc = ntt_seal_hit(nf, units, t->log_n, hit))) return rc;
+    // the checked transforms' hook between the two launches (fhe_ctx_inject_fault), two-launch sizes, as fhe_ntt_inverse_checked takes it
+    const bool between = ctx->fault_idx >= 0 && t->log_n >= 13;
+    const long long fidx = ctx->fault_idx;
+    if (between) {
+        ctx->fault_idx = -1;
+        if ((u64)fidx >= units * N) return fail(FHE_ERR_INVALID, "fault index outside the call's window");
+    }
+    if (!units) return FHE_OK;
+    fhe_abft *m = const_cast<fhe_abft *>(a);
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = pick(ctx, stream);
+    u32 tin = 1, tout = 1;
+    ntt_checked_tiles(t->log_n, &tin, &tout, true);
+    if (m->sum_in.bytes < units * 8 * tin || m->sum_out.bytes < units * 8 * tout) {
+        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(m->sum_in.alloc(units * 16 * tin));
+        HIP_TRY(m->sum_out.alloc(units * 16 * tout));
+    }
+    u64 *part;
+    if ((rc = scratch(ctx, ntt_seal_part_words((u32)units, t->log_n), &part))) return rc;
+    HIP_TRY(hipMemsetAsync(d_flags, 0, 2 * units * sizeof(u32), st));
+    // row (poly, l) of the call is row poly * limbs + l of the seal, the flags and the sums; a run of limbs addresses them from its
+    // first limb on
+    auto run = [&](int which) -> int {
+        return for_each_run(t, limbs, start_idx, [&](size_t off, size_t len, int path) -> int {
+            PassArgs pa{d_dst + off * N, t->d_lp.as<LimbParams>(), (u32)(start_idx + off), (u32)len, (u32)(n_poly * len), (u32)limbs, nullptr};
+            if (d_src != d_dst) pa.src = d_src + off * N;
+            NttSealIn s{d_seal_src ? d_seal_src + 2 * off : nullptr, d_flags + off, part + off * tin * 3};
+            const size_t hl = hit.hit_row % (limbs ? limbs : 1);
+            if (hit.hit_mask && hl >= off && hl < off + len) {
+                s.hit_row = hit.hit_row - (u32)off;
+                s.hit_coeff = hit.hit_coeff;
+                s.hit_mask = hit.hit_mask;
+            }
+            hipError_t e = launch_ntt_sealed_inv(st, pa, a->win.as<Tw>(), a->wout.as<Tw>(), a->wout8.as<u64>(), m->sum_in.as<u64>() + off * tin,
+                                                 m->sum_out.as<u64>() + off * tout, t->log_n, path, which, s);
+            return e == hipSuccess ? FHE_OK : hip_fail(e, "launch_ntt_sealed_inv");
+        });
+    };
+    if (between) {
+        if ((rc = run(0))) return rc;
+        hipError_t e = launch_flip_bit(st, d_dst, (u64)fidx, ctx->fault_bit);
+        if (e != hipSuccess) return hip_fail(e, "launch_flip_bit");
+        if ((rc = run(1))) return rc;
+    } else if ((rc = run(-1))) return rc;
+    hipError_t e = launch_compare_sums(st, d_flags + units, m->sum_in.as<u64>(), tin, m->sum_out.as<u64>(), tout, t->d_lp.as<LimbParams>(), (u32)start_idx,
+                                       (u32)limbs, (u32)units);
+    return e == hipSuccess ? FHE_OK : hip_fail(e, "launch_compare_sums");
+}
+
+int fhe_keyswitch_sealed_in_layout(const fhe_keyswitch *p, int out[5])
+{
+    if (!p || !out) return fail(FHE_ERR_INVALID, "null argument");
+    out[0] = 0;
+    out[1] = p->L;
+    out[2] = out[1] + (int)key_rows(p);
+    out[3] = out[2] + ksc_layout(p, plan_form(p)).total;
+    out[4] = ks_sealed_fused(p) ? 1 : 0;
+    return FHE_OK;
+}
+
+int fhe_keyswitch_apply_sealed_in(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk,
+                                  const uint64_t *d_add0, const uint64_t *d_add1, const fhe_abft *a, const uint64_t *d_seal_c, const uint64_t *d_seal_key,
+                                  uint32_t *d_flags, void *stream)
+{
+    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
+    const KsForm form = plan_form(p);
+    // the three hooks belong to this call whatever its outcome
+    const StagedFault ft = take_ks_hook(ctx, p);
+    const fhe_ctx::KsSealFault kf = ctx->ks_seal_fault.take();
+    const fhe_ctx::NttSealFault nf = ctx->ntt_seal_fault.take();
+    if (!d_seal_c) return fail(FHE_ERR_INVALID, "null d_seal_c: nothing would verify the input limbs (fhe_keyswitch_apply_sealed takes none)");
+    int rc = ksc_scope(ctx, p, a, d_flags, form, false);
+    if (rc) return rc;
+    if (!d_out0 || !d_out1 || !d_c || !d_evk) return fail(FHE_ERR_INVALID, "null argument");
+    if (d_out0 == d_out1) return fail(FHE_ERR_INVALID, "the two output parts must be distinct buffers");
+    if (misaligned({d_out0, d_out1, d_c, d_evk, d_add0, d_add1}))
+        return fail(FHE_ERR_INVALID, "sealed rows are read 16 bytes at a time: the buffers must be 16-byte aligned");
+    int lay[5];
+    if ((rc = fhe_keyswitch_sealed_in_layout(p, lay))) return rc;
+    SealedKeyStep key{d_seal_key, d_flags + lay[1], nullptr, KsSealHit{0, 0, 0}};
+    SealedInputStep in{d_seal_c, d_flags + lay[0], nullptr, 0, 0, 0};
+    if ((rc = ks_seal_hit(kf, p, key.hit))) return rc;
+    if ((rc = ntt_seal_hit(nf, (size_t)p->L, p->log_n, in))) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    // the checked key switch's own hook, against the call: before anything is launched (keyswitch_checked checks it again)
+    if ((rc = ksc_prepare(p))) return rc;
+    KscHook h;
+    if ((rc = ksc_hook(p, form, ft, p->acc.as<u64>(), d_add0 != nullptr, d_add1 != nullptr, h))) return rc;
+    hipStream_t st = pick(ctx, stream);
+    u64 *part;
+    if ((rc = scratch(ctx, std::max(ks_sealed_scratch_words(p), ntt_seal_part_words((u32)p->L, p->log_n)), &part))) return rc;
+    key.part = in.part = part;      // stage 0's verdict is out before stage 3 starts on the same stream
+    HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)lay[2] * sizeof(u32), st));
+    return keyswitch_checked(p, form, d_out0, d_out1, d_c, d_evk, d_add0, d_add1, a, d_flags + lay[2], st, ft, &key, &in);
+}
+
+int fhe_rotate_sealed_in_layout(const fhe_keyswitch *p, int out[7])
+{
+    if (!p || !out) return fail(FHE_ERR_INVALID, "null argument");
+    out[0] = 0;
+    out[1] = p->L;
+    out[2] = 2 * p->L;
+    out[3] = 3 * p->L;
+    out[4] = out[3] + (int)key_rows(p);
+    out[5] = out[4] + ksc_layout(p, plan_form(p)).total;
+    out[6] = ks_sealed_fused(p) ? 1 : 0;
+    return FHE_OK;
+}
+
+int fhe_rotate_sealed_in(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0, const uint64_t *d_c1, uint32_t galois_elt,
+                         const uint64_t *d_galois_key, const fhe_abft *a, const uint64_t *const *d_seal_in, const uint64_t *d_seal_key,
+                         uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
+{
+    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
+    const KsForm form = plan_form(p);
+    const StagedFault ft = take_ks_hook(ctx, p);
+    const fhe_ctx::KsSealFault kf = ctx->ks_seal_fault.take();
+    const fhe_ctx::NttSealFault nf = ctx->ntt_seal_fault.take();
+    int rc = ksc_scope(ctx, p, a, d_flags, form, false);
+    if (rc) return rc;
+    if (!d_out0 || !d_out1 || !d_c0 || !d_c1 || !d_galois_key) return fail(FHE_ERR_INVALID, "null argument");
+    if (!d_seal_in || !d_seal_in[0] || !d_seal_in[1]) return fail(FHE_ERR_INVALID, "null seal of c0 or c1: nothing would verify the permutation's source");
+    if (d_out0 == d_out1) return fail(FHE_ERR_INVALID, "the two output parts must be distinct buffers");
+    if (!(galois_elt & 1)) return fail(FHE_ERR_INVALID, "Galois elements are odd");
+    if (p->log_n < 1) return fail(FHE_ERR_UNSUPPORTED, "a sealed row has at least two words");
+    if (misaligned({d_out0, d_out1, d_c0, d_c1, d_galois_key}))
+        return fail(FHE_ERR_INVALID, "sealed rows are read 16 bytes at a time: the buffers must be 16-byte aligned");
+    int lay[7];
+    if ((rc = fhe_rotate_sealed_in_layout(p, lay))) return rc;
+    SealedKeyStep key{d_seal_key, d_flags + lay[3], nullptr, KsSealHit{0, 0, 0}};
+    SealedInputStep in{nullptr, d_flags + lay[2], nullptr, 0, 0, 0};
+    if ((rc = ks_seal_hit(kf, p, key.hit))) return rc;
+    if ((rc = ntt_seal_hit(nf, (size_t)p->L, p->log_n, in))) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if ((rc = ksc_prepare(p))) return rc;
+    KscHook h;
+    if ((rc = ksc_hook(p, form, ft, p->acc.as<u64>(), true, false, h))) return rc;
+    hipStream_t st = pick(ctx, stream);
+    const size_t L = (size_t)p->L, N = (size_t)1 << p->log_n;
+    // the launches' partials share one region (stream order keeps them apart); sigma(c1)'s seal lives behind it until stage 0 ends
+    const size_t pw = std::max(std::max(ks_sealed_scratch_words(p), ntt_seal_part_words((u32)L, p->log_n)),
+                               std::max(galois_seal_part_words((u32)L, p->log_n, true), seal_part_words((u32)L, p->log_n)));
+    u64 *part;
+    if ((rc = scratch(ctx, pw + 2 * L, &part))) return rc;
+    u64 *seal_sig1 = part + pw;
+    key.part = in.part = part;
+    in.seal = seal_sig1;
+    HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)lay[4] * sizeof(u32), st));
+    // sigma(c0) and sigma(c1) into the plan's buffers through the sealed permutation: both verified on the gather, sigma(c1)'s seal
+    // written from the registers that are stored
+    u64 *sig1 = p->rot.as<u64>(), *sig0 = sig1 + L * N;
+    const LimbParams *lp = p->t->d_lp.as<LimbParams>();
+    const GalSealHit no_hit{-1, 0, 0, 0};
+    const GalSealArgs g0{sig0, d_c0, lp, 0u, (u32)L, (u32)L, (u32)L, p->log_n, galois_elt}, g1{sig1, d_c1, lp, 0u, (u32)L, (u32)L, (u32)L, p->log_n, galois_elt};
+    hipError_t e = launch_automorphism_ntt_sealed(st, g0, part, d_seal_in[0], nullptr, d_flags + lay[0], no_hit);
+    if (e == hipSuccess) e = launch_automorphism_ntt_sealed(st, g1, part, d_seal_in[1], seal_sig1, d_flags + lay[1], no_hit);
+    if (e != hipSuccess) return hip_fail(e, "launch_automorphism_ntt_sealed");
+    if ((rc = keyswitch_checked(p, form, d_out0, d_out1, sig1, d_galois_key, sig0, nullptr, a, d_flags + lay[4], st, ft, &key, &in))) return rc;
+    const uint64_t *outs[2] = {d_out0, d_out1};
+    for (int hf = 0; hf < 2; hf++) {
+        if (!d_seal_out || !d_seal_out[hf]) continue;
+        const SealArgs sa{outs[hf], lp, 0u, (u32)L, (u32)L, (u32)L, p->log_n};
+        if ((e = launch_seal(st, sa, part, d_seal_out[hf], BcCheck{nullptr, -1, 0, 0, 0})) != hipSuccess) return hip_fail(e, "launch_seal");
+    }
+    return FHE_OK;
+}
+
+} // extern "C"

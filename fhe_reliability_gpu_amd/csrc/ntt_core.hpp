@@ -330,6 +330,10 @@ template <class P> FHE_HD u64 pk_extract(P w, u32 idx)
 // (a tap that declares PRELOAD = true instead offers load(idx) / apply(x, word, ctx): a second input of the pass, see AddSrcTap)
 template <class T, class = void> struct tap_preloads { static constexpr bool value = false; };
 template <class T> struct tap_preloads<T, decltype((void)T::PRELOAD)> { static constexpr bool value = T::PRELOAD; };
+// (a tap that declares SEES_RAW = true is also shown every 64-bit word a first step has just read, BEFORE the conversion:
+// raw(idx, word) with the index `in` gets, the word by reference -- the seal of the transform's input, ntt_seal_tap.hpp)
+template <class T, class = void> struct tap_sees_raw { static constexpr bool value = false; };
+template <class T> struct tap_sees_raw<T, decltype((void)T::SEES_RAW)> { static constexpr bool value = T::SEES_RAW; };
 struct NoTap {
     static constexpr bool ACTIVE = false;
     static constexpr bool MID = false;    // MID: the tap also sees the lazy words a pass hands to the next launch
@@ -405,6 +409,10 @@ struct ColPass {
 #pragma unroll
                     for (int r = 0; r < R; r++) tap->apply(x[r], extra[r], c);
                 } else {
+                    if constexpr (tap_sees_raw<TAP>::value) {
+#pragma unroll
+                        for (int r = 0; r < R; r++) tap->raw((g0 + ((u32)r << LOGS)) * STRIDE + col, raw[r]);
+                    }
                     convert_in<A, R, IN_MODE>(x, raw, c);
                     if constexpr (TAP::ACTIVE) {
 #pragma unroll
@@ -660,6 +668,10 @@ struct RowPass {
                         } else {
                             raw[r] = __builtin_bit_cast(u64, lrow[row_pad(g0 + ((u32)r << LOGS))]);
                         }
+                    }
+                    if constexpr (tap_sees_raw<TAP>::value && (FROM_GLOBAL || STAGE_IN)) {
+#pragma unroll
+                        for (int r = 0; r < R; r++) tap->raw(row * NPTS + g0 + ((u32)r << LOGS), raw[r]);
                     }
                     convert_in<A, R, IN_MODE>(x, raw, c);
                     if constexpr (TAP::ACTIVE && (FROM_GLOBAL || STAGE_IN)) {      // (STAGE_IN: the words the copy phase staged)

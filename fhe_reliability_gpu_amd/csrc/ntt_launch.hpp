@@ -466,4 +466,25 @@ size_t galois_seal_part_words(u32 units, int logn, bool out);
 hipError_t launch_automorphism_ntt_sealed(hipStream_t st, const GalSealArgs &a, u64 *part, const u64 *seal_src, u64 *seal_dst, u32 *flags,
                                           const GalSealHit &hit);
 
+// ---- ntt_sealed.hip: the checked inverse transform with its input's seal verified on the transform's own load (ntt_seal_tap.hpp) ----
+// what the sealed first launch needs beside launch_ntt_checked's arguments.  Rows are addressed as the detector's sums are: row
+// (poly, l) of the launch at index poly * a.poly_stride + l of seal_src ([rows][2], or null: not compared), flags ([rows]: every
+// row's word is WRITTEN -- SEAL_SUM where the row as the transform loaded it differs from its seal, SEAL_RANGE where a word is
+// >= q_l) and part (ntt_seal_part_words(rows, logn) words).  hit_mask != 0: the test fault, XOR into word hit_coeff of row hit_row
+// in the register as loaded
+struct NttSealIn {
+    const u64 *seal_src;
+    u32 *flags;
+    u64 *part;
+    u32 hit_row = 0, hit_coeff = 0;
+    u64 hit_mask = 0;
+};
+size_t ntt_seal_part_words(u32 rows, int logn);
+// launch_ntt_checked(inverse = true) with the first launch sealed; `which` as there (0: the sealed first launch and its verdict, 1:
+// the second launch), so the between-launch flip hook of the checked stages keeps working.  a.src (optional, mirrored layout): the
+// first launch reads the sealed rows from there and a.data receives the result -- out of place, no copy.  Whole-batch launches
+// only: a.map, a.tmp, a.scratch, a.src_bcast, a.src_stride, a.stream_hint and a.galois must be unset.  ntt_checked_supported sizes
+hipError_t launch_ntt_sealed_inv(hipStream_t st, const PassArgs &a, const Tw *win, const Tw *wout, const u64 *wout8, u64 *sum_in, u64 *sum_out, int logn, int path,
+                                 int which, const NttSealIn &s);
+
 } // namespace fhe

@@ -78,6 +78,13 @@ class Engine:
         ``point`` disarms."""
         check(lib.fhe_ctx_inject_fault_galois_sealed(self._h, rot, point, row, coeff, bit))
 
+    def inject_fault_ntt_sealed(self, row: int, coeff: int = 0, bit: int = 0):
+        """One-shot test hook of ``NttTables.intt_sealed`` / ``KeySwitch.apply_sealed_in`` / ``rotate_sealed_in``: flip ``bit`` of
+        word ``coeff`` of row ``row`` of the sealed inverse transform's input (a row of the source, of ``c``, of sigma(c1)) in the
+        register as the next such call's first launch loads it, before the window, the digest and the conversion read it; memory
+        stays clean.  A negative ``row`` disarms."""
+        check(lib.fhe_ctx_inject_fault_ntt_sealed(self._h, row, coeff, bit))
+
     def check(self):
         """Synchronise and raise if a fused-NTT launch reported a timed-out wait."""
         check(lib.fhe_ctx_check(self._h))
@@ -284,6 +291,23 @@ class NttTables:
         limbs = len(self) - start if limbs is None else limbs
         return _checked_flags(self.eng, n_poly * limbs, lambda fl: lib.fhe_seal_verify(self.eng._h, d.ptr, seal.ptr, self._h, n_poly, limbs, start, fl.ptr,
                                                                                        stream), stream)
+
+    def intt_sealed(self, src: DeviceArray, seal: Optional[DeviceArray], abft: "Abft", dst: Optional[DeviceArray] = None, limbs=None, start=0, n_poly=1,
+                    stream=None):
+        """The inverse NTT of the rows of ``src`` with their seal verified on the transform's own load: ``(dst, flags)``,
+        ``flags`` uint32 ``[2][rows]`` -- block 0 the seal verdict per row with ``seal_verify``'s bits (``SEAL_SUM`` the row as the
+        transform loaded it is not the row that was sealed, ``SEAL_RANGE`` a word >= q_l), block 1 ``Abft.inverse_checked``'s flag.
+        ``dst`` None: a new array (out of place, no copy; ``src`` is only read); ``dst`` may be ``src`` (in place).  ``seal`` from
+        ``seal`` (None: not compared, the window still is).  The words are ``intt``'s, bit for bit; a raised seal flag does not stop
+        the call.  Whole-batch launches only: never cut into sub-batches."""
+        limbs = len(self) - start if limbs is None else limbs
+        rows = n_poly * limbs
+        if dst is None:
+            dst = self.eng.alloc(src.size)
+            dst.shape = src.shape
+        f = _checked_flags(self.eng, 2 * rows, lambda fl: lib.fhe_ntt_inverse_sealed(
+            self.eng._h, dst.ptr, src.ptr, self._h, abft._h, n_poly, limbs, start, seal.ptr if seal is not None else None, fl.ptr, stream), stream)
+        return dst, f.reshape(2, rows)
 
     def seal_locator(self, d: DeviceArray, limbs=None, start=0, n_poly=1, stream=None) -> DeviceArray:
         """The locator sums of the rows of ``d``: a device array ``[n_poly * limbs]`` of S2 = sum (j + 1)^2 x_j modulo 2^61 - 1,
@@ -1275,6 +1299,56 @@ class KeySwitch:
         flags = self._split_flags(f, lay, ("key",))
         flags["checked"] = self._split_flags(f, self._ks_layout(bool(self.plain_modulus)), base=lay["checked"])
         return o0, o1, flags
+
+    # ---- sealed inverse NTT: the input limbs verified on the opening transform's own load (ntt_sealed.hip) ----
+    def apply_sealed_in_layout(self):
+        """``{"c": (offset, (L,)), "key": (offset, (dnum, 2, M)), "checked": offset, "total": n, "fused": bool}`` of
+        ``apply_sealed_in``'s flag buffer; the checked block is laid out as ``checked_layout`` (``bgv_checked_layout`` with a plain
+        modulus)."""
+        out = (C.c_int * 5)()
+        check(lib.fhe_keyswitch_sealed_in_layout(self._h, out))
+        return {"c": (int(out[0]), (self.L,)), "key": (int(out[1]), (self.dnum, 2, self.L + self.K)), "checked": int(out[2]), "total": int(out[3]),
+                "fused": bool(out[4])}
+
+    def apply_sealed_in(self, c: DeviceArray, evk: DeviceArray, abft: "Abft", c_seal: DeviceArray, key_seal: Optional[DeviceArray] = None,
+                        add0: Optional[DeviceArray] = None, add1: Optional[DeviceArray] = None, stream=None):
+        """``apply_sealed`` with the input limbs sealed as well: ``(out0, out1, flags)``, ``flags = {"c": [L], "key": [dnum][2][M],
+        "checked": {...}}``.  Stage 0 makes no copy of ``c``: the opening inverse transform reads ``c`` itself, digests every word
+        from the register its first step holds and is held against ``c_seal`` (from ``NttTables.seal``; required).  The words are
+        ``apply``'s.  Not covered: the inner product's own load of ``c`` and of the plan's digits."""
+        lay = self.apply_sealed_in_layout()
+        o0, o1 = self._out(self.L), self._out(self.L)
+        f = _checked_flags(self.eng, lay["total"], lambda fl: lib.fhe_keyswitch_apply_sealed_in(
+            self.eng._h, self._h, o0.ptr, o1.ptr, c.ptr, evk.ptr, add0.ptr if add0 is not None else None, add1.ptr if add1 is not None else None,
+            abft._h, c_seal.ptr if c_seal is not None else None, key_seal.ptr if key_seal is not None else None, fl.ptr, stream), stream)
+        flags = self._split_flags(f, lay, ("c", "key"))
+        flags["checked"] = self._split_flags(f, self._ks_layout(bool(self.plain_modulus)), base=lay["checked"])
+        return o0, o1, flags
+
+    def rotate_sealed_in_layout(self):
+        """``{"c0", "c1", "sigma_c1": (offset, (L,)), "key": (offset, (dnum, 2, M)), "checked": offset, "total": n, "fused": bool}``
+        of ``rotate_sealed_in``'s flag buffer."""
+        out = (C.c_int * 7)()
+        check(lib.fhe_rotate_sealed_in_layout(self._h, out))
+        lay = {name: (int(out[i]), (self.L,)) for i, name in enumerate(("c0", "c1", "sigma_c1"))}
+        lay.update({"key": (int(out[3]), (self.dnum, 2, self.L + self.K)), "checked": int(out[4]), "total": int(out[5]), "fused": bool(out[6])})
+        return lay
+
+    def rotate_sealed_in(self, c0: DeviceArray, c1: DeviceArray, galois_elt: int, galois_key: DeviceArray, abft: "Abft", seals,
+                         key_seal: Optional[DeviceArray] = None, stream=None):
+        """``rotate_sealed_fused`` without the sweeps over c0 and c1 and without the unchecked permutation: ``(out0, out1, (seal0,
+        seal1), flags)``, ``flags = {"c0", "c1", "sigma_c1": [L], "key": [dnum][2][M], "checked": {...}}``.  c0 and c1 (``seals`` =
+        their seals, both required) are verified on the sealed permutation's gather, sigma(c1)'s seal is written from the registers
+        that are stored, and the opening inverse transform verifies sigma(c1) against it on its own load.  The words are
+        ``rotate``'s.  Not covered: sigma(c0), which the tail re-reads from the plan; the inner product's own loads."""
+        names = ("c0", "c1")
+        lay = self.rotate_sealed_in_layout()
+        o0, o1, so, f = self._sealed(lay, names, self.L, seals, lambda o0, o1, sin, sout, fl: lib.fhe_rotate_sealed_in(
+            self.eng._h, self._h, o0.ptr, o1.ptr, c0.ptr, c1.ptr, galois_elt, galois_key.ptr, abft._h, sin,
+            key_seal.ptr if key_seal is not None else None, sout, fl.ptr, stream), stream)
+        flags = self._split_flags(f, lay, ("c0", "c1", "sigma_c1", "key"))
+        flags["checked"] = self._split_flags(f, self._ks_layout(bool(self.plain_modulus)), base=lay["checked"])
+        return o0, o1, so, flags
 
     def rotate_sealed_fused(self, c0: DeviceArray, c1: DeviceArray, galois_elt: int, galois_key: DeviceArray, abft: "Abft", seals=None,
                             key_seal: Optional[DeviceArray] = None, stream=None):

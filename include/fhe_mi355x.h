@@ -1213,6 +1213,64 @@ int fhe_rotate_hoisted_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *const *d
                               uint64_t *const *d_seal_out0, uint64_t *const *d_seal_out1, uint32_t *d_flags, void *stream);
 int fhe_ctx_inject_fault_galois_sealed(fhe_ctx *ctx, int rot, int point, int row, long long coeff, int bit);
 
+/* ---- sealed inverse NTT: the input limbs of a key switch verified on the transform's own load --------------------------------
+ * fhe_keyswitch_apply_sealed does not seal d_c, and the sealed rotations sweep c0 and c1 and then move them through the unchecked
+ * permutation: the verifying sweep, the copy into the plan's coefficient buffer and the opening inverse transform's load are
+ * separate loads.  A word that is wrong on the copy's load or on the transform's own load passes the seal and is a consistent input
+ * of the ABFT identity (the input-side sum is formed from the word as loaded): a wrong result and no flag.  Here the first launch of
+ * the checked inverse transform digests every raw 64-bit word its first register step takes -- the sums of fhe_seal, modulo
+ * 2^61 - 1, weight = index in the row plus one, and the window word < q_l -- before the word is converted and enters the
+ * butterflies, and a finish launch holds each row's two sums word for word against the stored seal.
+ *
+ * fhe_ntt_inverse_sealed: d_dst = the words of fhe_ntt_inverse_batch over d_src's rows [n_poly][limbs] of table limbs start_idx ..,
+ * bit for bit; d_dst == d_src is allowed (in place), otherwise the transform is out of place with no copy and d_src is only read.
+ * d_seal_src ([rows][2], fhe_seal's; NULL: not compared, the window still is).  d_flags [2][rows], cleared by the call: block 0 the
+ * seal verdict per row with fhe_seal_verify's bits (1 the row as the transform loaded it is not the row that was sealed, or a
+ * stored sum is not canonical; 2 a word >= q_l), block 1 fhe_ntt_inverse_checked's flag.  A raised seal flag does not stop the
+ * call: the words are then the transform of the row as loaded.  Scope: fhe_ntt_inverse_checked's fused scope (N >= 2^5, not with
+ * ntt_mode=1, ntt_resident, ntt_packed or a single-pass hook), FHE_ERR_UNSUPPORTED with nothing launched outside it.  The call
+ * always runs whole-batch launches: a batch that fhe_ntt_inverse_checked would cut into sub-batches is NOT cut here.  It takes
+ * fhe_ctx_inject_fault's flip between the two launches as fhe_ntt_inverse_checked does (N >= 2^13; the index counts from d_dst).
+ *
+ * fhe_keyswitch_apply_sealed_in: fhe_keyswitch_apply_sealed with d_c sealed as well.  d_seal_c ([L][2], required: a NULL is refused,
+ * since nothing would verify the input -- the refused call still takes an armed hook) comes before d_seal_key.  Stage 0 is: no
+ * copy, the sealed inverse out of place from d_c into the plan's coefficient buffer; its ABFT verdict goes where stage 0's goes,
+ * its seal verdict to the c rows.  Flags, cleared by the call:
+ *     [c rows L][key rows dnum 2 M][the checked key switch's own block, exactly its layout]
+ * fhe_keyswitch_sealed_in_layout: out = {0, offset of the key rows = L, offset of the checked block, total, 1 if the key takes the
+ * fused route}.  CKKS or BGV form by the plan's plain modulus; the words are fhe_keyswitch_apply's.  Refusals as
+ * fhe_keyswitch_apply_sealed's, with nothing launched and the flag buffer untouched.
+ *
+ * fhe_rotate_sealed_in: fhe_rotate_sealed_fused's arguments (d_seal_in = HOST [2] the seals of c0, c1, both required) with no sweep
+ * over c0 or c1 and no unchecked permutation: both go through the sealed Galois permutation (fhe_automorphism_ntt_sealed's
+ * kernel), c0 verified on the gather, c1 verified on the gather while sigma(c1)'s seal {carried S0, digested S1} is written into
+ * call scratch from the registers that are stored; stage 0 then verifies sigma(c1) against that seal on the transform's load.  The
+ * key is verified on the fused inner product, the outputs are sealed as in fhe_rotate_sealed.  Flags, cleared by the call:
+ *     [c0 rows L][c1 rows L][sigma(c1) rows L][key rows dnum 2 M][the checked key switch's own block]
+ * fhe_rotate_sealed_in_layout: out = {offsets of the c0 rows, c1 rows, sigma(c1) rows, key rows, checked block, total, 1 if the key
+ * takes the fused route}.  A c1 word corrupted at rest raises c1's row and, through the carried S0, sigma(c1)'s row.  The words are
+ * fhe_rotate's.
+ *
+ * Not covered: the inner product's own load of the input limbs d_c and of the digits (ext); sigma(c0), which the tail re-reads
+ * from the plan; hoisted rotations and the BSGS product (their front half can take the same step later); sharded plans; repair;
+ * sub-batched streaming batches.
+ *
+ * Test hook: fhe_ctx_inject_fault_ntt_sealed(row, coeff, bit), a negative row clears; taken, one shot and whatever the outcome, by
+ * the next of the three calls above (row = a row of the transform: of d_src, of d_c, of sigma(c1)).  The bit of that word is flipped
+ * in the register as loaded, before window, digest and conversion; memory stays clean.  A row or coeff outside the call that takes
+ * it makes that call return FHE_ERR_INVALID with nothing launched.  Calls that do not run the sealed transform do not take it. */
+int fhe_ntt_inverse_sealed(fhe_ctx *ctx, uint64_t *d_dst, const uint64_t *d_src, const fhe_ntt_tables *t, const fhe_abft *a, size_t n_poly,
+                           size_t limbs, size_t start_idx, const uint64_t *d_seal_src, uint32_t *d_flags, void *stream);
+int fhe_ctx_inject_fault_ntt_sealed(fhe_ctx *ctx, int row, long long coeff, int bit);
+int fhe_keyswitch_sealed_in_layout(const fhe_keyswitch *p, int out[5]);
+int fhe_keyswitch_apply_sealed_in(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk,
+                                  const uint64_t *d_add0, const uint64_t *d_add1, const fhe_abft *a, const uint64_t *d_seal_c,
+                                  const uint64_t *d_seal_key, uint32_t *d_flags, void *stream);
+int fhe_rotate_sealed_in_layout(const fhe_keyswitch *p, int out[7]);
+int fhe_rotate_sealed_in(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0, const uint64_t *d_c1,
+                         uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, const uint64_t *const *d_seal_in,
+                         const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream);
+
 /* ---- fault injection ---------------------------------------------------------------- */
 /* _flip_bit_kernel<<<1,1>>> (reliability_test/dotprod_test.cu:31-33,55): data[idx] ^= 1 << bit */
 int fhe_flip_bit(fhe_ctx *ctx, uint64_t *d_data, uint64_t idx, int bit, void *stream);

@@ -1,0 +1,174 @@
+// emu_ntt_seal.cpp -- CPU emulation of the sealed inverse transform's first launch (TEST INFRASTRUCTURE ONLY).
+//
+// Compiles fhe_reliability_gpu_amd/csrc/ntt_seal_tap.hpp together with ntt_core.hpp / ntt_plan.hpp with g++ and runs the first
+// launch of the checked inverse (the inverse row pass of the two-launch sizes, the single pass below 2^13) tile by tile, thread by
+// thread, with SealInTap -- the very pass templates and the very tap k_ntt_pass_sealed instantiates -- out of place from a source
+// array, so that the digest, the window, the hook and the words can be checked without a GPU.  The library never links this file.
+//
+//   g++ -O2 -std=c++17 -ffp-contract=off -shared -fPIC -I<csrc> emu_ntt_seal.cpp -o libemu_ntt_seal.so
+#include "ntt_plan.hpp"
+#include "ntt_seal_tap.hpp"
+
+#include <type_traits>
+#include <vector>
+
+using namespace fhe;
+
+namespace {
+
+u64 invmod(u64 a, u64 m)
+{
+    __int128 t = 0, nt = 1, r = m, nr = a % m;
+    while (nr != 0) {
+        __int128 q = r / nr, tmp;
+        tmp = t - q * nt; t = nt; nt = tmp;
+        tmp = r - q * nr; r = nr; nr = tmp;
+    }
+    if (t < 0) t += m;
+    return (u64)t;
+}
+
+// the tables and limb constants of one limb, laid out as the library uploads them (capi.cpp build_tables)
+struct Limb {
+    LimbParams p;
+    std::vector<Tw> fwd, inv, win, wout;
+    std::vector<u64> wout8;
+    Limb(int logn, u64 q, const u64 *rp, const u64 *w_hat, int path)
+    {
+        const size_t N = (size_t)1 << logn;
+        auto enc = [&](u64 w) { return path == PATH_F64 ? ArithF64::encode(w, q) : ArithU64::encode(w, q); };
+        fwd.resize(N);
+        inv.resize(N);
+        for (size_t k = 0; k < N; k++) {
+            const u32 at = tw_stored_index(logn, (u32)k);
+            fwd[at] = enc(rp[k]);
+            inv[at] = enc(invmod(rp[k], q));
+        }
+        const u64 ni = invmod(N % q, q);
+        inv[0] = enc((u64)((unsigned __int128)ni * invmod(rp[N > 1 ? 1 : 0], q) % q));
+        const u64 p2 = (u64)1 << (logn / 2);
+        win.resize(N);
+        wout.resize(N);
+        wout8.assign(w_hat, w_hat + N);
+        for (size_t i = 0; i < N; i++) {
+            win[i] = enc(((i % p2 + 1) + (i / p2 + 1)) % q);
+            wout[i] = enc(w_hat[i]);
+        }
+        p.q = q;
+        p.two_q = 2 * q;
+        p.n = (double)q;
+        p.ninv = 1.0 / p.n;
+        const unsigned __int128 ratio = ~(unsigned __int128)0 / q;     // floor(2^128 / q), q odd
+        p.barrett_lo = (u64)ratio;
+        p.barrett_hi = (u64)(ratio >> 64);
+        p.inv_n = enc(ni);
+        p.fwd = fwd.data();
+        p.inv = inv.data();
+        p.path = path;
+    }
+};
+
+// every phase of one tile, thread by thread, loading from `from`
+template <class PASS, class TAP>
+void run_tile(u64 *base, const u64 *from, typename PASS::elem *lds, TwPtr tw, u32 row0, const typename PASS::Arith::Ctx &ctx, const Tw &inv_n, TAP *t)
+{
+    auto run = [&](auto e) {
+        constexpr int E = decltype(e)::value;
+        if constexpr (E < PASS::NPHASE) {
+            for (int tid = 0; tid < PASS::THREADS; tid++) PASS::template phase<E>(tid, base, lds, tw, row0, ctx, inv_n, t, from);
+        }
+    };
+    run(std::integral_constant<int, 0>());
+    run(std::integral_constant<int, 1>());
+    run(std::integral_constant<int, 2>());
+    run(std::integral_constant<int, 3>());
+    run(std::integral_constant<int, 4>());
+}
+
+// mode 0: no tap; 1: SealInTap (hooked when hit_coeff >= 0); 2: InvChecksumTap (the checked inverse's own first launch)
+template <class PASS, int LOGN, bool OUT>
+int emu_first(const u64 *src, u64 *dst, const Limb &L, int mode, long long hit_coeff, int hit_bit, u64 *parts, u64 *sum_in)
+{
+    typedef typename PASS::Arith A;
+    PassArgs a{dst, &L.p, 0u, 1u, 1u, 1u};
+    std::vector<typename PASS::elem> lds(PASS::LDS_ELEMS > 0 ? PASS::LDS_ELEMS : 1);
+    const auto ctx = A::make_ctx(L.p);
+    const TwPtr tw = as_global(L.p.inv);
+    *sum_in = 0;
+    for (u32 b = 0; b < PASS::TILES; b++) {
+        u32 limb, row0 = 0;
+        u64 *base = row_tile<PASS, LOGN>(b, a, limb, row0);
+        const u32 pos0 = (u32)(base - dst);
+        const u64 *from = src + pos0;
+        if (mode == 0) {
+            run_tile<PASS, NoTap>(base, from, lds.data(), tw, row0, ctx, L.p.inv_n, nullptr);
+        } else if (mode == 2) {
+            InvChecksumTap<A, true, OUT> tap{L.win.data() + pos0, L.wout.data() + pos0, L.wout8.data() + pos0, pos0, LOGN / 2, typename A::elem(0), typename A::elem(0), 0, 0};
+            run_tile<PASS>(base, from, lds.data(), tw, row0, ctx, L.p.inv_n, &tap);
+            *sum_in = (*sum_in + A::canonical(tap.acc_in, ctx)) % L.p.q;
+        } else {
+            auto tapped = [&](auto hook) {
+                constexpr bool HOOK = decltype(hook)::value;
+                const u32 hit_idx = HOOK && (u64)hit_coeff - pos0 < (u64)(PASS::TROWS * PASS::NPTS) ? (u32)hit_coeff - pos0 : NTT_SEAL_NO_HIT;
+                SealInTap<A, HOOK, OUT> tap{{L.win.data() + pos0, L.wout.data() + pos0, L.wout8.data() + pos0, pos0, LOGN / 2, typename A::elem(0), typename A::elem(0), 0, 0},
+                                            SealAcc{}, 0u, L.p.q, hit_idx, (u64)1 << hit_bit};
+                run_tile<PASS>(base, from, lds.data(), tw, row0, ctx, L.p.inv_n, &tap);
+                *sum_in = (*sum_in + A::canonical(tap.acc_in, ctx)) % L.p.q;
+                parts[NTT_SEAL_PART * b] = tap.seal.s0;
+                parts[NTT_SEAL_PART * b + 1] = tap.seal.s1;
+                parts[NTT_SEAL_PART * b + 2] = tap.n_range;
+            };
+            if (hit_coeff >= 0) tapped(std::true_type());
+            else tapped(std::false_type());
+        }
+    }
+    return (int)PASS::TILES;
+}
+
+template <class A, int LOGN>
+int emu_size(const u64 *src, u64 *dst, const Limb &L, int mode, long long hit_coeff, int hit_bit, u64 *parts, u64 *sum_in)
+{
+    typedef Passes<A, LOGN, true, (LOGN >= 13 ? 1 : 0)> PS;
+    if constexpr (!PS::G::TWO_PASS) return emu_first<typename PS::Single, LOGN, true>(src, dst, L, mode, hit_coeff, hit_bit, parts, sum_in);
+    else return emu_first<typename PS::Row, LOGN, false>(src, dst, L, mode, hit_coeff, hit_bit, parts, sum_in);
+}
+
+template <class A>
+int dispatch(int logn, const u64 *src, u64 *dst, const Limb &L, int mode, long long hit_coeff, int hit_bit, u64 *parts, u64 *sum_in)
+{
+    switch (logn) {
+#define CASE(LG) case LG: return emu_size<A, LG>(src, dst, L, mode, hit_coeff, hit_bit, parts, sum_in);
+        CASE(5) CASE(10) CASE(13) CASE(14)
+#undef CASE
+    default: return -1;
+    }
+}
+
+} // namespace
+
+// The first launch of the checked inverse of one limb-polynomial, out of place from src into dst (the lazy words it hands to the
+// column pass; below 2^13 the transform's final words).  Returns the number of tiles (parts = [tiles][3] lazily reduced {S0, S1,
+// n_range}, mode 1 only), or -1.  rp = forward table (entry k = psi^bitrev(k)), w_hat = the ABFT input-side weights as residues.
+extern "C" int emu_ntt_seal_first(const u64 *src, u64 *dst, int logn, u64 q, const u64 *rp, const u64 *w_hat, int path, int mode, long long hit_coeff, int hit_bit,
+                                  u64 *parts, u64 *sum_in)
+{
+    const Limb L(logn, q, rp, w_hat, path);
+    return path == PATH_F64 ? dispatch<ArithF64>(logn, src, dst, L, mode, hit_coeff, hit_bit, parts, sum_in)
+                            : dispatch<ArithU64>(logn, src, dst, L, mode, hit_coeff, hit_bit, parts, sum_in);
+}
+
+// k_ntt_seal_finish for one row: the tiles' partials merged in the order given, made canonical into got[2], and the verdict
+// against `stored` (may be null)
+extern "C" unsigned emu_ntt_seal_finish(const u64 *parts, int tiles, const int *order, const u64 *stored, u64 *got)
+{
+    SealAcc acc;
+    u64 nr = 0;
+    for (int i = 0; i < tiles; i++) {
+        const u64 *p = parts + (size_t)NTT_SEAL_PART * order[i];
+        acc.merge(p[0], p[1]);
+        nr += p[2];
+    }
+    got[0] = seal_canonical(acc.s0);
+    got[1] = seal_canonical(acc.s1);
+    return ntt_seal_verdict(acc, nr, stored);
+}
