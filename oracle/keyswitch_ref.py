@@ -171,7 +171,11 @@ def rescale_ref(parts, qs, L, logn, plain_modulus=0):
 
 
 def hmult_ref(a0, a1, b0, b1, rlk, qs, L, K, dnum, logn, rescale=True, plain_modulus=0):
-    """multiply -> relinearize -> mod_switch_to_next (dotprod_test.cu:113-115)."""
+    """multiply -> relinearize -> mod_switch_to_next (dotprod_test.cu:113-115).
+    plain_modulus reaches the RESCALE ONLY: the relinearisation's mod-down stays in the CKKS form (delta = [acc]_P).  With a plain
+    modulus this is therefore NOT the multiply of a BGV plan -- it does not decrypt to m1 m2 modulo t
+    (tests/test_rlwe_helper.py::test_hmult_ref_with_a_plain_modulus_fails_the_product_property); the BGV reference is
+    tensor_ref -> keyswitch_ref(plain_modulus=t) -> rescale_ref(plain_modulus=t).  Kept as it is: other tests pin its words."""
     d0, d1, d2 = tensor_ref(a0, a1, b0, b1, qs)
     c0, c1 = keyswitch_ref(d2, rlk, qs, L, K, dnum, logn, add0=d0, add1=d1)
     if not rescale:
