@@ -5,8 +5,8 @@
 // consistent operand to the residue identity of bsgs_check.hpp: no flag, wrong product.  The inner sum loads every diagonal word
 // exactly once, so its seal (seal_check.hpp: S0 = sum x_j, S1 = sum (j + 1) x_j modulo p = 2^61 - 1, and the window x_j < q) is
 // digested from the very register that is then handed to DiagDot::mac -- no second sweep, and the verified load IS the consuming
-// load.  Per giant step g and limb row l a lane keeps one SealAcc per baby step b < n1; a row's digests are held against the
-// stored seal seal_diag[(g n1 + b) L + l] after the sweep (diag_seal_decide).
+// load.  Per giant step g and limb row l a lane keeps one SealAcc per baby step b < n1 (SealRows<NB>); a row's digests are held
+// against the stored seal seal_diag[(g n1 + b) L + l] after the sweep (seal_differs).
 //
 // The arithmetic is k_diag_mac_checked's, unchanged: DiagDot<KsDotU64 / KsDotF64> over the same terms in the same order, folds
 // after every eighth term, the same four fault points and residue flags; the words are fhe_bsgs_matvec's bit for bit.  The b loop
@@ -18,8 +18,6 @@
 // residue check then raises PW_OPERAND on both parts as before).  Integer arithmetic modulo p throughout: no digest depends on how
 // a row is cut into chunks, lanes or waves.
 #pragma once
-#include <type_traits>
-
 #include "bsgs_check.hpp"
 #include "seal_check.hpp"
 
@@ -35,31 +33,16 @@ struct DiagHit {
     u64 coeff, mask;
 };
 
-// f(integral_constant<int, B>) for B = 0 .. NB - 1, unrolled by the template and not by the optimiser: the accumulators below are
-// then indexed by constants whatever the size of the loop body, and never leave the registers
-template <int B, int NB, class F> FHE_HD void diag_seal_each(F &&f)
-{
-    if constexpr (B < NB) {
-        f(std::integral_constant<int, B>{});
-        diag_seal_each<B + 1, NB>(f);
-    }
-}
-
-// what one lane (one chunk, one row) has digested: the two sums of every diagonal row b < NB and the window bits
-template <int NB> struct DiagSeal {
-    SealAcc acc[NB];
-    u32 range = 0;      // bit b: a word of diagonal b was >= q
-};
-
 // Two adjacent words j, j + 1 of limb row p: ld(b, d, y0, y1) loads the diagonal words of baby step b and the words of both parts
-// of the b-th rotated ciphertext.  Digests every diagonal word, forms the two words of each part (c0, c1) and ORs their residue
-// flags into fl0 / fl1.  f0 / f1 = the checked call's test fault for word j and word j + 1 of part 0 / part 1.
+// of the b-th rotated ciphertext.  Digests every diagonal word into g (row b = diagonal b < NB), forms the two words of each part
+// (c0, c1) and ORs their residue flags into fl0 / fl1.  f0 / f1 = the checked call's test fault for word j and word j + 1 of part
+// 0 / part 1.
 template <class D, int NB, bool HOOK, class LD>
-FHE_HD void diag_seal_pair(DiagSeal<NB> &g, u32 n1, u32 j, const LimbParams &p, const LD &ld, const DiagHit &hit, const PwFault *f0, const PwFault *f1, u64 *c0,
+FHE_HD void diag_seal_pair(SealRows<NB> &g, u32 n1, u32 j, const LimbParams &p, const LD &ld, const DiagHit &hit, const PwFault *f0, const PwFault *f1, u64 *c0,
                            u64 *c1, u32 &fl0, u32 &fl1)
 {
     DiagDot<D> sx, sy;
-    diag_seal_each<0, NB>([&](auto bc) {
+    seal_each<0, NB>([&](auto bc) {
         constexpr int b = decltype(bc)::value;
         if ((u32)b < n1) {
             u64 d[2], y0[2], y1[2];
@@ -82,8 +65,8 @@ FHE_HD void diag_seal_pair(DiagSeal<NB> &g, u32 n1, u32 j, const LimbParams &p, 
     fl1 |= x1 | z1;
 }
 
-// what the finish step decides for one diagonal row: s0 / s1 = its lazily reduced digests, stored = the seal as it lies in memory.
-// True where the row raises SEAL_SUM; a stored sum is held word for word, so one that is not canonical counts as moved (seal_decide)
-FHE_HD bool diag_seal_decide(u64 s0, u64 s1, const u64 *stored) { return seal_canonical(s0) != stored[0] || seal_canonical(s1) != stored[1]; }
+// the names tests/emu/emu_bsgs_seal.cpp knows the record and the finish step's decision by
+template <int NB> using DiagSeal = SealRows<NB>;
+FHE_HD bool diag_seal_decide(u64 s0, u64 s1, const u64 *stored) { return seal_differs(s0, s1, stored); }
 
 } // namespace fhe

@@ -1,13 +1,13 @@
 // bsgs_sealed.hip -- the inner sum of the BSGS product with the diagonals' seals verified on the load that feeds the product
 // (bsgs_seal.hpp): fhe_bsgs_matvec_sealed.  A translation unit of its own, so that every other kernel compiles exactly as before.
 //
-// k_diag_mac_sealed is k_diag_mac_checked (bsgs_checked.hip) in the shape of k_modadd_carry (seal_carry.hip): a limb row of 2^logn
-// words is cut into chunks of 2^SEAL_LOG_CHUNK words and the (row, chunk) jobs are spread over a 1-D grid.  A lane takes two words
-// per step with 16-byte loads of the diagonal and of both parts of every rotated ciphertext, digests each diagonal word from the
-// register it then hands to DiagDot::mac, with the weight of its index in the ROW, and stores the two words of each part.  The b
-// loop is inside the element loop and unrolled to NB, so a lane's NB SealAcc stay in registers.  After the job the NB pairs of sums
-// combine through wave shuffles and LDS into one integer partial part[job][b][2]; a job that saw a word >= q ORs SEAL_RANGE into
-// the (b, l) flag with a global atomic.  A clean run stores nothing beyond the partials.
+// k_diag_mac_sealed runs the chunked sweep of seal_sweep.hpp (job loop, workgroup combine, launch) over limb rows, with
+// k_diag_mac_checked's arithmetic (bsgs_checked.hip).  Per word: a lane takes two words per step with 16-byte loads of the
+// diagonal and of both parts of every rotated ciphertext, digests each diagonal word from the register it then hands to
+// DiagDot::mac, with the weight of its index in the ROW, and stores the two words of each part.  The b loop is inside the element
+// loop and unrolled to NB, so a lane's NB SealAcc stay in registers.  The job's partial is part[job][b][2], b < n1 (LDS per
+// workgroup: 272, 528 and 1040 bytes at NB = 4, 8, 16); a job that saw a word >= q ORs SEAL_RANGE into the (b, l) flag with a
+// global atomic.  A clean run stores nothing beyond the partials.
 //
 // k_diag_seal_finish, one lane per (b, l): adds the row's partials, makes them canonical and holds them word for word against the
 // stored seal; a difference ORs SEAL_SUM.
@@ -15,8 +15,8 @@
 // Integer arithmetic modulo 2^61 - 1 in the digest: no floating point there, no scratch memory, vector stores only.  HOOK: the
 // checked call's one-shot fault (BcCheck, the four points of bsgs_check.hpp) and the sealed call's own (DiagHit: one bit of one
 // diagonal word in the register as loaded); memory stays clean.
-#include "checked_kernel.hpp"
 #include "bsgs_seal.hpp"
+#include "seal_sweep.hpp"
 
 namespace fhe {
 
@@ -24,7 +24,7 @@ size_t diag_seal_part_words(u32 limbs, int logn, u32 nb) { return ((size_t)limbs
 
 // one (row, chunk) job of one arithmetic path: words [j0, j0 + words) of limb row l
 template <class D, int NB, bool HOOK>
-__device__ __forceinline__ void diag_seal_job(const DiagMacArgs &a, const BcCheck &k, const DiagHit &hit, u32 l, u32 j0, u32 words, DiagSeal<NB> &g)
+__device__ __forceinline__ void diag_seal_job(const DiagMacArgs &a, const BcCheck &k, const DiagHit &hit, u32 l, u32 j0, u32 words, SealRows<NB> &g)
 {
     const LimbParams &p = a.lp[a.limb0 + l];
     const u64 part = (u64)a.limbs << a.logn;
@@ -60,45 +60,17 @@ __device__ __forceinline__ void diag_seal_job(const DiagMacArgs &a, const BcChec
 template <int NB, bool HOOK>
 __global__ __launch_bounds__(256) void k_diag_mac_sealed(DiagMacArgs a, BcCheck k, u64 *part, u32 *seal_flags, DiagHit hit)
 {
-    __shared__ u64 sh[4][NB][2];
-    __shared__ u32 shr[4];
-    const int lchunks = seal_log_chunks(a.logn);
-    const u32 words = 1u << (a.logn - lchunks);
-    const u32 jobs = a.limbs << lchunks;
-    for (u32 job = blockIdx.x; job < jobs; job += gridDim.x) {
-        const u32 l = job >> lchunks, chunk = job & ((1u << lchunks) - 1);
-        DiagSeal<NB> g;
-        if (a.lp[a.limb0 + l].path == PATH_F64) diag_seal_job<KsDotF64, NB, HOOK>(a, k, hit, l, chunk * words, words, g);
-        else diag_seal_job<KsDotU64, NB, HOOK>(a, k, hit, l, chunk * words, words, g);
-        for (int o = 32; o; o >>= 1) {
-            diag_seal_each<0, NB>([&](auto bc) {
-                constexpr int b = decltype(bc)::value;
-                g.acc[b].merge(__shfl_xor(g.acc[b].s0, o), __shfl_xor(g.acc[b].s1, o));
-            });
-            g.range |= __shfl_xor(g.range, o);
-        }
-        if ((threadIdx.x & 63) == 0) {
-            diag_seal_each<0, NB>([&](auto bc) {
-                constexpr int b = decltype(bc)::value;
-                sh[threadIdx.x >> 6][b][0] = g.acc[b].s0;
-                sh[threadIdx.x >> 6][b][1] = g.acc[b].s1;
-            });
-            shr[threadIdx.x >> 6] = g.range;
-        }
-        __syncthreads();
+    const SealJobs s(a.limbs, a.logn);
+    for (u64 job = blockIdx.x; job < s.jobs; job += gridDim.x) {
+        const u32 l = s.unit(job);
+        SealRows<NB> g;
+        if (a.lp[a.limb0 + l].path == PATH_F64) diag_seal_job<KsDotF64, NB, HOOK>(a, k, hit, l, s.j0(job), s.words, g);
+        else diag_seal_job<KsDotU64, NB, HOOK>(a, k, hit, l, s.j0(job), s.words, g);
+        const u32 range = seal_block_combine<true>(g, part + job * NB * 2, g.range, 2 * a.n1);      // the rows b >= n1 stay unwritten
         if (threadIdx.x == 0) {
-            const u32 range = g.range | shr[1] | shr[2] | shr[3];
-            diag_seal_each<0, NB>([&](auto bc) {
-                constexpr int b = decltype(bc)::value;
-                if ((u32)b < a.n1) {
-                    for (int w = 1; w < 4; w++) g.acc[b].merge(sh[w][b][0], sh[w][b][1]);
-                    part[((size_t)job * NB + b) * 2] = g.acc[b].s0;
-                    part[((size_t)job * NB + b) * 2 + 1] = g.acc[b].s1;
-                    if (range >> b & 1) atomicOr(seal_flags + (size_t)b * a.limbs + l, (u32)SEAL_RANGE);
-                }
-            });
+            for (u32 b = 0; b < a.n1; b++)
+                if (range >> b & 1) atomicOr(seal_flags + (size_t)b * a.limbs + l, (u32)SEAL_RANGE);
         }
-        __syncthreads();      // sh is reused by the next job
     }
 }
 
@@ -108,12 +80,8 @@ __global__ __launch_bounds__(256) void k_diag_seal_finish(const u64 *part, u32 n
     const u32 units = n1 * limbs;
     for (u32 u = blockIdx.x * blockDim.x + threadIdx.x; u < units; u += gridDim.x * blockDim.x) {
         const u32 b = u / limbs, l = u % limbs;
-        SealAcc s;
-        for (u32 c = 0; c < chunks; c++) {
-            const u64 *pj = part + (((size_t)l * chunks + c) * nb + b) * 2;
-            s.merge(pj[0], pj[1]);
-        }
-        if (diag_seal_decide(s.s0, s.s1, seal + 2 * (size_t)u)) atomicOr(flags + u, (u32)SEAL_SUM);
+        const SealAcc s = seal_merge_partials<SealAcc>(part + ((size_t)l * chunks * nb + b) * 2, chunks, (size_t)nb * 2);
+        if (seal_differs(s.s0, s.s1, seal + 2 * (size_t)u)) atomicOr(flags + u, (u32)SEAL_SUM);
     }
 }
 
@@ -122,15 +90,11 @@ namespace {
 template <int NB>
 hipError_t launch_sealed(hipStream_t st, const DiagMacArgs &a, u64 *part, const u64 *seal, u32 *seal_flags, const BcCheck &k, const DiagHit &hit)
 {
-    const u32 chunks = 1u << seal_log_chunks(a.logn);
-    const dim3 grid(checked_grid((u64)a.limbs * chunks * 256, 8192));
-    hipLaunchKernelGGL((k.fault_point >= 0 || hit.mask ? k_diag_mac_sealed<NB, true> : k_diag_mac_sealed<NB, false>), grid, dim3(256), 0, st, a, k, part, seal_flags,
-                       hit);
-    hipError_t e = hipGetLastError();
+    // either hook selects the hooked form
+    hipError_t e = launch_seal_sweep(k_diag_mac_sealed<NB, false>, k_diag_mac_sealed<NB, true>, k.fault_point >= 0 || hit.mask != 0, a.limbs, a.logn, st, a, k, part,
+                                     seal_flags, hit);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_diag_seal_finish, dim3(checked_grid((u64)a.n1 * a.limbs, 1024)), dim3(256), 0, st, (const u64 *)part, a.n1, a.limbs, chunks, (u32)NB, seal,
-                       seal_flags);
-    return hipGetLastError();
+    return launch_seal_finish(k_diag_seal_finish, (u64)a.n1 * a.limbs, st, (const u64 *)part, a.n1, a.limbs, 1u << seal_log_chunks(a.logn), (u32)NB, seal, seal_flags);
 }
 
 } // namespace

@@ -25,12 +25,19 @@ inline u32 checked_grid(u64 total, u32 cap)
     return (u32)(want < 1 ? 1 : want > cap ? cap : want);
 }
 
-// launch `hooked` when k arms the test fault, `clean` otherwise: the same kernel at HOOK = true / false
+// launch `hooked` when a test fault is armed, `clean` otherwise: the same kernel at HOOK = true / false
+template <class... P, class... A>
+hipError_t launch_armed(void (*clean)(P...), void (*hooked)(P...), bool armed, dim3 grid, hipStream_t st, const A &...args)
+{
+    hipLaunchKernelGGL(armed ? hooked : clean, grid, dim3(256), 0, st, args...);
+    return hipGetLastError();
+}
+
+// the same where k's fault is the only one the kernel knows
 template <class... P, class... A>
 hipError_t launch_checked(void (*clean)(P...), void (*hooked)(P...), const BcCheck &k, dim3 grid, hipStream_t st, const A &...args)
 {
-    hipLaunchKernelGGL(k.fault_point >= 0 ? hooked : clean, grid, dim3(256), 0, st, args...);
-    return hipGetLastError();
+    return launch_armed(clean, hooked, k.fault_point >= 0, grid, st, args...);
 }
 
 } // namespace fhe

@@ -2,12 +2,12 @@
 // one gather a permutation makes (galois_seal.hpp): fhe_automorphism_ntt_sealed and the c0 rows of fhe_rotate_hoisted_sealed.  A
 // translation unit of its own, so that every other kernel compiles exactly as before.
 //
-// k_automorphism_ntt_sealed is k_modadd_carry (seal_carry.hip) with a gather inside: a row of 2^logn words is cut into chunks of
-// 2^SEAL_LOG_CHUNK DESTINATION words and the (row, chunk) jobs are spread over a 1-D grid.  A lane handles two adjacent destination
-// words per step: two scalar gathers through galois_slot (the source words of a chunk lie anywhere in the row), each word digested
-// from the register with its source weight and, with OUT, its destination weight, the window counted, and one 16-byte store.  The
-// job's sums {s0, s1_in, [s1_out], over} combine through wave shuffles and 96 or 128 bytes of LDS into one integer partial per job.
-// The source sums of a row exist only once all its chunks are merged; that merge is why a finish launch is needed.
+// k_automorphism_ntt_sealed runs the chunked sweep of seal_sweep.hpp (job loop, workgroup combine, launch) over chunks of
+// DESTINATION words.  Per word: a lane handles two adjacent destination words per step: two scalar gathers through galois_slot
+// (the source words of a chunk lie anywhere in the row), each word digested from the register with its source weight and, with
+// OUT, its destination weight, the window counted, and one 16-byte store.  The job's partial is {s0, s1_in, [s1_out], over}: 96 or
+// 128 bytes of LDS per workgroup.  The source sums of a row exist only once all its chunks are merged; that merge is why a finish
+// launch is needed.
 //
 // k_galois_seal_finish, one lane per row: adds the row's partials, holds the canonical (s0, s1_in) word for word against
 // seal_src[row] (SEAL_SUM), raises SEAL_RANGE where a word was >= q_l, and with OUT stores seal_dst[row] = {the STORED
@@ -20,10 +20,10 @@
 // fhe_ctx_inject_fault_galois_sealed, applied in registers (GAL_AT_WORD, GAL_AT_INDEX); memory stays clean.
 //
 // Resources (gfx950, -Rpass-analysis=kernel-resource-usage), clean / hooked: OUT = false 48 / 48 VGPRs and 96 bytes of LDS, OUT =
-// true 56 / 52 VGPRs and 128 bytes of LDS; k_galois_seal_finish 20 / 26 VGPRs (OUT = false / true); no scratch memory, no AGPRs and
+// true 50 / 48 VGPRs and 128 bytes of LDS; k_galois_seal_finish 20 / 26 VGPRs (OUT = false / true); no scratch memory, no AGPRs and
 // 8 waves per SIMD in every instantiation.
-#include "checked_kernel.hpp"
 #include "galois_seal.hpp"
+#include "seal_sweep.hpp"
 
 namespace fhe {
 
@@ -34,21 +34,16 @@ size_t galois_seal_part_words(u32 units, int logn, bool out) { return ((size_t)u
 template <bool OUT, bool HOOK>
 __global__ __launch_bounds__(256) void k_automorphism_ntt_sealed(GalSealArgs a, u64 *part, GalSealHit hit)
 {
-    constexpr int W = GalSealAcc<OUT>::WORDS;
-    __shared__ u64 sh[4][W];
-    const int lchunks = seal_log_chunks(a.logn);
-    const u32 words = 1u << (a.logn - lchunks);
-    const u64 jobs = (u64)a.units << lchunks;
-    for (u64 job = blockIdx.x; job < jobs; job += gridDim.x) {
-        const u32 unit = (u32)(job >> lchunks), chunk = (u32)(job & (((u64)1 << lchunks) - 1));
+    const SealJobs s(a.units, a.logn);
+    for (u64 job = blockIdx.x; job < s.jobs; job += gridDim.x) {
+        const u32 unit = s.unit(job), j0 = s.j0(job);
         const u32 poly = unit / a.limbs, l = unit % a.limbs;
         const u64 q = a.lp[a.limb0 + l].q;
         const u64 base = ((u64)poly * a.poly_stride + l) << a.logn;
         const u64 *src_row = a.src + base;
-        const u32 j0 = chunk * words;
         GalSealAcc<OUT> acc;
 #pragma unroll 4
-        for (u32 i = threadIdx.x * 2; i < words; i += 512) {
+        for (u32 i = threadIdx.x * 2; i < s.words; i += 512) {
             const u32 j = j0 + i;
             const u64 m0 = HOOK && unit == hit.row && j == hit.coeff ? hit.mask : 0, m1 = HOOK && unit == hit.row && j + 1 == hit.coeff ? hit.mask : 0;
             const bool word = !HOOK || hit.point == GAL_AT_WORD;
@@ -57,23 +52,7 @@ __global__ __launch_bounds__(256) void k_automorphism_ntt_sealed(GalSealArgs a, 
             c.y = galois_seal_step<OUT>(acc, src_row, j + 1, a.logn, a.k, q, word ? m1 : 0, word ? 0u : (u32)m1);
             *reinterpret_cast<ulonglong2 *>(a.dst + base + j) = c;
         }
-        for (int o = 32; o; o >>= 1) {
-            u64 other[W];
-#pragma unroll
-            for (int i = 0; i < W; i++) other[i] = __shfl_xor(acc.get(i), o);
-            acc.merge(other);
-        }
-        if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-            for (int i = 0; i < W; i++) sh[threadIdx.x >> 6][i] = acc.get(i);
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            for (int w = 1; w < 4; w++) acc.merge(sh[w]);
-#pragma unroll
-            for (int i = 0; i < W; i++) part[W * job + i] = acc.get(i);
-        }
-        __syncthreads();      // sh is reused by the next job
+        seal_block_combine<false>(acc, part + GalSealAcc<OUT>::WORDS * job);      // the window travels as a count, a word of acc
     }
 }
 
@@ -83,9 +62,7 @@ __global__ __launch_bounds__(256) void k_galois_seal_finish(const u64 *part, u32
 {
     constexpr int W = GalSealAcc<OUT>::WORDS;
     for (u32 u = blockIdx.x * blockDim.x + threadIdx.x; u < units; u += gridDim.x * blockDim.x) {
-        GalSealAcc<OUT> acc;
-        const u64 *pu = part + (size_t)u * chunks * W;
-        for (u32 c = 0; c < chunks; c++) acc.merge(pu + (size_t)c * W);
+        const GalSealAcc<OUT> acc = seal_merge_partials<GalSealAcc<OUT>>(part + (size_t)u * chunks * W, chunks);
         const u32 f = galois_seal_finish<OUT>(acc, seal_src + 2 * (size_t)u, OUT ? seal_dst + 2 * (size_t)u : nullptr);
         if (f) atomicOr(flags + u, f);
     }
@@ -96,15 +73,9 @@ namespace {
 template <bool OUT>
 hipError_t launch_gal_sealed(hipStream_t st, const GalSealArgs &a, u64 *part, const u64 *seal_src, u64 *seal_dst, u32 *flags, const GalSealHit &hit)
 {
-    const u32 chunks = 1u << seal_log_chunks(a.logn);
-    const dim3 grid(checked_grid((u64)a.units * chunks * 256, 8192));
-    if (hit.point >= 0) hipLaunchKernelGGL((k_automorphism_ntt_sealed<OUT, true>), grid, dim3(256), 0, st, a, part, hit);
-    else hipLaunchKernelGGL((k_automorphism_ntt_sealed<OUT, false>), grid, dim3(256), 0, st, a, part, hit);
-    hipError_t e = hipGetLastError();
+    hipError_t e = launch_seal_sweep(k_automorphism_ntt_sealed<OUT, false>, k_automorphism_ntt_sealed<OUT, true>, hit.point >= 0, a.units, a.logn, st, a, part, hit);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_galois_seal_finish<OUT>), dim3(checked_grid(a.units, 1024)), dim3(256), 0, st, (const u64 *)part, a.units, chunks, seal_src, seal_dst,
-                       flags);
-    return hipGetLastError();
+    return launch_seal_finish(k_galois_seal_finish<OUT>, a.units, st, (const u64 *)part, a.units, 1u << seal_log_chunks(a.logn), seal_src, seal_dst, flags);
 }
 
 } // namespace

@@ -2,14 +2,14 @@
 // (ks_seal.hpp): stage 3 of fhe_keyswitch_apply_sealed, fhe_rotate_sealed_fused and fhe_hmult_sealed_fused_key.  A translation
 // unit of its own, so that every other kernel compiles exactly as before.
 //
-// k_ks_mac_sealed is k_ks_mac_checked (keyswitch_checked.hip) in the shape of k_modadd_carry (seal_carry.hip): a row of 2^logn words
-// is cut into chunks of 2^SEAL_LOG_CHUNK words and the (row, chunk) jobs are spread over a 1-D grid.  A lane takes two words per
-// step with 16-byte loads of the digit (the owned limb of c or its extension) and of both key halves, the key non-temporal as in
-// ks_load_key because it is read once, digests each key word from the register it then hands to D::mac, with the weight of its
-// index in the ROW, and stores the two words of each half of the sums 16 bytes at a time.  The d loop is inside the element loop
-// and unrolled to ND, so a lane's 2 ND SealAcc stay in registers.  After the job the sums combine through wave shuffles and LDS
-// into one integer partial part[job][2 dnum][2]; a job that saw a key word >= q ORs SEAL_RANGE into that key row's flag, a lane
-// that saw a residue flag ORs it into the [2][M] words, both with global atomics.  A clean run stores nothing beyond the partials.
+// k_ks_mac_sealed runs the chunked sweep of seal_sweep.hpp (job loop, workgroup combine, launch) over the M rows, with
+// k_ks_mac_checked's arithmetic (keyswitch_checked.hip).  Per word: a lane takes two words per step with 16-byte loads of the
+// digit (the owned limb of c or its extension) and of both key halves, the key non-temporal as in ks_load_key because it is read
+// once, digests each key word from the register it then hands to D::mac, with the weight of its index in the ROW, and stores the
+// two words of each half of the sums 16 bytes at a time.  The d loop is inside the element loop and unrolled to ND, so a lane's
+// 2 ND SealAcc stay in registers.  The job's partial is part[job][2 dnum][2]; a job that saw a key word >= q ORs SEAL_RANGE into
+// that key row's flag, a lane that saw a residue flag ORs it into the [2][M] words, both with global atomics.  A clean run stores
+// nothing beyond the partials.
 //
 // k_ks_seal_finish, one lane per key row r = (d 2 + h) M + j: adds the row's partials, makes them canonical and holds them word for
 // word against the stored seal; a difference ORs SEAL_SUM.  Without a stored seal it is not launched: the window alone is checked.
@@ -21,10 +21,11 @@
 // Resources, gfx950, from the compiler's resource-usage remarks (-Rpass-analysis=kernel-resource-usage), VGPRs clean / hooked;
 // scratch memory is 0 bytes per lane in every instantiation:
 //   ND = 2: 108 / 117     ND = 4: 140 / 150     ND = 8: 235 / 236     ND = 12: 256 + 22 AGPRs / 256 + 34 AGPRs
-// (ND = 12, the band of dnum = 11, keeps its overflow in accumulation registers, not in memory; k_ks_seal_finish: 18).  The
-// compiler's static waves per SIMD are 4, 3, 2 and 1; what that costs on the device, and the speed of any band, is unmeasured.
-#include "checked_kernel.hpp"
+// (ND = 12, the band of dnum = 11, keeps its overflow in accumulation registers, not in memory; k_ks_seal_finish: 18).  LDS per
+// workgroup: 272, 528, 1040 and 1552 bytes.  The compiler's static waves per SIMD are 4, 3, 2 and 1; what that costs on the
+// device at ND = 8 and 12 is unmeasured.
 #include "ks_seal.hpp"
+#include "seal_sweep.hpp"
 
 namespace fhe {
 
@@ -44,7 +45,7 @@ __device__ __forceinline__ void ks_load_key2(const u64 *p, u64 *k)
 // one (row, chunk) job of one arithmetic path: words [i0, i0 + words) of row j
 template <class D, int ND, bool HOOK>
 __device__ __forceinline__ void ks_seal_job(const KsMacArgs &a, const BcCheck &k, const KsSealHit &hit, u32 j, u32 i0, u32 words, const LimbParams &p,
-                                            KsSeal<ND> &g)
+                                            SealRows<2 * ND> &g)
 {
     const u64 N = (u64)1 << a.logn;
     const u32 tl = j < a.cn ? a.clo + j : 0xFFFFFFFFu;     // table limb when the row is a ciphertext limb
@@ -80,46 +81,18 @@ __device__ __forceinline__ void ks_seal_job(const KsMacArgs &a, const BcCheck &k
 template <int ND, bool HOOK>
 __global__ __launch_bounds__(256) void k_ks_mac_sealed(KsMacArgs a, BcCheck k, u64 *part, u32 *flags_key, KsSealHit hit)
 {
-    __shared__ u64 sh[4][2 * ND][2];
-    __shared__ u32 shr[4];
-    const int lchunks = seal_log_chunks(a.logn);
-    const u32 words = 1u << (a.logn - lchunks);
-    const u32 jobs = a.M << lchunks;
-    for (u32 job = blockIdx.x; job < jobs; job += gridDim.x) {
-        const u32 j = job >> lchunks, chunk = job & ((1u << lchunks) - 1);
+    const SealJobs s(a.M, a.logn);
+    for (u64 job = blockIdx.x; job < s.jobs; job += gridDim.x) {
+        const u32 j = s.unit(job);
         const LimbParams &p = a.lp[j < a.cn ? a.clo + j : j + a.sp_shift];
-        KsSeal<ND> g;
-        if (p.path == PATH_F64) ks_seal_job<KsDotF64, ND, HOOK>(a, k, hit, j, chunk * words, words, p, g);
-        else ks_seal_job<KsDotU64, ND, HOOK>(a, k, hit, j, chunk * words, words, p, g);
-        for (int o = 32; o; o >>= 1) {
-            diag_seal_each<0, 2 * ND>([&](auto rc) {
-                constexpr int r = decltype(rc)::value;
-                g.acc[r].merge(__shfl_xor(g.acc[r].s0, o), __shfl_xor(g.acc[r].s1, o));
-            });
-            g.range |= __shfl_xor(g.range, o);
-        }
-        if ((threadIdx.x & 63) == 0) {
-            diag_seal_each<0, 2 * ND>([&](auto rc) {
-                constexpr int r = decltype(rc)::value;
-                sh[threadIdx.x >> 6][r][0] = g.acc[r].s0;
-                sh[threadIdx.x >> 6][r][1] = g.acc[r].s1;
-            });
-            shr[threadIdx.x >> 6] = g.range;
-        }
-        __syncthreads();
+        SealRows<2 * ND> g;
+        if (p.path == PATH_F64) ks_seal_job<KsDotF64, ND, HOOK>(a, k, hit, j, s.j0(job), s.words, p, g);
+        else ks_seal_job<KsDotU64, ND, HOOK>(a, k, hit, j, s.j0(job), s.words, p, g);
+        const u32 range = seal_block_combine<true>(g, part + job * 4 * a.dnum, g.range, 4 * a.dnum);
         if (threadIdx.x == 0) {
-            const u32 range = g.range | shr[1] | shr[2] | shr[3];
-            diag_seal_each<0, 2 * ND>([&](auto rc) {
-                constexpr int r = decltype(rc)::value;      // r = 2 d + h
-                if ((u32)r < 2 * a.dnum) {
-                    for (int w = 1; w < 4; w++) g.acc[r].merge(sh[w][r][0], sh[w][r][1]);
-                    part[((size_t)job * 2 * a.dnum + r) * 2] = g.acc[r].s0;
-                    part[((size_t)job * 2 * a.dnum + r) * 2 + 1] = g.acc[r].s1;
-                    if (range >> r & 1) atomicOr(flags_key + (size_t)r * a.M + j, (u32)SEAL_RANGE);
-                }
-            });
+            for (u32 r = 0; r < 2 * a.dnum; r++)      // r = 2 d + h
+                if (range >> r & 1) atomicOr(flags_key + (size_t)r * a.M + j, (u32)SEAL_RANGE);
         }
-        __syncthreads();      // sh is reused by the next job
     }
 }
 
@@ -129,12 +102,8 @@ __global__ __launch_bounds__(256) void k_ks_seal_finish(const u64 *part, u32 dnu
     const u32 rows = 2 * dnum * M;
     for (u32 r = blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += gridDim.x * blockDim.x) {
         const u32 dh = r / M, j = r % M;
-        SealAcc s;
-        for (u32 c = 0; c < chunks; c++) {
-            const u64 *pj = part + (((size_t)j * chunks + c) * 2 * dnum + dh) * 2;
-            s.merge(pj[0], pj[1]);
-        }
-        if (ks_seal_decide(s.s0, s.s1, seal + 2 * (size_t)r)) atomicOr(flags + r, (u32)SEAL_SUM);
+        const SealAcc s = seal_merge_partials<SealAcc>(part + ((size_t)j * chunks * 2 * dnum + dh) * 2, chunks, (size_t)dnum * 4);
+        if (seal_differs(s.s0, s.s1, seal + 2 * (size_t)r)) atomicOr(flags + r, (u32)SEAL_SUM);
     }
 }
 
@@ -143,13 +112,11 @@ namespace {
 template <int ND>
 hipError_t launch_sealed(hipStream_t st, const KsMacArgs &a, u64 *part, const u64 *seal_key, u32 *flags_key, const BcCheck &k, const KsSealHit &hit)
 {
-    const u32 chunks = 1u << seal_log_chunks(a.logn);
-    const dim3 grid(checked_grid((u64)a.M * chunks * 256, 8192));
-    hipLaunchKernelGGL((k.fault_point >= 0 || hit.mask ? k_ks_mac_sealed<ND, true> : k_ks_mac_sealed<ND, false>), grid, dim3(256), 0, st, a, k, part, flags_key, hit);
-    hipError_t e = hipGetLastError();
+    // either hook selects the hooked form
+    hipError_t e = launch_seal_sweep(k_ks_mac_sealed<ND, false>, k_ks_mac_sealed<ND, true>, k.fault_point >= 0 || hit.mask != 0, a.M, a.logn, st, a, k, part,
+                                     flags_key, hit);
     if (e != hipSuccess || !seal_key) return e;
-    hipLaunchKernelGGL(k_ks_seal_finish, dim3(checked_grid((u64)2 * a.dnum * a.M, 1024)), dim3(256), 0, st, (const u64 *)part, a.dnum, a.M, chunks, seal_key, flags_key);
-    return hipGetLastError();
+    return launch_seal_finish(k_ks_seal_finish, (u64)2 * a.dnum * a.M, st, (const u64 *)part, a.dnum, a.M, 1u << seal_log_chunks(a.logn), seal_key, flags_key);
 }
 
 } // namespace

@@ -6,8 +6,8 @@
 // seal, is a perfectly consistent operand to the residue identity of residue_check.hpp, and pollutes both halves of the result
 // with no flag.  The inner product loads every key word exactly once, so the seal of seal_check.hpp (S0 = sum x_j, S1 = sum (j + 1)
 // x_j modulo p = 2^61 - 1, and the window x_j < q) is digested from the very register that is then handed to D::mac -- no second
-// sweep, and the verified load IS the consuming load.  Per row j a lane keeps one SealAcc per (digit d, half h); a row's digests are
-// held against the stored seal of key row (d 2 + h) M + j after the sweep (ks_seal_decide).
+// sweep, and the verified load IS the consuming load.  Per row j a lane keeps one SealAcc per (digit d, half h) (SealRows<2 ND>); a
+// row's digests are held against the stored seal of key row (d 2 + h) M + j after the sweep (seal_differs).
 //
 // The arithmetic is k_ks_mac_checked's, unchanged: KsDotU64 / KsDotF64 over the same terms in the same order d = 0 .. dnum - 1,
 // the same finish, the same two fault points per half and the same residue flags; the words are fhe_keyswitch_apply's bit for bit
@@ -20,7 +20,8 @@
 // arithmetic modulo p throughout: no digest depends on how a row is cut into chunks, lanes or waves, nor on the order in which
 // partial sums are merged.
 #pragma once
-#include "bsgs_seal.hpp"
+#include "residue_check.hpp"
+#include "seal_check.hpp"
 
 namespace fhe {
 
@@ -35,21 +36,16 @@ struct KsHit {
     u64 coeff, mask;
 };
 
-// what one lane (one chunk, one row) has digested: the two sums of every key row (d, h), d < ND, and the window bits
-template <int ND> struct KsSeal {
-    SealAcc acc[2 * ND];      // [d][h]
-    u32 range = 0;            // bit 2 d + h: a word of half h of digit d was >= q
-};
-
 // Two adjacent words j, j + 1 of row p: ld(d, x, k0, k1) loads the two words of digit d (the owned limb or its extension, as
-// k_ks_mac_checked chooses) and of both key halves.  Digests every key word, forms the two words of each half of the sums and ORs
-// their residue flags into fl0 / fl1.  f0 / f1 = the checked call's test fault for word j and word j + 1 of half 0 / half 1.
+// k_ks_mac_checked chooses) and of both key halves.  Digests every key word into g (row 2 d + h = half h of digit d < ND), forms
+// the two words of each half of the sums and ORs their residue flags into fl0 / fl1.  f0 / f1 = the checked call's test fault for
+// word j and word j + 1 of half 0 / half 1.
 template <class D, int ND, bool HOOK, class LD>
-FHE_HD void ks_seal_pair(KsSeal<ND> &g, u32 dnum, u32 j, const LimbParams &p, const LD &ld, const KsHit &hit, const PwFault *f0, const PwFault *f1, u64 *c0, u64 *c1,
-                         u32 &fl0, u32 &fl1)
+FHE_HD void ks_seal_pair(SealRows<2 * ND> &g, u32 dnum, u32 j, const LimbParams &p, const LD &ld, const KsHit &hit, const PwFault *f0, const PwFault *f1, u64 *c0,
+                         u64 *c1, u32 &fl0, u32 &fl1)
 {
     D s0x, s1x, s0y, s1y;      // half 0 / 1 of word j (x) and of word j + 1 (y)
-    diag_seal_each<0, ND>([&](auto dc) {
+    seal_each<0, ND>([&](auto dc) {
         constexpr int d = decltype(dc)::value;
         if ((u32)d < dnum) {
             u64 x[2], k0[2], k1[2];
@@ -79,8 +75,8 @@ FHE_HD void ks_seal_pair(KsSeal<ND> &g, u32 dnum, u32 j, const LimbParams &p, co
     fl1 |= b | e;
 }
 
-// what the finish step decides for one key row: s0 / s1 = its lazily reduced digests, stored = the seal as it lies in memory.
-// True where the row raises SEAL_SUM; a stored sum is held word for word, so one that is not canonical counts as moved (seal_decide)
-FHE_HD bool ks_seal_decide(u64 s0, u64 s1, const u64 *stored) { return seal_canonical(s0) != stored[0] || seal_canonical(s1) != stored[1]; }
+// the names tests/emu/emu_ks_seal.cpp knows the record ([d][h]: row 2 d + h) and the finish step's decision by
+template <int ND> using KsSeal = SealRows<2 * ND>;
+FHE_HD bool ks_seal_decide(u64 s0, u64 s1, const u64 *stored) { return seal_differs(s0, s1, stored); }
 
 } // namespace fhe

@@ -417,7 +417,7 @@ struct TensorSealHit {
     u32 row;
     u64 coeff, mask;
 };
-// the launcher's cap on the workgroups of the job loop
+// every sealed launcher's cap on the workgroups of its job loop (seal_sweep.hpp)
 constexpr u32 TENSOR_SEAL_GRID_CAP = 8192;
 // words of the partial-sum scratch a launch needs: [units][chunks per row][8, or 14 with output seals]
 size_t tensor_seal_part_words(u32 units, int logn, bool out);

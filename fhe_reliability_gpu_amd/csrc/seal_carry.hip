@@ -2,13 +2,12 @@
 // fhe_modsub_sealed and the adds of fhe_rotate_sum_sealed.  A translation unit of its own, so that every other kernel compiles
 // exactly as before.
 //
-// k_modadd_carry is k_row_digest (seal_checked.hip) with the operation inside: a row of 2^logn words is cut into chunks of
-// 2^SEAL_LOG_CHUNK words and the (row, chunk) jobs are spread over a 1-D grid.  A lane loads 16 bytes of a and of b once, with
-// default cache policy (the next sealed call consumes c), forms the two words of c, counts their wraps with the weight of their
-// index in the ROW, digests c from the registers it then stores, and the job's sums {s0, s1, [s2], E0, E1, [E2]} combine through
-// wave shuffles and 128 or 192 bytes of LDS into one integer partial per job.  A chunk with an operand word >= q ORs SEAL_RANGE
-// into its row's flag with a global atomic; a clean run stores nothing extra.  c may be a or b (a lane writes the 16 bytes it read),
-// a may be b.
+// k_modadd_carry runs the chunked sweep of seal_sweep.hpp (job loop, workgroup combine, launch).  Per word: a lane loads 16 bytes
+// of a and of b once, with default cache policy (the next sealed call consumes c), forms the two words of c, counts their wraps
+// with the weight of their index in the ROW and digests c from the registers it then stores; the job's partial is {s0, s1, [s2],
+// E0, E1, [E2]}.  LDS per workgroup, from the compiler: 144 bytes, 208 with a locator (the sums of four waves and their window
+// bits).  A chunk with an operand word >= q ORs SEAL_RANGE into its row's flag with a global atomic; a clean run stores nothing
+// extra.  c may be a or b (a lane writes the 16 bytes it read), a may be b.
 //
 // k_modadd_carry_finish, one lane per row: adds the row's partials, predicts the sums of c from the operands' seals (and locators)
 // and the wrap sums, ORs SEAL_SUM into the row's flag where digest and prediction differ, and stores the PREDICTED sums, matched
@@ -17,8 +16,8 @@
 // Integer arithmetic modulo p throughout: no result depends on the grid or on the order of any combination.  No scratch memory,
 // no floating point, vector stores only.  HOOK: the one-shot test fault of fhe_ctx_inject_fault_seal_carry, applied in registers
 // at one of the five points of seal_carry.hpp; memory stays clean (point 3 is the store itself).
-#include "checked_kernel.hpp"
 #include "seal_carry.hpp"
+#include "seal_sweep.hpp"
 
 namespace fhe {
 
@@ -29,22 +28,17 @@ size_t carry_part_words(u32 units, int logn, bool loc) { return ((size_t)units <
 template <bool SUB, bool LOC, bool HOOK>
 __global__ __launch_bounds__(256) void k_modadd_carry(PointwiseArgs p, u64 *part, BcCheck k)
 {
-    constexpr int W = CarryAcc<LOC>::WORDS;
-    __shared__ u64 sh[4][W];
-    const int lchunks = seal_log_chunks(p.logn);
-    const u32 words = 1u << (p.logn - lchunks);
-    const u64 jobs = (u64)p.units << lchunks;
-    for (u64 job = blockIdx.x; job < jobs; job += gridDim.x) {
-        const u32 unit = (u32)(job >> lchunks), chunk = (u32)(job & (((u64)1 << lchunks) - 1));
+    const SealJobs s(p.units, p.logn);
+    for (u64 job = blockIdx.x; job < s.jobs; job += gridDim.x) {
+        const u32 unit = s.unit(job), j0 = s.j0(job);
         const u32 poly = unit / p.limbs, l = unit % p.limbs;
         const LimbParams &lp = p.lp[p.limb0 + l];
         const u64 q = lp.q, r0 = lp.barrett_lo, r1 = lp.barrett_hi;
         const u64 base = ((u64)poly * p.poly_stride + l) << p.logn;
-        const u32 j0 = chunk * words;
         CarryAcc<LOC> acc;
         bool bad = false;
 #pragma unroll 4
-        for (u32 i = threadIdx.x * 2; i < words; i += 512) {
+        for (u32 i = threadIdx.x * 2; i < s.words; i += 512) {
             const u32 j = j0 + i;
             const ulonglong2 a = *reinterpret_cast<const ulonglong2 *>(p.a + base + j);
             const ulonglong2 b = *reinterpret_cast<const ulonglong2 *>(p.b + base + j);
@@ -53,24 +47,8 @@ __global__ __launch_bounds__(256) void k_modadd_carry(PointwiseArgs p, u64 *part
             c.y = acc.template step<SUB>(a.y, b.y, q, r0, r1, j + 1, fault_at<HOOK>(k, unit, j + 1), bad);
             *reinterpret_cast<ulonglong2 *>(p.c + base + j) = c;
         }
-        for (int o = 32; o; o >>= 1) {
-            u64 other[W];
-#pragma unroll
-            for (int i = 0; i < W; i++) other[i] = __shfl_xor(acc.get(i), o);
-            acc.merge(other);
-        }
-        if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-            for (int i = 0; i < W; i++) sh[threadIdx.x >> 6][i] = acc.get(i);
-        }
-        const int any_bad = __syncthreads_or(bad);
-        if (threadIdx.x == 0) {
-            for (int w = 1; w < 4; w++) acc.merge(sh[w]);
-#pragma unroll
-            for (int i = 0; i < W; i++) part[W * job + i] = acc.get(i);
-            if (any_bad) atomicOr(k.flags + unit, (u32)SEAL_RANGE);
-        }
-        __syncthreads();      // sh is reused by the next job
+        const u32 any_bad = seal_block_combine<true>(acc, part + CarryAcc<LOC>::WORDS * job, bad);
+        if (threadIdx.x == 0 && any_bad) atomicOr(k.flags + unit, (u32)SEAL_RANGE);
     }
 }
 
@@ -87,9 +65,7 @@ __global__ __launch_bounds__(256) void k_modadd_carry_finish(const u64 *part, u3
 {
     constexpr int W = CarryAcc<LOC>::WORDS, S = LOC ? 3 : 2;
     for (u32 u = blockIdx.x * blockDim.x + threadIdx.x; u < units; u += gridDim.x * blockDim.x) {
-        CarryAcc<LOC> acc;
-        const u64 *pu = part + (size_t)u * chunks * W;
-        for (u32 c = 0; c < chunks; c++) acc.merge(pu + (size_t)c * W);
+        const CarryAcc<LOC> acc = seal_merge_partials<CarryAcc<LOC>>(part + (size_t)u * chunks * W, chunks);
         u64 got[S], E[S], sa[S], sb[S], pred[S];
 #pragma unroll
         for (int i = 0; i < S; i++) got[i] = acc.get(i), E[i] = acc.get(S + i);
@@ -108,13 +84,10 @@ namespace {
 template <bool SUB, bool LOC>
 hipError_t launch_carry(hipStream_t st, const PointwiseArgs &p, u64 *part, const CarrySeals &s, const BcCheck &k)
 {
-    const u32 chunks = 1u << seal_log_chunks(p.logn);
-    hipError_t e = launch_checked(k_modadd_carry<SUB, LOC, false>, k_modadd_carry<SUB, LOC, true>, k, dim3(checked_grid((u64)p.units * chunks * 256, 8192)), st,
-                                  p, part, k);
+    hipError_t e = launch_seal_sweep(k_modadd_carry<SUB, LOC, false>, k_modadd_carry<SUB, LOC, true>, k.fault_point >= 0, p.units, p.logn, st, p, part, k);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_modadd_carry_finish<SUB, LOC>), dim3(checked_grid(p.units, 1024)), dim3(256), 0, st, (const u64 *)part, p.units, chunks, p.lp, p.limb0,
-                       p.limbs, s, k.flags);
-    return hipGetLastError();
+    return launch_seal_finish(k_modadd_carry_finish<SUB, LOC>, p.units, st, (const u64 *)part, p.units, 1u << seal_log_chunks(p.logn), p.lp, p.limb0, p.limbs, s,
+                              k.flags);
 }
 
 } // namespace

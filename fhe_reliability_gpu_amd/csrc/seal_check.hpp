@@ -24,9 +24,21 @@
 // row is cut into chunks, lanes or waves, nor on the order in which partial sums are combined.  The weight of a word is its index
 // in the ROW (plus one), whatever chunk it was read in.  One 61 x 32-bit product per word, no floating point.
 #pragma once
+#include <type_traits>
+
 #include "modarith.hpp"
 
 namespace fhe {
+
+// f(integral_constant<int, I>) for I = B .. N - 1, unrolled by the template and not by the optimiser: an accumulator indexed by I
+// is then indexed by a constant whatever the size of the loop body, and never leaves the registers
+template <int B, int N, class F> FHE_HD void seal_each(F &&f)
+{
+    if constexpr (B < N) {
+        f(std::integral_constant<int, B>{});
+        seal_each<B + 1, N>(f);
+    }
+}
 
 constexpr u64 SEAL_P = ((u64)1 << 61) - 1;
 enum { SEAL_SUM = 1, SEAL_RANGE = 2 };      // flag bits of a verification: a sum differs, a word >= q_l
@@ -45,8 +57,10 @@ FHE_HD u64 seal_wmul(u64 x, u32 w)
     return (((hi << 32) | (lo & 0xFFFFFFFFu)) & SEAL_P) + (hi >> 29);
 }
 
-// the two running sums, each at most p + 7 between calls
+// the two running sums, each at most p + 7 between calls.  WORDS, get(i) and merge(const u64 *) are what every accumulator shows
+// to the combine of seal_sweep.hpp: its sums as they travel (shuffles, LDS, a job's partials in memory), in the partials' order
 struct SealAcc {
+    static constexpr int WORDS = 2;
     u64 s0 = 0, s1 = 0;
     // word x at index j of its row: weight j + 1
     FHE_HD void add(u64 x, u32 j)
@@ -60,6 +74,8 @@ struct SealAcc {
         s0 = seal_fold(s0 + seal_fold(o0));
         s1 = seal_fold(s1 + seal_fold(o1));
     }
+    FHE_HD u64 get(int i) const { return i ? s1 : s0; }
+    FHE_HD void merge(const u64 *o) { merge(o[0], o[1]); }
 };
 
 // a lazily reduced sum -> [0, p): two folds bring any 64-bit value to at most p, and p itself is 0
@@ -68,6 +84,26 @@ FHE_HD u64 seal_canonical(u64 s)
     s = seal_fold(seal_fold(s));
     return s >= SEAL_P ? s - SEAL_P : s;
 }
+
+// what a finish step decides for one row: s0 / s1 = its lazily reduced digests, stored = the seal as it lies in memory.  True where
+// the row raises SEAL_SUM; a stored sum is held word for word, so one that is not canonical counts as moved (seal_decide)
+FHE_HD bool seal_differs(u64 s0, u64 s1, const u64 *stored) { return seal_canonical(s0) != stored[0] || seal_canonical(s1) != stored[1]; }
+
+// what one lane (one chunk, one row) of a fused sweep has digested of N operand rows it reads side by side (the diagonals of
+// bsgs_seal.hpp, the key rows of ks_seal.hpp): the two sums of each and the window bits
+template <int N> struct SealRows {
+    static constexpr int WORDS = 2 * N;
+    SealAcc acc[N];
+    u32 range = 0;      // bit r: a word of row r was >= q
+    FHE_HD u64 get(int i) const { return acc[i >> 1].get(i & 1); }
+    FHE_HD void merge(const u64 *o)
+    {
+        seal_each<0, N>([&](auto rc) {
+            constexpr int r = decltype(rc)::value;
+            acc[r].merge(o[2 * r], o[2 * r + 1]);
+        });
+    }
+};
 
 // ---- repair: a third sum locates and corrects one corrupted word per row (seal_repair.hip, capi_seal.cpp) ----
 // Beside the seal {S0, S1} a row may carry the locator sum S2 = sum_j (j + 1)^2 x_j mod p.  With syndromes D_i = S_i' - S_i (the

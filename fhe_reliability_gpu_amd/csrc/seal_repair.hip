@@ -1,10 +1,10 @@
 // seal_repair.hip -- the locator sum of a sealed row and the repair of one corrupted word per row (seal_check.hpp): fhe_seal_locator,
 // fhe_seal_repair and the repairing composites.  A translation unit of its own, so that every other kernel compiles exactly as before.
 //
-// k_row_locator is k_row_digest (seal_checked.hip) for the third sum S2 = sum_j (j + 1)^2 x_j mod p: (row, chunk) jobs over a 1-D
-// grid, 16 bytes per load, the weight of a word its index in the ROW applied twice, wave shuffles, 32 bytes of LDS, one integer
-// partial per job, and k_row_locator_finish adds a row's partials and makes the sum canonical.  Integer arithmetic modulo p: the
-// result does not depend on the grid or the order of any combination, reruns are identical.
+// k_row_locator forms the third sum S2 = sum_j (j + 1)^2 x_j mod p by the chunked sweep of seal_sweep.hpp (job loop, workgroup
+// combine, launch).  Per word: 16 bytes per load, the weight of a word its index in the ROW applied twice; one integer partial per
+// job, and k_row_locator_finish adds a row's partials and makes the sum canonical.  Integer arithmetic modulo p: the result does
+// not depend on the grid or the order of any combination, reruns are identical.
 //
 // k_row_repair runs after the verifying sweep has filled flags[row]: one workgroup per row, and a workgroup whose row has flag 0
 // writes a CLEAN report and moves on -- a clean call costs one nearly empty launch.  For a flagged row the workgroup re-reads the
@@ -12,51 +12,49 @@
 // counts the words >= q_l and keeps the index of one, lane 0 decides (seal_decide), stores the corrected word, and after a fence
 // and a barrier the workgroup sweeps the row a second time: only when all three sums equal the stored ones and every word is in
 // its window does the flag drop; otherwise the old word is put back.  No scratch, no floating point, vector stores only.
-#include "checked_kernel.hpp"
-#include "seal_check.hpp"
+#include "seal_sweep.hpp"
 
 namespace fhe {
+
+namespace {
+
+// the locator sum alone, at most p + 7 between calls, as the combine of seal_sweep.hpp takes an accumulator
+struct LocatorAcc {
+    static constexpr int WORDS = 1;
+    u64 s2 = 0;
+    // folded word f at index j of its row: weight (j + 1)^2
+    __device__ void add(u64 f, u32 j) { s2 = seal_fold(s2 + seal_w2mul(f, j + 1)); }
+    __device__ u64 get(int) const { return s2; }
+    __device__ void merge(const u64 *o) { s2 = seal_fold(s2 + seal_fold(o[0])); }
+};
+
+} // namespace
 
 // part = [units][chunks]
 __global__ __launch_bounds__(256) void k_row_locator(SealArgs p, u64 *part)
 {
-    __shared__ u64 sh[4];
-    const int lchunks = seal_log_chunks(p.logn);
-    const u32 words = 1u << (p.logn - lchunks);
-    const u64 jobs = (u64)p.units << lchunks;
-    for (u64 job = blockIdx.x; job < jobs; job += gridDim.x) {
-        const u32 unit = (u32)(job >> lchunks), chunk = (u32)(job & (((u64)1 << lchunks) - 1));
+    const SealJobs s(p.units, p.logn);
+    for (u64 job = blockIdx.x; job < s.jobs; job += gridDim.x) {
+        const u32 unit = s.unit(job), j0 = s.j0(job);
         const u32 poly = unit / p.limbs, l = unit % p.limbs;
         const u64 *row = p.x + (((u64)poly * p.poly_stride + l) << p.logn);
-        const u32 j0 = chunk * words;
-        u64 s2 = 0;
+        LocatorAcc a;
 #pragma unroll 4
-        for (u32 i = threadIdx.x * 2; i < words; i += 512) {
+        for (u32 i = threadIdx.x * 2; i < s.words; i += 512) {
             const u32 j = j0 + i;
             const ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(row + j);
-            s2 = seal_fold(s2 + seal_w2mul(seal_fold(v.x), j + 1));
-            s2 = seal_fold(s2 + seal_w2mul(seal_fold(v.y), j + 2));
+            a.add(seal_fold(v.x), j);
+            a.add(seal_fold(v.y), j + 1);
         }
-        for (int o = 32; o; o >>= 1) s2 = seal_fold(s2 + seal_fold(__shfl_xor(s2, o)));
-        if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s2;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            for (int w = 1; w < 4; w++) s2 = seal_fold(s2 + seal_fold(sh[w]));
-            part[job] = s2;
-        }
-        __syncthreads();      // sh is reused by the next job
+        seal_block_combine<false>(a, part + job);
     }
 }
 
 // one lane per row: locator[row] = the canonical sum of its partials
 __global__ __launch_bounds__(256) void k_row_locator_finish(const u64 *part, u32 units, u32 chunks, u64 *locator)
 {
-    for (u32 u = blockIdx.x * blockDim.x + threadIdx.x; u < units; u += gridDim.x * blockDim.x) {
-        u64 s2 = 0;
-        const u64 *pu = part + (size_t)u * chunks;
-        for (u32 c = 0; c < chunks; c++) s2 = seal_fold(s2 + seal_fold(pu[c]));
-        locator[u] = seal_canonical(s2);
-    }
+    for (u32 u = blockIdx.x * blockDim.x + threadIdx.x; u < units; u += gridDim.x * blockDim.x)
+        locator[u] = seal_canonical(seal_merge_partials<LocatorAcc>(part + (size_t)u * chunks, chunks).s2);
 }
 
 namespace {
@@ -161,13 +159,9 @@ __global__ __launch_bounds__(256) void k_row_repair(SealArgs p, const u64 *seal,
 hipError_t launch_seal_locator(hipStream_t st, const SealArgs &p, u64 *part, u64 *locator)
 {
     if (!p.units) return hipSuccess;
-    const u64 jobs = (u64)p.units << seal_log_chunks(p.logn);
-    hipLaunchKernelGGL(k_row_locator, dim3(checked_grid(jobs * 256, 8192)), dim3(256), 0, st, p, part);
-    hipError_t e = hipGetLastError();
+    hipError_t e = launch_seal_sweep(k_row_locator, k_row_locator, false, p.units, p.logn, st, p, part);      // no hooked form
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_row_locator_finish, dim3(checked_grid(p.units, 1024)), dim3(256), 0, st, (const u64 *)part, p.units,
-                       1u << seal_log_chunks(p.logn), locator);
-    return hipGetLastError();
+    return launch_seal_finish(k_row_locator_finish, p.units, st, (const u64 *)part, p.units, 1u << seal_log_chunks(p.logn), locator);
 }
 
 hipError_t launch_seal_repair(hipStream_t st, const SealArgs &p, const u64 *seal, const u64 *locator, u32 *flags, u64 *report)

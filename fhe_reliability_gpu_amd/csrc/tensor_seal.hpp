@@ -75,8 +75,7 @@ template <bool OUT> struct TensorSealAcc {
     }
 };
 
-// what the finish step decides for one operand row: s0 / s1 = its lazily reduced digests, stored = the seal as it lies in memory.
-// True where the row raises SEAL_SUM; a stored sum is held word for word, so one that is not canonical counts as moved (seal_decide)
-FHE_HD bool tensor_seal_decide(u64 s0, u64 s1, const u64 *stored) { return seal_canonical(s0) != stored[0] || seal_canonical(s1) != stored[1]; }
+// the name tests/emu/emu_tensor_seal.cpp knows the finish step's decision by
+FHE_HD bool tensor_seal_decide(u64 s0, u64 s1, const u64 *stored) { return seal_differs(s0, s1, stored); }
 
 } // namespace fhe

@@ -2,15 +2,14 @@
 // digested from the registers that are stored (tensor_seal.hpp): fhe_tensor_product_sealed and the tensor step of
 // fhe_hmult_sealed_fused.  A translation unit of its own, so that every other kernel compiles exactly as before.
 //
-// k_tensor_sealed is k_tensor_checked (pointwise_checked.hip) in the shape of k_modadd_carry (seal_carry.hip): a row of 2^logn
-// words is cut into chunks of 2^SEAL_LOG_CHUNK words and the (row, chunk) jobs are spread over a 1-D grid.  A lane takes two words
-// per step with 16-byte loads of a0, a1, b0, b1, default cache policy (the key switch consumes d2 next), digests each operand word
-// from the register it then hands to the product, with the weight of its index in the ROW, forms the two words of d0, d1, d2, with
-// OUT digests them as well, and stores them 16 bytes at a time.  After the job the sums combine through wave shuffles and
-// 4 x WORDS x 8 bytes of LDS into one integer partial part[job][WORDS]; a lane that saw a residue flag ORs it into the row's
-// [3] words, a job that saw an operand word >= q ORs SEAL_RANGE into that operand's row flag, both with global atomics.  A clean
-// run stores nothing beyond the partial.  A lane writes only the indices it read, after it read them: an output may be exactly an
-// operand's buffer, and a may be b.
+// k_tensor_sealed runs the chunked sweep of seal_sweep.hpp (job loop, workgroup combine, launch) with k_tensor_checked's
+// arithmetic (pointwise_checked.hip).  Per word: a lane takes two words per step with 16-byte loads of a0, a1, b0, b1, default
+// cache policy (the key switch consumes d2 next), digests each operand word from the register it then hands to the product, with
+// the weight of its index in the ROW, forms the two words of d0, d1, d2, with OUT digests them as well, and stores them 16 bytes
+// at a time.  The job's partial is part[job][WORDS] (272 bytes of LDS per workgroup, 464 with OUT); a lane that saw a residue flag
+// ORs it into the row's [3] words, a job that saw an operand word >= q ORs SEAL_RANGE into that operand's row flag, both with
+// global atomics.  A clean run stores nothing beyond the partial.  A lane writes only the indices it read, after it read them: an
+// output may be exactly an operand's buffer, and a may be b.
 //
 // k_tensor_seal_finish, one lane per row: adds the row's partials, makes them canonical, holds each operand's pair word for word
 // against its stored seal where one was given (a difference ORs SEAL_SUM), and with OUT writes the sums of d0, d1, d2 to the
@@ -19,7 +18,7 @@
 // Integer arithmetic modulo 2^61 - 1 in every digest: no result depends on the grid or on the order of any combination.  No
 // scratch memory, vector stores only.  HOOK: the pointwise call's one-shot fault on the d1 sum (BcCheck) and the sealed call's own
 // (TensorSealHit: one bit of one operand word in the register as loaded); memory stays clean.
-#include "checked_kernel.hpp"
+#include "seal_sweep.hpp"
 #include "tensor_seal.hpp"
 
 namespace fhe {
@@ -62,41 +61,19 @@ __device__ __forceinline__ void tensor_seal_job(const TensorSealArgs &t, const B
 template <bool OUT, bool HOOK>
 __global__ __launch_bounds__(256) void k_tensor_sealed(TensorSealArgs t, u64 *part, BcCheck k, TensorSealHit hit)
 {
-    constexpr int W = TensorSealAcc<OUT>::WORDS;
-    __shared__ u64 sh[4][W];
-    __shared__ u32 shb[4];
-    const int lchunks = seal_log_chunks(t.logn);
-    const u32 words = 1u << (t.logn - lchunks);
-    const u64 jobs = (u64)t.units << lchunks;
-    for (u64 job = blockIdx.x; job < jobs; job += gridDim.x) {
-        const u32 unit = (u32)(job >> lchunks), chunk = (u32)(job & (((u64)1 << lchunks) - 1));
+    const SealJobs s(t.units, t.logn);
+    for (u64 job = blockIdx.x; job < s.jobs; job += gridDim.x) {
+        const u32 unit = s.unit(job);
         TensorSealAcc<OUT> acc;
         u32 bad = 0;
-        if (t.lp[t.limb0 + unit % t.limbs].path == PATH_F64) tensor_seal_job<KsDotF64, OUT, HOOK>(t, k, hit, unit, chunk * words, words, acc, bad);
-        else tensor_seal_job<KsDotU64, OUT, HOOK>(t, k, hit, unit, chunk * words, words, acc, bad);
-        for (int o = 32; o; o >>= 1) {
-            u64 other[W];
-#pragma unroll
-            for (int i = 0; i < W; i++) other[i] = __shfl_xor(acc.get(i), o);
-            acc.merge(other);
-            bad |= __shfl_xor(bad, o);
-        }
-        if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-            for (int i = 0; i < W; i++) sh[threadIdx.x >> 6][i] = acc.get(i);
-            shb[threadIdx.x >> 6] = bad;
-        }
-        __syncthreads();
+        if (t.lp[t.limb0 + unit % t.limbs].path == PATH_F64) tensor_seal_job<KsDotF64, OUT, HOOK>(t, k, hit, unit, s.j0(job), s.words, acc, bad);
+        else tensor_seal_job<KsDotU64, OUT, HOOK>(t, k, hit, unit, s.j0(job), s.words, acc, bad);
+        bad = seal_block_combine<true>(acc, part + TensorSealAcc<OUT>::WORDS * job, bad);
         if (threadIdx.x == 0) {
-            for (int w = 1; w < 4; w++) acc.merge(sh[w]);
-#pragma unroll
-            for (int i = 0; i < W; i++) part[W * job + i] = acc.get(i);
-            bad |= shb[1] | shb[2] | shb[3];
 #pragma unroll
             for (int o = 0; o < 4; o++)
                 if (bad >> o & 1) atomicOr(t.flags_op[o] + unit, (u32)SEAL_RANGE);
         }
-        __syncthreads();      // sh is reused by the next job
     }
 }
 
@@ -106,12 +83,10 @@ __global__ __launch_bounds__(256) void k_tensor_seal_finish(TensorSealArgs t, co
 {
     constexpr int W = TensorSealAcc<OUT>::WORDS;
     for (u32 u = blockIdx.x * blockDim.x + threadIdx.x; u < t.units; u += gridDim.x * blockDim.x) {
-        TensorSealAcc<OUT> acc;
-        const u64 *pu = part + (size_t)u * chunks * W;
-        for (u32 c = 0; c < chunks; c++) acc.merge(pu + (size_t)c * W);
+        const TensorSealAcc<OUT> acc = seal_merge_partials<TensorSealAcc<OUT>>(part + (size_t)u * chunks * W, chunks);
 #pragma unroll
         for (int o = 0; o < 4; o++)
-            if (t.seal_in[o] && tensor_seal_decide(acc.s[o].s0, acc.s[o].s1, t.seal_in[o] + 2 * (size_t)u)) atomicOr(t.flags_op[o] + u, (u32)SEAL_SUM);
+            if (t.seal_in[o] && seal_differs(acc.s[o].s0, acc.s[o].s1, t.seal_in[o] + 2 * (size_t)u)) atomicOr(t.flags_op[o] + u, (u32)SEAL_SUM);
         if constexpr (OUT) {
 #pragma unroll
             for (int i = 0; i < 3; i++)
@@ -128,14 +103,10 @@ namespace {
 template <bool OUT>
 hipError_t launch_sealed(hipStream_t st, const TensorSealArgs &t, u64 *part, const BcCheck &k, const TensorSealHit &hit)
 {
-    const u32 chunks = 1u << seal_log_chunks(t.logn);
-    BcCheck sel = k;      // launch_checked picks the hooked form by the record's point: either hook selects it
-    if (hit.mask && sel.fault_point < 0) sel.fault_point = PW_AT_SUM, sel.fault_mask = 0;
-    hipError_t e = launch_checked(k_tensor_sealed<OUT, false>, k_tensor_sealed<OUT, true>, sel, dim3(checked_grid((u64)t.units * chunks * 256, TENSOR_SEAL_GRID_CAP)),
-                                  st, t, part, sel, hit);
+    // either hook selects the hooked form
+    hipError_t e = launch_seal_sweep(k_tensor_sealed<OUT, false>, k_tensor_sealed<OUT, true>, k.fault_point >= 0 || hit.mask != 0, t.units, t.logn, st, t, part, k, hit);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_tensor_seal_finish<OUT>, dim3(checked_grid(t.units, 1024)), dim3(256), 0, st, t, (const u64 *)part, chunks);
-    return hipGetLastError();
+    return launch_seal_finish(k_tensor_seal_finish<OUT>, t.units, st, t, (const u64 *)part, 1u << seal_log_chunks(t.logn));
 }
 
 } // namespace

@@ -27,6 +27,10 @@ takes.  Nothing asserts the launcher's rule: a launcher may change its cap, the 
   k_tensor, k_tensor_checked (aux_kernels, pointwise_checked)   16384 x 256    1 word     4 194 304 words
   k_bconv_fast (+ checked), k_crt_garner, k_bsgs_hadamard       4096 x 256     1 column   1 048 576 columns
   k_row_digest (seal, verify), k_row_locator                    8192 jobs      1 (row, chunk) job per workgroup
+  k_modadd_carry, k_automorphism_ntt_sealed, k_tensor_sealed    8192 jobs      1 (row, chunk) job per workgroup; their long cases are
+                                                                               test_the_job_loop_takes_a_second / a_fourth_trip of their own files
+  k_diag_mac_sealed, k_ks_mac_sealed                            8192 jobs      not listed: their rows are limbs, a few dozen at most, times
+                                                                               at most 16 chunks -- no plan reaches the cap
   k_row_repair                                                  2048 rows      1 row per workgroup
 """
 import numpy as np
@@ -147,6 +151,9 @@ GRID_CAPS = {
     "seal": (8192, 1, "job"),
     "seal_verify": (8192, 1, "job"),
     "seal_locator": (8192, 1, "job"),
+    "modadd_sealed": (8192, 1, "job"),
+    "automorphism_ntt_sealed": (8192, 1, "job"),
+    "tensor_product_sealed": (8192, 1, "job"),
     "seal_repair": (2048, 1, "row"),
 }
 

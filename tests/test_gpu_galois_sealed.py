@@ -18,6 +18,7 @@ SUM, RANGE = 1, 2
 WORD, INDEX = 0, 1
 PATTERN = 0x5A5A5A5A5A5A5A5A
 CAP = 12
+GRID_CAP = 8192                 # TENSOR_SEAL_GRID_CAP of ntt_launch.hpp: workgroups of the job loop at most
 SHAPES = (4, 10, 14)
 BITS = [50, 61, 50]
 N_POLY, LIMBS = 2, 3
@@ -151,6 +152,34 @@ def test_a_word_outside_the_window_raises_range(rows, logn):
         assert flags[row] & RANGE and np.flatnonzero(flags).tolist() == [row], (row, word)
     # x + p moves no sum: the window alone sees it
     assert flags[3] == RANGE
+
+
+def test_the_job_loop_takes_a_second_trip(F, eng):
+    """cap + 1 rows of two words: the last row is workgroup 0's second job, the one the combine's trailing barrier is for.  At
+    N = 2 and k = 3 the slots map 0 -> 1, 1 -> 0 (2 j + 1 times 3 modulo 4): the permutation swaps the two words of a row"""
+    P = (1 << 61) - 1
+    logn, N, k = 1, 2, 3
+    n_poly = GRID_CAP + 1
+    qs = F.create_moduli(N, [50])
+    t, q = eng.tables(logn, qs), qs[0]
+    src = np.random.default_rng(41).integers(16, q - 16, (n_poly, N), dtype=np.uint64)
+    assert src.nbytes < 1 << 20
+    d = eng.upload(src)
+    seal = t.seal(d, limbs=1, n_poly=n_poly)
+    dst, seal_dst, flags = F.automorphism_sealed(eng, t, d, seal, k, n_poly=n_poly, limbs=1)
+    assert flags.shape == (n_poly,) and not flags.any()
+    got, sums = dst.download().reshape(n_poly, N), seal_dst.download().reshape(n_poly, 2)
+    assert (got == src[:, ::-1]).all()
+    for r in (0, GRID_CAP - 1, GRID_CAP):
+        x0, x1 = int(src[r, 1]), int(src[r, 0])
+        assert sums[r].tolist() == [(x0 + x1) % P, (x0 + 2 * x1) % P], r
+    assert same(seal_dst, t.seal(dst, limbs=1, n_poly=n_poly))
+    # a word changed at rest in the last row raises exactly that row
+    bad = src.copy()
+    bad[GRID_CAP, 1] ^= np.uint64(8)
+    flags = F.automorphism_sealed(eng, t, eng.upload(bad), seal, k, n_poly=n_poly, limbs=1)[2]
+    assert np.flatnonzero(flags).tolist() == [GRID_CAP] and int(flags[GRID_CAP]) == SUM
+    eng.check()
 
 
 @pytest.mark.parametrize("logn", SHAPES)

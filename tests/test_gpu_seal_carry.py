@@ -20,6 +20,7 @@ INVALID = 1
 SUM, RANGE = 1, 2
 P = (1 << 61) - 1
 GARBAGE = 0x5A5A5A5A5A5A5A5A
+GRID_CAP = 8192                 # TENSOR_SEAL_GRID_CAP of ntt_launch.hpp: workgroups of the job loop at most
 SHAPES = [(1, 1, 0), (3, 2, 1), (1, 7, 0)]
 
 
@@ -186,6 +187,40 @@ def test_a_word_flipped_at_rest_raises_its_row_and_the_row_stays_raised(F, eng, 
     sc, fl = t.modadd_sealed(dc, da, db, sa, sb, **kw)
     assert fl.tolist() == [0, SUM | RANGE] + [0] * (rows - 2)
     assert (dc.download() == unchecked(eng, t, da, db, False, **kw).download()).all()
+    eng.check()
+
+
+def test_the_job_loop_takes_a_second_trip(F, eng):
+    """cap + 1 rows of two words: the last row is workgroup 0's second job, the one the combine's trailing barrier is for.  With
+    locators, the widest partial"""
+    logn, N = 1, 2
+    n_poly = GRID_CAP + 1
+    qs = F.create_moduli(N, [50])
+    t, q = eng.tables(logn, qs), qs[0]
+    kw = dict(limbs=1, start=0, n_poly=n_poly)
+    rng = np.random.default_rng(37)
+    ha, hb = (rng.integers(0, q, (n_poly, N), dtype=np.uint64) for _ in range(2))
+    assert ha.nbytes < 1 << 20
+    da, db = eng.upload(ha), eng.upload(hb)
+    sa, sb, la, lb = t.seal(da, **kw), t.seal(db, **kw), t.seal_locator(da, **kw), t.seal_locator(db, **kw)
+    probe = (0, GRID_CAP - 1, GRID_CAP)
+    for sub in (False, True):
+        call = t.modsub_sealed if sub else t.modadd_sealed
+        hw = ((ha.astype(object) - hb.astype(object)) % q if sub else (ha.astype(object) + hb.astype(object)) % q).astype(np.uint64)
+        dc = eng.upload(np.full(ha.shape, GARBAGE, dtype=np.uint64))
+        sc, lc, fl = call(dc, da, db, sa, sb, locators=(la, lb), **kw)
+        assert not fl.any()
+        assert (dc.download() == hw).all()
+        sums, locs = sc.download().reshape(n_poly, 2), lc.download()
+        for r in probe:
+            want = py_sums(hw[r:r + 1])[0]
+            assert sums[r].tolist() == want[:2] and int(locs[r]) == want[2], (sub, r)
+        assert (sums == t.seal(dc, **kw).download().reshape(n_poly, 2)).all() and (locs == t.seal_locator(dc, **kw).download()).all()
+        # a word changed at rest in the last row raises exactly that row
+        host = ha.copy()
+        host[GRID_CAP, 1] ^= np.uint64(1)
+        fl = call(dc, eng.upload(host), db, sa, sb, locators=(la, lb), **kw)[-1]
+        assert np.flatnonzero(fl).tolist() == [GRID_CAP] and int(fl[GRID_CAP]) == SUM, sub
     eng.check()
 
 
