@@ -19,11 +19,8 @@
 // per giant step the inner sum that digests each diagonal word from the register it multiplies (launch_diag_mac_sealed; n1 > 16: a
 // verifying sweep over the step's diagonal rows, then launch_diag_mac_checked) and seals both outputs.  Its flag buffer is
 //     [c0 L][c1 L][baby keys (n1 - 1) key_rows][giant keys (n2 - 1) key_rows][diagonals n2 n1 L][the checked call's own block]
-#include "capi_checked.hpp"
+#include "capi_sealed.hpp"
 #include "bsgs_seal.hpp"
-
-#include <climits>
-#include <cstdint>
 
 namespace {
 
@@ -60,8 +57,6 @@ struct SealedMode {
     uint64_t *const *seal_out;               // [2]
 };
 
-size_t bsgs_key_rows(const fhe_keyswitch *p) { return (size_t)p->dnum * 2 * (p->L + p->K); }
-
 // offsets of c0, c1, the baby keys, the giant keys, the diagonals and the checked block; total (-1: too large)
 struct BmsLayout {
     int off[6], total;
@@ -69,7 +64,7 @@ struct BmsLayout {
 
 BmsLayout bms_layout(const fhe_keyswitch *p, size_t n1, size_t n2)
 {
-    const unsigned long long L = p->L, kr = bsgs_key_rows(p);
+    const unsigned long long L = p->L, kr = key_rows(p);
     const BmcLayout c = bmc_layout(p, n1, n2);
     unsigned long long o[7];
     o[0] = 0;
@@ -83,25 +78,6 @@ BmsLayout bms_layout(const fhe_keyswitch *p, size_t n1, size_t n2)
     for (int i = 0; i < 6; i++) l.off[i] = o[i] > (unsigned long long)INT_MAX ? INT_MAX : (int)o[i];
     l.total = c.total < 0 || o[6] > (unsigned long long)INT_MAX ? -1 : (int)o[6];
     return l;
-}
-
-bool misaligned(std::initializer_list<const void *> ptrs)
-{
-    for (const void *q : ptrs)
-        if ((uintptr_t)q % 16) return true;
-    return false;
-}
-
-// rows [n_poly][limbs][N] from table limb 0 on against their seal, flags at d_flags; a null seal is skipped
-int verify_rows(hipStream_t st, const fhe_keyswitch *p, const uint64_t *words, const uint64_t *seal, size_t n_poly, size_t limbs, u32 *d_flags, u64 *part,
-                const BcCheck *hook = nullptr)
-{
-    if (!seal) return FHE_OK;
-    const SealArgs sa{words, p->t->d_lp.as<LimbParams>(), 0u, (u32)limbs, (u32)(n_poly * limbs), (u32)limbs, p->log_n};
-    BcCheck k = hook ? *hook : BcCheck{nullptr, -1, 0, 0, 0};
-    k.flags = d_flags;
-    hipError_t e = launch_seal_verify(st, sa, part, seal, k);
-    return e == hipSuccess ? FHE_OK : hip_fail(e, "launch_seal_verify");
 }
 
 // fhe_bsgs_matvec_checked (sm == nullptr) and fhe_bsgs_matvec_sealed
@@ -177,17 +153,7 @@ int fhe_bsgs_matvec_sealed_layout(const fhe_keyswitch *p, size_t n1, size_t n2, 
 int fhe_ctx_inject_fault_bsgs_sealed(fhe_ctx *ctx, int g, int b, int limb, long long coeff, int bit)
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
-    if (g < 0) {
-        (void)ctx->bsgs_seal_fault.take();
-        return FHE_OK;
-    }
-    if (b < 0 || limb < 0 || coeff < 0 || bit < 0 || bit > 63) return fail(FHE_ERR_INVALID, "bad fault");
-    ctx->bsgs_seal_fault.g = g;
-    ctx->bsgs_seal_fault.b = b;
-    ctx->bsgs_seal_fault.limb = limb;
-    ctx->bsgs_seal_fault.coeff = coeff;
-    ctx->bsgs_seal_fault.bit = bit;
-    return FHE_OK;
+    return ctx->bsgs_seal_fault.arm(INT_MAX, g, b, limb, coeff, bit) ? FHE_OK : fail(FHE_ERR_INVALID, "bad fault");
 }
 
 int fhe_bsgs_matvec_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0, const uint64_t *d_c1,
@@ -212,7 +178,7 @@ int bsgs_body(const SealedMode *sm, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_
     // the one-shot hooks of the steps this call runs belong to it whatever its outcome: all are taken here
     const StagedFault hf = ctx->hrc_fault.take(), kf = ctx->ksc_fault.take(), bf = ctx->bsgs_fault.take();
     const GaloisFault gf = ctx->gal_fault.take();
-    const fhe_ctx::DiagSealFault sf = sm ? ctx->bsgs_seal_fault.take() : fhe_ctx::DiagSealFault{};
+    const SealHook sf = sm ? ctx->bsgs_seal_fault.take() : SealHook{};
     int rc = ksc_scope(ctx, p, a, d_flags, KsForm::CKKS, false);
     if (rc) return rc;
     if (!d_out0 || !d_out1 || !d_c0 || !d_c1 || !d_diags || !bsgs_shape_ok(n1, n2)) return fail(FHE_ERR_INVALID, "bad arguments");
@@ -234,8 +200,8 @@ int bsgs_body(const SealedMode *sm, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_
         for (size_t b = 0; b + 1 < n1; b++) bad = bad || misaligned({d_baby_keys_prepared[b]});
         for (size_t g = 0; g + 1 < n2; g++) bad = bad || misaligned({d_giant_keys[g]});
         if (bad) return fail(FHE_ERR_INVALID, "sealed rows are read 16 bytes at a time: the buffers must be 16-byte aligned");
-        if (sf.g >= 0) {
-            if ((size_t)sf.g >= n2 || (size_t)sf.b >= n1 || sf.limb >= L || (size_t)sf.coeff >= N)
+        if (sf.sel >= 0) {
+            if ((size_t)sf.sel >= n2 || (size_t)sf.idx >= n1 || !sf.inside((size_t)L, logn))
                 return fail(FHE_ERR_INVALID, "sealed-diagonal fault outside the call");
             if (!sm->seal_diag) return fail(FHE_ERR_INVALID, "sealed-diagonal fault outside the call: no diagonal seals were given");
         }
@@ -276,26 +242,22 @@ int bsgs_body(const SealedMode *sm, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_
     u32 *d_sealed = d_flags;      // the sealed call's buffer; d_flags becomes the checked call's own block inside it
     if (sm) {
         // the partial-sum scratch of the context, sized once for the largest sweep of the call, before the first launch
-        size_t words = std::max(seal_part_words((u32)bsgs_key_rows(p), logn), seal_part_words((u32)L, logn));
+        size_t words = std::max(seal_part_words((u32)key_rows(p), logn), seal_part_words((u32)L, logn));
         if (sm->seal_diag) words = std::max(words, fused ? diag_seal_part_words((u32)L, logn, diag_seal_nb((u32)n1)) : seal_part_words((u32)(n1 * L), logn));
-        if (ctx->seal_part.bytes < words * 8) {
-            HIP_TRY(hipStreamSynchronize(st));        // (growing frees the old block)
-            HIP_TRY(ctx->seal_part.alloc(words * 8));
-        }
-        spart = ctx->seal_part.as<u64>();
+        if ((rc = seal_scratch(ctx, st, words, &spart))) return rc;
         HIP_TRY(hipMemsetAsync(d_sealed, 0, (size_t)sl.off[5] * sizeof(u32), st));
         d_flags = d_sealed + sl.off[5];
         // ---- the operands and keys at rest: a raised flag does not stop the call
         const uint64_t *ops[2] = {d_c0, d_c1};
         for (int h = 0; h < 2; h++)
-            if ((rc = verify_rows(st, p, ops[h], sm->seal_in ? sm->seal_in[h] : nullptr, 1, L, d_sealed + sl.off[h], spart))) return rc;
-        const size_t kr = bsgs_key_rows(p);
+            if ((rc = verify_rows(st, seal_args(p->t, ops[h], 1, L, 0), sm->seal_in ? sm->seal_in[h] : nullptr, d_sealed + sl.off[h], spart))) return rc;
+        const size_t kr = key_rows(p);
         for (size_t b = 0; b + 1 < n1; b++)
-            if ((rc = verify_rows(st, p, d_baby_keys_prepared[b], sm->seal_baby ? sm->seal_baby[b] : nullptr, (size_t)p->dnum * 2, L + p->K,
+            if ((rc = verify_rows(st, seal_args(p->t, d_baby_keys_prepared[b], (size_t)p->dnum * 2, L + p->K, 0), sm->seal_baby ? sm->seal_baby[b] : nullptr,
                                   d_sealed + sl.off[2] + b * kr, spart)))
                 return rc;
         for (size_t g = 0; g + 1 < n2; g++)
-            if ((rc = verify_rows(st, p, d_giant_keys[g], sm->seal_giant ? sm->seal_giant[g] : nullptr, (size_t)p->dnum * 2, L + p->K,
+            if ((rc = verify_rows(st, seal_args(p->t, d_giant_keys[g], (size_t)p->dnum * 2, L + p->K, 0), sm->seal_giant ? sm->seal_giant[g] : nullptr,
                                   d_sealed + sl.off[3] + g * kr, spart)))
                 return rc;
     }
@@ -322,14 +284,14 @@ int bsgs_body(const SealedMode *sm, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_
             // ---- the diagonal rows of this step against their seals: on the load that feeds the product, or (n1 > 16) in a sweep before it
             u32 *dflags = d_sealed + sl.off[4] + g * n1 * L;
             const u64 *dseal = sm->seal_diag + g * n1 * L * 2;
-            const bool hit = sf.g == (int)g;
+            const bool hit = sf.sel == (int)g;
             if (fused) {
-                const DiagHit dh{(u32)sf.b, (u32)sf.limb, (u64)sf.coeff, hit ? (u64)1 << sf.bit : 0};
+                const DiagHit dh{(u32)sf.idx, (u32)sf.row, (u64)sf.coeff, hit ? (u64)1 << sf.bit : 0};
                 if ((e = launch_diag_mac_sealed(st, da, spart, dseal, dflags, bc_check(bf.at((int)g, 0), block + lay.off[0]), dh)) != hipSuccess)
                     return hip_fail(e, "launch_diag_mac_sealed");
             } else {
-                const BcCheck hook{nullptr, hit ? 0 : -1, (u32)(sf.b * L + sf.limb), (u64)sf.coeff, (u64)1 << sf.bit};
-                if ((rc = verify_rows(st, p, da.diag, dseal, n1, L, dflags, spart, &hook))) return rc;
+                const BcCheck hook{nullptr, hit ? 0 : -1, (u32)(sf.idx * L + sf.row), (u64)sf.coeff, (u64)1 << sf.bit};
+                if ((rc = verify_rows(st, seal_args(p->t, da.diag, n1, L, 0), dseal, dflags, spart, &hook))) return rc;
             }
         }
         if (!fused && (e = launch_diag_mac_checked(st, da, bc_check(bf.at((int)g, 0), block + lay.off[0]))) != hipSuccess)
@@ -344,16 +306,8 @@ int bsgs_body(const SealedMode *sm, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_
         // ---- (out0, out1) = key switch of sigma(s1) + (t0, out1)
         if ((rc = keyswitch_checked(p, KsForm::CKKS, d_out0, d_out1, tmp + part, d_giant_keys[g - 1], tmp, d_out1, a, block + lay.off[3], st, g == 1 ? kf : StagedFault{}))) return rc;
     }
-    if (!sm || !sm->seal_out) return FHE_OK;
     // ---- both outputs sealed for the next sealed call
-    const uint64_t *outs[2] = {d_out0, d_out1};
-    for (int h = 0; h < 2; h++) {
-        if (!sm->seal_out[h]) continue;
-        const SealArgs sa{outs[h], lp, 0u, (u32)L, (u32)L, (u32)L, logn};
-        hipError_t e = launch_seal(st, sa, spart, sm->seal_out[h], BcCheck{nullptr, -1, 0, 0, 0});
-        if (e != hipSuccess) return hip_fail(e, "launch_seal");
-    }
-    return FHE_OK;
+    return sm ? seal_outputs(st, p->t, sm->seal_out, nullptr, d_out0, d_out1, L, spart) : FHE_OK;
 }
 
 } // namespace

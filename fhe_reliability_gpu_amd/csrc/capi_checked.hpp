@@ -182,14 +182,14 @@ bool ks_sealed_fused(const fhe_keyswitch *p);
 size_t ks_sealed_scratch_words(const fhe_keyswitch *p);
 // the sealed key switch's hook as a call took it (ctx->ks_seal_fault), checked against the plan: the key row and the word exist,
 // and the plan takes the fused route (above the cap there is no fused load to hit)
-int ks_seal_hit(const fhe_ctx::KsSealFault &f, const fhe_keyswitch *p, KsSealHit &hit);
+int ks_seal_hit(const SealHook &f, const fhe_keyswitch *p, KsSealHit &hit);
 // stage 3 of a key switch with a sealed key: the fused launch, or above the cap launch_seal_verify over the key's rows followed by
 // launch_ks_mac_checked; k = the residue check record of stage 3, its flags [2][M]
 int ks_mac_sealed_stage(const fhe_keyswitch *p, hipStream_t st, const KsMacArgs &ka, const BcCheck &k, const SealedKeyStep &key);
 
 // defined in capi_ntt_sealed.cpp
 // the sealed transform's hook as a call of `rows` rows took it (ctx->ntt_seal_fault), checked against that call
-int ntt_seal_hit(const fhe_ctx::NttSealFault &f, size_t rows, int log_n, SealedInputStep &in);
+int ntt_seal_hit(const SealHook &f, size_t rows, int log_n, SealedInputStep &in);
 
 // defined in capi_bgv_checked.cpp
 // one scalar stage: `limbs` rows from data on, of n_poly polynomials poly_stride rows apart (row l of polynomial i at data + (i
@@ -225,7 +225,7 @@ int hmult_checked(KsForm form, KsHookSlot ks_hook, KsHookSlot rs_hook, fhe_ctx *
 
 // defined in capi_tensor_sealed.cpp
 // the sealed tensor product's hook as a call of `units` rows took it (ctx->tensor_seal_fault), checked against that call
-int tensor_seal_hit(const fhe_ctx::TensorSealFault &f, size_t units, int log_n, TensorSealHit &hit);
+int tensor_seal_hit(const SealHook &f, size_t units, int log_n, TensorSealHit &hit);
 // words of ctx->seal_part the sealed tensor product of `units` rows needs
 size_t tensor_sealed_scratch_words(size_t units, int log_n, bool out);
 // the launches of the sealed tensor product over rows [n_poly][limbs]: d = {d0, d1, d2}, ops = {a0, a1, b0, b1}, all 16-byte

@@ -14,35 +14,19 @@
 //                   stay zero.  Without c0's seal c0 goes through the checked permutation exactly as in the checked call
 //   outputs         both sealed, one sweep each
 // A raised input flag does not stop the call.  CKKS form only, like the checked call.
-#include "capi_checked.hpp"
+#include "capi_sealed.hpp"
 #include "galois_seal.hpp"
-
-#include <cstdint>
 
 namespace {
 
-bool misaligned(std::initializer_list<const void *> ptrs)
-{
-    for (const void *q : ptrs)
-        if ((uintptr_t)q % 16) return true;
-    return false;
-}
-
 // the hook as a call took it, checked against that call: n_rot rotations (1 for the standalone call) of `rows` rows
-int gal_seal_hit(const fhe_ctx::GalSealFault &f, size_t n_rot, size_t rows, int log_n, GalSealHit &hit)
+int gal_seal_hit(const SealHook &f, size_t n_rot, size_t rows, int log_n, GalSealHit &hit)
 {
     hit = GalSealHit{-1, 0, 0, 0};
-    if (f.point < 0) return FHE_OK;
-    if ((size_t)f.rot >= n_rot || (size_t)f.row >= rows || (u64)f.coeff >> log_n) return fail(FHE_ERR_INVALID, "fault rotation, row or word outside the call");
-    if (!galois_point_exists(f.point, f.bit, log_n)) return fail(FHE_ERR_INVALID, "bad fault point: 0 takes a bit of the word, 1 a bit of the source index below log N");
-    hit = GalSealHit{f.point, (u32)f.row, (u32)f.coeff, (u64)1 << f.bit};
-    return FHE_OK;
-}
-
-int scratch(fhe_ctx *ctx, size_t words, u64 **out)
-{
-    if (ctx->seal_part.bytes < words * 8) HIP_TRY(ctx->seal_part.alloc(words * 8));
-    *out = ctx->seal_part.as<u64>();
+    if (f.sel < 0) return FHE_OK;
+    if ((size_t)f.idx >= n_rot || !f.inside(rows, log_n)) return fail(FHE_ERR_INVALID, "fault rotation, row or word outside the call");
+    if (!galois_point_exists(f.sel, f.bit, log_n)) return fail(FHE_ERR_INVALID, "bad fault point: 0 takes a bit of the word, 1 a bit of the source index below log N");
+    hit = GalSealHit{f.sel, (u32)f.row, (u32)f.coeff, (u64)1 << f.bit};
     return FHE_OK;
 }
 
@@ -53,20 +37,14 @@ extern "C" {
 int fhe_ctx_inject_fault_galois_sealed(fhe_ctx *ctx, int rot, int point, int row, long long coeff, int bit)
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
-    if (point < 0) {
-        (void)ctx->gal_seal_fault.take();
-        return FHE_OK;
-    }
-    if (point > GAL_AT_INDEX || rot < 0 || row < 0 || coeff < 0 || bit < 0 || bit > 63) return fail(FHE_ERR_INVALID, "bad fault");
-    ctx->gal_seal_fault = fhe_ctx::GalSealFault{rot, point, row, bit, coeff};
-    return FHE_OK;
+    return ctx->gal_seal_fault.arm(GAL_AT_INDEX, point, rot, row, coeff, bit) ? FHE_OK : fail(FHE_ERR_INVALID, "bad fault");
 }
 
 int fhe_automorphism_ntt_sealed(fhe_ctx *ctx, uint64_t *d_dst, const uint64_t *d_src, uint64_t *d_seal_dst, const uint64_t *d_seal_src,
                                 const fhe_ntt_tables *t, size_t n_poly, size_t limbs, size_t start_idx, uint32_t galois_elt, uint32_t *d_flags, void *stream)
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
-    const fhe_ctx::GalSealFault gf = ctx->gal_seal_fault.take();      // one shot, whatever the outcome
+    const SealHook gf = ctx->gal_seal_fault.take();      // one shot, whatever the outcome
     if (!d_dst || !d_src || !d_flags) return fail(FHE_ERR_INVALID, "null argument");
     if (!d_seal_src) return fail(FHE_ERR_INVALID, "a sealed permutation takes the source's seal: null seal (without one nothing checks the permutation)");
     if (d_dst == d_src) return fail(FHE_ERR_INVALID, "the permutation is out of place");
@@ -83,7 +61,7 @@ int fhe_automorphism_ntt_sealed(fhe_ctx *ctx, uint64_t *d_dst, const uint64_t *d
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = pick(ctx, stream);
     u64 *part;
-    if ((rc = scratch(ctx, galois_seal_part_words((u32)units, t->log_n, d_seal_dst != nullptr), &part))) return rc;
+    if ((rc = seal_scratch(ctx, st, galois_seal_part_words((u32)units, t->log_n, d_seal_dst != nullptr), &part))) return rc;
     HIP_TRY(hipMemsetAsync(d_flags, 0, units * sizeof(u32), st));
     const GalSealArgs ga{d_dst, d_src, t->d_lp.as<LimbParams>(), (u32)start_idx, (u32)limbs, (u32)units, (u32)limbs, t->log_n, galois_elt};
     hipError_t e = launch_automorphism_ntt_sealed(st, ga, part, d_seal_src, d_seal_dst, d_flags, hit);
@@ -97,7 +75,7 @@ int fhe_rotate_hoisted_sealed_layout(const fhe_keyswitch *p, size_t n_rot, int o
     int inner[12];
     int rc = fhe_rotate_hoisted_checked_layout(p, n_rot, inner);
     if (rc) return rc;
-    const size_t L = (size_t)p->L, per = L + (size_t)p->dnum * 2 * (size_t)(p->L + p->K);
+    const size_t L = (size_t)p->L, per = L + key_rows(p);
     if (n_rot > ((size_t)0x7FFFFFFF - L - (size_t)inner[11]) / per) return fail(FHE_ERR_INVALID, "too many rotations for one flag buffer");
     out[0] = 0;                                 // c1 rows
     out[1] = (int)L;                            // rotation 0's input block: [c0 rows L][key rows dnum 2 M]
@@ -116,7 +94,7 @@ int fhe_rotate_hoisted_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *const *d
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
     // both hooks belong to this call whatever its outcome
     const StagedFault ft = ctx->hrc_fault.take();
-    const fhe_ctx::GalSealFault gf = ctx->gal_seal_fault.take();
+    const SealHook gf = ctx->gal_seal_fault.take();
     int rc = ksc_scope(ctx, p, a, d_flags, KsForm::CKKS, false);
     if (rc) return rc;
     if (!d_c0 || !d_c1 || (n_rot && (!d_out0 || !d_out1 || !galois_elts || !d_prepared_keys))) return fail(FHE_ERR_INVALID, "null argument");
@@ -132,9 +110,9 @@ int fhe_rotate_hoisted_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *const *d
     const uint64_t *seal_c0 = d_seal_in ? d_seal_in[0] : nullptr, *seal_c1 = d_seal_in ? d_seal_in[1] : nullptr;
     const int L = p->L, M = L + p->K;
     HrcSealed sealed{seal_c0, d_seal_keys, nullptr, 0, nullptr, GalSealHit{-1, 0, 0, 0}, 0};
-    if (gf.point >= 0 && !seal_c0) return fail(FHE_ERR_INVALID, "fault outside the call: without c0's seal no sealed permutation runs");
+    if (gf.sel >= 0 && !seal_c0) return fail(FHE_ERR_INVALID, "fault outside the call: without c0's seal no sealed permutation runs");
     if ((rc = gal_seal_hit(gf, n_rot, (size_t)L, p->log_n, sealed.hit))) return rc;
-    sealed.hit_rot = gf.point >= 0 ? (size_t)gf.rot : 0;
+    sealed.hit_rot = gf.sel >= 0 ? (size_t)gf.idx : 0;
     if (!n_rot) return FHE_OK;
     int lay[6];
     if ((rc = fhe_rotate_hoisted_sealed_layout(p, n_rot, lay))) return rc;
@@ -146,26 +124,15 @@ int fhe_rotate_hoisted_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *const *d
         return fail(FHE_ERR_INVALID, "fault outside the call: with c0's seal the checked permutation covers the sums only");
     hipStream_t st = pick(ctx, stream);
     const size_t words = std::max({ks_sealed_scratch_words(p), seal_part_words((u32)L, p->log_n), galois_seal_part_words((u32)L, p->log_n, false)});
-    if ((rc = scratch(ctx, words, &sealed.part))) return rc;
+    if ((rc = seal_scratch(ctx, st, words, &sealed.part))) return rc;
     sealed.flags_in = d_flags + lay[1];
     sealed.stride = (size_t)lay[2];
     HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)lay[4] * sizeof(u32), st));
-    const LimbParams *lp = p->t->d_lp.as<LimbParams>();
-    if (seal_c1) {
-        const SealArgs sa{d_c1, lp, 0u, (u32)L, (u32)L, (u32)L, p->log_n};
-        hipError_t e = launch_seal_verify(st, sa, sealed.part, seal_c1, BcCheck{d_flags + lay[0], -1, 0, 0, 0});
-        if (e != hipSuccess) return hip_fail(e, "launch_seal_verify");
-    }
+    if ((rc = verify_rows(st, seal_args(p->t, d_c1, 1, L, 0), seal_c1, d_flags + lay[0], sealed.part))) return rc;
     if ((rc = hrc_run(p, d_out0, d_out1, d_c0, d_c1, galois_elts, d_prepared_keys, n_rot, a, d_flags + lay[3], st, hook, &sealed))) return rc;
     for (size_t r = 0; r < n_rot; r++) {
-        const uint64_t *outs[2] = {d_out0[r], d_out1[r]};
-        uint64_t *seals[2] = {d_seal_out0 ? d_seal_out0[r] : nullptr, d_seal_out1 ? d_seal_out1[r] : nullptr};
-        for (int h = 0; h < 2; h++) {
-            if (!seals[h]) continue;
-            const SealArgs sa{outs[h], lp, 0u, (u32)L, (u32)L, (u32)L, p->log_n};
-            hipError_t e = launch_seal(st, sa, sealed.part, seals[h], BcCheck{nullptr, -1, 0, 0, 0});
-            if (e != hipSuccess) return hip_fail(e, "launch_seal");
-        }
+        uint64_t *const seals[2] = {d_seal_out0 ? d_seal_out0[r] : nullptr, d_seal_out1 ? d_seal_out1[r] : nullptr};
+        if ((rc = seal_outputs(st, p->t, seals, nullptr, d_out0[r], d_out1[r], L, sealed.part))) return rc;
     }
     return FHE_OK;
 }

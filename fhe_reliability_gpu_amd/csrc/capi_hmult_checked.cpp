@@ -193,7 +193,7 @@ int hmult_checked(KsForm form, KsHookSlot ks_hook, KsHookSlot rs_hook, fhe_ctx *
     int rc = hmult_validate(form, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, d_flags, kf, rf, lay);
     TensorSealHit hit{-1, 0, 0, 0};
     if (sealed) {
-        const fhe_ctx::TensorSealFault tf = ctx->tensor_seal_fault.take();
+        const SealHook tf = ctx->tensor_seal_fault.take();
         if (!rc) rc = tensor_seal_hit(tf, (size_t)p->L, p->log_n, hit);
     }
     if (rc) {

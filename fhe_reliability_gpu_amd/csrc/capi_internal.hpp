@@ -119,66 +119,17 @@ struct fhe_ctx {
     PointHook seal_fault;  // fhe_ctx_inject_fault_seal: unit = the row, coeff = the word (point 0 when armed)
     PointHook carry_fault; // fhe_ctx_inject_fault_seal_carry: point = CARRY_AT_*, unit = the row, coeff = the word; taken by the carry launch
     int carry_skip = 0;    // that finds carry_skip == 0, every earlier one counts it down
-    // fhe_ctx_inject_fault_bsgs_sealed: one bit of diagonal word (g, b, limb, coeff) as fhe_bsgs_matvec_sealed loads it; g < 0 = disarmed
-    struct DiagSealFault {
-        int g = -1, b = 0, limb = 0, bit = 0;
-        long long coeff = 0;
-        DiagSealFault take()
-        {
-            const DiagSealFault f = *this;
-            g = -1;
-            return f;
-        }
-    } bsgs_seal_fault;
-    // fhe_ctx_inject_fault_tensor_sealed: one bit of word coeff of row `row` of operand op (a0, a1, b0, b1) as fhe_tensor_product_sealed
-    // or fhe_hmult_sealed_fused loads it; op < 0 = disarmed
-    struct TensorSealFault {
-        int op = -1, row = 0, bit = 0;
-        long long coeff = 0;
-        TensorSealFault take()
-        {
-            const TensorSealFault f = *this;
-            op = -1;
-            return f;
-        }
-    } tensor_seal_fault;
-    // fhe_ctx_inject_fault_keyswitch_sealed: one bit of word coeff of key row key_row = (d 2 + h) M + j as the inner product of
-    // fhe_keyswitch_apply_sealed, fhe_rotate_sealed_fused or fhe_hmult_sealed_fused_key loads it; key_row < 0 = disarmed
-    struct KsSealFault {
-        int key_row = -1, bit = 0;
-        long long coeff = 0;
-        KsSealFault take()
-        {
-            const KsSealFault f = *this;
-            key_row = -1;
-            return f;
-        }
-    } ks_seal_fault;
-    // fhe_ctx_inject_fault_galois_sealed: one bit at destination word coeff of row `row` of the sealed permutation of
-    // fhe_automorphism_ntt_sealed (rot = 0) or of c0 in rotation `rot` of fhe_rotate_hoisted_sealed; point = GAL_AT_WORD or
-    // GAL_AT_INDEX, point < 0 = disarmed
-    struct GalSealFault {
-        int rot = 0, point = -1, row = 0, bit = 0;
-        long long coeff = 0;
-        GalSealFault take()
-        {
-            const GalSealFault f = *this;
-            point = -1;
-            return f;
-        }
-    } gal_seal_fault;
-    // fhe_ctx_inject_fault_ntt_sealed: one bit of word coeff of row `row` as the sealed inverse transform of fhe_ntt_inverse_sealed,
-    // fhe_keyswitch_apply_sealed_in or fhe_rotate_sealed_in loads it; row < 0 = disarmed
-    struct NttSealFault {
-        int row = -1, bit = 0;
-        long long coeff = 0;
-        NttSealFault take()
-        {
-            const NttSealFault f = *this;
-            row = -1;
-            return f;
-        }
-    } ntt_seal_fault;
+    // one-shot test hooks of the sealed calls (SealHook, fault_hook.hpp), one per setter; each flips one bit of word coeff as the call
+    // loads it.  The fields, by setter:
+    //   fhe_ctx_inject_fault_bsgs_sealed       sel = g, idx = b, row = limb: diagonal word (g, b, limb, coeff) of fhe_bsgs_matvec_sealed
+    //   fhe_ctx_inject_fault_tensor_sealed     sel = operand (a0, a1, b0, b1), row: fhe_tensor_product_sealed, fhe_hmult_sealed_fused
+    //   fhe_ctx_inject_fault_keyswitch_sealed  sel = row = key_row = (d 2 + h) M + j: the inner product of fhe_keyswitch_apply_sealed,
+    //                                          fhe_rotate_sealed_fused, fhe_hmult_sealed_fused_key and the _in calls
+    //   fhe_ctx_inject_fault_galois_sealed     sel = point (GAL_AT_WORD, GAL_AT_INDEX), idx = rot, row: destination word coeff of `row` of
+    //                                          fhe_automorphism_ntt_sealed (rot = 0) or of c0 in rotation rot of fhe_rotate_hoisted_sealed
+    //   fhe_ctx_inject_fault_ntt_sealed        sel = row: the sealed inverse transform of fhe_ntt_inverse_sealed,
+    //                                          fhe_keyswitch_apply_sealed_in, fhe_rotate_sealed_in
+    SealHook bsgs_seal_fault, tensor_seal_fault, ks_seal_fault, gal_seal_fault, ntt_seal_fault;
     DevBuf seal_part;     // fhe_seal / fhe_seal_verify and the sealed composites: the chunks' partial sums, [rows][chunks][2] (the carried adds: [4] or [6], the sealed tensor product: [8] or [14]; grown on demand)
     DevBuf gal_sums;       // checked Galois permutation: the units' source-side and destination-side sums, [2][units] (grown on demand)
     int geo = 1;           // column-tile geometry of the two-launch path (ntt_launch.hpp)

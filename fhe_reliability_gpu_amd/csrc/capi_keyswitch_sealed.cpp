@@ -12,26 +12,24 @@
 // Above KS_SEAL_MAX_DNUM digits there is no fused instantiation: the stage is then the verifying sweep over the key's rows followed
 // by the checked inner product, writing the same flag words (a key without a stored seal is then not swept at all, as in the
 // sweep-based composites; on the fused route its window is checked all the same).
-#include "capi_checked.hpp"
+#include "capi_sealed.hpp"
 #include "ks_seal.hpp"
-
-#include <cstdint>
 
 bool ks_sealed_fused(const fhe_keyswitch *p) { return p->dnum >= 1 && (u32)p->dnum <= KS_SEAL_MAX_DNUM && p->log_n >= 1; }
 
 // either route: the partials of the fused launch are [M][chunks][2 dnum][2], those of the sweep [dnum 2 M][chunks][2]
 size_t ks_sealed_scratch_words(const fhe_keyswitch *p)
 {
-    return std::max(ks_seal_part_words((u32)(p->L + p->K), p->log_n, (u32)p->dnum), seal_part_words((u32)p->dnum * 2 * (u32)(p->L + p->K), p->log_n));
+    return std::max(ks_seal_part_words((u32)(p->L + p->K), p->log_n, (u32)p->dnum), seal_part_words((u32)key_rows(p), p->log_n));
 }
 
-int ks_seal_hit(const fhe_ctx::KsSealFault &f, const fhe_keyswitch *p, KsSealHit &hit)
+int ks_seal_hit(const SealHook &f, const fhe_keyswitch *p, KsSealHit &hit)
 {
     hit = KsSealHit{0, 0, 0};
-    if (f.key_row < 0) return FHE_OK;
-    if ((size_t)f.key_row >= (size_t)p->dnum * 2 * (p->L + p->K) || (u64)f.coeff >> p->log_n) return fail(FHE_ERR_INVALID, "fault key row or word outside the call");
+    if (f.sel < 0) return FHE_OK;
+    if (!f.inside(key_rows(p), p->log_n)) return fail(FHE_ERR_INVALID, "fault key row or word outside the call");
     if (!ks_sealed_fused(p)) return fail(FHE_ERR_INVALID, "fault outside the call: above the fused cap no load of the inner product digests the key");
-    hit = KsSealHit{(u32)f.key_row, (u64)f.coeff, (u64)1 << f.bit};
+    hit = KsSealHit{(u32)f.row, (u64)f.coeff, (u64)1 << f.bit};
     return FHE_OK;
 }
 
@@ -42,10 +40,8 @@ int ks_mac_sealed_stage(const fhe_keyswitch *p, hipStream_t st, const KsMacArgs 
         e = launch_ks_mac_sealed(st, ka, key.part, key.seal_key, key.flags_key, k, key.hit);
         return e == hipSuccess ? FHE_OK : hip_fail(e, "launch_ks_mac_sealed");
     }
-    if (key.seal_key) {
-        const SealArgs sa{ka.evk, ka.lp, 0u, ka.M, ka.dnum * 2 * ka.M, ka.M, ka.logn};
-        if ((e = launch_seal_verify(st, sa, key.part, key.seal_key, BcCheck{key.flags_key, -1, 0, 0, 0})) != hipSuccess) return hip_fail(e, "launch_seal_verify");
-    }
+    const int rc = verify_rows(st, seal_args(p->t, ka.evk, (size_t)p->dnum * 2, ka.M, 0), key.seal_key, key.flags_key, key.part);
+    if (rc) return rc;
     e = launch_ks_mac_checked(st, ka, k);
     return e == hipSuccess ? FHE_OK : hip_fail(e, "launch_ks_mac_checked");
 }
@@ -55,22 +51,15 @@ extern "C" {
 int fhe_ctx_inject_fault_keyswitch_sealed(fhe_ctx *ctx, int key_row, long long coeff, int bit)
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
-    if (key_row < 0) {
-        (void)ctx->ks_seal_fault.take();
-        return FHE_OK;
-    }
-    if (coeff < 0 || bit < 0 || bit > 63) return fail(FHE_ERR_INVALID, "bad fault");
-    ctx->ks_seal_fault = fhe_ctx::KsSealFault{key_row, bit, coeff};
-    return FHE_OK;
+    return ctx->ks_seal_fault.arm(INT_MAX, key_row, 0, key_row, coeff, bit) ? FHE_OK : fail(FHE_ERR_INVALID, "bad fault");
 }
 
 int fhe_keyswitch_sealed_layout(const fhe_keyswitch *p, int out[4])
 {
     if (!p || !out) return fail(FHE_ERR_INVALID, "null argument");
-    const KsForm form = p->plain_modulus ? KsForm::BGV : KsForm::CKKS;
     out[0] = 0;
-    out[1] = p->dnum * 2 * (p->L + p->K);
-    out[2] = out[1] + ksc_layout(p, form).total;
+    out[1] = (int)key_rows(p);
+    out[2] = out[1] + ksc_layout(p, sealed_form(p).form).total;
     out[3] = ks_sealed_fused(p) ? 1 : 0;
     return FHE_OK;
 }
@@ -79,17 +68,16 @@ int fhe_keyswitch_apply_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0,
                                const uint64_t *d_add0, const uint64_t *d_add1, const fhe_abft *a, const uint64_t *d_seal_key, uint32_t *d_flags, void *stream)
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
-    const bool bgv = p && p->plain_modulus;
-    const KsForm form = bgv ? KsForm::BGV : KsForm::CKKS;
+    const SealedForm f = sealed_form(p);
+    const KsForm form = f.form;
     // both hooks belong to this call whatever its outcome
-    const StagedFault ft = (bgv ? ctx->bgv_ksc_fault : ctx->ksc_fault).take();
-    const fhe_ctx::KsSealFault kf = ctx->ks_seal_fault.take();
+    const StagedFault ft = (ctx->*f.ks_hook).take();
+    const SealHook kf = ctx->ks_seal_fault.take();
     int rc = ksc_scope(ctx, p, a, d_flags, form, false);
     if (rc) return rc;
     if (!d_out0 || !d_out1 || !d_c || !d_evk) return fail(FHE_ERR_INVALID, "null argument");
     if (d_out0 == d_out1) return fail(FHE_ERR_INVALID, "the two output parts must be distinct buffers");
-    for (const void *q : {(const void *)d_out0, (const void *)d_out1, (const void *)d_c, (const void *)d_evk, (const void *)d_add0, (const void *)d_add1})
-        if ((uintptr_t)q % 16) return fail(FHE_ERR_INVALID, "sealed rows are read 16 bytes at a time: the buffers must be 16-byte aligned");
+    if (misaligned({d_out0, d_out1, d_c, d_evk, d_add0, d_add1})) return fail(FHE_ERR_INVALID, "sealed rows are read 16 bytes at a time: the buffers must be 16-byte aligned");
     SealedKeyStep key{d_seal_key, d_flags, nullptr, KsSealHit{0, 0, 0}};
     if ((rc = ks_seal_hit(kf, p, key.hit))) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
@@ -100,9 +88,7 @@ int fhe_keyswitch_apply_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0,
     int lay[4];
     if ((rc = fhe_keyswitch_sealed_layout(p, lay))) return rc;
     hipStream_t st = pick(ctx, stream);
-    const size_t words = ks_sealed_scratch_words(p);
-    if (ctx->seal_part.bytes < words * 8) HIP_TRY(ctx->seal_part.alloc(words * 8));
-    key.part = ctx->seal_part.as<u64>();
+    if ((rc = seal_scratch(ctx, st, ks_sealed_scratch_words(p), &key.part))) return rc;
     HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)lay[1] * sizeof(u32), st));
     return keyswitch_checked(p, form, d_out0, d_out1, d_c, d_evk, d_add0, d_add1, a, d_flags + lay[1], st, ft, &key);
 }

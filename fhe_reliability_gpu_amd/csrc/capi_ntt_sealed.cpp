@@ -10,25 +10,36 @@
 // capi_checked.hpp): no sweep, no copy.  The rotation is a chain of custody: c0 and c1 are verified on the sealed permutation's
 // gather (galois_sealed.hip), sigma(c1)'s seal is written from the registers that are stored, and stage 0 verifies sigma(c1) against
 // that seal on the transform's load.  A raised input flag does not stop a call.
-#include "capi_checked.hpp"
+#include "capi_sealed.hpp"
 #include "galois_seal.hpp"
-#include "seal_check.hpp"
 
-#include <cstdint>
-
-int ntt_seal_hit(const fhe_ctx::NttSealFault &f, size_t rows, int log_n, SealedInputStep &in)
+int ntt_seal_hit(const SealHook &f, size_t rows, int log_n, SealedInputStep &in)
 {
     in.hit_row = in.hit_coeff = 0;
     in.hit_mask = 0;
-    if (f.row < 0) return FHE_OK;
-    if ((size_t)f.row >= rows || (u64)f.coeff >> log_n) return fail(FHE_ERR_INVALID, "fault row or word outside the call");
+    if (f.sel < 0) return FHE_OK;
+    if (!f.inside(rows, log_n)) return fail(FHE_ERR_INVALID, "fault row or word outside the call");
     in.hit_row = (u32)f.row;
     in.hit_coeff = (u32)f.coeff;
     in.hit_mask = (u64)1 << f.bit;
     return FHE_OK;
 }
 
-// one launch per run of an arithmetic path; the seal, the flags, the partials and the hook's row move with the run
+// the sealed transform's record for the run of `len` limbs from limb `off` on, in a call whose row (poly, l) is row poly * limbs + l
+// of the seal, the flags and the partials: all three and the hook's row are addressed from the run's first limb on
+static NttSealIn run_seal_in(const SealedInputStep &in, size_t off, size_t len, size_t limbs, u32 tin)
+{
+    NttSealIn s{in.seal ? in.seal + 2 * off : nullptr, in.flags + off, in.part + off * tin * 3};
+    const size_t hl = in.hit_row % (limbs ? limbs : 1);
+    if (in.hit_mask && hl >= off && hl < off + len) {
+        s.hit_row = in.hit_row - (u32)off;
+        s.hit_coeff = in.hit_coeff;
+        s.hit_mask = in.hit_mask;
+    }
+    return s;
+}
+
+// one launch per run of an arithmetic path
 int KscNtt::launch_sealed(const KscRows &r, const u64 *src, const SealedInputStep &in, int which) const
 {
     const fhe_ntt_tables *t = p->t;
@@ -38,60 +49,25 @@ int KscNtt::launch_sealed(const KscRows &r, const u64 *src, const SealedInputSte
         pa.src = src + (r.row0 + off) * N;
         const size_t slot = (size_t)r.sum0 + r.row0 + off;
         if (r.n_poly != 1 || slot + len > ksc_slots(p)) return fail(FHE_ERR_INVALID, "checked call: a transform's sums lie outside the plan's scratch");
-        NttSealIn s{in.seal ? in.seal + 2 * off : nullptr, in.flags + off, in.part + off * tin * 3};
-        if (in.hit_mask && in.hit_row >= off && in.hit_row < off + len) {
-            s.hit_row = in.hit_row - (u32)off;
-            s.hit_coeff = in.hit_coeff;
-            s.hit_mask = in.hit_mask;
-        }
         hipError_t e = launch_ntt_sealed_inv(st, pa, a->win.as<Tw>(), a->wout.as<Tw>(), a->wout8.as<u64>(), sum_in() + slot * tin, sum_out() + slot * tout, p->log_n,
-                                             path, which, s);
+                                             path, which, run_seal_in(in, off, len, r.count, tin));
         return e == hipSuccess ? FHE_OK : hip_fail(e, "launch_ntt_sealed_inv");
     });
 }
-
-namespace {
-
-KsForm plan_form(const fhe_keyswitch *p) { return p && p->plain_modulus ? KsForm::BGV : KsForm::CKKS; }
-StagedFault take_ks_hook(fhe_ctx *ctx, const fhe_keyswitch *p) { return (p && p->plain_modulus ? ctx->bgv_ksc_fault : ctx->ksc_fault).take(); }
-size_t key_rows(const fhe_keyswitch *p) { return (size_t)p->dnum * 2 * (p->L + p->K); }
-
-bool misaligned(std::initializer_list<const void *> ptrs)
-{
-    for (const void *q : ptrs)
-        if ((uintptr_t)q % 16) return true;
-    return false;
-}
-
-// the context's partial-sum scratch, at least `words` long
-int scratch(fhe_ctx *ctx, size_t words, u64 **out)
-{
-    if (ctx->seal_part.bytes < words * 8) HIP_TRY(ctx->seal_part.alloc(words * 8));
-    *out = ctx->seal_part.as<u64>();
-    return FHE_OK;
-}
-
-} // namespace
 
 extern "C" {
 
 int fhe_ctx_inject_fault_ntt_sealed(fhe_ctx *ctx, int row, long long coeff, int bit)
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
-    if (row < 0) {
-        (void)ctx->ntt_seal_fault.take();
-        return FHE_OK;
-    }
-    if (coeff < 0 || bit < 0 || bit > 63) return fail(FHE_ERR_INVALID, "bad fault");
-    ctx->ntt_seal_fault = fhe_ctx::NttSealFault{row, bit, coeff};
-    return FHE_OK;
+    return ctx->ntt_seal_fault.arm(INT_MAX, row, 0, row, coeff, bit) ? FHE_OK : fail(FHE_ERR_INVALID, "bad fault");
 }
 
 int fhe_ntt_inverse_sealed(fhe_ctx *ctx, uint64_t *d_dst, const uint64_t *d_src, const fhe_ntt_tables *t, const fhe_abft *a, size_t n_poly, size_t limbs,
                            size_t start_idx, const uint64_t *d_seal_src, uint32_t *d_flags, void *stream)
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
-    const fhe_ctx::NttSealFault nf = ctx->ntt_seal_fault.take();      // one shot, whatever the outcome
+    const SealHook nf = ctx->ntt_seal_fault.take();      // one shot, whatever the outcome
     if (!d_dst || !d_src || !t || !a || !d_flags) return fail(FHE_ERR_INVALID, "null argument");
     if (a->t != t) return fail(FHE_ERR_INVALID, "the detector was made for another table set");
     int rc = check_range(t, n_poly, limbs, start_idx);
@@ -100,8 +76,8 @@ int fhe_ntt_inverse_sealed(fhe_ctx *ctx, uint64_t *d_dst, const uint64_t *d_src,
     if (ctx->mode != 0 || ctx->resident || ctx->packed_on || ctx->only_pass >= 0 || !ntt_checked_supported(t->log_n))
         return fail(FHE_ERR_UNSUPPORTED, "the sealed inverse transform runs the checked two-launch transform: not with ntt_mode=1, ntt_resident, ntt_packed, a single-pass hook, or N < 2^5");
     const size_t units = n_poly * limbs, N = (size_t)1 << t->log_n;
-    SealedInputStep hit{};
-    if ((rc = ntt_seal_hit(nf, units, t->log_n, hit))) return rc;
+    SealedInputStep in{d_seal_src, d_flags, nullptr, 0, 0, 0};
+    if ((rc = ntt_seal_hit(nf, units, t->log_n, in))) return rc;
     // the checked transforms' hook between the two launches (fhe_ctx_inject_fault), two-launch sizes, as fhe_ntt_inverse_checked takes it
     const bool between = ctx->fault_idx >= 0 && t->log_n >= 13;
     const long long fidx = ctx->fault_idx;
@@ -120,24 +96,15 @@ int fhe_ntt_inverse_sealed(fhe_ctx *ctx, uint64_t *d_dst, const uint64_t *d_src,
         HIP_TRY(m->sum_in.alloc(units * 16 * tin));
         HIP_TRY(m->sum_out.alloc(units * 16 * tout));
     }
-    u64 *part;
-    if ((rc = scratch(ctx, ntt_seal_part_words((u32)units, t->log_n), &part))) return rc;
+    if ((rc = seal_scratch(ctx, st, ntt_seal_part_words((u32)units, t->log_n), &in.part))) return rc;
     HIP_TRY(hipMemsetAsync(d_flags, 0, 2 * units * sizeof(u32), st));
-    // row (poly, l) of the call is row poly * limbs + l of the seal, the flags and the sums; a run of limbs addresses them from its
-    // first limb on
+    // row (poly, l) of the call is row poly * limbs + l of the sums as well; a run of limbs addresses them from its first limb on
     auto run = [&](int which) -> int {
         return for_each_run(t, limbs, start_idx, [&](size_t off, size_t len, int path) -> int {
             PassArgs pa{d_dst + off * N, t->d_lp.as<LimbParams>(), (u32)(start_idx + off), (u32)len, (u32)(n_poly * len), (u32)limbs, nullptr};
             if (d_src != d_dst) pa.src = d_src + off * N;
-            NttSealIn s{d_seal_src ? d_seal_src + 2 * off : nullptr, d_flags + off, part + off * tin * 3};
-            const size_t hl = hit.hit_row % (limbs ? limbs : 1);
-            if (hit.hit_mask && hl >= off && hl < off + len) {
-                s.hit_row = hit.hit_row - (u32)off;
-                s.hit_coeff = hit.hit_coeff;
-                s.hit_mask = hit.hit_mask;
-            }
             hipError_t e = launch_ntt_sealed_inv(st, pa, a->win.as<Tw>(), a->wout.as<Tw>(), a->wout8.as<u64>(), m->sum_in.as<u64>() + off * tin,
-                                                 m->sum_out.as<u64>() + off * tout, t->log_n, path, which, s);
+                                                 m->sum_out.as<u64>() + off * tout, t->log_n, path, which, run_seal_in(in, off, len, limbs, tin));
             return e == hipSuccess ? FHE_OK : hip_fail(e, "launch_ntt_sealed_inv");
         });
     };
@@ -158,7 +125,7 @@ int fhe_keyswitch_sealed_in_layout(const fhe_keyswitch *p, int out[5])
     out[0] = 0;
     out[1] = p->L;
     out[2] = out[1] + (int)key_rows(p);
-    out[3] = out[2] + ksc_layout(p, plan_form(p)).total;
+    out[3] = out[2] + ksc_layout(p, sealed_form(p).form).total;
     out[4] = ks_sealed_fused(p) ? 1 : 0;
     return FHE_OK;
 }
@@ -168,11 +135,12 @@ int fhe_keyswitch_apply_sealed_in(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_ou
                                   uint32_t *d_flags, void *stream)
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
-    const KsForm form = plan_form(p);
+    const SealedForm f = sealed_form(p);
+    const KsForm form = f.form;
     // the three hooks belong to this call whatever its outcome
-    const StagedFault ft = take_ks_hook(ctx, p);
-    const fhe_ctx::KsSealFault kf = ctx->ks_seal_fault.take();
-    const fhe_ctx::NttSealFault nf = ctx->ntt_seal_fault.take();
+    const StagedFault ft = (ctx->*f.ks_hook).take();
+    const SealHook kf = ctx->ks_seal_fault.take();
+    const SealHook nf = ctx->ntt_seal_fault.take();
     if (!d_seal_c) return fail(FHE_ERR_INVALID, "null d_seal_c: nothing would verify the input limbs (fhe_keyswitch_apply_sealed takes none)");
     int rc = ksc_scope(ctx, p, a, d_flags, form, false);
     if (rc) return rc;
@@ -193,7 +161,7 @@ int fhe_keyswitch_apply_sealed_in(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_ou
     if ((rc = ksc_hook(p, form, ft, p->acc.as<u64>(), d_add0 != nullptr, d_add1 != nullptr, h))) return rc;
     hipStream_t st = pick(ctx, stream);
     u64 *part;
-    if ((rc = scratch(ctx, std::max(ks_sealed_scratch_words(p), ntt_seal_part_words((u32)p->L, p->log_n)), &part))) return rc;
+    if ((rc = seal_scratch(ctx, st, std::max(ks_sealed_scratch_words(p), ntt_seal_part_words((u32)p->L, p->log_n)), &part))) return rc;
     key.part = in.part = part;      // stage 0's verdict is out before stage 3 starts on the same stream
     HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)lay[2] * sizeof(u32), st));
     return keyswitch_checked(p, form, d_out0, d_out1, d_c, d_evk, d_add0, d_add1, a, d_flags + lay[2], st, ft, &key, &in);
@@ -207,7 +175,7 @@ int fhe_rotate_sealed_in_layout(const fhe_keyswitch *p, int out[7])
     out[2] = 2 * p->L;
     out[3] = 3 * p->L;
     out[4] = out[3] + (int)key_rows(p);
-    out[5] = out[4] + ksc_layout(p, plan_form(p)).total;
+    out[5] = out[4] + ksc_layout(p, sealed_form(p).form).total;
     out[6] = ks_sealed_fused(p) ? 1 : 0;
     return FHE_OK;
 }
@@ -217,10 +185,11 @@ int fhe_rotate_sealed_in(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint6
                          uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
-    const KsForm form = plan_form(p);
-    const StagedFault ft = take_ks_hook(ctx, p);
-    const fhe_ctx::KsSealFault kf = ctx->ks_seal_fault.take();
-    const fhe_ctx::NttSealFault nf = ctx->ntt_seal_fault.take();
+    const SealedForm f = sealed_form(p);
+    const KsForm form = f.form;
+    const StagedFault ft = (ctx->*f.ks_hook).take();
+    const SealHook kf = ctx->ks_seal_fault.take();
+    const SealHook nf = ctx->ntt_seal_fault.take();
     int rc = ksc_scope(ctx, p, a, d_flags, form, false);
     if (rc) return rc;
     if (!d_out0 || !d_out1 || !d_c0 || !d_c1 || !d_galois_key) return fail(FHE_ERR_INVALID, "null argument");
@@ -246,7 +215,7 @@ int fhe_rotate_sealed_in(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint6
     const size_t pw = std::max(std::max(ks_sealed_scratch_words(p), ntt_seal_part_words((u32)L, p->log_n)),
                                std::max(galois_seal_part_words((u32)L, p->log_n, true), seal_part_words((u32)L, p->log_n)));
     u64 *part;
-    if ((rc = scratch(ctx, pw + 2 * L, &part))) return rc;
+    if ((rc = seal_scratch(ctx, st, pw + 2 * L, &part))) return rc;
     u64 *seal_sig1 = part + pw;
     key.part = in.part = part;
     in.seal = seal_sig1;
@@ -261,13 +230,7 @@ int fhe_rotate_sealed_in(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint6
     if (e == hipSuccess) e = launch_automorphism_ntt_sealed(st, g1, part, d_seal_in[1], seal_sig1, d_flags + lay[1], no_hit);
     if (e != hipSuccess) return hip_fail(e, "launch_automorphism_ntt_sealed");
     if ((rc = keyswitch_checked(p, form, d_out0, d_out1, sig1, d_galois_key, sig0, nullptr, a, d_flags + lay[4], st, ft, &key, &in))) return rc;
-    const uint64_t *outs[2] = {d_out0, d_out1};
-    for (int hf = 0; hf < 2; hf++) {
-        if (!d_seal_out || !d_seal_out[hf]) continue;
-        const SealArgs sa{outs[hf], lp, 0u, (u32)L, (u32)L, (u32)L, p->log_n};
-        if ((e = launch_seal(st, sa, part, d_seal_out[hf], BcCheck{nullptr, -1, 0, 0, 0})) != hipSuccess) return hip_fail(e, "launch_seal");
-    }
-    return FHE_OK;
+    return seal_outputs(st, p->t, d_seal_out, nullptr, d_out0, d_out1, L, part);
 }
 
 } // extern "C"

@@ -12,20 +12,9 @@
 // k_row_repair, and the repairing composites are the sealed composites' own bodies in another mode (RepairMode): each given
 // (seal, locator) pair is repaired in place instead of only verified, the outputs get locators when asked, and one report block
 // follows the flags, covering the input and key rows in the order of their flag words.
-#include "capi_checked.hpp"
-#include "seal_check.hpp"
-
-#include <cstdint>
+#include "capi_sealed.hpp"
 
 namespace {
-
-// the partial-sum scratch of the context, at least `words` long
-int seal_scratch(fhe_ctx *ctx, size_t words, u64 **out)
-{
-    if (ctx->seal_part.bytes < words * 8) HIP_TRY(ctx->seal_part.alloc(words * 8));
-    *out = ctx->seal_part.as<u64>();
-    return FHE_OK;
-}
 
 int seal_window(const fhe_ntt_tables *t, const uint64_t *d_words, size_t n_poly, size_t limbs, size_t start_idx)
 {
@@ -33,23 +22,6 @@ int seal_window(const fhe_ntt_tables *t, const uint64_t *d_words, size_t n_poly,
     if (rc) return rc;
     if (t->log_n < 1) return fail(FHE_ERR_UNSUPPORTED, "a sealed row has at least two words");
     if ((uintptr_t)d_words % 16) return fail(FHE_ERR_INVALID, "sealed rows are read 16 bytes at a time: the buffer must be 16-byte aligned");
-    return FHE_OK;
-}
-
-SealArgs seal_args(const fhe_ntt_tables *t, const uint64_t *d_words, size_t n_poly, size_t limbs, size_t start_idx)
-{
-    return SealArgs{d_words, t->d_lp.as<LimbParams>(), (u32)start_idx, (u32)limbs, (u32)(n_poly * limbs), (u32)limbs, t->log_n};
-}
-
-// the seal hook a call of `units` rows took, checked against that call
-int seal_fault(const PointFault &f, size_t units, int log_n, BcCheck &k)
-{
-    if (f.point < 0) return FHE_OK;
-    if (f.unit >= units || f.coeff >> log_n) return fail(FHE_ERR_INVALID, "fault row or word outside the call");
-    k.fault_point = 0;
-    k.fault_unit = f.unit;
-    k.fault_coeff = f.coeff;
-    k.fault_mask = (u64)1 << f.bit;
     return FHE_OK;
 }
 
@@ -69,33 +41,15 @@ struct SealedRows {
     int flag_off;
 };
 
-// d_report = the report block of the whole call, one record of four words per flag word of the input and key rows
-int verify_rows(hipStream_t st, const fhe_ntt_tables *t, const SealedRows &r, uint32_t *d_flags, uint64_t *d_report, u64 *part)
+// the operand verified and, with a locator, repaired; d_report = the report block of the whole call, one record of four words per
+// flag word of the input and key rows
+int verify_or_repair(hipStream_t st, const fhe_ntt_tables *t, const SealedRows &r, uint32_t *d_flags, uint64_t *d_report, u64 *part)
 {
-    if (!r.seal) return FHE_OK;
     const SealArgs sa = seal_args(t, r.words, r.n_poly, r.limbs, 0);
-    hipError_t e = launch_seal_verify(st, sa, part, r.seal, BcCheck{d_flags + r.flag_off, -1, 0, 0, 0});
-    if (e != hipSuccess) return hip_fail(e, "launch_seal_verify");
-    if (!r.locator) return FHE_OK;
-    e = launch_seal_repair(st, sa, r.seal, r.locator, d_flags + r.flag_off, d_report + 4 * (size_t)r.flag_off);
+    const int rc = verify_rows(st, sa, r.seal, d_flags + r.flag_off, part);
+    if (rc || !r.seal || !r.locator) return rc;
+    hipError_t e = launch_seal_repair(st, sa, r.seal, r.locator, d_flags + r.flag_off, d_report + 4 * (size_t)r.flag_off);
     return e == hipSuccess ? FHE_OK : hip_fail(e, "launch_seal_repair");
-}
-
-int seal_outputs(hipStream_t st, const fhe_ntt_tables *t, uint64_t *const *d_seal_out, uint64_t *const *d_loc_out, const uint64_t *d_out0,
-                 const uint64_t *d_out1, size_t limbs, u64 *part)
-{
-    const uint64_t *outs[2] = {d_out0, d_out1};
-    for (int h = 0; h < 2; h++) {
-        if (d_seal_out && d_seal_out[h]) {
-            hipError_t e = launch_seal(st, seal_args(t, outs[h], 1, limbs, 0), part, d_seal_out[h], BcCheck{nullptr, -1, 0, 0, 0});
-            if (e != hipSuccess) return hip_fail(e, "launch_seal");
-        }
-        if (d_loc_out && d_loc_out[h]) {
-            hipError_t e = launch_seal_locator(st, seal_args(t, outs[h], 1, limbs, 0), part, d_loc_out[h]);
-            if (e != hipSuccess) return hip_fail(e, "launch_seal_locator");
-        }
-    }
-    return FHE_OK;
 }
 
 // a repairing call takes seal and locator of an operand together or not at all
@@ -110,32 +64,12 @@ bool unpaired(const RepairMode *rm, const uint64_t *const *d_seal_in, int n, con
 // where the report block of a repairing composite starts, in flag words: 16-byte aligned after the sealed call's layout
 int report_offset(int sealed_total) { return (sealed_total + 3) & ~3; }
 
-// the form of the checked call a sealed composite runs, with that form's hook records
-struct SealedForm {
-    KsForm form;
-    KsHookSlot ks_hook, rs_hook;
-};
-SealedForm sealed_form(const fhe_keyswitch *p)
-{
-    if (p && p->plain_modulus) return SealedForm{KsForm::BGV, &fhe_ctx::bgv_ksc_fault, &fhe_ctx::bgv_rsc_fault};
-    return SealedForm{KsForm::CKKS, &fhe_ctx::ksc_fault, &fhe_ctx::rsc_fault};
-}
-
-size_t key_rows(const fhe_keyswitch *p) { return (size_t)p->dnum * 2 * (p->L + p->K); }
-
 // scratch for the largest launch of a sealed composite (the key's rows; tensor: or the sealed tensor step's), before anything is
 // launched
-int sealed_scratch(fhe_ctx *ctx, const fhe_keyswitch *p, bool tensor, u64 **part)
+int sealed_scratch(fhe_ctx *ctx, hipStream_t st, const fhe_keyswitch *p, bool tensor, u64 **part)
 {
     const size_t key = seal_part_words((u32)key_rows(p), p->log_n);
-    return seal_scratch(ctx, tensor ? std::max(key, tensor_sealed_scratch_words((size_t)p->L, p->log_n, false)) : key, part);
-}
-
-bool misaligned(std::initializer_list<const void *> ptrs)
-{
-    for (const void *q : ptrs)
-        if ((uintptr_t)q % 16) return true;
-    return false;
+    return seal_scratch(ctx, st, tensor ? std::max(key, tensor_sealed_scratch_words((size_t)p->L, p->log_n, false)) : key, part);
 }
 
 } // namespace
@@ -158,12 +92,13 @@ int fhe_seal(fhe_ctx *ctx, uint64_t *d_seal, const uint64_t *d_words, const fhe_
     if (rc) return rc;
     const size_t units = n_poly * limbs;
     BcCheck k{nullptr, -1, 0, 0, 0};
-    if ((rc = seal_fault(f, units, t->log_n, k))) return rc;
+    if ((rc = row_fault(f, 0, units, t->log_n, k))) return rc;
     if (!units) return FHE_OK;
     HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = pick(ctx, stream);
     u64 *part;
-    if ((rc = seal_scratch(ctx, seal_part_words((u32)units, t->log_n), &part))) return rc;
-    hipError_t e = launch_seal(pick(ctx, stream), seal_args(t, d_words, n_poly, limbs, start_idx), part, d_seal, k);
+    if ((rc = seal_scratch(ctx, st, seal_part_words((u32)units, t->log_n), &part))) return rc;
+    hipError_t e = launch_seal(st, seal_args(t, d_words, n_poly, limbs, start_idx), part, d_seal, k);
     return e == hipSuccess ? FHE_OK : hip_fail(e, "launch_seal");
 }
 
@@ -177,12 +112,12 @@ int fhe_seal_verify(fhe_ctx *ctx, const uint64_t *d_words, const uint64_t *d_sea
     if (rc) return rc;
     const size_t units = n_poly * limbs;
     BcCheck k{d_flags, -1, 0, 0, 0};
-    if ((rc = seal_fault(f, units, t->log_n, k))) return rc;
+    if ((rc = row_fault(f, 0, units, t->log_n, k))) return rc;
     if (!units) return FHE_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = pick(ctx, stream);
     u64 *part;
-    if ((rc = seal_scratch(ctx, seal_part_words((u32)units, t->log_n), &part))) return rc;
+    if ((rc = seal_scratch(ctx, st, seal_part_words((u32)units, t->log_n), &part))) return rc;
     HIP_TRY(hipMemsetAsync(d_flags, 0, units * sizeof(u32), st));
     hipError_t e = launch_seal_verify(st, seal_args(t, d_words, n_poly, limbs, start_idx), part, d_seal, k);
     return e == hipSuccess ? FHE_OK : hip_fail(e, "launch_seal_verify");
@@ -198,9 +133,10 @@ int fhe_seal_locator(fhe_ctx *ctx, uint64_t *d_locator, const uint64_t *d_words,
     const size_t units = n_poly * limbs;
     if (!units) return FHE_OK;
     HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = pick(ctx, stream);
     u64 *part;
-    if ((rc = seal_scratch(ctx, seal_part_words((u32)units, t->log_n), &part))) return rc;
-    hipError_t e = launch_seal_locator(pick(ctx, stream), seal_args(t, d_words, n_poly, limbs, start_idx), part, d_locator);
+    if ((rc = seal_scratch(ctx, st, seal_part_words((u32)units, t->log_n), &part))) return rc;
+    hipError_t e = launch_seal_locator(st, seal_args(t, d_words, n_poly, limbs, start_idx), part, d_locator);
     return e == hipSuccess ? FHE_OK : hip_fail(e, "launch_seal_locator");
 }
 
@@ -215,12 +151,12 @@ int fhe_seal_repair(fhe_ctx *ctx, uint64_t *d_words, const uint64_t *d_seal, con
     if ((uintptr_t)d_report % 16) return fail(FHE_ERR_INVALID, "a report record is written 16 bytes at a time: the buffer must be 16-byte aligned");
     const size_t units = n_poly * limbs;
     BcCheck k{d_flags, -1, 0, 0, 0};
-    if ((rc = seal_fault(f, units, t->log_n, k))) return rc;
+    if ((rc = row_fault(f, 0, units, t->log_n, k))) return rc;
     if (!units) return FHE_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = pick(ctx, stream);
     u64 *part;
-    if ((rc = seal_scratch(ctx, seal_part_words((u32)units, t->log_n), &part))) return rc;
+    if ((rc = seal_scratch(ctx, st, seal_part_words((u32)units, t->log_n), &part))) return rc;
     HIP_TRY(hipMemsetAsync(d_flags, 0, units * sizeof(u32), st));
     const SealArgs sa = seal_args(t, d_words, n_poly, limbs, start_idx);
     hipError_t e = launch_seal_verify(st, sa, part, d_seal, k);      // the hook lives in this sweep only
@@ -258,7 +194,7 @@ static int hmult_sealed_body(const RepairMode *rm, bool fused, bool fused_key, f
     const SealedForm f = sealed_form(p);
     SealedTensorStep step{d_seal_in, {nullptr, nullptr, nullptr, nullptr}};
     SealedKeyStep kstep{d_seal_key, nullptr, nullptr, KsSealHit{0, 0, 0}};
-    const fhe_ctx::KsSealFault kf = fused_key ? ctx->ks_seal_fault.take() : fhe_ctx::KsSealFault{};      // one shot, whatever the outcome
+    const SealHook kf = fused_key ? ctx->ks_seal_fault.take() : SealHook{};      // one shot, whatever the outcome
     auto checked = [&](uint32_t *flags) {
         return hmult_checked(f.form, f.ks_hook, f.rs_hook, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, flags, stream,
                              fused ? &step : nullptr, fused_key ? &kstep : nullptr);
@@ -295,7 +231,7 @@ static int hmult_sealed_body(const RepairMode *rm, bool fused, bool fused_key, f
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = pick(ctx, stream);
     u64 *part;
-    if ((rc = sealed_scratch(ctx, p, fused, &part))) return rc;
+    if ((rc = sealed_scratch(ctx, st, p, fused, &part))) return rc;
     kstep.flags_key = d_flags + lay[4];
     kstep.part = part;
     HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)lay[5] * sizeof(u32), st));
@@ -305,10 +241,10 @@ static int hmult_sealed_body(const RepairMode *rm, bool fused, bool fused_key, f
     const uint64_t *ops[4] = {d_a0, d_a1, d_b0, d_b1};
     for (int i = 0; i < 4 && !fused; i++) {
         const SealedRows r{ops[i], d_seal_in ? d_seal_in[i] : nullptr, rm && rm->loc_in ? rm->loc_in[i] : nullptr, 1, L, lay[i]};
-        if ((rc = verify_rows(st, p->t, r, d_flags, d_report, part))) return rc;
+        if ((rc = verify_or_repair(st, p->t, r, d_flags, d_report, part))) return rc;
     }
     const SealedRows key{d_relin_key, d_seal_key, rm ? rm->loc_key : nullptr, (size_t)p->dnum * 2, L + p->K, lay[4]};
-    if (!fused_key && (rc = verify_rows(st, p->t, key, d_flags, d_report, part))) return rc;
+    if (!fused_key && (rc = verify_or_repair(st, p->t, key, d_flags, d_report, part))) return rc;
     if ((rc = checked(d_flags + lay[5]))) return rc;
     return seal_outputs(st, p->t, d_seal_out, rm ? rm->loc_out : nullptr, d_out0, d_out1, rescale ? L - 1 : L, part);
 }
@@ -379,7 +315,7 @@ static int rotate_sealed_body(const RepairMode *rm, bool fused_key, fhe_ctx *ctx
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
     const SealedForm f = sealed_form(p);
     SealedKeyStep kstep{d_seal_key, nullptr, nullptr, KsSealHit{0, 0, 0}};
-    const fhe_ctx::KsSealFault kf = fused_key ? ctx->ks_seal_fault.take() : fhe_ctx::KsSealFault{};      // one shot, whatever the outcome
+    const SealHook kf = fused_key ? ctx->ks_seal_fault.take() : SealHook{};      // one shot, whatever the outcome
     auto checked = [&](uint32_t *flags) {
         return rotate_checked(f.form, f.ks_hook, ctx, p, d_out0, d_out1, d_c0, d_c1, galois_elt, d_galois_key, a, flags, stream, fused_key ? &kstep : nullptr);
     };
@@ -404,7 +340,7 @@ static int rotate_sealed_body(const RepairMode *rm, bool fused_key, fhe_ctx *ctx
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = pick(ctx, stream);
     u64 *part;
-    if ((rc = sealed_scratch(ctx, p, false, &part))) return rc;
+    if ((rc = sealed_scratch(ctx, st, p, false, &part))) return rc;
     kstep.flags_key = d_flags + lay[2];
     kstep.part = part;
     HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)lay[3] * sizeof(u32), st));
@@ -414,10 +350,10 @@ static int rotate_sealed_body(const RepairMode *rm, bool fused_key, fhe_ctx *ctx
     const uint64_t *ops[2] = {d_c0, d_c1};
     for (int i = 0; i < 2; i++) {
         const SealedRows r{ops[i], d_seal_in ? d_seal_in[i] : nullptr, rm && rm->loc_in ? rm->loc_in[i] : nullptr, 1, L, lay[i]};
-        if ((rc = verify_rows(st, p->t, r, d_flags, d_report, part))) return rc;
+        if ((rc = verify_or_repair(st, p->t, r, d_flags, d_report, part))) return rc;
     }
     const SealedRows key{d_galois_key, d_seal_key, rm ? rm->loc_key : nullptr, (size_t)p->dnum * 2, L + p->K, lay[2]};
-    if (!fused_key && (rc = verify_rows(st, p->t, key, d_flags, d_report, part))) return rc;
+    if (!fused_key && (rc = verify_or_repair(st, p->t, key, d_flags, d_report, part))) return rc;
     if ((rc = checked(d_flags + lay[3]))) return rc;
     return seal_outputs(st, p->t, d_seal_out, rm ? rm->loc_out : nullptr, d_out0, d_out1, L, part);
 }

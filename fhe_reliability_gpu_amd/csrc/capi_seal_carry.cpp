@@ -8,27 +8,10 @@
 // rotated copy, then one carried add per half back into the accumulators, seals updated in place.  A step's flag block is
 //     [fhe_rotate_sealed_layout's block][add rows of c0: L][add rows of c1: L]
 // and step s + 1 verifies on entry what step s's adds stored, so the chain needs no closing sweep.
-#include "capi_checked.hpp"
+#include "capi_sealed.hpp"
 #include "seal_carry.hpp"
 
-#include <cstdint>
-
 namespace {
-
-// the partial-sum scratch of the context, at least `words` long
-int carry_scratch(fhe_ctx *ctx, size_t words, u64 **out)
-{
-    if (ctx->seal_part.bytes < words * 8) HIP_TRY(ctx->seal_part.alloc(words * 8));
-    *out = ctx->seal_part.as<u64>();
-    return FHE_OK;
-}
-
-bool misaligned(std::initializer_list<const void *> ptrs)
-{
-    for (const void *q : ptrs)
-        if ((uintptr_t)q % 16) return true;
-    return false;
-}
 
 // the carry hook as a call of n carry launches meets it: the record when it fires in one of them (*at = which), a disarmed one
 // (*at = -1) when it is not armed or fires later -- those launches are then counted off
@@ -43,18 +26,6 @@ PointFault carry_take(fhe_ctx *ctx, int n, int *at)
     *at = ctx->carry_skip;
     ctx->carry_skip = 0;
     return ctx->carry_fault.take();
-}
-
-// the record a carry launch of `units` rows reads, checked against that launch
-int carry_fault(const PointFault &f, size_t units, int log_n, BcCheck &k)
-{
-    if (f.point < 0) return FHE_OK;
-    if (f.unit >= units || f.coeff >> log_n) return fail(FHE_ERR_INVALID, "fault row or word outside the call");
-    k.fault_point = f.point;
-    k.fault_unit = f.unit;
-    k.fault_coeff = f.coeff;
-    k.fault_mask = (u64)1 << f.bit;
-    return FHE_OK;
 }
 
 PointwiseArgs carry_args(const fhe_ntt_tables *t, uint64_t *c, const uint64_t *a, const uint64_t *b, size_t n_poly, size_t limbs, size_t start_idx)
@@ -79,12 +50,12 @@ int carry_body(bool sub, fhe_ctx *ctx, uint64_t *d_c, const uint64_t *d_a, const
     if (misaligned({d_c, d_a, d_b})) return fail(FHE_ERR_INVALID, "sealed rows are read 16 bytes at a time: the buffers must be 16-byte aligned");
     const size_t units = n_poly * limbs;
     BcCheck k{d_flags, -1, 0, 0, 0};
-    if ((rc = carry_fault(f, units, t->log_n, k))) return rc;
+    if ((rc = row_fault(f, f.point, units, t->log_n, k))) return rc;
     if (!units) return FHE_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = pick(ctx, stream);
     u64 *part;
-    if ((rc = carry_scratch(ctx, carry_part_words((u32)units, t->log_n, d_locator_c != nullptr), &part))) return rc;
+    if ((rc = seal_scratch(ctx, st, carry_part_words((u32)units, t->log_n, d_locator_c != nullptr), &part))) return rc;
     HIP_TRY(hipMemsetAsync(d_flags, 0, units * sizeof(u32), st));
     hipError_t e = launch_modadd_carry(st, carry_args(t, d_c, d_a, d_b, n_poly, limbs, start_idx), sub, part, d_seal_a, d_seal_b, d_seal_c, d_locator_a,
                                        d_locator_b, d_locator_c, k);
@@ -159,7 +130,7 @@ int fhe_rotate_sum_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_c0, uint64
     }
     const size_t L = p->L;
     BcCheck armed{nullptr, -1, 0, 0, 0};
-    if ((rc = carry_fault(f, L, p->log_n, armed))) return rc;
+    if ((rc = row_fault(f, f.point, L, p->log_n, armed))) return rc;
     hipStream_t st = pick(ctx, stream);
     for (int s = 0; s < n_steps; s++) {
         uint32_t *block = d_flags + (size_t)s * lay[0];
@@ -168,7 +139,7 @@ int fhe_rotate_sum_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_c0, uint64
                                d_seal_tmp, block, stream);
         if (rc) return rc;
         u64 *part;
-        if ((rc = carry_scratch(ctx, carry_part_words((u32)L, p->log_n, false), &part))) return rc;
+        if ((rc = seal_scratch(ctx, st, carry_part_words((u32)L, p->log_n, false), &part))) return rc;
         HIP_TRY(hipMemsetAsync(block + lay[1], 0, 2 * L * sizeof(u32), st));
         uint64_t *acc[2] = {d_c0, d_c1};
         const uint64_t *rot[2] = {d_tmp0, d_tmp1};

@@ -8,17 +8,15 @@
 //     [rows of a0][rows of a1][rows of b0][rows of b1][the tensor block, [rows][3] as fhe_tensor_product_checked's]
 // with R = n_poly * limbs rows each.  A raised operand flag does not stop the call: the words are the product of the operands as
 // they were loaded, and the residue identity holds on them.
-#include "capi_checked.hpp"
+#include "capi_sealed.hpp"
 #include "tensor_seal.hpp"
 
-#include <cstdint>
-
-int tensor_seal_hit(const fhe_ctx::TensorSealFault &f, size_t units, int log_n, TensorSealHit &hit)
+int tensor_seal_hit(const SealHook &f, size_t units, int log_n, TensorSealHit &hit)
 {
     hit = TensorSealHit{-1, 0, 0, 0};
-    if (f.op < 0) return FHE_OK;
-    if ((size_t)f.row >= units || (u64)f.coeff >> log_n) return fail(FHE_ERR_INVALID, "fault row or word outside the call");
-    hit = TensorSealHit{f.op, (u32)f.row, (u64)f.coeff, (u64)1 << f.bit};
+    if (f.sel < 0) return FHE_OK;
+    if (!f.inside(units, log_n)) return fail(FHE_ERR_INVALID, "fault row or word outside the call");
+    hit = TensorSealHit{f.sel, (u32)f.row, (u64)f.coeff, (u64)1 << f.bit};
     return FHE_OK;
 }
 
@@ -39,9 +37,10 @@ int tensor_sealed_run(fhe_ctx *ctx, hipStream_t st, uint64_t *const d[3], const 
         ta.seal_out[i] = seal_out ? seal_out[i] : nullptr;
         out = out || ta.seal_out[i];
     }
-    const size_t words = tensor_seal_part_words(ta.units, t->log_n, out);
-    if (ctx->seal_part.bytes < words * 8) HIP_TRY(ctx->seal_part.alloc(words * 8));
-    hipError_t e = launch_tensor_sealed(st, ta, ctx->seal_part.as<u64>(), k, hit);
+    u64 *part;
+    const int rc = seal_scratch(ctx, st, tensor_seal_part_words(ta.units, t->log_n, out), &part);
+    if (rc) return rc;
+    hipError_t e = launch_tensor_sealed(st, ta, part, k, hit);
     return e == hipSuccess ? FHE_OK : hip_fail(e, "launch_tensor_sealed");
 }
 
@@ -50,13 +49,7 @@ extern "C" {
 int fhe_ctx_inject_fault_tensor_sealed(fhe_ctx *ctx, int operand, int row, long long coeff, int bit)
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
-    if (operand < 0) {
-        (void)ctx->tensor_seal_fault.take();
-        return FHE_OK;
-    }
-    if (operand > 3 || row < 0 || coeff < 0 || bit < 0 || bit > 63) return fail(FHE_ERR_INVALID, "bad fault");
-    ctx->tensor_seal_fault = fhe_ctx::TensorSealFault{operand, row, bit, coeff};
-    return FHE_OK;
+    return ctx->tensor_seal_fault.arm(3, operand, 0, row, coeff, bit) ? FHE_OK : fail(FHE_ERR_INVALID, "bad fault");
 }
 
 int fhe_tensor_product_sealed_layout(size_t n_poly, size_t limbs, int out[6])
@@ -76,13 +69,12 @@ int fhe_tensor_product_sealed(fhe_ctx *ctx, uint64_t *d_d0, uint64_t *d_d1, uint
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
     // both hooks belong to this call whatever its outcome
     const PointFault pf = ctx->pw_fault.take();
-    const fhe_ctx::TensorSealFault tf = ctx->tensor_seal_fault.take();
+    const SealHook tf = ctx->tensor_seal_fault.take();
     if (!d_d0 || !d_d1 || !d_d2 || !d_a0 || !d_a1 || !d_b0 || !d_b1 || !d_flags) return fail(FHE_ERR_INVALID, "null argument");
     int rc = check_range(t, n_poly, limbs, start_idx);
     if (rc) return rc;
     if (t->log_n < 1) return fail(FHE_ERR_UNSUPPORTED, "a sealed row has at least two words");
-    for (const void *q : {(const void *)d_d0, (const void *)d_d1, (const void *)d_d2, (const void *)d_a0, (const void *)d_a1, (const void *)d_b0, (const void *)d_b1})
-        if ((uintptr_t)q % 16) return fail(FHE_ERR_INVALID, "sealed rows are read 16 bytes at a time: the buffers must be 16-byte aligned");
+    if (misaligned({d_d0, d_d1, d_d2, d_a0, d_a1, d_b0, d_b1})) return fail(FHE_ERR_INVALID, "sealed rows are read 16 bytes at a time: the buffers must be 16-byte aligned");
     const size_t R = n_poly * limbs;
     int lay[6];
     if ((rc = fhe_tensor_product_sealed_layout(n_poly, limbs, lay))) return rc;

@@ -1,4 +1,4 @@
-// fault_hook.hpp -- the one-shot test hooks of the checked calls (fhe_ctx_inject_fault_*): how a hook is stored in the context,
+// fault_hook.hpp -- the one-shot test hooks of the checked and sealed calls (fhe_ctx_inject_fault_*): how a hook is stored in the context,
 // armed by its setter, taken by the call it belongs to, and turned into the check record a launch reads.  Host only and free of
 // HIP, so that tests/emu/emu_fault_hook.cpp compiles it with g++.
 //
@@ -8,6 +8,7 @@
 // against the record it took, before anything is launched.
 #pragma once
 #include <climits>
+#include <cstddef>
 
 #include "galois_check.hpp"
 
@@ -43,6 +44,33 @@ struct PointHook : PointFault {
         static_cast<PointFault &>(*this) = PointFault{pt, (u32)u, (u64)c, b};
         return true;
     }
+};
+
+// ---- hooks of the sealed calls, which flip one bit of word coeff of a row on the load that digests it: sel < 0 = disarmed.  sel is
+// the setter's disarming argument, idx and row are its further indices (fhe_ctx lists the fields per setter)
+struct SealHook {
+    int sel = -1, idx = 0, row = 0, bit = 0;
+    long long coeff = 0;
+
+    SealHook take()
+    {
+        const SealHook f = *this;
+        sel = -1;
+        return f;
+    }
+    // the setter's core: a negative selector disarms; false (nothing stored) for what no call could honour
+    bool arm(int max_sel, int s, int i, int r, long long c, int b)
+    {
+        if (s < 0) {
+            take();
+            return true;
+        }
+        if (s > max_sel || i < 0 || r < 0 || c < 0 || b < 0 || b > 63) return false;
+        *this = SealHook{s, i, r, b, c};
+        return true;
+    }
+    // does an armed hook's word lie inside a call of `rows` rows of 2^log_n words
+    bool inside(size_t rows, int log_n) const { return (size_t)row < rows && !((u64)coeff >> log_n); }
 };
 
 // ---- hooks of a composite call, which address one of its stages: stage < 0 = disarmed

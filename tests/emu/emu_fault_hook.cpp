@@ -1,4 +1,4 @@
-// emu_fault_hook.cpp -- the one-shot test hooks of the checked calls on the CPU (TEST INFRASTRUCTURE ONLY).
+// emu_fault_hook.cpp -- the one-shot test hooks of the checked and sealed calls on the CPU (TEST INFRASTRUCTURE ONLY).
 //
 // Compiles fhe_reliability_gpu_amd/csrc/fault_hook.hpp -- the records the context stores, the setters' shared validation, take()
 // and the check-record builder -- with g++, so that what the setters accept, refuse and store can be compared with the rules of
@@ -21,6 +21,12 @@ void put(long long out[6], const StagedFault &f)
 {
     const long long v[6] = {f.block, f.stage, f.point, f.unit, f.coeff, f.bit};
     for (int i = 0; i < 6; i++) out[i] = v[i];
+}
+
+void put(long long out[5], const SealHook &f)
+{
+    const long long v[5] = {f.sel, f.idx, f.row, f.coeff, f.bit};
+    for (int i = 0; i < 5; i++) out[i] = v[i];
 }
 
 void put(long long out[4], const PointFault &f)
@@ -78,6 +84,33 @@ int emu_point_take_twice(int max_point, int point, int unit, long long coeff, in
     put(second, h.take());
     put(stored, h);
     return ok;
+}
+
+// the hooks of the sealed calls: a hook that holds `before` ({sel, idx, row, coeff, bit}) is armed with a setter's arguments as that
+// setter passes them on (max_sel = its highest selector); returns 1 where the setter accepts, 0 where it refuses
+int emu_seal_arm(int max_sel, const long long before[5], int sel, int idx, int row, long long coeff, int bit, long long stored[5])
+{
+    SealHook h{(int)before[0], (int)before[1], (int)before[2], (int)before[4], before[3]};
+    const bool ok = h.arm(max_sel, sel, idx, row, coeff, bit);
+    put(stored, h);
+    return ok;
+}
+
+int emu_seal_take_twice(int max_sel, int sel, int idx, int row, long long coeff, int bit, long long first[5], long long second[5], long long stored[5])
+{
+    SealHook h;
+    const bool ok = h.arm(max_sel, sel, idx, row, coeff, bit);
+    put(first, h.take());
+    put(second, h.take());
+    put(stored, h);
+    return ok;
+}
+
+// is the word of the armed hook {row, coeff} inside a call of `rows` rows of 2^log_n words
+int emu_seal_inside(int row, long long coeff, unsigned long long rows, int log_n)
+{
+    const SealHook h{0, 0, row, 0, coeff};
+    return h.inside((size_t)rows, log_n);
 }
 
 // bc_check of the record {block, stage, point, unit, coeff, bit} as seen from (at_block, at_stage), over the unit window [u0, u1)

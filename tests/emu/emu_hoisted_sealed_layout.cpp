@@ -35,7 +35,7 @@ int emu_sealed_null_source_seal(int *armed_after)
     static uint32_t flags[2];
     fhe_ctx_inject_fault_galois_sealed(ctx, 0, 0, 0, 0, 0);
     const int rc = fhe_automorphism_ntt_sealed(ctx, words, words + 4, words + 2, nullptr, nullptr, 1, 1, 0, 3, flags, nullptr);
-    *armed_after = ctx->gal_seal_fault.point >= 0 ? 1 : 0;
+    *armed_after = ctx->gal_seal_fault.sel >= 0 ? 1 : 0;
     return rc;
 }
 

@@ -44,10 +44,10 @@ int emu_null_seal_c(int log_n, int L, int K, int dnum, int *out)
     uint32_t flags[1] = {0x5A5A5A5Au};
     int rc = fhe_ctx_inject_fault_ntt_sealed(&ctx, 1, 2, 3);
     if (rc) return rc;
-    out[1] = ctx.ntt_seal_fault.row;
+    out[1] = ctx.ntt_seal_fault.sel;
     out[0] = fhe_keyswitch_apply_sealed_in(&ctx, &p, dummy, dummy + 2, dummy, dummy, nullptr, nullptr, reinterpret_cast<const fhe_abft *>(dummy), nullptr, dummy, flags,
                                            nullptr);
-    out[2] = ctx.ntt_seal_fault.row;
+    out[2] = ctx.ntt_seal_fault.sel;
     out[3] = flags[0] == 0x5A5A5A5Au;
     return 0;
 }

@@ -152,6 +152,35 @@ def test_seal_argument_rules(F, eng, tables):
     eng.check()
 
 
+def test_scratch_growth_between_launches_in_flight(F):
+    """The context's partial-sum scratch grows while an earlier launch that uses the old block may still be in flight: one row of
+    2^5 (the smallest scratch), then 8 rows of 2^12 sealed and verified, on one stream with no host synchronisation in between.
+    The second seal is that of an engine whose scratch never had the small size, bit for bit."""
+    from fhe_reliability_gpu_amd._lib import check, lib
+    eng, fresh = F.Engine(0), F.Engine(0)
+    n_poly, limbs, N = 2, 4, 1 << 12
+    rows = n_poly * limbs
+    qs = F.create_moduli(N, limb_bits("mixed", limbs, 0))
+    qs5 = F.create_moduli(1 << 5, [50])
+    t5, t12, t12_fresh = eng.tables(5, qs5), eng.tables(12, qs), fresh.tables(12, qs)
+    rng = np.random.default_rng(22)
+    x = np.stack([rng.integers(0, qs[r % limbs], N, dtype=np.uint64) for r in range(rows)])
+    x[5, 77] = 12345                                         # small, so that the flipped bit 9 below stays below q
+    d5, d, d_fresh = eng.upload(rng.integers(0, qs5[0], 1 << 5, dtype=np.uint64)), eng.upload(x), fresh.upload(x)
+    s5, s, fl = eng.alloc(2), eng.alloc(2 * rows), eng.upload(np.full((rows + 1) // 2, GARBAGE, dtype=np.uint64))
+    eng.sync()
+    check(lib.fhe_seal(eng._h, s5.ptr, d5.ptr, t5._h, 1, 1, 0, None))
+    check(lib.fhe_seal(eng._h, s.ptr, d.ptr, t12._h, n_poly, limbs, 0, None))
+    check(lib.fhe_seal_verify(eng._h, d.ptr, s.ptr, t12._h, n_poly, limbs, 0, fl.ptr, None))
+    got = s.download().reshape(rows, 2)
+    assert got.tobytes() == t12_fresh.seal(d_fresh, limbs=limbs, n_poly=n_poly).download().tobytes()
+    assert got.tolist() == py_seals(x)
+    assert not fl.download().view(np.uint32)[:rows].any()
+    flip(eng, d, 5 * N + 77, 9)
+    assert t12.seal_verify(d, s, limbs=limbs, n_poly=n_poly).tolist() == [0] * 5 + [SUM] + [0] * 2
+    eng.check()
+
+
 # ---------------------------------------------------------------------------------------------------------------- composites
 class Case:
     """a plan, its detector, seeded operands on the host and on the device, and their seals"""
