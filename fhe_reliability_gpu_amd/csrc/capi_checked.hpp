@@ -133,13 +133,51 @@ struct SealedKeyStep {
     KsSealHit hit;                 // the sealed call's hook, checked against the plan (ks_seal_hit)
 };
 // in != nullptr: stage 0 is the sealed inverse transform (SealedInputStep above); absent, every launch list is the checked call's own
+// tail != nullptr (fhe_hmult_sealed_out, fhe_rotate_sealed_out, fhe_rescale_sealed; capi_subscale_sealed.cpp): the call's last launch
+// -- the key switch's stage 7 when no rescale follows, the rescale's stage 3 otherwise -- is the sealed tail (subscale_sealed.hip)
+// instead of launch_sub_scale_checked -- same words, same residue flags at the same place -- which writes the outputs' seals from the
+// registers it stores; absent, every launch list is the checked call's own
+struct SealedTailStep {
+    uint64_t *seal_out[3];           // DEVICE [limbs][2] per output part, or null: that part is not sealed
+    u64 *part;                       // at least subscale_seal_part_words(2 limbs, log_n, flags_in != nullptr) words
+    int hit_point = -1;              // the sealed tail's hook, checked against the call (subscale_seal_hit): SS_AT_*, < 0: not armed
+    u32 hit_part = 0, hit_limb = 0, hit_coeff = 0;
+    u64 hit_mask = 0;
+    // fhe_rescale_sealed alone: the rescale's input [n_parts][L] is verified on the loads that consume it -- rows below L - 1 on
+    // stage 3's, the last limbs on stage 0's, which is then the sealed inverse transform out of place from the caller's rows
+    const uint64_t *seal_in = nullptr;      // DEVICE [n_parts][L][2]
+    uint32_t *flags_in = nullptr;           // [n_parts][L], zeroed by the caller
+    u64 *part_ntt = nullptr;                // at least n_parts * ntt_seal_part_words(1, log_n) words, apart from `part`
+    int ntt_hit_part = -1;                  // the sealed transform's hook, checked against the call: the part whose last limb it hits
+    u32 ntt_hit_coeff = 0;
+    u64 ntt_hit_mask = 0;
+    // the record of one launch over output parts part0 and (two) part0 + 1 of `limbs` rows; L_in = rows per part of the sealed input
+    SubScaleSeal launch(size_t part0, bool two, u32 limbs, u32 L_in) const
+    {
+        SubScaleSeal s{part, seal_out[part0], two ? seal_out[part0 + 1] : nullptr};
+        if (flags_in) {
+            s.seal_in = seal_in ? seal_in + 2 * part0 * L_in : nullptr;
+            s.flags_in = flags_in + part0 * L_in;
+            s.in_stride = L_in;
+        }
+        if (hit_point >= 0 && hit_part >= part0 && hit_part < part0 + (two ? 2 : 1)) {
+            s.hit_point = hit_point;
+            s.hit_row = (u32)(hit_part - part0) * limbs + hit_limb;
+            s.hit_coeff = hit_coeff;
+            s.hit_mask = hit_mask;
+        }
+        return s;
+    }
+    // does that launch have anything to verify or to seal (otherwise it is the checked launch)
+    bool runs(size_t part0, bool two) const { return flags_in || seal_out[part0] || (two && seal_out[part0 + 1]); }
+};
 int keyswitch_checked(fhe_keyswitch *p, KsForm form, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk,
                       const uint64_t *d_add0, const uint64_t *d_add1, const fhe_abft *a, uint32_t *d_flags, hipStream_t st, const StagedFault &ft,
-                      const SealedKeyStep *key = nullptr, const SealedInputStep *in = nullptr);
+                      const SealedKeyStep *key = nullptr, const SealedInputStep *in = nullptr, const SealedTailStep *tail = nullptr);
 // the whole rotation behind an entry point (fhe_rotate_checked, fhe_bgv_rotate_checked, fhe_rotate_sealed, fhe_rotate_sealed_fused)
 int rotate_checked(KsForm form, KsHookSlot hook, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0,
                    const uint64_t *d_c1, uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, uint32_t *d_flags, void *stream,
-                   const SealedKeyStep *key = nullptr);
+                   const SealedKeyStep *key = nullptr, const SealedTailStep *tail = nullptr);
 
 // ---- the checked key switch as two halves (keyswitch_checked = front + back; hoisted rotations: one front, a back per element)
 // where each stage's flag words go: s[0..7] the stages of the key switch, s[8] the Galois permutation of a hoisted rotation, s[9]
@@ -173,7 +211,7 @@ int ksc_front(fhe_keyswitch *p, const uint64_t *d_c, const fhe_abft *a, const Ks
               const SealedInputStep *in = nullptr);
 int ksc_back(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk, const uint64_t *d_add0,
              const uint64_t *d_add1, const fhe_abft *a, const KscFlags &fl, hipStream_t st, const KscHook &h, const KscPerm *perm, KsForm form,
-             const SealedKeyStep *key = nullptr);
+             const SealedKeyStep *key = nullptr, const SealedTailStep *tail = nullptr);
 
 // defined in capi_keyswitch_sealed.cpp
 // does the plan take the fused route (dnum <= KS_SEAL_MAX_DNUM), or the sweep followed by the checked inner product
@@ -206,14 +244,14 @@ RscLayout rsc_layout(const fhe_keyswitch *p, size_t n_parts, KsForm form);
 // the rescale's fault checked against the plan and the number of parts; *flip = the word a transform stage flips
 int rsc_hook(const fhe_keyswitch *p, KsForm form, const StagedFault &ft, size_t n_parts, u64 **flip);
 // d_in = [n_parts][L][N], outs[i] = [L - 1][N]; the caller has checked scope, arguments and overlap.  Clears the lay.total words
-// at d_flags
+// at d_flags.  tail != nullptr: stage 3 is the sealed tail (SealedTailStep), and with tail->flags_in stage 0 the sealed inverse transform
 int rescale_checked(fhe_keyswitch *p, KsForm form, uint64_t *const *outs, const uint64_t *d_in, size_t n_parts, const fhe_abft *a, uint32_t *d_flags,
-                    hipStream_t st, const StagedFault &ft);
+                    hipStream_t st, const StagedFault &ft, const SealedTailStep *tail = nullptr);
 // the multiply behind an entry point (fhe_hmult_checked, fhe_bgv_hmult_checked, fhe_hmult_sealed, fhe_hmult_sealed_fused) and its
 // layout.  sealed != nullptr (fhe_hmult_sealed_fused): the tensor step is the sealed one (tensor_sealed.hip) instead of
 // fhe_tensor_product_checked -- same words, same residue flags at the same place -- and the call takes the sealed tensor product's
 // hook as well; absent, the launch list is the checked multiply's own.  key != nullptr (fhe_hmult_sealed_fused_key): the key switch's
-// inner product is the sealed one (SealedKeyStep)
+// inner product is the sealed one (SealedKeyStep).  tail != nullptr (fhe_hmult_sealed_out): the last launch is the sealed tail (SealedTailStep)
 struct SealedTensorStep {
     const uint64_t *const *seal_in;      // HOST array of the seals of a0, a1, b0, b1; an entry or the array may be null
     uint32_t *flags_op[4];               // the operands' row flags, [L] each, zeroed by the caller
@@ -221,7 +259,14 @@ struct SealedTensorStep {
 int hmult_checked_layout(const fhe_keyswitch *p, KsForm form, int rescale, int out[4]);
 int hmult_checked(KsForm form, KsHookSlot ks_hook, KsHookSlot rs_hook, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1,
                   const uint64_t *d_a0, const uint64_t *d_a1, const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale,
-                  const fhe_abft *a, uint32_t *d_flags, void *stream, const SealedTensorStep *sealed = nullptr, const SealedKeyStep *key = nullptr);
+                  const fhe_abft *a, uint32_t *d_flags, void *stream, const SealedTensorStep *sealed = nullptr, const SealedKeyStep *key = nullptr,
+                  const SealedTailStep *tail = nullptr);
+
+// defined in capi_subscale_sealed.cpp
+// the sealed tail's hook as a call took it (ctx->subscale_seal_fault), checked against that call: in_rows_per_part != 0: the call
+// runs the IN form over input parts of that many rows, of which the last is not read by the tail; out_limbs = rows per output part
+// (0: the call has no output seals)
+int subscale_seal_hit(const SealHook &f, size_t n_parts, size_t in_rows_per_part, size_t out_limbs, int log_n, SealedTailStep &tail);
 
 // defined in capi_tensor_sealed.cpp
 // the sealed tensor product's hook as a call of `units` rows took it (ctx->tensor_seal_fault), checked against that call

@@ -63,7 +63,7 @@ int rsc_hook(const fhe_keyswitch *p, KsForm form, const StagedFault &ft, size_t 
 // BGV form: the last limbs times t^-1 mod q_last between stages 0 and 1 (stage 4), the residues times t mod q_j between stages 1
 // and 2 (stage 5), so that the part the switch removes is t [c t^-1]_{q_last}
 int rescale_checked(fhe_keyswitch *p, KsForm form, uint64_t *const *outs, const uint64_t *d_in, size_t n_parts, const fhe_abft *a, uint32_t *d_flags,
-                    hipStream_t st, const StagedFault &ft)
+                    hipStream_t st, const StagedFault &ft, const SealedTailStep *tail)
 {
     const fhe_ntt_tables *t = p->t;
     const int L = p->L, R = L - 1, logn = p->log_n;
@@ -83,9 +83,20 @@ int rescale_checked(fhe_keyswitch *p, KsForm form, uint64_t *const *outs, const 
     HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)lay.total * sizeof(u32), st));
     const KscNtt fwd = ksc_ntt(p, a, st, false), inv = ksc_ntt(p, a, st, true);
 
-    // ---- 0: INTT of the last limbs
-    HIP_TRY(hipMemcpy2DAsync(x, N * 8, d_in + (size_t)R * N, (size_t)L * N * 8, N * 8, n_parts, hipMemcpyDeviceToDevice, st));
-    if ((rc = inv.run({KscRows{x, 0, (u32)R, 1, (u32)n_parts, 1, 0}}, ft.stage == 0 ? flip : nullptr, ft.bit))) return rc;
+    // ---- 0: INTT of the last limbs (sealed input: no copy, each part's last limb verified on the transform's own load -- the
+    // launcher takes contiguous rows, so one call per part)
+    if (tail && tail->flags_in) {
+        for (size_t part = 0; part < n_parts; part++) {
+            const size_t row = part * L + R;
+            SealedInputStep in{tail->seal_in ? tail->seal_in + 2 * row : nullptr, tail->flags_in + row, tail->part_ntt + part * ntt_seal_part_words(1, logn), 0, 0, 0};
+            if (tail->ntt_hit_part == (int)part) in.hit_coeff = tail->ntt_hit_coeff, in.hit_mask = tail->ntt_hit_mask;
+            const bool mine = ft.stage == 0 && (size_t)ft.unit == part;
+            if ((rc = inv.run_sealed(KscRows{x + part * N, 0, (u32)R, 1, 1, 1, (u32)part}, d_in + row * N, in, mine ? flip : nullptr, ft.bit))) return rc;
+        }
+    } else {
+        HIP_TRY(hipMemcpy2DAsync(x, N * 8, d_in + (size_t)R * N, (size_t)L * N * 8, N * 8, n_parts, hipMemcpyDeviceToDevice, st));
+        if ((rc = inv.run({KscRows{x, 0, (u32)R, 1, (u32)n_parts, 1, 0}}, ft.stage == 0 ? flip : nullptr, ft.bit))) return rc;
+    }
     if ((rc = inv.compare(d_flags + lay.off[0], 0, (u32)R, 1, (u32)n_parts))) return rc;
 
     // ---- 4 (BGV): last limbs times t^-1
@@ -109,7 +120,10 @@ int rescale_checked(fhe_keyswitch *p, KsForm form, uint64_t *const *outs, const 
         const BcCheck k = bc_check(ft.at(0, 3), d_flags + lay.off[3] + u0, u0, u1);
         const SubScaleArgs sa{outs[part], two ? outs[part + 1] : nullptr, d_in + part * L * N, delta + part * R * N, nullptr, p->qlast_inv.as<u64>(),
                               (u64)((size_t)L * N), (u64)((size_t)R * N), lp, 0u, (u32)R, logn, nullptr};
-        if ((e = launch_sub_scale_checked(st, sa, k)) != hipSuccess) return hip_fail(e, "launch_sub_scale_checked");
+        if (tail && tail->runs(part, two)) {
+            // the sealed tail: rows 0 .. L - 2 of the parts verified on this load (sealed input), the outputs' seals from the stored registers
+            if ((e = launch_sub_scale_sealed(st, sa, k, tail->launch(part, two, (u32)R, (u32)L))) != hipSuccess) return hip_fail(e, "launch_sub_scale_sealed");
+        } else if ((e = launch_sub_scale_checked(st, sa, k)) != hipSuccess) return hip_fail(e, "launch_sub_scale_checked");
     }
     return FHE_OK;
 }
@@ -182,7 +196,7 @@ int hmult_validate(KsForm form, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0
 
 int hmult_checked(KsForm form, KsHookSlot ks_hook, KsHookSlot rs_hook, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1,
                   const uint64_t *d_a0, const uint64_t *d_a1, const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale,
-                  const fhe_abft *a, uint32_t *d_flags, void *stream, const SealedTensorStep *sealed, const SealedKeyStep *key)
+                  const fhe_abft *a, uint32_t *d_flags, void *stream, const SealedTensorStep *sealed, const SealedKeyStep *key, const SealedTailStep *tail)
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
     // the one-shot hooks of the steps this call runs belong to it whatever its outcome: the key switch's and (when it rescales) the
@@ -213,10 +227,11 @@ int hmult_checked(KsForm form, KsHookSlot ks_hook, KsHookSlot rs_hook, fhe_ctx *
         const uint64_t *const ops[4] = {d_a0, d_a1, d_b0, d_b1};
         if ((rc = tensor_sealed_run(ctx, st, d, ops, p->t, 1, L, 0, sealed->seal_in, nullptr, sealed->flags_op, k, hit))) return rc;
     } else if ((rc = fhe_tensor_product_checked(ctx, d0, d1, d2, d_a0, d_a1, d_b0, d_b1, p->t, L, 0, d_flags + lay[0], st))) return rc;
-    if (!rescale) return keyswitch_checked(p, form, d_out0, d_out1, d2, d_relin_key, d0, d1, a, d_flags + lay[1], st, kf, key);
+    // (tail: the last launch -- the key switch's stage 7, or with a rescale its stage 3 -- writes the outputs' seals)
+    if (!rescale) return keyswitch_checked(p, form, d_out0, d_out1, d2, d_relin_key, d0, d1, a, d_flags + lay[1], st, kf, key, nullptr, tail);
     if ((rc = keyswitch_checked(p, form, pre, pre + L * N, d2, d_relin_key, d0, d1, a, d_flags + lay[1], st, kf, key))) return rc;
     uint64_t *outs[3] = {d_out0, d_out1, nullptr};
-    return rescale_checked(p, form, outs, pre, 2, a, d_flags + lay[2], st, rf);
+    return rescale_checked(p, form, outs, pre, 2, a, d_flags + lay[2], st, rf, tail);
 }
 
 extern "C" {

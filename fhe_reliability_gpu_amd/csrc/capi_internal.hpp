@@ -128,8 +128,10 @@ struct fhe_ctx {
     //   fhe_ctx_inject_fault_galois_sealed     sel = point (GAL_AT_WORD, GAL_AT_INDEX), idx = rot, row: destination word coeff of `row` of
     //                                          fhe_automorphism_ntt_sealed (rot = 0) or of c0 in rotation rot of fhe_rotate_hoisted_sealed
     //   fhe_ctx_inject_fault_ntt_sealed        sel = row: the sealed inverse transform of fhe_ntt_inverse_sealed,
-    //                                          fhe_keyswitch_apply_sealed_in, fhe_rotate_sealed_in
-    SealHook bsgs_seal_fault, tensor_seal_fault, ks_seal_fault, gal_seal_fault, ntt_seal_fault;
+    //                                          fhe_keyswitch_apply_sealed_in, fhe_rotate_sealed_in, fhe_rescale_sealed
+    //   fhe_ctx_inject_fault_subscale_sealed   sel = point (SS_AT_LOAD, SS_AT_STORE), row: an input row (load) or output row (store) of
+    //                                          fhe_rescale_sealed, an output row of fhe_hmult_sealed_out, fhe_rotate_sealed_out
+    SealHook bsgs_seal_fault, tensor_seal_fault, ks_seal_fault, gal_seal_fault, ntt_seal_fault, subscale_seal_fault;
     DevBuf seal_part;     // fhe_seal / fhe_seal_verify and the sealed composites: the chunks' partial sums, [rows][chunks][2] (the carried adds: [4] or [6], the sealed tensor product: [8] or [14]; grown on demand)
     DevBuf gal_sums;       // checked Galois permutation: the units' source-side and destination-side sums, [2][units] (grown on demand)
     int geo = 1;           // column-tile geometry of the two-launch path (ntt_launch.hpp)

@@ -177,7 +177,7 @@ int ksc_front(fhe_keyswitch *p, const uint64_t *d_c, const fhe_abft *a, const Ks
 // stages 5 and 6 (stage 10), so that the part the mod-down removes is t [acc t^-1]_P
 int ksc_back(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk, const uint64_t *d_add0,
              const uint64_t *d_add1, const fhe_abft *a, const KscFlags &fl, hipStream_t st, const KscHook &h, const KscPerm *perm,
-             KsForm form, const SealedKeyStep *key)
+             KsForm form, const SealedKeyStep *key, const SealedTailStep *tail)
 {
     const int L = p->L, K = p->K, M = L + K, logn = p->log_n;
     const size_t N = (size_t)1 << logn;
@@ -232,15 +232,18 @@ int ksc_back(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_
     if ((rc = fwd.run({KscRows{conv, 0, 0, (u32)L, 2, (u32)L, 0}}, h.f.stage == 6 ? h.flip : nullptr, h.f.bit))) return rc;
     if ((rc = fwd.compare(fl.s[6], 0, 0, (u32)L, (u32)(2 * L)))) return rc;
 
-    // ---- 7: tail
+    // ---- 7: tail (tail: the outputs' seals written from the registers it stores, capi_subscale_sealed.cpp)
     const SubScaleArgs sa{d_out0, d_out1, acc, conv, d_add0, p->pinv.as<u64>(), (u64)((size_t)M * N), (u64)((size_t)L * N), lp, 0u, (u32)L, logn, d_add1};
-    if ((e = launch_sub_scale_checked(st, sa, bc_check(h.f.at(0, 7), fl.s[7]))) != hipSuccess) return hip_fail(e, "launch_sub_scale_checked");
+    if (tail && tail->runs(0, true)) {
+        if ((e = launch_sub_scale_sealed(st, sa, bc_check(h.f.at(0, 7), fl.s[7]), tail->launch(0, true, (u32)L, 0))) != hipSuccess)
+            return hip_fail(e, "launch_sub_scale_sealed");
+    } else if ((e = launch_sub_scale_checked(st, sa, bc_check(h.f.at(0, 7), fl.s[7]))) != hipSuccess) return hip_fail(e, "launch_sub_scale_checked");
     return FHE_OK;
 }
 
 int keyswitch_checked(fhe_keyswitch *p, KsForm form, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk,
                       const uint64_t *d_add0, const uint64_t *d_add1, const fhe_abft *a, uint32_t *d_flags, hipStream_t st, const StagedFault &ft,
-                      const SealedKeyStep *key, const SealedInputStep *in)
+                      const SealedKeyStep *key, const SealedInputStep *in, const SealedTailStep *tail)
 {
     int rc;
     if ((rc = ksc_prepare(p))) return rc;
@@ -252,7 +255,7 @@ int keyswitch_checked(fhe_keyswitch *p, KsForm form, uint64_t *d_out0, uint64_t 
         if (lay.units(s)) fl.s[s] = d_flags + lay.off[s];
     HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)lay.total * sizeof(u32), st));
     if ((rc = ksc_front(p, d_c, a, fl, st, h, in))) return rc;
-    return ksc_back(p, d_out0, d_out1, d_c, d_evk, d_add0, d_add1, a, fl, st, h, nullptr, form, key);
+    return ksc_back(p, d_out0, d_out1, d_c, d_evk, d_add0, d_add1, a, fl, st, h, nullptr, form, key, tail);
 }
 
 int ksc_scope(const fhe_ctx *ctx, const fhe_keyswitch *p, const fhe_abft *a, const uint32_t *d_flags, KsForm form, bool mod_switch)
@@ -303,7 +306,7 @@ int apply_checked(KsForm form, KsHookSlot hook, fhe_ctx *ctx, fhe_keyswitch *p, 
 
 int rotate_checked(KsForm form, KsHookSlot hook, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0,
                    const uint64_t *d_c1, uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, uint32_t *d_flags, void *stream,
-                   const SealedKeyStep *key)
+                   const SealedKeyStep *key, const SealedTailStep *tail)
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
     const StagedFault ft = (ctx->*hook).take();      // one shot, whatever the outcome
@@ -320,7 +323,7 @@ int rotate_checked(KsForm form, KsHookSlot hook, fhe_ctx *ctx, fhe_keyswitch *p,
     u64 *sig1 = p->rot.as<u64>(), *sig0 = sig1 + (size_t)p->L * N;
     hipError_t e = launch_automorphism_ntt(st, sig1, d_c1, (u32)p->L, p->log_n, galois_elt, sig0, d_c0);
     if (e != hipSuccess) return hip_fail(e, "launch_automorphism_ntt");
-    return keyswitch_checked(p, form, d_out0, d_out1, sig1, d_galois_key, sig0, nullptr, a, d_flags, st, ft, key);
+    return keyswitch_checked(p, form, d_out0, d_out1, sig1, d_galois_key, sig0, nullptr, a, d_flags, st, ft, key, nullptr, tail);
 }
 
 extern "C" {

@@ -180,9 +180,13 @@ int fhe_rotate_sealed_in_layout(const fhe_keyswitch *p, int out[7])
     return FHE_OK;
 }
 
-int fhe_rotate_sealed_in(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0, const uint64_t *d_c1, uint32_t galois_elt,
-                         const uint64_t *d_galois_key, const fhe_abft *a, const uint64_t *const *d_seal_in, const uint64_t *d_seal_key,
-                         uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
+} // extern "C"
+
+// fhe_rotate_sealed_in, and fhe_rotate_sealed_out (out): the two output sweeps are gone and the key switch's stage 7 is the sealed
+// tail (capi_subscale_sealed.cpp), which writes the outputs' seals from the registers it stores; the call takes that step's hook
+static int rotate_sealed_in_body(bool out, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0, const uint64_t *d_c1,
+                                 uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, const uint64_t *const *d_seal_in, const uint64_t *d_seal_key,
+                                 uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
 {
     if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
     const SealedForm f = sealed_form(p);
@@ -190,6 +194,7 @@ int fhe_rotate_sealed_in(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint6
     const StagedFault ft = (ctx->*f.ks_hook).take();
     const SealHook kf = ctx->ks_seal_fault.take();
     const SealHook nf = ctx->ntt_seal_fault.take();
+    const SealHook tf = out ? ctx->subscale_seal_fault.take() : SealHook{};
     int rc = ksc_scope(ctx, p, a, d_flags, form, false);
     if (rc) return rc;
     if (!d_out0 || !d_out1 || !d_c0 || !d_c1 || !d_galois_key) return fail(FHE_ERR_INVALID, "null argument");
@@ -205,6 +210,8 @@ int fhe_rotate_sealed_in(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint6
     SealedInputStep in{nullptr, d_flags + lay[2], nullptr, 0, 0, 0};
     if ((rc = ks_seal_hit(kf, p, key.hit))) return rc;
     if ((rc = ntt_seal_hit(nf, (size_t)p->L, p->log_n, in))) return rc;
+    SealedTailStep tail{{d_seal_out ? d_seal_out[0] : nullptr, d_seal_out ? d_seal_out[1] : nullptr, nullptr}, nullptr};
+    if (out && (rc = subscale_seal_hit(tf, 2, 0, tail.seal_out[0] && tail.seal_out[1] ? (size_t)p->L : 0, p->log_n, tail))) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     if ((rc = ksc_prepare(p))) return rc;
     KscHook h;
@@ -217,7 +224,7 @@ int fhe_rotate_sealed_in(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint6
     u64 *part;
     if ((rc = seal_scratch(ctx, st, pw + 2 * L, &part))) return rc;
     u64 *seal_sig1 = part + pw;
-    key.part = in.part = part;
+    key.part = in.part = tail.part = part;      // the tail's partials, [2 L][chunks][2], are fewer than the key's
     in.seal = seal_sig1;
     HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)lay[4] * sizeof(u32), st));
     // sigma(c0) and sigma(c1) into the plan's buffers through the sealed permutation: both verified on the gather, sigma(c1)'s seal
@@ -229,8 +236,25 @@ int fhe_rotate_sealed_in(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint6
     hipError_t e = launch_automorphism_ntt_sealed(st, g0, part, d_seal_in[0], nullptr, d_flags + lay[0], no_hit);
     if (e == hipSuccess) e = launch_automorphism_ntt_sealed(st, g1, part, d_seal_in[1], seal_sig1, d_flags + lay[1], no_hit);
     if (e != hipSuccess) return hip_fail(e, "launch_automorphism_ntt_sealed");
-    if ((rc = keyswitch_checked(p, form, d_out0, d_out1, sig1, d_galois_key, sig0, nullptr, a, d_flags + lay[4], st, ft, &key, &in))) return rc;
+    if ((rc = keyswitch_checked(p, form, d_out0, d_out1, sig1, d_galois_key, sig0, nullptr, a, d_flags + lay[4], st, ft, &key, &in, out ? &tail : nullptr)) || out)
+        return rc;
     return seal_outputs(st, p->t, d_seal_out, nullptr, d_out0, d_out1, L, part);
+}
+
+extern "C" {
+
+int fhe_rotate_sealed_in(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0, const uint64_t *d_c1, uint32_t galois_elt,
+                         const uint64_t *d_galois_key, const fhe_abft *a, const uint64_t *const *d_seal_in, const uint64_t *d_seal_key,
+                         uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
+{
+    return rotate_sealed_in_body(false, ctx, p, d_out0, d_out1, d_c0, d_c1, galois_elt, d_galois_key, a, d_seal_in, d_seal_key, d_seal_out, d_flags, stream);
+}
+
+int fhe_rotate_sealed_out(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0, const uint64_t *d_c1, uint32_t galois_elt,
+                          const uint64_t *d_galois_key, const fhe_abft *a, const uint64_t *const *d_seal_in, const uint64_t *d_seal_key,
+                          uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
+{
+    return rotate_sealed_in_body(true, ctx, p, d_out0, d_out1, d_c0, d_c1, galois_elt, d_galois_key, a, d_seal_in, d_seal_key, d_seal_out, d_flags, stream);
 }
 
 } // extern "C"

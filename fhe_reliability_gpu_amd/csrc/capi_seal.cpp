@@ -68,6 +68,7 @@ int report_offset(int sealed_total) { return (sealed_total + 3) & ~3; }
 // launched
 int sealed_scratch(fhe_ctx *ctx, hipStream_t st, const fhe_keyswitch *p, bool tensor, u64 **part)
 {
+    // (the sealed tail's partials, [2 L][chunks][2], are never more than the key's)
     const size_t key = seal_part_words((u32)key_rows(p), p->log_n);
     return seal_scratch(ctx, st, tensor ? std::max(key, tensor_sealed_scratch_words((size_t)p->L, p->log_n, false)) : key, part);
 }
@@ -185,8 +186,10 @@ int fhe_hmult_sealed_layout(const fhe_keyswitch *p, int rescale, int out[8])
 // sweeps wrote them; the key's sweep, the key switch, the rescale and the output seals are the same launches.  fused_key
 // (fhe_hmult_sealed_fused_key, with fused): the key's sweep is gone as well and the key switch's inner product is the sealed one
 // (capi_keyswitch_sealed.cpp), which verifies the key on the load that multiplies it and writes the key rows' flags where the
-// sweep wrote them; the call takes that step's hook
-static int hmult_sealed_body(const RepairMode *rm, bool fused, bool fused_key, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_a0,
+// sweep wrote them; the call takes that step's hook.  out (fhe_hmult_sealed_out, with fused_key): the two output sweeps are gone as
+// well and the multiply's last launch is the sealed tail (capi_subscale_sealed.cpp), which writes the outputs' seals from the
+// registers it stores; the call takes that step's hook
+static int hmult_sealed_body(const RepairMode *rm, bool fused, bool fused_key, bool out, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_a0,
                              const uint64_t *d_a1, const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a,
                              const uint64_t *const *d_seal_in, const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
 {
@@ -194,10 +197,12 @@ static int hmult_sealed_body(const RepairMode *rm, bool fused, bool fused_key, f
     const SealedForm f = sealed_form(p);
     SealedTensorStep step{d_seal_in, {nullptr, nullptr, nullptr, nullptr}};
     SealedKeyStep kstep{d_seal_key, nullptr, nullptr, KsSealHit{0, 0, 0}};
+    SealedTailStep tstep{{d_seal_out ? d_seal_out[0] : nullptr, d_seal_out ? d_seal_out[1] : nullptr, nullptr}, nullptr};
     const SealHook kf = fused_key ? ctx->ks_seal_fault.take() : SealHook{};      // one shot, whatever the outcome
+    const SealHook tf = out ? ctx->subscale_seal_fault.take() : SealHook{};
     auto checked = [&](uint32_t *flags) {
         return hmult_checked(f.form, f.ks_hook, f.rs_hook, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, flags, stream,
-                             fused ? &step : nullptr, fused_key ? &kstep : nullptr);
+                             fused ? &step : nullptr, fused_key ? &kstep : nullptr, out ? &tstep : nullptr);
     };
     // what must hold before the first verifying launch, so that a call outside the checked call's scope launches nothing: the
     // checked call itself then refuses (it returns the status and takes its hooks)
@@ -228,12 +233,17 @@ static int hmult_sealed_body(const RepairMode *rm, bool fused, bool fused_key, f
         (void)checked(nullptr);      // takes the hooks, launches nothing
         return fail(FHE_ERR_INVALID, "fault key row or word outside the call");
     }
+    const size_t out_limbs = tstep.seal_out[0] && tstep.seal_out[1] ? (size_t)(rescale ? p->L - 1 : p->L) : 0;
+    if (out && subscale_seal_hit(tf, 2, 0, out_limbs, p->log_n, tstep)) {
+        (void)checked(nullptr);      // takes the hooks, launches nothing
+        return subscale_seal_hit(tf, 2, 0, out_limbs, p->log_n, tstep);      // the status and its message
+    }
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t st = pick(ctx, stream);
     u64 *part;
     if ((rc = sealed_scratch(ctx, st, p, fused, &part))) return rc;
     kstep.flags_key = d_flags + lay[4];
-    kstep.part = part;
+    kstep.part = tstep.part = part;      // the key's verdict is out before the tail starts on the same stream
     HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)lay[5] * sizeof(u32), st));
     uint64_t *d_report = rm ? reinterpret_cast<uint64_t *>(d_flags + report_offset(lay[6])) : nullptr;
     if (rm) HIP_TRY(hipMemsetAsync(d_report, 0, (size_t)lay[5] * 4 * sizeof(u64), st));      // rows without a seal report CLEAN
@@ -245,15 +255,23 @@ static int hmult_sealed_body(const RepairMode *rm, bool fused, bool fused_key, f
     }
     const SealedRows key{d_relin_key, d_seal_key, rm ? rm->loc_key : nullptr, (size_t)p->dnum * 2, L + p->K, lay[4]};
     if (!fused_key && (rc = verify_or_repair(st, p->t, key, d_flags, d_report, part))) return rc;
-    if ((rc = checked(d_flags + lay[5]))) return rc;
+    if ((rc = checked(d_flags + lay[5])) || out) return rc;
     return seal_outputs(st, p->t, d_seal_out, rm ? rm->loc_out : nullptr, d_out0, d_out1, rescale ? L - 1 : L, part);
+}
+
+int fhe_hmult_sealed_out(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_a0, const uint64_t *d_a1,
+                         const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a,
+                         const uint64_t *const *d_seal_in, const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
+{
+    return hmult_sealed_body(nullptr, true, true, true, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, d_seal_in, d_seal_key, d_seal_out,
+                             d_flags, stream);
 }
 
 int fhe_hmult_sealed_fused(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_a0, const uint64_t *d_a1,
                            const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a,
                            const uint64_t *const *d_seal_in, const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
 {
-    return hmult_sealed_body(nullptr, true, false, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, d_seal_in, d_seal_key, d_seal_out,
+    return hmult_sealed_body(nullptr, true, false, false, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, d_seal_in, d_seal_key, d_seal_out,
                              d_flags, stream);
 }
 
@@ -261,7 +279,7 @@ int fhe_hmult_sealed_fused_key(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0,
                                const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a,
                                const uint64_t *const *d_seal_in, const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
 {
-    return hmult_sealed_body(nullptr, true, true, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, d_seal_in, d_seal_key, d_seal_out,
+    return hmult_sealed_body(nullptr, true, true, false, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, d_seal_in, d_seal_key, d_seal_out,
                              d_flags, stream);
 }
 
@@ -269,7 +287,7 @@ int fhe_hmult_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t 
                      const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a,
                      const uint64_t *const *d_seal_in, const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
 {
-    return hmult_sealed_body(nullptr, false, false, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, d_seal_in, d_seal_key, d_seal_out, d_flags,
+    return hmult_sealed_body(nullptr, false, false, false, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, d_seal_in, d_seal_key, d_seal_out, d_flags,
                              stream);
 }
 
@@ -289,7 +307,7 @@ int fhe_hmult_sealed_repair(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, ui
                             uint64_t *const *d_seal_out, uint64_t *const *d_locator_out, uint32_t *d_flags, void *stream)
 {
     const RepairMode rm{d_locator_in, d_locator_key, d_locator_out};
-    return hmult_sealed_body(&rm, false, false, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, d_seal_in, d_seal_key, d_seal_out, d_flags,
+    return hmult_sealed_body(&rm, false, false, false, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, d_seal_in, d_seal_key, d_seal_out, d_flags,
                              stream);
 }
 

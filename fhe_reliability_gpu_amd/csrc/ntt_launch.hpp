@@ -487,4 +487,26 @@ size_t ntt_seal_part_words(u32 rows, int logn);
 hipError_t launch_ntt_sealed_inv(hipStream_t st, const PassArgs &a, const Tw *win, const Tw *wout, const u64 *wout8, u64 *sum_in, u64 *sum_out, int logn, int path,
                                  int which, const NttSealIn &s);
 
+// ---- subscale_sealed.hip: the mod-down tail with its first operand verified on load and its result sealed on store (subscale_seal.hpp) ----
+// what the sealed tail needs beside launch_sub_scale_checked's arguments.  Rows are (half h, limb l) of the launch.  seal_out0 /
+// seal_out1 = [limbs][2] receive the seal of out0 / out1 from the registers that are stored (either may be null: that half is not
+// sealed).  flags_in != nullptr selects the IN form: row (h, l) of p.a is digested on the load that subtracts from it and held
+// against seal_in[h * in_stride + l] ([..][2], or null: not compared); flags_in[h * in_stride + l] |= SEAL_SUM where they differ,
+// SEAL_RANGE where a word is >= q_l; zeroed by the caller.  hit_point >= 0: the sealed tail's test fault (SS_AT_LOAD needs the IN
+// form), XOR hit_mask into word hit_coeff of row hit_row = h * limbs + l
+struct SubScaleSeal {
+    u64 *part;      // subscale_seal_part_words(rows, logn, IN) words
+    u64 *seal_out0, *seal_out1;
+    const u64 *seal_in = nullptr;
+    u32 *flags_in = nullptr;
+    u32 in_stride = 0;
+    int hit_point = -1;
+    u32 hit_row = 0, hit_coeff = 0;
+    u64 hit_mask = 0;
+};
+// words of the partial-sum scratch a launch needs: [rows][chunks per row][2, or 4 in the IN form]
+size_t subscale_seal_part_words(u32 rows, int logn, bool in);
+// launch_sub_scale_checked's words and flags (k) with every buffer of p 16-byte aligned and logn >= 1
+hipError_t launch_sub_scale_sealed(hipStream_t st, const SubScaleArgs &p, const BcCheck &k, const SubScaleSeal &s);
+
 } // namespace fhe

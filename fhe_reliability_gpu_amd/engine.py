@@ -85,6 +85,13 @@ class Engine:
         stays clean.  A negative ``row`` disarms."""
         check(lib.fhe_ctx_inject_fault_ntt_sealed(self._h, row, coeff, bit))
 
+    def inject_fault_subscale_sealed(self, point: int, row: int = 0, coeff: int = 0, bit: int = 0):
+        """One-shot test hook of ``KeySwitch.rescale_sealed`` / ``hmult_sealed_out`` / ``rotate_sealed_out``: point 0 flips ``bit`` of
+        word ``coeff`` of input row ``row = part * L + l`` (l < L - 1; ``rescale_sealed`` only) in the register as the sealed tail
+        loads it, before the window, the digest and the arithmetic read it; point 1 flips ``bit`` of word ``coeff`` of output row
+        ``row = part * limbs + l`` in the register after its digest and before its store.  A negative ``point`` disarms."""
+        check(lib.fhe_ctx_inject_fault_subscale_sealed(self._h, point, row, coeff, bit))
+
     def check(self):
         """Synchronise and raise if a fused-NTT launch reported a timed-out wait."""
         check(lib.fhe_ctx_check(self._h))
@@ -1341,9 +1348,12 @@ class KeySwitch:
         their seals, both required) are verified on the sealed permutation's gather, sigma(c1)'s seal is written from the registers
         that are stored, and the opening inverse transform verifies sigma(c1) against it on its own load.  The words are
         ``rotate``'s.  Not covered: sigma(c0), which the tail re-reads from the plan; the inner product's own loads."""
+        return self._rotate_sealed_in(lib.fhe_rotate_sealed_in, c0, c1, galois_elt, galois_key, abft, seals, key_seal, stream)
+
+    def _rotate_sealed_in(self, call, c0, c1, galois_elt, galois_key, abft, seals, key_seal, stream):
         names = ("c0", "c1")
         lay = self.rotate_sealed_in_layout()
-        o0, o1, so, f = self._sealed(lay, names, self.L, seals, lambda o0, o1, sin, sout, fl: lib.fhe_rotate_sealed_in(
+        o0, o1, so, f = self._sealed(lay, names, self.L, seals, lambda o0, o1, sin, sout, fl: call(
             self.eng._h, self._h, o0.ptr, o1.ptr, c0.ptr, c1.ptr, galois_elt, galois_key.ptr, abft._h, sin,
             key_seal.ptr if key_seal is not None else None, sout, fl.ptr, stream), stream)
         flags = self._split_flags(f, lay, ("c0", "c1", "sigma_c1", "key"))
@@ -1363,6 +1373,46 @@ class KeySwitch:
         key fused as well: no input is swept at all.  Not covered on the consuming load: the plan's d0, d1, d2 and digits, which
         the key switch re-reads; no repairing form."""
         return self._hmult_sealed(lib.fhe_hmult_sealed_fused_key, a0, a1, b0, b1, relin_key, abft, seals, key_seal, rescale, stream)
+
+    # ---- sealed rescale and sealed tail: inputs verified on load, outputs sealed on store (subscale_sealed.hip) ----
+    def rescale_sealed_layout(self, n_parts: int = 2):
+        """``{"in": (offset, (n_parts, L)), "checked": offset, "total": n}`` of ``rescale_sealed``'s flag buffer; the checked block is
+        laid out as ``rescale_checked_layout`` (``bgv_mod_switch_checked_layout`` with a plain modulus)."""
+        out = (C.c_int * 4)()
+        check(lib.fhe_rescale_sealed_layout(self._h, n_parts, out))
+        return {"in": (int(out[0]), (n_parts, self.L)), "checked": int(out[1]), "total": int(out[2])}
+
+    def rescale_sealed(self, c: DeviceArray, abft: "Abft", seal: DeviceArray, n_parts: int = 2, stream=None):
+        """``rescale_checked`` (``bgv_mod_switch_checked`` on a plan with a plain modulus) with the input verified on the loads that
+        consume it and the output sealed from the registers that are stored: ``(out, seal_out, flags)``, ``seal`` = the input's
+        seal ``[n_parts][L][2]`` from ``NttTables.seal`` (required), ``seal_out`` = ``[n_parts][L - 1][2]``, ``flags = {"in":
+        [n_parts][L], "checked": {the stage names of rescale_checked_layout / bgv_mod_switch_checked_layout}}``, input words with
+        the bits of ``seal_verify``.  No copy and no sweep: the last limbs are verified on the opening inverse transform's load, the
+        other rows on the load that subtracts from them.  The words are ``rescale``'s, bit for bit.  Not covered: the plan's own
+        residues, which the tail also loads; a fault after the output's digest -- whoever verifies ``seal_out`` next sees it."""
+        lay = self.rescale_sealed_layout(n_parts)
+        R = self.L - 1
+        o = self.eng.alloc(n_parts * R * self.t.N)
+        o.shape = (n_parts, R, self.t.N)
+        so = self.eng.alloc(n_parts * R * 2)
+        so.shape = (n_parts, R, 2)
+        f = _checked_flags(self.eng, lay["total"], lambda fl: lib.fhe_rescale_sealed(
+            self.eng._h, self._h, o.ptr, c.ptr, n_parts, abft._h, seal.ptr if seal is not None else None, so.ptr, fl.ptr, stream), stream)
+        flags = self._split_flags(f, lay, ("in",))
+        flags["checked"] = self._split_flags(f, self._rs_layout(bool(self.plain_modulus), n_parts), base=lay["checked"])
+        return o, so, flags
+
+    def hmult_sealed_out(self, a0: DeviceArray, a1: DeviceArray, b0: DeviceArray, b1: DeviceArray, relin_key: DeviceArray, abft: "Abft",
+                         seals=None, key_seal: Optional[DeviceArray] = None, rescale: bool = True, stream=None):
+        """``hmult_sealed_fused_key`` -- same arguments, same result structure, same words and flag layout -- without the two output
+        sweeps: the multiply's last launch writes both outputs' seals from the registers it stores."""
+        return self._hmult_sealed(lib.fhe_hmult_sealed_out, a0, a1, b0, b1, relin_key, abft, seals, key_seal, rescale, stream)
+
+    def rotate_sealed_out(self, c0: DeviceArray, c1: DeviceArray, galois_elt: int, galois_key: DeviceArray, abft: "Abft", seals,
+                          key_seal: Optional[DeviceArray] = None, stream=None):
+        """``rotate_sealed_in`` -- same arguments, same result structure, same words and flag layout -- without the two output
+        sweeps: the key switch's last launch writes both outputs' seals from the registers it stores."""
+        return self._rotate_sealed_in(lib.fhe_rotate_sealed_out, c0, c1, galois_elt, galois_key, abft, seals, key_seal, stream)
 
     def rotate_sum_sealed_layout(self, n_steps: int):
         """``{"stride": words per step, "add": offset of the add rows inside a step's block, "total": n, "rotate": the layout of

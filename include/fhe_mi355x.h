@@ -1271,6 +1271,52 @@ int fhe_rotate_sealed_in(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint6
                          uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, const uint64_t *const *d_seal_in,
                          const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream);
 
+/* ---- sealed rescale and sealed tail: inputs verified on load, outputs sealed on store ------------------------------------------
+ * fhe_rescale_checked and fhe_bgv_mod_switch_checked do not cover faults already in their input, and every sealed composite seals
+ * its outputs with a sweep after its last launch: a word corrupted between the final store and that sweep's load is sealed as it
+ * is.  The last launch of a key switch (stage 7) and of a rescale (stage 3) is the same kernel, which loads each word of its first
+ * operand once and stores each result word once.  Its sealed form digests the operand from the register it subtracts from (IN) and
+ * the result from the register it stores (OUT) -- the sums of fhe_seal, modulo 2^61 - 1, weight = index in the row plus one, and
+ * the window word < q_l -- and a finish launch holds the input rows' sums word for word against their stored seals and writes the
+ * output rows' seals.  The arithmetic, the words, the residue flags and their place are the checked tail's.
+ *
+ * fhe_rescale_sealed: fhe_rescale_checked's arguments (the CKKS or the BGV form by the plan's plain modulus) with d_seal_in
+ * ([n_parts][L][2], fhe_seal's, required) and d_seal_out ([n_parts][L - 1][2], required, written).  Stage 0 makes no copy: each
+ * part's last limb goes through the sealed inverse transform (fhe_ntt_inverse_sealed's kernel) out of place from d_in into the
+ * plan; stages 1, 2, 4, 5 are the checked rescale's; stage 3 is the sealed tail, IN and OUT.  Flags, cleared by the call:
+ *     [input rows n_parts L][the checked rescale's own block, exactly its layout]
+ * input words with fhe_seal_verify's bits: rows 0 .. L - 2 of a part from stage 3's load, row L - 1 from stage 0's.  A raised
+ * input flag does not stop the call.  fhe_rescale_sealed_layout: out = {0, offset of the checked block = n_parts L, total, 0}.
+ * Out of place only, 16-byte aligned buffers, N >= 2; a NULL seal argument, an overlap or a sharded plan is refused with nothing
+ * launched and the flag buffer untouched.  The words are fhe_rescale's, bit for bit -- also for an input word >= q_l: it is
+ * flagged (bit 2 on its row, bit 4 in the stage-3 word), not fixed.
+ *
+ * fhe_hmult_sealed_out: fhe_hmult_sealed_fused_key's arguments, flag layout and words, without the two output sweeps: the last
+ * launch -- the key switch's stage 7, or with rescale the rescale's stage 3 -- is the sealed tail in its OUT form and writes
+ * d_seal_out[0], d_seal_out[1] (an entry that is NULL is not written).  fhe_rotate_sealed_out: the same for fhe_rotate_sealed_in.
+ *
+ * Not covered: the tail's second operand (the plan's own residues) and its addends (plan-internal in these calls, the caller's
+ * own in fhe_keyswitch_apply_*) are not digested; a fault after the output's digest (the store, memory) is caught by whoever
+ * verifies the seal next; repair and locators; sharded plans; the hoisted rotations' and the BSGS product's tails.
+ *
+ * Test hook: fhe_ctx_inject_fault_subscale_sealed(point, row, coeff, bit), a negative point clears; taken, one shot and whatever
+ * the outcome, by the next of the three calls above.  Point 0 flips the bit of an input word in the register as loaded, before
+ * window, digest and arithmetic (row = part * L + l, l < L - 1; fhe_rescale_sealed only); point 1 flips the bit of an output word
+ * in the register after its digest and before its store (row = part * limbs + l of the outputs).  A row or word outside the call,
+ * point 0 in a call without the input step, a last-limb row, or point 1 without output seals makes that call return
+ * FHE_ERR_INVALID with nothing launched.  Calls that do not run the sealed tail do not take it.  fhe_rescale_sealed also takes
+ * fhe_ctx_inject_fault_ntt_sealed (row = a last-limb row part * L + L - 1) and the checked rescale's own hook of its form. */
+int fhe_ctx_inject_fault_subscale_sealed(fhe_ctx *ctx, int point, int row, long long coeff, int bit);
+int fhe_rescale_sealed_layout(const fhe_keyswitch *p, size_t n_parts, int out[4]);
+int fhe_rescale_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out, const uint64_t *d_in, size_t n_parts, const fhe_abft *a,
+                       const uint64_t *d_seal_in, uint64_t *d_seal_out, uint32_t *d_flags, void *stream);
+int fhe_hmult_sealed_out(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_a0, const uint64_t *d_a1,
+                         const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a,
+                         const uint64_t *const *d_seal_in, const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream);
+int fhe_rotate_sealed_out(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0, const uint64_t *d_c1,
+                          uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, const uint64_t *const *d_seal_in,
+                          const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream);
+
 /* ---- fault injection ---------------------------------------------------------------- */
 /* _flip_bit_kernel<<<1,1>>> (reliability_test/dotprod_test.cu:31-33,55): data[idx] ^= 1 << bit */
 int fhe_flip_bit(fhe_ctx *ctx, uint64_t *d_data, uint64_t idx, int bit, void *stream);

@@ -1,0 +1,172 @@
+"""The sealed composites whose last launch writes the outputs' seals from the registers it stores (hmult_sealed_out,
+rotate_sealed_out), on the GPU: words and whole flag buffers are those of hmult_sealed_fused_key and rotate_sealed_in, the output
+seals are NttTables.seal's of the outputs, and a fault after the digest -- which the sweep-based siblings cannot even be given --
+leaves the returned seal that of the fault-free output, so that the next verification raises exactly that row.
+
+Plans (logn, L, K, dnum) as test_gpu_ntt_sealed.py: A (10, 4, 2, 2), B (13, 3, 1, 3) with a 61-bit prime among 50-bit ones, C (14,
+6, 2, 3), two chunks per row.  Each without and with plain modulus 65537."""
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+INVALID = 1
+LOAD, STORE = 0, 1
+GARBAGE = 0x5A5A5A5A5A5A5A5A
+PLANS = {"A": (10, 4, 2, 2, [50] * 6), "B": (13, 3, 1, 3, [50, 61, 50, 50]), "C": (14, 6, 2, 3, [50] * 8)}
+PARAMS = [(name, tp) for name in PLANS for tp in (0, 65537)]
+GALOIS = 5
+CHUNK = 8192
+
+
+@pytest.fixture(scope="module")
+def F():
+    import fhe_reliability_gpu_amd as f
+    return f
+
+
+@pytest.fixture(scope="module")
+def eng(F):
+    return F.default_engine()
+
+
+class Case:
+    """a plan, its detector, seeded operands and key on the device, and their seals"""
+
+    def __init__(self, F, eng, name):
+        self.logn, self.L, self.K, self.dnum, bits = PLANS[name]
+        self.N, self.M = 1 << self.logn, self.L + self.K
+        self.qs = F.create_moduli(self.N, bits)
+        self.t = eng.tables(self.logn, self.qs)
+        self.ks, self.ab = F.KeySwitch(eng, self.t, self.L, self.K, self.dnum), F.Abft(eng, self.t)
+        rng = np.random.default_rng(419 + self.logn + self.dnum)
+        poly = lambda: np.stack([rng.integers(16, q - 16, self.N, dtype=np.uint64) for q in self.qs[:self.L]])
+        self.ops = [poly() for _ in range(4)]
+        self.key = np.stack([np.stack([np.stack([rng.integers(16, q - 16, self.N, dtype=np.uint64) for q in self.qs]) for _ in range(2)])
+                             for _ in range(self.dnum)])
+        self.d = [eng.upload(v) for v in self.ops]
+        self.dk = eng.upload(self.key)
+        self.seals = [self.t.seal(v, limbs=self.L) for v in self.d]
+        self.key_seal = self.ks.seal_key(self.dk)
+        self.edge = CHUNK if self.N > CHUNK else self.N // 2
+
+    def unchanged(self):
+        return all((dv.download().reshape(-1) == v.reshape(-1)).all() for dv, v in zip(self.d + [self.dk], self.ops + [self.key]))
+
+
+@pytest.fixture(scope="module")
+def cases(F, eng):
+    made = {}
+
+    def get(name):
+        if name not in made:
+            made[name] = Case(F, eng, name)
+        return made[name]
+    return get
+
+
+class plain_modulus:
+    def __init__(self, ks, t):
+        self.ks, self.t = ks, t
+
+    def __enter__(self):
+        self.ks.set_plain_modulus(self.t)
+
+    def __exit__(self, *exc):
+        self.ks.set_plain_modulus(0)
+
+
+def flat(d):
+    out = []
+    for name in sorted(d):
+        f = d[name]
+        if isinstance(f, dict):
+            out += [(name + "." + n, v) for n, v in flat(f)]
+        elif f is not None:
+            out.append((name, np.asarray(f).reshape(-1).tolist()))
+    return out
+
+
+def any_raised(d):
+    return any(any(v) for _, v in flat(d))
+
+
+def same(a, b):
+    return (a.download().reshape(-1) == b.download().reshape(-1)).all()
+
+
+def calls(c, which):
+    """(the _out call, its sweep-based sibling, rows per output) of hmult with rescale, hmult without, or the rotation"""
+    ks, ab = c.ks, c.ab
+    if which == "rotate":
+        kw = dict(seals=c.seals[:2], key_seal=c.key_seal)
+        return (lambda: ks.rotate_sealed_out(c.d[0], c.d[1], GALOIS, c.dk, ab, **kw), lambda: ks.rotate_sealed_in(c.d[0], c.d[1], GALOIS, c.dk, ab, **kw), c.L)
+    rescale = which == "hmult_rescale"
+    kw = dict(seals=c.seals, key_seal=c.key_seal, rescale=rescale)
+    return (lambda: ks.hmult_sealed_out(*c.d, c.dk, ab, **kw), lambda: ks.hmult_sealed_fused_key(*c.d, c.dk, ab, **kw), c.L - 1 if rescale else c.L)
+
+
+WHICH = ("hmult_rescale", "hmult", "rotate")
+
+
+@pytest.mark.parametrize("which", WHICH)
+@pytest.mark.parametrize("name,tp", PARAMS)
+def test_words_flags_and_seals_are_the_siblings(F, eng, cases, name, tp, which):
+    c = cases(name)
+    with plain_modulus(c.ks, tp):
+        out, sib, limbs = calls(c, which)
+        o0, o1, so, fl = out()
+        r0, r1, rs, rf = sib()
+        assert not any_raised(fl)
+        assert same(o0, r0) and same(o1, r1)
+        assert flat(fl) == flat(rf)
+        assert same(so[0], rs[0]) and same(so[1], rs[1])
+        assert same(so[0], c.t.seal(o0, limbs=limbs)) and same(so[1], c.t.seal(o1, limbs=limbs))
+        assert c.unchanged()
+    eng.check()
+
+
+@pytest.mark.parametrize("which", WHICH)
+@pytest.mark.parametrize("name,tp", PARAMS)
+def test_a_fault_after_the_digest_is_caught_by_the_next_verification(F, eng, cases, name, tp, which):
+    c = cases(name)
+    with plain_modulus(c.ks, tp):
+        out, sib, limbs = calls(c, which)
+        clean = out()
+        for half, l, j in ((0, 1, c.edge - 1), (1, limbs - 1, c.edge)):
+            eng.inject_fault_subscale_sealed(STORE, half * limbs + l, j, 3)
+            # the sweep-based sibling does not run the sealed tail: it sees nothing and leaves the hook armed
+            r = sib()
+            assert not any_raised(r[3]) and same(r[0], clean[0]) and same(r[1], clean[1]) and same(r[2][half], clean[2][half])
+            o0, o1, so, fl = out()
+            assert not any_raised(fl)
+            assert same(so[0], clean[2][0]) and same(so[1], clean[2][1])      # the seals of the fault-free outputs
+            got, want = (o0, o1)[half].download().reshape(limbs, c.N), clean[half].download().reshape(limbs, c.N)
+            assert np.argwhere(got != want).tolist() == [[l, j]] and int(got[l, j]) == int(want[l, j]) ^ 8
+            assert same((o0, o1)[1 - half], clean[1 - half])
+            v = [np.asarray(c.t.seal_verify(o, s, limbs=limbs)).reshape(-1) for o, s in zip((o0, o1), so)]
+            assert np.flatnonzero(v[half]).tolist() == [l] and not v[1 - half].any()
+            again = out()                                                     # one shot
+            assert same(again[0], clean[0]) and same(again[1], clean[1])
+        assert c.unchanged()
+    eng.check()
+
+
+@pytest.mark.parametrize("which", WHICH)
+@pytest.mark.parametrize("name,tp", PARAMS[:2])
+def test_hooks_that_do_not_fit_are_refused(F, eng, cases, name, tp, which):
+    from fhe_reliability_gpu_amd._lib import FheError
+    c = cases(name)
+    with plain_modulus(c.ks, tp):
+        out, sib, limbs = calls(c, which)
+        clean = out()
+        for args, why in (((LOAD, 0, 0, 3), "input seal step"), ((STORE, 2 * limbs, 0, 3), "outside the call"), ((STORE, 0, c.N, 3), "outside the call")):
+            eng.inject_fault_subscale_sealed(*args)
+            with pytest.raises(FheError, match=why):
+                out()
+            got = out()                                                       # the refused call took the hook
+            assert not any_raised(got[3]) and same(got[0], clean[0]) and same(got[2][0], clean[2][0])
+        eng.inject_fault_subscale_sealed(STORE, 0, 0, 3)
+        eng.inject_fault_subscale_sealed(-1)                                  # disarmed
+        assert same(out()[0], clean[0])
+    eng.check()
