@@ -16,6 +16,7 @@ import torch
 
 import fhe_reliability_gpu_amd as F
 from fhe_reliability_gpu_amd._lib import check, lib
+from fhe_reliability_gpu_amd.tools import _rate
 
 FABRIC_SUSTAINED_GBS = 6000.0
 PLAIN_MODULUS = 65537
@@ -27,21 +28,7 @@ ONCE = "--once" in sys.argv
 ONLY = int(sys.argv[sys.argv.index("--logn") + 1]) if "--logn" in sys.argv else None
 
 
-def timed(fn, reps):
-    """Mean device time of fn() in microseconds."""
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    total = 0.0
-    with torch.cuda.stream(s):
-        for _ in range(reps):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record(s)
-            fn()
-            b.record(s)
-            b.synchronize()
-            total += a.elapsed_time(b)
-    return total / reps * 1e3
+timed = lambda fn, reps: _rate.timed(fn, reps, s, warmups=3)
 
 
 rows = []

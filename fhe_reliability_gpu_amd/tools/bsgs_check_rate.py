@@ -17,6 +17,8 @@ import torch
 
 import fhe_reliability_gpu_amd as F
 from fhe_reliability_gpu_amd._lib import check, lib, vp
+from fhe_reliability_gpu_amd.tools import _rate
+from fhe_reliability_gpu_amd.tools._rate import med
 
 eng = F.Engine(0)
 s = torch.cuda.Stream()
@@ -25,30 +27,13 @@ P = lambda x: C.c_void_p(x.data_ptr())
 ONCE = "--once" in sys.argv
 
 
-def timed(fn, reps):
-    """Mean device time of fn() in microseconds."""
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    total = 0.0
-    with torch.cuda.stream(s):
-        for _ in range(reps):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record(s)
-            fn()
-            b.record(s)
-            b.synchronize()
-            total += a.elapsed_time(b)
-    return total / reps * 1e3
+timed = lambda fn, reps: _rate.timed(fn, reps, s, warmups=3)
 
 
-med = lambda rows, key: sorted(rows, key=key)[len(rows) // 2]
 summary = []
 for logn, L, K, dnum, n1, n2 in ((16, 16, 4, 4, 4, 4), (16, 44, 11, 4, 4, 2)):
     N, M = 1 << logn, L + K
-    qs = F.create_moduli(N, [50] * L + [61] * K)
-    t = eng.tables(logn, qs)
-    ks, ab = F.KeySwitch(eng, t, L, K, dnum), F.Abft(eng, t)
+    qs, t, ks, ab = _rate.plan(eng, logn, L, K, dnum)
     lim = min(qs)
     rnd = lambda *shape: torch.randint(0, lim, shape, device="cuda", dtype=torch.int64)
     c0, c1, diags = rnd(L, N), rnd(L, N), rnd(n2, n1, L, N)

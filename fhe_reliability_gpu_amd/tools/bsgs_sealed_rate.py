@@ -13,52 +13,31 @@ Before timing, the sealed call's words and output seals are held against the com
 Reported, not gated.
 python -m fhe_reliability_gpu_amd.tools.bsgs_sealed_rate [--config 4|5]"""
 import ctypes as C
-import sys
 
 import torch
 
 import fhe_reliability_gpu_amd as F
 from fhe_reliability_gpu_amd._lib import check, lib, vp
+from fhe_reliability_gpu_amd.tools import _rate
+from fhe_reliability_gpu_amd.tools._rate import med
 
 eng = F.Engine(0)
 s = torch.cuda.Stream()
 sp = C.c_void_p(s.cuda_stream)
 P = lambda x: C.c_void_p(x.data_ptr())
 h = eng._h
-ONLY = int(sys.argv[sys.argv.index("--config") + 1]) if "--config" in sys.argv else 0
 
 
-def timed(fn, reps):
-    """Mean device time of fn() in microseconds."""
-    for _ in range(2):
-        fn()
-    torch.cuda.synchronize()
-    total = 0.0
-    with torch.cuda.stream(s):
-        for _ in range(reps):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record(s)
-            fn()
-            b.record(s)
-            b.synchronize()
-            total += a.elapsed_time(b)
-    return total / reps * 1e3
+timed = lambda fn, reps: _rate.timed(fn, reps, s)
 
 
-med = lambda rows, key: sorted(rows, key=key)[len(rows) // 2]
-print(f"device: {torch.cuda.get_device_name(0) or torch.cuda.get_device_properties(0).gcnArchName}")
+_rate.print_device()
 summary = []
-for cfg, logn, L, K, dnum, n1, n2 in ((4, 17, 32, 8, 4, 8, 8), (5, 16, 44, 11, 4, 8, 8)):
-    if ONLY and cfg != ONLY:
-        continue
+for cfg, logn, L, K, dnum, n1, n2 in _rate.configs(((4, 17, 32, 8, 4, 8, 8), (5, 16, 44, 11, 4, 8, 8))):
     N, M = 1 << logn, L + K
     kr = dnum * 2 * M
-    qs = F.create_moduli(N, [50] * L + [61] * K)
-    t = eng.tables(logn, qs)
-    ks, ab = F.KeySwitch(eng, t, L, K, dnum), F.Abft(eng, t)
-    lim = min(qs)
-    rnd = lambda *shape: torch.randint(0, lim, shape, device="cuda", dtype=torch.int64)
-    u64 = lambda *shape: torch.zeros(shape, device="cuda", dtype=torch.int64)
+    qs, t, ks, ab = _rate.plan(eng, logn, L, K, dnum)
+    rnd, u64, _ = _rate.factories(min(qs))
     c0, c1, diags = rnd(L, N), rnd(L, N), rnd(n2, n1, L, N)
     y0, y1, z0, z1 = (torch.empty_like(c0) for _ in range(4))
     nb, ng = n1 - 1, n2 - 1
@@ -73,12 +52,7 @@ for cfg, logn, L, K, dnum, n1, n2 in ((4, 17, 32, 8, 4, 8, 8), (5, 16, 44, 11, 4
     vflags = torch.zeros(max(n1 * n2 * L, kr), dtype=torch.int32, device="cuda")
     so, so2 = [u64(L, 2), u64(L, 2)], [u64(L, 2), u64(L, 2)]
     # the seals that travel with the operands, taken once
-    def seal(words, n_poly, limbs):
-        out = u64(n_poly * limbs, 2)
-        torch.cuda.synchronize()          # torch fills on its own stream, the library writes on `s`
-        check(lib.fhe_seal(h, P(out), P(words), t._h, n_poly, limbs, 0, sp))
-        return out
-
+    seal = lambda words, n_poly, limbs: _rate.seal(eng, t, words, n_poly, limbs, sp)
     s_c, s_b, s_g, s_d = [seal(c0, 1, L), seal(c1, 1, L)], [seal(k, dnum * 2, M) for k in bkeys], [seal(k, dnum * 2, M) for k in gkeys], seal(diags, n1 * n2, L)
     sin, sout = (vp * 2)(*[x.data_ptr() for x in s_c]), (vp * 2)(*[x.data_ptr() for x in so])
     sbk, sgk = (vp * nb)(*[x.data_ptr() for x in s_b]), (vp * ng)(*[x.data_ptr() for x in s_g])

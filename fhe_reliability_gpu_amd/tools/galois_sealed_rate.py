@@ -11,38 +11,24 @@ more).  The seal kernels have so far run bound by integer work, not by bytes: th
 pass condition.  Before timing, words, seals and flags are held against the composition's on the same operands.
 python -m fhe_reliability_gpu_amd.tools.galois_sealed_rate [--config 4|5]"""
 import ctypes as C
-import sys
 
 import torch
 
 import fhe_reliability_gpu_amd as F
 from fhe_reliability_gpu_amd._lib import check, lib, vp
+from fhe_reliability_gpu_amd.tools import _rate
+from fhe_reliability_gpu_amd.tools._rate import ptrs
 
 eng = F.Engine(0)
 s = torch.cuda.Stream()
 sp = C.c_void_p(s.cuda_stream)
 P = lambda x: C.c_void_p(x.data_ptr())
 h = eng._h
-ONLY = int(sys.argv[sys.argv.index("--config") + 1]) if "--config" in sys.argv else 0
 GALOIS = 5
 N_ROT = 8
 
 
-def timed(fn, reps):
-    """Mean device time of fn() in microseconds."""
-    for _ in range(2):
-        fn()
-    torch.cuda.synchronize()
-    total = 0.0
-    with torch.cuda.stream(s):
-        for _ in range(reps):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record(s)
-            fn()
-            b.record(s)
-            b.synchronize()
-            total += a.elapsed_time(b)
-    return total / reps * 1e3
+timed = lambda fn, reps: _rate.timed(fn, reps, s)
 
 
 def spread(rows, key):
@@ -50,27 +36,14 @@ def spread(rows, key):
     return v[len(v) // 2], v[0], v[-1]
 
 
-print(f"device: {torch.cuda.get_device_name(0) or torch.cuda.get_device_properties(0).gcnArchName}")
+_rate.print_device()
 summary = []
-for cfg, logn, L, K, dnum in ((4, 17, 32, 8, 4), (5, 16, 44, 11, 4)):
-    if ONLY and cfg != ONLY:
-        continue
+for cfg, logn, L, K, dnum in _rate.configs(((4, 17, 32, 8, 4), (5, 16, 44, 11, 4))):
     N, M = 1 << logn, L + K
-    qs = F.create_moduli(N, [50] * L + [61] * K)
-    t = eng.tables(logn, qs)
-    ks, ab = F.KeySwitch(eng, t, L, K, dnum), F.Abft(eng, t)
-    lim = min(qs)
-    rnd = lambda *shape: torch.randint(0, lim, shape, device="cuda", dtype=torch.int64)
-    u64 = lambda *shape: torch.zeros(shape, device="cuda", dtype=torch.int64)
-    i32 = lambda n: torch.zeros(n, dtype=torch.int32, device="cuda")
-    ptrs = lambda xs: (vp * len(xs))(*[x.data_ptr() for x in xs])
+    qs, t, ks, ab = _rate.plan(eng, logn, L, K, dnum)
+    rnd, u64, i32 = _rate.factories(min(qs))
 
-    def seal(words, n_poly, limbs):
-        out = u64(n_poly * limbs, 2)
-        torch.cuda.synchronize()          # torch fills on its own stream, the library writes on `s`
-        check(lib.fhe_seal(h, P(out), P(words), t._h, n_poly, limbs, 0, sp))
-        return out
-
+    seal = lambda words, n_poly, limbs: _rate.seal(eng, t, words, n_poly, limbs, sp)
     # ---- (a) the permutation over the 2 L rows of a ciphertext
     ct = rnd(2, L, N)
     s_ct = seal(ct, 2, L)

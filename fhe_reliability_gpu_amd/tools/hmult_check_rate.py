@@ -15,6 +15,7 @@ import torch
 
 import fhe_reliability_gpu_amd as F
 from fhe_reliability_gpu_amd._lib import check, lib
+from fhe_reliability_gpu_amd.tools import _rate
 
 FABRIC_SUSTAINED_GBS = 6000.0
 eng = F.Engine(0)
@@ -25,21 +26,7 @@ ONCE = "--once" in sys.argv
 ONLY = int(sys.argv[sys.argv.index("--logn") + 1]) if "--logn" in sys.argv else None
 
 
-def timed(fn, reps):
-    """Mean device time of fn() in microseconds."""
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    total = 0.0
-    with torch.cuda.stream(s):
-        for _ in range(reps):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record(s)
-            fn()
-            b.record(s)
-            b.synchronize()
-            total += a.elapsed_time(b)
-    return total / reps * 1e3
+timed = lambda fn, reps: _rate.timed(fn, reps, s, warmups=3)
 
 
 rows = []
@@ -47,9 +34,7 @@ for logn, L, K, dnum in ((16, 16, 4, 4), (17, 32, 8, 4)):
     if ONLY is not None and logn != ONLY:
         continue
     N, M, R = 1 << logn, L + K, L - 1
-    qs = F.create_moduli(N, [50] * L + [61] * K)
-    t = eng.tables(logn, qs)
-    ks, ab = F.KeySwitch(eng, t, L, K, dnum), F.Abft(eng, t)
+    qs, t, ks, ab = _rate.plan(eng, logn, L, K, dnum)
     lim = min(qs)
     a0, a1, b0, b1 = (torch.randint(0, lim, (L, N), device="cuda", dtype=torch.int64) for _ in range(4))
     c = torch.randint(0, lim, (2, L, N), device="cuda", dtype=torch.int64)

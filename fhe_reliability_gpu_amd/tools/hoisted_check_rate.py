@@ -14,6 +14,7 @@ import torch
 
 import fhe_reliability_gpu_amd as F
 from fhe_reliability_gpu_amd._lib import check, lib, vp
+from fhe_reliability_gpu_amd.tools import _rate
 
 eng = F.Engine(0)
 s = torch.cuda.Stream()
@@ -23,29 +24,13 @@ ONCE = "--once" in sys.argv
 N_ROT = 8
 
 
-def timed(fn, reps):
-    """Mean device time of fn() in microseconds."""
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    total = 0.0
-    with torch.cuda.stream(s):
-        for _ in range(reps):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record(s)
-            fn()
-            b.record(s)
-            b.synchronize()
-            total += a.elapsed_time(b)
-    return total / reps * 1e3
+timed = lambda fn, reps: _rate.timed(fn, reps, s, warmups=3)
 
 
 rows = []
 for logn, L, K, dnum in ((16, 16, 4, 4), (16, 44, 11, 4)):
     N, M = 1 << logn, L + K
-    qs = F.create_moduli(N, [50] * L + [61] * K)
-    t = eng.tables(logn, qs)
-    ks, ab = F.KeySwitch(eng, t, L, K, dnum), F.Abft(eng, t)
+    qs, t, ks, ab = _rate.plan(eng, logn, L, K, dnum)
     lim = min(qs)
     rnd = lambda *shape: torch.randint(0, lim, shape, device="cuda", dtype=torch.int64)
     c0, c1 = rnd(L, N), rnd(L, N)

@@ -12,6 +12,7 @@ import torch
 
 import fhe_reliability_gpu_amd as F
 from fhe_reliability_gpu_amd._lib import check, lib
+from fhe_reliability_gpu_amd.tools import _rate
 
 eng = F.Engine(0)
 s = torch.cuda.Stream()
@@ -20,29 +21,13 @@ P = lambda x: C.c_void_p(x.data_ptr())
 ONCE = "--once" in sys.argv
 
 
-def timed(fn, reps):
-    """Mean device time of fn() in microseconds."""
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    total = 0.0
-    with torch.cuda.stream(s):
-        for _ in range(reps):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record(s)
-            fn()
-            b.record(s)
-            b.synchronize()
-            total += a.elapsed_time(b)
-    return total / reps * 1e3
+timed = lambda fn, reps: _rate.timed(fn, reps, s, warmups=3)
 
 
 rows = []
 for logn, L, K, dnum in ((16, 16, 4, 4), (16, 44, 11, 4), (17, 32, 8, 4)):
     N, M = 1 << logn, L + K
-    qs = F.create_moduli(N, [50] * L + [61] * K)
-    t = eng.tables(logn, qs)
-    ks, ab = F.KeySwitch(eng, t, L, K, dnum), F.Abft(eng, t)
+    qs, t, ks, ab = _rate.plan(eng, logn, L, K, dnum)
     lim = min(qs)
     c = torch.randint(0, lim, (L, N), device="cuda", dtype=torch.int64)
     evk = torch.randint(0, lim, (dnum, 2, M, N), device="cuda", dtype=torch.int64)

@@ -11,56 +11,31 @@ integer work, not by bytes: the ratios are reported, not promised, and none is a
 Before timing, the new calls' words, output seals and flags are held against their baselines' on the same operands.
 python -m fhe_reliability_gpu_amd.tools.ntt_sealed_rate [--config 4|5|14]"""
 import ctypes as C
-import sys
 
 import torch
 
 import fhe_reliability_gpu_amd as F
 from fhe_reliability_gpu_amd._lib import check, lib, vp
+from fhe_reliability_gpu_amd.tools import _rate
+from fhe_reliability_gpu_amd.tools._rate import med, ptrs, spread
 
 eng = F.Engine(0)
 s = torch.cuda.Stream()
 sp = C.c_void_p(s.cuda_stream)
 P = lambda x: C.c_void_p(x.data_ptr())
 h = eng._h
-ONLY = int(sys.argv[sys.argv.index("--config") + 1]) if "--config" in sys.argv else 0
 GALOIS = 5
 
 
-def timed(fn, reps):
-    """Mean device time of fn() in microseconds."""
-    for _ in range(2):
-        fn()
-    torch.cuda.synchronize()
-    total = 0.0
-    with torch.cuda.stream(s):
-        for _ in range(reps):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record(s)
-            fn()
-            b.record(s)
-            b.synchronize()
-            total += a.elapsed_time(b)
-    return total / reps * 1e3
+timed = lambda fn, reps: _rate.timed(fn, reps, s)
 
 
-med = lambda rows, key: sorted(rows, key=key)[len(rows) // 2]
-spread = lambda rows, key: (min(key(r) for r in rows), max(key(r) for r in rows))
-print(f"device: {torch.cuda.get_device_name(0) or torch.cuda.get_device_properties(0).gcnArchName}")
+_rate.print_device()
 summary = []
-for cfg, logn, L, K, dnum, tp in ((4, 17, 32, 8, 4, 0), (5, 16, 44, 11, 4, 0), (14, 14, 4, 2, 2, 65537)):
-    if ONLY and cfg != ONLY:
-        continue
+for cfg, logn, L, K, dnum, tp in _rate.configs():
     N, M = 1 << logn, L + K
-    qs = F.create_moduli(N, [50] * M if tp else [50] * L + [61] * K)
-    t = eng.tables(logn, qs)
-    ks, ab = F.KeySwitch(eng, t, L, K, dnum), F.Abft(eng, t)
-    if tp:
-        ks.set_plain_modulus(tp)
-    lim = min(qs)
-    rnd = lambda *shape: torch.randint(0, lim, shape, device="cuda", dtype=torch.int64)
-    u64 = lambda *shape: torch.zeros(shape, device="cuda", dtype=torch.int64)
-    i32 = lambda n: torch.zeros(n, dtype=torch.int32, device="cuda")
+    qs, t, ks, ab = _rate.plan(eng, logn, L, K, dnum, tp)
+    rnd, u64, i32 = _rate.factories(min(qs))
     ops = [rnd(L, N) for _ in range(2)]
     key = rnd(dnum, 2, M, N)                                    # any canonical words time the same
     rows = dnum * 2 * M
@@ -72,15 +47,9 @@ for cfg, logn, L, K, dnum, tp in ((4, 17, 32, 8, 4, 0), (5, 16, 44, 11, 4, 0), (
     a_out, c_out, r_out, r_out2 = ([u64(L, N) for _ in range(2)] for _ in range(4))
     r_so, r_so2 = ([u64(L, 2) for _ in range(2)] for _ in range(2))
 
-    def seal(words, n_poly, limbs):
-        out = u64(n_poly * limbs, 2)
-        torch.cuda.synchronize()          # torch fills on its own stream, the library writes on `s`
-        check(lib.fhe_seal(h, P(out), P(words), t._h, n_poly, limbs, 0, sp))
-        return out
-
+    seal = lambda words, n_poly, limbs: _rate.seal(eng, t, words, n_poly, limbs, sp)
     s_ops, s_key = [seal(x, 1, L) for x in ops], seal(key, dnum * 2, M)
     sin2 = (vp * 2)(*[x.data_ptr() for x in s_ops])
-    ptrs = lambda xs: (vp * len(xs))(*[x.data_ptr() for x in xs])
 
     intt_sealed = lambda: check(lib.fhe_ntt_inverse_sealed(h, P(t_dst), P(ops[0]), t._h, ab._h, 1, L, 0, P(s_ops[0]), P(tflags), sp))
 

@@ -8,6 +8,7 @@ import torch
 
 import fhe_reliability_gpu_amd as F
 from fhe_reliability_gpu_amd._lib import check, lib
+from fhe_reliability_gpu_amd.tools import _rate
 
 eng = F.Engine(0)
 s = torch.cuda.Stream()
@@ -15,21 +16,7 @@ sp = C.c_void_p(s.cuda_stream)
 P = lambda x: C.c_void_p(x.data_ptr())
 
 
-def timed(fn, reps):
-    """Mean device time of fn() in microseconds."""
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    total = 0.0
-    with torch.cuda.stream(s):
-        for _ in range(reps):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record(s)
-            fn()
-            b.record(s)
-            b.synchronize()
-            total += a.elapsed_time(b)
-    return total / reps * 1e3
+timed = lambda fn, reps: _rate.timed(fn, reps, s, warmups=3)
 
 
 def compare(name, plain, checked, flags, reps=50, rounds=3):

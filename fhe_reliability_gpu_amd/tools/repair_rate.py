@@ -16,6 +16,8 @@ import torch
 
 import fhe_reliability_gpu_amd as F
 from fhe_reliability_gpu_amd._lib import check, lib, vp
+from fhe_reliability_gpu_amd.tools import _rate
+from fhe_reliability_gpu_amd.tools._rate import med
 
 eng = F.Engine(0)
 s = torch.cuda.Stream()
@@ -24,29 +26,11 @@ P = lambda x: C.c_void_p(x.data_ptr())
 h = eng._h
 
 
-def timed(fn, reps):
-    """Mean device time of fn() in microseconds."""
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    total = 0.0
-    with torch.cuda.stream(s):
-        for _ in range(reps):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record(s)
-            fn()
-            b.record(s)
-            b.synchronize()
-            total += a.elapsed_time(b)
-    return total / reps * 1e3
-
-
-def median(rows, key):
-    return sorted(rows, key=key)[len(rows) // 2]
+timed = lambda fn, reps: _rate.timed(fn, reps, s, warmups=3)
 
 
 u64 = lambda *shape: torch.zeros(shape, device="cuda", dtype=torch.int64)
-print(f"device: {torch.cuda.get_device_name(0) or torch.cuda.get_device_properties(0).gcnArchName}")
+_rate.print_device()
 summary = []
 for cfg, logn, L in ((4, 17, 32), (5, 16, 44)):
     N = 1 << logn
@@ -67,9 +51,9 @@ for cfg, logn, L in ((4, 17, 32), (5, 16, 44)):
         out.append((ts, tl, tv, tr))
         print(f"config {cfg} (N = 2^{logn}, {2 * L} rows) round {rnd}: fhe_seal {ts:7.1f} us, fhe_seal_locator {tl:7.1f} us ({tl / ts:.3f} x), "
               f"fhe_seal_verify {tv:7.1f} us, fhe_seal_repair {tr:7.1f} us ({tr / tv:.3f} x)", flush=True)
-    _, tl, _, _ = median(out, lambda r: r[1] / r[0])
-    ts = median(out, lambda r: r[1] / r[0])[0]
-    tv, tr = median(out, lambda r: r[3] / r[2])[2:]
+    _, tl, _, _ = med(out, lambda r: r[1] / r[0])
+    ts = med(out, lambda r: r[1] / r[0])[0]
+    tv, tr = med(out, lambda r: r[3] / r[2])[2:]
     nbytes = 2 * L * N * 8
     summary.append(f"config {cfg}: {nbytes / 2**20:.0f} MiB; fhe_seal_locator {tl:.1f} us = {tl / ts:.3f} x fhe_seal ({ts:.1f} us; {nbytes / tl / 1e6:.2f} TB/s); "
                    f"fhe_seal_repair on clean rows {tr:.1f} us = {tr / tv:.3f} x fhe_seal_verify ({tv:.1f} us; {tr - tv:+.1f} us)")
@@ -78,9 +62,7 @@ for cfg, logn, L in ((4, 17, 32), (5, 16, 44)):
 if "--skip-composites" not in sys.argv:
     logn, L, K, dnum = 17, 32, 8, 4
     N, M, R = 1 << logn, L + K, L - 1
-    qs = F.create_moduli(N, [50] * L + [61] * K)
-    t = eng.tables(logn, qs)
-    ks, ab = F.KeySwitch(eng, t, L, K, dnum), F.Abft(eng, t)
+    qs, t, ks, ab = _rate.plan(eng, logn, L, K, dnum)
     ops = [torch.randint(0, min(qs), (L, N), device="cuda", dtype=torch.int64) for _ in range(4)]
     key = torch.randint(0, min(qs), (dnum, 2, M, N), device="cuda", dtype=torch.int64)
     o0, o1 = u64(L, N), u64(L, N)
@@ -113,7 +95,7 @@ if "--skip-composites" not in sys.argv:
             assert not flags[:lay["flags_total"]].any() and not flags[lay["report"]:lay["total"]].any(), f"a clean {base}_repair raised a flag or reported an outcome"
             out.append((t0, t1))
             print(f"config 4 {base} round {rnd}: sealed {t0:8.1f} us, repairing {t1:8.1f} us ({t1 / t0:.3f} x)", flush=True)
-        t0, t1 = median(out, lambda r: r[1] / r[0])
+        t0, t1 = med(out, lambda r: r[1] / r[0])
         summary.append(f"config 4 {base}_repair over {base}: {t0:.1f} us -> {t1:.1f} us ({t1 / t0:.3f} x), output locators included")
 eng.check()
 print("summary (median round):")

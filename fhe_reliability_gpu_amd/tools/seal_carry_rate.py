@@ -17,6 +17,8 @@ import torch
 
 import fhe_reliability_gpu_amd as F
 from fhe_reliability_gpu_amd._lib import check, lib, vp
+from fhe_reliability_gpu_amd.tools import _rate
+from fhe_reliability_gpu_amd.tools._rate import med
 
 PLAIN_MODULUS = 65537
 eng = F.Engine(0)
@@ -26,32 +28,14 @@ P = lambda x: C.c_void_p(x.data_ptr())
 h = eng._h
 
 
-def timed(fn, reps):
-    """Mean device time of fn() in microseconds."""
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    total = 0.0
-    with torch.cuda.stream(s):
-        for _ in range(reps):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record(s)
-            fn()
-            b.record(s)
-            b.synchronize()
-            total += a.elapsed_time(b)
-    return total / reps * 1e3
-
-
-def median(rows, key):
-    return sorted(rows, key=key)[len(rows) // 2]
+timed = lambda fn, reps: _rate.timed(fn, reps, s, warmups=3)
 
 
 def sync():
     check(lib.fhe_sync(h, sp))
 
 
-print(f"device: {torch.cuda.get_device_name(0) or torch.cuda.get_device_properties(0).gcnArchName}")
+_rate.print_device()
 summary = []
 for cfg, logn, L in ((4, 17, 32), (5, 16, 44)):
     N = 1 << logn
@@ -84,7 +68,7 @@ for cfg, logn, L in ((4, 17, 32), (5, 16, 44)):
         out.append((ta, tc, tf))
         print(f"config {cfg} (N = 2^{logn}, {rows} rows) round {rnd}: fhe_modadd {ta:7.1f} us, fhe_modadd_sealed {tc:7.1f} us ({tc / ta:.3f} x), "
               f"verify + verify + modadd_checked + seal {tf:7.1f} us ({tc / tf:.3f} x of it)", flush=True)
-    ta, tc, tf = median(out, lambda r: r[1] / r[0])
+    ta, tc, tf = med(out, lambda r: r[1] / r[0])
     nbytes = 3 * rows * N * 8
     summary.append(f"config {cfg}: {nbytes / 2**20:.0f} MiB moved; fhe_modadd {ta:.1f} us ({nbytes / ta / 1e6:.2f} TB/s), fhe_modadd_sealed {tc:.1f} us = "
                    f"{tc / ta:.3f} x ({nbytes / tc / 1e6:.2f} TB/s); the four-launch composition {tf:.1f} us: the carried add takes {tc / tf:.3f} x of it")
@@ -93,9 +77,7 @@ for cfg, logn, L in ((4, 17, 32), (5, 16, 44)):
 if "--skip-rotate" not in sys.argv:
     logn, L, K, dnum, steps = 17, 32, 8, 4, 3
     N, M = 1 << logn, L + K
-    qs = F.create_moduli(N, [50] * L + [61] * K)
-    t = eng.tables(logn, qs)
-    ks, ab = F.KeySwitch(eng, t, L, K, dnum), F.Abft(eng, t)
+    qs, t, ks, ab = _rate.plan(eng, logn, L, K, dnum)
     c_in = [torch.randint(0, min(qs), (L, N), device="cuda", dtype=torch.int64) for _ in range(2)]
     c, w, tmp = ([torch.empty_like(v) for v in c_in] for _ in range(3))
     key = torch.randint(0, min(qs), (dnum, 2, M, N), device="cuda", dtype=torch.int64)      # one key serves every step: the cost is the same
@@ -147,7 +129,7 @@ if "--skip-rotate" not in sys.argv:
             out.append((t1, t2))
             print(f"config 4 {form} round {rnd}: fhe_rotate_sum_sealed ({steps} steps) {t1:9.1f} us, fhe_rotate_sealed + composition {t2:9.1f} us ({t1 / t2:.3f} x)",
                   flush=True)
-        t1, t2 = median(out, lambda r: r[0] / r[1])
+        t1, t2 = med(out, lambda r: r[0] / r[1])
         summary.append(f"config 4 {form}: fhe_rotate_sum_sealed ({steps} steps, key seals verified) {t1:.1f} us against {t2:.1f} us for fhe_rotate_sealed plus "
                        f"verify + verify + modadd_checked + seal per half: {t1 / t2:.3f} x")
 eng.check()

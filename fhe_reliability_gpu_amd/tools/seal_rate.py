@@ -16,6 +16,8 @@ import torch
 
 import fhe_reliability_gpu_amd as F
 from fhe_reliability_gpu_amd._lib import check, lib, vp
+from fhe_reliability_gpu_amd.tools import _rate
+from fhe_reliability_gpu_amd.tools._rate import med
 
 PLAIN_MODULUS = 65537
 eng = F.Engine(0)
@@ -25,28 +27,10 @@ P = lambda x: C.c_void_p(x.data_ptr())
 h = eng._h
 
 
-def timed(fn, reps):
-    """Mean device time of fn() in microseconds."""
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    total = 0.0
-    with torch.cuda.stream(s):
-        for _ in range(reps):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record(s)
-            fn()
-            b.record(s)
-            b.synchronize()
-            total += a.elapsed_time(b)
-    return total / reps * 1e3
+timed = lambda fn, reps: _rate.timed(fn, reps, s, warmups=3)
 
 
-def median(rows, key):
-    return sorted(rows, key=key)[len(rows) // 2]
-
-
-print(f"device: {torch.cuda.get_device_name(0) or torch.cuda.get_device_properties(0).gcnArchName}")
+_rate.print_device()
 summary = []
 for cfg, logn, L in ((4, 17, 32), (5, 16, 44)):
     N = 1 << logn
@@ -67,7 +51,7 @@ for cfg, logn, L in ((4, 17, 32), (5, 16, 44)):
         out.append((ta, ts, tv))
         print(f"config {cfg} (N = 2^{logn}, {2 * L} rows) round {rnd}: fhe_modadd {ta:7.1f} us, fhe_seal {ts:7.1f} us ({ts / ta:.3f} x), "
               f"fhe_seal_verify {tv:7.1f} us ({tv / ta:.3f} x)", flush=True)
-    ta, ts, tv = median(out, lambda r: r[1] / r[0])
+    ta, ts, tv = med(out, lambda r: r[1] / r[0])
     nbytes = 2 * L * N * 8
     summary.append(f"config {cfg}: {nbytes / 2**20:.0f} MiB sealed; fhe_modadd {ta:.1f} us ({3 * nbytes / ta / 1e6:.2f} TB/s over 3x the bytes), fhe_seal {ts:.1f} us "
                    f"= {ts / ta:.3f} x ({nbytes / ts / 1e6:.2f} TB/s), fhe_seal_verify {tv:.1f} us = {tv / ta:.3f} x ({nbytes / tv / 1e6:.2f} TB/s)")
@@ -76,9 +60,7 @@ for cfg, logn, L in ((4, 17, 32), (5, 16, 44)):
 if "--skip-hmult" not in sys.argv:
     logn, L, K, dnum = 17, 32, 8, 4
     N, M, R = 1 << logn, L + K, L - 1
-    qs = F.create_moduli(N, [50] * L + [61] * K)
-    t = eng.tables(logn, qs)
-    ks, ab = F.KeySwitch(eng, t, L, K, dnum), F.Abft(eng, t)
+    qs, t, ks, ab = _rate.plan(eng, logn, L, K, dnum)
     ops = [torch.randint(0, min(qs), (L, N), device="cuda", dtype=torch.int64) for _ in range(4)]
     rlk = torch.randint(0, min(qs), (dnum, 2, M, N), device="cuda", dtype=torch.int64)
     o0, o1 = (torch.empty((R, N), device="cuda", dtype=torch.int64) for _ in range(2))
@@ -105,7 +87,7 @@ if "--skip-hmult" not in sys.argv:
             out.append((tc, t0, t1))
             print(f"config 4 {form} round {rnd}: checked {tc:8.1f} us, sealed without key seal {t0:8.1f} us ({t0 / tc:.3f} x), with key seal {t1:8.1f} us "
                   f"({t1 / tc:.3f} x)", flush=True)
-        tc, t0, t1 = median(out, lambda r: r[2] / r[0])
+        tc, t0, t1 = med(out, lambda r: r[2] / r[0])
         key_mb, op_mb = dnum * 2 * M * N * 8 / 2**20, (4 * L + 2 * R) * N * 8 / 2**20
         summary.append(f"config 4 fhe_hmult_sealed over {form}: {tc:.1f} us -> {t0:.1f} us ({t0 / tc:.3f} x) with the operands' and outputs' seals ({op_mb:.0f} MiB "
                        f"swept), {t1:.1f} us ({t1 / tc:.3f} x) with the key's as well ({key_mb:.0f} MiB more: {t1 - t0:.1f} us)")

@@ -3,27 +3,19 @@ templates the kernels instantiate): the checked inverse transform's two sums agr
 flip between its launches, and the checked product's per-point sums satisfy sum w^ a^ b^ == sum w c against the
 oracle's negacyclic product -- without a GPU."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from helpers.emu_build import build_emu
 from oracle import cport as O
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-CSRC = os.path.join(ROOT, "fhe_reliability_gpu_amd", "csrc")
 p64 = C.POINTER(C.c_uint64)
 
 
 @pytest.fixture(scope="module")
 def emu():
-    so = os.path.join(EMU_DIR, "libemu_abft.so")
-    srcs = [os.path.join(EMU_DIR, "emu_abft.cpp")] + [os.path.join(CSRC, f) for f in ("modarith.hpp", "ntt_core.hpp", "ntt_plan.hpp", "abft_taps.hpp")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-I" + CSRC, srcs[0], "-o", so])
-    L = C.CDLL(so)
+    L = build_emu("libemu_abft.so", ["emu_abft.cpp"], ("modarith.hpp", "ntt_core.hpp", "ntt_plan.hpp", "abft_taps.hpp"))
     L.emu_inverse_checked.restype = C.c_int
     L.emu_inverse_checked.argtypes = [p64, C.c_int, C.c_uint64, p64, p64, C.c_int, C.c_longlong, C.c_int, p64]
     L.emu_product_sums.restype = C.c_int

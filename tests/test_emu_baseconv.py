@@ -3,17 +3,13 @@ element functions the kernels of baseconv_checked.hip call): clean digits and wo
 bit flip at any injection point raises the flag of the unit it hit exactly when it changes that unit's digit / word --
 without a GPU."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from helpers.emu_build import build_emu
 from oracle import cport as O
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-CSRC = os.path.join(ROOT, "fhe_reliability_gpu_amd", "csrc")
 p64 = C.POINTER(C.c_uint64)
 p32 = C.POINTER(C.c_uint32)
 RESIDUE, RANGE, OPERAND = 1, 2, 4
@@ -31,11 +27,7 @@ def moduli(bits, m, k):
 
 @pytest.fixture(scope="module")
 def emu():
-    so = os.path.join(EMU_DIR, "libemu_baseconv.so")
-    srcs = [os.path.join(EMU_DIR, "emu_baseconv.cpp")] + [os.path.join(CSRC, f) for f in ("modarith.hpp", "residue_check.hpp", "baseconv_check.hpp")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-I" + CSRC, srcs[0], "-o", so])
-    L = C.CDLL(so)
+    L = build_emu("libemu_baseconv.so", ["emu_baseconv.cpp"], ("modarith.hpp", "residue_check.hpp", "baseconv_check.hpp"))
     L.emu_bc_exact_checked.restype = C.c_int
     L.emu_bc_exact_checked.argtypes = [p64, C.c_int, p64, C.c_int, p64, C.c_size_t, C.c_int, C.c_int, C.c_int, p64, p64, p32]
     L.emu_bc_exact_plain.restype = C.c_int

@@ -5,17 +5,13 @@ bsgs_check.hpp) and Python integers, and a row that is not the row that was seal
 
 Every expected value is a Python integer computed here.  No trial is filtered out."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from helpers.emu_build import build_emu
 from oracle import cport as O
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-CSRC = os.path.join(ROOT, "fhe_reliability_gpu_amd", "csrc")
 p64 = C.POINTER(C.c_uint64)
 p32 = C.POINTER(C.c_uint32)
 P = (1 << 61) - 1
@@ -31,17 +27,9 @@ PRIMES = {(bits, n): O.gen_primes(n, bits, 1)[0] for bits in (30, 50, 61) for n 
 HEADERS = ("modarith.hpp", "residue_check.hpp", "baseconv_check.hpp", "keyswitch_check.hpp", "bsgs_check.hpp", "seal_check.hpp", "bsgs_seal.hpp")
 
 
-def _build(name, headers):
-    so = os.path.join(EMU_DIR, f"lib{name}.so")
-    srcs = [os.path.join(EMU_DIR, f"{name}.cpp")] + [os.path.join(CSRC, f) for f in headers]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-I" + CSRC, srcs[0], "-o", so])
-    return C.CDLL(so)
-
-
 @pytest.fixture(scope="module")
 def emu():
-    L = _build("emu_bsgs_seal", HEADERS)
+    L = build_emu("libemu_bsgs_seal.so", ["emu_bsgs_seal.cpp"], HEADERS)
     L.emu_diag_mac_sealed.restype = C.c_int
     L.emu_diag_mac_sealed.argtypes = [p64, p64, p64, C.c_int, C.c_uint32, C.c_uint64, C.c_int, C.c_int, p64, C.c_int, C.c_uint32, C.c_int, p64, p64, p32, p64,
                                       p32]
@@ -51,7 +39,7 @@ def emu():
 @pytest.fixture(scope="module")
 def checked():
     """the emulation of bsgs_check.hpp: the checked inner sum, element by element"""
-    L = _build("emu_bsgs_check", HEADERS[:5])
+    L = build_emu("libemu_bsgs_check.so", ["emu_bsgs_check.cpp"], HEADERS[:5])
     L.emu_diag_mac_checked.restype = C.c_int
     L.emu_diag_mac_checked.argtypes = [p64, p64, p64, C.c_int, C.c_size_t, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, p64, p64, p32, p32]
     return L

@@ -5,14 +5,11 @@ once, the check-record builder arms exactly the launch whose flags hold the faul
 call exactly when its row and word are -- without a GPU."""
 import ctypes as C
 import itertools
-import os
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-CSRC = os.path.join(ROOT, "fhe_reliability_gpu_amd", "csrc")
+from helpers.emu_build import build_emu
+
 Rec6, Rec5, Rec4 = C.c_longlong * 6, C.c_longlong * 5, C.c_longlong * 4
 
 T = "transform"          # a transform stage: one point between its two launches, `point` ignored and stored as 0
@@ -31,11 +28,8 @@ SENTINEL = (2, 1, 2, 9, 11, 13)            # an armed hook that every family's r
 
 @pytest.fixture(scope="module")
 def emu():
-    so = os.path.join(EMU_DIR, "libemu_fault_hook.so")
-    srcs = [os.path.join(EMU_DIR, "emu_fault_hook.cpp")] + [os.path.join(CSRC, f) for f in ("fault_hook.hpp", "galois_check.hpp", "modarith.hpp")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I" + CSRC, srcs[0], "-o", so])
-    L = C.CDLL(so)
+    # variation: no -ffp-contract=off -- emu_fault_hook.cpp does integer work only, and the flags stay as they have always been
+    L = build_emu("libemu_fault_hook.so", ["emu_fault_hook.cpp"], ("fault_hook.hpp", "galois_check.hpp", "modarith.hpp"), flags=("-O2", "-std=c++17"))
     ll, i = C.c_longlong, C.c_int
     L.emu_hook_stages.argtypes = [i]
     L.emu_hook_arm.argtypes = [i, Rec6, i, i, i, i, ll, i, Rec6]

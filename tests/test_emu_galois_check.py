@@ -3,18 +3,14 @@ element functions the kernel of galois_checked.hip calls): the slot maps of k an
 the automorphism of the oracle, clean sums agree, every single-bit flip of a moved word is flagged, and every single-bit flip of
 a source index is flagged unless the weighted residues of the two words coincide -- without a GPU."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from helpers.emu_build import build_emu
 from oracle import cport as O
 from oracle.keyswitch_ref import galois_coeff
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-CSRC = os.path.join(ROOT, "fhe_reliability_gpu_amd", "csrc")
 p64 = C.POINTER(C.c_uint64)
 p32 = C.POINTER(C.c_uint32)
 WORD, INDEX = 0, 1
@@ -23,11 +19,7 @@ M32 = (1 << 32) - 1
 
 @pytest.fixture(scope="module")
 def emu():
-    so = os.path.join(EMU_DIR, "libemu_galois_check.so")
-    srcs = [os.path.join(EMU_DIR, "emu_galois_check.cpp")] + [os.path.join(CSRC, f) for f in ("modarith.hpp", "ntt_core.hpp", "residue_check.hpp", "galois_check.hpp")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-I" + CSRC, srcs[0], "-o", so])
-    L = C.CDLL(so)
+    L = build_emu("libemu_galois_check.so", ["emu_galois_check.cpp"], ("modarith.hpp", "ntt_core.hpp", "residue_check.hpp", "galois_check.hpp"))
     L.emu_galois_slot.restype = C.c_uint32
     L.emu_galois_slot.argtypes = [C.c_uint32, C.c_int, C.c_uint32]
     L.emu_galois_permute.restype = C.c_int

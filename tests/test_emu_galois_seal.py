@@ -4,15 +4,12 @@ seals of source and destination whatever the chunking, every one-word and two-wo
 patterns the 2^32 - 1 fold is blind to included --, an index fault raises a row of distinct words, and the written seal is {stored
 S0, digested S1}, so a register fault poisons the destination's seal -- without a GPU."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-CSRC = os.path.join(ROOT, "fhe_reliability_gpu_amd", "csrc")
+from helpers.emu_build import build_emu
+
 p64 = C.POINTER(C.c_uint64)
 P = (1 << 61) - 1
 SUM, RANGE = 1, 2
@@ -24,12 +21,8 @@ PATTERN = 0xA5A5A5A5A5A5A5A5
 
 @pytest.fixture(scope="module")
 def emu():
-    so = os.path.join(EMU_DIR, "libemu_galois_seal.so")
-    srcs = [os.path.join(EMU_DIR, "emu_galois_seal.cpp")] + [os.path.join(CSRC, f) for f in ("modarith.hpp", "ntt_core.hpp", "residue_check.hpp", "galois_check.hpp",
-                                                                                            "seal_check.hpp", "galois_seal.hpp")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-I" + CSRC, srcs[0], "-o", so])
-    L = C.CDLL(so)
+    L = build_emu("libemu_galois_seal.so", ["emu_galois_seal.cpp"], ("modarith.hpp", "ntt_core.hpp", "residue_check.hpp", "galois_check.hpp",
+                                                                     "seal_check.hpp", "galois_seal.hpp"))
     L.emu_gs_slot.restype = C.c_uint32
     L.emu_gs_slot.argtypes = [C.c_uint32, C.c_int, C.c_uint32]
     L.emu_gs_permute.restype = C.c_uint32

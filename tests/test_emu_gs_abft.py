@@ -7,16 +7,13 @@ a GPU."""
 import ctypes as C
 import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
+from helpers.emu_build import CSRC, build_emu
 from oracle import cport as O
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-CSRC = os.path.join(ROOT, "fhe_reliability_gpu_amd", "csrc")
 p64 = C.POINTER(C.c_uint64)
 
 ROW_STAGES = {13: 8, 14: 8, 16: 8}          # P of the two-launch plans used here (ntt_plan.hpp): E2 = 2^P points, E1 = 2^(logN - P) columns
@@ -25,11 +22,9 @@ CASES = [("f64-ntt-prime", 0, 0), ("f64-50bit", 0, 50), ("u64-61bit", 1, 61)]
 
 @pytest.fixture(scope="module")
 def emu():
-    so = os.path.join(EMU_DIR, "libemu_gs_abft.so")
-    srcs = [os.path.join(EMU_DIR, "emu_gs_abft.cpp")] + [os.path.join(CSRC, f) for f in ("host_math.cpp", "host_math.hpp", "modarith.hpp", "ntt_core.hpp", "ntt_plan.hpp", "abft_taps.hpp")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-I" + CSRC, srcs[0], srcs[1], "-o", so])
-    L = C.CDLL(so)
+    # variation: two sources -- the library's own host_math.cpp is compiled in, since the emulation builds its tables with it
+    L = build_emu("libemu_gs_abft.so", ["emu_gs_abft.cpp", os.path.join(CSRC, "host_math.cpp")],
+                  ("host_math.hpp", "modarith.hpp", "ntt_core.hpp", "ntt_plan.hpp", "abft_taps.hpp"))
     L.emu_gs_checked.restype = C.c_int
     L.emu_gs_checked.argtypes = [p64, p64, C.c_int, C.c_uint64, C.c_uint64, p64, p64, p64, C.c_int, C.c_longlong, C.c_int, p64, p64]
     return L

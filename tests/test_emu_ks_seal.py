@@ -6,18 +6,14 @@ identity goes on holding -- without a GPU.
 
 Every expected value is a Python integer computed here."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from helpers.emu_build import build_emu
 from helpers.stream_cases import barrett_shortfall, fp64_edge_pairs, small_residue_pairs
 from oracle import cport as O
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-CSRC = os.path.join(ROOT, "fhe_reliability_gpu_amd", "csrc")
 p64, p32 = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
 P = (1 << 61) - 1
 SUM, RANGE = 1, 2
@@ -39,12 +35,8 @@ def band(dnum):
 
 @pytest.fixture(scope="module")
 def emu():
-    so = os.path.join(EMU_DIR, "libemu_ks_seal.so")
-    srcs = [os.path.join(EMU_DIR, "emu_ks_seal.cpp")] + [os.path.join(CSRC, f) for f in ("modarith.hpp", "residue_check.hpp", "seal_check.hpp", "bsgs_check.hpp",
-                                                                                          "bsgs_seal.hpp", "ks_seal.hpp")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-I" + CSRC, srcs[0], "-o", so])
-    L = C.CDLL(so)
+    L = build_emu("libemu_ks_seal.so", ["emu_ks_seal.cpp"], ("modarith.hpp", "residue_check.hpp", "seal_check.hpp", "bsgs_check.hpp", "bsgs_seal.hpp",
+                                                             "ks_seal.hpp"))
     L.emu_ks_seal_max_dnum.restype = C.c_uint
     L.emu_ks_sealed.restype = C.c_int
     L.emu_ks_sealed.argtypes = [p64, p64, p64, C.c_uint32, C.c_uint32, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int, p64, C.c_int,

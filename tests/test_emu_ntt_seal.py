@@ -3,17 +3,13 @@ pass templates k_ntt_pass_sealed instantiates): the digest the pass forms from t
 whatever the tile order, every single-word change the seal promises to catch is caught on that load, and the hooked tap changes
 the words and the digest together while the source stays clean -- without a GPU."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from helpers.emu_build import build_emu
 from oracle import cport as O
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-CSRC = os.path.join(ROOT, "fhe_reliability_gpu_amd", "csrc")
 p64 = C.POINTER(C.c_uint64)
 P = (1 << 61) - 1
 SEAL_SUM, SEAL_RANGE = 1, 2
@@ -23,12 +19,8 @@ PATHS = [(0, 50), (1, 61)]
 
 @pytest.fixture(scope="module")
 def emu():
-    so = os.path.join(EMU_DIR, "libemu_ntt_seal.so")
-    srcs = [os.path.join(EMU_DIR, "emu_ntt_seal.cpp")] + [os.path.join(CSRC, f) for f in ("modarith.hpp", "ntt_core.hpp", "ntt_plan.hpp", "abft_taps.hpp",
-                                                                                           "seal_check.hpp", "ntt_seal_tap.hpp")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-I" + CSRC, srcs[0], "-o", so])
-    L = C.CDLL(so)
+    L = build_emu("libemu_ntt_seal.so", ["emu_ntt_seal.cpp"], ("modarith.hpp", "ntt_core.hpp", "ntt_plan.hpp", "abft_taps.hpp", "seal_check.hpp",
+                                                               "ntt_seal_tap.hpp"))
     L.emu_ntt_seal_first.restype = C.c_int
     L.emu_ntt_seal_first.argtypes = [p64, p64, C.c_int, C.c_uint64, p64, p64, C.c_int, C.c_int, C.c_longlong, C.c_int, p64, p64]
     L.emu_ntt_seal_finish.restype = C.c_uint

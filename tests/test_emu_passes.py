@@ -4,16 +4,13 @@ indexing, the LDS exchange addressing and the FP64 lazy-range schedule for every
 supported size, without a GPU."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from helpers.emu_build import build_emu
 from oracle import cport as O
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-CSRC = os.path.join(ROOT, "fhe_reliability_gpu_amd", "csrc")
 p64 = C.POINTER(C.c_uint64)
 
 
@@ -22,12 +19,10 @@ def emu():
     # FHE_EMU_SANITIZE=1 (with LD_PRELOAD=$(gcc -print-file-name=libasan.so)): AddressSanitizer + UBSan build of the
     # emulation -- the CPU-side sanitizer run of the kernels' indexing (GPU sanitizers are not available on the pool)
     san = os.environ.get("FHE_EMU_SANITIZE") == "1"
-    so = os.path.join(EMU_DIR, "libemu_ntt_san.so" if san else "libemu_ntt.so")
-    srcs = [os.path.join(EMU_DIR, "emu_ntt.cpp")] + [os.path.join(CSRC, f) for f in ("modarith.hpp", "ntt_core.hpp", "ntt_plan.hpp", "ntt_fused.hpp")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs):
-        flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"] if san else ["-O2"]
-        subprocess.check_call(["g++"] + flags + ["-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-I" + CSRC, srcs[0], "-o", so])
-    L = C.CDLL(so)
+    # variation: the flags depend on the environment, and the sanitized build has a library of its own
+    flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"] if san else ["-O2"]
+    L = build_emu("libemu_ntt_san.so" if san else "libemu_ntt.so", ["emu_ntt.cpp"], ("modarith.hpp", "ntt_core.hpp", "ntt_plan.hpp", "ntt_fused.hpp"),
+                  flags=flags + ["-std=c++17", "-ffp-contract=off"])
     L.emu_ntt.restype = C.c_int
     L.emu_ntt.argtypes = [p64, C.c_int, C.c_int, C.c_int, C.c_int, p64, p64, C.c_int, C.c_int]
     L.emu_max_ratio.restype = C.c_double

@@ -2,17 +2,13 @@
 element functions the kernels of pointwise_checked.hip call): clean words equal Python-integer products, and a bit flip
 at any injection point raises a flag exactly when it changes the output word -- without a GPU."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from helpers.emu_build import build_emu
 from oracle import cport as O
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-CSRC = os.path.join(ROOT, "fhe_reliability_gpu_amd", "csrc")
 p64 = C.POINTER(C.c_uint64)
 p32 = C.POINTER(C.c_uint32)
 RESIDUE, RANGE, OPERAND = 1, 2, 4
@@ -24,11 +20,7 @@ PRIMES = {bits: O.gen_primes(N, bits, 1)[0] for bits in (30, 50, 61)}
 
 @pytest.fixture(scope="module")
 def emu():
-    so = os.path.join(EMU_DIR, "libemu_pointwise.so")
-    srcs = [os.path.join(EMU_DIR, "emu_pointwise.cpp")] + [os.path.join(CSRC, f) for f in ("modarith.hpp", "residue_check.hpp")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-I" + CSRC, srcs[0], "-o", so])
-    L = C.CDLL(so)
+    L = build_emu("libemu_pointwise.so", ["emu_pointwise.cpp"], ("modarith.hpp", "residue_check.hpp"))
     L.emu_modmul_checked.restype = C.c_int
     L.emu_modmul_checked.argtypes = [p64, p64, p64, C.c_size_t, C.c_uint64, C.c_int, C.c_int, C.c_int, p64, p32]
     L.emu_modmul_plain.restype = C.c_int

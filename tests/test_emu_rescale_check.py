@@ -7,17 +7,13 @@ modulo m = 2^32 - 1 a change of k by a multiple of m / gcd(q, m) leaves k q unch
 and so does a 64-bit wrap of the remainder by a multiple of m words (primes just below a power of two).  Neither case is
 filtered out below: both are constructed on purpose and must come out flagged by the window bit alone."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from helpers.emu_build import build_emu
 from oracle import cport as O
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-CSRC = os.path.join(ROOT, "fhe_reliability_gpu_amd", "csrc")
 p64 = C.POINTER(C.c_uint64)
 p32 = C.POINTER(C.c_uint32)
 RESIDUE, RANGE, OPERAND = 1, 2, 4
@@ -32,11 +28,7 @@ IDS = [f"{ql.bit_length()}b{ql % 1000}-{qj.bit_length()}b{qj % 1000}" for ql, qj
 
 @pytest.fixture(scope="module")
 def emu():
-    so = os.path.join(EMU_DIR, "libemu_rescale_check.so")
-    srcs = [os.path.join(EMU_DIR, "emu_rescale_check.cpp")] + [os.path.join(CSRC, f) for f in ("modarith.hpp", "residue_check.hpp", "rescale_check.hpp")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-I" + CSRC, srcs[0], "-o", so])
-    L = C.CDLL(so)
+    L = build_emu("libemu_rescale_check.so", ["emu_rescale_check.cpp"], ("modarith.hpp", "residue_check.hpp", "rescale_check.hpp"))
     L.emu_rescale_reduce_checked.restype = C.c_int
     L.emu_rescale_reduce_checked.argtypes = [p64, C.c_size_t, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, p64, p32]
     L.emu_rescale_reduce_plain.restype = C.c_int

@@ -6,17 +6,13 @@ outcome the header promises -- without a GPU.
 Every expected value is a Python integer computed here.  No trial is filtered out: where a flipped operand bit leaves the window
 [0, q) the row must raise the range bit as well, and the test says which case it is in from the operands alone."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from helpers.emu_build import build_emu
 from oracle import cport as O
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-CSRC = os.path.join(ROOT, "fhe_reliability_gpu_amd", "csrc")
 p64 = C.POINTER(C.c_uint64)
 P = (1 << 61) - 1
 SUM, RANGE = 1, 2
@@ -28,12 +24,7 @@ PRIMES = {(bits, n): O.gen_primes(n, bits, 1)[0] for bits in BITS for n in (1 <<
 
 @pytest.fixture(scope="module")
 def emu():
-    so = os.path.join(EMU_DIR, "libemu_seal_carry.so")
-    srcs = [os.path.join(EMU_DIR, "emu_seal_carry.cpp")] + [os.path.join(CSRC, f) for f in ("modarith.hpp", "residue_check.hpp", "seal_check.hpp",
-                                                                                             "seal_carry.hpp")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-I" + CSRC, srcs[0], "-o", so])
-    L = C.CDLL(so)
+    L = build_emu("libemu_seal_carry.so", ["emu_seal_carry.cpp"], ("modarith.hpp", "residue_check.hpp", "seal_check.hpp", "seal_carry.hpp"))
     L.emu_carry.restype = C.c_uint32
     L.emu_carry.argtypes = [p64, p64, p64, C.c_uint32, C.c_uint64, C.c_int, C.c_int, C.c_int, p64, p64, p64, C.c_int, C.c_uint32, C.c_int]
     L.emu_carry_predict.restype = C.c_uint64

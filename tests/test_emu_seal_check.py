@@ -5,17 +5,13 @@ every change confined to one or two words of a row is caught -- without a GPU.
 The changes a fold modulo 2^32 - 1 cannot see are constructed on purpose and none is filtered out: +-(2^b - 2^(b+32)) inside one
 word (asserted here to pass residue_check.hpp's fold unseen), and d1 = -d2 on two words whose distance is a multiple of 3 * 5 * 17."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from helpers.emu_build import build_emu
 from oracle import cport as O
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-CSRC = os.path.join(ROOT, "fhe_reliability_gpu_amd", "csrc")
 p64 = C.POINTER(C.c_uint64)
 p32 = C.POINTER(C.c_uint32)
 P = (1 << 61) - 1
@@ -27,11 +23,7 @@ PRIMES = {(bits, n): O.gen_primes(n, bits, 1)[0] for bits in BITS for n in SIZES
 
 @pytest.fixture(scope="module")
 def emu():
-    so = os.path.join(EMU_DIR, "libemu_seal_check.so")
-    srcs = [os.path.join(EMU_DIR, "emu_seal_check.cpp")] + [os.path.join(CSRC, f) for f in ("modarith.hpp", "residue_check.hpp", "seal_check.hpp")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-I" + CSRC, srcs[0], "-o", so])
-    L = C.CDLL(so)
+    L = build_emu("libemu_seal_check.so", ["emu_seal_check.cpp"], ("modarith.hpp", "residue_check.hpp", "seal_check.hpp"))
     L.emu_seal.restype = None
     L.emu_seal.argtypes = [p64, C.c_size_t, C.c_size_t, p64]
     L.emu_seal_chunked.restype = None

@@ -6,17 +6,13 @@ The two-word traps are built on purpose: the same bit set in two words whose ind
 integral weighted mean.  Each is first shown to be ACCEPTED by a locator made of S0 and S1 alone (it names an intact word), then to
 be refused once S2 is held against it: that is what the third sum buys."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from helpers.emu_build import build_emu
 from oracle import cport as O
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-CSRC = os.path.join(ROOT, "fhe_reliability_gpu_amd", "csrc")
 p64 = C.POINTER(C.c_uint64)
 P = (1 << 61) - 1
 CLEAN, REPAIRED, UNCORRECTABLE, TRANSIENT, SUSPECT = 0, 1, 2, 3, 4
@@ -27,11 +23,7 @@ PRIMES = {(bits, logn): O.gen_primes(1 << max(logn, 2), bits, 1)[0] for bits in 
 
 @pytest.fixture(scope="module")
 def emu():
-    so = os.path.join(EMU_DIR, "libemu_seal_repair.so")
-    srcs = [os.path.join(EMU_DIR, "emu_seal_repair.cpp")] + [os.path.join(CSRC, f) for f in ("modarith.hpp", "seal_check.hpp")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-I" + CSRC, srcs[0], "-o", so])
-    L = C.CDLL(so)
+    L = build_emu("libemu_seal_repair.so", ["emu_seal_repair.cpp"], ("modarith.hpp", "seal_check.hpp"))
     u64, u32 = C.c_uint64, C.c_uint32
     for name, res, args in (("emu_seal_mulmod", u64, [u64, u64]), ("emu_seal_inv", u64, [u64]), ("emu_seal_restore", u64, [u64, u64]),
                             ("emu_seal_locate", C.c_longlong, [u64, u64, u64, u32]), ("emu_seal3", None, [p64, C.c_size_t, u32, p64]),

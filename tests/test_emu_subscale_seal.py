@@ -4,17 +4,13 @@ operands, the digests of a row are the seal Python integers give whatever the ch
 moves the input digest while the residue identity stays true, and a flip at the store leaves both digests alone -- without a GPU."""
 import ctypes as C
 import itertools
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from helpers.emu_build import build_emu
 from oracle import cport as O
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-CSRC = os.path.join(ROOT, "fhe_reliability_gpu_amd", "csrc")
 p64 = C.POINTER(C.c_uint64)
 p32 = C.POINTER(C.c_uint32)
 P = (1 << 61) - 1
@@ -27,12 +23,8 @@ N = 1 << 10
 
 @pytest.fixture(scope="module")
 def emu():
-    so = os.path.join(EMU_DIR, "libemu_subscale_seal.so")
-    srcs = [os.path.join(EMU_DIR, "emu_subscale_seal.cpp")] + [os.path.join(CSRC, f) for f in ("modarith.hpp", "residue_check.hpp", "baseconv_check.hpp",
-                                                                                                "keyswitch_check.hpp", "seal_check.hpp", "subscale_seal.hpp")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-I" + CSRC, srcs[0], "-o", so])
-    L = C.CDLL(so)
+    L = build_emu("libemu_subscale_seal.so", ["emu_subscale_seal.cpp"], ("modarith.hpp", "residue_check.hpp", "baseconv_check.hpp",
+                                                                         "keyswitch_check.hpp", "seal_check.hpp", "subscale_seal.hpp"))
     L.emu_subscale_word.restype = None
     L.emu_subscale_word.argtypes = [C.c_uint64] * 3 + [C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, p64]
     L.emu_subscale_row.restype = C.c_int

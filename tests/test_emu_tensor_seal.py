@@ -5,18 +5,14 @@ the digest of the operand it hits while the residue identity goes on holding -- 
 
 Every expected value is a Python integer computed here."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from helpers.emu_build import build_emu
 from helpers.stream_cases import barrett_shortfall, fp64_edge_pairs, small_residue_pairs
 from oracle import cport as O
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-CSRC = os.path.join(ROOT, "fhe_reliability_gpu_amd", "csrc")
 p64, p32 = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
 P = (1 << 61) - 1
 SUM, RANGE = 1, 2
@@ -29,12 +25,7 @@ PRIMES = {(bits, logn): O.gen_primes(1 << logn, bits, 1)[0] for bits in (50, 61)
 
 @pytest.fixture(scope="module")
 def emu():
-    so = os.path.join(EMU_DIR, "libemu_tensor_seal.so")
-    srcs = [os.path.join(EMU_DIR, "emu_tensor_seal.cpp")] + [os.path.join(CSRC, f) for f in ("modarith.hpp", "residue_check.hpp", "seal_check.hpp",
-                                                                                              "tensor_seal.hpp")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-I" + CSRC, srcs[0], "-o", so])
-    L = C.CDLL(so)
+    L = build_emu("libemu_tensor_seal.so", ["emu_tensor_seal.cpp"], ("modarith.hpp", "residue_check.hpp", "seal_check.hpp", "tensor_seal.hpp"))
     L.emu_tensor_sealed.restype = C.c_int
     L.emu_tensor_sealed.argtypes = [p64, p64, p64, p64, C.c_uint32, C.c_uint64, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_int, p64, C.c_int, C.c_uint32,
                                     C.c_int, p64, p64, p64, p32, p64, p32]

@@ -11,18 +11,19 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from helpers.sealed_case import CAP, case_cache, flat, plans, raised, same, sealed_plan
+
 pytestmark = pytest.mark.gpu
 
 INVALID = 1
 SUM, RANGE = 1, 2
 WORD, INDEX = 0, 1
 PATTERN = 0x5A5A5A5A5A5A5A5A
-CAP = 12
 GRID_CAP = 8192                 # TENSOR_SEAL_GRID_CAP of ntt_launch.hpp: workgroups of the job loop at most
 SHAPES = (4, 10, 14)
 BITS = [50, 61, 50]
 N_POLY, LIMBS = 2, 3
-PLANS = {"A": (10, 4, 2, 2, [50] * 6), "B": (13, 3, 1, 3, [50, 61, 50, 50]), "C": (14, 6, 2, 3, [50] * 8), "D": (10, CAP + 1, 1, CAP + 1, [50] * (CAP + 2))}
+PLANS = plans("ABCD")
 N_ROT = 3
 
 
@@ -35,39 +36,6 @@ def F():
 @pytest.fixture(scope="module")
 def eng(F):
     return F.default_engine()
-
-
-def same(a, b):
-    return (a.download().reshape(-1) == b.download().reshape(-1)).all()
-
-
-def raised(d, prefix=""):
-    """[(name, flat unit)] of every raised word of a (nested) flag dictionary; lists are numbered"""
-    out = []
-    for name, f in d.items():
-        if isinstance(f, dict):
-            out += raised(f, prefix + name + ".")
-        elif isinstance(f, list):
-            for i, g in enumerate(f):
-                out += raised(g, f"{prefix}{name}[{i}].")
-        else:
-            out += [(prefix + name, int(u)) for u in np.flatnonzero(np.asarray(f).reshape(-1))]
-    return out
-
-
-def flat(d):
-    """every flag word of a (nested) flag dictionary, in a fixed order"""
-    out = []
-    for name in sorted(d):
-        f = d[name]
-        if isinstance(f, dict):
-            out += flat(f)
-        elif isinstance(f, list):
-            for g in f:
-                out += flat(g)
-        else:
-            out += np.asarray(f).reshape(-1).tolist()
-    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -100,13 +68,7 @@ class Rows:
 
 @pytest.fixture(scope="module")
 def rows(F, eng):
-    made = {}
-
-    def get(logn):
-        if logn not in made:
-            made[logn] = Rows(F, eng, logn)
-        return made[logn]
-    return get
+    return case_cache(lambda logn: Rows(F, eng, logn))
 
 
 @pytest.mark.parametrize("logn", SHAPES)
@@ -243,11 +205,9 @@ class Case:
 
     def __init__(self, F, eng, name):
         self.eng = eng
-        self.logn, self.L, self.K, self.dnum, bits = PLANS[name]
+        self.logn, self.L, self.K, self.dnum, _ = PLANS[name]
         self.N, self.M = 1 << self.logn, self.L + self.K
-        self.qs = F.create_moduli(self.N, bits)
-        self.t = eng.tables(self.logn, self.qs)
-        self.ks, self.ab = F.KeySwitch(eng, self.t, self.L, self.K, self.dnum), F.Abft(eng, self.t)
+        self.qs, self.t, self.ks, self.ab = sealed_plan(F, eng, PLANS[name])
         rng = np.random.default_rng(1919 + self.logn + self.dnum)
         poly = lambda: np.stack([rng.integers(16, q - 16, self.N, dtype=np.uint64) for q in self.qs[:self.L]])
         self.c0, self.c1 = poly(), poly()
@@ -280,13 +240,7 @@ class Case:
 
 @pytest.fixture(scope="module")
 def cases(F, eng):
-    made = {}
-
-    def get(name):
-        if name not in made:
-            made[name] = Case(F, eng, name)
-        return made[name]
-    return get
+    return case_cache(lambda name: Case(F, eng, name))
 
 
 @pytest.mark.parametrize("name", list(PLANS))

@@ -7,13 +7,14 @@ each without and with plain modulus 65537, without and with the rescale."""
 import numpy as np
 import pytest
 
+from helpers.sealed_case import SealedCase, case_cache, flat, flip, plain_modulus, plans, py_seals, raised, same
+
 pytestmark = pytest.mark.gpu
 
 INVALID = 1
 SUM, RANGE = 1, 2
-P = (1 << 61) - 1
 GARBAGE = 0x5A5A5A5A5A5A5A5A
-PLANS = {"A": (10, 4, 2, 2, [50] * 6), "B": (13, 3, 1, 3, [50, 61, 50, 50]), "C": (14, 6, 2, 3, [50] * 8)}
+PLANS = plans("ABC")
 NAMES = ("a0", "a1", "b0", "b1")
 PARAMS = [(name, tp, resc) for name in PLANS for tp in (0, 65537) for resc in (False, True)]
 
@@ -29,89 +30,18 @@ def eng(F):
     return F.default_engine()
 
 
-def py_seals(x):
-    out = []
-    for row in np.asarray(x).reshape(-1, np.shape(x)[-1]).tolist():
-        out.append([sum(row) % P, sum((j + 1) * v for j, v in enumerate(row)) % P])
-    return out
-
-
-class Case:
+class Case(SealedCase):
     """a plan, its detector, seeded operands and key on the host and on the device, and their seals"""
 
     def __init__(self, F, eng, name):
-        self.logn, self.L, self.K, self.dnum, bits = PLANS[name]
-        self.N, self.M = 1 << self.logn, self.L + self.K
-        self.qs = F.create_moduli(self.N, bits)
-        self.t = eng.tables(self.logn, self.qs)
-        self.ks, self.ab = F.KeySwitch(eng, self.t, self.L, self.K, self.dnum), F.Abft(eng, self.t)
-        rng = np.random.default_rng(77 + self.logn)
-        poly = lambda: np.stack([rng.integers(16, q - 16, self.N, dtype=np.uint64) for q in self.qs[:self.L]])      # bit 3 flips stay below q
-        self.ops = [poly() for _ in range(4)]
-        self.key = np.stack([np.stack([np.stack([rng.integers(16, q - 16, self.N, dtype=np.uint64) for q in self.qs]) for _ in range(2)])
-                             for _ in range(self.dnum)])
-        self.d = [eng.upload(v) for v in self.ops]
-        self.dk = eng.upload(self.key)
-        self.seals = [self.t.seal(v, limbs=self.L) for v in self.d]
-        self.key_seal = self.ks.seal_key(self.dk)
+        super().__init__(F, eng, PLANS[name], seed=77 + PLANS[name][0], margin=16)      # bit 3 flips stay below q
         for v, s in zip(self.ops, self.seals):
             assert s.download().tolist() == py_seals(v)
 
 
 @pytest.fixture(scope="module")
 def cases(F, eng):
-    made = {}
-
-    def get(name):
-        if name not in made:
-            made[name] = Case(F, eng, name)
-        return made[name]
-    return get
-
-
-class plain_modulus:
-    def __init__(self, ks, t):
-        self.ks, self.t = ks, t
-
-    def __enter__(self):
-        self.ks.set_plain_modulus(self.t)
-
-    def __exit__(self, *exc):
-        self.ks.set_plain_modulus(0)
-
-
-def raised(d, prefix=""):
-    """[(name, flat unit)] of every raised word of a (nested) flag dictionary"""
-    out = []
-    for name, f in d.items():
-        if f is None:
-            continue
-        if isinstance(f, dict):
-            out += raised(f, prefix + name + ".")
-        else:
-            out += [(prefix + name, int(u)) for u in np.flatnonzero(np.asarray(f).reshape(-1))]
-    return out
-
-
-def flat(d):
-    """every flag word of a (nested) flag dictionary with its name, in a fixed order"""
-    out = []
-    for name in sorted(d):
-        f = d[name]
-        if isinstance(f, dict):
-            out += [(name + "." + n, v) for n, v in flat(f)]
-        elif f is not None:
-            out.append((name, np.asarray(f).reshape(-1).tolist()))
-    return out
-
-
-def flip(eng, d, idx, bit):
-    from fhe_reliability_gpu_amd._lib import check, lib
-    check(lib.fhe_flip_bit(eng._h, d.ptr, idx, bit, None))
-
-
-def same(a, b):
-    return (a.download().reshape(-1) == b.download().reshape(-1)).all()
+    return case_cache(lambda name: Case(F, eng, name))
 
 
 @pytest.mark.parametrize("name,tp,resc", PARAMS)

@@ -10,14 +10,14 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from helpers.sealed_case import CAP, SealedCase, case_cache, flat, flip, plain_modulus, plans, py_seals, raised, same, same_call
+
 pytestmark = pytest.mark.gpu
 
 INVALID = 1
 SUM, RANGE = 1, 2
-P = (1 << 61) - 1
 GARBAGE = 0x5A5A5A5A5A5A5A5A
-CAP = 12
-PLANS = {"A": (10, 4, 2, 2, [50] * 6), "B": (13, 3, 1, 3, [50, 61, 50, 50]), "C": (14, 6, 2, 3, [50] * 8), "D": (10, CAP + 1, 1, CAP + 1, [50] * (CAP + 2))}
+PLANS = plans("ABCD")
 PARAMS = [(name, tp) for name in PLANS for tp in (0, 65537)]
 FUSED = [(name, tp) for name, tp in PARAMS if name != "D"]
 GALOIS = 5
@@ -34,32 +34,13 @@ def eng(F):
     return F.default_engine()
 
 
-def py_seals(x):
-    out = []
-    for row in np.asarray(x).reshape(-1, np.shape(x)[-1]).tolist():
-        out.append([sum(row) % P, sum((j + 1) * v for j, v in enumerate(row)) % P])
-    return out
-
-
-class Case:
+class Case(SealedCase):
     """a plan, its detector, seeded operands and key on the host and on the device, and their seals"""
 
     def __init__(self, F, eng, name):
-        self.logn, self.L, self.K, self.dnum, bits = PLANS[name]
-        self.N, self.M = 1 << self.logn, self.L + self.K
+        logn, _, _, dnum, _ = PLANS[name]
+        super().__init__(F, eng, PLANS[name], seed=177 + logn + dnum, margin=16)
         self.alpha = -(-self.L // self.dnum)
-        self.qs = F.create_moduli(self.N, bits)
-        self.t = eng.tables(self.logn, self.qs)
-        self.ks, self.ab = F.KeySwitch(eng, self.t, self.L, self.K, self.dnum), F.Abft(eng, self.t)
-        rng = np.random.default_rng(177 + self.logn + self.dnum)
-        poly = lambda: np.stack([rng.integers(16, q - 16, self.N, dtype=np.uint64) for q in self.qs[:self.L]])
-        self.ops = [poly() for _ in range(4)]
-        self.key = np.stack([np.stack([np.stack([rng.integers(16, q - 16, self.N, dtype=np.uint64) for q in self.qs]) for _ in range(2)])
-                             for _ in range(self.dnum)])
-        self.d = [eng.upload(v) for v in self.ops]
-        self.dk = eng.upload(self.key)
-        self.seals = [self.t.seal(v, limbs=self.L) for v in self.d]
-        self.key_seal = self.ks.seal_key(self.dk)
         self.rows = self.dnum * 2 * self.M
         sample = [0, self.rows - 1, (self.rows // 2) | 1]
         got = self.key_seal.download().reshape(self.rows, 2)
@@ -80,63 +61,7 @@ class Case:
 
 @pytest.fixture(scope="module")
 def cases(F, eng):
-    made = {}
-
-    def get(name):
-        if name not in made:
-            made[name] = Case(F, eng, name)
-        return made[name]
-    return get
-
-
-class plain_modulus:
-    def __init__(self, ks, t):
-        self.ks, self.t = ks, t
-
-    def __enter__(self):
-        self.ks.set_plain_modulus(self.t)
-
-    def __exit__(self, *exc):
-        self.ks.set_plain_modulus(0)
-
-
-def raised(d, prefix=""):
-    """[(name, flat unit)] of every raised word of a (nested) flag dictionary"""
-    out = []
-    for name, f in d.items():
-        if f is None:
-            continue
-        if isinstance(f, dict):
-            out += raised(f, prefix + name + ".")
-        else:
-            out += [(prefix + name, int(u)) for u in np.flatnonzero(np.asarray(f).reshape(-1))]
-    return out
-
-
-def flat(d):
-    """every flag word of a (nested) flag dictionary with its name, in a fixed order"""
-    out = []
-    for name in sorted(d):
-        f = d[name]
-        if isinstance(f, dict):
-            out += [(name + "." + n, v) for n, v in flat(f)]
-        elif f is not None:
-            out.append((name, np.asarray(f).reshape(-1).tolist()))
-    return out
-
-
-def flip(eng, d, idx, bit):
-    from fhe_reliability_gpu_amd._lib import check, lib
-    check(lib.fhe_flip_bit(eng._h, d.ptr, idx, bit, None))
-
-
-def same(a, b):
-    return (a.download().reshape(-1) == b.download().reshape(-1)).all()
-
-
-def same_call(x, y):
-    """two sealed composites' results (out0, out1, (seal0, seal1), flags): words, output seals and every flag word"""
-    return same(x[0], y[0]) and same(x[1], y[1]) and all(same(s, r) for s, r in zip(x[2], y[2])) and flat(x[3]) == flat(y[3])
+    return case_cache(lambda name: Case(F, eng, name))
 
 
 def swept_apply(c, tp, key_seal=None):
@@ -144,10 +69,6 @@ def swept_apply(c, tp, key_seal=None):
     kf = c.t.seal_verify(c.dk, c.key_seal if key_seal is None else key_seal, limbs=c.M, n_poly=2 * c.dnum)
     o0, o1, cf = (c.ks.bgv_apply_checked if tp else c.ks.apply_checked)(c.d[0], c.dk, c.ab)
     return o0, o1, {"key": np.asarray(kf).reshape(c.dnum, 2, c.M), "checked": cf}
-
-
-def unchanged(c):
-    return all((dv.download().reshape(-1) == v.reshape(-1)).all() for dv, v in zip(c.d + [c.dk], c.ops + [c.key]))
 
 
 @pytest.mark.parametrize("name,tp", PARAMS)
@@ -179,7 +100,7 @@ def test_clean_words_flags_and_seals_are_the_sweep_based_calls(F, eng, cases, na
             assert raised(got[3]) == [] and same_call(got, ks.hmult_sealed(*c.d, c.dk, ab, **kw))
             w0, w1 = ks.hmult(*c.d, c.dk, rescale=resc)
             assert same(got[0], w0) and same(got[1], w1)
-        assert unchanged(c)
+        assert c.unchanged()
     eng.check()
 
 
@@ -220,7 +141,7 @@ def test_corruptions_at_rest_in_the_key_give_the_sweep_based_calls_flags_and_wor
         check_all(all_calls(eng.upload(s)), row, "seal word")
         # the call after it is clean
         assert all(raised(f[-1]) == [] for f, _ in all_calls(c.key_seal))
-        assert unchanged(c)
+        assert c.unchanged()
     eng.check()
 
 
@@ -250,7 +171,7 @@ def test_a_fault_on_the_multiplying_load_is_seen_by_the_fused_calls_only(F, eng,
             mac = fl["checked"]["mac"] if "mac" in fl["checked"] else fl["checked"]["keyswitch"]["mac"]
             assert not np.asarray(mac).any(), what
             assert not (same(got[0], clean[0]) and same(got[1], clean[1])), what      # the product is that of the word as loaded
-            assert unchanged(c), what                                                  # memory is clean
+            assert c.unchanged(), what                                                  # memory is clean
             again = fused()                                                           # one shot
             assert raised(again[-1]) == [] and same(again[0], clean[0]) and same(again[1], clean[1]), what
         # out of the window on the load: both bits on the key row, and that half of the inner product cannot be checked

@@ -11,12 +11,14 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from helpers.sealed_case import SealedCase, case_cache, flat, flip, plain_modulus, plans, raised, same
+
 pytestmark = pytest.mark.gpu
 
 INVALID = 1
 SUM, RANGE = 1, 2
 GARBAGE = 0x5A5A5A5A5A5A5A5A
-PLANS = {"A": (10, 4, 2, 2, [50] * 6), "B": (13, 3, 1, 3, [50, 61, 50, 50]), "C": (14, 6, 2, 3, [50] * 8)}
+PLANS = plans("ABC")
 NAMES = list(PLANS)
 PARAMS = [(name, tp) for name in PLANS for tp in (0, 65537)]
 GALOIS = 5
@@ -34,24 +36,12 @@ def eng(F):
     return F.default_engine()
 
 
-class Case:
+class Case(SealedCase):
     """a plan, its detector, seeded operands and key on the host and on the device, their seals, and the unchecked references"""
 
     def __init__(self, F, eng, name):
-        self.logn, self.L, self.K, self.dnum, bits = PLANS[name]
-        self.N, self.M = 1 << self.logn, self.L + self.K
-        self.qs = F.create_moduli(self.N, bits)
-        self.t = eng.tables(self.logn, self.qs)
-        self.ks, self.ab = F.KeySwitch(eng, self.t, self.L, self.K, self.dnum), F.Abft(eng, self.t)
-        rng = np.random.default_rng(277 + self.logn + self.dnum)
-        poly = lambda: np.stack([rng.integers(16, q - 16, self.N, dtype=np.uint64) for q in self.qs[:self.L]])
-        self.ops = [poly() for _ in range(2)]
-        self.key = np.stack([np.stack([np.stack([rng.integers(16, q - 16, self.N, dtype=np.uint64) for q in self.qs]) for _ in range(2)])
-                             for _ in range(self.dnum)])
-        self.d = [eng.upload(v) for v in self.ops]
-        self.dk = eng.upload(self.key)
-        self.seals = [self.t.seal(v, limbs=self.L) for v in self.d]
-        self.key_seal = self.ks.seal_key(self.dk)
+        logn, _, _, dnum, _ = PLANS[name]
+        super().__init__(F, eng, PLANS[name], seed=277 + logn + dnum, margin=16, n_ops=2)
         self.rows = self.dnum * 2 * self.M
         self.edge = TILE if self.logn >= 13 else self.N // 2
         self.intt_ref = self.unchecked_intt(eng, self.d[0])      # computed once, shared
@@ -66,63 +56,11 @@ class Case:
         """(row, word): word 0, both sides of a tile edge, the last word -- on chosen rows"""
         return [(0, 0), (1, self.edge - 1), (self.L - 1, self.edge), (self.L // 2, self.N - 1)]
 
-    def unchanged(self):
-        return all((dv.download().reshape(-1) == v.reshape(-1)).all() for dv, v in zip(self.d + [self.dk], self.ops + [self.key]))
-
 
 @pytest.fixture(scope="module")
 def cases(F, eng):
-    made = {}
+    return case_cache(lambda name: Case(F, eng, name))
 
-    def get(name):
-        if name not in made:
-            made[name] = Case(F, eng, name)
-        return made[name]
-    return get
-
-
-class plain_modulus:
-    def __init__(self, ks, t):
-        self.ks, self.t = ks, t
-
-    def __enter__(self):
-        self.ks.set_plain_modulus(self.t)
-
-    def __exit__(self, *exc):
-        self.ks.set_plain_modulus(0)
-
-
-def raised(d, prefix=""):
-    """[(name, flat unit)] of every raised word of a (nested) flag dictionary"""
-    out = []
-    for name, f in d.items():
-        if f is None:
-            continue
-        if isinstance(f, dict):
-            out += raised(f, prefix + name + ".")
-        else:
-            out += [(prefix + name, int(u)) for u in np.flatnonzero(np.asarray(f).reshape(-1))]
-    return out
-
-
-def flat(d):
-    out = []
-    for name in sorted(d):
-        f = d[name]
-        if isinstance(f, dict):
-            out += [(name + "." + n, v) for n, v in flat(f)]
-        elif f is not None:
-            out.append((name, np.asarray(f).reshape(-1).tolist()))
-    return out
-
-
-def flip(eng, d, idx, bit):
-    from fhe_reliability_gpu_amd._lib import check, lib
-    check(lib.fhe_flip_bit(eng._h, d.ptr, idx, bit, None))
-
-
-def same(a, b):
-    return (a.download().reshape(-1) == b.download().reshape(-1)).all()
 
 
 # ---- the transform ----

@@ -12,6 +12,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from helpers.sealed_case import case_cache, flip, plain_modulus, plans, raised, sealed_plan
+
 pytestmark = pytest.mark.gpu
 
 INVALID = 1
@@ -19,7 +21,7 @@ SUM, RANGE = 1, 2
 PW_OPERAND = 4
 LOAD, STORE = 0, 1
 GARBAGE = 0x5A5A5A5A5A5A5A5A
-PLANS = {"A": (10, 4, 2, 2, [50] * 6), "B": (13, 3, 1, 3, [50, 61, 50, 50]), "C": (14, 6, 2, 3, [50] * 8)}
+PLANS = plans("ABC")
 PARAMS = [(name, tp) for name in PLANS for tp in (0, 65537)]
 CHUNK = 8192
 
@@ -39,11 +41,9 @@ class Case:
     """a plan, its detector, a seeded three-part input on the host and on the device, and its seal"""
 
     def __init__(self, F, eng, name):
-        self.logn, self.L, self.K, self.dnum, bits = PLANS[name]
+        self.logn, self.L, self.K, self.dnum, _ = PLANS[name]
         self.N, self.R = 1 << self.logn, self.L - 1
-        self.qs = F.create_moduli(self.N, bits)
-        self.t = eng.tables(self.logn, self.qs)
-        self.ks, self.ab = F.KeySwitch(eng, self.t, self.L, self.K, self.dnum), F.Abft(eng, self.t)
+        self.qs, self.t, self.ks, self.ab = sealed_plan(F, eng, PLANS[name])
         rng = np.random.default_rng(311 + self.logn + self.dnum)
         self.c = np.stack([np.stack([rng.integers(16, q - 16, self.N, dtype=np.uint64) for q in self.qs[:self.L]]) for _ in range(3)])
         self.d = eng.upload(self.c)
@@ -66,42 +66,7 @@ class Case:
 
 @pytest.fixture(scope="module")
 def cases(F, eng):
-    made = {}
-
-    def get(name):
-        if name not in made:
-            made[name] = Case(F, eng, name)
-        return made[name]
-    return get
-
-
-class plain_modulus:
-    def __init__(self, ks, t):
-        self.ks, self.t = ks, t
-
-    def __enter__(self):
-        self.ks.set_plain_modulus(self.t)
-
-    def __exit__(self, *exc):
-        self.ks.set_plain_modulus(0)
-
-
-def raised(d, prefix=""):
-    """[(name, flat unit)] of every raised word of a (nested) flag dictionary"""
-    out = []
-    for name, f in d.items():
-        if f is None:
-            continue
-        if isinstance(f, dict):
-            out += raised(f, prefix + name + ".")
-        else:
-            out += [(prefix + name, int(u)) for u in np.flatnonzero(np.asarray(f).reshape(-1))]
-    return out
-
-
-def flip(eng, d, idx, bit):
-    from fhe_reliability_gpu_amd._lib import check, lib
-    check(lib.fhe_flip_bit(eng._h, d.ptr, idx, bit, None))
+    return case_cache(lambda name: Case(F, eng, name))
 
 
 def words_of(o, c, n):

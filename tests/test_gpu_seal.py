@@ -13,14 +13,14 @@ import numpy as np
 import pytest
 
 from helpers.checked_plan import limb_bits
+from helpers.sealed_case import SealedCase, case_cache, flip, plain_modulus, plans, py_seals, raised, safe_coeff, same
 
 pytestmark = pytest.mark.gpu
 
 INVALID, UNSUPPORTED = 1, 3
 SUM, RANGE = 1, 2
-P = (1 << 61) - 1
 GARBAGE = 0x5A5A5A5A5A5A5A5A
-PLANS = {"A": (10, 4, 2, 2, [50] * 6), "B": (13, 3, 1, 3, [50, 61, 50, 50])}
+PLANS = plans("AB")
 SHAPES = [(1, 1, 0), (3, 2, 1), (1, 7, 0)]
 
 
@@ -33,19 +33,6 @@ def F():
 @pytest.fixture(scope="module")
 def eng(F):
     return F.default_engine()
-
-
-def py_seals(x):
-    """[rows][2] Python integers of x = [..., N]"""
-    out = []
-    for row in np.asarray(x).reshape(-1, np.shape(x)[-1]).tolist():
-        out.append([sum(row) % P, sum((j + 1) * v for j, v in enumerate(row)) % P])
-    return out
-
-
-def flip(eng, d, idx, bit):
-    from fhe_reliability_gpu_amd._lib import check, lib
-    check(lib.fhe_flip_bit(eng._h, d.ptr, idx, bit, None))
 
 
 # ---------------------------------------------------------------------------------------------------------------- primitives
@@ -182,24 +169,11 @@ def test_scratch_growth_between_launches_in_flight(F):
 
 
 # ---------------------------------------------------------------------------------------------------------------- composites
-class Case:
+class Case(SealedCase):
     """a plan, its detector, seeded operands on the host and on the device, and their seals"""
 
     def __init__(self, F, eng, name):
-        self.logn, self.L, self.K, self.dnum, bits = PLANS[name]
-        self.N, self.M = 1 << self.logn, self.L + self.K
-        self.qs = F.create_moduli(self.N, bits)
-        self.t = eng.tables(self.logn, self.qs)
-        self.ks, self.ab = F.KeySwitch(eng, self.t, self.L, self.K, self.dnum), F.Abft(eng, self.t)
-        rng = np.random.default_rng(self.logn)
-        poly = lambda: np.stack([rng.integers(0, q, self.N, dtype=np.uint64) for q in self.qs[:self.L]])
-        self.ops = [poly() for _ in range(4)]
-        self.key = np.stack([np.stack([np.stack([rng.integers(0, q, self.N, dtype=np.uint64) for q in self.qs]) for _ in range(2)])
-                             for _ in range(self.dnum)])
-        self.d = [eng.upload(v) for v in self.ops]
-        self.dk = eng.upload(self.key)
-        self.seals = [self.t.seal(v, limbs=self.L) for v in self.d]
-        self.key_seal = self.ks.seal_key(self.dk)
+        super().__init__(F, eng, PLANS[name], seed=PLANS[name][0], margin=0)
         # the seals the composites are handed are right: Python integers
         for v, s in zip(self.ops, self.seals):
             assert s.download().tolist() == py_seals(v)
@@ -208,50 +182,11 @@ class Case:
 
 @pytest.fixture(scope="module")
 def cases(F, eng):
-    made = {}
-
-    def get(name):
-        if name not in made:
-            made[name] = Case(F, eng, name)
-        return made[name]
-    return get
-
-
-class plain_modulus:
-    def __init__(self, ks, t):
-        self.ks, self.t = ks, t
-
-    def __enter__(self):
-        self.ks.set_plain_modulus(self.t)
-
-    def __exit__(self, *exc):
-        self.ks.set_plain_modulus(0)
-
-
-def _raised(d, prefix=""):
-    """[(name, flat unit)] of every raised word of a (nested) flag dictionary"""
-    out = []
-    for name, f in d.items():
-        if f is None:
-            continue
-        if isinstance(f, dict):
-            out += _raised(f, prefix + name + ".")
-        else:
-            out += [(prefix + name, int(u)) for u in np.flatnonzero(np.asarray(f).reshape(-1))]
-    return out
+    return case_cache(lambda name: Case(F, eng, name))
 
 
 def _seal_blocks(flags):
     return {k: v for k, v in flags.items() if k != "checked"}
-
-
-def _same(a, b):
-    return (a.download().reshape(-1) == b.download().reshape(-1)).all()
-
-
-def _safe_coeff(words, q, first):
-    """a coefficient from `first` on whose word stays below q whichever way bit 3 flips"""
-    return next(j for j in range(first, len(words)) if int(words[j]) < q - 16)
 
 
 PARAMS = [("A", 0), ("A", 65537), ("B", 0), ("B", 65537)]
@@ -269,18 +204,18 @@ def test_clean_sealed_calls_give_the_unchecked_words_no_flag_and_the_outputs_sea
             assert [lay[k][0] for k in ("a0", "a1", "b0", "b1", "key")] == [0, L, 2 * L, 3 * L, 4 * L]
             assert lay["checked"] == 4 * L + 2 * c.dnum * c.M and lay["total"] == lay["checked"] + inner["total"]
             o0, o1, so, fl = ks.hmult_sealed(*c.d, c.dk, ab, seals=c.seals, key_seal=c.key_seal, rescale=resc)
-            assert _raised(fl) == [], (resc, _raised(fl))
+            assert raised(fl) == [], (resc, raised(fl))
             assert sorted(fl) == ["a0", "a1", "b0", "b1", "checked", "key"] and fl["key"].shape == (c.dnum, 2, c.M)
             w0, w1 = ks.hmult(*c.d, c.dk, rescale=resc)
-            assert _same(o0, w0) and _same(o1, w1), resc
+            assert same(o0, w0) and same(o1, w1), resc
             assert so[0].download().tolist() == py_seals(w0.download()) and so[1].download().tolist() == py_seals(w1.download())
         rl = ks.rotate_sealed_layout()
         inner = ks.bgv_checked_layout() if tp else ks.checked_layout()
         assert [rl[k][0] for k in ("c0", "c1", "key")] == [0, L, 2 * L] and rl["total"] == rl["checked"] + inner["total"]
         o0, o1, so, fl = ks.rotate_sealed(c.d[0], c.d[1], gal, c.dk, ab, seals=c.seals[:2], key_seal=c.key_seal)
-        assert _raised(fl) == []
+        assert raised(fl) == []
         w0, w1 = ks.rotate(c.d[0], c.d[1], gal, c.dk)
-        assert _same(o0, w0) and _same(o1, w1)
+        assert same(o0, w0) and same(o1, w1)
         assert so[0].download().tolist() == py_seals(w0.download()) and so[1].download().tolist() == py_seals(w1.download())
         # inputs untouched
         for dv, v in zip(c.d + [c.dk], c.ops + [c.key]):
@@ -302,30 +237,30 @@ def test_a_flipped_word_at_rest_passes_the_checked_call_and_raises_its_seal_row(
         targets = [("a0", c.d[0], L - 1, c.ops[0][L - 1], c.qs[L - 1]), ("b1", c.d[3], 0, c.ops[3][0], c.qs[0]),
                    ("key", c.dk, key_row, c.key[1, 1, M - 1], c.qs[M - 1])]
         for what, dev, row, words, q in targets:
-            j = _safe_coeff(words, q, N // 2 + 7)
+            j = safe_coeff(words, q, N // 2 + 7)
             flip(eng, dev, row * N + j, 3)
             try:
                 # the gap: the checked call computes on the flipped operand and raises nothing
                 o0, o1, fl = checked(*c.d, c.dk, ab)
-                assert _raised(fl) == [], what
+                assert raised(fl) == [], what
                 assert (o0.download() != clean[0]).any() or (o1.download() != clean[1]).any(), what
                 # its closure: exactly that row of the seal blocks
                 p0, p1, so, sfl = ks.hmult_sealed(*c.d, c.dk, ab, seals=c.seals, key_seal=c.key_seal)
-                assert _raised(_seal_blocks(sfl)) == [(what, row)], (what, _raised(_seal_blocks(sfl)))
+                assert raised(_seal_blocks(sfl)) == [(what, row)], (what, raised(_seal_blocks(sfl)))
                 assert int(np.asarray(sfl[what]).reshape(-1)[row]) == SUM
-                assert _same(p0, o0) and _same(p1, o1)           # the call went on, on what it was given
+                assert same(p0, o0) and same(p1, o1)           # the call went on, on what it was given
                 # a NULL seal skips its rows
                 seals = [None if n == what else s for n, s in zip(("a0", "a1", "b0", "b1"), c.seals)]
                 sfl = ks.hmult_sealed(*c.d, c.dk, ab, seals=seals, key_seal=None if what == "key" else c.key_seal)[3]
-                assert _raised(_seal_blocks(sfl)) == [], what
+                assert raised(_seal_blocks(sfl)) == [], what
                 if what in ("a0", "key"):      # a0 is the rotation's c0
                     o0, o1, fl = rchecked(c.d[0], c.d[1], 5, c.dk, ab)
-                    assert _raised(fl) == [] and ((o0.download() != rclean[0]).any() or (o1.download() != rclean[1]).any()), what
+                    assert raised(fl) == [] and ((o0.download() != rclean[0]).any() or (o1.download() != rclean[1]).any()), what
                     sfl = ks.rotate_sealed(c.d[0], c.d[1], 5, c.dk, ab, seals=c.seals[:2], key_seal=c.key_seal)[3]
-                    assert _raised(_seal_blocks(sfl)) == [("c0" if what == "a0" else "key", row)], what
+                    assert raised(_seal_blocks(sfl)) == [("c0" if what == "a0" else "key", row)], what
             finally:
                 flip(eng, dev, row * N + j, 3)
-        assert _raised(ks.hmult_sealed(*c.d, c.dk, ab, seals=c.seals, key_seal=c.key_seal)[3]) == []
+        assert raised(ks.hmult_sealed(*c.d, c.dk, ab, seals=c.seals, key_seal=c.key_seal)[3]) == []
         assert ks.hmult_sealed(*c.d, c.dk, ab)[3]["a0"].tolist() == [0] * L      # no seal at all: nothing verified
     eng.check()
 
@@ -340,20 +275,20 @@ def test_the_checked_calls_hook_fires_in_the_embedded_block_and_the_chain_carrie
         # stage 7 (tail), the word before its window check, unit 1: its own word of the embedded block, nothing in the seal blocks
         check(arm(eng._h, 7, 2, 1, 3, 30))
         fl = ks.hmult_sealed(*c.d, c.dk, ab, seals=c.seals, key_seal=c.key_seal)[3]
-        assert _raised(fl) == [("checked.keyswitch.tail", 1)], _raised(fl)
+        assert raised(fl) == [("checked.keyswitch.tail", 1)], raised(fl)
         check(arm(eng._h, 7, 2, L + 1, 3, 30))
         fl = ks.rotate_sealed(c.d[0], c.d[1], 5, c.dk, ab, seals=c.seals[:2], key_seal=c.key_seal)[3]
-        assert _raised(fl) == [("checked.tail", L + 1)], _raised(fl)
+        assert raised(fl) == [("checked.tail", L + 1)], raised(fl)
         # the chain: a multiply's sealed output, one bit flipped at rest, into a sealed rotation
         o0, o1, so, fl = ks.hmult_sealed(*c.d, c.dk, ab, seals=c.seals, key_seal=c.key_seal, rescale=False)
-        assert _raised(fl) == []
-        assert _raised(ks.rotate_sealed(o0, o1, 5, c.dk, ab, seals=so, key_seal=c.key_seal)[3]) == []
+        assert raised(fl) == []
+        assert raised(ks.rotate_sealed(o0, o1, 5, c.dk, ab, seals=so, key_seal=c.key_seal)[3]) == []
         host = o1.download()
         row = L - 1
-        j = _safe_coeff(host[row], c.qs[row], 11)
+        j = safe_coeff(host[row], c.qs[row], 11)
         flip(eng, o1, row * N + j, 3)
         fl = ks.rotate_sealed(o0, o1, 5, c.dk, ab, seals=so, key_seal=c.key_seal)[3]
-        assert _raised(_seal_blocks(fl)) == [("c1", row)]
+        assert raised(_seal_blocks(fl)) == [("c1", row)]
     eng.check()
 
 

@@ -13,12 +13,12 @@ import numpy as np
 import pytest
 
 from helpers.checked_plan import limb_bits
+from helpers.sealed_case import PLANS, flip, plain_modulus, py_seals_and_locator, raised, sealed_plan
 
 pytestmark = pytest.mark.gpu
 
 INVALID = 1
 SUM, RANGE = 1, 2
-P = (1 << 61) - 1
 GARBAGE = 0x5A5A5A5A5A5A5A5A
 GRID_CAP = 8192                 # TENSOR_SEAL_GRID_CAP of ntt_launch.hpp: workgroups of the job loop at most
 SHAPES = [(1, 1, 0), (3, 2, 1), (1, 7, 0)]
@@ -45,19 +45,6 @@ def tables(F, eng):
             made[logn] = (qs, eng.tables(logn, qs))
         return made[logn]
     return get
-
-
-def py_sums(x):
-    """[rows][3] Python integers of x = [..., N]"""
-    out = []
-    for row in np.asarray(x).reshape(-1, np.shape(x)[-1]).tolist():
-        out.append([sum(row) % P, sum((j + 1) * v for j, v in enumerate(row)) % P, sum((j + 1) ** 2 * v for j, v in enumerate(row)) % P])
-    return out
-
-
-def flip(eng, d, idx, bit):
-    from fhe_reliability_gpu_amd._lib import check, lib
-    check(lib.fhe_flip_bit(eng._h, d.ptr, idx, bit, None))
 
 
 def unchecked(eng, t, a, b, sub, **kw):
@@ -126,7 +113,7 @@ def test_carried_add_and_sub_give_the_unchecked_words_and_the_seal_of_the_result
             assert (hw.astype(object) == ((ha.astype(object) - hb.astype(object)) % q_col if sub else (ha.astype(object) + hb.astype(object)) % q_col)).all()
             want_seal, want_loc = t.seal(want, **kw).download(), t.seal_locator(want, **kw).download()
             if seed == 1:      # the library's own seal of the result is the Python-integer one
-                ps = py_sums(hw)
+                ps = py_seals_and_locator(hw)
                 assert want_seal.tolist() == [r[:2] for r in ps] and want_loc.tolist() == [r[2] for r in ps]
             call = t.modsub_sealed if sub else t.modadd_sealed
             for loc in (False, True):
@@ -213,7 +200,7 @@ def test_the_job_loop_takes_a_second_trip(F, eng):
         assert (dc.download() == hw).all()
         sums, locs = sc.download().reshape(n_poly, 2), lc.download()
         for r in probe:
-            want = py_sums(hw[r:r + 1])[0]
+            want = py_seals_and_locator(hw[r:r + 1])[0]
             assert sums[r].tolist() == want[:2] and int(locs[r]) == want[2], (sub, r)
         assert (sums == t.seal(dc, **kw).download().reshape(n_poly, 2)).all() and (locs == t.seal_locator(dc, **kw).download()).all()
         # a word changed at rest in the last row raises exactly that row
@@ -339,11 +326,9 @@ class Case:
     """plan A, its detector, seeded accumulators and one Galois key per step on the device, and their seals"""
 
     def __init__(self, F, eng):
-        self.logn, self.L, self.K, self.dnum = 10, 4, 2, 2
+        self.logn, self.L, self.K, self.dnum, _ = PLANS["A"]
         self.N, self.M = 1 << self.logn, self.L + self.K
-        self.qs = F.create_moduli(self.N, [50] * 6)
-        self.t = eng.tables(self.logn, self.qs)
-        self.ks, self.ab = F.KeySwitch(eng, self.t, self.L, self.K, self.dnum), F.Abft(eng, self.t)
+        self.qs, self.t, self.ks, self.ab = sealed_plan(F, eng, PLANS["A"])
         rng = np.random.default_rng(self.logn)
         self.c = [np.stack([rng.integers(16, q - 16, self.N, dtype=np.uint64) for q in self.qs[:self.L]]) for _ in range(2)]
         self.keys = [eng.upload(np.stack([rng.integers(0, q, self.N, dtype=np.uint64) for _ in range(2 * self.dnum) for q in self.qs])) for _ in GALOIS]
@@ -356,28 +341,6 @@ class Case:
 @pytest.fixture(scope="module")
 def case(F, eng):
     return Case(F, eng)
-
-
-class plain_modulus:
-    def __init__(self, ks, t):
-        self.ks, self.t = ks, t
-
-    def __enter__(self):
-        self.ks.set_plain_modulus(self.t)
-
-    def __exit__(self, *exc):
-        self.ks.set_plain_modulus(0)
-
-
-def _raised(d, prefix=""):
-    """[(name, flat unit)] of every raised word of a (nested) flag dictionary"""
-    out = []
-    for name, f in d.items():
-        if isinstance(f, dict):
-            out += _raised(f, prefix + name + ".")
-        elif f is not None:
-            out += [(prefix + name, int(u)) for u in np.flatnonzero(np.asarray(f).reshape(-1))]
-    return out
 
 
 def run(c, d=None):
@@ -393,7 +356,7 @@ def test_clean_rotate_and_sum_gives_the_unchecked_chain_no_flag_and_the_final_se
         lay, rl = ks.rotate_sum_sealed_layout(len(GALOIS)), ks.rotate_sealed_layout()
         assert lay["add"] == rl["total"] and lay["stride"] == rl["total"] + 2 * L and lay["total"] == len(GALOIS) * lay["stride"]
         o0, o1, so, steps = run(c)
-        assert [_raised(s) for s in steps] == [[]] * len(GALOIS)
+        assert [raised(s) for s in steps] == [[]] * len(GALOIS)
         assert sorted(steps[0]) == ["add0", "add1", "c0", "c1", "checked", "key"]
         # the chain of unchecked calls
         w = [clone(eng, c.d[0]), clone(eng, c.d[1])]
@@ -404,7 +367,7 @@ def test_clean_rotate_and_sum_gives_the_unchecked_chain_no_flag_and_the_final_se
         assert (o0.download() == w[0].download()).all() and (o1.download() == w[1].download()).all()
         for h in range(2):
             assert (so[h].download() == c.t.seal(w[h], limbs=L).download()).all()
-            assert so[h].download().tolist() == [r[:2] for r in py_sums(w[h].download())]
+            assert so[h].download().tolist() == [r[:2] for r in py_seals_and_locator(w[h].download())]
         # the inputs and their seals are untouched
         assert all((dv.download() == v).all() for dv, v in zip(c.d, c.c))
     eng.check()
@@ -427,20 +390,20 @@ def test_faults_at_rest_and_in_the_adds_show_where_the_layout_says(F, eng, case,
         # the carry hook after the digest of add 0 (step 0, c0): nothing in step 0, exactly that row of step 1's input block
         check(lib.fhe_ctx_inject_fault_seal_carry(eng._h, 0, 3, row, j, 0))
         steps = run(c)[3]
-        assert _raised(steps[0]) == []
+        assert raised(steps[0]) == []
         assert only(steps[1]["c0"]) and int(steps[1]["c0"][row]) & SUM and not steps[1]["c1"].any() and not steps[1]["key"].any()
         # the carry hook before the digest of add 2 (step 1, c0): that add row, the same row of step 2's input block, nothing before
         check(lib.fhe_ctx_inject_fault_seal_carry(eng._h, 2, 2, row, j, 0))
         steps = run(c)[3]
-        assert _raised(steps[0]) == []
-        assert _raised({k: v for k, v in steps[1].items() if k not in ("add0", "add1")}) == []
+        assert raised(steps[0]) == []
+        assert raised({k: v for k, v in steps[1].items() if k not in ("add0", "add1")}) == []
         assert steps[1]["add0"].tolist() == [SUM if r == row else 0 for r in range(L)] and not steps[1]["add1"].any()
         assert only(steps[2]["c0"]) and int(steps[2]["c0"][row]) & SUM and not steps[2]["c1"].any() and not steps[2]["key"].any()
         # one shot: clean again
-        assert [_raised(s) for s in run(c)[3]] == [[]] * len(GALOIS)
+        assert [raised(s) for s in run(c)[3]] == [[]] * len(GALOIS)
         # a hook row outside the composite's adds: refused with nothing launched
         check(lib.fhe_ctx_inject_fault_seal_carry(eng._h, 5, 2, L, 0, 0))
         with pytest.raises(F.FheError):
             run(c)
-        assert [_raised(s) for s in run(c)[3]] == [[]] * len(GALOIS)
+        assert [raised(s) for s in run(c)[3]] == [[]] * len(GALOIS)
     eng.check()

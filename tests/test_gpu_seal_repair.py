@@ -11,14 +11,14 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from helpers.checked_plan import checked_plan, limb_bits
+from helpers.checked_plan import limb_bits
+from helpers.sealed_case import P, SealedCase, case_cache, flip, plain_modulus, py_seals_and_locator, raised, safe_coeff
 
 pytestmark = pytest.mark.gpu
 
 INVALID = 1
 SUM, RANGE = 1, 2
 CLEAN, REPAIRED, UNCORRECTABLE, TRANSIENT, SUSPECT = 0, 1, 2, 3, 4
-P = (1 << 61) - 1
 GARBAGE = 0x5A5A5A5A5A5A5A5A
 SHAPES = {5: (2, 3, 1), 13: (2, 3, 1), 14: (2, 3, 1), 17: (1, 3, 0)}      # logn: (n_poly, limbs, start_idx)
 
@@ -32,19 +32,6 @@ def F():
 @pytest.fixture(scope="module")
 def eng(F):
     return F.default_engine()
-
-
-def py_sums(x):
-    """[rows][3] Python integers of x = [..., N]"""
-    out = []
-    for row in np.asarray(x).reshape(-1, np.shape(x)[-1]).tolist():
-        out.append([sum(row) % P, sum((j + 1) * v for j, v in enumerate(row)) % P, sum((j + 1) * (j + 1) * v for j, v in enumerate(row)) % P])
-    return out
-
-
-def flip(eng, d, idx, bit):
-    from fhe_reliability_gpu_amd._lib import check, lib
-    check(lib.fhe_flip_bit(eng._h, d.ptr, int(idx), int(bit), None))
 
 
 class Rows:
@@ -71,7 +58,7 @@ class Rows:
         self.x = x
         self.kw = dict(limbs=self.limbs, start=self.start, n_poly=self.n_poly)
         self.d = eng.upload(x)
-        self.want = py_sums(x)
+        self.want = py_seals_and_locator(x)
         self.seal = self.t.seal(self.d, **self.kw)
         self.loc = self.t.seal_locator(self.d, **self.kw)
 
@@ -86,13 +73,7 @@ class Rows:
 
 @pytest.fixture(scope="module")
 def rows_of(F, eng):
-    made = {}
-
-    def get(logn):
-        if logn not in made:
-            made[logn] = Rows(F, eng, logn)
-        return made[logn]
-    return get
+    return case_cache(lambda logn: Rows(F, eng, logn))
 
 
 LOGNS = [5, 13, 14, 17]
@@ -344,57 +325,21 @@ def test_repair_argument_rules(F, eng, rows_of):
 
 
 # ---------------------------------------------------------------------------------------------------------------- composites
-class Case:
+class Case(SealedCase):
     """the 2^13 plan, seeded operands on the host and on the device, their seals and locators"""
 
     def __init__(self, F, eng):
-        self.logn, self.L, self.K, self.dnum = 13, 3, 1, 3
-        self.N, self.M = 1 << self.logn, self.L + self.K
-        self.qs, self.t, self.ks, self.ab, rng = checked_plan(F, eng, self.logn, self.L, self.K, self.dnum, "mixed", 14)
-        poly = lambda: np.stack([rng.integers(0, q, self.N, dtype=np.uint64) for q in self.qs[:self.L]])
-        self.ops = [poly() for _ in range(4)]
-        self.key = np.stack([np.stack([np.stack([rng.integers(0, q, self.N, dtype=np.uint64) for q in self.qs]) for _ in range(2)])
-                             for _ in range(self.dnum)])
-        self.d = [eng.upload(v) for v in self.ops]
-        self.dk = eng.upload(self.key)
-        self.seals = [self.t.seal(v, limbs=self.L) for v in self.d]
+        super().__init__(F, eng, (13, 3, 1, 3, limb_bits("mixed", 3, 1)), seed=14, margin=0)
         self.locs = [self.t.seal_locator(v, limbs=self.L) for v in self.d]
-        self.key_seal, self.key_loc = self.ks.seal_key(self.dk), self.ks.seal_key_locator(self.dk)
+        self.key_loc = self.ks.seal_key_locator(self.dk)
         for v, s, l in zip(self.ops + [self.key], self.seals + [self.key_seal], self.locs + [self.key_loc]):
-            want = py_sums(v)
+            want = py_seals_and_locator(v)
             assert s.download().tolist() == [w[:2] for w in want] and l.download().tolist() == [w[2] for w in want]
-
-    def intact(self):
-        return all((dv.download().reshape(-1) == v.reshape(-1)).all() for dv, v in zip(self.d + [self.dk], self.ops + [self.key]))
 
 
 @pytest.fixture(scope="module")
 def case(F, eng):
     return Case(F, eng)
-
-
-class plain_modulus:
-    def __init__(self, ks, t):
-        self.ks, self.t = ks, t
-
-    def __enter__(self):
-        self.ks.set_plain_modulus(self.t)
-
-    def __exit__(self, *exc):
-        self.ks.set_plain_modulus(0)
-
-
-def _raised(d, prefix=""):
-    """[(name, flat unit)] of every raised word of a (nested) flag dictionary"""
-    out = []
-    for name, f in d.items():
-        if f is None:
-            continue
-        if isinstance(f, dict):
-            out += _raised(f, prefix + name + ".")
-        else:
-            out += [(prefix + name, int(u)) for u in np.flatnonzero(np.asarray(f).reshape(-1))]
-    return out
 
 
 def _outcomes(reports):
@@ -410,11 +355,6 @@ def _words(*arrays):
     return [a.download().tolist() for a in arrays]
 
 
-def _safe_coeff(words, q, first):
-    """a coefficient from `first` on whose word stays below q whichever way bits 3 and 4 flip"""
-    return next(j for j in range(first, len(words)) if int(words[j]) < q - 64)
-
-
 @pytest.mark.parametrize("tp", [0, 65537])
 def test_repairing_composites_correct_a_flipped_word_and_give_the_clean_results(F, eng, case, tp):
     c = case
@@ -427,7 +367,7 @@ def test_repairing_composites_correct_a_flipped_word_and_give_the_clean_results(
         pairs = dict(seals=c.seals, locators=c.locs, key_seal=c.key_seal, key_locator=c.key_loc)
         hm_clean = ks.hmult_sealed(*c.d, c.dk, ab, seals=c.seals, key_seal=c.key_seal)
         rot_clean = ks.rotate_sealed(c.d[0], c.d[1], gal, c.dk, ab, seals=c.seals[:2], key_seal=c.key_seal)
-        assert _raised(hm_clean[3]) == [] and _raised(rot_clean[3]) == []
+        assert raised(hm_clean[3]) == [] and raised(rot_clean[3]) == []
         hm_want, rot_want = _words(hm_clean[0], hm_clean[1], *hm_clean[2]), _words(rot_clean[0], rot_clean[1], *rot_clean[2])
 
         def hmult_repair():
@@ -439,15 +379,15 @@ def test_repairing_composites_correct_a_flipped_word_and_give_the_clean_results(
         # a clean repairing call: the sealed call's words and seals, no flag, every report CLEAN, and the outputs' locators
         for got, want in ((hmult_repair(), hm_want), (rotate_repair(), rot_want)):
             o0, o1, so, lo, fl, rep = got
-            assert _words(o0, o1, *so) == want and _raised(fl) == [] and _outcomes(rep) == []
+            assert _words(o0, o1, *so) == want and raised(fl) == [] and _outcomes(rep) == []
             for o, l in zip((o0, o1), lo):
                 limbs = o.size // N
-                assert l.download().tolist() == [w[2] for w in py_sums(o.download().reshape(limbs, N))]
+                assert l.download().tolist() == [w[2] for w in py_seals_and_locator(o.download().reshape(limbs, N))]
                 assert l.download().tolist() == c.t.seal_locator(o, limbs=limbs).download().tolist()
         key_row = (1 * 2 + 1) * M + (M - 1)                      # digit 1, half 1, the special limb
         targets = [("a0", c.d[0], L - 1, c.ops[0][L - 1], c.qs[L - 1]), ("key", c.dk, key_row, c.key[1, 1, M - 1], c.qs[M - 1])]
         for what, dev, row, words, q in targets:
-            j = _safe_coeff(words, q, N // 2 + 7)
+            j = safe_coeff(words, q, N // 2 + 7, room=64)      # bits 3 and 4 flip
             rwhat = "c0" if what == "a0" else "key"
             record = [REPAIRED, j, int(words[j]) ^ 8, int(words[j])]
             for sealed, repairing, name, want in ((lambda: ks.hmult_sealed(*c.d, c.dk, ab, seals=c.seals, key_seal=c.key_seal), hmult_repair, what, hm_want),
@@ -456,14 +396,14 @@ def test_repairing_composites_correct_a_flipped_word_and_give_the_clean_results(
                 flip(eng, dev, row * N + j, 3)
                 # the verifying composite, unchanged: it raises the row and computes on what it was given
                 fl = sealed()[3]
-                assert _raised({k: v for k, v in fl.items() if k != "checked"}) == [(name, row)]
-                assert not c.intact()
+                assert raised({k: v for k, v in fl.items() if k != "checked"}) == [(name, row)]
+                assert not c.unchanged()
                 # the repairing composite: the clean call's words and output seals, no flag raised anywhere, the word named
                 o0, o1, so, lo, fl, rep = repairing()
-                assert _raised(fl) == [], (what, name, _raised(fl))
+                assert raised(fl) == [], (what, name, raised(fl))
                 assert _outcomes(rep) == [(name, row, record)], (what, name, _outcomes(rep))
                 assert _words(o0, o1, *so) == want, (what, name)
-                assert c.intact()
+                assert c.unchanged()
             # two words of that row: the row is raised, reported UNCORRECTABLE and left as it was found; the call goes on
             flip(eng, dev, row * N + j, 3)
             flip(eng, dev, row * N + j + 1, 4)
@@ -471,13 +411,13 @@ def test_repairing_composites_correct_a_flipped_word_and_give_the_clean_results(
                 before = dev.download().tobytes()
                 for repairing, name in ((hmult_repair, what), (rotate_repair, rwhat)):
                     fl, rep = repairing()[4:]
-                    assert _raised({k: v for k, v in fl.items() if k != "checked"}) == [(name, row)]
+                    assert raised({k: v for k, v in fl.items() if k != "checked"}) == [(name, row)]
                     assert _outcomes(rep) == [(name, row, [UNCORRECTABLE, 0, 0, 0])]
                     assert dev.download().tobytes() == before
             finally:
                 flip(eng, dev, row * N + j, 3)
                 flip(eng, dev, row * N + j + 1, 4)
-            assert c.intact()
+            assert c.unchanged()
     eng.check()
 
 
@@ -509,5 +449,5 @@ def test_repairing_composites_take_seal_and_locator_together(F, eng, case):
     assert both(None, None, None, None, fl.ptr) == [0, 0]
     none1 = (vp * 4)(c.seals[0].ptr, None, c.seals[2].ptr, c.seals[3].ptr)
     assert both(none1, half, c.key_seal.ptr, c.key_loc.ptr, fl.ptr) == [0, 0]
-    assert c.intact()
+    assert c.unchanged()
     eng.check()

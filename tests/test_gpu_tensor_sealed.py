@@ -10,12 +10,12 @@ import numpy as np
 import pytest
 
 from helpers.checked_plan import checked_plan
+from helpers.sealed_case import P, case_cache, flip, py_seals, raised
 
 pytestmark = pytest.mark.gpu
 
 INVALID, UNSUPPORTED = 1, 3
 SUM, RANGE = 1, 2
-P = (1 << 61) - 1
 GARBAGE = 0x5A5A5A5A5A5A5A5A
 GRID_CAP = 8192                 # TENSOR_SEAL_GRID_CAP of ntt_launch.hpp: workgroups of the job loop at most
 SHAPES = [(5, 2, "50"), (10, 3, "mixed"), (13, 2, "50"), (14, 2, "61")]
@@ -32,14 +32,6 @@ def F():
 @pytest.fixture(scope="module")
 def eng(F):
     return F.default_engine()
-
-
-def py_seals(x):
-    """[rows][2] Python integers of x = [..., N]"""
-    out = []
-    for row in np.asarray(x).reshape(-1, np.shape(x)[-1]).tolist():
-        out.append([sum(row) % P, sum((j + 1) * v for j, v in enumerate(row)) % P])
-    return out
 
 
 def py_tensor(ops, qs):
@@ -81,22 +73,7 @@ class Case:
 
 @pytest.fixture(scope="module")
 def cases(F, eng):
-    made = {}
-
-    def get(shape):
-        if shape not in made:
-            made[shape] = Case(F, eng, *shape)
-        return made[shape]
-    return get
-
-
-def raised(fl):
-    return [(name, int(u)) for name, f in fl.items() for u in np.flatnonzero(np.asarray(f).reshape(-1))]
-
-
-def flip(eng, d, idx, bit):
-    from fhe_reliability_gpu_amd._lib import check, lib
-    check(lib.fhe_flip_bit(eng._h, d.ptr, idx, bit, None))
+    return case_cache(lambda shape: Case(F, eng, *shape))
 
 
 def words(d):

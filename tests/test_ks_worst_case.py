@@ -3,18 +3,14 @@ exact integers, the magnitudes its families reach (derived from the families, as
 the families fed to the CPU emulation libraries, which compile the kernels' own element functions: words equal Python-integer
 results and no range window fires at the largest legal sums."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import cport as O
 from helpers import ks_worst_case as KW
+from helpers.emu_build import build_emu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-CSRC = os.path.join(ROOT, "fhe_reliability_gpu_amd", "csrc")
 p64 = C.POINTER(C.c_uint64)
 p32 = C.POINTER(C.c_uint32)
 U = np.uint64
@@ -26,11 +22,7 @@ SLOTS = 512
 
 
 def _emu(name, headers, protos):
-    so = os.path.join(EMU_DIR, f"lib{name}.so")
-    srcs = [os.path.join(EMU_DIR, f"{name}.cpp")] + [os.path.join(CSRC, h) for h in headers]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-I" + CSRC, srcs[0], "-o", so])
-    lib = C.CDLL(so)
+    lib = build_emu(f"lib{name}.so", [f"{name}.cpp"], headers)
     for fn, args in protos.items():
         getattr(lib, fn).restype = C.c_int
         getattr(lib, fn).argtypes = args
