@@ -206,6 +206,8 @@ _SIG = {
                                        C.POINTER(vp), C.POINTER(vp), vp, vp]),
     "fhe_ctx_inject_fault_galois_sealed": (ci, [vp, ci, ci, ci, C.c_longlong, ci]),
     "fhe_ntt_inverse_sealed": (ci, [vp, vp, vp, vp, vp, sz, sz, sz, vp, vp, vp]),
+    "fhe_ntt_forward_sealed": (ci, [vp, vp, vp, vp, vp, sz, sz, sz, vp, vp, vp, vp]),
+    "fhe_ntt_inverse_sealed_out": (ci, [vp, vp, vp, vp, vp, sz, sz, sz, vp, vp, vp, vp]),
     "fhe_ctx_inject_fault_ntt_sealed": (ci, [vp, ci, C.c_longlong, ci]),
     "fhe_keyswitch_sealed_in_layout": (ci, [vp, C.POINTER(ci)]),
     "fhe_keyswitch_apply_sealed_in": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),

@@ -228,6 +228,9 @@ int ks_mac_sealed_stage(const fhe_keyswitch *p, hipStream_t st, const KsMacArgs 
 // defined in capi_ntt_sealed.cpp
 // the sealed transform's hook as a call of `rows` rows took it (ctx->ntt_seal_fault), checked against that call
 int ntt_seal_hit(const SealHook &f, size_t rows, int log_n, SealedInputStep &in);
+// the sealed transform's record for the run of `len` limbs from limb `off` on, in a call of `limbs` limbs per polynomial whose input
+// partials are `tin` per row
+NttSealIn run_seal_in(const SealedInputStep &in, size_t off, size_t len, size_t limbs, u32 tin);
 
 // defined in capi_bgv_checked.cpp
 // one scalar stage: `limbs` rows from data on, of n_poly polynomials poly_stride rows apart (row l of polynomial i at data + (i

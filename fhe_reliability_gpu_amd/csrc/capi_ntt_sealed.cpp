@@ -27,7 +27,7 @@ int ntt_seal_hit(const SealHook &f, size_t rows, int log_n, SealedInputStep &in)
 
 // the sealed transform's record for the run of `len` limbs from limb `off` on, in a call whose row (poly, l) is row poly * limbs + l
 // of the seal, the flags and the partials: all three and the hook's row are addressed from the run's first limb on
-static NttSealIn run_seal_in(const SealedInputStep &in, size_t off, size_t len, size_t limbs, u32 tin)
+NttSealIn run_seal_in(const SealedInputStep &in, size_t off, size_t len, size_t limbs, u32 tin)
 {
     NttSealIn s{in.seal ? in.seal + 2 * off : nullptr, in.flags + off, in.part + off * tin * 3};
     const size_t hl = in.hit_row % (limbs ? limbs : 1);

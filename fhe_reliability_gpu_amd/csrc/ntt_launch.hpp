@@ -487,6 +487,28 @@ size_t ntt_seal_part_words(u32 rows, int logn);
 hipError_t launch_ntt_sealed_inv(hipStream_t st, const PassArgs &a, const Tw *win, const Tw *wout, const u64 *wout8, u64 *sum_in, u64 *sum_out, int logn, int path,
                                  int which, const NttSealIn &s);
 
+// k_ntt_seal_finish over the rows of launch `a`, whose first launch left `tiles` partials per row at s.part
+hipError_t launch_ntt_seal_finish(hipStream_t st, const PassArgs &a, u32 tiles, const NttSealIn &s);
+
+// ---- ntt_fwd_sealed.hip: the checked forward transform with its input's seal verified on load and its output sealed on store, and
+// the sealed inverse with an output seal (ntt_seal_tap.hpp) ----
+// words of the output digest's partials, [rows][tiles of the storing launch][2]; the input side's: ntt_seal_part_words (inverse) /
+// ntt_seal_fwd_part_words (forward).  The two regions are distinct: the single pass writes both in one launch
+size_t ntt_seal_fwd_part_words(u32 rows, int logn);
+size_t ntt_seal_out_part_words(u32 rows, int logn, bool inverse);
+// launch_ntt_checked(inverse = false) with the first launch (the column pass; below 2^13 the single pass) sealed as NttSealIn
+// describes, and the storing launch (the row pass; the single pass) digesting every word it stores into part_out, addressed as
+// s.part is.  part_out == nullptr: no output digest (two-launch sizes: the second launch is launch_ntt_checked's own).  `which`,
+// a.src and the scope as launch_ntt_sealed_inv
+hipError_t launch_ntt_sealed_fwd(hipStream_t st, const PassArgs &a, const Tw *win, const Tw *wout, const u64 *wout8, u64 *sum_in, u64 *sum_out, int logn, int path,
+                                 int which, const NttSealIn &s, u64 *part_out);
+// launch_ntt_sealed_inv whose storing launch (the inverse column pass; the single pass) digests every word it stores into part_out
+hipError_t launch_ntt_sealed_inv_out(hipStream_t st, const PassArgs &a, const Tw *win, const Tw *wout, const u64 *wout8, u64 *sum_in, u64 *sum_out, int logn,
+                                     int path, int which, const NttSealIn &s, u64 *part_out);
+// one lane per row: seal_dst[row] = the row's merged output digest, canonical, where flags_in[row] and flags_abft[row] are both
+// zero, {~0, ~0} otherwise (ntt_seal_out).  Runs after the verdicts and launch_compare_sums on the same stream
+hipError_t launch_ntt_seal_out_finish(hipStream_t st, const u64 *part_out, u32 tiles, u32 rows, const u32 *flags_in, const u32 *flags_abft, u64 *seal_dst);
+
 // ---- subscale_sealed.hip: the mod-down tail with its first operand verified on load and its result sealed on store (subscale_seal.hpp) ----
 // what the sealed tail needs beside launch_sub_scale_checked's arguments.  Rows are (half h, limb l) of the launch.  seal_out0 /
 // seal_out1 = [limbs][2] receive the seal of out0 / out1 from the registers that are stored (either may be null: that half is not

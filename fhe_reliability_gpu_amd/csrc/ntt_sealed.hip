@@ -122,6 +122,14 @@ __global__ __launch_bounds__(256) void k_ntt_seal_finish(const u64 *part, u32 ti
     }
 }
 
+hipError_t launch_ntt_seal_finish(hipStream_t st, const PassArgs &a, u32 tiles, const NttSealIn &s)
+{
+    const u32 fgrid = (a.units + 255) / 256;
+    hipLaunchKernelGGL(k_ntt_seal_finish, dim3(fgrid < 1024 ? fgrid : 1024), dim3(256), 0, st, (const u64 *)s.part, tiles, a.units, a.limbs, a.poly_stride, s.seal_src,
+                       s.flags);
+    return hipGetLastError();
+}
+
 namespace {
 
 template <class PASS, int LOGN, bool OUT>
@@ -132,10 +140,7 @@ hipError_t launch_first(hipStream_t st, const PassArgs &a, const SealPassArgs &s
     else hipLaunchKernelGGL((k_ntt_pass_sealed<PASS, LOGN, false, OUT>), grid, th, 0, st, a, sp);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    const u32 fgrid = (a.units + 255) / 256;
-    hipLaunchKernelGGL(k_ntt_seal_finish, dim3(fgrid < 1024 ? fgrid : 1024), dim3(256), 0, st, (const u64 *)s.part, (u32)PASS::TILES, a.units, a.limbs, a.poly_stride,
-                       s.seal_src, s.flags);
-    return hipGetLastError();
+    return launch_ntt_seal_finish(st, a, (u32)PASS::TILES, s);
 }
 
 template <class A, int LOGN>

@@ -79,8 +79,9 @@ class Engine:
         check(lib.fhe_ctx_inject_fault_galois_sealed(self._h, rot, point, row, coeff, bit))
 
     def inject_fault_ntt_sealed(self, row: int, coeff: int = 0, bit: int = 0):
-        """One-shot test hook of ``NttTables.intt_sealed`` / ``KeySwitch.apply_sealed_in`` / ``rotate_sealed_in``: flip ``bit`` of
-        word ``coeff`` of row ``row`` of the sealed inverse transform's input (a row of the source, of ``c``, of sigma(c1)) in the
+        """One-shot test hook of ``NttTables.intt_sealed`` / ``ntt_sealed`` / ``intt_sealed_out`` / ``KeySwitch.apply_sealed_in`` /
+        ``rotate_sealed_in``: flip ``bit`` of
+        word ``coeff`` of row ``row`` of the sealed transform's input (a row of the source, of ``c``, of sigma(c1)) in the
         register as the next such call's first launch loads it, before the window, the digest and the conversion read it; memory
         stays clean.  A negative ``row`` disarms."""
         check(lib.fhe_ctx_inject_fault_ntt_sealed(self._h, row, coeff, bit))
@@ -315,6 +316,38 @@ class NttTables:
         f = _checked_flags(self.eng, 2 * rows, lambda fl: lib.fhe_ntt_inverse_sealed(
             self.eng._h, dst.ptr, src.ptr, self._h, abft._h, n_poly, limbs, start, seal.ptr if seal is not None else None, fl.ptr, stream), stream)
         return dst, f.reshape(2, rows)
+
+    def _sealed_io(self, call, src, seal, abft, dst, seal_out, limbs, start, n_poly, stream):
+        limbs = len(self) - start if limbs is None else limbs
+        rows = n_poly * limbs
+        if dst is None:
+            dst = self.eng.alloc(src.size)
+            dst.shape = src.shape
+        seal_dst = None
+        if seal_out:
+            seal_dst = self.eng.alloc(rows * 2)
+            seal_dst.shape = (rows, 2)
+        f = _checked_flags(self.eng, 2 * rows, lambda fl: call(
+            self.eng._h, dst.ptr, src.ptr, self._h, abft._h, n_poly, limbs, start, seal.ptr if seal is not None else None,
+            seal_dst.ptr if seal_dst is not None else None, fl.ptr, stream), stream)
+        return dst, seal_dst, f.reshape(2, rows)
+
+    def ntt_sealed(self, src: DeviceArray, seal: Optional[DeviceArray], abft: "Abft", dst: Optional[DeviceArray] = None, seal_out: bool = True, limbs=None,
+                   start=0, n_poly=1, stream=None):
+        """The forward NTT of the rows of ``src`` with their seal verified on the transform's own load and the seal of the result
+        written from the words the transform stores: ``(dst, seal_dst, flags)``.  ``flags`` uint32 ``[2][rows]`` -- block 0 the input
+        seal verdict per row with ``seal_verify``'s bits, block 1 ``Abft.forward_checked``'s flag.  ``seal_dst`` is ``[rows][2]``,
+        ``seal``'s of ``dst`` word for word on a row with no raised flag and ``{~0, ~0}`` otherwise: a raised row leaves the call with
+        a seal that can never verify.  ``seal_out`` False: no output digest, ``seal_dst`` is None.  ``dst`` None: a new array (out
+        of place, no copy; ``src`` is only read); ``dst`` may be ``src`` (in place).  ``seal`` None: not compared, the window still
+        is.  The words are ``forward``'s, bit for bit; a raised flag does not stop the call.  Whole-batch launches only."""
+        return self._sealed_io(lib.fhe_ntt_forward_sealed, src, seal, abft, dst, seal_out, limbs, start, n_poly, stream)
+
+    def intt_sealed_out(self, src: DeviceArray, seal: Optional[DeviceArray], abft: "Abft", dst: Optional[DeviceArray] = None, seal_out: bool = True, limbs=None,
+                        start=0, n_poly=1, stream=None):
+        """``intt_sealed`` that also writes the seal of its result from the words it stores: ``(dst, seal_dst, flags)`` as
+        ``ntt_sealed``, over ``inverse``'s words and ``Abft.inverse_checked``'s flag."""
+        return self._sealed_io(lib.fhe_ntt_inverse_sealed_out, src, seal, abft, dst, seal_out, limbs, start, n_poly, stream)
 
     def seal_locator(self, d: DeviceArray, limbs=None, start=0, n_poly=1, stream=None) -> DeviceArray:
         """The locator sums of the rows of ``d``: a device array ``[n_poly * limbs]`` of S2 = sum (j + 1)^2 x_j modulo 2^61 - 1,

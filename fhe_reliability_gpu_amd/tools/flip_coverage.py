@@ -35,7 +35,14 @@ and runs hmult_sealed_fused_key: no input is swept at all, and the flipped key w
 itself, on the load that multiplies it.  The fault-free words and flags are held against hmult_sealed's first.  Per trial the tool
 prints which key rows were raised.  Exit status as in the default mode.
 
-python -m fhe_reliability_gpu_amd.tools.flip_coverage [--repair | --rotate-sum | --bsgs | --fused | --fused-key] [--trials 32] [--num-symbols 1] [--bits-per-symbol 1] [--logn 14] [--row 8] [--seed 1]"""
+--ntt runs the reference's other experiment, reliability_test/ntt_test.cu:104-144, with a verdict: a batch of ``--batch`` random rows
+(one 50-bit prime each, as ``ntt_test <log_dim> <batch_size>``) is sealed, each trial places its flips in the source of the forward
+transform at rest, and ntt_sealed must raise exactly the flipped rows in its input block, raise nothing in its ABFT block, and leave
+exactly those rows with a poisoned output seal, which a seal_verify sweep of the result then refuses.  Per trial the tool prints
+the reference's damage count (output words that differ, the symbol error rate) next to the rows raised.  The control trial must
+raise nothing and produce seals equal to seal(dst).  Exit status 1 when a trial's raised rows are not its flipped rows.
+
+python -m fhe_reliability_gpu_amd.tools.flip_coverage [--repair | --rotate-sum | --bsgs | --fused | --fused-key | --ntt [--batch 4]] [--trials 32] [--num-symbols 1] [--bits-per-symbol 1] [--logn 14] [--row 8] [--seed 1]"""
 import argparse
 import sys
 
@@ -72,7 +79,11 @@ def main():
     ap.add_argument("--bsgs", action="store_true", help="flip a diagonal or a giant key of a sealed BSGS matrix-vector product")
     ap.add_argument("--fused", action="store_true", help="run the multiply as hmult_sealed_fused: operands verified on the multiplying load")
     ap.add_argument("--fused-key", action="store_true", help="flip the relinearisation key at rest and run hmult_sealed_fused_key")
+    ap.add_argument("--ntt", action="store_true", help="flip the source of the forward transform at rest and run ntt_sealed (ntt_test.cu:104-144)")
+    ap.add_argument("--batch", type=int, default=4, help="--ntt: rows of the batch, one 50-bit prime each")
     a = ap.parse_args()
+    if a.ntt and (a.repair or a.bsgs or a.rotate_sum or a.fused or a.fused_key):
+        ap.error("--ntt is a mode of its own")
     if a.fused_key and (a.repair or a.bsgs or a.rotate_sum or a.fused):
         ap.error("--fused-key is a mode of its own")
     if a.fused and (a.repair or a.bsgs):
@@ -84,6 +95,8 @@ def main():
     if a.row < 1 or a.row & (a.row - 1) or not 1 <= a.bits_per_symbol <= 64 or a.num_symbols < 0:
         ap.error("row is a power of two, bits-per-symbol 1..64, num-symbols >= 0")
     eng = F.Engine(0)
+    if a.ntt:
+        return main_ntt(a, eng)
     if a.bsgs:
         return main_bsgs(a, eng)
     if a.fused_key:
@@ -289,6 +302,49 @@ def main_fused_key(a, eng):
     eng.check()
     print(f"summary: {a.trials} trials, {missed} with a flip and no flag")
     return 1 if missed else 0
+
+
+def main_ntt(a, eng):
+    """the trials of --ntt: the reference's flips in the forward transform's input at rest, through ntt_sealed"""
+    N, B = 1 << a.logn, a.batch
+    qs = F.create_moduli(N, [50] * B)
+    rng = np.random.default_rng(a.seed)
+    t = eng.tables(a.logn, qs)
+    ab = F.Abft(eng, t)
+    x = np.stack([rng.integers(0, q, N, dtype=np.uint64) for q in qs])
+    d_x = eng.upload(x)
+    seal = t.seal(d_x, limbs=B)
+    ref = eng.upload(x)
+    t.forward(ref, limbs=B)
+    clean = ref.download().reshape(B, N)
+    poison = np.uint64((1 << 64) - 1)
+    print(f"N = 2^{a.logn}, batch {B} (50-bit primes): ntt_sealed, flips in the transform's input at rest; {a.num_symbols} symbols x {a.bits_per_symbol} bits per trial")
+    wrong = 0
+    for trial in range(a.trials):
+        d = eng.upload(x)
+        n_sym = 0 if trial == 0 else a.num_symbols
+        hit = set()
+        for idx in rng.choice(x.size, n_sym, replace=False):
+            hit.add(int(idx) // N)
+            for bit in rng.choice(64, a.bits_per_symbol, replace=False):
+                check(lib.fhe_flip_bit(eng._h, d.ptr, int(idx), int(bit), None))
+        dst, seal_dst, fl = t.ntt_sealed(d, seal, ab, limbs=B)
+        out = dst.download().reshape(B, N)
+        corrupted = int(np.count_nonzero(out != clean))
+        rows = np.flatnonzero(fl[0]).tolist()
+        s_dst, s_ref = seal_dst.download().reshape(B, 2), t.seal(dst, limbs=B).download().reshape(B, 2)
+        poisoned = [r for r in range(B) if (s_dst[r] == poison).all()]
+        sealed = all((s_dst[r] == s_ref[r]).all() for r in range(B) if r not in poisoned)
+        refused = np.flatnonzero(t.seal_verify(dst, seal_dst, limbs=B)).tolist()
+        ok = rows == sorted(hit) and not fl[1].any() and poisoned == rows and refused == rows and sealed
+        wrong += not ok
+        assert n_sym > 0 or (ok and corrupted == 0), "the control trial raised a flag, or its seals are not seal(dst)"
+        print(f"trial {trial:3d}: flipped rows {sorted(hit)}, corrupted output words {corrupted:7d} of {out.size} (symbol error rate {corrupted / out.size:.3f}), "
+              f"input rows raised {rows}, ABFT words raised {int(np.count_nonzero(fl[1]))}, output seals poisoned {poisoned}, refused by seal_verify {refused}: "
+              f"{'ok' if ok else 'WRONG'}", flush=True)
+    eng.check()
+    print(f"summary: {a.trials} trials (one control), {wrong} whose raised rows, poisoned seals or refused rows are not exactly the flipped rows")
+    return 1 if wrong else 0
 
 
 def main_bsgs(a, eng):

@@ -1271,6 +1271,43 @@ int fhe_rotate_sealed_in(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint6
                          uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, const uint64_t *const *d_seal_in,
                          const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream);
 
+/* ---- sealed forward NTT: input verified on load, output sealed on store; the sealed inverse with an output seal --------------
+ * fhe_ntt_forward_checked forms its input-side ABFT sum from the word as loaded, so a word corrupted at rest -- the experiment of
+ * reliability_test/ntt_test.cu:104-144 -- is a consistent input: no flag, every output word wrong.  The composition fhe_seal_verify
+ * + fhe_ntt_forward_checked + fhe_seal verifies on one load, transforms from another and seals the output by re-reading it after
+ * the store.  Here the launch that loads the transform's input (the forward column pass; below 2^13 the single pass) digests every
+ * raw 64-bit word its first register step takes, as fhe_ntt_inverse_sealed does, and the launch that stores the result digests
+ * every final word on its way to memory with weight = its index in the stored row plus one: the seal of fhe_seal over the output
+ * row, word for word.  A change of domain keeps its chain of custody.
+ *
+ * fhe_ntt_forward_sealed: d_dst = the words of fhe_ntt_forward_batch over d_src's rows [n_poly][limbs] of table limbs start_idx ..,
+ * bit for bit -- also for a source word >= q_l, which is digested as it is, raises bit 2 and is reduced as the unchecked transform
+ * reduces it.  d_dst == d_src runs in place, otherwise out of place with no copy and d_src is only read.  d_seal_src ([rows][2],
+ * fhe_seal's; NULL: not compared, the window still is).  d_seal_dst ([rows][2]; NULL: nothing is written and no output digest is
+ * launched).  d_flags [2][rows], cleared by the call: block 0 the input seal verdict per row with fhe_seal_verify's bits, block 1
+ * fhe_ntt_forward_checked's flag.  A raised flag does not stop the call.
+ * fhe_ntt_inverse_sealed_out: the same arguments and rules over fhe_ntt_inverse_batch's words and fhe_ntt_inverse_checked's flag;
+ * with d_seal_dst == NULL it is fhe_ntt_inverse_sealed.
+ *
+ * The poison rule: d_seal_dst[row] is the canonical digest of the stored row where the row's word in block 0 and its word in block
+ * 1 are both zero, and {~0, ~0} otherwise.  A stored sum that is not canonical differs from every digest in every verifier, so a
+ * row with any raised flag leaves the call with a seal that can never verify: it stays raised in every later verification and
+ * fhe_seal_repair reports it FHE_SEAL_UNCORRECTABLE.
+ *
+ * Scope and refusals are fhe_ntt_inverse_sealed's: N >= 2^5, not with ntt_mode=1, ntt_resident, ntt_packed or a single-pass hook
+ * (FHE_ERR_UNSUPPORTED with nothing launched and the flag buffer untouched); whole-batch launches only.  Both calls take
+ * fhe_ctx_inject_fault's flip between the two launches at N >= 2^13, as the checked transforms do, and
+ * fhe_ctx_inject_fault_ntt_sealed, one shot and whatever the outcome: the bit of that input word is flipped in the register as
+ * loaded, memory stays clean; a row or word outside the call gives FHE_ERR_INVALID with nothing launched.
+ *
+ * Not covered: a fault between the tap's read of a register and the conversion that consumes it; the hand-off between the two
+ * launches beyond what the whole-transform ABFT sum sees; sub-batched streaming batches; the forward transforms inside the key
+ * switch (stages 2 and 6), which stay the checked ones; fhe_polymul; repair; sharded plans. */
+int fhe_ntt_forward_sealed(fhe_ctx *ctx, uint64_t *d_dst, const uint64_t *d_src, const fhe_ntt_tables *t, const fhe_abft *a, size_t n_poly,
+                           size_t limbs, size_t start_idx, const uint64_t *d_seal_src, uint64_t *d_seal_dst, uint32_t *d_flags, void *stream);
+int fhe_ntt_inverse_sealed_out(fhe_ctx *ctx, uint64_t *d_dst, const uint64_t *d_src, const fhe_ntt_tables *t, const fhe_abft *a, size_t n_poly,
+                               size_t limbs, size_t start_idx, const uint64_t *d_seal_src, uint64_t *d_seal_dst, uint32_t *d_flags, void *stream);
+
 /* ---- sealed rescale and sealed tail: inputs verified on load, outputs sealed on store ------------------------------------------
  * fhe_rescale_checked and fhe_bgv_mod_switch_checked do not cover faults already in their input, and every sealed composite seals
  * its outputs with a sweep after its last launch: a word corrupted between the final store and that sweep's load is sealed as it
