@@ -40,7 +40,7 @@ inline size_t ksc_slots(const fhe_keyswitch *p)
 struct SealedInputStep {
     const uint64_t *seal;          // DEVICE [L][2] the stored seals of d_c's rows, or null: not compared (the window still is)
     uint32_t *flags;               // the rows' flags, [L]: every word is written by stage 0
-    u64 *part;                     // at least ntt_seal_part_words(L, log_n) words, not shared with a launch that runs before stage 0 ends
+    u64 *part;                     // at least ntt_seal_part_words(L, log_n, true) words, not shared with a launch that runs before stage 0 ends
     u32 hit_row, hit_coeff;        // the sealed transform's hook, checked against the call (ntt_seal_hit); hit_mask == 0: not armed
     u64 hit_mask;
 };
@@ -147,7 +147,7 @@ struct SealedTailStep {
     // stage 3's, the last limbs on stage 0's, which is then the sealed inverse transform out of place from the caller's rows
     const uint64_t *seal_in = nullptr;      // DEVICE [n_parts][L][2]
     uint32_t *flags_in = nullptr;           // [n_parts][L], zeroed by the caller
-    u64 *part_ntt = nullptr;                // at least n_parts * ntt_seal_part_words(1, log_n) words, apart from `part`
+    u64 *part_ntt = nullptr;                // at least n_parts * ntt_seal_part_words(1, log_n, true) words, apart from `part`
     int ntt_hit_part = -1;                  // the sealed transform's hook, checked against the call: the part whose last limb it hits
     u32 ntt_hit_coeff = 0;
     u64 ntt_hit_mask = 0;
@@ -225,7 +225,7 @@ int ks_seal_hit(const SealHook &f, const fhe_keyswitch *p, KsSealHit &hit);
 // launch_ks_mac_checked; k = the residue check record of stage 3, its flags [2][M]
 int ks_mac_sealed_stage(const fhe_keyswitch *p, hipStream_t st, const KsMacArgs &ka, const BcCheck &k, const SealedKeyStep &key);
 
-// defined in capi_ntt_sealed.cpp
+// defined in capi_ntt_fwd_sealed.cpp
 // the sealed transform's hook as a call of `rows` rows took it (ctx->ntt_seal_fault), checked against that call
 int ntt_seal_hit(const SealHook &f, size_t rows, int log_n, SealedInputStep &in);
 // the sealed transform's record for the run of `len` limbs from limb `off` on, in a call of `limbs` limbs per polynomial whose input

@@ -88,7 +88,7 @@ int rescale_checked(fhe_keyswitch *p, KsForm form, uint64_t *const *outs, const 
     if (tail && tail->flags_in) {
         for (size_t part = 0; part < n_parts; part++) {
             const size_t row = part * L + R;
-            SealedInputStep in{tail->seal_in ? tail->seal_in + 2 * row : nullptr, tail->flags_in + row, tail->part_ntt + part * ntt_seal_part_words(1, logn), 0, 0, 0};
+            SealedInputStep in{tail->seal_in ? tail->seal_in + 2 * row : nullptr, tail->flags_in + row, tail->part_ntt + part * ntt_seal_part_words(1, logn, true), 0, 0, 0};
             if (tail->ntt_hit_part == (int)part) in.hit_coeff = tail->ntt_hit_coeff, in.hit_mask = tail->ntt_hit_mask;
             const bool mine = ft.stage == 0 && (size_t)ft.unit == part;
             if ((rc = inv.run_sealed(KscRows{x + part * N, 0, (u32)R, 1, 1, 1, (u32)part}, d_in + row * N, in, mine ? flip : nullptr, ft.bit))) return rc;

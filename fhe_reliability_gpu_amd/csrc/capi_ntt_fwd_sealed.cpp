@@ -1,13 +1,39 @@
-// capi_ntt_fwd_sealed.cpp -- the transforms that verify their input's seal on their own load and write their output's seal from the
-// words they store (ntt_seal_tap.hpp, ntt_fwd_sealed.hip, ntt_inv_sealed_out.hip): fhe_ntt_forward_sealed and
-// fhe_ntt_inverse_sealed_out (part of the C ABI of include/fhe_mi355x.h).
+// capi_ntt_fwd_sealed.cpp -- the transforms that verify their input's seal on their own load and, where asked, write their
+// output's seal from the words they store (ntt_seal_tap.hpp, ntt_sealed_io.hpp): fhe_ntt_inverse_sealed, fhe_ntt_forward_sealed,
+// fhe_ntt_inverse_sealed_out and their test hook (part of the C ABI of include/fhe_mi355x.h), and what the sealed key switch
+// (capi_ntt_sealed.cpp) shares with them: the hook's check against a call and the launch record of a run of limbs.
 //
-// One body for both directions, in fhe_ntt_inverse_sealed's structure (capi_ntt_sealed.cpp): the hooks are taken first, refusals
-// come before anything is launched, the flag buffer is cleared, the launches run per run of an arithmetic path, and the ABFT
-// comparison closes block 1.  What is added: the output digest's partials live behind the input digest's in the context's seal
-// scratch, and k_ntt_seal_out_finish writes each row's seal after both flag blocks are final -- the poison rule: a row with any
-// raised flag leaves the call with a seal that can never verify.
+// One body for all three calls: the hooks are taken first, refusals come before anything is launched, the flag buffer is cleared,
+// the launches run per run of an arithmetic path, and the ABFT comparison closes block 1.  With an output seal the output digest's
+// partials live behind the input digest's in the context's seal scratch, and k_ntt_seal_out_finish writes each row's seal after
+// both flag blocks are final -- the poison rule: a row with any raised flag leaves the call with a seal that can never verify.
 #include "capi_sealed.hpp"
+
+int ntt_seal_hit(const SealHook &f, size_t rows, int log_n, SealedInputStep &in)
+{
+    in.hit_row = in.hit_coeff = 0;
+    in.hit_mask = 0;
+    if (f.sel < 0) return FHE_OK;
+    if (!f.inside(rows, log_n)) return fail(FHE_ERR_INVALID, "fault row or word outside the call");
+    in.hit_row = (u32)f.row;
+    in.hit_coeff = (u32)f.coeff;
+    in.hit_mask = (u64)1 << f.bit;
+    return FHE_OK;
+}
+
+// the sealed transform's record for the run of `len` limbs from limb `off` on, in a call whose row (poly, l) is row poly * limbs + l
+// of the seal, the flags and the partials: all three and the hook's row are addressed from the run's first limb on
+NttSealIn run_seal_in(const SealedInputStep &in, size_t off, size_t len, size_t limbs, u32 tin)
+{
+    NttSealIn s{in.seal ? in.seal + 2 * off : nullptr, in.flags + off, in.part + off * tin * 3};
+    const size_t hl = in.hit_row % (limbs ? limbs : 1);
+    if (in.hit_mask && hl >= off && hl < off + len) {
+        s.hit_row = in.hit_row - (u32)off;
+        s.hit_coeff = in.hit_coeff;
+        s.hit_mask = in.hit_mask;
+    }
+    return s;
+}
 
 static int sealed_transform(bool inverse, fhe_ctx *ctx, uint64_t *d_dst, const uint64_t *d_src, const fhe_ntt_tables *t, const fhe_abft *a, size_t n_poly,
                             size_t limbs, size_t start_idx, const uint64_t *d_seal_src, uint64_t *d_seal_dst, uint32_t *d_flags, void *stream)
@@ -43,7 +69,7 @@ static int sealed_transform(bool inverse, fhe_ctx *ctx, uint64_t *d_dst, const u
         HIP_TRY(m->sum_out.alloc(units * 16 * tout));
     }
     // [the input digest's partials][the output digest's partials]: distinct regions, the single pass writes both in one launch
-    const size_t in_words = inverse ? ntt_seal_part_words((u32)units, t->log_n) : ntt_seal_fwd_part_words((u32)units, t->log_n);
+    const size_t in_words = ntt_seal_part_words((u32)units, t->log_n, inverse);
     const size_t out_words = d_seal_dst ? ntt_seal_out_part_words((u32)units, t->log_n, inverse) : 0;
     if ((rc = seal_scratch(ctx, st, in_words + out_words, &in.part))) return rc;
     u64 *part_out = d_seal_dst ? in.part + in_words : nullptr;
@@ -56,9 +82,8 @@ static int sealed_transform(bool inverse, fhe_ctx *ctx, uint64_t *d_dst, const u
             const NttSealIn s = run_seal_in(in, off, len, limbs, tin);
             u64 *po = part_out ? part_out + off * tout * 2 : nullptr;
             u64 *si = m->sum_in.as<u64>() + off * tin, *so = m->sum_out.as<u64>() + off * tout;
-            hipError_t e = inverse ? launch_ntt_sealed_inv_out(st, pa, a->win.as<Tw>(), a->wout.as<Tw>(), a->wout8.as<u64>(), si, so, t->log_n, path, which, s, po)
-                                   : launch_ntt_sealed_fwd(st, pa, a->win.as<Tw>(), a->wout.as<Tw>(), a->wout8.as<u64>(), si, so, t->log_n, path, which, s, po);
-            return e == hipSuccess ? FHE_OK : hip_fail(e, inverse ? "launch_ntt_sealed_inv_out" : "launch_ntt_sealed_fwd");
+            hipError_t e = launch_ntt_sealed(st, pa, a->win.as<Tw>(), a->wout.as<Tw>(), a->wout8.as<u64>(), si, so, t->log_n, path, which, inverse, s, po);
+            return e == hipSuccess ? FHE_OK : hip_fail(e, "launch_ntt_sealed");
         });
     };
     if (between) {
@@ -76,6 +101,18 @@ static int sealed_transform(bool inverse, fhe_ctx *ctx, uint64_t *d_dst, const u
 }
 
 extern "C" {
+
+int fhe_ctx_inject_fault_ntt_sealed(fhe_ctx *ctx, int row, long long coeff, int bit)
+{
+    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
+    return ctx->ntt_seal_fault.arm(INT_MAX, row, 0, row, coeff, bit) ? FHE_OK : fail(FHE_ERR_INVALID, "bad fault");
+}
+
+int fhe_ntt_inverse_sealed(fhe_ctx *ctx, uint64_t *d_dst, const uint64_t *d_src, const fhe_ntt_tables *t, const fhe_abft *a, size_t n_poly, size_t limbs,
+                           size_t start_idx, const uint64_t *d_seal_src, uint32_t *d_flags, void *stream)
+{
+    return sealed_transform(true, ctx, d_dst, d_src, t, a, n_poly, limbs, start_idx, d_seal_src, nullptr, d_flags, stream);
+}
 
 int fhe_ntt_forward_sealed(fhe_ctx *ctx, uint64_t *d_dst, const uint64_t *d_src, const fhe_ntt_tables *t, const fhe_abft *a, size_t n_poly, size_t limbs,
                            size_t start_idx, const uint64_t *d_seal_src, uint64_t *d_seal_dst, uint32_t *d_flags, void *stream)

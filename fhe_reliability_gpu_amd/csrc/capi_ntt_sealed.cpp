@@ -1,7 +1,6 @@
-// capi_ntt_sealed.cpp -- the inverse transform that verifies its input's seal on its own load (ntt_seal_tap.hpp, ntt_sealed.hip):
-// fhe_ntt_inverse_sealed and its test hook, and the key switch and rotation whose input limbs are verified on the opening
-// transform's load -- fhe_keyswitch_apply_sealed_in, fhe_rotate_sealed_in and their layouts (part of the C ABI of
-// include/fhe_mi355x.h).
+// capi_ntt_sealed.cpp -- the key switch and rotation whose input limbs are verified on the opening transform's own load
+// (ntt_seal_tap.hpp, ntt_sealed.hip; the transforms themselves: capi_ntt_fwd_sealed.cpp) -- fhe_keyswitch_apply_sealed_in,
+// fhe_rotate_sealed_in, fhe_rotate_sealed_out and their layouts (part of the C ABI of include/fhe_mi355x.h).
 //
 // fhe_keyswitch_apply_sealed does not seal d_c, and the sealed rotations sweep c0 and c1 and then move them through the unchecked
 // permutation: the verifying sweep, the copy into the plan and the opening transform's load are separate loads, and a word that is
@@ -13,32 +12,6 @@
 #include "capi_sealed.hpp"
 #include "galois_seal.hpp"
 
-int ntt_seal_hit(const SealHook &f, size_t rows, int log_n, SealedInputStep &in)
-{
-    in.hit_row = in.hit_coeff = 0;
-    in.hit_mask = 0;
-    if (f.sel < 0) return FHE_OK;
-    if (!f.inside(rows, log_n)) return fail(FHE_ERR_INVALID, "fault row or word outside the call");
-    in.hit_row = (u32)f.row;
-    in.hit_coeff = (u32)f.coeff;
-    in.hit_mask = (u64)1 << f.bit;
-    return FHE_OK;
-}
-
-// the sealed transform's record for the run of `len` limbs from limb `off` on, in a call whose row (poly, l) is row poly * limbs + l
-// of the seal, the flags and the partials: all three and the hook's row are addressed from the run's first limb on
-NttSealIn run_seal_in(const SealedInputStep &in, size_t off, size_t len, size_t limbs, u32 tin)
-{
-    NttSealIn s{in.seal ? in.seal + 2 * off : nullptr, in.flags + off, in.part + off * tin * 3};
-    const size_t hl = in.hit_row % (limbs ? limbs : 1);
-    if (in.hit_mask && hl >= off && hl < off + len) {
-        s.hit_row = in.hit_row - (u32)off;
-        s.hit_coeff = in.hit_coeff;
-        s.hit_mask = in.hit_mask;
-    }
-    return s;
-}
-
 // one launch per run of an arithmetic path
 int KscNtt::launch_sealed(const KscRows &r, const u64 *src, const SealedInputStep &in, int which) const
 {
@@ -49,75 +22,13 @@ int KscNtt::launch_sealed(const KscRows &r, const u64 *src, const SealedInputSte
         pa.src = src + (r.row0 + off) * N;
         const size_t slot = (size_t)r.sum0 + r.row0 + off;
         if (r.n_poly != 1 || slot + len > ksc_slots(p)) return fail(FHE_ERR_INVALID, "checked call: a transform's sums lie outside the plan's scratch");
-        hipError_t e = launch_ntt_sealed_inv(st, pa, a->win.as<Tw>(), a->wout.as<Tw>(), a->wout8.as<u64>(), sum_in() + slot * tin, sum_out() + slot * tout, p->log_n,
-                                             path, which, run_seal_in(in, off, len, r.count, tin));
-        return e == hipSuccess ? FHE_OK : hip_fail(e, "launch_ntt_sealed_inv");
+        hipError_t e = launch_ntt_sealed(st, pa, a->win.as<Tw>(), a->wout.as<Tw>(), a->wout8.as<u64>(), sum_in() + slot * tin, sum_out() + slot * tout, p->log_n, path,
+                                         which, true, run_seal_in(in, off, len, r.count, tin), nullptr);
+        return e == hipSuccess ? FHE_OK : hip_fail(e, "launch_ntt_sealed");
     });
 }
 
 extern "C" {
-
-int fhe_ctx_inject_fault_ntt_sealed(fhe_ctx *ctx, int row, long long coeff, int bit)
-{
-    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
-    return ctx->ntt_seal_fault.arm(INT_MAX, row, 0, row, coeff, bit) ? FHE_OK : fail(FHE_ERR_INVALID, "bad fault");
-}
-
-int fhe_ntt_inverse_sealed(fhe_ctx *ctx, uint64_t *d_dst, const uint64_t *d_src, const fhe_ntt_tables *t, const fhe_abft *a, size_t n_poly, size_t limbs,
-                           size_t start_idx, const uint64_t *d_seal_src, uint32_t *d_flags, void *stream)
-{
-    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
-    const SealHook nf = ctx->ntt_seal_fault.take();      // one shot, whatever the outcome
-    if (!d_dst || !d_src || !t || !a || !d_flags) return fail(FHE_ERR_INVALID, "null argument");
-    if (a->t != t) return fail(FHE_ERR_INVALID, "the detector was made for another table set");
-    int rc = check_range(t, n_poly, limbs, start_idx);
-    if (rc) return rc;
-    if (!t->has_inverse) return fail(FHE_ERR_UNSUPPORTED, "table set has no inverse (twiddle or N not invertible)");
-    if (ctx->mode != 0 || ctx->resident || ctx->packed_on || ctx->only_pass >= 0 || !ntt_checked_supported(t->log_n))
-        return fail(FHE_ERR_UNSUPPORTED, "the sealed inverse transform runs the checked two-launch transform: not with ntt_mode=1, ntt_resident, ntt_packed, a single-pass hook, or N < 2^5");
-    const size_t units = n_poly * limbs, N = (size_t)1 << t->log_n;
-    SealedInputStep in{d_seal_src, d_flags, nullptr, 0, 0, 0};
-    if ((rc = ntt_seal_hit(nf, units, t->log_n, in))) return rc;
-    // the checked transforms' hook between the two launches (fhe_ctx_inject_fault), two-launch sizes, as fhe_ntt_inverse_checked takes it
-    const bool between = ctx->fault_idx >= 0 && t->log_n >= 13;
-    const long long fidx = ctx->fault_idx;
-    if (between) {
-        ctx->fault_idx = -1;
-        if ((u64)fidx >= units * N) return fail(FHE_ERR_INVALID, "fault index outside the call's window");
-    }
-    if (!units) return FHE_OK;
-    fhe_abft *m = const_cast<fhe_abft *>(a);
-    HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t st = pick(ctx, stream);
-    u32 tin = 1, tout = 1;
-    ntt_checked_tiles(t->log_n, &tin, &tout, true);
-    if (m->sum_in.bytes < units * 8 * tin || m->sum_out.bytes < units * 8 * tout) {
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(m->sum_in.alloc(units * 16 * tin));
-        HIP_TRY(m->sum_out.alloc(units * 16 * tout));
-    }
-    if ((rc = seal_scratch(ctx, st, ntt_seal_part_words((u32)units, t->log_n), &in.part))) return rc;
-    HIP_TRY(hipMemsetAsync(d_flags, 0, 2 * units * sizeof(u32), st));
-    // row (poly, l) of the call is row poly * limbs + l of the sums as well; a run of limbs addresses them from its first limb on
-    auto run = [&](int which) -> int {
-        return for_each_run(t, limbs, start_idx, [&](size_t off, size_t len, int path) -> int {
-            PassArgs pa{d_dst + off * N, t->d_lp.as<LimbParams>(), (u32)(start_idx + off), (u32)len, (u32)(n_poly * len), (u32)limbs, nullptr};
-            if (d_src != d_dst) pa.src = d_src + off * N;
-            hipError_t e = launch_ntt_sealed_inv(st, pa, a->win.as<Tw>(), a->wout.as<Tw>(), a->wout8.as<u64>(), m->sum_in.as<u64>() + off * tin,
-                                                 m->sum_out.as<u64>() + off * tout, t->log_n, path, which, run_seal_in(in, off, len, limbs, tin));
-            return e == hipSuccess ? FHE_OK : hip_fail(e, "launch_ntt_sealed_inv");
-        });
-    };
-    if (between) {
-        if ((rc = run(0))) return rc;
-        hipError_t e = launch_flip_bit(st, d_dst, (u64)fidx, ctx->fault_bit);
-        if (e != hipSuccess) return hip_fail(e, "launch_flip_bit");
-        if ((rc = run(1))) return rc;
-    } else if ((rc = run(-1))) return rc;
-    hipError_t e = launch_compare_sums(st, d_flags + units, m->sum_in.as<u64>(), tin, m->sum_out.as<u64>(), tout, t->d_lp.as<LimbParams>(), (u32)start_idx,
-                                       (u32)limbs, (u32)units);
-    return e == hipSuccess ? FHE_OK : hip_fail(e, "launch_compare_sums");
-}
 
 int fhe_keyswitch_sealed_in_layout(const fhe_keyswitch *p, int out[5])
 {
@@ -161,7 +72,7 @@ int fhe_keyswitch_apply_sealed_in(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_ou
     if ((rc = ksc_hook(p, form, ft, p->acc.as<u64>(), d_add0 != nullptr, d_add1 != nullptr, h))) return rc;
     hipStream_t st = pick(ctx, stream);
     u64 *part;
-    if ((rc = seal_scratch(ctx, st, std::max(ks_sealed_scratch_words(p), ntt_seal_part_words((u32)p->L, p->log_n)), &part))) return rc;
+    if ((rc = seal_scratch(ctx, st, std::max(ks_sealed_scratch_words(p), ntt_seal_part_words((u32)p->L, p->log_n, true)), &part))) return rc;
     key.part = in.part = part;      // stage 0's verdict is out before stage 3 starts on the same stream
     HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)lay[2] * sizeof(u32), st));
     return keyswitch_checked(p, form, d_out0, d_out1, d_c, d_evk, d_add0, d_add1, a, d_flags + lay[2], st, ft, &key, &in);
@@ -219,7 +130,7 @@ static int rotate_sealed_in_body(bool out, fhe_ctx *ctx, fhe_keyswitch *p, uint6
     hipStream_t st = pick(ctx, stream);
     const size_t L = (size_t)p->L, N = (size_t)1 << p->log_n;
     // the launches' partials share one region (stream order keeps them apart); sigma(c1)'s seal lives behind it until stage 0 ends
-    const size_t pw = std::max(std::max(ks_sealed_scratch_words(p), ntt_seal_part_words((u32)L, p->log_n)),
+    const size_t pw = std::max(std::max(ks_sealed_scratch_words(p), ntt_seal_part_words((u32)L, p->log_n, true)),
                                std::max(galois_seal_part_words((u32)L, p->log_n, true), seal_part_words((u32)L, p->log_n)));
     u64 *part;
     if ((rc = seal_scratch(ctx, st, pw + 2 * L, &part))) return rc;

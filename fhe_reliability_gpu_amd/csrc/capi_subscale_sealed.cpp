@@ -93,7 +93,7 @@ int fhe_rescale_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out, const ui
     hipStream_t st = pick(ctx, stream);
     const size_t tail_words = subscale_seal_part_words((u32)(2 * R), p->log_n, true);
     u64 *part;
-    if ((rc = seal_scratch(ctx, st, tail_words + n_parts * ntt_seal_part_words(1, p->log_n), &part))) return rc;
+    if ((rc = seal_scratch(ctx, st, tail_words + n_parts * ntt_seal_part_words(1, p->log_n, true), &part))) return rc;
     tail.part = part;
     tail.part_ntt = part + tail_words;
     HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)lay[1] * sizeof(u32), st));

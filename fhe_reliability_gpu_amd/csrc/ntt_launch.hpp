@@ -466,12 +466,13 @@ size_t galois_seal_part_words(u32 units, int logn, bool out);
 hipError_t launch_automorphism_ntt_sealed(hipStream_t st, const GalSealArgs &a, u64 *part, const u64 *seal_src, u64 *seal_dst, u32 *flags,
                                           const GalSealHit &hit);
 
-// ---- ntt_sealed.hip: the checked inverse transform with its input's seal verified on the transform's own load (ntt_seal_tap.hpp) ----
+// ---- ntt_sealed.hip, ntt_fwd_sealed.hip: the checked transforms with their input's seal verified on the transform's own load and
+// their output sealed on store (ntt_seal_tap.hpp, ntt_sealed_io.hpp) ----
 // what the sealed first launch needs beside launch_ntt_checked's arguments.  Rows are addressed as the detector's sums are: row
 // (poly, l) of the launch at index poly * a.poly_stride + l of seal_src ([rows][2], or null: not compared), flags ([rows]: every
 // row's word is WRITTEN -- SEAL_SUM where the row as the transform loaded it differs from its seal, SEAL_RANGE where a word is
-// >= q_l) and part (ntt_seal_part_words(rows, logn) words).  hit_mask != 0: the test fault, XOR into word hit_coeff of row hit_row
-// in the register as loaded
+// >= q_l) and part (ntt_seal_part_words(rows, logn, inverse) words).  hit_mask != 0: the test fault, XOR into word hit_coeff of row
+// hit_row in the register as loaded
 struct NttSealIn {
     const u64 *seal_src;
     u32 *flags;
@@ -479,32 +480,21 @@ struct NttSealIn {
     u32 hit_row = 0, hit_coeff = 0;
     u64 hit_mask = 0;
 };
-size_t ntt_seal_part_words(u32 rows, int logn);
-// launch_ntt_checked(inverse = true) with the first launch sealed; `which` as there (0: the sealed first launch and its verdict, 1:
-// the second launch), so the between-launch flip hook of the checked stages keeps working.  a.src (optional, mirrored layout): the
-// first launch reads the sealed rows from there and a.data receives the result -- out of place, no copy.  Whole-batch launches
-// only: a.map, a.tmp, a.scratch, a.src_bcast, a.src_stride, a.stream_hint and a.galois must be unset.  ntt_checked_supported sizes
-hipError_t launch_ntt_sealed_inv(hipStream_t st, const PassArgs &a, const Tw *win, const Tw *wout, const u64 *wout8, u64 *sum_in, u64 *sum_out, int logn, int path,
-                                 int which, const NttSealIn &s);
-
+// words of the input digest's partials, [rows][tiles of the loading launch][3], and of the output digest's, [rows][tiles of the
+// storing launch][2].  The two regions are distinct: the single pass writes both in one launch
+size_t ntt_seal_part_words(u32 rows, int logn, bool inverse);
+size_t ntt_seal_out_part_words(u32 rows, int logn, bool inverse);
+// launch_ntt_checked with the first launch (forward: the column pass, inverse: the row pass; below 2^13 the single pass) sealed as
+// NttSealIn describes, and the storing launch digesting every word it stores into part_out, addressed as s.part is.  part_out ==
+// nullptr: no output seal (two-launch sizes: the second launch is launch_ntt_checked's own).  `which` as there (0: the sealed first
+// launch and its verdict, 1: the second launch), so the between-launch flip hook of the checked stages keeps working.  a.src
+// (optional, mirrored layout): the first launch reads the sealed rows from there and a.data receives the result -- out of place, no
+// copy.  Whole-batch launches only: a.map, a.tmp, a.scratch, a.src_bcast, a.src_stride, a.stream_hint and a.galois must be unset.
+// ntt_checked_supported sizes
+hipError_t launch_ntt_sealed(hipStream_t st, const PassArgs &a, const Tw *win, const Tw *wout, const u64 *wout8, u64 *sum_in, u64 *sum_out, int logn, int path,
+                             int which, bool inverse, const NttSealIn &s, u64 *part_out);
 // k_ntt_seal_finish over the rows of launch `a`, whose first launch left `tiles` partials per row at s.part
 hipError_t launch_ntt_seal_finish(hipStream_t st, const PassArgs &a, u32 tiles, const NttSealIn &s);
-
-// ---- ntt_fwd_sealed.hip: the checked forward transform with its input's seal verified on load and its output sealed on store, and
-// the sealed inverse with an output seal (ntt_seal_tap.hpp) ----
-// words of the output digest's partials, [rows][tiles of the storing launch][2]; the input side's: ntt_seal_part_words (inverse) /
-// ntt_seal_fwd_part_words (forward).  The two regions are distinct: the single pass writes both in one launch
-size_t ntt_seal_fwd_part_words(u32 rows, int logn);
-size_t ntt_seal_out_part_words(u32 rows, int logn, bool inverse);
-// launch_ntt_checked(inverse = false) with the first launch (the column pass; below 2^13 the single pass) sealed as NttSealIn
-// describes, and the storing launch (the row pass; the single pass) digesting every word it stores into part_out, addressed as
-// s.part is.  part_out == nullptr: no output digest (two-launch sizes: the second launch is launch_ntt_checked's own).  `which`,
-// a.src and the scope as launch_ntt_sealed_inv
-hipError_t launch_ntt_sealed_fwd(hipStream_t st, const PassArgs &a, const Tw *win, const Tw *wout, const u64 *wout8, u64 *sum_in, u64 *sum_out, int logn, int path,
-                                 int which, const NttSealIn &s, u64 *part_out);
-// launch_ntt_sealed_inv whose storing launch (the inverse column pass; the single pass) digests every word it stores into part_out
-hipError_t launch_ntt_sealed_inv_out(hipStream_t st, const PassArgs &a, const Tw *win, const Tw *wout, const u64 *wout8, u64 *sum_in, u64 *sum_out, int logn,
-                                     int path, int which, const NttSealIn &s, u64 *part_out);
 // one lane per row: seal_dst[row] = the row's merged output digest, canonical, where flags_in[row] and flags_abft[row] are both
 // zero, {~0, ~0} otherwise (ntt_seal_out).  Runs after the verdicts and launch_compare_sums on the same stream
 hipError_t launch_ntt_seal_out_finish(hipStream_t st, const u64 *part_out, u32 tiles, u32 rows, const u32 *flags_in, const u32 *flags_abft, u64 *seal_dst);

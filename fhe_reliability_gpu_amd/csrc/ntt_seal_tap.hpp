@@ -1,14 +1,14 @@
-// ntt_seal_tap.hpp -- the seal of a transform's input, digested from the words the inverse transform's first launch reads (host +
-// device: the kernels of ntt_sealed.hip and the CPU emulation tests/emu/emu_ntt_seal.cpp compile the same tap with the same pass
-// templates).
+// ntt_seal_tap.hpp -- the seal of a transform's input, digested from the words the transform's first launch reads, and the seal of
+// its output, digested from the words its last launch stores (host + device: k_ntt_pass_sealed_io of ntt_sealed_io.hpp and the CPU
+// emulation tests/emu/emu_ntt_seal.cpp compile the same tap with the same pass templates).
 //
 // The sealed streaming kernels digest an operand from the register that is then consumed.  The input limbs of a key switch are
-// consumed by a transform: its first launch (the inverse row pass, or the single pass below 2^13) reads them.  SealInTap is the
-// checked inverse's input-side tap (abft_taps.hpp InvChecksumTap<A, true, OUT>) plus the seal of seal_check.hpp over the same
+// consumed by a transform: its first launch (the inverse row pass, or the single pass below 2^13) reads them.  SealTap is the
+// checked transform's tap (abft_taps.hpp InvChecksumTap / ChecksumTap) plus the seal of seal_check.hpp over the same
 // words: the pass hands every raw 64-bit word of its first register step to raw() BEFORE the conversion to the arithmetic's
 // element (ntt_core.hpp tap_sees_raw) -- on the FP64 path a corrupted word above 2^53 does not survive that conversion, so the
 // digest cannot be taken from the element.  The word's weight is its index in the row plus one, as in every seal; words >= q_l
-// are counted (the window).  in() and the ABFT sum are InvChecksumTap's, unchanged: they see the converted element.
+// are counted (the window).  in() and the ABFT sum are the base's, unchanged: they see the converted element.
 //
 // What is covered: the word as the first register step holds it -- after the load from memory and, where the pass stages its
 // tile through LDS (rows of 32 points and more), after that staging.  Not covered: a fault between raw()'s read of the register
@@ -17,8 +17,8 @@
 // HOOK: the one-shot test fault of fhe_ctx_inject_fault_ntt_sealed, a one-word XOR at (row, index) applied inside raw() before
 // window, digest and conversion; memory stays clean.
 //
-// The sealed forward transform and the inverse with an output seal (ntt_fwd_sealed.hip: fhe_ntt_forward_sealed,
-// fhe_ntt_inverse_sealed_out) are the same tap over either ABFT base.  Input side: raw() as above, on the forward column pass
+// The sealed forward transform and the inverse with an output seal (fhe_ntt_forward_sealed, fhe_ntt_inverse_sealed_out) are the
+// same tap over either ABFT base.  Input side: raw() as above, on the forward column pass
 // (N >= 2^13) or the single pass -- ColPass hands its first register step's words to raw() exactly as RowPass does.  A word >= q_l
 // is digested as it is and raises SEAL_RANGE; the transform then reduces it as the unchecked transform does.  Output side: out()
 // is called with every final word on its way to memory (RowPass::copy_out, the TO_GLOBAL branch of the single pass, ColPass's last
@@ -32,6 +32,8 @@
 #pragma once
 #include "abft_taps.hpp"
 #include "seal_check.hpp"
+
+#include <type_traits>
 
 namespace fhe {
 
@@ -77,12 +79,15 @@ template <class PASS, bool IS_COL> FHE_HD u32 ntt_seal_tile_hit(u32 hit_coeff, u
     else return d < (u32)(PASS::TROWS * PASS::NPTS) ? d : NTT_SEAL_NO_HIT;
 }
 
-// the sealed inverse's first launch: the input digest over InvChecksumTap (OUT: the single pass's output-side ABFT sum)
-template <class A, bool HOOK, bool OUT = false> using SealInTap = SealTap<InvChecksumTap<A, true, OUT>, HOOK, true, false>;
-// the sealed forward transform (IN: the launch that loads the input, OUT: the launch that stores the result; both in the single
-// pass) and the inverse with an output seal: ABFT sum and digest on the same side(s)
-template <class A, bool HOOK, bool IN, bool OUT> using SealFwdTap = SealTap<ChecksumTap<A, IN, OUT>, HOOK, IN, OUT>;
-template <class A, bool HOOK, bool IN, bool OUT> using SealInvTap = SealTap<InvChecksumTap<A, IN, OUT>, HOOK, IN, OUT>;
+// the tap of a sealed pass (k_ntt_pass_sealed_io): the ABFT sums of the direction's base on the sides IN / OUT, the input digest
+// where IN, the output digest where DIGEST -- OUT without DIGEST is the inverse single pass of a call that writes no output seal
+template <class A, bool INV, bool HOOK, bool IN, bool OUT, bool DIGEST = OUT>
+using SealPassTap = SealTap<std::conditional_t<INV, InvChecksumTap<A, IN, OUT>, ChecksumTap<A, IN, OUT>>, HOOK, IN, DIGEST>;
+// the names the tap's three uses had before there was one kernel, kept for code written against them: the sealed inverse's first
+// launch without an output digest, the forward transform, the inverse with an output seal
+template <class A, bool HOOK, bool OUT = false> using SealInTap = SealPassTap<A, true, HOOK, true, OUT, false>;
+template <class A, bool HOOK, bool IN, bool OUT> using SealFwdTap = SealPassTap<A, false, HOOK, IN, OUT>;
+template <class A, bool HOOK, bool IN, bool OUT> using SealInvTap = SealPassTap<A, true, HOOK, IN, OUT>;
 
 // a row's merged partials against its stored seal: SEAL_SUM where a canonical sum differs word for word from the stored one (a
 // stored sum that is not canonical therefore counts as different; stored == nullptr: not compared), SEAL_RANGE where a word was

@@ -308,14 +308,9 @@ class NttTables:
         ``dst`` None: a new array (out of place, no copy; ``src`` is only read); ``dst`` may be ``src`` (in place).  ``seal`` from
         ``seal`` (None: not compared, the window still is).  The words are ``intt``'s, bit for bit; a raised seal flag does not stop
         the call.  Whole-batch launches only: never cut into sub-batches."""
-        limbs = len(self) - start if limbs is None else limbs
-        rows = n_poly * limbs
-        if dst is None:
-            dst = self.eng.alloc(src.size)
-            dst.shape = src.shape
-        f = _checked_flags(self.eng, 2 * rows, lambda fl: lib.fhe_ntt_inverse_sealed(
-            self.eng._h, dst.ptr, src.ptr, self._h, abft._h, n_poly, limbs, start, seal.ptr if seal is not None else None, fl.ptr, stream), stream)
-        return dst, f.reshape(2, rows)
+        call = lambda h, d, s, t, a, n_poly, limbs, start, seal_src, seal_dst, fl, st: lib.fhe_ntt_inverse_sealed(h, d, s, t, a, n_poly, limbs, start, seal_src, fl, st)
+        dst, _, f = self._sealed_io(call, src, seal, abft, dst, False, limbs, start, n_poly, stream)
+        return dst, f
 
     def _sealed_io(self, call, src, seal, abft, dst, seal_out, limbs, start, n_poly, stream):
         limbs = len(self) - start if limbs is None else limbs

@@ -1,62 +1,15 @@
 // emu_ntt_fwd_seal.cpp -- CPU emulation of the sealed forward transform and of the sealed inverse with an output seal (TEST
 // INFRASTRUCTURE ONLY).
 //
-// Runs every launch of the transform tile by tile, thread by thread, with SealFwdTap / SealInvTap (ntt_seal_tap.hpp) on the very
-// pass templates k_ntt_pass_sealed_io instantiates: the launch that loads the input out of place from a source array with the input
-// digest (and the hook), the launch that stores the result with the output digest; below 2^13 one pass with both.  The limb's tables
-// and the tile runner are emu_ntt_seal.cpp's, included as they are.  The library never links this file.
+// Runs every launch of the transform tile by tile, thread by thread, with SealPassTap (ntt_seal_tap.hpp) on the very pass templates
+// k_ntt_pass_sealed_io instantiates: the launch that loads the input out of place from a source array with the input digest (and
+// the hook), the launch that stores the result with the output digest; below 2^13 one pass with both.  The limb's tables, the tile
+// runner and the launch (emu_launch) are emu_ntt_seal.cpp's, included as they are.  The library never links this file.
 //
 //   g++ -O2 -std=c++17 -ffp-contract=off -shared -fPIC -I<csrc> emu_ntt_fwd_seal.cpp -o libemu_ntt_fwd_seal.so
 #include "emu_ntt_seal.cpp"
 
 namespace {
-
-struct IoOut {
-    u64 *parts_in, *parts_out, *sums;      // [tin][3], [tout][2], {sum_in, sum_out}
-    int tin, tout;
-};
-
-// one launch: every tile of PASS over dst (loading from src where IN), the tiles' partials and ABFT sums collected
-template <class PASS, int LOGN, bool IS_COL, bool INV, bool IN, bool OUT>
-void emu_launch(const u64 *src, u64 *dst, const Limb &L, long long hit_coeff, int hit_bit, IoOut &o)
-{
-    typedef typename PASS::Arith A;
-    PassArgs a{dst, &L.p, 0u, 1u, 1u, 1u};
-    std::vector<typename PASS::elem> lds(PASS::LDS_ELEMS > 0 ? PASS::LDS_ELEMS : 1);
-    const auto ctx = A::make_ctx(L.p);
-    const TwPtr tw = as_global(INV ? L.p.inv : L.p.fwd);
-    for (u32 b = 0; b < PASS::TILES; b++) {
-        u32 limb, row0 = 0;
-        u64 *base;
-        if constexpr (IS_COL) base = col_tile<PASS, LOGN>(b, a, limb);
-        else base = row_tile<PASS, LOGN>(b, a, limb, row0);
-        const u32 pos0 = (u32)(base - dst);
-        const u64 *from = IN && src != dst ? src + pos0 : nullptr;
-        auto tapped = [&](auto hook) {
-            constexpr bool HOOK = decltype(hook)::value;
-            typedef std::conditional_t<INV, SealInvTap<A, HOOK, IN, OUT>, SealFwdTap<A, HOOK, IN, OUT>> Tap;
-            const u32 hit_idx = HOOK ? ntt_seal_tile_hit<PASS, IS_COL>((u32)hit_coeff, pos0) : NTT_SEAL_NO_HIT;
-            Tap tap{{L.win.data() + pos0, L.wout.data() + pos0, L.wout8.data() + pos0, pos0, LOGN / 2, typename A::elem(0), typename A::elem(0), 0, 0},
-                    SealAcc{}, 0u, L.p.q, hit_idx, (u64)1 << hit_bit, SealAcc{}};
-            run_tile<PASS>(base, from, lds.data(), tw, row0, ctx, L.p.inv_n, &tap);
-            if constexpr (IN) {
-                o.sums[0] = (o.sums[0] + A::canonical(tap.acc_in, ctx)) % L.p.q;
-                o.parts_in[NTT_SEAL_PART * b] = tap.seal.s0;
-                o.parts_in[NTT_SEAL_PART * b + 1] = tap.seal.s1;
-                o.parts_in[NTT_SEAL_PART * b + 2] = tap.n_range;
-                o.tin = (int)PASS::TILES;
-            }
-            if constexpr (OUT) {
-                o.sums[1] = (o.sums[1] + A::canonical(tap.acc_out, ctx)) % L.p.q;
-                o.parts_out[NTT_SEAL_OUT_PART * b] = tap.seal_out.s0;
-                o.parts_out[NTT_SEAL_OUT_PART * b + 1] = tap.seal_out.s1;
-                o.tout = (int)PASS::TILES;
-            }
-        };
-        if (IN && hit_coeff >= 0) tapped(std::bool_constant<IN>());
-        else tapped(std::false_type());
-    }
-}
 
 template <class A, int LOGN, bool INV>
 void emu_transform(const u64 *src, u64 *dst, const Limb &L, long long hit_coeff, int hit_bit, IoOut &o)

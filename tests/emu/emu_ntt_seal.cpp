@@ -2,8 +2,9 @@
 //
 // Compiles fhe_reliability_gpu_amd/csrc/ntt_seal_tap.hpp together with ntt_core.hpp / ntt_plan.hpp with g++ and runs the first
 // launch of the checked inverse (the inverse row pass of the two-launch sizes, the single pass below 2^13) tile by tile, thread by
-// thread, with SealInTap -- the very pass templates and the very tap k_ntt_pass_sealed instantiates -- out of place from a source
-// array, so that the digest, the window, the hook and the words can be checked without a GPU.  The library never links this file.
+// thread, with the very pass templates and the very tap k_ntt_pass_sealed_io instantiates (SealPassTap) -- out of place from a
+// source array, so that the digest, the window, the hook and the words can be checked without a GPU.  emu_launch, one sealed launch
+// of either direction, serves emu_ntt_fwd_seal.cpp as well.  The library never links this file.
 //
 //   g++ -O2 -std=c++17 -ffp-contract=off -shared -fPIC -I<csrc> emu_ntt_seal.cpp -o libemu_ntt_seal.so
 #include "ntt_plan.hpp"
@@ -85,16 +86,71 @@ void run_tile(u64 *base, const u64 *from, typename PASS::elem *lds, TwPtr tw, u3
     run(std::integral_constant<int, 4>());
 }
 
-// mode 0: no tap; 1: SealInTap (hooked when hit_coeff >= 0); 2: InvChecksumTap (the checked inverse's own first launch)
-template <class PASS, int LOGN, bool OUT>
-int emu_first(const u64 *src, u64 *dst, const Limb &L, int mode, long long hit_coeff, int hit_bit, u64 *parts, u64 *sum_in)
+struct IoOut {
+    u64 *parts_in, *parts_out, *sums;      // [tin][3], [tout][2], {sum_in, sum_out}
+    int tin, tout;
+};
+
+// one sealed launch: every tile of PASS over dst (loading from src where IN) with the tap k_ntt_pass_sealed_io builds (hooked when
+// hit_coeff >= 0), the tiles' partials and ABFT sums collected.  The one place where the tap is constructed and read back
+template <class PASS, int LOGN, bool IS_COL, bool INV, bool IN, bool OUT, bool DIGEST = OUT>
+void emu_launch(const u64 *src, u64 *dst, const Limb &L, long long hit_coeff, int hit_bit, IoOut &o)
 {
     typedef typename PASS::Arith A;
     PassArgs a{dst, &L.p, 0u, 1u, 1u, 1u};
     std::vector<typename PASS::elem> lds(PASS::LDS_ELEMS > 0 ? PASS::LDS_ELEMS : 1);
     const auto ctx = A::make_ctx(L.p);
-    const TwPtr tw = as_global(L.p.inv);
+    const TwPtr tw = as_global(INV ? L.p.inv : L.p.fwd);
+    for (u32 b = 0; b < PASS::TILES; b++) {
+        u32 limb, row0 = 0;
+        u64 *base;
+        if constexpr (IS_COL) base = col_tile<PASS, LOGN>(b, a, limb);
+        else base = row_tile<PASS, LOGN>(b, a, limb, row0);
+        const u32 pos0 = (u32)(base - dst);
+        const u64 *from = IN && src != dst ? src + pos0 : nullptr;
+        auto tapped = [&](auto hook) {
+            constexpr bool HOOK = decltype(hook)::value;
+            const u32 hit_idx = HOOK ? ntt_seal_tile_hit<PASS, IS_COL>((u32)hit_coeff, pos0) : NTT_SEAL_NO_HIT;
+            SealPassTap<A, INV, HOOK, IN, OUT, DIGEST> tap{
+                {L.win.data() + pos0, L.wout.data() + pos0, L.wout8.data() + pos0, pos0, LOGN / 2, typename A::elem(0), typename A::elem(0), 0, 0},
+                SealAcc{}, 0u, L.p.q, hit_idx, (u64)1 << hit_bit, SealAcc{}};
+            run_tile<PASS>(base, from, lds.data(), tw, row0, ctx, L.p.inv_n, &tap);
+            if constexpr (IN) {
+                o.sums[0] = (o.sums[0] + A::canonical(tap.acc_in, ctx)) % L.p.q;
+                o.parts_in[NTT_SEAL_PART * b] = tap.seal.s0;
+                o.parts_in[NTT_SEAL_PART * b + 1] = tap.seal.s1;
+                o.parts_in[NTT_SEAL_PART * b + 2] = tap.n_range;
+                o.tin = (int)PASS::TILES;
+            }
+            if constexpr (OUT) o.sums[1] = (o.sums[1] + A::canonical(tap.acc_out, ctx)) % L.p.q;
+            if constexpr (DIGEST) {
+                o.parts_out[NTT_SEAL_OUT_PART * b] = tap.seal_out.s0;
+                o.parts_out[NTT_SEAL_OUT_PART * b + 1] = tap.seal_out.s1;
+                o.tout = (int)PASS::TILES;
+            }
+        };
+        if (IN && hit_coeff >= 0) tapped(std::bool_constant<IN>());
+        else tapped(std::false_type());
+    }
+}
+
+// mode 0: no tap; 1: the sealed first launch, through emu_launch; 2: InvChecksumTap (the checked inverse's own first launch)
+template <class PASS, int LOGN, bool OUT>
+int emu_first(const u64 *src, u64 *dst, const Limb &L, int mode, long long hit_coeff, int hit_bit, u64 *parts, u64 *sum_in)
+{
+    typedef typename PASS::Arith A;
     *sum_in = 0;
+    if (mode == 1) {      // the single pass forms the output-side ABFT sum and no output digest
+        u64 sums[2] = {0, 0};
+        IoOut o{parts, nullptr, sums, 0, 0};
+        emu_launch<PASS, LOGN, false, true, true, OUT, false>(src, dst, L, hit_coeff, hit_bit, o);
+        *sum_in = sums[0];
+        return o.tin;
+    }
+    PassArgs a{dst, &L.p, 0u, 1u, 1u, 1u};
+    std::vector<typename PASS::elem> lds(PASS::LDS_ELEMS > 0 ? PASS::LDS_ELEMS : 1);
+    const auto ctx = A::make_ctx(L.p);
+    const TwPtr tw = as_global(L.p.inv);
     for (u32 b = 0; b < PASS::TILES; b++) {
         u32 limb, row0 = 0;
         u64 *base = row_tile<PASS, LOGN>(b, a, limb, row0);
@@ -102,24 +158,10 @@ int emu_first(const u64 *src, u64 *dst, const Limb &L, int mode, long long hit_c
         const u64 *from = src + pos0;
         if (mode == 0) {
             run_tile<PASS, NoTap>(base, from, lds.data(), tw, row0, ctx, L.p.inv_n, nullptr);
-        } else if (mode == 2) {
+        } else {
             InvChecksumTap<A, true, OUT> tap{L.win.data() + pos0, L.wout.data() + pos0, L.wout8.data() + pos0, pos0, LOGN / 2, typename A::elem(0), typename A::elem(0), 0, 0};
             run_tile<PASS>(base, from, lds.data(), tw, row0, ctx, L.p.inv_n, &tap);
             *sum_in = (*sum_in + A::canonical(tap.acc_in, ctx)) % L.p.q;
-        } else {
-            auto tapped = [&](auto hook) {
-                constexpr bool HOOK = decltype(hook)::value;
-                const u32 hit_idx = HOOK && (u64)hit_coeff - pos0 < (u64)(PASS::TROWS * PASS::NPTS) ? (u32)hit_coeff - pos0 : NTT_SEAL_NO_HIT;
-                SealInTap<A, HOOK, OUT> tap{{L.win.data() + pos0, L.wout.data() + pos0, L.wout8.data() + pos0, pos0, LOGN / 2, typename A::elem(0), typename A::elem(0), 0, 0},
-                                            SealAcc{}, 0u, L.p.q, hit_idx, (u64)1 << hit_bit};
-                run_tile<PASS>(base, from, lds.data(), tw, row0, ctx, L.p.inv_n, &tap);
-                *sum_in = (*sum_in + A::canonical(tap.acc_in, ctx)) % L.p.q;
-                parts[NTT_SEAL_PART * b] = tap.seal.s0;
-                parts[NTT_SEAL_PART * b + 1] = tap.seal.s1;
-                parts[NTT_SEAL_PART * b + 2] = tap.n_range;
-            };
-            if (hit_coeff >= 0) tapped(std::true_type());
-            else tapped(std::false_type());
         }
     }
     return (int)PASS::TILES;

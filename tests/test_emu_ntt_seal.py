@@ -1,5 +1,5 @@
 """CPU emulation of the sealed inverse transform's first launch (tests/emu/emu_ntt_seal.cpp compiles ntt_seal_tap.hpp with the very
-pass templates k_ntt_pass_sealed instantiates): the digest the pass forms from the words it loads is the seal of seal_check.hpp
+pass templates k_ntt_pass_sealed_io instantiates): the digest the pass forms from the words it loads is the seal of seal_check.hpp
 whatever the tile order, every single-word change the seal promises to catch is caught on that load, and the hooked tap changes
 the words and the digest together while the source stays clean -- without a GPU."""
 import ctypes as C

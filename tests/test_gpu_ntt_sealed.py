@@ -180,6 +180,31 @@ def test_a_fault_on_the_transforms_own_load_is_seen_by_the_sealed_transform_only
     eng.check()
 
 
+def test_intt_sealed_is_intt_sealed_out_without_an_output_seal(F, eng):
+    """One host body and one launcher serve both calls: at the largest single-pass size and the smallest two-launch size, with a
+    50-bit and a 61-bit prime (both arithmetic paths), words and flags are equal on clean rows and on a hooked row of either path."""
+    for logn in (12, 13):
+        N = 1 << logn
+        qs = F.create_moduli(N, [50, 61])
+        t = eng.tables(logn, qs)
+        ab = F.Abft(eng, t)
+        rng = np.random.default_rng(500 + logn)
+        d = eng.upload(np.stack([rng.integers(16, q - 16, N, dtype=np.uint64) for q in qs]))
+        seal = t.seal(d)
+        for hit in (None, (0, N // 2 + 1, 3), (1, N - 1, 3)):
+            if hit:
+                eng.inject_fault_ntt_sealed(*hit)
+            a, fa = t.intt_sealed(d, seal, ab)
+            if hit:
+                eng.inject_fault_ntt_sealed(*hit)
+            b, no_seal, fb = t.intt_sealed_out(d, seal, ab, seal_out=False)
+            assert no_seal is None and fa.shape == fb.shape == (2, 2)
+            assert (fa == fb).all() and not fa[1].any(), (logn, hit, fa, fb)
+            assert fa[0].tolist() == [SUM if hit and r == hit[0] else 0 for r in range(2)], (logn, hit, fa)
+            assert (a.download() == b.download()).all(), (logn, hit)
+    eng.check()
+
+
 # ---- apply_sealed_in ----
 
 def swept_apply(c, tp):
