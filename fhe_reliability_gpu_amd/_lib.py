@@ -218,6 +218,8 @@ _SIG = {
     "fhe_rescale_sealed": (ci, [vp, vp, vp, vp, sz, vp, vp, vp, vp, vp]),
     "fhe_hmult_sealed_out": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, C.POINTER(vp), vp, C.POINTER(vp), vp, vp]),
     "fhe_rotate_sealed_out": (ci, [vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp, C.POINTER(vp), vp, C.POINTER(vp), vp, vp]),
+    "fhe_polymul_sealed": (ci, [vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, vp, vp, vp, vp]),
+    "fhe_ctx_inject_fault_polymul_sealed": (ci, [vp, ci, ci, C.c_longlong, ci]),
     "fhe_ctx_trace": (ci, [vp, ci]),
     "fhe_ctx_trace_read": (ci, [vp, C.c_char_p, sz, C.POINTER(sz)]),
 }

@@ -1,6 +1,6 @@
 // capi_abft.cpp -- ABFT detector around the forward and inverse transforms and the negacyclic product, and the residue-checked
 // element-wise products (part of the C ABI of include/fhe_mi355x.h; shared pieces in capi_internal.hpp)
-#include "capi_internal.hpp"
+#include "capi_sealed.hpp"
 
 extern "C" {
 
@@ -261,29 +261,14 @@ int fhe_polymul_checked(fhe_ctx *ctx, uint64_t *d_c, uint64_t *d_a, uint64_t *d_
     PolymulSums s{};
     if (fused) polymul_checked_tiles(t->log_n, &s.t_in, &s.t_mid, &s.t_out);
     else s.t_in = s.t_mid = s.t_out = 1;
-    const size_t words = units * (2 * s.t_in + 3 * s.t_mid + s.t_out);
-    if (m->psum.bytes < words * 8) {
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(m->psum.alloc(words * 16));
-    }
-    u64 *ps = m->psum.as<u64>();
-    s.ain = ps;
-    s.bin = s.ain + units * s.t_in;
-    s.aout = s.bin + units * s.t_in;
-    s.bout = s.aout + units * s.t_mid;
-    s.cin = s.bout + units * s.t_mid;
-    s.cout = s.cin + units * s.t_mid;
-    if (d_b == d_a) s.bin = s.ain;           // squaring: one forward transform, both checks read its input sums
+    if ((rc = polymul_sums(m, st, units, d_b == d_a, s))) return rc;
     TraceScope tr(ctx, st, "POLYMUL");
     if (fused) {
         const size_t hit_unit = (size_t)fidx / N, hit_limb = hit_unit % limbs;
         rc = for_each_run(t, limbs, start_idx, [&](size_t off, size_t len, int path) -> int {
             PassArgs pa{d_a + off * N, t->d_lp.as<LimbParams>(), (u32)(start_idx + off), (u32)len, (u32)(n_poly * len), (u32)limbs};
             PolymulChecks k{a->win.as<Tw>(), a->wout.as<Tw>(), a->wout8.as<u64>(), s, -1, nullptr, pf.bit};
-            auto rows = [&](PolymulSums &r, size_t o) {      // this launch's rows of the sums: unit (p0 * limbs + l0) of the call
-                r.ain += o * r.t_in, r.bin += o * r.t_in, r.aout += o * r.t_mid, r.bout += o * r.t_mid, r.cin += o * r.t_mid, r.cout += o * r.t_out;
-            };
-            rows(k.s, off);
+            polymul_sums_from(k.s, off);
             if (point >= 0 && hit_limb >= off && hit_limb < off + len) {
                 k.fault_point = point;
                 k.fault_at = (point == 1 ? d_b : point == 3 ? d_c : d_a) + fidx;
@@ -301,7 +286,7 @@ int fhe_polymul_checked(fhe_ctx *ctx, uint64_t *d_c, uint64_t *d_a, uint64_t *d_
                     w.limbs = (u32)lc;
                     w.units = (u32)(pc * lc);
                     PolymulChecks kp = k;
-                    rows(kp.s, p0 * limbs + l0);
+                    polymul_sums_from(kp.s, p0 * limbs + l0);
                     return launch_polymul_checked(sp, w, d_b + off * N + o, d_c + off * N + o, t->log_n, path, kp);
                 });
             }

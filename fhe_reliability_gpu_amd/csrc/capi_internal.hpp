@@ -131,7 +131,8 @@ struct fhe_ctx {
     //                                          fhe_keyswitch_apply_sealed_in, fhe_rotate_sealed_in, fhe_rescale_sealed
     //   fhe_ctx_inject_fault_subscale_sealed   sel = point (SS_AT_LOAD, SS_AT_STORE), row: an input row (load) or output row (store) of
     //                                          fhe_rescale_sealed, an output row of fhe_hmult_sealed_out, fhe_rotate_sealed_out
-    SealHook bsgs_seal_fault, tensor_seal_fault, ks_seal_fault, gal_seal_fault, ntt_seal_fault, subscale_seal_fault;
+    //   fhe_ctx_inject_fault_polymul_sealed    sel = operand (a, b), row: a factor row of fhe_polymul_sealed
+    SealHook bsgs_seal_fault, tensor_seal_fault, ks_seal_fault, gal_seal_fault, ntt_seal_fault, subscale_seal_fault, pm_seal_fault;
     DevBuf seal_part;     // fhe_seal / fhe_seal_verify and the sealed composites: the chunks' partial sums, [rows][chunks][2] (the carried adds: [4] or [6], the sealed tensor product: [8] or [14]; grown on demand)
     DevBuf gal_sums;       // checked Galois permutation: the units' source-side and destination-side sums, [2][units] (grown on demand)
     int geo = 1;           // column-tile geometry of the two-launch path (ntt_launch.hpp)

@@ -28,6 +28,31 @@ inline int seal_scratch(fhe_ctx *ctx, hipStream_t st, size_t words, u64 **out)
     return FHE_OK;
 }
 
+// the six partial-sum arrays of a checked product of `units` rows in the detector's psum (grown on demand, the stream drained first),
+// laid out as fhe_polymul_checked lays them out; s.t_in / t_mid / t_out are set by the caller.  Squaring: one forward transform,
+// both checks read its input sums
+inline int polymul_sums(fhe_abft *m, hipStream_t st, size_t units, bool square, PolymulSums &s)
+{
+    const size_t words = units * (2 * s.t_in + 3 * s.t_mid + s.t_out);
+    if (m->psum.bytes < words * 8) {
+        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(m->psum.alloc(words * 16));
+    }
+    s.ain = m->psum.as<u64>();
+    s.bin = s.ain + units * s.t_in;
+    s.aout = s.bin + units * s.t_in;
+    s.bout = s.aout + units * s.t_mid;
+    s.cin = s.bout + units * s.t_mid;
+    s.cout = s.cin + units * s.t_mid;
+    if (square) s.bin = s.ain;
+    return FHE_OK;
+}
+// a launch's rows of those sums: row o of the call on
+inline void polymul_sums_from(PolymulSums &r, size_t o)
+{
+    r.ain += o * r.t_in, r.bin += o * r.t_in, r.aout += o * r.t_mid, r.bout += o * r.t_mid, r.cin += o * r.t_mid, r.cout += o * r.t_out;
+}
+
 // rows of a switching key, [dnum][2][M]
 inline size_t key_rows(const fhe_keyswitch *p) { return (size_t)p->dnum * 2 * (p->L + p->K); }
 

@@ -82,6 +82,8 @@ struct PolymulChecks {
 };
 void polymul_checked_tiles(int logn, u32 *t_in, u32 *t_mid, u32 *t_out);
 hipError_t launch_polymul_checked(hipStream_t st, const PassArgs &a, u64 *b, u64 *c, int logn, int path, const PolymulChecks &k);
+// its middle launch alone (k_polymul_mid_checked with fault point 2), for a caller that runs the column passes itself
+hipError_t launch_polymul_mid_checked(hipStream_t st, const PassArgs &a, u64 *b, u64 *c, int logn, int path, const PolymulChecks &k);
 // flags[3 unit + k]: k = 0 / 1 / 2 = sums of a / b / the product differ (PolymulSums; tiles 1 for the unfused sequence)
 hipError_t launch_compare_polymul(hipStream_t st, u32 *flags, const PolymulSums &s, const LimbParams *lp, u32 limb0, u32 limbs, u32 units);
 
@@ -496,8 +498,24 @@ hipError_t launch_ntt_sealed(hipStream_t st, const PassArgs &a, const Tw *win, c
 // k_ntt_seal_finish over the rows of launch `a`, whose first launch left `tiles` partials per row at s.part
 hipError_t launch_ntt_seal_finish(hipStream_t st, const PassArgs &a, u32 tiles, const NttSealIn &s);
 // one lane per row: seal_dst[row] = the row's merged output digest, canonical, where flags_in[row] and flags_abft[row] are both
-// zero, {~0, ~0} otherwise (ntt_seal_out).  Runs after the verdicts and launch_compare_sums on the same stream
-hipError_t launch_ntt_seal_out_finish(hipStream_t st, const u64 *part_out, u32 tiles, u32 rows, const u32 *flags_in, const u32 *flags_abft, u64 *seal_dst);
+// zero, {~0, ~0} otherwise (ntt_seal_out).  Runs after the verdicts and launch_compare_sums on the same stream.  flags_in2 (optional):
+// a second verdict block, [rows], counted with the first; abft_words: the ABFT block holds that many words per row, any of them
+// raised poisons the row (the sealed product: two factors' verdicts and launch_compare_polymul's three words)
+hipError_t launch_ntt_seal_out_finish(hipStream_t st, const u64 *part_out, u32 tiles, u32 rows, const u32 *flags_in, const u32 *flags_abft, u64 *seal_dst,
+                                      const u32 *flags_in2 = nullptr, u32 abft_words = 1);
+
+// ---- polymul_sealed.hip: launch_polymul_checked with both factors' seals verified on the loads that transform them and the product
+// sealed from the words the last launch stores (polymul_seal.hpp) ----
+// Rows are addressed as the detector's sums are (NttSealIn).  a / b: the factors' records -- seal, flag block and partials
+// ([rows][t_in][3] each, t_in from polymul_checked_tiles); b is not read when squaring (b == a.data): the caller copies a's verdicts.
+// part_c: [rows][t_out][2] partials of the product's digest, or null: no output seal.  The test fault of either record (hit_mask
+// != 0) is applied in the register as the loading launch takes the word; squaring applies a's to both loads of the single launch.
+// Whole-batch launches only (launch_ntt_sealed's conditions on the PassArgs)
+struct PolymulSealIo {
+    NttSealIn a, b;
+    u64 *part_c;
+};
+hipError_t launch_polymul_sealed(hipStream_t st, const PassArgs &a, u64 *b, u64 *c, int logn, int path, const PolymulChecks &k, const PolymulSealIo &io);
 
 // ---- subscale_sealed.hip: the mod-down tail with its first operand verified on load and its result sealed on store (subscale_seal.hpp) ----
 // what the sealed tail needs beside launch_sub_scale_checked's arguments.  Rows are (half h, limb l) of the launch.  seal_out0 /

@@ -37,24 +37,29 @@ hipError_t launch_ntt_seal_finish(hipStream_t st, const PassArgs &a, u32 tiles, 
     return hipGetLastError();
 }
 
-__global__ __launch_bounds__(256) void k_ntt_seal_out_finish(const u64 *part_out, u32 tiles, u32 rows, const u32 *flags_in, const u32 *flags_abft, u64 *seal_dst)
+__global__ __launch_bounds__(256) void k_ntt_seal_out_finish(const u64 *part_out, u32 tiles, u32 rows, const u32 *flags_in, const u32 *flags_in2, const u32 *flags_abft,
+                                                             u32 abft_words, u64 *seal_dst)
 {
     for (u32 r = blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += gridDim.x * blockDim.x) {
         const u64 *pr = part_out + (size_t)r * tiles * NTT_SEAL_OUT_PART;
         SealAcc acc;
         for (u32 t = 0; t < tiles; t++) acc.merge(pr[(size_t)t * NTT_SEAL_OUT_PART], pr[(size_t)t * NTT_SEAL_OUT_PART + 1]);
+        u32 fin = flags_in[r] | (flags_in2 ? flags_in2[r] : 0u), fab = 0;
+        for (u32 w = 0; w < abft_words; w++) fab |= flags_abft[(size_t)r * abft_words + w];
         u64 out[2];
-        ntt_seal_out(acc, flags_in[r], flags_abft[r], out);
+        ntt_seal_out(acc, fin, fab, out);
         seal_dst[2 * (size_t)r] = out[0];
         seal_dst[2 * (size_t)r + 1] = out[1];
     }
 }
 
-hipError_t launch_ntt_seal_out_finish(hipStream_t st, const u64 *part_out, u32 tiles, u32 rows, const u32 *flags_in, const u32 *flags_abft, u64 *seal_dst)
+hipError_t launch_ntt_seal_out_finish(hipStream_t st, const u64 *part_out, u32 tiles, u32 rows, const u32 *flags_in, const u32 *flags_abft, u64 *seal_dst,
+                                      const u32 *flags_in2, u32 abft_words)
 {
     if (!rows) return hipSuccess;
     const u32 grid = (rows + 255) / 256;
-    hipLaunchKernelGGL(k_ntt_seal_out_finish, dim3(grid < 1024 ? grid : 1024), dim3(256), 0, st, part_out, tiles, rows, flags_in, flags_abft, seal_dst);
+    hipLaunchKernelGGL(k_ntt_seal_out_finish, dim3(grid < 1024 ? grid : 1024), dim3(256), 0, st, part_out, tiles, rows, flags_in, flags_in2, flags_abft, abft_words,
+                       seal_dst);
     return hipGetLastError();
 }
 

@@ -172,6 +172,22 @@ void polymul_checked_tiles(int logn, u32 *t_in, u32 *t_mid, u32 *t_out)
     }
 }
 
+// the middle launch alone (fault point 2 honoured): what launch_polymul_checked runs between the column passes, and what the sealed
+// product (polymul_sealed.hip) runs between its sealed ones at two-launch sizes
+hipError_t launch_polymul_mid_checked(hipStream_t st, const PassArgs &a, u64 *b, u64 *c, int logn, int path, const PolymulChecks &k)
+{
+    const PolymulChkArgs pk{a, b, c, k.win, k.wout, k.wout8, logn / 2, k.s, k.fault_point == 2 ? k.fault_at : nullptr, k.fault_bit};
+    switch (logn) {
+#define FHE_CASE(L) \
+    case L: return path == PATH_F64 ? launch_mid_checked<ArithF64, L>(st, pk) : launch_mid_checked<ArithU64, L>(st, pk);
+        FHE_CASE(5) FHE_CASE(6) FHE_CASE(7) FHE_CASE(8) FHE_CASE(9) FHE_CASE(10) FHE_CASE(11) FHE_CASE(12) FHE_CASE(13)
+        FHE_CASE(14) FHE_CASE(15) FHE_CASE(16) FHE_CASE(17) FHE_CASE(18) FHE_CASE(19) FHE_CASE(20)
+#undef FHE_CASE
+    default:
+        return hipErrorInvalidValue;
+    }
+}
+
 // launch_polymul with the detector: forward column passes with the input taps (two-launch sizes), the checked middle launch,
 // inverse column pass with the output tap.  k.s's pointers are this launch's rows (the caller offsets them like the data).
 hipError_t launch_polymul_checked(hipStream_t st, const PassArgs &a, u64 *b, u64 *c, int logn, int path, const PolymulChecks &k)
@@ -187,19 +203,7 @@ hipError_t launch_polymul_checked(hipStream_t st, const PassArgs &a, u64 *b, u64
         if (b != a.data && (e = launch_ntt_checked(st, pb, k.win, k.wout, k.wout8, k.s.bin, nullptr, logn, path, 0)) != hipSuccess) return e;
         if ((k.fault_point == 0 || k.fault_point == 1) && (e = launch_flip_bit(st, k.fault_at, 0, k.fault_bit)) != hipSuccess) return e;
     }
-    const PolymulChkArgs pk{a, b, c, k.win, k.wout, k.wout8, logn / 2, k.s, k.fault_point == 2 ? k.fault_at : nullptr, k.fault_bit};
-    switch (logn) {
-#define FHE_CASE(L)                                                                                                  \
-    case L:                                                                                                          \
-        e = path == PATH_F64 ? launch_mid_checked<ArithF64, L>(st, pk) : launch_mid_checked<ArithU64, L>(st, pk);    \
-        break;
-        FHE_CASE(5) FHE_CASE(6) FHE_CASE(7) FHE_CASE(8) FHE_CASE(9) FHE_CASE(10) FHE_CASE(11) FHE_CASE(12) FHE_CASE(13)
-        FHE_CASE(14) FHE_CASE(15) FHE_CASE(16) FHE_CASE(17) FHE_CASE(18) FHE_CASE(19) FHE_CASE(20)
-#undef FHE_CASE
-    default:
-        return hipErrorInvalidValue;
-    }
-    if (e != hipSuccess) return e;
+    if ((e = launch_polymul_mid_checked(st, a, b, c, logn, path, k)) != hipSuccess) return e;
     if (logn >= 13) {
         if (k.fault_point == 3 && (e = launch_flip_bit(st, k.fault_at, 0, k.fault_bit)) != hipSuccess) return e;
         return launch_ntt_checked(st, pc, k.win, k.wout, k.wout8, nullptr, k.s.cout, logn, path, 1, true);

@@ -86,6 +86,12 @@ class Engine:
         stays clean.  A negative ``row`` disarms."""
         check(lib.fhe_ctx_inject_fault_ntt_sealed(self._h, row, coeff, bit))
 
+    def inject_fault_polymul_sealed(self, operand: int, row: int = 0, coeff: int = 0, bit: int = 0):
+        """One-shot test hook of ``Abft.polymul_sealed``: flip ``bit`` of word ``coeff`` of row ``row`` of factor ``operand`` (0 = a,
+        1 = b) in the register as the next such call's loading launch takes it, before the window, the digest and the conversion
+        read it; memory stays clean.  A negative ``operand`` disarms.  ``Abft.polymul_checked`` does not take it."""
+        check(lib.fhe_ctx_inject_fault_polymul_sealed(self._h, operand, row, coeff, bit))
+
     def inject_fault_subscale_sealed(self, point: int, row: int = 0, coeff: int = 0, bit: int = 0):
         """One-shot test hook of ``KeySwitch.rescale_sealed`` / ``hmult_sealed_out`` / ``rotate_sealed_out``: point 0 flips ``bit`` of
         word ``coeff`` of input row ``row = part * L + l`` (l < L - 1; ``rescale_sealed`` only) in the register as the sealed tail
@@ -1674,6 +1680,27 @@ class Abft:
         n = n_poly * limbs * 3
         return _checked_flags(self.eng, n, lambda fl: lib.fhe_polymul_checked(self.eng._h, c.ptr, a.ptr, b.ptr, self.t._h, self._h, n_poly, limbs, start, fl.ptr,
                                                                               None)).reshape(n_poly * limbs, 3)
+
+    def polymul_sealed(self, c: DeviceArray, a: DeviceArray, b: DeviceArray, seal_a: Optional[DeviceArray], seal_b: Optional[DeviceArray],
+                       seal_out: bool = True, n_poly: int = 1, limbs: Optional[int] = None, start: int = 0, stream=None):
+        """``polymul_checked`` with the factors' seals verified on the loads that transform them and the seal of ``c`` written from
+        the words the last launch stores: ``(seal_c, flags)``.  ``flags`` is a dict of uint32 arrays: ``a[rows]`` and ``b[rows]``
+        the factors' verdicts with ``seal_verify``'s bits (a seal that is None is not compared, the window still is), ``checked[rows,
+        3]`` ``polymul_checked``'s own flags.  ``seal_c`` is ``[rows][2]``, ``seal``'s of ``c`` word for word on a row with no raised
+        flag and ``{~0, ~0}`` otherwise; ``seal_out`` False: no output digest, ``seal_c`` is None.  ``a`` and ``b`` are scratch: their
+        seals no longer describe them after the call.  ``c`` may alias either factor; ``b is a`` squares (``seal_b`` None or
+        ``seal_a``; ``flags['b']`` repeats ``flags['a']``).  The words are ``polymul``'s, bit for bit; a raised flag does not stop
+        the call.  Whole-batch launches only."""
+        limbs = len(self.t) - start if limbs is None else limbs
+        rows = n_poly * limbs
+        seal_c = None
+        if seal_out:
+            seal_c = self.eng.alloc(rows * 2)
+            seal_c.shape = (rows, 2)
+        f = _checked_flags(self.eng, 5 * rows, lambda fl: lib.fhe_polymul_sealed(
+            self.eng._h, c.ptr, a.ptr, b.ptr, self.t._h, self._h, n_poly, limbs, start, seal_a.ptr if seal_a is not None else None,
+            seal_b.ptr if seal_b is not None else None, seal_c.ptr if seal_c is not None else None, fl.ptr, stream), stream)
+        return seal_c, {"a": f[:rows], "b": f[rows:2 * rows], "checked": f[2 * rows:].reshape(rows, 3)}
 
     def __del__(self):
         try:

@@ -42,7 +42,13 @@ exactly those rows with a poisoned output seal, which a seal_verify sweep of the
 the reference's damage count (output words that differ, the symbol error rate) next to the rows raised.  The control trial must
 raise nothing and produce seals equal to seal(dst).  Exit status 1 when a trial's raised rows are not its flipped rows.
 
-python -m fhe_reliability_gpu_amd.tools.flip_coverage [--repair | --rotate-sum | --bsgs | --fused | --fused-key | --ntt [--batch 4]] [--trials 32] [--num-symbols 1] [--bits-per-symbol 1] [--logn 14] [--row 8] [--seed 1]"""
+--polymul applies the same fault model to the factors of the negacyclic product at rest (the protected chain of
+rfhe_framewk/src/four_step_ntt_protected.py:219-282): two batches of ``--batch`` random rows are sealed, each trial places its flips in
+a or b at rest, and polymul_sealed must raise exactly the flipped rows in exactly the flipped factor's block, raise nothing in the
+checked product's own block -- the corrupted factor is a consistent input to all three ABFT identities -- and leave exactly those
+rows with a poisoned output seal.  The control trial must raise nothing and produce seals equal to seal(c).  Exit status as --ntt.
+
+python -m fhe_reliability_gpu_amd.tools.flip_coverage [--repair | --rotate-sum | --bsgs | --fused | --fused-key | --ntt [--batch 4] | --polymul [--batch 4]] [--trials 32] [--num-symbols 1] [--bits-per-symbol 1] [--logn 14] [--row 8] [--seed 1]"""
 import argparse
 import sys
 
@@ -80,8 +86,11 @@ def main():
     ap.add_argument("--fused", action="store_true", help="run the multiply as hmult_sealed_fused: operands verified on the multiplying load")
     ap.add_argument("--fused-key", action="store_true", help="flip the relinearisation key at rest and run hmult_sealed_fused_key")
     ap.add_argument("--ntt", action="store_true", help="flip the source of the forward transform at rest and run ntt_sealed (ntt_test.cu:104-144)")
-    ap.add_argument("--batch", type=int, default=4, help="--ntt: rows of the batch, one 50-bit prime each")
+    ap.add_argument("--polymul", action="store_true", help="flip a factor of the negacyclic product at rest and run polymul_sealed")
+    ap.add_argument("--batch", type=int, default=4, help="--ntt, --polymul: rows of the batch, one 50-bit prime each")
     a = ap.parse_args()
+    if a.polymul and (a.ntt or a.repair or a.bsgs or a.rotate_sum or a.fused or a.fused_key):
+        ap.error("--polymul is a mode of its own")
     if a.ntt and (a.repair or a.bsgs or a.rotate_sum or a.fused or a.fused_key):
         ap.error("--ntt is a mode of its own")
     if a.fused_key and (a.repair or a.bsgs or a.rotate_sum or a.fused):
@@ -97,6 +106,8 @@ def main():
     eng = F.Engine(0)
     if a.ntt:
         return main_ntt(a, eng)
+    if a.polymul:
+        return main_polymul(a, eng)
     if a.bsgs:
         return main_bsgs(a, eng)
     if a.fused_key:
@@ -342,6 +353,51 @@ def main_ntt(a, eng):
         print(f"trial {trial:3d}: flipped rows {sorted(hit)}, corrupted output words {corrupted:7d} of {out.size} (symbol error rate {corrupted / out.size:.3f}), "
               f"input rows raised {rows}, ABFT words raised {int(np.count_nonzero(fl[1]))}, output seals poisoned {poisoned}, refused by seal_verify {refused}: "
               f"{'ok' if ok else 'WRONG'}", flush=True)
+    eng.check()
+    print(f"summary: {a.trials} trials (one control), {wrong} whose raised rows, poisoned seals or refused rows are not exactly the flipped rows")
+    return 1 if wrong else 0
+
+
+def main_polymul(a, eng):
+    """the trials of --polymul: the reference's flips in a factor of the product at rest, through polymul_sealed"""
+    N, B = 1 << a.logn, a.batch
+    qs = F.create_moduli(N, [50] * B)
+    rng = np.random.default_rng(a.seed)
+    t = eng.tables(a.logn, qs)
+    ab = F.Abft(eng, t)
+    xa, xb = (np.stack([rng.integers(0, q, N, dtype=np.uint64) for q in qs]) for _ in range(2))
+    seal_a, seal_b = t.seal(eng.upload(xa), limbs=B), t.seal(eng.upload(xb), limbs=B)
+    ref = eng.alloc(B * N)
+    t.polymul(ref, eng.upload(xa), eng.upload(xb), limbs=B)
+    clean = ref.download().reshape(B, N)
+    poison = np.uint64((1 << 64) - 1)
+    print(f"N = 2^{a.logn}, batch {B} (50-bit primes): polymul_sealed, flips in a factor at rest; {a.num_symbols} symbols x {a.bits_per_symbol} bits per trial")
+    wrong = 0
+    for trial in range(a.trials):
+        d = [eng.upload(xa), eng.upload(xb)]
+        n_sym = 0 if trial == 0 else a.num_symbols
+        hit = [set(), set()]
+        for idx in rng.choice(2 * xa.size, n_sym, replace=False):
+            op, at = int(idx) // xa.size, int(idx) % xa.size
+            hit[op].add(at // N)
+            for bit in rng.choice(64, a.bits_per_symbol, replace=False):
+                check(lib.fhe_flip_bit(eng._h, d[op].ptr, at, int(bit), None))
+        c = eng.alloc(B * N)
+        seal_c, fl = ab.polymul_sealed(c, d[0], d[1], seal_a, seal_b, limbs=B)
+        out = c.download().reshape(B, N)
+        corrupted = int(np.count_nonzero(out != clean))
+        rows = [np.flatnonzero(fl["a"]).tolist(), np.flatnonzero(fl["b"]).tolist()]
+        s_c, s_ref = seal_c.download().reshape(B, 2), t.seal(c, limbs=B).download().reshape(B, 2)
+        poisoned = [r for r in range(B) if (s_c[r] == poison).all()]
+        sealed = all((s_c[r] == s_ref[r]).all() for r in range(B) if r not in poisoned)
+        refused = np.flatnonzero(t.seal_verify(c, seal_c, limbs=B)).tolist()
+        both = sorted(hit[0] | hit[1])
+        ok = rows == [sorted(hit[0]), sorted(hit[1])] and not fl["checked"].any() and poisoned == both and refused == both and sealed
+        wrong += not ok
+        assert n_sym > 0 or (ok and corrupted == 0), "the control trial raised a flag, or its seals are not seal(c)"
+        print(f"trial {trial:3d}: flipped rows a {sorted(hit[0])} b {sorted(hit[1])}, corrupted product words {corrupted:7d} of {out.size} (symbol error rate "
+              f"{corrupted / out.size:.3f}), rows raised a {rows[0]} b {rows[1]}, ABFT words raised {int(np.count_nonzero(fl['checked']))}, output seals poisoned "
+              f"{poisoned}, refused by seal_verify {refused}: {'ok' if ok else 'WRONG'}", flush=True)
     eng.check()
     print(f"summary: {a.trials} trials (one control), {wrong} whose raised rows, poisoned seals or refused rows are not exactly the flipped rows")
     return 1 if wrong else 0

@@ -1302,7 +1302,8 @@ int fhe_rotate_sealed_in(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint6
  *
  * Not covered: a fault between the tap's read of a register and the conversion that consumes it; the hand-off between the two
  * launches beyond what the whole-transform ABFT sum sees; sub-batched streaming batches; the forward transforms inside the key
- * switch (stages 2 and 6), which stay the checked ones; fhe_polymul; repair; sharded plans. */
+ * switch (stages 2 and 6), which stay the checked ones; repair; sharded plans.  (The negacyclic product has a sealed call of its
+ * own, fhe_polymul_sealed below.) */
 int fhe_ntt_forward_sealed(fhe_ctx *ctx, uint64_t *d_dst, const uint64_t *d_src, const fhe_ntt_tables *t, const fhe_abft *a, size_t n_poly,
                            size_t limbs, size_t start_idx, const uint64_t *d_seal_src, uint64_t *d_seal_dst, uint32_t *d_flags, void *stream);
 int fhe_ntt_inverse_sealed_out(fhe_ctx *ctx, uint64_t *d_dst, const uint64_t *d_src, const fhe_ntt_tables *t, const fhe_abft *a, size_t n_poly,
@@ -1353,6 +1354,43 @@ int fhe_hmult_sealed_out(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint6
 int fhe_rotate_sealed_out(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0, const uint64_t *d_c1,
                           uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, const uint64_t *const *d_seal_in,
                           const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream);
+
+/* ---- sealed negacyclic product: factors verified on load, product sealed on store ----------------------------------------------
+ * fhe_polymul_checked forms its input-side sums from the words as loaded: a bit that rots in a factor at rest -- the fault model of
+ * reliability_test/ntt_test.cu:104-144 and dotprod_test.cu:31-61 -- is a consistent input to all three identities: no flag, every
+ * word of c wrong.  The composition fhe_seal_verify(a) + fhe_seal_verify(b) + fhe_polymul_checked + fhe_seal(c) verifies each factor
+ * on one load and consumes it on another, leaves c unsealed between its final store and the sweep's load, and reads a and b twice
+ * and c once more than needed.  Here the launch that loads a factor (its forward column pass; below 2^13 the single launch that is
+ * the whole product) digests every raw 64-bit word its first register step takes and holds it against the window, and the launch
+ * that stores c (the inverse column pass; below 2^13 the same single launch) digests every final word on its way to memory.
+ *
+ * fhe_polymul_sealed: the data contract of fhe_polymul and fhe_polymul_checked -- rows [n_poly][limbs] of table limbs start_idx ..,
+ * c may alias either factor, a and b are SCRATCH: AFTER THE CALL d_seal_a AND d_seal_b NO LONGER DESCRIBE d_a AND d_b.  The words of
+ * c are fhe_polymul's, bit for bit -- also for a factor word >= q_l, which is flagged, not fixed.  rows = n_poly limbs, row (poly, l)
+ * = poly limbs + l.  d_flags, uint32 [rows a][rows b][rows][3] = 5 rows words, cleared by the call: block 0 a's seal verdict per row
+ * and block 1 b's, with fhe_seal_verify's bits (a NULL seal is not compared, the window always is); block 2 fhe_polymul_checked's
+ * own block, exactly its layout and meaning.  A raised input flag does not stop the call.  d_a == d_b is squaring: one forward
+ * transform, d_seal_b must be NULL or d_seal_a (anything else: FHE_ERR_INVALID), block 1 repeats block 0.  d_seal_c ([rows][2]; NULL:
+ * no output digest) equals fhe_seal(c) word for word on a row with no raised flag; the poison rule applies otherwise: a row with its
+ * a-verdict, its b-verdict or any of its three ABFT words raised leaves with {~0, ~0}, a seal that can never verify.
+ *
+ * Refused with nothing launched and the flag buffer untouched: FHE_ERR_UNSUPPORTED for ntt_mode=1, ntt_resident, ntt_packed, a
+ * single-pass hook, N < 2^5, a table set without an inverse; FHE_ERR_INVALID for a detector made for another table set, a NULL
+ * d_a / d_b / d_c / d_flags, buffers that are not 16-byte aligned.  Whole-batch launches only: no sub-batch cut, no side streams.
+ *
+ * Test hooks, both taken one shot and whatever the call's outcome (a refused call takes them with it): fhe_ctx_inject_fault_polymul's
+ * points 0-3 as in the checked call (2 at every size, 0 / 1 / 3 from 2^13 on) -- they poison the row's output seal through block 2 --
+ * and fhe_ctx_inject_fault_polymul_sealed(operand, row, coeff, bit), operand 0 = a, 1 = b, negative clears: the bit of word coeff of
+ * that factor's row is flipped in the register as the loading launch takes it, before window, digest and conversion; memory stays
+ * clean.  A row or word outside the call, or operand 1 when squaring: FHE_ERR_INVALID with nothing launched.  fhe_polymul_checked
+ * does not run the step: it leaves the hook armed and sees nothing.
+ *
+ * Not covered: a fault between the tap's read of a register and the conversion that consumes it; the hand-offs between the launches
+ * beyond what the ABFT sums see; sub-batched streaming batches; repair (it needs the sweep); sharded plans; ntt_mode=1; N < 2^5. */
+int fhe_ctx_inject_fault_polymul_sealed(fhe_ctx *ctx, int operand /* 0 = a, 1 = b, < 0 disarms */, int row, long long coeff, int bit);
+int fhe_polymul_sealed(fhe_ctx *ctx, uint64_t *d_c, uint64_t *d_a, uint64_t *d_b, const fhe_ntt_tables *t, const fhe_abft *a,
+                       size_t n_poly, size_t limbs, size_t start_idx,
+                       const uint64_t *d_seal_a, const uint64_t *d_seal_b, uint64_t *d_seal_c, uint32_t *d_flags, void *stream);
 
 /* ---- fault injection ---------------------------------------------------------------- */
 /* _flip_bit_kernel<<<1,1>>> (reliability_test/dotprod_test.cu:31-33,55): data[idx] ^= 1 << bit */
