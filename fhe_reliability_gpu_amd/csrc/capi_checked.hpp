@@ -33,10 +33,7 @@ inline size_t ksc_slots(const fhe_keyswitch *p)
     return std::max((size_t)std::max(p->dnum, 2) * (p->L + p->K), (size_t)3 * std::max(p->L - 1, 0));
 }
 
-// in != nullptr (fhe_keyswitch_apply_sealed_in, fhe_rotate_sealed_in; capi_ntt_sealed.cpp): stage 0 is the sealed inverse transform
-// (ntt_sealed.hip) out of place from d_c into the plan's coefficient buffer instead of the copy followed by the checked inverse in
-// place -- same words, same ABFT flags at the same place -- which verifies d_c's seal on the transform's own load; absent, every
-// launch list is the checked call's own
+// the sealed inverse transform that opens a key switch (SealedSteps::in below) or a sealed product
 struct SealedInputStep {
     const uint64_t *seal;          // DEVICE [L][2] the stored seals of d_c's rows, or null: not compared (the window still is)
     uint32_t *flags;               // the rows' flags, [L]: every word is written by stage 0
@@ -123,20 +120,15 @@ KscNtt ksc_ntt(const fhe_keyswitch *p, const fhe_abft *a, hipStream_t st, bool i
 // a plan with a plain modulus (FHE_ERR_UNSUPPORTED), the BGV form one without (FHE_ERR_INVALID) or with more than 64 limbs per
 // scalar stage; mod_switch: the call drops a prime
 int ksc_scope(const fhe_ctx *ctx, const fhe_keyswitch *p, const fhe_abft *a, const uint32_t *d_flags, KsForm form, bool mod_switch);
-// key != nullptr (fhe_keyswitch_apply_sealed, fhe_rotate_sealed_fused, fhe_hmult_sealed_fused_key): stage 3 is the sealed inner
-// product (keyswitch_sealed.hip) instead of launch_ks_mac_checked -- same words, same residue flags at the same place -- which
-// verifies the key on the load that multiplies it; absent, every launch list is the checked call's own
+
+// ---- the sealed steps of a checked call: each replaces one launch of the checked call's list by its sealed form -- same words, same
+// ABFT or residue flags at the same place -- and an absent step leaves that launch the checked call's own (SealedSteps below)
 struct SealedKeyStep {
     const uint64_t *seal_key;      // DEVICE [dnum 2 M][2] the stored seals of the key's rows, or null: not compared
     uint32_t *flags_key;           // the key rows' flags, [dnum][2][M], zeroed by the caller
     u64 *part;                     // ctx->seal_part, at least ks_sealed_scratch_words(p) long
     KsSealHit hit;                 // the sealed call's hook, checked against the plan (ks_seal_hit)
 };
-// in != nullptr: stage 0 is the sealed inverse transform (SealedInputStep above); absent, every launch list is the checked call's own
-// tail != nullptr (fhe_hmult_sealed_out, fhe_rotate_sealed_out, fhe_rescale_sealed; capi_subscale_sealed.cpp): the call's last launch
-// -- the key switch's stage 7 when no rescale follows, the rescale's stage 3 otherwise -- is the sealed tail (subscale_sealed.hip)
-// instead of launch_sub_scale_checked -- same words, same residue flags at the same place -- which writes the outputs' seals from the
-// registers it stores; absent, every launch list is the checked call's own
 struct SealedTailStep {
     uint64_t *seal_out[3];           // DEVICE [limbs][2] per output part, or null: that part is not sealed
     u64 *part;                       // at least subscale_seal_part_words(2 limbs, log_n, flags_in != nullptr) words
@@ -171,13 +163,37 @@ struct SealedTailStep {
     // does that launch have anything to verify or to seal (otherwise it is the checked launch)
     bool runs(size_t part0, bool two) const { return flags_in || seal_out[part0] || (two && seal_out[part0 + 1]); }
 };
+struct SealedTensorStep {
+    const uint64_t *const *seal_in;      // HOST array of the seals of a0, a1, b0, b1; an entry or the array may be null
+    uint32_t *flags_op[4];               // the operands' row flags, [L] each, zeroed by the caller
+};
+// the steps one call runs sealed, named by the caller that sets them; every checked body takes the record last and reads the steps of
+// the launches it owns (ksc_front: in; ksc_back: key, tail; keyswitch_checked and rotate_checked: those three; hmult_checked: tensor,
+// key, tail)
+struct SealedSteps {
+    // the multiply's tensor step is the sealed tensor product (tensor_sealed.hip) instead of fhe_tensor_product_checked: a0, a1, b0, b1
+    // are verified on the load that multiplies them, and the call owns that step's hook (fhe_hmult_sealed_fused and above)
+    const SealedTensorStep *tensor = nullptr;
+    // stage 3 is the sealed inner product (keyswitch_sealed.hip) instead of launch_ks_mac_checked: the key is verified on the load that
+    // multiplies it (fhe_keyswitch_apply_sealed*, fhe_rotate_sealed_fused, _in, _out, fhe_hmult_sealed_fused_key, _out, the hoisted rotations)
+    const SealedKeyStep *key = nullptr;
+    // stage 0 is the sealed inverse transform (ntt_sealed.hip) out of place from d_c into the plan's coefficient buffer instead of the
+    // copy followed by the checked inverse in place: d_c's seal is verified on the transform's own load (fhe_keyswitch_apply_sealed_in,
+    // fhe_rotate_sealed_in, _out; capi_ntt_sealed.cpp)
+    const SealedInputStep *in = nullptr;
+    // the call's last launch -- the key switch's stage 7 when no rescale follows, the rescale's stage 3 otherwise -- is the sealed tail
+    // (subscale_sealed.hip) instead of launch_sub_scale_checked: the outputs' seals are written from the registers it stores
+    // (fhe_hmult_sealed_out, fhe_rotate_sealed_out, fhe_rescale_sealed; capi_subscale_sealed.cpp)
+    const SealedTailStep *tail = nullptr;
+};
 int keyswitch_checked(fhe_keyswitch *p, KsForm form, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk,
                       const uint64_t *d_add0, const uint64_t *d_add1, const fhe_abft *a, uint32_t *d_flags, hipStream_t st, const StagedFault &ft,
-                      const SealedKeyStep *key = nullptr, const SealedInputStep *in = nullptr, const SealedTailStep *tail = nullptr);
-// the whole rotation behind an entry point (fhe_rotate_checked, fhe_bgv_rotate_checked, fhe_rotate_sealed, fhe_rotate_sealed_fused)
-int rotate_checked(KsForm form, KsHookSlot hook, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0,
+                      const SealedSteps &steps = {});
+// the whole rotation behind an entry point (fhe_rotate_checked, fhe_bgv_rotate_checked, fhe_rotate_sealed, fhe_rotate_sealed_fused),
+// which has taken the form's key-switch hook: ft
+int rotate_checked(KsForm form, const StagedFault &ft, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0,
                    const uint64_t *d_c1, uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, uint32_t *d_flags, void *stream,
-                   const SealedKeyStep *key = nullptr, const SealedTailStep *tail = nullptr);
+                   const SealedSteps &steps = {});
 
 // ---- the checked key switch as two halves (keyswitch_checked = front + back; hoisted rotations: one front, a back per element)
 // where each stage's flag words go: s[0..7] the stages of the key switch, s[8] the Galois permutation of a hoisted rotation, s[9]
@@ -208,10 +224,10 @@ struct KscPerm {
     GalSealHit hit{-1, 0, 0, 0};       // the sealed permutation's hook, checked against the call
 };
 int ksc_front(fhe_keyswitch *p, const uint64_t *d_c, const fhe_abft *a, const KscFlags &fl, hipStream_t st, const KscHook &h,
-              const SealedInputStep *in = nullptr);
+              const SealedSteps &steps = {});
 int ksc_back(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk, const uint64_t *d_add0,
              const uint64_t *d_add1, const fhe_abft *a, const KscFlags &fl, hipStream_t st, const KscHook &h, const KscPerm *perm, KsForm form,
-             const SealedKeyStep *key = nullptr, const SealedTailStep *tail = nullptr);
+             const SealedSteps &steps = {});
 
 // defined in capi_keyswitch_sealed.cpp
 // does the plan take the fused route (dnum <= KS_SEAL_MAX_DNUM), or the sweep followed by the checked inner product
@@ -247,23 +263,22 @@ RscLayout rsc_layout(const fhe_keyswitch *p, size_t n_parts, KsForm form);
 // the rescale's fault checked against the plan and the number of parts; *flip = the word a transform stage flips
 int rsc_hook(const fhe_keyswitch *p, KsForm form, const StagedFault &ft, size_t n_parts, u64 **flip);
 // d_in = [n_parts][L][N], outs[i] = [L - 1][N]; the caller has checked scope, arguments and overlap.  Clears the lay.total words
-// at d_flags.  tail != nullptr: stage 3 is the sealed tail (SealedTailStep), and with tail->flags_in stage 0 the sealed inverse transform
+// at d_flags.  tail (the one step a rescale has, so passed as itself): stage 3 is the sealed tail, and with tail->flags_in stage 0 the sealed inverse transform
 int rescale_checked(fhe_keyswitch *p, KsForm form, uint64_t *const *outs, const uint64_t *d_in, size_t n_parts, const fhe_abft *a, uint32_t *d_flags,
                     hipStream_t st, const StagedFault &ft, const SealedTailStep *tail = nullptr);
-// the multiply behind an entry point (fhe_hmult_checked, fhe_bgv_hmult_checked, fhe_hmult_sealed, fhe_hmult_sealed_fused) and its
-// layout.  sealed != nullptr (fhe_hmult_sealed_fused): the tensor step is the sealed one (tensor_sealed.hip) instead of
-// fhe_tensor_product_checked -- same words, same residue flags at the same place -- and the call takes the sealed tensor product's
-// hook as well; absent, the launch list is the checked multiply's own.  key != nullptr (fhe_hmult_sealed_fused_key): the key switch's
-// inner product is the sealed one (SealedKeyStep).  tail != nullptr (fhe_hmult_sealed_out): the last launch is the sealed tail (SealedTailStep)
-struct SealedTensorStep {
-    const uint64_t *const *seal_in;      // HOST array of the seals of a0, a1, b0, b1; an entry or the array may be null
-    uint32_t *flags_op[4];               // the operands' row flags, [L] each, zeroed by the caller
+// the one-shot hooks a multiply owns whatever its outcome, taken by its entry point before the first refusal: the key switch's, the
+// rescale's when it rescales, the tensor step's pointwise one, and the sealed tensor product's when that is the tensor step
+struct HmultHooks {
+    StagedFault ks, rs;
+    PointFault pw;
+    SealHook tensor;
 };
+HmultHooks hmult_take(fhe_ctx *ctx, KsHookSlot ks_hook, KsHookSlot rs_hook, int rescale, bool sealed_tensor);
+// the multiply behind an entry point (fhe_hmult_checked, fhe_bgv_hmult_checked, the fhe_hmult_sealed* calls) and its layout
 int hmult_checked_layout(const fhe_keyswitch *p, KsForm form, int rescale, int out[4]);
-int hmult_checked(KsForm form, KsHookSlot ks_hook, KsHookSlot rs_hook, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1,
-                  const uint64_t *d_a0, const uint64_t *d_a1, const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale,
-                  const fhe_abft *a, uint32_t *d_flags, void *stream, const SealedTensorStep *sealed = nullptr, const SealedKeyStep *key = nullptr,
-                  const SealedTailStep *tail = nullptr);
+int hmult_checked(KsForm form, const HmultHooks &hk, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_a0,
+                  const uint64_t *d_a1, const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a,
+                  uint32_t *d_flags, void *stream, const SealedSteps &steps = {});
 
 // defined in capi_subscale_sealed.cpp
 // the sealed tail's hook as a call took it (ctx->subscale_seal_fault), checked against that call: in_rows_per_part != 0: the call

@@ -175,7 +175,7 @@ int rescale_call(KsForm form, KsHookSlot hook, fhe_ctx *ctx, fhe_keyswitch *p, u
 // again, to the same end)
 int hmult_validate(KsForm form, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_a0, const uint64_t *d_a1,
                    const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a, uint32_t *d_flags,
-                   const StagedFault &kf, const StagedFault &rf, int lay[4])
+                   const HmultHooks &hk, int lay[4])
 {
     int rc = ksc_scope(ctx, p, a, d_flags, form, rescale != 0);
     if (rc) return rc;
@@ -187,51 +187,57 @@ int hmult_validate(KsForm form, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0
     KscHook h;
     u64 *flip;
     BcCheck k{d_flags, -1, 0, 0, 0};
-    if ((rc = ksc_hook(p, form, kf, p->acc.as<u64>(), true, true, h))) return rc;
-    if (rescale && (rc = rsc_hook(p, form, rf, 2, &flip))) return rc;
-    return pointwise_fault(ctx->pw_fault, true, (size_t)p->L << p->log_n, p->log_n, k);
+    if ((rc = ksc_hook(p, form, hk.ks, p->acc.as<u64>(), true, true, h))) return rc;
+    if (rescale && (rc = rsc_hook(p, form, hk.rs, 2, &flip))) return rc;
+    return pointwise_fault(hk.pw, true, (size_t)p->L << p->log_n, p->log_n, k);
 }
 
 } // namespace
 
-int hmult_checked(KsForm form, KsHookSlot ks_hook, KsHookSlot rs_hook, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1,
-                  const uint64_t *d_a0, const uint64_t *d_a1, const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale,
-                  const fhe_abft *a, uint32_t *d_flags, void *stream, const SealedTensorStep *sealed, const SealedKeyStep *key, const SealedTailStep *tail)
+HmultHooks hmult_take(fhe_ctx *ctx, KsHookSlot ks_hook, KsHookSlot rs_hook, int rescale, bool sealed_tensor)
 {
-    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
-    // the one-shot hooks of the steps this call runs belong to it whatever its outcome: the key switch's and (when it rescales) the
-    // rescale's are taken here, the pointwise one by the tensor step (cleared here when the call ends before it), and so is the
-    // sealed tensor product's when that is the tensor step
-    const StagedFault kf = (ctx->*ks_hook).take(), rf = rescale ? (ctx->*rs_hook).take() : StagedFault{};
+    return HmultHooks{(ctx->*ks_hook).take(), rescale ? (ctx->*rs_hook).take() : StagedFault{}, ctx->pw_fault.take(),
+                      sealed_tensor ? ctx->tensor_seal_fault.take() : SealHook{}};
+}
+
+int hmult_checked(KsForm form, const HmultHooks &hk, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_a0,
+                  const uint64_t *d_a1, const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a,
+                  uint32_t *d_flags, void *stream, const SealedSteps &steps)
+{
     int lay[4];
-    int rc = hmult_validate(form, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, d_flags, kf, rf, lay);
+    int rc = hmult_validate(form, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, d_flags, hk, lay);
     TensorSealHit hit{-1, 0, 0, 0};
-    if (sealed) {
-        const SealHook tf = ctx->tensor_seal_fault.take();
-        if (!rc) rc = tensor_seal_hit(tf, (size_t)p->L, p->log_n, hit);
-    }
-    if (rc) {
-        (void)ctx->pw_fault.take();
-        return rc;
-    }
+    if (!rc && steps.tensor) rc = tensor_seal_hit(hk.tensor, (size_t)p->L, p->log_n, hit);
+    if (rc) return rc;
     hipStream_t st = pick(ctx, stream);
     HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)lay[3] * sizeof(u32), st));
     const size_t N = (size_t)1 << p->log_n, L = p->L;
     u64 *d0 = p->hm.as<u64>(), *d1 = d0 + L * N, *d2 = d1 + L * N, *pre = p->hm_pre.as<u64>();
     // (the operands are read by the first step only, the outputs written by the last launches of the last step: an output may reuse
     // an operand's buffer, as for fhe_hmult)
-    if (sealed) {
-        BcCheck k{d_flags + lay[0], -1, 0, 0, 0};
-        if ((rc = pointwise_fault(ctx->pw_fault.take(), true, L << p->log_n, p->log_n, k))) return rc;      // validated above
+    BcCheck k{d_flags + lay[0], -1, 0, 0, 0};
+    if ((rc = pointwise_fault(hk.pw, true, L << p->log_n, p->log_n, k))) return rc;      // validated above
+    if (steps.tensor) {
         uint64_t *const d[3] = {d0, d1, d2};
         const uint64_t *const ops[4] = {d_a0, d_a1, d_b0, d_b1};
-        if ((rc = tensor_sealed_run(ctx, st, d, ops, p->t, 1, L, 0, sealed->seal_in, nullptr, sealed->flags_op, k, hit))) return rc;
-    } else if ((rc = fhe_tensor_product_checked(ctx, d0, d1, d2, d_a0, d_a1, d_b0, d_b1, p->t, L, 0, d_flags + lay[0], st))) return rc;
+        if ((rc = tensor_sealed_run(ctx, st, d, ops, p->t, 1, L, 0, steps.tensor->seal_in, nullptr, steps.tensor->flags_op, k, hit))) return rc;
+    } else {
+        // fhe_tensor_product_checked's launches, with the hook this call took
+        HIP_TRY(hipMemsetAsync(k.flags, 0, L * 3 * sizeof(u32), st));
+        const TensorArgs ta{d0, d1, d2, d_a0, d_a1, d_b0, d_b1, p->t->d_lp.as<LimbParams>(), 0u, (u32)L, p->log_n};
+        hipError_t e = launch_tensor_checked(st, ta, k);
+        if (e != hipSuccess) return hip_fail(e, "launch_tensor_checked");
+    }
     // (tail: the last launch -- the key switch's stage 7, or with a rescale its stage 3 -- writes the outputs' seals)
-    if (!rescale) return keyswitch_checked(p, form, d_out0, d_out1, d2, d_relin_key, d0, d1, a, d_flags + lay[1], st, kf, key, nullptr, tail);
-    if ((rc = keyswitch_checked(p, form, pre, pre + L * N, d2, d_relin_key, d0, d1, a, d_flags + lay[1], st, kf, key))) return rc;
+    SealedSteps ks;
+    ks.key = steps.key;
+    if (!rescale) {
+        ks.tail = steps.tail;
+        return keyswitch_checked(p, form, d_out0, d_out1, d2, d_relin_key, d0, d1, a, d_flags + lay[1], st, hk.ks, ks);
+    }
+    if ((rc = keyswitch_checked(p, form, pre, pre + L * N, d2, d_relin_key, d0, d1, a, d_flags + lay[1], st, hk.ks, ks))) return rc;
     uint64_t *outs[3] = {d_out0, d_out1, nullptr};
-    return rescale_checked(p, form, outs, pre, 2, a, d_flags + lay[2], st, rf, tail);
+    return rescale_checked(p, form, outs, pre, 2, a, d_flags + lay[2], st, hk.rs, steps.tail);
 }
 
 extern "C" {
@@ -264,16 +270,18 @@ int fhe_hmult_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t
                       const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a, uint32_t *d_flags,
                       void *stream)
 {
-    return hmult_checked(KsForm::CKKS, &fhe_ctx::ksc_fault, &fhe_ctx::rsc_fault, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a,
-                         d_flags, stream);
+    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
+    return hmult_checked(KsForm::CKKS, hmult_take(ctx, &fhe_ctx::ksc_fault, &fhe_ctx::rsc_fault, rescale, false), ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1,
+                         d_relin_key, rescale, a, d_flags, stream);
 }
 
 int fhe_bgv_hmult_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_a0, const uint64_t *d_a1,
                           const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a, uint32_t *d_flags,
                           void *stream)
 {
-    return hmult_checked(KsForm::BGV, &fhe_ctx::bgv_ksc_fault, &fhe_ctx::bgv_rsc_fault, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key,
-                         rescale, a, d_flags, stream);
+    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
+    return hmult_checked(KsForm::BGV, hmult_take(ctx, &fhe_ctx::bgv_ksc_fault, &fhe_ctx::bgv_rsc_fault, rescale, false), ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0,
+                         d_b1, d_relin_key, rescale, a, d_flags, stream);
 }
 
 } // extern "C"

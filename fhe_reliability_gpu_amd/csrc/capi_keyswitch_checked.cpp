@@ -129,7 +129,7 @@ KscNtt ksc_ntt(const fhe_keyswitch *p, const fhe_abft *a, hipStream_t st, bool i
 }
 
 // stages 0-2: what does not depend on the key (nor, for hoisted rotations, on the Galois element)
-int ksc_front(fhe_keyswitch *p, const uint64_t *d_c, const fhe_abft *a, const KscFlags &fl, hipStream_t st, const KscHook &h, const SealedInputStep *in)
+int ksc_front(fhe_keyswitch *p, const uint64_t *d_c, const fhe_abft *a, const KscFlags &fl, hipStream_t st, const KscHook &h, const SealedSteps &steps)
 {
     const int L = p->L, K = p->K, M = L + K, dnum = p->dnum;
     const size_t N = (size_t)1 << p->log_n;
@@ -140,8 +140,8 @@ int ksc_front(fhe_keyswitch *p, const uint64_t *d_c, const fhe_abft *a, const Ks
     const KscNtt fwd = ksc_ntt(p, a, st, false), inv = ksc_ntt(p, a, st, true);
 
     // ---- 0: opening INTT (in: no copy, d_c's seal verified on the transform's own load, capi_ntt_sealed.cpp)
-    if (in) {
-        if ((rc = inv.run_sealed(KscRows{coef, 0, 0, (u32)L, 1, (u32)L, 0}, d_c, *in, h.f.stage == 0 ? h.flip : nullptr, h.f.bit))) return rc;
+    if (steps.in) {
+        if ((rc = inv.run_sealed(KscRows{coef, 0, 0, (u32)L, 1, (u32)L, 0}, d_c, *steps.in, h.f.stage == 0 ? h.flip : nullptr, h.f.bit))) return rc;
     } else {
         HIP_TRY(hipMemcpyAsync(coef, d_c, (size_t)L * N * 8, hipMemcpyDeviceToDevice, st));
         if ((rc = inv.run({KscRows{coef, 0, 0, (u32)L, 1, (u32)L, 0}}, h.f.stage == 0 ? h.flip : nullptr, h.f.bit))) return rc;
@@ -177,7 +177,7 @@ int ksc_front(fhe_keyswitch *p, const uint64_t *d_c, const fhe_abft *a, const Ks
 // stages 5 and 6 (stage 10), so that the part the mod-down removes is t [acc t^-1]_P
 int ksc_back(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk, const uint64_t *d_add0,
              const uint64_t *d_add1, const fhe_abft *a, const KscFlags &fl, hipStream_t st, const KscHook &h, const KscPerm *perm,
-             KsForm form, const SealedKeyStep *key, const SealedTailStep *tail)
+             KsForm form, const SealedSteps &steps)
 {
     const int L = p->L, K = p->K, M = L + K, logn = p->log_n;
     const size_t N = (size_t)1 << logn;
@@ -187,12 +187,13 @@ int ksc_back(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_
     hipError_t e;
     const KscNtt fwd = ksc_ntt(p, a, st, false), inv = ksc_ntt(p, a, st, true);
     const bool bgv = form == KsForm::BGV;
+    const SealedTailStep *tail = steps.tail;
 
     // ---- 3: inner product with the key (key: its seal verified on these loads, capi_keyswitch_sealed.cpp)
     {
         const KsMacArgs ka{acc, p->ext.as<u64>(), d_c, d_evk, lp, (u32)L, (u32)M, (u32)p->dnum, (u32)p->alpha, logn, (u32)L, 0u, 0u};
-        if (key) {
-            if ((rc = ks_mac_sealed_stage(p, st, ka, bc_check(h.f.at(0, 3), fl.s[3]), *key))) return rc;
+        if (steps.key) {
+            if ((rc = ks_mac_sealed_stage(p, st, ka, bc_check(h.f.at(0, 3), fl.s[3]), *steps.key))) return rc;
         } else if ((e = launch_ks_mac_checked(st, ka, bc_check(h.f.at(0, 3), fl.s[3]))) != hipSuccess) return hip_fail(e, "launch_ks_mac_checked");
     }
 
@@ -243,7 +244,7 @@ int ksc_back(fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_
 
 int keyswitch_checked(fhe_keyswitch *p, KsForm form, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c, const uint64_t *d_evk,
                       const uint64_t *d_add0, const uint64_t *d_add1, const fhe_abft *a, uint32_t *d_flags, hipStream_t st, const StagedFault &ft,
-                      const SealedKeyStep *key, const SealedInputStep *in, const SealedTailStep *tail)
+                      const SealedSteps &steps)
 {
     int rc;
     if ((rc = ksc_prepare(p))) return rc;
@@ -254,8 +255,8 @@ int keyswitch_checked(fhe_keyswitch *p, KsForm form, uint64_t *d_out0, uint64_t 
     for (int s = 0; s < 11; s++)
         if (lay.units(s)) fl.s[s] = d_flags + lay.off[s];
     HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)lay.total * sizeof(u32), st));
-    if ((rc = ksc_front(p, d_c, a, fl, st, h, in))) return rc;
-    return ksc_back(p, d_out0, d_out1, d_c, d_evk, d_add0, d_add1, a, fl, st, h, nullptr, form, key, tail);
+    if ((rc = ksc_front(p, d_c, a, fl, st, h, steps))) return rc;
+    return ksc_back(p, d_out0, d_out1, d_c, d_evk, d_add0, d_add1, a, fl, st, h, nullptr, form, steps);
 }
 
 int ksc_scope(const fhe_ctx *ctx, const fhe_keyswitch *p, const fhe_abft *a, const uint32_t *d_flags, KsForm form, bool mod_switch)
@@ -304,12 +305,10 @@ int apply_checked(KsForm form, KsHookSlot hook, fhe_ctx *ctx, fhe_keyswitch *p, 
 
 } // namespace
 
-int rotate_checked(KsForm form, KsHookSlot hook, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0,
+int rotate_checked(KsForm form, const StagedFault &ft, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0,
                    const uint64_t *d_c1, uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, uint32_t *d_flags, void *stream,
-                   const SealedKeyStep *key, const SealedTailStep *tail)
+                   const SealedSteps &steps)
 {
-    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
-    const StagedFault ft = (ctx->*hook).take();      // one shot, whatever the outcome
     int rc = ksc_scope(ctx, p, a, d_flags, form, false);
     if (rc) return rc;
     if (!d_out0 || !d_out1 || !d_c0 || !d_c1 || !d_galois_key) return fail(FHE_ERR_INVALID, "null argument");
@@ -323,7 +322,7 @@ int rotate_checked(KsForm form, KsHookSlot hook, fhe_ctx *ctx, fhe_keyswitch *p,
     u64 *sig1 = p->rot.as<u64>(), *sig0 = sig1 + (size_t)p->L * N;
     hipError_t e = launch_automorphism_ntt(st, sig1, d_c1, (u32)p->L, p->log_n, galois_elt, sig0, d_c0);
     if (e != hipSuccess) return hip_fail(e, "launch_automorphism_ntt");
-    return keyswitch_checked(p, form, d_out0, d_out1, sig1, d_galois_key, sig0, nullptr, a, d_flags, st, ft, key, nullptr, tail);
+    return keyswitch_checked(p, form, d_out0, d_out1, sig1, d_galois_key, sig0, nullptr, a, d_flags, st, ft, steps);
 }
 
 extern "C" {
@@ -364,13 +363,15 @@ int fhe_bgv_relinearize_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0
 int fhe_rotate_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0, const uint64_t *d_c1,
                        uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, uint32_t *d_flags, void *stream)
 {
-    return rotate_checked(KsForm::CKKS, &fhe_ctx::ksc_fault, ctx, p, d_out0, d_out1, d_c0, d_c1, galois_elt, d_galois_key, a, d_flags, stream);
+    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
+    return rotate_checked(KsForm::CKKS, ctx->ksc_fault.take(), ctx, p, d_out0, d_out1, d_c0, d_c1, galois_elt, d_galois_key, a, d_flags, stream);
 }
 
 int fhe_bgv_rotate_checked(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0, const uint64_t *d_c1,
                            uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, uint32_t *d_flags, void *stream)
 {
-    return rotate_checked(KsForm::BGV, &fhe_ctx::bgv_ksc_fault, ctx, p, d_out0, d_out1, d_c0, d_c1, galois_elt, d_galois_key, a, d_flags, stream);
+    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
+    return rotate_checked(KsForm::BGV, ctx->bgv_ksc_fault.take(), ctx, p, d_out0, d_out1, d_c0, d_c1, galois_elt, d_galois_key, a, d_flags, stream);
 }
 
 } // extern "C"

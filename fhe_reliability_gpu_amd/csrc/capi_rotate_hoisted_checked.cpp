@@ -123,13 +123,15 @@ int hrc_run(fhe_keyswitch *p, uint64_t *const *d_out0, uint64_t *const *d_out1, 
         // the sealed call: the key verified on the inner product's load, c0 on the permutation's gather
         u32 *in = sealed->flags_in + r * sealed->stride;
         const SealedKeyStep key{sealed->seal_keys ? sealed->seal_keys[r] : nullptr, in + p->L, sealed->part, KsSealHit{0, 0, 0}};
+        SealedSteps steps;
+        steps.key = &key;
         if (sealed->seal_c0) {
             perm.seal_c0 = sealed->seal_c0;
             perm.flags_c0 = in;
             perm.part = sealed->part;
             if (sealed->hit.point >= 0 && sealed->hit_rot == r) perm.hit = sealed->hit;
         }
-        if ((rc = ksc_back(p, d_out0[r], d_out1[r], d_c1, d_prepared_keys[r], nullptr, nullptr, a, fl, st, armed ? h.hook : none, &perm, KsForm::CKKS, &key)))
+        if ((rc = ksc_back(p, d_out0[r], d_out1[r], d_c1, d_prepared_keys[r], nullptr, nullptr, a, fl, st, armed ? h.hook : none, &perm, KsForm::CKKS, steps)))
             return rc;
     }
     return FHE_OK;

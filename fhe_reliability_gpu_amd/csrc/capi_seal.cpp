@@ -73,6 +73,129 @@ int sealed_scratch(fhe_ctx *ctx, hipStream_t st, const fhe_keyswitch *p, bool te
     return seal_scratch(ctx, st, tensor ? std::max(key, tensor_sealed_scratch_words((size_t)p->L, p->log_n, false)) : key, part);
 }
 
+// how much of a sweep-based composite rides on the loads that consume the data instead of sweeps of its own; each level keeps what
+// the one before it fused.  A repairing call (RepairMode) runs at Sweep: repair needs the sweep
+enum class SealedLevel {
+    Sweep,             // every given seal verified by a sweep of its own, both outputs sealed by sweeps
+    Tensor,            // the multiply's four operand sweeps are gone: its tensor step is the sealed tensor product (capi_tensor_sealed.cpp),
+                       // which verifies a0, a1, b0, b1 on the load that multiplies them and writes their row flags where the sweeps wrote them
+    TensorKey,         // the key's sweep is gone as well: the key switch's inner product is the sealed one (capi_keyswitch_sealed.cpp), which
+                       // writes the key rows' flags where the sweep wrote them; the call takes that step's hook.  (A rotation has no tensor
+                       // step: the sweeps over c0 and c1 stay)
+    TensorKeyOut,      // the two output sweeps are gone as well: the call's last launch is the sealed tail (capi_subscale_sealed.cpp), which
+                       // writes the outputs' seals from the registers it stores; the call takes that step's hook
+};
+
+// one sweep-based composite as its entry point describes it; the entry point has taken the checked call's own hooks
+struct SealedCall {
+    fhe_ctx *ctx;
+    fhe_keyswitch *p;
+    uint64_t *d_out0, *d_out1;
+    int n_ops;
+    const uint64_t *ops[4];              // the operands in flag order, L rows each
+    const uint64_t *d_key;
+    int rescale;                         // the multiply drops a prime: outputs of L - 1 rows
+    const SealHook *tensor_hook;         // the sealed tensor product's hook as the multiply took it; null: the checked call has no tensor step
+    bool refused;                        // what else the checked call refuses before its first launch (an even Galois element)
+    const fhe_abft *a;
+    const uint64_t *const *d_seal_in;
+    const uint64_t *d_seal_key;
+    uint64_t *const *d_seal_out;
+    uint32_t *d_flags;
+    void *stream;
+    int (*checked_words)(const fhe_keyswitch *p, KsForm form, int rescale);      // words of the checked call's own block
+};
+
+// the body of every sweep-based composite; checked(flags, steps) runs the checked call with the hooks its entry point took.  Every
+// hook the call owns is taken before the first refusal.  Refusals, in order: scope and the arguments the checked call refuses (its
+// status and message), alignment, an unpaired seal and locator, then the sealed steps' hooks against the call (tensor, key, tail)
+template <class Checked>
+int sealed_composite(const RepairMode *rm, SealedLevel level, const SealedCall &c, KsForm form, Checked checked)
+{
+    if (rm && level != SealedLevel::Sweep) return fail(FHE_ERR_INVALID, "a repairing call runs the sweeps");
+    fhe_ctx *ctx = c.ctx;
+    fhe_keyswitch *p = c.p;
+    uint32_t *d_flags = c.d_flags;
+    const int n = c.n_ops;
+    const bool fused_ops = level >= SealedLevel::Tensor && c.tensor_hook, fused_key = level >= SealedLevel::TensorKey, out = level >= SealedLevel::TensorKeyOut;
+    const SealHook kf = fused_key ? ctx->ks_seal_fault.take() : SealHook{};      // one shot, whatever the outcome
+    const SealHook tf = out ? ctx->subscale_seal_fault.take() : SealHook{};
+    SealedTensorStep tstep{c.d_seal_in, {nullptr, nullptr, nullptr, nullptr}};
+    SealedKeyStep kstep{c.d_seal_key, nullptr, nullptr, KsSealHit{0, 0, 0}};
+    SealedTailStep tail{{c.d_seal_out ? c.d_seal_out[0] : nullptr, c.d_seal_out ? c.d_seal_out[1] : nullptr, nullptr}, nullptr};
+    SealedSteps steps;
+    if (fused_ops) steps.tensor = &tstep;
+    if (fused_key) steps.key = &kstep;
+    if (out) steps.tail = &tail;
+    // what must hold before the first verifying launch, so that a call outside the checked call's scope launches nothing: the
+    // checked call itself then refuses, and its status and message are the call's
+    bool bad = c.refused || !c.d_out0 || !c.d_out1 || c.d_out0 == c.d_out1 || !c.d_key;
+    for (int i = 0; i < n; i++) bad = bad || !c.ops[i];
+    if (ksc_scope(ctx, p, c.a, d_flags, form, c.rescale != 0) || bad) {
+        const int rc = checked(d_flags, steps);
+        return rc ? rc : fail(FHE_ERR_INVALID, "sealed call: bad argument");
+    }
+    if (misaligned({c.d_out0, c.d_out1, c.ops[0], c.ops[1], c.ops[2], c.ops[3], c.d_key, rm ? d_flags : nullptr}))
+        return fail(FHE_ERR_INVALID, "sealed rows are read 16 bytes at a time: the buffers must be 16-byte aligned");
+    if (unpaired(rm, c.d_seal_in, n, c.d_seal_key)) return fail(FHE_ERR_INVALID, "a repairing call takes an operand's seal and locator together");
+    int lay[8], rc;
+    sealed_layout(p, n, c.checked_words(p, form, c.rescale), lay);      // lay[i] operand i, lay[n] the key, lay[n + 1] the checked block, lay[n + 2] the total
+    const size_t L = p->L, out_limbs = c.rescale ? L - 1 : L;
+    if (fused_ops) {
+        TensorSealHit hit;
+        if ((rc = tensor_seal_hit(*c.tensor_hook, L, p->log_n, hit))) return rc;
+        for (int i = 0; i < n; i++) tstep.flags_op[i] = d_flags + lay[i];
+    }
+    if (fused_key && ks_seal_hit(kf, p, kstep.hit)) return fail(FHE_ERR_INVALID, "fault key row or word outside the call");
+    if (out && (rc = subscale_seal_hit(tf, 2, 0, tail.seal_out[0] && tail.seal_out[1] ? out_limbs : 0, p->log_n, tail))) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = pick(ctx, c.stream);
+    u64 *part;
+    if ((rc = sealed_scratch(ctx, st, p, fused_ops, &part))) return rc;
+    kstep.flags_key = d_flags + lay[n];
+    kstep.part = tail.part = part;      // the key's verdict is out before the tail starts on the same stream
+    HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)lay[n + 1] * sizeof(u32), st));
+    uint64_t *d_report = rm ? reinterpret_cast<uint64_t *>(d_flags + report_offset(lay[n + 2])) : nullptr;
+    if (rm) HIP_TRY(hipMemsetAsync(d_report, 0, (size_t)lay[n + 1] * 4 * sizeof(u64), st));      // rows without a seal report CLEAN
+    for (int i = 0; i < n && !fused_ops; i++) {
+        const SealedRows r{c.ops[i], c.d_seal_in ? c.d_seal_in[i] : nullptr, rm && rm->loc_in ? rm->loc_in[i] : nullptr, 1, L, lay[i]};
+        if ((rc = verify_or_repair(st, p->t, r, d_flags, d_report, part))) return rc;
+    }
+    const SealedRows key{c.d_key, c.d_seal_key, rm ? rm->loc_key : nullptr, (size_t)p->dnum * 2, L + p->K, lay[n]};
+    if (!fused_key && (rc = verify_or_repair(st, p->t, key, d_flags, d_report, part))) return rc;
+    if ((rc = checked(d_flags + lay[n + 1], steps)) || out) return rc;
+    return seal_outputs(st, p->t, c.d_seal_out, rm ? rm->loc_out : nullptr, c.d_out0, c.d_out1, out_limbs, part);
+}
+
+// the ten sealed multiplies and rotations: the form by the plan's plain modulus, the checked call's hooks taken here
+int hmult_sealed(const RepairMode *rm, SealedLevel level, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_a0,
+                 const uint64_t *d_a1, const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a,
+                 const uint64_t *const *d_seal_in, const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
+{
+    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
+    const SealedForm f = sealed_form(p);
+    const HmultHooks hk = hmult_take(ctx, f.ks_hook, f.rs_hook, rescale, level >= SealedLevel::Tensor);
+    const SealedCall c{ctx, p, d_out0, d_out1, 4, {d_a0, d_a1, d_b0, d_b1}, d_relin_key, rescale, &hk.tensor, false, a, d_seal_in, d_seal_key, d_seal_out, d_flags, stream,
+                       [](const fhe_keyswitch *q, KsForm form, int rs) { int in[4] = {}; return hmult_checked_layout(q, form, rs, in) ? 0 : in[3]; }};
+    return sealed_composite(rm, level, c, f.form, [&](uint32_t *flags, const SealedSteps &steps) {
+        return hmult_checked(f.form, hk, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, flags, stream, steps);
+    });
+}
+
+int rotate_sealed(const RepairMode *rm, SealedLevel level, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0,
+                  const uint64_t *d_c1, uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, const uint64_t *const *d_seal_in,
+                  const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
+{
+    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
+    const SealedForm f = sealed_form(p);
+    const StagedFault ft = (ctx->*f.ks_hook).take();
+    const SealedCall c{ctx, p, d_out0, d_out1, 2, {d_c0, d_c1, nullptr, nullptr}, d_galois_key, 0, nullptr, !(galois_elt & 1), a, d_seal_in, d_seal_key, d_seal_out, d_flags, stream,
+                       [](const fhe_keyswitch *q, KsForm form, int) { return ksc_layout(q, form).total; }};
+    return sealed_composite(rm, level, c, f.form, [&](uint32_t *flags, const SealedSteps &steps) {
+        return rotate_checked(f.form, ft, ctx, p, d_out0, d_out1, d_c0, d_c1, galois_elt, d_galois_key, a, flags, stream, steps);
+    });
+}
+
 } // namespace
 
 extern "C" {
@@ -172,123 +295,36 @@ int fhe_hmult_sealed_layout(const fhe_keyswitch *p, int rescale, int out[8])
     int inner[4];
     int rc = hmult_checked_layout(p, sealed_form(p).form, rescale, inner);
     if (rc) return rc;
-    for (int i = 0; i < 4; i++) out[i] = i * p->L;
-    out[4] = 4 * p->L;
-    out[5] = out[4] + (int)key_rows(p);
-    out[6] = out[5] + inner[3];
-    out[7] = 0;
+    out[sealed_layout(p, 4, inner[3], out)] = 0;
     return FHE_OK;
 }
 
-// fhe_hmult_sealed (rm == nullptr), fhe_hmult_sealed_repair and fhe_hmult_sealed_fused (fused, never with rm: repair needs the
-// sweep).  fused: the four operand sweeps are gone and the checked multiply's tensor step is the sealed tensor product
-// (capi_tensor_sealed.cpp), which verifies a0, a1, b0, b1 on the load that multiplies them and writes their row flags where the
-// sweeps wrote them; the key's sweep, the key switch, the rescale and the output seals are the same launches.  fused_key
-// (fhe_hmult_sealed_fused_key, with fused): the key's sweep is gone as well and the key switch's inner product is the sealed one
-// (capi_keyswitch_sealed.cpp), which verifies the key on the load that multiplies it and writes the key rows' flags where the
-// sweep wrote them; the call takes that step's hook.  out (fhe_hmult_sealed_out, with fused_key): the two output sweeps are gone as
-// well and the multiply's last launch is the sealed tail (capi_subscale_sealed.cpp), which writes the outputs' seals from the
-// registers it stores; the call takes that step's hook
-static int hmult_sealed_body(const RepairMode *rm, bool fused, bool fused_key, bool out, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_a0,
-                             const uint64_t *d_a1, const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a,
-                             const uint64_t *const *d_seal_in, const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
+int fhe_hmult_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_a0, const uint64_t *d_a1,
+    const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a,
+    const uint64_t *const *d_seal_in, const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
 {
-    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
-    const SealedForm f = sealed_form(p);
-    SealedTensorStep step{d_seal_in, {nullptr, nullptr, nullptr, nullptr}};
-    SealedKeyStep kstep{d_seal_key, nullptr, nullptr, KsSealHit{0, 0, 0}};
-    SealedTailStep tstep{{d_seal_out ? d_seal_out[0] : nullptr, d_seal_out ? d_seal_out[1] : nullptr, nullptr}, nullptr};
-    const SealHook kf = fused_key ? ctx->ks_seal_fault.take() : SealHook{};      // one shot, whatever the outcome
-    const SealHook tf = out ? ctx->subscale_seal_fault.take() : SealHook{};
-    auto checked = [&](uint32_t *flags) {
-        return hmult_checked(f.form, f.ks_hook, f.rs_hook, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, flags, stream,
-                             fused ? &step : nullptr, fused_key ? &kstep : nullptr, out ? &tstep : nullptr);
-    };
-    // what must hold before the first verifying launch, so that a call outside the checked call's scope launches nothing: the
-    // checked call itself then refuses (it returns the status and takes its hooks)
-    if (ksc_scope(ctx, p, a, d_flags, f.form, rescale != 0) || !d_out0 || !d_out1 || d_out0 == d_out1 || !d_a0 || !d_a1 || !d_b0 || !d_b1 || !d_relin_key) {
-        const int rc = checked(d_flags);      // refuses before its first launch
-        return rc ? rc : fail(FHE_ERR_INVALID, "sealed multiply: bad argument");
-    }
-    if (misaligned({d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rm ? d_flags : nullptr})) {
-        (void)checked(nullptr);      // takes the hooks, launches nothing
-        return fail(FHE_ERR_INVALID, "sealed rows are read 16 bytes at a time: the buffers must be 16-byte aligned");
-    }
-    if (unpaired(rm, d_seal_in, 4, d_seal_key)) {
-        (void)checked(nullptr);
-        return fail(FHE_ERR_INVALID, "a repairing call takes an operand's seal and locator together");
-    }
-    int lay[8], rc;
-    if ((rc = fhe_hmult_sealed_layout(p, rescale, lay))) return rc;
-    if (fused) {
-        // the sealed tensor product's hook is checked against the call before the key's sweep is launched
-        TensorSealHit hit;
-        if (tensor_seal_hit(ctx->tensor_seal_fault, (size_t)p->L, p->log_n, hit)) {
-            (void)checked(nullptr);      // takes the hooks, launches nothing
-            return fail(FHE_ERR_INVALID, "fault row or word outside the call");
-        }
-        for (int i = 0; i < 4; i++) step.flags_op[i] = d_flags + lay[i];
-    }
-    if (fused_key && ks_seal_hit(kf, p, kstep.hit)) {
-        (void)checked(nullptr);      // takes the hooks, launches nothing
-        return fail(FHE_ERR_INVALID, "fault key row or word outside the call");
-    }
-    const size_t out_limbs = tstep.seal_out[0] && tstep.seal_out[1] ? (size_t)(rescale ? p->L - 1 : p->L) : 0;
-    if (out && subscale_seal_hit(tf, 2, 0, out_limbs, p->log_n, tstep)) {
-        (void)checked(nullptr);      // takes the hooks, launches nothing
-        return subscale_seal_hit(tf, 2, 0, out_limbs, p->log_n, tstep);      // the status and its message
-    }
-    HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t st = pick(ctx, stream);
-    u64 *part;
-    if ((rc = sealed_scratch(ctx, st, p, fused, &part))) return rc;
-    kstep.flags_key = d_flags + lay[4];
-    kstep.part = tstep.part = part;      // the key's verdict is out before the tail starts on the same stream
-    HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)lay[5] * sizeof(u32), st));
-    uint64_t *d_report = rm ? reinterpret_cast<uint64_t *>(d_flags + report_offset(lay[6])) : nullptr;
-    if (rm) HIP_TRY(hipMemsetAsync(d_report, 0, (size_t)lay[5] * 4 * sizeof(u64), st));      // rows without a seal report CLEAN
-    const size_t L = p->L;
-    const uint64_t *ops[4] = {d_a0, d_a1, d_b0, d_b1};
-    for (int i = 0; i < 4 && !fused; i++) {
-        const SealedRows r{ops[i], d_seal_in ? d_seal_in[i] : nullptr, rm && rm->loc_in ? rm->loc_in[i] : nullptr, 1, L, lay[i]};
-        if ((rc = verify_or_repair(st, p->t, r, d_flags, d_report, part))) return rc;
-    }
-    const SealedRows key{d_relin_key, d_seal_key, rm ? rm->loc_key : nullptr, (size_t)p->dnum * 2, L + p->K, lay[4]};
-    if (!fused_key && (rc = verify_or_repair(st, p->t, key, d_flags, d_report, part))) return rc;
-    if ((rc = checked(d_flags + lay[5])) || out) return rc;
-    return seal_outputs(st, p->t, d_seal_out, rm ? rm->loc_out : nullptr, d_out0, d_out1, rescale ? L - 1 : L, part);
-}
-
-int fhe_hmult_sealed_out(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_a0, const uint64_t *d_a1,
-                         const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a,
-                         const uint64_t *const *d_seal_in, const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
-{
-    return hmult_sealed_body(nullptr, true, true, true, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, d_seal_in, d_seal_key, d_seal_out,
-                             d_flags, stream);
+    return hmult_sealed(nullptr, SealedLevel::Sweep, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, d_seal_in, d_seal_key, d_seal_out, d_flags, stream);
 }
 
 int fhe_hmult_sealed_fused(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_a0, const uint64_t *d_a1,
-                           const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a,
-                           const uint64_t *const *d_seal_in, const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
+    const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a,
+    const uint64_t *const *d_seal_in, const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
 {
-    return hmult_sealed_body(nullptr, true, false, false, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, d_seal_in, d_seal_key, d_seal_out,
-                             d_flags, stream);
+    return hmult_sealed(nullptr, SealedLevel::Tensor, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, d_seal_in, d_seal_key, d_seal_out, d_flags, stream);
 }
 
 int fhe_hmult_sealed_fused_key(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_a0, const uint64_t *d_a1,
-                               const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a,
-                               const uint64_t *const *d_seal_in, const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
+    const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a,
+    const uint64_t *const *d_seal_in, const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
 {
-    return hmult_sealed_body(nullptr, true, true, false, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, d_seal_in, d_seal_key, d_seal_out,
-                             d_flags, stream);
+    return hmult_sealed(nullptr, SealedLevel::TensorKey, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, d_seal_in, d_seal_key, d_seal_out, d_flags, stream);
 }
 
-int fhe_hmult_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_a0, const uint64_t *d_a1,
-                     const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a,
-                     const uint64_t *const *d_seal_in, const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
+int fhe_hmult_sealed_out(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_a0, const uint64_t *d_a1,
+    const uint64_t *d_b0, const uint64_t *d_b1, const uint64_t *d_relin_key, int rescale, const fhe_abft *a,
+    const uint64_t *const *d_seal_in, const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
 {
-    return hmult_sealed_body(nullptr, false, false, false, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, d_seal_in, d_seal_key, d_seal_out, d_flags,
-                             stream);
+    return hmult_sealed(nullptr, SealedLevel::TensorKeyOut, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, d_seal_in, d_seal_key, d_seal_out, d_flags, stream);
 }
 
 int fhe_hmult_sealed_repair_layout(const fhe_keyswitch *p, int rescale, int out[10])
@@ -307,87 +343,23 @@ int fhe_hmult_sealed_repair(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, ui
                             uint64_t *const *d_seal_out, uint64_t *const *d_locator_out, uint32_t *d_flags, void *stream)
 {
     const RepairMode rm{d_locator_in, d_locator_key, d_locator_out};
-    return hmult_sealed_body(&rm, false, false, false, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, d_seal_in, d_seal_key, d_seal_out, d_flags,
-                             stream);
+    return hmult_sealed(&rm, SealedLevel::Sweep, ctx, p, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_relin_key, rescale, a, d_seal_in, d_seal_key, d_seal_out, d_flags, stream);
 }
 
-int fhe_rotate_sealed_layout(const fhe_keyswitch *p, int out[6])
-{
-    if (!p || !out) return fail(FHE_ERR_INVALID, "null argument");
-    out[0] = 0;
-    out[1] = p->L;
-    out[2] = 2 * p->L;
-    out[3] = out[2] + (int)key_rows(p);
-    out[4] = out[3] + ksc_layout(p, sealed_form(p).form).total;
-    out[5] = 0;
-    return FHE_OK;
-}
-
-// fhe_rotate_sealed (rm == nullptr), fhe_rotate_sealed_repair and fhe_rotate_sealed_fused (fused_key, never with rm: repair needs
-// the sweep).  fused_key: the sweeps over c0 and c1 stay, the key's sweep is gone and the key switch's inner product is the sealed
-// one (capi_keyswitch_sealed.cpp), which writes the key rows' flags where the sweep wrote them; the call takes that step's hook
-static int rotate_sealed_body(const RepairMode *rm, bool fused_key, fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0,
-                              const uint64_t *d_c1, uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, const uint64_t *const *d_seal_in,
-                              const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
-{
-    if (!ctx) return fail(FHE_ERR_INVALID, "null ctx");
-    const SealedForm f = sealed_form(p);
-    SealedKeyStep kstep{d_seal_key, nullptr, nullptr, KsSealHit{0, 0, 0}};
-    const SealHook kf = fused_key ? ctx->ks_seal_fault.take() : SealHook{};      // one shot, whatever the outcome
-    auto checked = [&](uint32_t *flags) {
-        return rotate_checked(f.form, f.ks_hook, ctx, p, d_out0, d_out1, d_c0, d_c1, galois_elt, d_galois_key, a, flags, stream, fused_key ? &kstep : nullptr);
-    };
-    if (ksc_scope(ctx, p, a, d_flags, f.form, false) || !d_out0 || !d_out1 || d_out0 == d_out1 || !d_c0 || !d_c1 || !d_galois_key || !(galois_elt & 1)) {
-        const int rc = checked(d_flags);      // refuses before its first launch
-        return rc ? rc : fail(FHE_ERR_INVALID, "sealed rotation: bad argument");
-    }
-    if (misaligned({d_out0, d_out1, d_c0, d_c1, d_galois_key, rm ? d_flags : nullptr})) {
-        (void)checked(nullptr);      // takes the hook, launches nothing
-        return fail(FHE_ERR_INVALID, "sealed rows are read 16 bytes at a time: the buffers must be 16-byte aligned");
-    }
-    if (unpaired(rm, d_seal_in, 2, d_seal_key)) {
-        (void)checked(nullptr);
-        return fail(FHE_ERR_INVALID, "a repairing call takes an operand's seal and locator together");
-    }
-    int lay[6], rc;
-    if ((rc = fhe_rotate_sealed_layout(p, lay))) return rc;
-    if (fused_key && ks_seal_hit(kf, p, kstep.hit)) {
-        (void)checked(nullptr);      // takes the hook, launches nothing
-        return fail(FHE_ERR_INVALID, "fault key row or word outside the call");
-    }
-    HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t st = pick(ctx, stream);
-    u64 *part;
-    if ((rc = sealed_scratch(ctx, st, p, false, &part))) return rc;
-    kstep.flags_key = d_flags + lay[2];
-    kstep.part = part;
-    HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)lay[3] * sizeof(u32), st));
-    uint64_t *d_report = rm ? reinterpret_cast<uint64_t *>(d_flags + report_offset(lay[4])) : nullptr;
-    if (rm) HIP_TRY(hipMemsetAsync(d_report, 0, (size_t)lay[3] * 4 * sizeof(u64), st));      // rows without a seal report CLEAN
-    const size_t L = p->L;
-    const uint64_t *ops[2] = {d_c0, d_c1};
-    for (int i = 0; i < 2; i++) {
-        const SealedRows r{ops[i], d_seal_in ? d_seal_in[i] : nullptr, rm && rm->loc_in ? rm->loc_in[i] : nullptr, 1, L, lay[i]};
-        if ((rc = verify_or_repair(st, p->t, r, d_flags, d_report, part))) return rc;
-    }
-    const SealedRows key{d_galois_key, d_seal_key, rm ? rm->loc_key : nullptr, (size_t)p->dnum * 2, L + p->K, lay[2]};
-    if (!fused_key && (rc = verify_or_repair(st, p->t, key, d_flags, d_report, part))) return rc;
-    if ((rc = checked(d_flags + lay[3]))) return rc;
-    return seal_outputs(st, p->t, d_seal_out, rm ? rm->loc_out : nullptr, d_out0, d_out1, L, part);
-}
+int fhe_rotate_sealed_layout(const fhe_keyswitch *p, int out[6]) { return ks_sealed_layout(p, 2, false, out); }
 
 int fhe_rotate_sealed(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0, const uint64_t *d_c1,
-                      uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, const uint64_t *const *d_seal_in,
-                      const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
+    uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, const uint64_t *const *d_seal_in,
+    const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
 {
-    return rotate_sealed_body(nullptr, false, ctx, p, d_out0, d_out1, d_c0, d_c1, galois_elt, d_galois_key, a, d_seal_in, d_seal_key, d_seal_out, d_flags, stream);
+    return rotate_sealed(nullptr, SealedLevel::Sweep, ctx, p, d_out0, d_out1, d_c0, d_c1, galois_elt, d_galois_key, a, d_seal_in, d_seal_key, d_seal_out, d_flags, stream);
 }
 
 int fhe_rotate_sealed_fused(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c0, const uint64_t *d_c1,
-                            uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, const uint64_t *const *d_seal_in,
-                            const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
+    uint32_t galois_elt, const uint64_t *d_galois_key, const fhe_abft *a, const uint64_t *const *d_seal_in,
+    const uint64_t *d_seal_key, uint64_t *const *d_seal_out, uint32_t *d_flags, void *stream)
 {
-    return rotate_sealed_body(nullptr, true, ctx, p, d_out0, d_out1, d_c0, d_c1, galois_elt, d_galois_key, a, d_seal_in, d_seal_key, d_seal_out, d_flags, stream);
+    return rotate_sealed(nullptr, SealedLevel::TensorKey, ctx, p, d_out0, d_out1, d_c0, d_c1, galois_elt, d_galois_key, a, d_seal_in, d_seal_key, d_seal_out, d_flags, stream);
 }
 
 int fhe_rotate_sealed_repair_layout(const fhe_keyswitch *p, int out[8])
@@ -406,7 +378,7 @@ int fhe_rotate_sealed_repair(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, u
                              uint32_t *d_flags, void *stream)
 {
     const RepairMode rm{d_locator_in, d_locator_key, d_locator_out};
-    return rotate_sealed_body(&rm, false, ctx, p, d_out0, d_out1, d_c0, d_c1, galois_elt, d_galois_key, a, d_seal_in, d_seal_key, d_seal_out, d_flags, stream);
+    return rotate_sealed(&rm, SealedLevel::Sweep, ctx, p, d_out0, d_out1, d_c0, d_c1, galois_elt, d_galois_key, a, d_seal_in, d_seal_key, d_seal_out, d_flags, stream);
 }
 
 } // extern "C"

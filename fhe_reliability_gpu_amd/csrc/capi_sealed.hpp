@@ -1,6 +1,7 @@
 // capi_sealed.hpp -- what the sealed entry points share (capi_seal.cpp, capi_seal_carry.cpp, capi_tensor_sealed.cpp,
-// capi_keyswitch_sealed.cpp, capi_galois_sealed.cpp, capi_ntt_sealed.cpp, capi_bsgs_checked.cpp): the alignment test, the context's
-// partial-sum scratch, the form a plan runs, and the sweeps that verify given seals and seal outputs.  Host only.
+// capi_keyswitch_sealed.cpp, capi_galois_sealed.cpp, capi_ntt_sealed.cpp, capi_ntt_fwd_sealed.cpp, capi_polymul_sealed.cpp,
+// capi_subscale_sealed.cpp, capi_bsgs_checked.cpp, capi_abft.cpp): the alignment test, the context's partial-sum scratch, the form a plan runs, the
+// flag layout and the prologue of the sealed key-switch calls, and the sweeps that verify given seals and seal outputs.  Host only.
 #pragma once
 #include "capi_checked.hpp"
 #include "seal_check.hpp"
@@ -66,6 +67,66 @@ inline SealedForm sealed_form(const fhe_keyswitch *p)
     if (p && p->plain_modulus) return SealedForm{KsForm::BGV, &fhe_ctx::bgv_ksc_fault, &fhe_ctx::bgv_rsc_fault};
     return SealedForm{KsForm::CKKS, &fhe_ctx::ksc_fault, &fhe_ctx::rsc_fault};
 }
+
+// the flag layout every sealed key-switch call shares -- k input blocks of L rows, the key's rows, the checked call's block of
+// `checked` words: out[0 .. k - 1] the inputs, out[k] the key, out[k + 1] the checked block, out[k + 2] the total.  Returns k + 3,
+// the index of the word the caller closes the layout with
+inline int sealed_layout(const fhe_keyswitch *p, int k, int checked, int *out)
+{
+    for (int i = 0; i <= k; i++) out[i] = i * p->L;
+    out[k + 1] = out[k] + (int)key_rows(p);
+    out[k + 2] = out[k + 1] + checked;
+    return k + 3;
+}
+// that layout around the checked key switch, as a layout call: closed by "the plan takes the fused route" (fused_word), or by 0
+inline int ks_sealed_layout(const fhe_keyswitch *p, int k, bool fused_word, int *out)
+{
+    if (!p || !out) return fail(FHE_ERR_INVALID, "null argument");
+    out[sealed_layout(p, k, ksc_layout(p, sealed_form(p).form).total, out)] = fused_word && ks_sealed_fused(p);
+    return FHE_OK;
+}
+
+// ---- the key-switch family (fhe_keyswitch_apply_sealed, fhe_keyswitch_apply_sealed_in, fhe_rotate_sealed_in, fhe_rotate_sealed_out):
+// one prologue and one call of keyswitch_checked, both defined in capi_keyswitch_sealed.cpp
+// what a rotation of the family adds to the key switch it ends in; `out`: the tail seals the outputs (fhe_rotate_sealed_out)
+struct KsSealedRotation {
+    uint32_t galois_elt;
+    const uint64_t *const *d_seal_in;      // the seals of c0 and c1, both required
+    uint64_t *const *d_seal_out;
+    bool out;
+};
+// the call as its entry point takes it.  A rotation switches sigma(c1) with sigma(c0) as the first addend: d_c = c1, d_evk = the
+// Galois key, d_add0 = c0 (required), d_add1 = null
+struct KsSealedCall {
+    fhe_ctx *ctx;
+    fhe_keyswitch *p;
+    uint64_t *d_out0, *d_out1;
+    const uint64_t *d_c, *d_evk, *d_add0, *d_add1;
+    const fhe_abft *a;
+    const uint64_t *d_seal_key;
+    uint32_t *d_flags;
+    void *stream;
+    int in_blocks;                   // blocks of L input flag words before the key's: 0, 1 (c: _apply_sealed_in), 3 (c0, c1, sigma(c1): rot)
+    const uint64_t *d_seal_c;        // in_blocks == 1: the seal of d_c, required
+    const KsSealedRotation *rot;     // in_blocks == 3
+};
+// the call between its prologue and keyswitch_checked
+struct KsSealed {
+    KsForm form;
+    StagedFault ft;                  // the form's key-switch hook
+    hipStream_t st;
+    int lay[7];                      // ks_sealed_layout(p, in_blocks)
+    u64 *part, *behind;              // the launches' shared partials (stream order keeps them apart); rotation: 2 L words behind them
+    SealedKeyStep key;
+    SealedInputStep in;              // in_blocks != 0; its flags are the last input block
+    SealedTailStep tail;             // rot->out
+};
+// the prologue, in this order: every hook of the steps the call runs is taken (they belong to it whatever its outcome); a missing
+// d_seal_c; scope; null, missing-seal (rotation), identical-output, Galois-element and alignment refusals; the sealed steps' hooks
+// against the call; ksc_prepare and the checked key switch's hook against the call; the scratch; the clear of the input and key flags
+int ks_sealed_open(const KsSealedCall &c, KsSealed &k);
+// keyswitch_checked on d_c with first addend d_add0 (the call's own, or a rotation's sigma(c1) and sigma(c0)) and the steps k holds
+int ks_sealed_run(const KsSealedCall &c, const KsSealed &k, const uint64_t *d_c, const uint64_t *d_add0);
 
 // rows [n_poly][limbs] of table set t from limb start_idx on
 inline SealArgs seal_args(const fhe_ntt_tables *t, const uint64_t *d_words, size_t n_poly, size_t limbs, size_t start_idx)

@@ -1300,15 +1300,14 @@ class KeySwitch:
         "key": [dnum][2][M], "checked": {the stage names of checked_layout / bgv_checked_layout}}``."""
         return self._rotate_sealed(lib.fhe_rotate_sealed, c0, c1, galois_elt, galois_key, abft, seals, key_seal, stream)
 
-    def _rotate_sealed(self, call, c0, c1, galois_elt, galois_key, abft, seals, key_seal, stream):
-        names = ("c0", "c1")
-        lay = self.rotate_sealed_layout()
-        o0, o1, so, f = self._sealed(lay, names, self.L, seals, lambda o0, o1, sin, sout, fl: call(
+    def _rotate_sealed(self, call, c0, c1, galois_elt, galois_key, abft, seals, key_seal, stream, lay=None, rows=("c0", "c1")):
+        """One sealed rotation: ``lay`` its layout (``rotate_sealed_layout`` by default), ``rows`` the input blocks of its flags."""
+        lay = lay or self.rotate_sealed_layout()
+        o0, o1, so, f = self._sealed(lay, ("c0", "c1"), self.L, seals, lambda o0, o1, sin, sout, fl: call(
             self.eng._h, self._h, o0.ptr, o1.ptr, c0.ptr, c1.ptr, galois_elt, galois_key.ptr, abft._h, sin,
             key_seal.ptr if key_seal is not None else None, sout, fl.ptr, stream), stream)
-        flags = self._split_flags(f, lay, names + ("key",))
-        kl = self._ks_layout(bool(self.plain_modulus))
-        flags["checked"] = self._split_flags(f, kl, base=lay["checked"])
+        flags = self._split_flags(f, lay, rows + ("key",))
+        flags["checked"] = self._split_flags(f, self._ks_layout(bool(self.plain_modulus)), base=lay["checked"])
         return o0, o1, so, flags
 
     # ---- sealed key-switch inner product: the key verified on the load that multiplies it (keyswitch_sealed.hip) ----
@@ -1332,12 +1331,15 @@ class KeySwitch:
         (seal_check.hpp); no key word is read twice.  A changed key word raises its row and not ``checked["mac"]``: the residue
         identity holds on the key as loaded.  Not covered on the consuming load: ``c`` (its loads are inside transform kernels)
         and the plan's digits, which the inner product also loads."""
-        lay = self.apply_sealed_layout()
+        return self._apply_sealed(lib.fhe_keyswitch_apply_sealed, self.apply_sealed_layout(), ("key",), c, evk, abft, (key_seal,), add0, add1, stream)
+
+    def _apply_sealed(self, call, lay, rows, c, evk, abft, seals, add0, add1, stream):
+        """One sealed key switch: ``seals`` the seal arguments of ``call`` in its order, ``rows`` the input blocks of its flags."""
         o0, o1 = self._out(self.L), self._out(self.L)
-        f = _checked_flags(self.eng, lay["total"], lambda fl: lib.fhe_keyswitch_apply_sealed(
+        f = _checked_flags(self.eng, lay["total"], lambda fl: call(
             self.eng._h, self._h, o0.ptr, o1.ptr, c.ptr, evk.ptr, add0.ptr if add0 is not None else None, add1.ptr if add1 is not None else None,
-            abft._h, key_seal.ptr if key_seal is not None else None, fl.ptr, stream), stream)
-        flags = self._split_flags(f, lay, ("key",))
+            abft._h, *[x.ptr if x is not None else None for x in seals], fl.ptr, stream), stream)
+        flags = self._split_flags(f, lay, rows)
         flags["checked"] = self._split_flags(f, self._ks_layout(bool(self.plain_modulus)), base=lay["checked"])
         return o0, o1, flags
 
@@ -1357,14 +1359,8 @@ class KeySwitch:
         "checked": {...}}``.  Stage 0 makes no copy of ``c``: the opening inverse transform reads ``c`` itself, digests every word
         from the register its first step holds and is held against ``c_seal`` (from ``NttTables.seal``; required).  The words are
         ``apply``'s.  Not covered: the inner product's own load of ``c`` and of the plan's digits."""
-        lay = self.apply_sealed_in_layout()
-        o0, o1 = self._out(self.L), self._out(self.L)
-        f = _checked_flags(self.eng, lay["total"], lambda fl: lib.fhe_keyswitch_apply_sealed_in(
-            self.eng._h, self._h, o0.ptr, o1.ptr, c.ptr, evk.ptr, add0.ptr if add0 is not None else None, add1.ptr if add1 is not None else None,
-            abft._h, c_seal.ptr if c_seal is not None else None, key_seal.ptr if key_seal is not None else None, fl.ptr, stream), stream)
-        flags = self._split_flags(f, lay, ("c", "key"))
-        flags["checked"] = self._split_flags(f, self._ks_layout(bool(self.plain_modulus)), base=lay["checked"])
-        return o0, o1, flags
+        return self._apply_sealed(lib.fhe_keyswitch_apply_sealed_in, self.apply_sealed_in_layout(), ("c", "key"), c, evk, abft, (c_seal, key_seal), add0, add1,
+                                  stream)
 
     def rotate_sealed_in_layout(self):
         """``{"c0", "c1", "sigma_c1": (offset, (L,)), "key": (offset, (dnum, 2, M)), "checked": offset, "total": n, "fused": bool}``
@@ -1385,14 +1381,8 @@ class KeySwitch:
         return self._rotate_sealed_in(lib.fhe_rotate_sealed_in, c0, c1, galois_elt, galois_key, abft, seals, key_seal, stream)
 
     def _rotate_sealed_in(self, call, c0, c1, galois_elt, galois_key, abft, seals, key_seal, stream):
-        names = ("c0", "c1")
-        lay = self.rotate_sealed_in_layout()
-        o0, o1, so, f = self._sealed(lay, names, self.L, seals, lambda o0, o1, sin, sout, fl: call(
-            self.eng._h, self._h, o0.ptr, o1.ptr, c0.ptr, c1.ptr, galois_elt, galois_key.ptr, abft._h, sin,
-            key_seal.ptr if key_seal is not None else None, sout, fl.ptr, stream), stream)
-        flags = self._split_flags(f, lay, ("c0", "c1", "sigma_c1", "key"))
-        flags["checked"] = self._split_flags(f, self._ks_layout(bool(self.plain_modulus)), base=lay["checked"])
-        return o0, o1, so, flags
+        return self._rotate_sealed(call, c0, c1, galois_elt, galois_key, abft, seals, key_seal, stream, self.rotate_sealed_in_layout(),
+                                   ("c0", "c1", "sigma_c1"))
 
     def rotate_sealed_fused(self, c0: DeviceArray, c1: DeviceArray, galois_elt: int, galois_key: DeviceArray, abft: "Abft", seals=None,
                             key_seal: Optional[DeviceArray] = None, stream=None):

@@ -125,3 +125,59 @@ def test_hooks_that_do_not_fit_are_refused(F, eng, cases, name, tp, which):
         eng.inject_fault_subscale_sealed(-1)                                  # disarmed
         assert same(out()[0], clean[0])
     eng.check()
+
+
+class _Off:
+    """a device array's pointer moved by 8 bytes: refused for its alignment, before anything is launched"""
+
+    def __init__(self, d):
+        import ctypes
+        self.ptr = ctypes.c_void_p(d.ptr.value + 8)
+
+
+@pytest.mark.parametrize("tp", (0, 65537))
+def test_a_refused_composite_takes_every_hook_it_owns(F, eng, tp):
+    """The sweep-based composites at each refusal kind -- scope, alignment, an unpaired locator, a sealed step's hit outside the call
+    -- with every hook the call owns armed: the next valid call runs clean.  The smallest plan: N = 2^10, L = 3, K = 1, dnum = 3."""
+    from fhe_reliability_gpu_amd._lib import FheError, check, lib
+    c = SealedCase(F, eng, (10, 3, 1, 3, [50, 61, 50, 50]), seed=431, margin=16)
+    ks, ab, d, h = c.ks, c.ab, c.d, eng._h
+    locs, key_loc = [c.t.seal_locator(v, limbs=c.L) for v in d], ks.seal_key_locator(c.dk)
+    kw = dict(seals=c.seals, key_seal=c.key_seal)
+
+    def arm(tensor_row=1):
+        check((lib.fhe_ctx_inject_fault_bgv_keyswitch if tp else lib.fhe_ctx_inject_fault_keyswitch)(h, 3, 0, 1, 5, 3))
+        check((lib.fhe_ctx_inject_fault_bgv_mod_switch if tp else lib.fhe_ctx_inject_fault_rescale)(h, 1, 0, 1, 5, 3))
+        check(lib.fhe_ctx_inject_fault_pointwise(h, 0, 7, 3))
+        eng.inject_fault_tensor_sealed(2, tensor_row, 6, 3)
+        eng.inject_fault_keyswitch_sealed(c.M + 1, 4, 3)
+        eng.inject_fault_subscale_sealed(STORE, 1, 3, 3)
+
+    def out_of_scope(call):
+        eng.set_option("ntt_mode", 1)
+        try:
+            call()
+        finally:
+            eng.set_option("ntt_mode", 0)
+
+    hm_out = lambda a0=d[0]: ks.hmult_sealed_out(a0, d[1], d[2], d[3], c.dk, ab, **kw)
+    rot = lambda c0=d[0]: ks.rotate_sealed_fused(c0, d[1], GALOIS, c.dk, ab, seals=c.seals[:2], key_seal=c.key_seal)
+    repair = lambda a0=d[0], l=locs: ks.hmult_sealed_repair(a0, d[1], d[2], d[3], c.dk, ab, seals=c.seals, locators=l, key_seal=c.key_seal, key_locator=key_loc)
+    with plain_modulus(ks, tp):
+        # (the valid call, its refusals by kind): a call's own hooks are a subset of those armed
+        for valid, refusals in ((hm_out, {"two-launch": lambda: out_of_scope(hm_out), "16-byte": lambda: hm_out(_Off(d[0])), "outside the call": hm_out}),
+                                (rot, {"two-launch": lambda: out_of_scope(rot), "16-byte": lambda: rot(_Off(d[0]))}),
+                                (repair, {"two-launch": lambda: out_of_scope(repair), "16-byte": lambda: repair(_Off(d[0])),
+                                          "together": lambda: repair(l=[locs[0], None, locs[2], locs[3]])})):
+            clean = valid()
+            assert not any_raised(clean[-2] if valid is repair else clean[3])
+            for why, refused in refusals.items():
+                arm(tensor_row=c.L if why == "outside the call" else 1)
+                with pytest.raises(FheError, match=why):
+                    refused()
+                got = valid()      # the refused call took its hooks
+                assert not any_raised(got[-2] if valid is repair else got[3]), why
+                assert same(got[0], clean[0]) and same(got[1], clean[1]) and same(got[2][0], clean[2][0]) and same(got[2][1], clean[2][1])
+                hm_out()           # takes what the refused call did not own
+        assert c.unchanged()
+    eng.check()
