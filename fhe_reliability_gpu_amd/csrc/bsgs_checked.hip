@@ -12,15 +12,13 @@ namespace fhe {
 template <class D, bool HOOK>
 __device__ __forceinline__ void diag_mac_elem_checked(const DiagMacArgs &a, const BcCheck &k, u64 e, const LimbParams &p)
 {
-    const u64 part = (u64)a.limbs << a.logn;
     const u32 l = (u32)(e >> a.logn);
     const u64 i = e & (((u64)1 << a.logn) - 1);
     const PwFault f0 = fault_at<HOOK>(k, l, i), f1 = fault_at<HOOK>(k, a.limbs + l, i);
     DiagDot<D> s;
     for (u32 b = 0; b < a.n1; b++) {
-        const u64 d = a.diag[(u64)b * part + e];
-        const u64 *r = b ? a.rot + (u64)(b - 1) * 2 * part : nullptr;
-        const u64 y0 = b ? r[e] : a.x0[e], y1 = b ? r[part + e] : a.x1[e];
+        u64 d, y0, y1;
+        diag_mac_load(a, b, e, d, y0, y1);
         s.mac(d, y0, y1, b, p, f0, f1);
     }
     u64 c0, c1;

@@ -174,7 +174,7 @@ struct SealedSteps {
     // the multiply's tensor step is the sealed tensor product (tensor_sealed.hip) instead of fhe_tensor_product_checked: a0, a1, b0, b1
     // are verified on the load that multiplies them, and the call owns that step's hook (fhe_hmult_sealed_fused and above)
     const SealedTensorStep *tensor = nullptr;
-    // stage 3 is the sealed inner product (keyswitch_sealed.hip) instead of launch_ks_mac_checked: the key is verified on the load that
+    // stage 3 is the sealed inner product (mac_sealed.hip) instead of launch_ks_mac_checked: the key is verified on the load that
     // multiplies it (fhe_keyswitch_apply_sealed*, fhe_rotate_sealed_fused, _in, _out, fhe_hmult_sealed_fused_key, _out, the hoisted rotations)
     const SealedKeyStep *key = nullptr;
     // stage 0 is the sealed inverse transform (ntt_sealed.hip) out of place from d_c into the plan's coefficient buffer instead of the

@@ -1,5 +1,5 @@
-// capi_keyswitch_sealed.cpp -- the key switch with the switching key verified on the load that multiplies it (ks_seal.hpp,
-// keyswitch_sealed.hip): fhe_keyswitch_apply_sealed, its layout and its test hook (part of the C ABI of include/fhe_mi355x.h), and
+// capi_keyswitch_sealed.cpp -- the key switch with the switching key verified on the load that multiplies it (mac_seal.hpp,
+// mac_sealed.hip): fhe_keyswitch_apply_sealed, its layout and its test hook (part of the C ABI of include/fhe_mi355x.h), and
 // the sealed stage 3 behind them as a step of a composite (fhe_rotate_sealed_fused, fhe_hmult_sealed_fused_key, capi_seal.cpp).
 //
 // The sealed composites verify the key's rows in a sweep of their own and the checked key switch multiplies from a second load.
@@ -13,7 +13,7 @@
 // by the checked inner product, writing the same flag words (a key without a stored seal is then not swept at all, as in the
 // sweep-based composites; on the fused route its window is checked all the same).
 #include "capi_sealed.hpp"
-#include "ks_seal.hpp"
+#include "mac_seal.hpp"
 
 bool ks_sealed_fused(const fhe_keyswitch *p) { return p->dnum >= 1 && (u32)p->dnum <= KS_SEAL_MAX_DNUM && p->log_n >= 1; }
 

@@ -17,11 +17,10 @@ __device__ __forceinline__ void ks_mac_limb_checked(const KsMacArgs &a, const Bc
     const u64 N = (u64)1 << a.logn;
     D s0, s1;
     const PwFault f0 = fault_at<HOOK>(k, j, i), f1 = fault_at<HOOK>(k, a.M + j, i);
-    const u32 tl = j < a.cn ? a.clo + j : 0xFFFFFFFFu;     // table limb when the row is a ciphertext limb
+    const u32 tl = ks_mac_table_limb(a, j);
     for (u32 d = 0; d < a.dnum; d++) {
-        const u32 lo = d * a.alpha, hi = lo + a.alpha < a.L ? lo + a.alpha : a.L;
-        const u64 x = (tl >= lo && tl < hi) ? a.c[(u64)j * N + i] : a.ext[((u64)d * a.M + j) * N + i];
-        const u64 *key = a.evk + ((u64)d * 2 * a.M + j) * N + i;
+        u64 x;
+        const u64 *key = ks_mac_load(a, tl, d, j, i, x);
         s0.mac(x, ks_load_key(key), d, p, f0);
         s1.mac(x, ks_load_key(key + (u64)a.M * N), d, p, f1);
     }

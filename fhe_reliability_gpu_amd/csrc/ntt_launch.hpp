@@ -176,6 +176,16 @@ struct DiagMacArgs {
     u32 limb0, limbs, n1;
     int logn;
 };
+// term b at word e = (l << logn) + i as the checked and the sealed inner sum load it, each operand as a V (one word, or two adjacent
+// ones): d = the diagonal, y0 / y1 = the two parts of R_b
+template <class V> FHE_HD void diag_mac_load(const DiagMacArgs &a, u32 b, u64 e, V &d, V &y0, V &y1)
+{
+    const u64 part = (u64)a.limbs << a.logn;
+    d = *reinterpret_cast<const V *>(a.diag + ((u64)b * part + e));
+    const u64 *r = b ? a.rot + (u64)(b - 1) * 2 * part : nullptr;
+    y0 = b ? *reinterpret_cast<const V *>(r + e) : *reinterpret_cast<const V *>(a.x0 + e);
+    y1 = b ? *reinterpret_cast<const V *>(r + (part + e)) : *reinterpret_cast<const V *>(a.x1 + e);
+}
 hipError_t launch_diag_mac(hipStream_t st, const DiagMacArgs &a);
 hipError_t launch_modadd(hipStream_t st, const PointwiseArgs &p);
 hipError_t launch_modsub(hipStream_t st, const PointwiseArgs &p);
@@ -276,6 +286,18 @@ struct KsMacArgs {
     int logn;
     u32 cn, clo, sp_shift;
 };
+// the table limb of row j when it is a ciphertext limb (no limb otherwise): a row's own invariant, hoisted by the caller
+FHE_HD u32 ks_mac_table_limb(const KsMacArgs &a, u32 j) { return j < a.cn ? a.clo + j : 0xFFFFFFFFu; }
+// term d at word i of row j (table limb tl) as the checked and the sealed inner product load it: x = the digit as a V (one word, or
+// two adjacent ones) -- from the owned limb of c where the row is a ciphertext limb of the digit's own range, from the digit's
+// extension elsewhere -- and the address of half 0 of the key (half 1: M N words on), which each kernel loads in its own way
+template <class V> FHE_HD const u64 *ks_mac_load(const KsMacArgs &a, u32 tl, u32 d, u32 j, u64 i, V &x)
+{
+    const u64 N = (u64)1 << a.logn;
+    const u32 lo = d * a.alpha, hi = lo + a.alpha < a.L ? lo + a.alpha : a.L;
+    x = (tl >= lo && tl < hi) ? *reinterpret_cast<const V *>(a.c + ((u64)j * N + i)) : *reinterpret_cast<const V *>(a.ext + (((u64)d * a.M + j) * N + i));
+    return a.evk + ((u64)d * 2 * a.M + j) * N + i;
+}
 hipError_t launch_ks_mac(hipStream_t st, const KsMacArgs &a);
 // n <= 4 keys on the same digits: acc[r] = sum_d ext_d * evk[r][d] (a.acc / a.evk unused)
 struct KsMacMultiArgs {
@@ -385,15 +407,15 @@ size_t carry_part_words(u32 units, int logn, bool loc);
 hipError_t launch_modadd_carry(hipStream_t st, const PointwiseArgs &p, bool sub, u64 *part, const u64 *seal_a, const u64 *seal_b, u64 *seal_c,
                                const u64 *loc_a, const u64 *loc_b, u64 *loc_c, const BcCheck &k);
 
-// ---- bsgs_sealed.hip: the inner sum of the BSGS product with the diagonals' seals verified on the consuming load (bsgs_seal.hpp) ----
+// ---- mac_sealed.hip: the inner sum of the BSGS product with the diagonals' seals verified on the consuming load (mac_seal.hpp) ----
 // the compile-time bound on the baby steps the launch picks for n1 <= DIAG_SEAL_MAX_NB: the smallest of 4, 8, 16 that holds n1
 u32 diag_seal_nb(u32 n1);
-// words of the partial-sum scratch a launch needs: [limbs][chunks per row][nb][2]
+// words of the partial-sum scratch a launch needs: room for [limbs][chunks per row][nb][2], of which a job writes [n1][2]
 size_t diag_seal_part_words(u32 limbs, int logn, u32 nb);
 // launch_diag_mac_checked's words and flags (k) with every buffer of a 16-byte aligned, logn >= 1 and n1 <= DIAG_SEAL_MAX_NB;
 // seal = [n1 * limbs][2] the stored seals of this giant step's diagonal rows (row b * limbs + l); seal_flags[b * limbs + l] |=
 // SEAL_SUM where the row as loaded differs from its seal, SEAL_RANGE where a word is >= q_l; zeroed by the caller.  hit.mask != 0:
-// the sealed call's test fault, in the register as loaded
+// the sealed call's test fault, in the register as loaded (bsgs_seal.hpp)
 struct DiagHit;
 hipError_t launch_diag_mac_sealed(hipStream_t st, const DiagMacArgs &a, u64 *part, const u64 *seal, u32 *seal_flags, const BcCheck &k, const DiagHit &hit);
 
@@ -427,7 +449,7 @@ size_t tensor_seal_part_words(u32 units, int logn, bool out);
 // of row fault_unit
 hipError_t launch_tensor_sealed(hipStream_t st, const TensorSealArgs &t, u64 *part, const BcCheck &k, const TensorSealHit &hit);
 
-// ---- keyswitch_sealed.hip: the key switch's inner product with the key's seal verified on the multiplying load (ks_seal.hpp) ----
+// ---- mac_sealed.hip: the key switch's inner product with the key's seal verified on the multiplying load (mac_seal.hpp) ----
 // the sealed call's test fault as a launch reads it: XOR mask into word coeff of key row key_row = (d 2 + h) M + j, in the register
 // as loaded (mask == 0: not armed)
 struct KsSealHit {

@@ -90,7 +90,7 @@ FHE_HD u64 seal_canonical(u64 s)
 FHE_HD bool seal_differs(u64 s0, u64 s1, const u64 *stored) { return seal_canonical(s0) != stored[0] || seal_canonical(s1) != stored[1]; }
 
 // what one lane (one chunk, one row) of a fused sweep has digested of N operand rows it reads side by side (the diagonals of
-// bsgs_seal.hpp, the key rows of ks_seal.hpp): the two sums of each and the window bits
+// BSGS inner sum, the key rows of the key switch: mac_seal.hpp): the two sums of each and the window bits
 template <int N> struct SealRows {
     static constexpr int WORDS = 2 * N;
     SealAcc acc[N];

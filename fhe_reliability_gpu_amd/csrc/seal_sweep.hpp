@@ -1,5 +1,5 @@
 // seal_sweep.hpp -- the chunked row sweep the seal kernels share (seal_checked.hip, seal_repair.hip, seal_carry.hip,
-// galois_sealed.hip, tensor_sealed.hip, bsgs_sealed.hip, keyswitch_sealed.hip): the job loop, the workgroup combine, the finish
+// galois_sealed.hip, tensor_sealed.hip, subscale_sealed.hip, mac_sealed.hip): the job loop, the workgroup combine, the finish
 // kernels' merge and the two launches.  Device side only; the arithmetic of every kernel stays in its own header.
 //
 // A row of 2^logn words is cut into chunks of 2^SEAL_LOG_CHUNK words (a whole row below that) and the (row, chunk) jobs are spread
@@ -34,8 +34,8 @@ template <class Acc> __device__ __forceinline__ void seal_wave_step(Acc &acc, in
     seal_each<0, Acc::WORDS>([&](auto ic) { other[decltype(ic)::value] = __shfl_xor(acc.get(decltype(ic)::value), o); });
     acc.merge(other);
 }
-// the same row by row: with all 2 N words gathered before the first merge the compiler holds k_ks_mac_sealed<8> and
-// k_diag_mac_sealed<16> in 249 VGPRs instead of 235, and k_ks_mac_sealed<12> in 40 AGPRs instead of 22
+// the same row by row: with all 2 N words gathered before the first merge the compiler holds k_mac_sealed<KsSweep, 8> and
+// k_mac_sealed<DiagSweep, 16> in 249 VGPRs instead of 235, and k_mac_sealed<KsSweep, 12> in 40 AGPRs instead of 22
 template <int N> __device__ __forceinline__ void seal_wave_step(SealRows<N> &g, int o)
 {
     seal_each<0, N>([&](auto rc) {

@@ -1,6 +1,7 @@
 """Measurement tool: what verifying the diagonals on the load that multiplies them costs.  Timed with HIP events on one stream after
 a warm-up, several rounds alternating in one process, on resident data.  50-bit ciphertext primes with 61-bit special primes, at
-BASELINE config 4 (N = 2^17, L = 32, K = 8, dnum = 4) and config 5 (N = 2^16, L = 44, K = 11, dnum = 4) with n1 = n2 = 8.
+BASELINE config 4 (N = 2^17, L = 32, K = 8, dnum = 4) and config 5 (N = 2^16, L = 44, K = 11, dnum = 4) with n1 = n2 = 8; config 16
+(N = 2^15, L = 8, K = 2, dnum = 2, n1 = 16, n2 = 2) reaches the inner sum's widest instantiation.
   (a) fhe_bsgs_matvec_sealed with every seal given, next to fhe_bsgs_matvec_checked and next to the four-part composition it
       replaces: fhe_seal_verify of c0, c1, every key and all diagonals, fhe_bsgs_matvec_checked, fhe_seal of both outputs.
   (b) the per-giant-step kernel pair on its own.  Neither has an entry point, so each is timed as a difference inside the same
@@ -11,7 +12,7 @@ BASELINE config 4 (N = 2^17, L = 32, K = 8, dnum = 4) and config 5 (N = 2^16, L 
       reported, not promised.  The difference of two timed loops carries the noise of both, which the per-round figures show.
 Before timing, the sealed call's words and output seals are held against the composition's on the same operands.
 Reported, not gated.
-python -m fhe_reliability_gpu_amd.tools.bsgs_sealed_rate [--config 4|5]"""
+python -m fhe_reliability_gpu_amd.tools.bsgs_sealed_rate [--config 4|5|16]"""
 import ctypes as C
 
 import torch
@@ -33,7 +34,7 @@ timed = lambda fn, reps: _rate.timed(fn, reps, s)
 
 _rate.print_device()
 summary = []
-for cfg, logn, L, K, dnum, n1, n2 in _rate.configs(((4, 17, 32, 8, 4, 8, 8), (5, 16, 44, 11, 4, 8, 8))):
+for cfg, logn, L, K, dnum, n1, n2 in _rate.configs(((4, 17, 32, 8, 4, 8, 8), (5, 16, 44, 11, 4, 8, 8), (16, 15, 8, 2, 2, 16, 2))):
     N, M = 1 << logn, L + K
     kr = dnum * 2 * M
     qs, t, ks, ab = _rate.plan(eng, logn, L, K, dnum)

@@ -1,7 +1,8 @@
 """Measurement tool: what verifying the switching key on the load that multiplies it costs.  Timed with HIP events on one stream
 after a warm-up, several rounds alternating in one process at one commit, on resident data.  50-bit ciphertext primes with 61-bit
 special primes at BASELINE config 4 (N = 2^17, L = 32, K = 8, dnum = 4) and config 5 (N = 2^16, L = 44, K = 11, dnum = 4); the
-reference's shape (N = 2^14, six 50-bit primes of which two special: L = 4, K = 2, dnum = 2, plain modulus 65537) in the BGV form.
+reference's shape (N = 2^14, six 50-bit primes of which two special: L = 4, K = 2, dnum = 2, plain modulus 65537) in the BGV form;
+configs 8 and 12 (N = 2^15, K = 2, L = 16 / 24, dnum = 8 / 12) reach the inner product's two widest instantiations.
   (a) fhe_keyswitch_apply_sealed next to the composition it replaces: fhe_seal_verify over the key's rows + fhe_keyswitch_apply_checked;
   (b) fhe_rotate_sealed_fused against fhe_rotate_sealed, every seal given;
   (c) fhe_hmult_sealed_fused_key against fhe_hmult_sealed_fused, rescale on, every seal given;
@@ -11,7 +12,7 @@ Every fused call reads the key once where its baseline reads it twice: dnum 2 M 
 far run bound by integer work, not by bytes, and the fused BSGS inner sum turned out slower than its composition: the ratios are
 reported, not promised, and none is a pass condition.
 Before timing, the fused calls' words, output seals and flags are held against their baselines' on the same operands.
-python -m fhe_reliability_gpu_amd.tools.keyswitch_sealed_rate [--config 4|5|14]"""
+python -m fhe_reliability_gpu_amd.tools.keyswitch_sealed_rate [--config 4|5|14|8|12]"""
 import ctypes as C
 
 import torch
@@ -34,7 +35,7 @@ timed = lambda fn, reps: _rate.timed(fn, reps, s)
 
 _rate.print_device()
 summary = []
-for cfg, logn, L, K, dnum, tp in _rate.configs():
+for cfg, logn, L, K, dnum, tp in _rate.configs(_rate.CONFIGS + ((8, 15, 16, 2, 8, 0), (12, 15, 24, 2, 12, 0))):
     N, M = 1 << logn, L + K
     qs, t, ks, ab = _rate.plan(eng, logn, L, K, dnum, tp)
     rnd, u64, i32 = _rate.factories(min(qs))

@@ -29,7 +29,7 @@ takes.  Nothing asserts the launcher's rule: a launcher may change its cap, the 
   k_row_digest (seal, verify), k_row_locator                    8192 jobs      1 (row, chunk) job per workgroup
   k_modadd_carry, k_automorphism_ntt_sealed, k_tensor_sealed    8192 jobs      1 (row, chunk) job per workgroup; their long cases are
                                                                                test_the_job_loop_takes_a_second / a_fourth_trip of their own files
-  k_diag_mac_sealed, k_ks_mac_sealed                            8192 jobs      not listed: their rows are limbs, a few dozen at most, times
+  k_mac_sealed (both families)                                  8192 jobs      not listed: their rows are limbs, a few dozen at most, times
                                                                                at most 16 chunks -- no plan reaches the cap
   k_row_repair                                                  2048 rows      1 row per workgroup
 """

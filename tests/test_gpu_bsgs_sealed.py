@@ -108,9 +108,9 @@ def _sums(row):
 
 
 # a row shorter than a workgroup; NB = 4 with one term; the edge of NB = 4; the first n1 of NB = 8 on two arithmetic paths; two chunks
-# per row (the weight is the ROW index); the first n1 of NB = 16; its edge; the fallback route
+# per row (the weight is the ROW index); the edge of NB = 8; the first n1 of NB = 16; its edge; the fallback route
 CLEAN = [(5, 2, 1, 2, 2, 2, "50"), (10, 3, 1, 3, 1, 2, "mixed"), (10, 3, 1, 3, 4, 2, "50/50"), (13, 4, 2, 2, 5, 2, "mixed"), (14, 2, 1, 2, 3, 2, "61"),
-         (8, 2, 1, 2, 9, 2, "mixed"), (8, 2, 1, 1, 16, 1, "mixed"), (8, 2, 1, 1, 17, 2, "mixed")]
+         (8, 2, 1, 1, 8, 1, "mixed"), (8, 2, 1, 2, 9, 2, "mixed"), (8, 2, 1, 1, 16, 1, "mixed"), (8, 2, 1, 1, 17, 2, "mixed")]
 
 
 @pytest.mark.parametrize("logn,L,K,dnum,n1,n2,kind", CLEAN)
@@ -237,12 +237,12 @@ def test_a_diagonal_word_out_of_range_raises_range_and_sum_and_bit_4_on_both_par
     eng.check()
 
 
-def test_the_hook_on_the_consuming_load_raises_the_row_and_not_the_residue_check(F, eng):
+def _hook_on_the_consuming_load(F, eng, shape, seed, words):
     from fhe_reliability_gpu_amd._lib import check, lib
-    logn, L, K, dnum, n1, n2 = 10, 3, 1, 3, 3, 2
-    c = _Case(F, eng, logn, L, K, dnum, n1, n2, "mixed", 21)
+    logn, L, K, dnum, n1, n2 = shape
+    c = _Case(F, eng, logn, L, K, dnum, n1, n2, "mixed", seed)
     want = c.plain()
-    for g, b, limb, j in ((0, 0, 0, 0), (1, 2, 1, c.N - 1), (1, 1, 2, 513)):
+    for g, b, limb, j in words:
         word = int(c.diags[g, b, limb, j])
         bit = max(i for i in range(61) if word >> i & 1)          # a bit that is SET: the flipped word stays below q
         assert word ^ (1 << bit) < c.qs[limb]
@@ -271,6 +271,15 @@ def test_the_hook_on_the_consuming_load_raises_the_row_and_not_the_residue_check
     o0, o1, so, fl = c.sealed()
     assert _raised(fl) == {}
     eng.check()
+
+
+def test_the_hook_on_the_consuming_load_raises_the_row_and_not_the_residue_check(F, eng):
+    _hook_on_the_consuming_load(F, eng, (10, 3, 1, 3, 3, 2), 21, ((0, 0, 0, 0), (1, 2, 1, (1 << 10) - 1), (1, 1, 2, 513)))
+
+
+def test_the_hook_on_the_consuming_load_at_sixteen_baby_steps(F, eng):
+    """the hooked form of the widest instantiation: the first and the last diagonal of a giant step, and one between"""
+    _hook_on_the_consuming_load(F, eng, (8, 2, 1, 1, 16, 2), 23, ((0, 0, 0, 0), (1, 15, 1, (1 << 8) - 1), (1, 7, 0, 129)))
 
 
 def test_the_hook_on_the_fallback_route_lives_in_the_verifying_sweep(F, eng):

@@ -4,7 +4,8 @@ the sweep-based calls', word for word.  What only the fused calls can see: a fau
 
 Plans (logn, L, K, dnum): A (10, 4, 2, 2); B (13, 3, 1, 3) with a 61-bit prime among 50-bit ones; C (14, 6, 2, 3), two chunks per row;
 D (10, 13, 1, 13), one digit more than the fused kernel is instantiated for: the sweep followed by the checked inner product.  Each
-without and with plain modulus 65537.  Operands and key words are drawn from [16, q - 16), so that bit-3 flips stay below q."""
+without and with plain modulus 65537.  E to H (5, d, 1, d) for d = 5, 8, 9, 12, a 61-bit prime among 50-bit ones: both edges of the
+instantiations for up to 8 and up to 12 digits, in the clean, the at-rest and the multiplying-load tests, without plain modulus.  Operands and key words are drawn from [16, q - 16), so that bit-3 flips stay below q."""
 import ctypes as C
 
 import numpy as np
@@ -19,6 +20,8 @@ SUM, RANGE = 1, 2
 GARBAGE = 0x5A5A5A5A5A5A5A5A
 PLANS = plans("ABCD")
 PARAMS = [(name, tp) for name in PLANS for tp in (0, 65537)]
+BANDS = [(name, 0) for name in "EFGH"]
+PLANS.update(plans("EFGH"))
 FUSED = [(name, tp) for name, tp in PARAMS if name != "D"]
 GALOIS = 5
 
@@ -71,7 +74,7 @@ def swept_apply(c, tp, key_seal=None):
     return o0, o1, {"key": np.asarray(kf).reshape(c.dnum, 2, c.M), "checked": cf}
 
 
-@pytest.mark.parametrize("name,tp", PARAMS)
+@pytest.mark.parametrize("name,tp", PARAMS + BANDS)
 def test_clean_words_flags_and_seals_are_the_sweep_based_calls(F, eng, cases, name, tp):
     c = cases(name)
     ks, ab = c.ks, c.ab
@@ -104,7 +107,7 @@ def test_clean_words_flags_and_seals_are_the_sweep_based_calls(F, eng, cases, na
     eng.check()
 
 
-@pytest.mark.parametrize("name,tp", PARAMS)
+@pytest.mark.parametrize("name,tp", PARAMS + BANDS)
 def test_corruptions_at_rest_in_the_key_give_the_sweep_based_calls_flags_and_words(F, eng, cases, name, tp):
     c = cases(name)
     ks, ab, N = c.ks, c.ab, c.N
@@ -145,7 +148,7 @@ def test_corruptions_at_rest_in_the_key_give_the_sweep_based_calls_flags_and_wor
     eng.check()
 
 
-@pytest.mark.parametrize("name,tp", FUSED)
+@pytest.mark.parametrize("name,tp", FUSED + BANDS)
 def test_a_fault_on_the_multiplying_load_is_seen_by_the_fused_calls_only(F, eng, cases, name, tp):
     c = cases(name)
     ks, ab, N = c.ks, c.ab, c.N
