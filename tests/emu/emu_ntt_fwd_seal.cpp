@@ -35,7 +35,7 @@ int dispatch_io(int logn, bool inverse, const u64 *src, u64 *dst, const Limb &L,
         if (inverse) emu_transform<A, LG, true>(src, dst, L, hit_coeff, hit_bit, o); \
         else emu_transform<A, LG, false>(src, dst, L, hit_coeff, hit_bit, o);    \
         return 0;
-        CASE(5) CASE(12) CASE(13) CASE(14)
+        CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10) CASE(11) CASE(12) CASE(13) CASE(14) CASE(15) CASE(16) CASE(17) CASE(18) CASE(19) CASE(20)
 #undef CASE
     default: return -1;
     }

@@ -40,10 +40,23 @@ struct Limb {
         auto enc = [&](u64 w) { return path == PATH_F64 ? ArithF64::encode(w, q) : ArithU64::encode(w, q); };
         fwd.resize(N);
         inv.resize(N);
+        // the table's inverses by one invmod (prefix products, inverted once and peeled back): 2^20 entries in milliseconds
+        auto mul = [&](u64 a, u64 b) { return (u64)((unsigned __int128)a * b % q); };
+        std::vector<u64> pre(N), rinv(N);
+        u64 acc = 1;
+        for (size_t k = 0; k < N; k++) {
+            pre[k] = acc;
+            acc = mul(acc, rp[k]);
+        }
+        u64 ia = invmod(acc, q);
+        for (size_t k = N; k-- > 0;) {
+            rinv[k] = mul(ia, pre[k]);
+            ia = mul(ia, rp[k]);
+        }
         for (size_t k = 0; k < N; k++) {
             const u32 at = tw_stored_index(logn, (u32)k);
             fwd[at] = enc(rp[k]);
-            inv[at] = enc(invmod(rp[k], q));
+            inv[at] = enc(rinv[k]);
         }
         const u64 ni = invmod(N % q, q);
         inv[0] = enc((u64)((unsigned __int128)ni * invmod(rp[N > 1 ? 1 : 0], q) % q));
@@ -180,7 +193,7 @@ int dispatch(int logn, const u64 *src, u64 *dst, const Limb &L, int mode, long l
 {
     switch (logn) {
 #define CASE(LG) case LG: return emu_size<A, LG>(src, dst, L, mode, hit_coeff, hit_bit, parts, sum_in);
-        CASE(5) CASE(10) CASE(13) CASE(14)
+        CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10) CASE(11) CASE(12) CASE(13) CASE(14) CASE(15) CASE(16) CASE(17) CASE(18) CASE(19) CASE(20)
 #undef CASE
     default: return -1;
     }

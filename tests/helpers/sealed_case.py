@@ -8,9 +8,13 @@ CAP = 12      # digits the fused inner product is instantiated for
 # name: (logn, L, K, dnum, limb bits).  A: a row shorter than a chunk; B: a 61-bit prime among 50-bit ones, one chunk per row; C: the
 # reference's shape, two chunks per row; D: one digit above the fused cap; E to H: both edges of the fused inner product's two widest
 # instantiations (5 to 8 digits, 9 to 12), at the smallest N the checked key switch takes, alpha = 1 and a 61-bit prime among 50-bit
-# ones, so that both arithmetic paths run in one launch.  Each file names the subset it runs.
+# ones, so that both arithmetic paths run in one launch; I to K: 4, 8 and 16 chunks of 2^13 words per row -- the sealed inner product's
+# sweep over more than two chunks and its finish merging 4, 8 and 16 partials -- with a 61-bit prime among 50-bit ones, two and one
+# term per digit.  Each file names the subset it runs.
 PLANS = {"A": (10, 4, 2, 2, [50] * 6), "B": (13, 3, 1, 3, [50, 61, 50, 50]), "C": (14, 6, 2, 3, [50] * 8), "D": (10, CAP + 1, 1, CAP + 1, [50] * (CAP + 2))}
 PLANS.update({name: (5, d, 1, d, [50, 61] + [50] * (d - 1)) for name, d in (("E", 5), ("F", 8), ("G", 9), ("H", 12))})
+PLANS.update({"I": (15, 2, 1, 2, [50, 61, 50]), "J": (16, 2, 1, 2, [50, 61, 50]), "K": (17, 2, 1, 1, [50, 61, 50])})
+CHUNK = 1 << 13      # words of one chunk of the sealed row sweeps
 
 
 def plans(names):

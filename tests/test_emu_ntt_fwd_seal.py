@@ -2,7 +2,12 @@
 compiles ntt_seal_tap.hpp with the very pass templates k_ntt_pass_sealed_io instantiates): the digest the loading launch forms is
 the seal of the source whatever the tile order, the digest the storing launch forms is the seal of the row as stored, every
 single-word change the seal promises to catch is caught on the load, the hooked tap changes words and digests together, and the
-poison rule gives a raised row a seal that no verifier accepts -- without a GPU."""
+poison rule gives a raised row a seal that no verifier accepts -- without a GPU.
+
+Every size 2^5 .. 2^20, both arithmetic paths, both directions.  Tiles per row (tiles()): one below 2^13; from there on the row
+pass has N // 4096 and the column pass (1 << (logn - PC)) // 16 -- 16-column tiles of the 2^(logn - PC) columns, PC the stages of
+the column plan of ntt_plan.hpp: PC = 5, 6, 7 at 2^13, 2^14, 2^15 and 8 from 2^16 on.  The forward transform loads with its column
+pass and stores with its row pass, the inverse the other way round.  From 2^15 on a case samples its words and bits."""
 import ctypes as C
 
 import numpy as np
@@ -10,16 +15,28 @@ import pytest
 
 from helpers.emu_build import build_emu
 from helpers.sealed_case import py_seals
+from helpers.sealed_ntt_runs import pow2_words
 from oracle import cport as O
 
 p64 = C.POINTER(C.c_uint64)
 P = (1 << 61) - 1
 SEAL_SUM, SEAL_RANGE = 1, 2
 POISON = (1 << 64) - 1
-SIZES = [5, 12, 13, 14]
+SIZES = list(range(5, 21))
 PATHS = [(0, 50), (1, 61)]
-# (tiles of the loading launch, tiles of the storing launch): 16-column tiles of 2^8 columns, 16-row tiles of 2^5 / 2^6 rows
-TILES = {False: {5: (1, 1), 12: (1, 1), 13: (16, 2), 14: (16, 4)}, True: {5: (1, 1), 12: (1, 1), 13: (2, 16), 14: (4, 16)}}
+SAMPLED = 15      # from this size on: fewer words and bits per case
+MAX_TILES = 256
+PC = {13: 5, 14: 6, 15: 7, 16: 8, 17: 8, 18: 8, 19: 8, 20: 8}
+
+
+def tiles(logn, inv):
+    """(tiles of the loading launch, tiles of the storing launch) per row: the plan's formula"""
+    if logn < 13:
+        return 1, 1
+    col, row = (1 << (logn - PC[logn])) // 16, (1 << logn) // 4096
+    return (row, col) if inv else (col, row)
+
+
 GRID = [(logn, path, bits, inv) for logn in SIZES for path, bits in PATHS for inv in (False, True)]
 FWD = [g[:3] for g in GRID if not g[3]]
 
@@ -71,7 +88,7 @@ def run(emu, c, src, inv=False, hit=(-1, 0)):
     """(dst, parts_in [tin][3], parts_out [tout][2], (sum_in, sum_out)) of the sealed transform out of place from src"""
     src = np.ascontiguousarray(src, dtype=np.uint64)
     dst = np.zeros(c.N, dtype=np.uint64)
-    pin, pout = np.zeros(3 * 64, dtype=np.uint64), np.zeros(2 * 64, dtype=np.uint64)
+    pin, pout = np.zeros(3 * MAX_TILES, dtype=np.uint64), np.zeros(2 * MAX_TILES, dtype=np.uint64)
     sums = np.zeros(2, dtype=np.uint64)
     tiles = (C.c_int * 2)()
     rc = emu.emu_ntt_sealed_io(int(inv), src.ctypes.data_as(p64), dst.ctypes.data_as(p64), c.logn, c.q, c.rp.ctypes.data_as(p64), c.w_hat.ctypes.data_as(p64),
@@ -104,7 +121,7 @@ def finish_out(emu, parts, flag_in=0, flag_abft=0, order=None):
 def test_clean_row_both_digests_are_the_seals_in_any_tile_order(emu, logn, path, bits, inv):
     c = case(logn, path, bits)
     dst, pin, pout, sums = run(emu, c, c.x, inv)
-    assert (len(pin), len(pout)) == TILES[inv][logn]
+    assert (len(pin), len(pout)) == tiles(logn, inv)
     want = oracle(c, c.x, inv)
     assert (dst == want).all()
     seal_dst = tuple(py_seals(want)[0])
@@ -124,8 +141,8 @@ def test_clean_row_both_digests_are_the_seals_in_any_tile_order(emu, logn, path,
 @pytest.mark.parametrize("logn,path,bits", FWD)
 def test_single_bit_changes_move_the_sums_and_bit_63_raises_the_window(emu, logn, path, bits):
     c = case(logn, path, bits)
-    for j in (0, c.N // 2 + 1, c.N - 1):
-        for bit in (0, 40, 63):
+    for i, j in enumerate((0, c.N // 2 + 1, c.N - 1)):
+        for bit in ((0, 40, 63) if logn < SAMPLED else (0, 40, 63)[i:i + 1]):
             y = c.x.copy()
             y[j] ^= np.uint64(1 << bit)
             dst, pin, pout, _ = run(emu, c, y)
@@ -174,7 +191,7 @@ def test_hooked_tap_changes_words_and_digests_together(emu, logn, path, bits, in
         assert bool(f & SEAL_RANGE) == (int(y[j]) >= c.q)
 
 
-@pytest.mark.parametrize("logn,path,bits", FWD[:2] + FWD[-2:])
+@pytest.mark.parametrize("logn,path,bits", [f for f in FWD if f[0] in (5, 14, 20)])      # the smallest size, two launches, the largest
 def test_poison_rule(emu, logn, path, bits):
     c = case(logn, path, bits)
     _, _, pout, _ = run(emu, c, c.x)
@@ -191,3 +208,22 @@ def test_poison_rule(emu, logn, path, bits):
         assert emu.emu_seal_differs(s0, s1, poison.ctypes.data_as(p64)) == 1
     assert emu.emu_seal_differs(canonical[0], canonical[1], ok.ctypes.data_as(p64)) == 0
     assert emu.emu_seal_differs(canonical[0] + P, canonical[1], ok.ctypes.data_as(p64)) == 0      # a lazily reduced digest of the same residue
+
+
+@pytest.mark.parametrize("logn,path,bits,inv", [g for g in GRID if g[0] < 18])
+def test_hook_on_both_sides_of_every_power_of_two_moves_the_digest_by_that_words_weight(emu, logn, path, bits, inv):
+    """The words 2^k - 1 and 2^k for every k and N - 1 hold both sides of the first edge of any tile size, column tiles included.
+    Bit 3 flipped in word j on the load moves S0 by d = +-8 and S1 by (j + 1) d: the weight names the word, so the input digest
+    proves that the hook hit word j of its tile and no other, and the output digest is the seal of the transform of that row.
+    Below 2^18, where a case stays within a few seconds; test_gpu_sealed_sizes.py holds every size on the device."""
+    c = case(logn, path, bits)
+    for j in pow2_words(logn):
+        dst, pin, pout, _ = run(emu, c, c.x, inv, hit=(j, 3))
+        d = -8 if int(c.x[j]) & 8 else 8
+        f, got = finish_in(emu, pin, c.seal)
+        assert got == ((c.seal[0] + d) % P, (c.seal[1] + (j + 1) * d) % P) and f == SEAL_SUM, j
+        if logn < SAMPLED:
+            y = c.x.copy()
+            y[j] ^= np.uint64(8)
+            want = oracle(c, y, inv)
+            assert (dst == want).all() and finish_out(emu, pout) == tuple(py_seals(want)[0]), j

@@ -5,13 +5,15 @@ the sweep-based calls', word for word.  What only the fused calls can see: a fau
 Plans (logn, L, K, dnum): A (10, 4, 2, 2); B (13, 3, 1, 3) with a 61-bit prime among 50-bit ones; C (14, 6, 2, 3), two chunks per row;
 D (10, 13, 1, 13), one digit more than the fused kernel is instantiated for: the sweep followed by the checked inner product.  Each
 without and with plain modulus 65537.  E to H (5, d, 1, d) for d = 5, 8, 9, 12, a 61-bit prime among 50-bit ones: both edges of the
-instantiations for up to 8 and up to 12 digits, in the clean, the at-rest and the multiplying-load tests, without plain modulus.  Operands and key words are drawn from [16, q - 16), so that bit-3 flips stay below q."""
+instantiations for up to 8 and up to 12 digits, in the clean, the at-rest and the multiplying-load tests, without plain modulus.
+I (15, 2, 1, 2), J (16, 2, 1, 2), K (17, 2, 1, 1), a 61-bit prime among 50-bit ones: 4, 8 and 16 chunks per row -- stage 0 above
+2^14, the sealed inner product over more than two chunks, its finish merging 4, 8 and 16 partials -- in the same three tests.  Operands and key words are drawn from [16, q - 16), so that bit-3 flips stay below q."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
-from helpers.sealed_case import CAP, SealedCase, case_cache, flat, flip, plain_modulus, plans, py_seals, raised, same, same_call
+from helpers.sealed_case import CAP, CHUNK, SealedCase, case_cache, flat, flip, plain_modulus, plans, py_seals, raised, same, same_call
 
 pytestmark = pytest.mark.gpu
 
@@ -20,8 +22,8 @@ SUM, RANGE = 1, 2
 GARBAGE = 0x5A5A5A5A5A5A5A5A
 PLANS = plans("ABCD")
 PARAMS = [(name, tp) for name in PLANS for tp in (0, 65537)]
-BANDS = [(name, 0) for name in "EFGH"]
-PLANS.update(plans("EFGH"))
+BANDS = [(name, 0) for name in "EFGHIJK"]
+PLANS.update(plans("EFGHIJK"))
 FUSED = [(name, tp) for name, tp in PARAMS if name != "D"]
 GALOIS = 5
 
@@ -55,11 +57,15 @@ class Case(SealedCase):
 
     def key_words(self):
         """(key row, word): the key's first word, both sides of a chunk edge (of the row's middle below two chunks), the last word of
-        the last special limb of the last digit's half 1, and a word of a row inside its digit's own limb range"""
-        edge = (1 << 13) if self.logn > 13 else self.N // 2
+        the last special limb of the last digit's half 1, and a word of a row inside its digit's own limb range; above two chunks per
+        row also both sides of the last chunk edge"""
+        edge = CHUNK if self.logn > 13 else self.N // 2
         d = self.dnum - 1
         own = min(d * self.alpha, self.L - 1)
-        return [(0, 0), (self.key_row(0, 1, 1), edge - 1), (self.key_row(d // 2, 0, self.M - 1), edge), (self.rows - 1, self.N - 1), (self.key_row(d, 0, own), 9)]
+        out = [(0, 0), (self.key_row(0, 1, 1), edge - 1), (self.key_row(d // 2, 0, self.M - 1), edge), (self.rows - 1, self.N - 1), (self.key_row(d, 0, own), 9)]
+        if self.N > 2 * CHUNK:
+            out += [(self.key_row(d, 1, 0), self.N - CHUNK - 1), (self.key_row(0, 0, self.M - 1), self.N - CHUNK)]
+        return out
 
 
 @pytest.fixture(scope="module")
@@ -161,7 +167,9 @@ def test_a_fault_on_the_multiplying_load_is_seen_by_the_fused_calls_only(F, eng,
             "hmult": (lambda: ks.hmult_sealed_fused(*c.d, c.dk, ab, **hk), lambda: ks.hmult_sealed_fused_key(*c.d, c.dk, ab, **hk)),
         }
         words = c.key_words()
-        for (what, (swept, fused)), (row, j) in zip(calls.items(), (words[4], words[2], words[3])):
+        # above two chunks per row: the apply call's hook on both sides of the last chunk edge as well
+        hooked = list(zip(calls.items(), (words[4], words[2], words[3]))) + [(("apply", calls["apply"]), w) for w in words[5:]]
+        for (what, (swept, fused)), (row, j) in hooked:
             clean = fused()
             assert raised(clean[-1]) == []
             eng.inject_fault_keyswitch_sealed(row, j, 3)

@@ -5,7 +5,8 @@ row's seal word while the ABFT identity, formed from the word as loaded, stays s
 
 Plans (logn, L, K, dnum) as test_gpu_keyswitch_sealed.py: A (10, 4, 2, 2), one launch and one tile per row; B (13, 3, 1, 3) with a
 61-bit prime among 50-bit ones, two tiles per row; C (14, 6, 2, 3), four tiles per row.  Each composite without and with plain
-modulus 65537.  Operands are drawn from [16, q - 16), so that bit-3 flips stay below q."""
+modulus 65537.  I (15, 2, 1, 2), J (16, 2, 1, 2), K (17, 2, 1, 1) with a 61-bit prime among 50-bit ones -- stage 0 above 2^14 and a
+key of 4, 8 and 16 chunks per row -- through the composites' clean and at-rest tests, without plain modulus.  Operands are drawn from [16, q - 16), so that bit-3 flips stay below q."""
 import ctypes as C
 
 import numpy as np
@@ -21,6 +22,8 @@ GARBAGE = 0x5A5A5A5A5A5A5A5A
 PLANS = plans("ABC")
 NAMES = list(PLANS)
 PARAMS = [(name, tp) for name in PLANS for tp in (0, 65537)]
+BIG = [(name, 0) for name in "IJK"]
+PLANS.update(plans("IJK"))
 GALOIS = 5
 TILE = 4096      # words per (row, tile) of the two-launch sizes' first launch
 
@@ -214,7 +217,7 @@ def swept_apply(c, tp):
     return o0, o1, {"c": np.asarray(cf), "key": fl["key"], "checked": fl["checked"]}
 
 
-@pytest.mark.parametrize("name,tp", PARAMS)
+@pytest.mark.parametrize("name,tp", PARAMS + BIG)
 def test_apply_sealed_in_clean_and_corrupted_at_rest(F, eng, cases, name, tp):
     c = cases(name)
     ks, ab = c.ks, c.ab
@@ -285,7 +288,7 @@ def test_apply_sealed_in_hooks_and_refusals(F, eng, cases, name, tp):
 
 # ---- rotate_sealed_in ----
 
-@pytest.mark.parametrize("name,tp", PARAMS)
+@pytest.mark.parametrize("name,tp", PARAMS + BIG)
 def test_rotate_sealed_in(F, eng, cases, name, tp):
     c = cases(name)
     ks, ab, L, N = c.ks, c.ab, c.L, c.N

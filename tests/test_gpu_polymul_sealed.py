@@ -6,11 +6,18 @@ product's hooks poison through block 2, and the seal travels on into the sealed 
 
 Shapes, the smallest at which each code path exists: 2^5 (rows shorter than a wave), 2^10, 2^12 (the largest single launch), 2^13
 (the smallest two-launch size; two polynomials from limb 1 on, a 61-bit prime among 50-bit ones: both arithmetic paths, a run
-boundary and the slot addressing of flags, seals and partials), 2^14.  Operands are drawn from [16, q - 16)."""
+boundary and the slot addressing of flags, seals and partials), 2^14.  Operands are drawn from [16, q - 16).
+
+And every size the product accepts, 2^5 .. 2^20 (polymul_fused_supported, ntt_kernels.hip: 5 <= logn <= NTT_MAX_LOGN = 20, which is
+also the largest table set fhe_ntt_tables_create builds), in one shape -- the table set [50, 50, 61] from limb 1 on, two limbs, two
+polynomials: four rows, both arithmetic paths, a run boundary -- through the clean, the rot-in-a-factor, the own-load, the flip-in-c
+and the custody tests (ids "all-<logn>"); the own-load test there also hooks, for either factor, the words 2^k - 1 and 2^k for
+every k and N - 1: a word on both sides of the first edge of any tile size."""
 import numpy as np
 import pytest
 
 from helpers.sealed_case import case_cache, flip
+from helpers.sealed_ntt_runs import pow2_words
 
 pytestmark = pytest.mark.gpu
 
@@ -22,6 +29,10 @@ GARBAGE = 0x5A5A5A5A5A5A5A5A
 SHAPES = {5: ([50, 50], 1, 0), 10: ([50, 50], 1, 0), 12: ([50, 50], 1, 0), 13: ([50, 61, 50, 50], 2, 1), 14: ([50, 50, 50], 1, 0)}
 SIZES = list(SHAPES)
 TWO_LAUNCH = [13, 14]
+# every size the product accepts, in one four-row shape; a case key is then ("all", logn)
+MAX_LOGN = 20
+FOUR_ROWS = ([50, 50, 61], 2, 1)
+EVERY_SIZE = SIZES + [pytest.param(("all", logn), id=f"all-{logn}") for logn in range(5, MAX_LOGN + 1)]
 
 
 @pytest.fixture(scope="module")
@@ -39,8 +50,9 @@ class Case:
     """a table set, its detector, two seeded factors [n_poly][limbs][N] on the host and on the device, their seals, and the
     references computed once: the unchecked product, the unchecked square of a, and their seals"""
 
-    def __init__(self, F, eng, logn):
-        bits, self.n_poly, self.start = SHAPES[logn]
+    def __init__(self, F, eng, key):
+        logn = key[1] if isinstance(key, tuple) else key
+        bits, self.n_poly, self.start = FOUR_ROWS if isinstance(key, tuple) else SHAPES[key]
         self.logn, self.N = logn, 1 << logn
         self.qs = F.create_moduli(self.N, bits)
         self.limbs = len(bits) - self.start
@@ -120,7 +132,7 @@ def run(c, eng, a=None, b=None, alias=None, seal_a="own", seal_b="own", seal_out
 
 
 # ---- 1 ----
-@pytest.mark.parametrize("logn", SIZES)
+@pytest.mark.parametrize("logn", EVERY_SIZE)
 def test_clean_fresh_aliased_squared_and_without_an_output_seal(eng, cases, logn):
     c = cases(logn)
     for alias in (None, "a", "b"):
@@ -149,7 +161,7 @@ def test_clean_fresh_aliased_squared_and_without_an_output_seal(eng, cases, logn
 
 
 # ---- 2 ----
-@pytest.mark.parametrize("logn", SIZES)
+@pytest.mark.parametrize("logn", EVERY_SIZE)
 def test_a_bit_that_rots_in_a_factor_raises_its_row_in_its_block_and_poisons_that_rows_seal(eng, cases, logn):
     c = cases(logn)
     for op in (0, 1):
@@ -176,7 +188,7 @@ def test_a_bit_that_rots_in_a_factor_raises_its_row_in_its_block_and_poisons_tha
 
 
 # ---- 3 ----
-@pytest.mark.parametrize("logn", SIZES)
+@pytest.mark.parametrize("logn", EVERY_SIZE)
 def test_a_fault_on_the_products_own_load_is_seen_by_the_sealed_product_only(eng, cases, logn):
     c = cases(logn)
     for op in (0, 1):
@@ -194,7 +206,7 @@ def test_a_fault_on_the_products_own_load_is_seen_by_the_sealed_product_only(eng
             check_seal(c, dc, seal_c, [row])
             got = rows_of(dc, c)
             assert not (got[row] == c.c[row]).all() and (np.delete(got, row, 0) == np.delete(c.c, row, 0)).all()
-            if logn < 13:       # the single launch only reads its factors: memory is clean (two-launch sizes transform them in place)
+            if c.logn < 13:     # the single launch only reads its factors: memory is clean (two-launch sizes transform them in place)
                 assert (rows_of(a, c) == c.a).all() and (rows_of(b, c) == c.b).all()
             else:               # what the fault computes is the product of the flipped word
                 fa, fb = c.factors(eng)
@@ -203,6 +215,23 @@ def test_a_fault_on_the_products_own_load_is_seen_by_the_sealed_product_only(eng
             dc, seal_c, fl = run(c, eng)      # one shot
             check_flags(c, fl)
             assert (rows_of(dc, c) == c.c).all()
+    if isinstance(logn, tuple):
+        # both sides of every power of two, alternating between row 0 and the last row: the product is that of the one flipped word
+        for op in (0, 1):
+            for i, j in enumerate(pow2_words(c.logn)):
+                row = (0, c.rows - 1)[i & 1]
+                eng.inject_fault_polymul_sealed(op, row, j, 3)
+                dc, seal_c, fl = run(c, eng)
+                check_flags(c, fl, **{"ab"[op]: [row]})
+                assert int(fl["ab"[op]][row]) == SUM, (op, row, j)
+                fa, fb = c.factors(eng)
+                flip(eng, (fa, fb)[op], row * c.N + j, 3)
+                got = rows_of(dc, c)
+                assert (got == c.unchecked(eng, fa, fb)).all(), (op, row, j)
+                assert not (got[row] == c.c[row]).all(), (op, row, j)
+        dc, seal_c, fl = run(c, eng)          # one shot
+        check_flags(c, fl)
+        assert (rows_of(dc, c) == c.c).all()
     eng.check()
 
 
@@ -224,7 +253,7 @@ def test_the_checked_products_hooks_raise_block_2_and_poison_that_row(eng, cases
 
 
 # ---- 5 ----
-@pytest.mark.parametrize("logn", SIZES)
+@pytest.mark.parametrize("logn", EVERY_SIZE)
 def test_a_bit_flipped_in_c_after_the_call_fails_its_seal_on_that_row_only(eng, cases, logn):
     c = cases(logn)
     dc, seal_c, fl = run(c, eng)
@@ -311,7 +340,7 @@ def test_refusals_leave_the_flag_buffer_untouched_and_take_the_hooks(F, eng, cas
 
 
 # ---- 8 ----
-@pytest.mark.parametrize("logn", SIZES)
+@pytest.mark.parametrize("logn", EVERY_SIZE)
 def test_custody_from_seal_to_product_to_the_sealed_transforms(eng, cases, logn):
     c = cases(logn)
     a, b = c.factors(eng)
@@ -323,4 +352,14 @@ def test_custody_from_seal_to_product_to_the_sealed_transforms(eng, cases, logn)
     for call in (c.t.ntt_sealed, c.t.intt_sealed_out):
         _, _, f2 = call(dc, seal_c, c.ab, **c.kw)
         assert not f2.any()
+    eng.check()
+
+
+# ---- 9 ----
+def test_one_size_above_the_largest_there_is_no_table_set_to_call_with(F, eng):
+    """polymul_fused_supported holds up to NTT_MAX_LOGN, which is also the largest table set: one size above MAX_LOGN the refusal is
+    fhe_ntt_tables_create's (FHE_ERR_INVALID), so no call of the sealed product exists that could answer FHE_ERR_UNSUPPORTED"""
+    qs = F.create_moduli(1 << MAX_LOGN, [50])
+    with pytest.raises(F.FheError, match="bad table arguments"):
+        eng.tables(MAX_LOGN + 1, qs)
     eng.check()
