@@ -70,6 +70,75 @@ struct TrackF64 : ArithF64 {
     }
 };
 
+// What the integer path met (tests/test_emu_harvey_cases.py): equalities at its comparisons, Shoup products in the upper half, and
+// operands outside the documented ranges.  Indices of emu_u64_events().
+enum { EV_FOLD_EQ, EV_SUM_EQ, EV_FINAL_Q, EV_FINAL_2Q, EV_FINAL_3Q, EV_SHOUP_HI, EV_BARRETT_Q, EV_RANGE, EV_COUNT };
+u64 g_ev[EV_COUNT];
+
+// ArithU64 with every operand watched.  It delegates to ArithU64 unchanged, so the words are the kernels' words; the Shoup product a
+// butterfly makes inside is made once more here (it is a pure function) only to be looked at.  The documented ranges -- operands
+// below 4q forward, below 2q inverse, so that canonical() has at most 3q to remove -- are checked on every butterfly and counted
+// in EV_RANGE instead of aborting, so that a test can say which input broke them.
+struct TrackU64 : ArithU64 {
+    static void shoup(elem a, const Tw &t, const Ctx &c)
+    {
+        const u64 r = ArithU64::mulmod(a, t, c);
+        if (r >= c.two_q) g_ev[EV_RANGE]++;
+        else if (r >= c.q) g_ev[EV_SHOUP_HI]++;
+    }
+    static u64 canonical(elem x, const Ctx &c)
+    {
+        if (x == c.q) g_ev[EV_FINAL_Q]++;
+        if (x == c.two_q) g_ev[EV_FINAL_2Q]++;
+        if (x == c.two_q + c.q) g_ev[EV_FINAL_3Q]++;
+        if (x >= 2 * c.two_q) g_ev[EV_RANGE]++;
+        return ArithU64::canonical(x, c);
+    }
+    static elem mulmod(elem a, const Tw &t, const Ctx &c)
+    {
+        shoup(a, t, c);
+        return ArithU64::mulmod(a, t, c);
+    }
+    static void bfly_fwd(elem &X, elem &Y, const Tw &t, const Ctx &c)
+    {
+        if (X >= 2 * c.two_q || Y >= 2 * c.two_q) g_ev[EV_RANGE]++;
+        if (X == c.two_q) g_ev[EV_FOLD_EQ]++;
+        shoup(Y, t, c);
+        ArithU64::bfly_fwd(X, Y, t, c);
+        if (X >= 2 * c.two_q || Y >= 2 * c.two_q) g_ev[EV_RANGE]++;
+    }
+    static void inv_head(elem X, elem Y, const Ctx &c)
+    {
+        if (X >= c.two_q || Y >= c.two_q) g_ev[EV_RANGE]++;
+        if (X + Y == c.two_q) g_ev[EV_SUM_EQ]++;
+    }
+    static void bfly_inv(elem &X, elem &Y, const Tw &t, const Ctx &c)
+    {
+        inv_head(X, Y, c);
+        shoup(X - Y + c.two_q, t, c);
+        ArithU64::bfly_inv(X, Y, t, c);
+        if (X >= c.two_q || Y >= c.two_q) g_ev[EV_RANGE]++;
+    }
+    static void bfly_inv_scaled(elem &X, elem &Y, const Tw &n, const Tw &wn, const Ctx &c)
+    {
+        inv_head(X, Y, c);
+        shoup(X + Y, n, c), shoup(X - Y + c.two_q, wn, c);
+        ArithU64::bfly_inv_scaled(X, Y, n, wn, c);
+        if (X >= c.two_q || Y >= c.two_q) g_ev[EV_RANGE]++;
+    }
+    // the quotient estimate of barrett128 once more: floor(x * floor(2^128 / q) / 2^128) for x = (hi:lo)
+    static elem mulvar_lazy(elem a, elem b, const LimbParams &p)
+    {
+        if (a >= 2 * p.two_q || b >= 2 * p.two_q) g_ev[EV_RANGE]++;
+        const u64 lo = a * b, hi = mulhi64(a, b), r0 = p.barrett_lo, r1 = p.barrett_hi;
+        const unsigned __int128 mid = (unsigned __int128)lo * r1 + mulhi64(lo, r0);
+        const unsigned __int128 mid2 = (unsigned __int128)hi * r0 + (u64)mid;
+        const u64 qhat = hi * r1 + (u64)(mid >> 64) + (u64)(mid2 >> 64);
+        if (lo - qhat * p.q == p.q) g_ev[EV_BARRETT_Q]++;
+        return ArithU64::mulvar_lazy(a, b, p);
+    }
+};
+
 template <class PASS, int LOGN, bool INV, bool IS_COL>
 void emu_pass(const PassArgs &a)
 {
@@ -357,19 +426,20 @@ extern "C" int emu_ntt(u64 *data, int logn, int inverse, int n_poly, int limbs, 
         a.map = map.data();
     }
     g_max_ratio = g_max_pair = 0.0;      // the maxima are per call
+    for (u64 &e : g_ev) e = 0;            // and so are the integer path's events
     if (fused_dist == -3) {          // forward transform with the packed hand-off (2^16, FP64 path)
         if (logn == 16 && path == PATH_F64 && !inverse) return emu_packed<TrackF64, 16>(a);
         return -1;
     }
     if (fused_dist == -2) {          // resident pass
-        if (logn == 13) return path == PATH_F64 ? emu_resident<TrackF64, 13>(a, inverse) : emu_resident<ArithU64, 13>(a, inverse);
-        if (logn == 14) return path == PATH_F64 ? emu_resident<TrackF64, 14>(a, inverse) : emu_resident<ArithU64, 14>(a, inverse);
+        if (logn == 13) return path == PATH_F64 ? emu_resident<TrackF64, 13>(a, inverse) : emu_resident<TrackU64, 13>(a, inverse);
+        if (logn == 14) return path == PATH_F64 ? emu_resident<TrackF64, 14>(a, inverse) : emu_resident<TrackU64, 14>(a, inverse);
         return -1;
     }
     if (fused_dist > 0)
         return path == PATH_F64 ? emu_fused_size<TrackF64>(a, logn, inverse, (u32)fused_dist)
-                                : emu_fused_size<ArithU64>(a, logn, inverse, (u32)fused_dist);
-    return path == PATH_F64 ? emu_size<TrackF64>(a, logn, inverse) : emu_size<ArithU64>(a, logn, inverse);
+                                : emu_fused_size<TrackU64>(a, logn, inverse, (u32)fused_dist);
+    return path == PATH_F64 ? emu_size<TrackF64>(a, logn, inverse) : emu_size<TrackU64>(a, logn, inverse);
 }
 
 // Natural-order transform of one vector under the tracker (FP64 path, q < 2^50): dst = scale * W src, src and dst in natural order
@@ -403,6 +473,24 @@ extern "C" int emu_ntt_gs(u64 *dst, const u64 *src, int logn, u64 q, const u64 *
 // maxima of the last emu_ntt / emu_ntt_gs call (path 0; the integer path leaves them 0): register values, and inverse pair sums
 extern "C" double emu_max_ratio() { return g_max_ratio; }
 extern "C" double emu_max_pair() { return g_max_pair; }
+// events of the last emu_ntt call on path 1 and of the emu_u64_mulvar_lazy calls since (the FP64 path leaves them 0), in the order of
+// the EV_ enumeration: X == 2q at the forward fold, X + Y == 2q at the inverse sum, a word q / 2q / 3q on entry to canonical(), a
+// Shoup product in [q, 2q), barrett128 left exactly q before its first fix-up, an operand outside its documented range
+extern "C" void emu_u64_events(u64 *out)
+{
+    for (int i = 0; i < EV_COUNT; i++) out[i] = g_ev[i];
+}
+// c[i] = ArithU64::mulvar_lazy(a[i], b[i]) under the tracker: the one Barrett step of the fused product, on lazy words
+extern "C" void emu_u64_mulvar_lazy(u64 *c, const u64 *a, const u64 *b, size_t n, u64 q)
+{
+    LimbParams p{};
+    p.q = q;
+    p.two_q = 2 * q;
+    const unsigned __int128 ratio = ~(unsigned __int128)0 / q;      // = floor(2^128 / q): q is odd, so it does not divide 2^128
+    p.barrett_lo = (u64)ratio;
+    p.barrett_hi = (u64)(ratio >> 64);
+    for (size_t i = 0; i < n; i++) c[i] = TrackU64::mulvar_lazy(a[i], b[i], p);
+}
 
 // the per-register lazy-range plan of K inverse stages (ntt_core.hpp inv_lazy_plan), as the kernels' templates evaluate it
 template <int K> static void dump_plan(int in8, int exit8, int fold, uint32_t *before, uint32_t *at_exit, int *out8)

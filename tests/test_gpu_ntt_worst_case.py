@@ -191,7 +191,9 @@ def test_checked_transforms_on_ladders_and_pulses(F, eng, O, logn):
 
 
 def test_integer_path_on_soak_patterns(F, eng, O):
-    """parity only: Harvey's [0, 4q) has no fold schedule to break"""
+    """parity on the soak patterns: Harvey's [0, 4q) has no fold schedule to break.  What it has is comparisons, x >= 2q and x >= q,
+    which these patterns and random words never bring to equality: tests/test_gpu_integer_path_edges.py runs the integer path on
+    inputs whose results vanish (tests/helpers/harvey_cases.py), where they meet it all the time."""
     for logn in (9, 13, 16):
         N = 1 << logn
         assert Q61 % (2 * N) == 1
