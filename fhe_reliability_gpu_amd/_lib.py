@@ -156,6 +156,8 @@ _SIG = {
     "fhe_scalar_affine": (ci, [vp, vp, vp, p64, p64, vp, sz, sz, sz, vp]),
     "fhe_scalar_affine_checked": (ci, [vp, vp, vp, p64, p64, vp, sz, sz, sz, vp, vp]),
     "fhe_keyswitch_set_plain_modulus": (ci, [vp, u64]),
+    "fhe_keyswitch_set_rescale_rounding": (ci, [vp, ci]),
+    "fhe_keyswitch_get_rescale_rounding": (ci, [vp, C.POINTER(ci)]),
     "fhe_bgv_keyswitch_checked_layout": (ci, [vp, C.POINTER(ci)]),
     "fhe_bgv_keyswitch_apply_checked": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "fhe_bgv_relinearize_checked": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),

@@ -3,6 +3,7 @@
 // Garner CRT and the BSGS Hadamard accumulate.  All integer work, one element (or one
 // coefficient column) per lane, 64-bit coalesced accesses along N.
 #include "ntt_launch.hpp"
+#include "rescale_round.hpp"
 
 #include <cstdlib>
 #include <type_traits>
@@ -849,6 +850,28 @@ hipError_t launch_sub_scale(hipStream_t st, const SubScaleArgs &p)
     if (!total) return hipSuccess;
     u64 want = (total + 255) / 256;
     hipLaunchKernelGGL(k_sub_scale, dim3((u32)(want > 8192 ? 8192 : want), p.out1 ? 2 : 1), dim3(256), 0, st, p);
+    return hipGetLastError();
+}
+
+// The residues a nearest rescale subtracts, where they exist as words (the launch lists below 2^13): in place of the one-limb
+// conversion y mod q_l, the centred remainder of y modulo the last prime as a residue of q_l (rescale_round.hpp).
+__global__ __launch_bounds__(256) void k_round_residues(u64 *out, const u64 *y, const LimbParams *lp, u32 limb0, u32 limbs, u32 n_parts, int logn, ColRound r)
+{
+    const u64 n = (u64)1 << logn, total = ((u64)n_parts * limbs) << logn;
+    for (u64 g = blockIdx.x * (u64)blockDim.x + threadIdx.x; g < total; g += (u64)gridDim.x * blockDim.x) {
+        const u64 row = g >> logn;                      // part * limbs + l
+        const u32 part = (u32)(row / limbs), l = (u32)(row % limbs);
+        out[g] = round_residue(y[(u64)part * n + (g & (n - 1))], r.q, r.h, lp[limb0 + l].q);
+    }
+}
+
+hipError_t launch_round_residues(hipStream_t st, u64 *out, const u64 *y, const LimbParams *lp, u32 limb0, u32 limbs, u32 n_parts, int logn, const ColRound &r)
+{
+    const u64 total = ((u64)n_parts * limbs) << logn;
+    if (!total) return hipSuccess;
+    if (!r.q) return hipErrorInvalidValue;
+    u64 want = (total + 255) / 256;
+    hipLaunchKernelGGL(k_round_residues, dim3((u32)(want > 8192 ? 8192 : want)), dim3(256), 0, st, out, y, lp, limb0, limbs, n_parts, logn, r);
     return hipGetLastError();
 }
 

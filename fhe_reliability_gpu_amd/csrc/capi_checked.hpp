@@ -120,6 +120,15 @@ KscNtt ksc_ntt(const fhe_keyswitch *p, const fhe_abft *a, hipStream_t st, bool i
 // a plan with a plain modulus (FHE_ERR_UNSUPPORTED), the BGV form one without (FHE_ERR_INVALID) or with more than 64 limbs per
 // scalar stage; mod_switch: the call drops a prime
 int ksc_scope(const fhe_ctx *ctx, const fhe_keyswitch *p, const fhe_abft *a, const uint32_t *d_flags, KsForm form, bool mod_switch);
+// a plan that rounds its rescale to nearest (fhe_keyswitch_set_rescale_rounding) has no checked, sealed or repairing form of a call
+// that drops a prime: those restate the flooring words stage by stage and would floor silently.  Part of ksc_scope, so every such
+// entry point refuses after taking its hooks and before its first launch; a call that drops no prime runs as on any other plan
+inline int ksc_rounding_scope(const fhe_keyswitch *p, bool mod_switch)
+{
+    if (mod_switch && p->rescale_rounding)
+        return fail(FHE_ERR_UNSUPPORTED, "the plan rounds its rescale to nearest: the checked and sealed rescales restate the flooring form (fhe_keyswitch_set_rescale_rounding)");
+    return FHE_OK;
+}
 
 // ---- the sealed steps of a checked call: each replaces one launch of the checked call's list by its sealed form -- same words, same
 // ABFT or residue flags at the same place -- and an absent step leaves that launch the checked call's own (SealedSteps below)

@@ -34,7 +34,8 @@ int fhe_relinearize(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *
 } // extern "C"
 
 // (c - [c]_{q_last}) / q_last on every part: INTT of the last limb, its residues modulo the remaining primes, NTT,
-// subtract, times q_last^-1.  BGV (plain modulus t set on the plan): the removed part is t * [c t^-1]_{q_last}.
+// subtract, times q_last^-1.  BGV (plain modulus t set on the plan): the removed part is t * [c t^-1]_{q_last}.  A plan that rounds
+// to nearest (fhe_keyswitch_set_rescale_rounding) removes the centred remainder, [c]_{q_last} or [c]_{q_last} - q_last, instead.
 // d_in = [n_parts][cn][N] (the rows this rank owns; one device: cn = L).  Two phases around the one exchange a sharded job
 // needs: the owner of limb L-1 produces the last limbs in coefficient form (rs_bc), everybody consumes them.
 static int rescale_begin(fhe_ctx *ctx, fhe_keyswitch *p, const uint64_t *d_in, size_t n_parts, hipStream_t st)
@@ -68,7 +69,13 @@ static int rescale_finish(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *const *outs,
     const bool plain = !ntt_subscale_supported(p->log_n) || ctx->mode != 0 || ctx->fault_idx >= 0 || ctx->packed_on || ctx->only_pass >= 0 || ctx->resident;
     // a rescale converts ONE limb: at the two-launch sizes x mod q_j rides on the column pass of the residues' transform
     const bool trivial = p->log_n >= 13 && !plain;
-    if (!trivial) {
+    // a plan that rounds to nearest removes the centred remainder of the last limb instead of the limb itself (rescale_round.hpp): the
+    // residues differ, every launch after them is the same; where they are words, one launch forms them in the conversion's place
+    const ColRound round = p->rs_round();
+    if (!trivial && round.q) {
+        e = launch_round_residues(st, delta, p->rs_bc, lp, (u32)lo, (u32)R, (u32)n_parts, p->log_n, round);
+        if (e != hipSuccess) return hip_fail(e, "launch_round_residues");
+    } else if (!trivial) {
         e = launch_baseconv_exact_jobs(st, p->rs_jobs.as<BcJob>(), (u32)n_parts, 1, (int)R, p->last->dev.f64 != 0, N, 1u);
         if (e != hipSuccess) return hip_fail(e, "launch_baseconv_exact_jobs");
         if (p->plain_modulus && (rc = fhe_scalar_affine(ctx, delta, delta, p->t_mod_Q.data() + lo, nullptr, t, n_parts, R, lo, st))) return rc;
@@ -94,7 +101,7 @@ static int rescale_finish(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *const *outs,
             a.src_bcast = N;
             if (p->plain_modulus) ep.pre = p->d_t_mod_Q.as<u64>() + lo + off;          // BGV: delta = t * [c t^-1]_{q_last}
         }
-        hipError_t e2 = launch_ntt_subscale(st, a, ep, p->log_n, path);
+        hipError_t e2 = launch_ntt_subscale(st, a, ep, p->log_n, path, nullptr, trivial ? &round : nullptr);     // nearest: the remainder is centred on the column pass's load
         return e2 == hipSuccess ? FHE_OK : hip_fail(e2, "launch_ntt_subscale");
     });
 }

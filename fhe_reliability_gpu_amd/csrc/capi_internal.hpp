@@ -212,6 +212,12 @@ struct fhe_keyswitch {
     bool own_last = false;             // this rank owns limb L-1 (it feeds the broadcast)
     u64 *rs_bc = nullptr;              // [3][N] last limbs in coefficient form: plan-owned on one device, the caller's broadcast buffer when sharded
     DevBuf qlast_inv;                  // q_{L-1}^-1 mod q_j, owned j < L-1
+    // rounding of the rescale (fhe_keyswitch_set_rescale_rounding): 0 = floor, 1 = nearest.  The nearest form removes the centred
+    // remainder of the last limb (rescale_round.hpp); its two constants, q_{L-1} and h = (q_{L-1} - 1) / 2, are fixed at creation and
+    // travel as launch arguments: the centred form needs no per-limb h mod q_j, so nothing is uploaded, by the setter or per call
+    int rescale_rounding = 0;
+    u64 rs_half = 0;
+    ColRound rs_round() const { return rescale_rounding ? ColRound{t->q[L - 1], rs_half} : ColRound{}; }
     DevBuf rs_last, rs_delta, rs_jobs; // rs_last backs rs_bc on one device; [3][rs_n][N] residues; job list (3 parts)
     DevBuf hm, hm_pre;                 // [3][L][N] tensor product, [2][L][N] relinearised product before the rescale
     DevBuf pq_tw;                      // one device: P mod q_j as a twiddle of limb j's arithmetic, j < L (mod-down and rescale sharing one transform)

@@ -182,6 +182,7 @@ static int ks_create(fhe_ctx *ctx, const fhe_ntt_tables *t, int L, int K, int dn
         // form; every rank needs it (one device: it is simply there; sharded: ONE broadcast of n_parts x N words into d_bcast)
         // and forms (c - delta) / q_last on the ciphertext limbs below L-1 that it owns.
         const u64 ql = t->q[L - 1];
+        p->rs_half = (ql - 1) / 2;
         p->own_last = sh.clo <= L - 1 && L - 1 < sh.clo + sh.cn;
         p->rs_n = std::max(0, std::min(sh.clo + sh.cn, L - 1) - sh.clo);
         if (!sharded) {
@@ -487,7 +488,8 @@ static int ks_finish_rescale_end(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out
     const size_t N = (size_t)1 << p->log_n, MO = p->m_own;
     const LimbParams *lp = t->d_lp.as<LimbParams>();
     u64 *acc = p->acc_cur(), *conv = p->conv_cur();
-    const ColAddSrc as{p->rs_bc, (u64)N, p->pq_tw.as<Tw>()};
+    // (a plan that rounds to nearest: y enters as the residue of its centred remainder, the one place where the two forms differ)
+    const ColAddSrc as{p->rs_bc, (u64)N, p->pq_tw.as<Tw>(), p->rs_round()};
     return for_each_run(t, p->rs_n, sh.clo, [&](size_t off, size_t len, int path) -> int {
         PassArgs a{conv + off * N, lp, (u32)(sh.clo + off), (u32)len, (u32)(2 * len), (u32)sh.cn};
         RowEpiArgs ep{{d_out0 + off * N, d_out1 + off * N, nullptr}, {d_add0 ? d_add0 + off * N : nullptr, d_add1 ? d_add1 + off * N : nullptr, nullptr},
@@ -578,6 +580,8 @@ int fhe_keyswitch_shard_layout(int L, int K, int world, int rank, int out[6])
 int fhe_keyswitch_set_plain_modulus(fhe_keyswitch *p, uint64_t plain_modulus)
 {
     if (!p) return fail(FHE_ERR_INVALID, "null plan");
+    if (plain_modulus && p->rescale_rounding)
+        return fail(FHE_ERR_UNSUPPORTED, "the plan rounds its rescale to nearest: the BGV mod switch removes t [c t^-1] and has no such form");
     p->plain_modulus = plain_modulus;
     p->t_inv_P.clear();
     p->t_mod_Q.clear();
@@ -596,6 +600,26 @@ int fhe_keyswitch_set_plain_modulus(fhe_keyswitch *p, uint64_t plain_modulus)
             if (!p->t_inv_qlast) return fail(FHE_ERR_INVALID, "plain modulus must be coprime to the ciphertext primes");
         }
     }
+    return FHE_OK;
+}
+
+// Rounding of every rescale the plan runs: fhe_rescale, fhe_hmult with rescale on both of its routes, the sharded phases of both.
+// Host state only: the kernels take the two constants as launch arguments (fhe_keyswitch::rs_round), so switching back leaves
+// nothing behind.  The key switch's own mod-down floors in either mode.
+int fhe_keyswitch_set_rescale_rounding(fhe_keyswitch *p, int mode)
+{
+    if (mode != 0 && mode != 1) return fail(FHE_ERR_INVALID, "rescale rounding mode must be 0 (floor) or 1 (nearest)");
+    if (!p) return fail(FHE_ERR_INVALID, "null plan");
+    if (mode && p->plain_modulus)
+        return fail(FHE_ERR_UNSUPPORTED, "the plan has a plain modulus: the BGV mod switch removes t [c t^-1] and has no round-to-nearest form");
+    p->rescale_rounding = mode;
+    return FHE_OK;
+}
+
+int fhe_keyswitch_get_rescale_rounding(const fhe_keyswitch *p, int *mode)
+{
+    if (!p || !mode) return fail(FHE_ERR_INVALID, "null argument");
+    *mode = p->rescale_rounding;
     return FHE_OK;
 }
 

@@ -267,6 +267,7 @@ int ksc_scope(const fhe_ctx *ctx, const fhe_keyswitch *p, const fhe_abft *a, con
     if (p->sharded) return fail(FHE_ERR_INVALID, "a sharded plan has no checked key switch: the checked call runs the whole switch on one device");
     if (!bgv && p->plain_modulus) return fail(FHE_ERR_UNSUPPORTED, "the BGV steps of a plan with a plain modulus have no checked form");
     if (bgv && !p->plain_modulus) return fail(FHE_ERR_INVALID, "the plan has no plain modulus: use the existing checked calls");
+    if (int rc = ksc_rounding_scope(p, mod_switch)) return rc;      // (after the form: a BGV-form call on a plan without a plain modulus answers as it did)
     if (ctx->mode != 0 || ctx->resident || ctx->packed_on || ctx->only_pass >= 0 || !ntt_checked_supported(p->log_n))
         return fail(FHE_ERR_UNSUPPORTED, "the checked key switch runs the two-launch transforms: not with ntt_mode=1, ntt_resident, ntt_packed, a single-pass hook, or N < 2^5");
     if (!p->t->has_inverse) return fail(FHE_ERR_UNSUPPORTED, "table set has no inverse (twiddle or N not invertible)");

@@ -6,6 +6,7 @@
 #include "ntt_launch.hpp"
 #include "ntt_plan.hpp"
 #include "abft_taps.hpp"
+#include "rescale_round.hpp"
 
 #include <cstdlib>
 #include <type_traits>
@@ -810,7 +811,10 @@ struct SubScaleTap {
 // Column pass of that transform with a second input (ColAddSrc): every word it loads becomes x + w_l * y (mod q_l), y read from the
 // part's ONE extra limb at the same position.  The sum is folded back right away, so the pass's lazy-range schedule sees an input no
 // larger than a canonical one.
-template <class A>
+// ROUND (ColRound, a plan that rescales to nearest): the extra limb's words enter as the residues of their centred remainders modulo rq.
+// A template flag, not a run-time test: the run-time form cost the flooring launches 2 to 23 registers and, on the FP64 path at 2^13 and
+// 2^14, a wave of occupancy (profiles/r25_rescale_round.md); the flooring instantiations are the ones they were.
+template <class A, bool ROUND>
 struct AddSrcTap {
     static constexpr bool ACTIVE = true;
     static constexpr bool MID = false;
@@ -818,11 +822,15 @@ struct AddSrcTap {
     static constexpr bool PRELOAD = true;
     const u64 *y;               // the tile's first word inside the part's extra limb
     Tw w;
+    u64 rq, rh;                 // ROUND: the last prime and its half
     FHE_D u64 load(u32 idx) const { return y[idx]; }
     // one cold branch for the whole register set (FP64 limbs under an extra limb of the integer path: words up to 2^61)
     template <int R> FHE_D void prepare(u64 (&e)[R], const typename A::Ctx &c) const
     {
-        if constexpr (A::PATH == PATH_F64) {
+        if constexpr (ROUND) {  // canonical words of this limb afterwards: nothing below has anything left to do
+#pragma unroll
+            for (int r = 0; r < R; r++) e[r] = round_residue(e[r], rq, rh, c.q);
+        } else if constexpr (A::PATH == PATH_F64) {
             bool big = false;
 #pragma unroll
             for (int r = 0; r < R; r++) big |= (e[r] >> 52) != 0;
@@ -843,20 +851,16 @@ struct AddSrcTap {
     }
 };
 
-template <class PASS, int LOGN>
-__global__ __launch_bounds__(NTT_THREADS) void k_ntt_col_addsrc(PassArgs a, ColAddSrc s)
+// the column pass of a forward transform with a tap on its loading step: the body k_ntt_col_addsrc and k_ntt_col_round share
+template <class PASS, int LOGN, class TAP>
+FHE_D void col_pass_tapped(const PassArgs &a, u64 *base, const LimbParams &p, TAP &tap)
 {
     typedef typename PASS::Arith A;
     __shared__ __attribute__((aligned(16))) typename PASS::elem lds[PASS::LDS_ELEMS > 0 ? PASS::LDS_ELEMS : 1];
-    u32 limb;
-    u64 *base = col_tile<PASS, LOGN>(blockIdx.x, a, limb);
-    const u32 unit = blockIdx.x / PASS::TILES, tile = blockIdx.x % PASS::TILES, polys = a.units / a.limbs;
-    const LimbParams &p = a.lp[limb];
     const typename A::Ctx ctx = A::make_ctx(p);
     const TwPtr tw = as_global(p.fwd);
     const Tw inv_n = p.inv_n;
     const int tid = threadIdx.x;
-    AddSrcTap<A> tap{s.y + (size_t)(unit % polys) * s.y_stride + (size_t)tile * PASS::TCOLS, s.w[limb]};
     const u64 *from = pass_source<PASS, LOGN, true>(a, base, 0u);
     PASS::template phase<0>(tid, base, lds, tw, 0u, ctx, inv_n, &tap, from);
     if constexpr (PASS::NPHASE > 1) {
@@ -867,6 +871,39 @@ __global__ __launch_bounds__(NTT_THREADS) void k_ntt_col_addsrc(PassArgs a, ColA
         __syncthreads();
         PASS::template phase<2>(tid, base, lds, tw, 0u, ctx, inv_n);
     }
+}
+
+template <class PASS, int LOGN, bool ROUND>
+__global__ __launch_bounds__(NTT_THREADS) void k_ntt_col_addsrc(PassArgs a, ColAddSrc s)
+{
+    u32 limb;
+    u64 *base = col_tile<PASS, LOGN>(blockIdx.x, a, limb);
+    const u32 unit = blockIdx.x / PASS::TILES, tile = blockIdx.x % PASS::TILES, polys = a.units / a.limbs;
+    AddSrcTap<typename PASS::Arith, ROUND> tap{s.y + (size_t)(unit % polys) * s.y_stride + (size_t)tile * PASS::TCOLS, s.w[limb], s.round.q, s.round.h};
+    col_pass_tapped<PASS, LOGN>(a, base, a.lp[limb], tap);
+}
+
+// Column pass of the nearest rescale's residues (ColRound without a second input): the tile comes from the part's ONE last limb in
+// coefficient form (PassArgs::src_bcast) and every word of it enters as round_residue() of this limb's prime -- on the raw word,
+// before the conversion, which then finds a canonical word where the flooring pass reduces y itself.  A kernel of its own, so that
+// k_ntt_pass -- every plain transform's kernel -- carries neither the two constants nor the test for them.
+struct RoundSrcTap {
+    static constexpr bool ACTIVE = false;
+    static constexpr bool MID = false;
+    static constexpr bool STORES = false;
+    static constexpr bool SEES_RAW = true;
+    u64 q, h, qj;
+    FHE_D void raw(u32, u64 &word) const { word = round_residue(word, q, h, qj); }
+};
+
+template <class PASS, int LOGN>
+__global__ __launch_bounds__(NTT_THREADS) void k_ntt_col_round(PassArgs a, ColRound rd)
+{
+    u32 limb;
+    u64 *base = col_tile<PASS, LOGN>(blockIdx.x, a, limb);
+    const LimbParams &p = a.lp[limb];
+    RoundSrcTap tap{rd.q, rd.h, p.q};
+    col_pass_tapped<PASS, LOGN>(a, base, p, tap);
 }
 
 template <class PASS, int LOGN>
@@ -904,17 +941,21 @@ __global__ __launch_bounds__(NTT_THREADS) void k_ntt_row_subscale(PassArgs a, Ro
 }
 
 template <class A, int LOGN>
-static hipError_t launch_subscale_t(hipStream_t st, const PassArgs &a, const RowEpiArgs &ep, const ColAddSrc *add_src)
+static hipError_t launch_subscale_t(hipStream_t st, const PassArgs &a, const RowEpiArgs &ep, const ColAddSrc *add_src, const ColRound *round)
 {
     constexpr int GEO = LOGN >= 13 ? 1 : 0;
     typedef Passes<A, LOGN, false, GEO> PS;
     if constexpr (!PS::G::TWO_PASS) {
-        if (add_src) return hipErrorInvalidValue;
+        if (add_src || round) return hipErrorInvalidValue;
         hipLaunchKernelGGL((k_ntt_row_subscale<typename PS::Single, LOGN>), dim3(a.units * PS::Single::TILES), dim3(NTT_THREADS), 0, st, a, ep);
     } else {
         hipError_t e;
         if (add_src) {
-            hipLaunchKernelGGL((k_ntt_col_addsrc<typename PS::Col, LOGN>), dim3(a.units * PS::Col::TILES), dim3(NTT_THREADS), 0, st, a, *add_src);
+            if (add_src->round.q) hipLaunchKernelGGL((k_ntt_col_addsrc<typename PS::Col, LOGN, true>), dim3(a.units * PS::Col::TILES), dim3(NTT_THREADS), 0, st, a, *add_src);
+            else hipLaunchKernelGGL((k_ntt_col_addsrc<typename PS::Col, LOGN, false>), dim3(a.units * PS::Col::TILES), dim3(NTT_THREADS), 0, st, a, *add_src);
+            e = hipGetLastError();
+        } else if (round) {
+            hipLaunchKernelGGL((k_ntt_col_round<typename PS::Col, LOGN>), dim3(a.units * PS::Col::TILES), dim3(NTT_THREADS), 0, st, a, *round);
             e = hipGetLastError();
         } else {
             e = launch_pass<typename PS::Col, LOGN, false, true>(st, a);
@@ -929,13 +970,16 @@ static hipError_t launch_subscale_t(hipStream_t st, const PassArgs &a, const Row
 
 bool ntt_subscale_supported(int logn) { return logn >= 5 && logn <= NTT_MAX_LOGN; }
 
-hipError_t launch_ntt_subscale(hipStream_t st, const PassArgs &a, const RowEpiArgs &ep, int logn, int path, const ColAddSrc *add_src)
+hipError_t launch_ntt_subscale(hipStream_t st, const PassArgs &a, const RowEpiArgs &ep, int logn, int path, const ColAddSrc *add_src, const ColRound *round)
 {
     if (a.units == 0) return hipSuccess;
     if (a.map || !ntt_subscale_supported(logn) || a.units / a.limbs > 3) return hipErrorInvalidValue;
+    if (round && !round->q) round = nullptr;
+    // the rounding of a launch with a second input travels in that input's record; without one it is taken on the broadcast source's load
+    if (round && (add_src || !a.src || !a.src_bcast)) return hipErrorInvalidValue;
     switch (logn) {
 #define FHE_CASE(L) \
-    case L: return path == PATH_F64 ? launch_subscale_t<ArithF64, L>(st, a, ep, add_src) : launch_subscale_t<ArithU64, L>(st, a, ep, add_src);
+    case L: return path == PATH_F64 ? launch_subscale_t<ArithF64, L>(st, a, ep, add_src, round) : launch_subscale_t<ArithU64, L>(st, a, ep, add_src, round);
         FHE_CASE(5) FHE_CASE(6) FHE_CASE(7) FHE_CASE(8) FHE_CASE(9) FHE_CASE(10) FHE_CASE(11) FHE_CASE(12) FHE_CASE(13)
         FHE_CASE(14) FHE_CASE(15) FHE_CASE(16) FHE_CASE(17) FHE_CASE(18) FHE_CASE(19) FHE_CASE(20)
 #undef FHE_CASE

@@ -36,13 +36,25 @@ struct RowEpiArgs {
 // Optional second input of the transform (two-launch sizes): the column pass loads data_h[l] + w[l] * y_h (mod q_l) instead of
 // data_h[l]; y_h = y + h * y_stride words is ONE limb per part (residues of some other prime, any 64-bit words), w = per TABLE limb
 // factors in the limb's twiddle encoding.  By linearity NTT(data + w y) = NTT(data) + w NTT(y): two subtractions share one transform.
+// Round-to-nearest rescale (rescale_round.hpp): q != 0 (two-launch sizes) turns every word y < q that the column pass takes from a
+// part's ONE extra limb -- the second input below, or without one the broadcast source PassArgs::src_bcast -- into the residue of
+// its centred remainder, y or y - q, instead of y mod q_l; h = (q - 1) / 2.  q == 0: the flooring form, the kernels as they were
+// (the host picks the column pass's rounding instantiation by q: ntt_kernels.hip k_ntt_col_addsrc<.., true>, k_ntt_col_round).
+struct ColRound {
+    u64 q = 0, h = 0;
+};
 struct ColAddSrc {
     const u64 *y;
     u64 y_stride;
     const Tw *w;
+    ColRound round = {};
 };
 bool ntt_subscale_supported(int logn);
-hipError_t launch_ntt_subscale(hipStream_t st, const PassArgs &a, const RowEpiArgs &ep, int logn, int path, const ColAddSrc *add_src = nullptr);
+hipError_t launch_ntt_subscale(hipStream_t st, const PassArgs &a, const RowEpiArgs &ep, int logn, int path, const ColAddSrc *add_src = nullptr,
+                               const ColRound *round = nullptr);
+// the residues of a nearest rescale as words, where a launch of its own forms them (N < 2^13, test hooks, experimental transform
+// variants): out[(part * limbs + l) * N + i] = centred remainder of y[part * N + i] modulo q, as a residue of q_(limb0 + l)
+hipError_t launch_round_residues(hipStream_t st, u64 *out, const u64 *y, const LimbParams *lp, u32 limb0, u32 limbs, u32 n_parts, int logn, const ColRound &r);
 
 // c = a * b mod (x^N + 1, q_l): forward column passes, one launch that finishes both forward transforms,
 // multiplies and starts the inverse, inverse column pass.  a and b are scratch afterwards.

@@ -227,6 +227,23 @@ class ShardedKeySwitch:
         from ._lib import check, lib
         check(lib.fhe_keyswitch_set_plain_modulus(self._h, t))
 
+    def set_rescale_rounding(self, nearest: bool):
+        """Rounding of the rescale phases (``rescale_*``, ``hm_finish_*``) on this rank's rows: round to nearest (SEAL's
+        ``rescale_to_next_inplace``) instead of the default floor.  Every rank sets the same value: the owner of the last limb
+        broadcasts the raw limb in either mode and each rank centres the remainder on its own loads, so ranks that disagree
+        produce limbs of two different ciphertexts."""
+        from ._lib import check, lib
+        check(lib.fhe_keyswitch_set_rescale_rounding(self._h, 1 if nearest else 0))
+
+    @property
+    def rescale_rounding(self) -> bool:
+        import ctypes as C
+
+        from ._lib import check, lib
+        mode = C.c_int()
+        check(lib.fhe_keyswitch_get_rescale_rounding(self._h, C.byref(mode)))
+        return bool(mode.value)
+
     # the three phases of a rotation: the automorphism rides on loads of the key switch's own launches (fhe_rotate_shard_*)
     def rotate_begin(self, c1_local, galois_elt: int):
         from ._lib import check, lib

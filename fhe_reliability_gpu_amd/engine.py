@@ -837,6 +837,18 @@ class KeySwitch:
         check(lib.fhe_keyswitch_set_plain_modulus(self._h, t))
         self.plain_modulus = int(t)
 
+    def set_rescale_rounding(self, nearest: bool):
+        """Rounding of every rescale on this plan (``rescale``, ``hmult`` with rescale): round to nearest -- SEAL's
+        ``rescale_to_next_inplace``, floor((C + (q-1)/2) / q) -- instead of the default floor.  The checked and sealed calls that
+        drop a prime refuse a plan that rounds to nearest; a plan with a plain modulus cannot round."""
+        check(lib.fhe_keyswitch_set_rescale_rounding(self._h, 1 if nearest else 0))
+
+    @property
+    def rescale_rounding(self) -> bool:
+        mode = C.c_int()
+        check(lib.fhe_keyswitch_get_rescale_rounding(self._h, C.byref(mode)))
+        return bool(mode.value)
+
     def _out(self, limbs: int) -> DeviceArray:
         o = self.eng.alloc(limbs * self.t.N)
         o.shape = (limbs, self.t.N)

@@ -308,6 +308,16 @@ int fhe_keyswitch_shard_finish(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0_
  * above) the removed part delta satisfies delta = acc mod P and delta = 0 mod plain_modulus, so the
  * plaintext is preserved exactly (scheme of reliability_test/dotprod_test.cu:199-204). */
 int fhe_keyswitch_set_plain_modulus(fhe_keyswitch *p, uint64_t plain_modulus);
+/* Rounding of every rescale the plan runs: mode 0 = floor (the default), 1 = round to nearest (fhe_rescale below gives both
+ * definitions).  Honoured by fhe_rescale, fhe_hmult with rescale != 0 on both of its routes, fhe_rescale_shard_begin / _finish and
+ * fhe_hmult_shard_finish_begin / _end (every rank sets the same mode).  Host state only; mode 0 restores every launch list and word.
+ * The mod-down inside the key switch floors in either mode.  Refusals: another mode FHE_ERR_INVALID; mode 1 on a plan with a plain
+ * modulus, and a plain modulus on a plan in mode 1, FHE_ERR_UNSUPPORTED (the BGV mod switch removes t [c t^-1] -- another operation).
+ * On a plan in mode 1 every checked, sealed or repairing call that would drop a prime -- fhe_rescale_checked, fhe_rescale_sealed,
+ * fhe_hmult_checked / _sealed / _sealed_fused / _sealed_fused_key / _sealed_out / _sealed_repair with rescale != 0 -- returns
+ * FHE_ERR_UNSUPPORTED after taking its one-shot hooks, with nothing launched: they restate the flooring form. */
+int fhe_keyswitch_set_rescale_rounding(fhe_keyswitch *p, int mode);
+int fhe_keyswitch_get_rescale_rounding(const fhe_keyswitch *p, int *mode);
 int fhe_keyswitch_destroy(fhe_keyswitch *p);
 int fhe_keyswitch_apply(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_c,
                         const uint64_t *d_evk, void *stream);
@@ -377,10 +387,16 @@ int fhe_tensor_product(fhe_ctx *ctx, uint64_t *d_d0, uint64_t *d_d1, uint64_t *d
  * additions ride on the key switch's last launch. */
 int fhe_relinearize(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out0, uint64_t *d_out1, const uint64_t *d_d0, const uint64_t *d_d1,
                     const uint64_t *d_d2, const uint64_t *d_relin_key, void *stream);
-/* phantom::mod_switch_to_next_inplace (dotprod_test.cu:115) / CKKS rescale: drop the plan's last ciphertext prime,
- * c' = (c - [c]_{q_last}) / q_last on each of n_parts (1..3) parts; d_in = [n_parts][L][N], d_out = [n_parts][L-1][N],
- * NTT domain.  With a plain modulus set on the plan (BGV) the removed part is t [c t^-1]_{q_last}, so the plaintext is
- * kept up to the factor q_last^-1 mod t. */
+/* phantom::mod_switch_to_next_inplace (dotprod_test.cu:115) / CKKS rescale: drop the plan's last ciphertext prime on each of
+ * n_parts (1..3) parts; d_in = [n_parts][L][N], d_out = [n_parts][L-1][N], NTT domain.  Two roundings, chosen per plan
+ * (fhe_keyswitch_set_rescale_rounding below), with C in [0, Q) the CRT lift of a coefficient, q = q_last, h = (q - 1) / 2:
+ *   mode 0, floor (the default):  c' = (C - [C]_q) / q,  [C]_q in [0, q);
+ *   mode 1, nearest:              c' = floor((C + h) / q) = (C - r) / q,  r = [C]_q if [C]_q <= h else [C]_q - q  (q is odd: no ties)
+ *                                 -- SEAL's rescale_to_next_inplace (RNSTool::divide_and_round_q_last_ntt_inplace).
+ * Output limb j is the canonical word of NTT_j((c_j - (r mod q_j)) q^-1 mod q_j).  The nearest form is pinned by this integer
+ * definition (tests/helpers/rescale_round.py); its word-for-word parity with a SEAL or Phantom build is unpinned -- neither is at hand.
+ * With a plain modulus set on the plan (BGV) the removed part is t [c t^-1]_{q_last}, so the plaintext is kept up to the factor
+ * q_last^-1 mod t; that form has no rounding mode. */
 /* OUT OF PLACE: input parts are L rows apart, output parts L-1 -- d_out must not overlap d_in (FHE_ERR_INVALID). */
 int fhe_rescale(fhe_ctx *ctx, fhe_keyswitch *p, uint64_t *d_out, const uint64_t *d_in, size_t n_parts, void *stream);
 /* fhe_rescale with the limbs sharded (plans of fhe_keyswitch_create_sharded with a d_bcast buffer): d_in_local = [n_parts][cn][N], the
