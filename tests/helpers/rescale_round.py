@@ -104,12 +104,42 @@ def branch_words(q):
     return [0, 1, h - 1, h, h + 1, q - 1]
 
 
-def branch_positions(N, tile_cols=16):
-    """where they go: the ends of the limb, and the two sides of the first column-tile boundary (16 columns at the two-launch sizes)"""
+# Row length 2^PR of the column pass's 2^PC x 2^PR matrix at the two-launch sizes, and the width of a column tile: data copied from
+# fhe_reliability_gpu_amd/csrc/ntt_plan.hpp (Plan<LOGN>::Row::P = 8, 8, 8, 8, 9 for LOGN 13..17; PlanGeom<LOGN, 1>::TC = 16).  Nothing
+# asserts the plan: the table only says which input word reaches which tile of which row.
+ROW_LEN = {13: 256, 14: 256, 15: 256, 16: 256, 17: 512}
+TILE_COLS = 16
+
+
+def branch_positions(N, tile_cols=16, row_len=None):
+    """where they go: the ends of the limb, and the two sides of the first column-tile boundary (16 columns at the two-launch sizes).
+    With row_len, after those: the first word of row 1 and the two sides of its first tile boundary, then the first word of the last
+    row and the two sides of its last tile boundary (its last word, N - 1, is there already)"""
     pos = [0, 1, N - 1]
     if N > 2 * tile_cols:
         pos += [tile_cols - 1, tile_cols]
+    if row_len is not None:
+        pos += [row_len, row_len + tile_cols - 1, row_len + tile_cols, N - row_len, N - tile_cols - 1, N - tile_cols]
     return pos
+
+
+def position_classes(N, row_len, tile_cols=16):
+    """the positions of branch_positions(N, tile_cols, row_len) by what they probe: a class is the unit over which the parts of a
+    three-part case carry every branch word (first_word)"""
+    return {"row start": [0, row_len, N - row_len],
+            "left of a tile boundary": [tile_cols - 1, row_len + tile_cols - 1, N - tile_cols - 1],
+            "right of a tile boundary": [tile_cols, row_len + tile_cols, N - tile_cols],
+            "row 0": [0, 1, tile_cols - 1, tile_cols],
+            "row 1": [row_len, row_len + tile_cols - 1, row_len + tile_cols],
+            "last row": [N - row_len, N - tile_cols - 1, N - tile_cols, N - 1]}
+
+
+def first_word(k, n_base):
+    """index of the branch word that part 0 puts at position number k (part p: p further on, cyclically).  The n_base positions
+    without row_len count up, as they always did: 0, 1, N-1, 15, 16 start at words 0, 1, 2, 3, 4.  A position that row_len adds starts
+    three words away from its counterpart in row 0 -- row starts at 3 (0 has 0), left sides at 0 (15 has 3), right sides at 1 (16 has
+    4) -- so that over three parts, which give a position three consecutive words, the pair sees all six"""
+    return k if k < n_base else (3, 0, 1)[(k - n_base) % 3]
 
 
 def last_limb(y, q, logn):
@@ -117,28 +147,101 @@ def last_limb(y, q, logn):
     return O.nwt_forward(np.asarray(y, dtype=U), int(q), O.root_powers(int(q), logn))
 
 
-def dictated_parts(qs, L, logn, n_parts, seed, fill=None):
+def dictated_y(q, logn, p, rng, row_len=None):
+    """the coefficient form of part p's last limb: the branch words at the branch positions, random words between"""
+    N = 1 << logn
+    words, pos, n_base = branch_words(q), branch_positions(N, row_len=row_len), len(branch_positions(N))
+    y = rng.integers(0, q, N, dtype=U)
+    for k, at in enumerate(pos):
+        y[at] = words[(p + first_word(k, n_base)) % len(words)]
+    # every word once more, next to each other, past the second tile
+    base = min(N - len(words), 40)
+    if base > pos[n_base - 1] or N <= 32:
+        for k, w in enumerate(words):
+            if base + k not in pos:
+                y[base + k] = w
+    return y
+
+
+def dictated_parts(qs, L, logn, n_parts, seed, fill=None, row_len=None):
     """(n_parts, L, N) NTT-domain parts: random limbs below L-1; the last limb is the transform of a y that carries every branch word
-    at every branch position in turn (part p starts the cycle at word p) and random words between -- or, with fill, y = fill everywhere"""
+    at every branch position in turn (part p starts the cycle at word p) and random words between -- or, with fill, y = fill everywhere.
+    row_len adds the positions in row 1 and in the last row of the column pass's matrix (branch_positions); without it the parts are
+    what they were before the argument existed"""
     qs = [int(q) for q in qs[:L]]
     N, q = 1 << logn, qs[L - 1]
     rng = np.random.default_rng(seed)
     parts = np.zeros((n_parts, L, N), dtype=U)
-    words, pos = branch_words(q), branch_positions(N)
     for p in range(n_parts):
         for j in range(L - 1):
             parts[p, j] = rng.integers(0, qs[j], N, dtype=U)
-        if fill is not None:
-            y = np.full(N, fill, dtype=U)
-        else:
-            y = rng.integers(0, q, N, dtype=U)
-            for k, at in enumerate(pos):
-                y[at] = words[(p + k) % len(words)]
-            # every word once more, next to each other, past the second tile
-            base = min(N - len(words), 40)
-            if base > pos[-1] or N <= 32:
-                for k, w in enumerate(words):
-                    if base + k not in pos:
-                        y[base + k] = w
+        y = np.full(N, fill, dtype=U) if fill is not None else dictated_y(q, logn, p, rng, row_len)
         parts[p, L - 1] = last_limb(y, q, logn)
     return parts
+
+
+# ------------------------------------------------------------------------------------------------ limb layouts, and what every case is held to
+# ciphertext primes, then the size of the special primes.  L = 3: the two remaining limbs are one run of one arithmetic path
+PRIME_SETS = {"50": ([50, 50, 50], 50), "61": ([61, 61, 61], 61), "50+61last": ([50, 50, 61], 50), "61+50last": ([61, 61, 50], 61),
+              "30+61last": ([30, 30, 61], 61)}
+# L = 5, the paths alternating: the four remaining limbs are four runs of one limb each (for_each_run: off = 0 .. 3)
+ALTERNATING = {"50/61/50/61/50": ([50, 61, 50, 61, 50], 61), "61/50/61/50/61": ([61, 50, 61, 50, 61], 50)}
+
+
+def limb_bits(kind, K):
+    """the bit sizes of a named layout's ciphertext primes followed by its K special primes"""
+    bits, sp = (PRIME_SETS.get(kind) or ALTERNATING[kind])
+    return bits + [sp] * K
+
+
+def moduli(F, logn, kind, K):
+    return F.create_moduli(1 << logn, limb_bits(kind, K))
+
+
+def random_parts(qs, L, logn, n_parts, seed):
+    rng = np.random.default_rng(seed)
+    return np.stack([np.stack([rng.integers(0, int(q), 1 << logn, dtype=U) for q in qs[:L]]) for _ in range(n_parts)])
+
+
+def references(parts, qs, L, logn, differs=True, what=""):
+    """(nearest, floor) of one case: statement (a), the oracle's rescale, and the condition that makes the nearest words tell"""
+    near, floor = round_rescale_ref(parts, qs, L, logn, True), KR.rescale_ref(parts, qs, L, logn)
+    if differs:
+        assert_every_tile_differs(near, floor, what)
+    else:
+        assert (near == floor).all(), what
+    return near, floor
+
+
+def assert_every_tile_differs(near, floor, what="", tile_cols=TILE_COLS):
+    """in every 16-column tile of every output limb of every part the nearest words differ from the flooring words somewhere: a tile
+    computed by the flooring form cannot pass a comparison with ``near``"""
+    tiles = (near != floor).reshape(near.shape[:-1] + (-1, tile_cols)).any(axis=-1)
+    assert tiles.all(), f"{what}: nearest equals floor on {int((~tiles).sum())} of {tiles.size} tiles, first (part, limb, tile) {np.argwhere(~tiles)[0].tolist()}"
+
+
+def same(got, want, what):
+    got = got.download().reshape(want.shape)
+    assert (got == want).all(), f"{what}: {int((got != want).sum())} words differ, first at {np.argwhere(got != want)[0].tolist()}"
+
+
+# ------------------------------------------------------------------------------------------------ fhe_hmult
+def hmult_case(F, logn, kind, L, K, dnum, seed):
+    qs = moduli(F, logn, kind, K)
+    N = 1 << logn
+    rng = np.random.default_rng(seed)
+    rnd = lambda qq: np.stack([rng.integers(0, q, N, dtype=U) for q in qq])
+    a0, a1, b0, b1 = (rnd(qs[:L]) for _ in range(4))
+    key = np.stack([np.stack([rnd(qs) for _ in range(2)]) for _ in range(dnum)])
+    return qs, a0, a1, b0, b1, key
+
+
+def hmult_relin_ref(qs, a0, a1, b0, b1, key, L, K, dnum, logn):
+    """the relinearised product before its rescale, (2, L, N)"""
+    d0, d1, d2 = KR.tensor_ref(a0, a1, b0, b1, qs)
+    return np.stack(KR.keyswitch_ref(d2, key, qs, L, K, dnum, logn, add0=d0, add1=d1))
+
+
+def hmult_want(qs, a0, a1, b0, b1, key, L, K, dnum, logn, nearest):
+    r = round_rescale_ref(hmult_relin_ref(qs, a0, a1, b0, b1, key, L, K, dnum, logn), qs, L, logn, nearest)
+    return r[0], r[1]

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from helpers import rescale_round as RR
+from helpers import rescale_round_sizes as RS
 from helpers import rlwe
 
 pytestmark = pytest.mark.gpu
@@ -17,9 +18,7 @@ U = np.uint64
 FHE_ERR_INVALID, FHE_ERR_UNSUPPORTED = 1, 3
 SENTINEL = 0xA5A5A5A5A5A5A5A5
 
-# ciphertext primes (L = 3), then the size of the special primes
-PRIME_SETS = {"50": ([50, 50, 50], 50), "61": ([61, 61, 61], 61), "50+61last": ([50, 50, 61], 50), "61+50last": ([61, 61, 50], 61),
-              "30+61last": ([30, 30, 61], 61)}
+PRIME_SETS = RR.PRIME_SETS
 
 
 @pytest.fixture(scope="module")
@@ -33,14 +32,7 @@ def eng(F):
     return F.default_engine()
 
 
-def _moduli(F, logn, kind, K):
-    bits, sp = PRIME_SETS[kind]
-    return F.create_moduli(1 << logn, bits + [sp] * K)
-
-
-def _same(got, want, what):
-    got = got.download().reshape(want.shape)
-    assert (got == want).all(), f"{what}: {int((got != want).sum())} words differ, first at {np.argwhere(got != want)[0].tolist()}"
+_moduli, _same = RR.moduli, RR.same
 
 
 # ------------------------------------------------------------------------------------------------ fhe_rescale, every route
@@ -71,22 +63,7 @@ def test_rescale_nearest_on_every_route(F, eng, logn, kind):
 
 
 # ------------------------------------------------------------------------------------------------ fhe_hmult, both routes
-def _hmult_case(F, logn, kind, L, K, dnum, seed):
-    qs = _moduli(F, logn, kind, K)
-    N = 1 << logn
-    rng = np.random.default_rng(seed)
-    rnd = lambda qq: np.stack([rng.integers(0, q, N, dtype=U) for q in qq])
-    a0, a1, b0, b1 = (rnd(qs[:L]) for _ in range(4))
-    key = np.stack([np.stack([rnd(qs) for _ in range(2)]) for _ in range(dnum)])
-    return qs, a0, a1, b0, b1, key
-
-
-def _hmult_want(qs, a0, a1, b0, b1, key, L, K, dnum, logn, nearest):
-    from oracle.keyswitch_ref import keyswitch_ref, tensor_ref
-    d0, d1, d2 = tensor_ref(a0, a1, b0, b1, qs)
-    c0, c1 = keyswitch_ref(d2, key, qs, L, K, dnum, logn, add0=d0, add1=d1)
-    r = RR.round_rescale_ref([c0, c1], qs, L, logn, nearest)
-    return r[0], r[1]
+_hmult_case, _hmult_want = RR.hmult_case, RR.hmult_want
 
 
 @pytest.mark.parametrize("kind", list(PRIME_SETS))
@@ -251,135 +228,14 @@ def test_checked_multiply_without_rescale_runs_on_a_rounding_plan(F, eng, refusa
 
 
 # ------------------------------------------------------------------------------------------------ sharded phases
-def _to_cuda(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.int64).copy()).cuda()
-
-
-def _from_cuda(t):
-    return t.cpu().numpy().view(U)
-
-
 def test_one_rank_phase_path_equals_the_single_call(F, eng):
-    import torch
-
-    from fhe_reliability_gpu_amd.dist import ShardedKeySwitch
-    logn, L, K, dnum = 13, 5, 2, 3
-    N = 1 << logn
-    qs = F.create_moduli(N, [50] * (L + K))
-    t = eng.tables(logn, qs)
-    parts = np.stack([RR.dictated_parts(qs, L, logn, 1, seed=40 + i)[0] for i in range(2)])
-    want = RR.round_rescale_ref(parts, qs, L, logn, True)
-    ks = F.KeySwitch(eng, t, L, K, dnum)
-    ks.set_rescale_rounding(True)
-    _same(ks.rescale(eng.upload(parts), 2), want, "single call")
-    sh = ShardedKeySwitch(eng, t, L, K, dnum)
-    sh.set_rescale_rounding(True)
-    assert sh.rescale_rounding is True
-    loc = _to_cuda(parts)
-    torch.cuda.synchronize()
-    with sh.stream_scope():
-        sh.rescale_begin(loc)
-        out = sh.rescale_finish(loc)
-    torch.cuda.synchronize()
-    assert (_from_cuda(out) == want).all()
+    RS.one_rank_phase_path(F, eng, 13, [50] * 7, L=5, K=2, dnum=3)
 
 
 def test_two_ranks_in_one_process(F, eng):
     """both ranks' plans in one process, the host doing the collectives: fhe_rescale_shard_* and the fused multiply's finish, gathered
     limbs against the single-device words (which test_hmult_nearest_on_both_routes holds against the helper)"""
-    import torch
-
-    from fhe_reliability_gpu_amd._lib import check, lib, vp
-    from fhe_reliability_gpu_amd.dist import ks_layout, own_ct_rows, own_rows
-    world, logn, L, K, dnum = 2, 13, 4, 2, 2
-    N = 1 << logn
-    qs = F.create_moduli(N, [50] * (L + K))
-    t = eng.tables(logn, qs)
-    rng = np.random.default_rng(5)
-    rnd = lambda qq: np.stack([rng.integers(0, q, N, dtype=U) for q in qq])
-    a0, a1, b0, b1 = (rnd(qs[:L]) for _ in range(4))
-    key = np.stack([np.stack([rnd(qs) for _ in range(2)]) for _ in range(dnum)])
-    parts = RR.dictated_parts(qs, L, logn, 3, seed=9)
-    P = lambda x: C.c_void_p(x.data_ptr() if x is not None and x.numel() else 0)
-    lays = [ks_layout(L, K, world, r) for r in range(world)]
-    cmax, smax = lays[0]["cmax"], lays[0]["smax"]
-    zeros = lambda rows: torch.zeros((rows, N), dtype=torch.int64, device="cuda")
-    g1, g2, bc = [zeros(world * cmax) for _ in range(world)], [zeros(world * 2 * smax) for _ in range(world)], [zeros(3) for _ in range(world)]
-    plans = []
-    for r in range(world):
-        h = vp()
-        check(lib.fhe_keyswitch_create_sharded(eng._h, t._h, L, K, dnum, world, r, P(g1[r]), P(g2[r]), P(bc[r]), C.byref(h)))
-        check(lib.fhe_keyswitch_set_rescale_rounding(h, 1))
-        plans.append(h)
-    owner = next(r for r, l in enumerate(lays) if l["clo"] <= L - 1 < l["clo"] + l["cn"])
-    rs_rows = [max(0, min(l["clo"] + l["cn"], L - 1) - l["clo"]) for l in lays]
-    empty = lambda *shape: torch.empty(shape, dtype=torch.int64, device="cuda")
-    torch.cuda.synchronize()
-
-    def gather(bufs, rows):
-        torch.cuda.synchronize()
-        for r in range(world):
-            for s in range(world):
-                if r != s:
-                    bufs[r][s * rows:(s + 1) * rows] = bufs[s][s * rows:(s + 1) * rows]
-        torch.cuda.synchronize()
-
-    def bcast(n_rows):
-        torch.cuda.synchronize()
-        for r in range(world):
-            if r != owner:
-                bc[r][:n_rows] = bc[owner][:n_rows]
-        torch.cuda.synchronize()
-
-    try:
-        # ---- the rescale of three parts
-        want = RR.round_rescale_ref(parts, qs, L, logn, True)
-        pl = [_to_cuda(parts[:, own_ct_rows(lays[r])]) for r in range(world)]
-        for r in range(world):
-            check(lib.fhe_rescale_shard_begin(eng._h, plans[r], P(pl[r]), 3, None))
-        bcast(3)
-        outs = []
-        for r in range(world):
-            o = empty(3, rs_rows[r], N)
-            check(lib.fhe_rescale_shard_finish(eng._h, plans[r], P(o), P(pl[r]), 3, None))
-            outs.append(o)
-        eng.sync()
-        assert (np.concatenate([_from_cuda(o) for o in outs], axis=1) == want).all()
-        # ---- the fused multiply's finish
-        assert lib.fhe_hmult_shard_fusable(eng._h, plans[0])
-        ks = F.KeySwitch(eng, t, L, K, dnum)
-        ks.set_rescale_rounding(True)
-        h0, h1 = ks.hmult(*[eng.upload(x) for x in (a0, a1, b0, b1, key)], rescale=True)
-        h0, h1 = h0.download(), h1.download()
-        loc = lambda a, r: _to_cuda(a[own_ct_rows(lays[r])])
-        keyl = [_to_cuda(key[:, :, own_rows(lays[r])]) for r in range(world)]
-        d = []
-        for r in range(world):
-            x = [loc(v, r) for v in (a0, a1, b0, b1)]
-            dd = [torch.empty_like(x[0]) for _ in range(3)]
-            check(lib.fhe_tensor_product(eng._h, P(dd[0]), P(dd[1]), P(dd[2]), P(x[0]), P(x[1]), P(x[2]), P(x[3]), t._h, lays[r]["cn"], lays[r]["clo"], None))
-            d.append(dd)
-        for r in range(world):
-            check(lib.fhe_keyswitch_shard_begin(eng._h, plans[r], P(d[r][2]), None))
-        gather(g1, cmax)
-        for r in range(world):
-            check(lib.fhe_keyswitch_shard_inner(eng._h, plans[r], P(d[r][2]), P(keyl[r]), None))
-        gather(g2, 2 * smax)
-        for r in range(world):
-            check(lib.fhe_hmult_shard_finish_begin(eng._h, plans[r], P(d[r][0]), P(d[r][1]), None))
-        bcast(2)
-        outs = []
-        for r in range(world):
-            o = empty(2, rs_rows[r], N)
-            check(lib.fhe_hmult_shard_finish_end(eng._h, plans[r], P(o[0]), P(o[1]), P(d[r][0]), P(d[r][1]), None))
-            outs.append(o)
-        eng.sync()
-        assert (np.concatenate([_from_cuda(o[0]) for o in outs]) == h0).all()
-        assert (np.concatenate([_from_cuda(o[1]) for o in outs]) == h1).all()
-    finally:
-        for h in plans:
-            lib.fhe_keyswitch_destroy(h)
+    RS.two_ranks_in_one_process(F, eng, 13, [50] * 6, L=4, K=2, dnum=2)
 
 
 # ------------------------------------------------------------------------------------------------ decryption level
